@@ -7,7 +7,7 @@ periodic boxes evaluated with BOTH derivative back-ends on the same inputs -- th
 difference stencil (csrc/residual_kernels.hip) and the Fourier-spectral path (two LDS-resident FFT
 passes, csrc/spectral_kernels.hip).  One residual update = one grid point through both.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -26,12 +26,21 @@ fails or hangs makes the launcher exit non-zero with the ranks' logs on stderr (
 only with `--fallback-batch` does it re-run the ranks in `--mode batch`, and then the line says so in `launcher` and carries the
 batch number under `value` with `scaling: weak`.  Both attempts and the teardown fit 540 s (`--launch-timeout`, default 240 s each).
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the --steps steps and prints rank 0's ONE JSON line with the contract fields (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ...); `roofline` and `cpu_baseline` are null there.  Everything else is measured only
+with `--full`, after the timed steps:
   roofline     -- for the dominant kernel: algorithmic bytes per launch / its average launch time,
                   measured here with HIP events on the launch stream, against the 8 TB/s HBM peak;
   cpu_baseline -- the NumPy oracle (oracle/periodic.py, kind "port") timed on this host on a bounded
                   sample of the same workload: one core (the headline row, "cores": 1) and, as
-                  cpu_baseline.all_cores, one oracle process per usable host core (at most 16).
+                  cpu_baseline.all_cores, one oracle process per usable host core (at most 16);
+  precision.float64_forward_forced, secondary (BASELINE configs 1, 2, 3, 5) and, for N > 1, the multi-GPU extras above.
+
+`--dump-outputs DIR` writes what the timed step returned in its LAST timed step (rank 0's arrays; a slab rank holds its own rows)
+as float32 .npy files, before anything else runs: for each of fd_r_u, fd_r_v, fd_r_div, spec_r_u, spec_r_v, spec_r_div,
+DIR/<name>_grid0.npy (grid 0 whole, when it has at most 2^20 points) and DIR/<name>_sample.npy (a fixed, seeded sample of at
+most 2^20 points of the whole batch, the same points for every field; the whole batch when it is no larger).  At most 48 MB.
+The inputs are seeded (seeds 1234 ...): the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -92,6 +101,30 @@ def make_inputs(batch, n, distinct, seed0, device):
     d = f[0].shape[0]
     reps = (batch + d - 1) // d
     return [torch.as_tensor(np.tile(a, (reps, 1, 1))[:batch] if d < batch else a[:batch], device=device).contiguous() for a in f]
+
+
+DUMP_POINTS = 1 << 20            # --dump-outputs: at most this many points per file (4 MB of float32)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, fd, sp):
+    """--dump-outputs: the six residual fields of the last timed step, [B, nx, ny] device tensors, as float32 .npy files:
+    <name>_grid0.npy (grid 0 whole, if it has at most DUMP_POINTS points) and <name>_sample.npy (DUMP_POINTS points of the whole
+    batch drawn with a fixed seed, sorted, the same for every field; the whole batch when it is no larger)."""
+    os.makedirs(out_dir, exist_ok=True)
+    names = ('fd_r_u', 'fd_r_v', 'fd_r_div', 'spec_r_u', 'spec_r_v', 'spec_r_div')
+    total = fd[0].numel()
+    idx = None
+    if total > DUMP_POINTS:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_POINTS))
+        idx = torch.as_tensor(idx, device=fd[0].device)
+    for name, t in zip(names, list(fd) + list(sp)):
+        t = t.detach().float()
+        if t[0].numel() <= DUMP_POINTS:
+            np.save(os.path.join(out_dir, name + '_grid0.npy'), t[0].cpu().numpy())
+        s = t if idx is None else t.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '_sample.npy'), s.cpu().numpy())
+    log('bench: outputs of the last timed step written to %s' % out_dir)
 
 
 def time_kernel(fn, iters):
@@ -288,6 +321,36 @@ def self_launch(args, argv=None, script=None):
     return failures[-1]['status'] or 1
 
 
+def headline(args, world, slab, prec, value, elapsed, fused, n_in, alt):
+    """The result line's contract fields and their description; `roofline` and `cpu_baseline` are filled in by --full."""
+    n, B = args.n, args.batch
+    return dict(metric='grid-point residual-updates/sec at 1024^2 (FD 5-point + spectral residual on the same inputs)',
+                parity_note='operator defined by oracle/periodic.py (the reference has no periodic residual: SURVEY 8 row a17), pinned analytically; '
+                            'tests hold the kernels to 1e-5 rel-L2 of that float64 oracle',
+                value=value, unit='residual-updates/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
+                ms_per_step=1e3 * elapsed / args.steps, higher_is_better=True, scaling='strong' if slab else 'weak', vs_baseline=None,
+                scaling_note=('the SAME %d grids on all %d GPUs, each grid slab-decomposed by rows (BASELINE config 4): every evaluation sends 24 (P-1)/P B/pt '
+                              'over xGMI (u, v, p out, three partials back) against the 80 B/pt its kernels move in HBM at ~5 TB/s; the links are point-to-point '
+                              '(P = 2: ONE link carries 12 B/pt per direction), so the decomposition is link-bound at every P and slower than one GPU at small P. '
+                              '`batch_split` (same grids, whole grids per rank, strong) and `batch_sharded` (weak) are the no-collective alternatives, measured in '
+                              'the same run' % (B, world)) if slab else None,
+                dtype='f32' if prec < 2 else 'f32 fields; f64 forward FFT + f32 inverse FFT; f32 stencil',
+                precision=dict(precise=prec, note='precise=1: the library takes all-float32 transforms on forward-differenced lines while the viscous '
+                               'amplification nu pi N/(sqrt(3) L) <= 8 (1.86 here), float64 forward transforms otherwise; rel-L2 against the float64 '
+                               'oracle in cpu_baseline.oracle_check', float64_forward_forced=alt),
+                data='synthetic',
+                config=dict(workload='periodic-box NS residual, %dx%d, batch %d grids per GPU, FD %d-point + Fourier spectral%s'
+                                     % (n, n, B, args.stencil, ' (fused row pass: 2 launches)' if fused else
+                                        (' (per rank and batch chunk: pack, all-to-all, column pass, all-to-all, unpack, fused row pass)' if slab else ' (separate launches)')),
+                            grid=[n, n], batch_per_gpu=B, global_batch=B if slab else B * world,
+                            parallelism=('row-slab x%d: the same %d grids on all ranks; halo send/recv + 2 all-to-all transposes per evaluation over %s'
+                                         % (world, B, 'RCCL' if args.backend == 'nccl' else 'gloo (host-staged rehearsal)')) if slab
+                            else 'batch-sharded x%d (no data-path collective)' % world,
+                            inputs=('Taylor-Green t=0.1 + band-limited noise, nu=2pi/1000, dt=1e-3, resident in HBM; %d DISTINCT grids (seeds 1234 ... %d)%s'
+                                    % (n_in, 1233 + n_in, '' if n_in >= B else ' tiled to the batch of %d (timing is data-independent)' % B))),
+                roofline=None, cpu_baseline=None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -316,6 +379,10 @@ def main():
     ap.add_argument('--launch-timeout', type=float, default=240.0, help='self-launcher: seconds before the child ranks of ONE attempt are killed (all attempts + teardown: 540 s)')
     ap.add_argument('--fallback-batch', action='store_true', help='self-launcher: after a failed / hung slab attempt, run the ranks again in --mode batch (off by default: a slab failure exits non-zero)')
     ap.add_argument('--extras-timeout', type=float, default=150.0, help='N > 1: seconds the untimed extras after the headline (phases, chunked pipeline, batch splits) may take before the line is printed without them')
+    ap.add_argument('--full', action='store_true', help='also measure everything beyond the headline (roofline, CPU baselines, the float64-forward '
+                    'step, the secondary configs, the N > 1 extras); off: the run does only what the headline needs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed step to DIR/<name>.npy (float32, a fixed '
+                    'seeded sample of the batch plus grid 0)')
     args = ap.parse_args()
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -334,7 +401,7 @@ def main():
     if world != args.gpus:
         raise SystemExit("WORLD_SIZE=%d does not match --gpus %d" % (world, args.gpus))
     all_cores = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log('bench: timing the NumPy oracle on all host cores (before the GPU is touched) ...')
         try:
             all_cores = cpu_baseline_all_cores(args.n)
@@ -342,10 +409,13 @@ def main():
             log('bench: all-core CPU baseline skipped: %r' % (e,))
     n_distinct = max(1, min(args.distinct, args.batch))
     slab_mode = (args.mode or 'slab') == 'slab' and (world > 1 or args.loopback)
+    seed0 = 1234 + (0 if (slab_mode or world == 1) else 1000 * rank)
     try:
-        pregen_inputs(args.n, n_distinct, 1234 + (0 if (slab_mode or world == 1) else 1000 * rank))          # before the GPU is touched: forked workers
-    except Exception as e:                                     # noqa: BLE001 -- fall back to a few grids generated serially and tiled
-        log('bench: parallel input generation failed (%r): generating %d grids serially' % (e, min(n_distinct, 8)))
+        pregen_inputs(args.n, n_distinct, seed0)          # before the GPU is touched: forked workers
+    except Exception as e:                                     # noqa: BLE001 -- fall back to the same grids generated serially
+        log('bench: parallel input generation failed (%r): generating the %d grids serially' % (e, n_distinct))
+        from nns.synthetic import residual_inputs
+        _HOST_INPUTS[(args.n, seed0)] = list(residual_inputs(n_distinct, args.n, seed0=seed0))
     ndev = torch.cuda.device_count()
     dev_index = local_rank if args.backend == 'nccl' else local_rank % max(ndev, 1)     # gloo rehearsal: ranks may share a GPU
     torch.cuda.set_device(dev_index)
@@ -411,12 +481,25 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if args.backend == 'nccl' else 'cpu')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:             # before anything below reuses the output buffers
+        dump_outputs(args.dump_outputs, *((s_fd, s_sp) if slab else (out_fd, out_sp)))
+
+    pts = float(B) * n * n
+    value = (1 if slab else world) * pts * args.steps / elapsed          # slab: the ranks share ONE batch of grids
+    fused = (not slab) and (not args.separate) and args.stencil == 5
+    if not args.full:
+        if dist is not None:
+            dist.barrier()
+        if rank == 0:
+            print(json.dumps(headline(args, world, slab, prec, value, elapsed, fused, n_in, alt=None)), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # N > 1 extras, measured after the timed region: what RCCL really saw, one un-pipelined evaluation phase by phase, and the
     # embarrassingly parallel alternative (every rank its own --batch grids)
     multi = None
-    pts = float(B) * n * n
-    value = (1 if slab else world) * pts * args.steps / elapsed          # slab: the ranks share ONE batch of grids
     watchdog = None
     if world > 1 or args.loopback:
         # The headline is measured.  What follows (phase timings, the chunked pipeline, the batch splits) are untimed EXTRAS over collectives that
@@ -562,7 +645,6 @@ def main():
     if rank == 0:
         # per-kernel durations, live, for the roofline object (same process, same inputs)
         iters = max(5, args.steps)
-        fused = (not slab) and (not args.separate) and args.stencil == 5
         standalone = {
             'fd_residual': time_kernel(lambda: eng.fd(*f, stencil=args.stencil, out=out_fd), iters),
             'spec_xpass': time_kernel(lambda: ops.spec_residual_xpass(f[0], f[1], f[2], L, rho, nu, prec, out=out_sp), iters),
@@ -638,31 +720,8 @@ def main():
                         step_launches=list(kt),
                         standalone_kernels={k: dict(avg_launch_ms=v, bytes_per_pt=BYTES_PER_PT[k],
                                                     achieved_GBs=BYTES_PER_PT[k] * pts / (v * 1e-3) / 1e9) for k, v in standalone.items()})
-        result = dict(metric='grid-point residual-updates/sec at 1024^2 (FD 5-point + spectral residual on the same inputs)',
-                      parity_note='operator defined by oracle/periodic.py (the reference has no periodic residual: SURVEY 8 row a17), pinned analytically; '
-                                  'tests hold the kernels to 1e-5 rel-L2 of that float64 oracle',
-                      value=value, unit='residual-updates/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
-                      ms_per_step=1e3 * elapsed / args.steps, higher_is_better=True, scaling='strong' if slab else 'weak', vs_baseline=None,
-                      scaling_note=('the SAME %d grids on all %d GPUs, each grid slab-decomposed by rows (BASELINE config 4): every evaluation sends 24 (P-1)/P B/pt '
-                                    'over xGMI (u, v, p out, three partials back) against the 80 B/pt its kernels move in HBM at ~5 TB/s; the links are point-to-point '
-                                    '(P = 2: ONE link carries 12 B/pt per direction), so the decomposition is link-bound at every P and slower than one GPU at small P. '
-                                    '`batch_split` (same grids, whole grids per rank, strong) and `batch_sharded` (weak) are the no-collective alternatives, measured in '
-                                    'the same run' % (B, world)) if slab else None,
-                      dtype='f32' if prec < 2 else 'f32 fields; f64 forward FFT + f32 inverse FFT; f32 stencil',
-                      precision=dict(precise=prec, note='precise=1: the library takes all-float32 transforms on forward-differenced lines while the viscous '
-                                     'amplification nu pi N/(sqrt(3) L) <= 8 (1.86 here), float64 forward transforms otherwise; rel-L2 against the float64 '
-                                     'oracle in cpu_baseline.oracle_check', float64_forward_forced=alt),
-                      data='synthetic',
-                      config=dict(workload='periodic-box NS residual, %dx%d, batch %d grids per GPU, FD %d-point + Fourier spectral%s'
-                                           % (n, n, B, args.stencil, ' (fused row pass: 2 launches)' if fused else
-                                              (' (per rank and batch chunk: pack, all-to-all, column pass, all-to-all, unpack, fused row pass)' if slab else ' (separate launches)')),
-                                  grid=[n, n], batch_per_gpu=B, global_batch=B if slab else B * world,
-                                  parallelism=('row-slab x%d: the same %d grids on all ranks; halo send/recv + 2 all-to-all transposes per evaluation over %s'
-                                               % (world, B, 'RCCL' if args.backend == 'nccl' else 'gloo (host-staged rehearsal)')) if slab
-                                  else 'batch-sharded x%d (no data-path collective)' % world,
-                                  inputs=('Taylor-Green t=0.1 + band-limited noise, nu=2pi/1000, dt=1e-3, resident in HBM; %d DISTINCT grids (seeds 1234 ... %d)%s'
-                                          % (n_in, 1233 + n_in, '' if n_in >= B else ' tiled to the batch of %d (timing is data-independent)' % B))),
-                      roofline=roofline)
+        result = headline(args, world, slab, prec, value, elapsed, fused, n_in, alt)
+        result['roofline'] = roofline
         if multi is not None:
             result.update(multi)
     if dist is not None:

@@ -26,7 +26,10 @@ def test_error_paths_under_address_and_ub_sanitizer():
     b = subprocess.run(['make', '-C', CSRC, '-j', '8', 'asan'], capture_output=True, text=True)
     assert b.returncode == 0, b.stdout[-2000:] + b.stderr[-2000:]
     lib = os.path.join(CSRC, 'libnns_hip_asan.so')
-    env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS='detect_leaks=0:abort_on_error=1:halt_on_error=1', UBSAN_OPTIONS='halt_on_error=1:print_stacktrace=1')
+    # host code only: every GPU is hidden from the runtime, so that on a machine with one the walk's device query (nns_device_info)
+    # answers "no device" instead of initialising the GPU under ASan
+    env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS='detect_leaks=0:abort_on_error=1:halt_on_error=1', UBSAN_OPTIONS='halt_on_error=1:print_stacktrace=1',
+               ROCR_VISIBLE_DEVICES='-1', HIP_VISIBLE_DEVICES='-1')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'capi_error_walk.py'), lib], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout[-1500:] + '\n' + r.stderr[-3000:])
     assert 'walked' in r.stdout and 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr
