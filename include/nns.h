@@ -155,6 +155,24 @@ int nns_fd_sor_redblack_f32(float* p, const float* C, float* info, void* work, i
 int nns_fd_sor_redblack_f64(double* p, const double* C, double* info, void* work, int batch, int nx, int ny,
                             double dx, double dy, double beta, double tol, int max_sweeps, void* stream);
 
+/* Multigrid solve of the same pressure equation (an option of the build; src/chorin_fd/simulate.py:186-196 is the equation, not the method):
+ * on interior points  dy^2 (p[i+1,j] + p[i-1,j] - 2p) + dx^2 (p[i,j+1] + p[i,j-1] - 2p) = C[i,j]  -- the fixed point of the reference's SOR
+ * update -- with p's boundary ring as Dirichlet data, read and never written.  C as for nns_fd_sor (nns_fd_pressure_rhs, the reference's dx2dy2C).
+ * V(2,2) cycles: red-black Gauss-Seidel smoothing, per-axis coarsening n -> (n - 1) / 2 + 1 by node coordinate (any n >= 5), linear
+ * prolongation, restriction = scaled transpose, exact coarsest solve; restatement: tests/mg_oracle.py.  Each grid of the batch stops on its own,
+ * on the device, after the cycle in which max|r_k| <= tol max|r_0| or max|r_k| >= 0.9 max|r_(k-1)| (the rounding floor); a grid with
+ * max|r_0| = 0 runs no cycle and keeps p bitwise.  info[b] = (cycles done, max|r_k| / max|r_0|) in p's type ((0, 0) for a zero residual).
+ * cycles: at most this many cycles are enqueued by this call, no host synchronisation.  resume = 0 starts a solve (measures max|r_0|);
+ * resume = 1 continues the solve whose state `work` holds from an earlier call on the same p, C, info.  The first batch int32 of `work` are
+ * the grids' active flags (1 = not stopped), readable by the caller between calls.
+ * work: nns_fd_poisson_mg_workspace bytes, written to *bytes.  NNS_ERR_UNSUPPORTED: a grid axis < 5 nodes, a level's cell aspect ratio > 2,
+ * a coarsest level of more than 33 nodes on an axis, batch > 65535. */
+int nns_fd_poisson_mg_workspace(int batch, int nx, int ny, int elem_size, size_t* bytes);
+int nns_fd_poisson_mg_f32(float* p, const float* C, float* info, void* work, int batch, int nx, int ny,
+                          double dx, double dy, double tol, int cycles, int resume, void* stream);
+int nns_fd_poisson_mg_f64(double* p, const double* C, double* info, void* work, int batch, int nx, int ny,
+                          double dx, double dy, double tol, int cycles, int resume, void* stream);
+
 /* One red-black HALF-sweep on a row slab p[nxl][ny] whose rows 0 and nxl-1 are halo / boundary rows (not written);
  * local row i is global row gi0 + i (that fixes the colours).  Multi-workgroup.  *err_bits (4 bytes for f32, 8 for f64,
  * zeroed by the caller) receives max|p_new - p_old| as an IEEE bit pattern via an unsigned atomic max.  Building block

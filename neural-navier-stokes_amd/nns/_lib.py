@@ -41,6 +41,7 @@ _DUAL = {
     'nns_fd_sor': [_P] * 4 + [_I] * 3 + [_D] * 4 + [_I, _P],
     'nns_fd_sor_hint': [_P] * 5 + [_I] * 3 + [_D] * 4 + [_I, _P],
     'nns_fd_sor_redblack': [_P] * 4 + [_I] * 3 + [_D] * 4 + [_I, _P],
+    'nns_fd_poisson_mg': [_P] * 4 + [_I] * 3 + [_D] * 3 + [_I, _I, _P],
     'nns_fd_sor_redblack_halfsweep': [_P] * 3 + [_I] * 4 + [_D] * 3 + [_P],
     'nns_fd_correction': [_P] * 5 + [_I] * 3 + [_D] * 3 + [_P],
     'nns_fd_step_explicit': [_P] * 5 + [_BCP] * 3 + [_P] * 6 + [_I] * 3 + [_D] * 7 + [_I, _I, _P],
@@ -100,6 +101,7 @@ _SINGLE = {
     'nns_fd_predictor_adi_workspace': [_I, _I, _I, _I],
     'nns_fd_sor_workspace': [_I, _I, _I, _I],
     'nns_fd_sor_redblack_workspace': [_I, _I, _I, _I, _I],
+    'nns_fd_poisson_mg_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
     'nns_device_info': [C.c_char_p, _I, C.POINTER(_I), C.POINTER(_SZ)],
     'nns_version': [],
     'nns_last_error': [],

@@ -28,7 +28,7 @@ class NavierStokesSystem():
     def __init__(self, u_ic, v_ic, p_ic, u_bc, v_bc, p_bc,
                  nt=200, nit=50, nx=50, ny=50, dt=0.001,
                  rho=1, nu=1, beta=1.25, method='semi_implicit', dtype=np.float64, device=None,
-                 advection='reference', pressure_solver='sor'):
+                 advection='reference', pressure_solver='sor', mg_tol=1e-6, mg_max_cycles=30):
         self.u_ic, self.v_ic, self.p_ic = u_ic, v_ic, p_ic
         self.u_bc, self.v_bc, self.p_bc = u_bc, v_bc, p_bc
         self.nt, self.nit, self.dt, self.nx, self.ny = nt, nit, dt, nx, ny
@@ -40,15 +40,18 @@ class NavierStokesSystem():
         #   advection='corrected'      : explicit: v d/dy along y (the reference differences along x twice);
         #                                semi_implicit: second ADI solve along axis 1 (the reference solves along axis 0 twice)
         #   pressure_solver='redblack' : red-black SOR (parallel half-sweeps) instead of the lexicographic order
-        assert advection in ['reference', 'corrected'] and pressure_solver in ['sor', 'redblack']
+        #   pressure_solver='multigrid': V(2,2) multigrid cycles on the same equation until max|r| <= mg_tol max|r_0| (or the rounding floor,
+        #                                or mg_max_cycles); nit and beta do not apply to it
+        assert advection in ['reference', 'corrected'] and pressure_solver in ['sor', 'redblack', 'multigrid']
         # (for method='semi_implicit', advection='corrected' selects the true y-direction second ADI solve)
         self.advection, self.pressure_solver = advection, pressure_solver
+        self.mg_tol, self.mg_max_cycles = mg_tol, mg_max_cycles
         self.dtype = np.dtype(dtype)
         self.device = device if device is not None else default_device()
         self._u_bcl = ops.make_bc_list(u_bc) if u_bc is not None else None
         self._v_bcl = ops.make_bc_list(v_bc) if v_bc is not None else None
         self._p_bcl = ops.make_bc_list(p_bc) if p_bc is not None else None
-        self.last_sor_info = None      # device tensor [B, 2]: (sweeps, err) of the last pressure solve
+        self.last_sor_info = None      # device tensor [B, 2]: (sweeps, err) of the last pressure solve; multigrid: (cycles, max|r| / max|r_0|)
 
     # ------------------------------------------------------------------ device-level operators
     def _d(self, x):
@@ -65,6 +68,9 @@ class NavierStokesSystem():
 
     def _pressure_dev_(self, ui, vi, p):
         C = ops.fd_pressure_rhs(ui, vi, self.dt, self.dx, self.dy, self.rho)
+        if self.pressure_solver == 'multigrid':
+            self.last_sor_info = ops.fd_poisson_mg_(p, C, self.dx, self.dy, tol=self.mg_tol, max_cycles=self.mg_max_cycles, hint=self._hint_for(p))
+            return p
         solve = ops.fd_sor_redblack_ if self.pressure_solver == 'redblack' else ops.fd_sor_
         kw = {} if self.pressure_solver == 'redblack' else dict(hint=self._hint_for(p))       # the previous solve's sweep count sizes the first batch
         self.last_sor_info = solve(p, C, self.dx, self.dy, self.beta, SOR_TOL, max(int(self.nit) - 1, 0), **kw)
@@ -135,7 +141,7 @@ class NavierStokesSystem():
         return like_input(u, ui), like_input(v, ui)
 
     def sor_info(self):
-        """(sweeps, last err) of the most recent pressure solve (host sync), per grid."""
+        """(sweeps, last err) of the most recent pressure solve (host sync), per grid; (cycles, residual ratio) for multigrid."""
         info = self.last_sor_info.cpu().numpy()
         return [(int(r[0]), float(r[1])) for r in info]
 
@@ -164,6 +170,8 @@ class NavierStokesSystem():
         (static state buffers) and replays it; results are bitwise identical.  It is OFF by default: measured on
         MI355X at 64^2, nit = 50 the step is bound by the SOR kernel (~600 barrier-separated pipeline steps, 0.25 ms),
         not by launch overhead -- replay 0.287 ms/step vs eager 0.270 ms/step."""
+        if use_graph and self.pressure_solver == 'multigrid':
+            raise ValueError("simulate_device: use_graph=True is not available with pressure_solver='multigrid' (its cycle count is read on the host)")
         u, v, p = self._init_variables()
         u1, v1 = u.clone(), v.clone()
         us = torch.empty((self.nt,) + tuple(u.shape), dtype=u.dtype, device=u.device)

@@ -157,6 +157,44 @@ def fd_sor_redblack_(p, C, dx, dy, beta, tol, max_sweeps):
     return info
 
 
+MG_FIRST_CHUNK = 4        # cycles enqueued before the first status read when no hint is given
+MG_CHUNK = 2              # cycles per later chunk (the f64 solves of a time loop need 5-7 cycles at tol 1e-6)
+
+
+def fd_poisson_mg_workspace(B, nx, ny, elem_size):
+    import ctypes
+    n = ctypes.c_size_t(0)
+    check(_lib.lib().nns_fd_poisson_mg_workspace(int(B), int(nx), int(ny), int(elem_size), ctypes.byref(n)), 'nns_fd_poisson_mg_workspace')
+    return n.value
+
+
+def fd_poisson_mg_(p, C, dx, dy, tol=1e-6, max_cycles=30, hint=None):
+    """Multigrid solve of the pressure equation (nns_fd_poisson_mg_*), in place on p.  Returns the device info tensor [batch, 2] = (cycles done,
+    max|r_k| / max|r_0|), the layout of fd_sor_'s.  Cycles are enqueued in chunks; after each chunk ONE host sync reads the grids' active flags,
+    and the solve goes on while any grid is active (each grid stops on its own, on the device) and fewer than max_cycles have run.  hint: the
+    info of the previous solve of the same grids (a time loop) sizes the first chunk; the result does not depend on it."""
+    suf, (B, nx, ny) = _chk(p, C)
+    max_cycles = int(max_cycles)
+    if max_cycles < 0:
+        raise ValueError("fd_poisson_mg_: max_cycles must be >= 0")
+    info = torch.empty(B, 2, dtype=p.dtype, device=p.device)
+    nbytes = fd_poisson_mg_workspace(B, nx, ny, p.element_size())
+    work = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    first = MG_FIRST_CHUNK
+    if hint is not None:
+        _sor_hint(hint, B, p)
+        first = max(1, int(hint[:, 0].max().item()))
+    done, chunk, resume = 0, min(first, max_cycles), 0
+    active = work[:4 * B].view(torch.int32)
+    while True:
+        _call('nns_fd_poisson_mg', suf, _p(p), _p(C), _p(info), _p(work), B, nx, ny, float(dx), float(dy), float(tol), chunk, resume, _stream())
+        done += chunk
+        resume = 1
+        if done >= max_cycles or not bool(active.any().item()):
+            return info
+        chunk = min(MG_CHUNK, max_cycles - done)
+
+
 def fd_sor_redblack_halfsweep_(p, C, err, gi0, colour, dx, dy, beta):
     """One red-black half-sweep in place on a row slab p [nxl, ny] (rows 0 and nxl-1 = halo / boundary rows).
     err: a zeroed one-element tensor of p's dtype; afterwards err.max-accumulates max|p_new - p_old| (bit pattern)."""
