@@ -398,6 +398,27 @@ int nns_spec_derivs_f32(const float* f, float* f_x, float* f_y, float* f_lap, in
 int nns_spec_rfft2_f32(const float* f, float* spec, int batch, int nx, int ny, void* stream);
 int nns_spec_irfft2_f32(float* spec, float* f, int batch, int nx, int ny, void* stream);
 
+/* ---- pseudo-spectral Navier-Stokes solver on the periodic box [0, Lx) x [0, Ly) (csrc/pspec_kernels.hip; restatement: tests/pspec_oracle.py) --
+ * Vorticity-streamfunction form, float32, fields [batch][nx][ny] (axis 0 = x), nx and ny each a power of two in [64, 1024].
+ * kx = 2 pi m_x / Lx, ky = 2 pi m_y / Ly (m = the fftfreq index); 2/3-rule mask M = 1 where 3|m_x| < nx and 3|m_y| < ny.
+ * State: what = the vorticity spectrum w^ (numpy.fft.rfft2 convention, M w^ = w^, w^(0,0) = 0), COMPACTED to the kept y-wavenumbers
+ * j < my1 = (ny - 1) / 3 + 1 and transposed: interleaved complex64 [batch][my1][nx], element [b][j][i] = w^[b][i][j] (i in fftfreq order);
+ * mean = the conserved mean velocity (U0, V0), float32 [batch][2].  u = U0 + irfft2(i ky psi^), v = V0 - irfft2(i kx psi^), psi^ = w^ / |k|^2.
+ * work: nns_spec_ns_workspace bytes (one workspace serves all three calls; none of them keeps data in it between calls).
+ * Errors: NNS_ERR_INVALID_ARG for a NULL pointer, batch < 1, non-positive or non-finite Lx, Ly, dt, negative nu, nsteps < 0;
+ * NNS_ERR_UNSUPPORTED for an axis that is not a power of two in [64, 1024]; NNS_ERR_WORKSPACE for work_bytes below the size query. */
+int nns_spec_ns_workspace(int batch, int nx, int ny, size_t* bytes);
+/* what = M (i kx v^ - i ky u^), mean = grid means of u, v: projects (u, v) onto divergence-free, band-limited fields. */
+int nns_spec_ns_init_f32(const float* u, const float* v, float* what, float* mean, void* work, size_t work_bytes, int batch, int nx, int ny,
+                         double Lx, double Ly, void* stream);
+/* nsteps steps (0: nothing) of integrating-factor (Lawson) RK4, L = -nu |k|^2, on what in place; N(w^) = -M rfft2(u w_x + v w_y).
+ * 8 launches per step plus one per call, no allocation and no host synchronisation (capturable in a HIP graph). */
+int nns_spec_ns_step_f32(float* what, const float* mean, void* work, size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly,
+                         double dt, double nu, int nsteps, void* stream);
+/* u, v [batch][nx][ny] as above and p = irfft2(-M rfft2(2 rho (u_x v_y - u_y v_x)) / |k|^2), p^(0,0) = 0 (derivatives from psi^). */
+int nns_spec_ns_fields_f32(const float* what, const float* mean, float* u, float* v, float* p, void* work, size_t work_bytes, int batch,
+                           int nx, int ny, double Lx, double Ly, double rho, void* stream);
+
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */
 /* ODEFunc (spectral_ode.py:14-34: Linear(K,hidden)-ReLU-Linear(hidden,hidden)-ELU-Linear(hidden,K), torch

@@ -1,0 +1,488 @@
+// Pseudo-spectral 2-D Navier-Stokes on the periodic box [0, Lx) x [0, Ly), vorticity-streamfunction form, gfx950
+// (include/nns.h: nns_spec_ns_*; restatement: tests/pspec_oracle.py).
+//
+// State: the vorticity spectrum w^ (numpy.fft.rfft2 convention, unnormalised) of every grid, kept COMPACTED and TRANSPOSED:
+// only the kept y-wavenumbers j < my1 = (ny - 1) / 3 + 1 (the 2/3 rule, 3 j < ny) are stored, as complex lines along x,
+// W[b][j][i] (i = x-wavenumber index, fftfreq order), plus the conserved mean velocity (U0, V0) per grid.
+//
+// Time step: integrating-factor (Lawson) RK4 with L = -nu |k|^2; each of the four stages is TWO launches:
+//   ps_row_kernel<ny>   one line per grid row i (B nx lines): the c2r of (u, v, w_x, w_y) along y from their kept
+//                       y-wavenumbers (two complex inverse transforms, u + i v and w_x + i w_y: Hermitian packing), the
+//                       product u w_x + v w_y in registers, its r2c, and the kept part j < my1 written to Ph[b][i][j].
+//   ps_col_kernel<nx,S> one line per kept column (b, j) (B my1 lines): Ph's column through an LDS transpose, the forward
+//                       transform along x, N^ = -M P^, the Lawson update of stage S of W and the accumulator A (lane-owned,
+//                       coalesced), then the next stage's four spectra i ky psi^, -i kx psi^, i kx w^, i ky w^ (scaled by
+//                       1 / (nx ny), the means put in the (0, 0) mode) inverse-transformed along x and written, through the same
+//                       LDS transpose, to G[f][b][i][j].
+// Stage 4 of step n also prepares stage 1 of step n + 1 (w^ is the next stage input); a call starts with one column launch
+// (S = 0) that only prepares.  Nothing but the kept third of the spectral columns is ever read, transformed or written.
+// Decay factors are applied as z + expm1(x) z: the float32 rounding of E itself would be a systematic per-step error.
+//
+// Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
+#include "nns_common.h"
+#include "fft_lds.h"
+#include <type_traits>
+#include <cmath>
+
+using namespace nns;
+
+namespace {
+
+constexpr int kT = 256;                    // threads per workgroup (4 waves): more workgroups for the B my1 column lines
+constexpr int kW = kT / kWave;
+constexpr long kGridCap = 2048;
+
+template <int N>
+struct PsLds {
+    static constexpr int TPF = N / 16, FPW = kWave / TPF, LINES = kW * FPW;
+    static constexpr int XB_BYTES = (N + N / 16) * 8;                             // exchange image
+    static constexpr int STAGE_BYTES = (N + 16) * 8 + 128;                        // one staged complex line + skew
+    static constexpr int LINE_BYTES = ((XB_BYTES > STAGE_BYTES ? XB_BYTES : STAGE_BYTES) + 127) / 128 * 128;
+    static constexpr int TAB_BYTES = (N / 2 + Pass2<N>::ENTRIES) * 8;
+    static constexpr int TOTAL = TAB_BYTES + LINES * LINE_BYTES;
+    static constexpr int SKEW_MOD = LINES < 32 ? LINES : 32, SKEW_DW = 32 / SKEW_MOD;
+};
+
+struct PsArgs {
+    long nlines;          // row kernel: B nx rows; column kernel: B my1 columns
+    long fstride;         // complex elements between the four fields of G (= B nx my1)
+    int my1;              // kept y-wavenumbers
+    float kx1, ky1;       // 2 pi / Lx, 2 pi / Ly
+    float hnudt;          // -nu dt / 2
+    float dt;
+    float inv_n;          // 1 / (nx ny)
+};
+
+using cf = C2<float>;
+__device__ __forceinline__ cf scal(float em, cf z) { return {fmaf(em, z.x, z.x), fmaf(em, z.y, z.y)}; }     // (1 + em) z
+__device__ __forceinline__ cf axpy(float a, cf x, cf y) { return {fmaf(a, x.x, y.x), fmaf(a, x.y, y.y)}; }   // a x + y
+__device__ __forceinline__ cf imul(float a, cf z) { return {-a * z.y, a * z.x}; }                            // i a z
+
+template <int N>
+__device__ __forceinline__ cf* ps_tables(unsigned char* smem) {
+    cf* tab = reinterpret_cast<cf*>(smem);
+    fill_twiddles<float, N>(tab, threadIdx.x, kT);
+    fill_twiddles2<float, N>(tab + N / 2, threadIdx.x, kT);
+    __syncthreads();
+    return tab;
+}
+
+// ---------------------------------------------------------------------------------------------------- row pass (axis y)
+template <int N>
+__global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a) {
+    using L = PsLds<N>;
+    constexpr int TPF = L::TPF;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const cf* tab = ps_tables<N>(smem);
+    unsigned char* lines = smem + L::TAB_BYTES;
+    const int my1 = a.my1;
+    const long niter = (a.nlines + L::LINES - 1) / L::LINES;
+    for (long it = blockIdx.x; it < niter; it += gridDim.x) {
+        int tx = threadIdx.x;
+        asm volatile("" : "+v"(tx));
+        const int wave = tx / kWave, lane = tx % kWave, sub = lane / TPF, tid = lane % TPF;
+        const int line = wave * L::FPW + sub;
+        cf* xb = reinterpret_cast<cf*>(lines + (size_t)line * L::LINE_BYTES);
+        const long row_raw = it * L::LINES + line;
+        const bool valid = row_raw < a.nlines;
+        const long row = valid ? row_raw : a.nlines - 1;
+        const float2* g0 = G + (size_t)row * my1;
+        // Hermitian fill of two half spectra A, B into Z = A + i B (ifft(Z) = irfft(A) + i irfft(B)); j = 0 takes the real parts
+        auto load2 = [&](const float2* ga, const float2* gb, cf (&z)[16]) {
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const int e = tid + TPF * m;
+                z[m] = {0.f, 0.f};
+                if (m < 8) {
+                    if (e < my1) {
+                        const float2 p = ga[e], q = gb[e];
+                        z[m] = e == 0 ? cf{p.x, q.x} : cf{p.x - q.y, p.y + q.x};
+                    }
+                } else {
+                    const int r = N - e;
+                    if (r < my1) {
+                        const float2 p = ga[r], q = gb[r];
+                        z[m] = {p.x + q.y, q.x - p.y};
+                    }
+                }
+            }
+        };
+        cf zu[16], zw[16];
+        load2(g0, g0 + a.fstride, zu);                       // u + i v
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
+        __builtin_amdgcn_sched_barrier(0);
+        load2(g0 + 2 * a.fstride, g0 + 3 * a.fstride, zw);   // w_x + i w_y
+        fft_line<float, N, true>(zw, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zu[m] = {zu[m].x * zw[m].x + zu[m].y * zw[m].y, 0.f};    // u w_x + v w_y
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
+        if (valid) {
+            float2* o = Ph + (size_t)row * my1;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int e = tid + TPF * m;
+                if (e < my1) o[e] = make_float2(zu[m].x, zu[m].y);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- column pass (axis x)
+// S = 0: prepare stage 1 from W; S = 1..4: consume the RK stage's N (from Ph) and update W / A, then (S < 4 or emit) prepare the next stage.
+template <int N, int S>
+__global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, float2* __restrict__ W,
+                                                    float2* __restrict__ A, const float* __restrict__ mean, PsArgs a, int emit) {
+    using L = PsLds<N>;
+    constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const cf* tab = ps_tables<N>(smem);
+    unsigned char* lines = smem + L::TAB_BYTES;
+    const int my1 = a.my1;
+    const long ntiles = (a.nlines + CW - 1) / CW;
+    const float dt = a.dt, dt2 = 0.5f * dt, dt3 = dt / 3.f, dt6 = dt / 6.f;
+    for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        int tx = threadIdx.x;
+        asm volatile("" : "+v"(tx));
+        const int wave = tx / kWave, lane = tx % kWave, sub = lane / TPF, tid = lane % TPF;
+        const int line = wave * L::FPW + sub;
+        cf* xb = reinterpret_cast<cf*>(lines + (size_t)line * L::LINE_BYTES);
+        float* mine = reinterpret_cast<float*>(xb) + (line % L::SKEW_MOD) * L::SKEW_DW;
+        // staging role: thread (cc, cr) moves rows cr, cr + RPI, ... of tile column cc
+        const int cc = tx % CW, cr = tx / CW;
+        float* cp = reinterpret_cast<float*>(lines + (size_t)cc * L::LINE_BYTES) + (cc % L::SKEW_MOD) * L::SKEW_DW;
+        const long scol = t * CW + cc;
+        const bool sok = scol < a.nlines;
+        const size_t sbase = sok ? (size_t)(scol / my1) * N * my1 + (size_t)(scol % my1) : 0;     // (b, i = 0, j) in [b][i][j]
+        // transform role: this line is column lcol = (b, j)
+        const long lcol = t * CW + line;
+        const bool lok = lcol < a.nlines;
+        const int lb = lok ? (int)(lcol / my1) : 0, lj = lok ? (int)(lcol % my1) : 0;
+        const size_t wbase = (size_t)(lok ? lcol : 0) * N;
+        int tv = tid;
+        asm volatile("" : "+v"(tv));
+        const float ky = a.ky1 * (float)lj;
+        cf y[16];
+        if constexpr (S == 0) {
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const float2 w = lok ? W[wbase + tv + TPF * m] : make_float2(0.f, 0.f);
+                y[m] = {w.x, w.y};
+            }
+        } else {
+            for (int r = cr; r < N; r += RPI) {
+                const float2 v = sok ? Ph[sbase + (size_t)r * my1] : make_float2(0.f, 0.f);
+                cp[2 * r] = v.x; cp[2 * r + 1] = v.y;
+            }
+            __syncthreads();
+            cf z[16];
+#pragma unroll
+            for (int m = 0; m < 16; ++m) z[m] = {mine[2 * (tv + TPF * m)], mine[2 * (tv + TPF * m) + 1]};
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            fft_line<float, N, false>(z, tab, tab + N / 2, xb, tv);
+            int te = tv;
+            asm volatile("" : "+v"(te), "+v"(z[0].x));
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const int e = te + TPF * m;
+                const int mx = m < 8 ? e : e - N;
+                const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (mx | lj) != 0;    // 2/3 rule in x (y: j < my1), no (0, 0)
+                const float kx = a.kx1 * (float)mx;
+                const float x = a.hnudt * (kx * kx + ky * ky);                     // L dt / 2
+                const float em1 = expm1f(x), em2 = expm1f(2.f * x);                // E - 1, E^2 - 1
+                const cf n = keep ? cf{-z[m].x, -z[m].y} : cf{0.f, 0.f};
+                const size_t si = wbase + e;
+                if constexpr (S == 1) {                 // a: A = E^2 (w + dt/6 a), next = E (w + dt/2 a)
+                    const float2 w2 = lok ? W[si] : make_float2(0.f, 0.f);
+                    const cf w = keep ? cf{w2.x, w2.y} : cf{0.f, 0.f};
+                    const cf acc = scal(em2, axpy(dt6, n, w));
+                    if (lok) A[si] = make_float2(acc.x, acc.y);
+                    y[m] = scal(em1, axpy(dt2, n, w));
+                } else if constexpr (S == 2) {          // b: A += dt/3 E b, next = E w + dt/2 b
+                    const float2 w2 = lok ? W[si] : make_float2(0.f, 0.f), a2 = lok ? A[si] : make_float2(0.f, 0.f);
+                    const cf w = keep ? cf{w2.x, w2.y} : cf{0.f, 0.f};
+                    const cf acc = axpy(dt3, scal(em1, n), cf{a2.x, a2.y});
+                    if (lok) A[si] = make_float2(acc.x, acc.y);
+                    y[m] = axpy(dt2, n, scal(em1, w));
+                } else if constexpr (S == 3) {          // c: A += dt/3 E c, next = E^2 w + dt E c
+                    const float2 w2 = lok ? W[si] : make_float2(0.f, 0.f), a2 = lok ? A[si] : make_float2(0.f, 0.f);
+                    const cf w = keep ? cf{w2.x, w2.y} : cf{0.f, 0.f};
+                    const cf ec = scal(em1, n);
+                    const cf acc = axpy(dt3, ec, cf{a2.x, a2.y});
+                    if (lok) A[si] = make_float2(acc.x, acc.y);
+                    y[m] = axpy(dt, ec, scal(em2, w));
+                } else {                                // d: w = A + dt/6 d
+                    const float2 a2 = lok ? A[si] : make_float2(0.f, 0.f);
+                    const cf acc = keep ? cf{a2.x, a2.y} : cf{0.f, 0.f};
+                    const cf w = axpy(dt6, n, acc);
+                    if (lok) W[si] = make_float2(w.x, w.y);
+                    y[m] = w;
+                }
+            }
+        }
+        if (S < 4 || emit) {
+            const float U0 = lok ? mean[2 * lb] : 0.f, V0 = lok ? mean[2 * lb + 1] : 0.f;
+            auto field = [&](auto fc) {
+                constexpr int F = decltype(fc)::value;
+                int te = tv;
+                asm volatile("" : "+v"(te), "+v"(y[0].x));
+                cf o[16];
+#pragma unroll
+                for (int m = 0; m < 16; ++m) {
+                    const int e = te + TPF * m;
+                    const int mx = m < 8 ? e : e - N;
+                    const float kx = a.kx1 * (float)mx;
+                    const float k2 = kx * kx + ky * ky;
+                    const float ik2 = k2 > 0.f ? a.inv_n / k2 : 0.f;
+                    if constexpr (F == 0) o[m] = imul(ky * ik2, y[m]);                 // u^ = i ky psi^
+                    else if constexpr (F == 1) o[m] = imul(-kx * ik2, y[m]);           // v^ = -i kx psi^
+                    else if constexpr (F == 2) o[m] = imul(kx * a.inv_n, y[m]);        // (w_x)^
+                    else o[m] = imul(ky * a.inv_n, y[m]);                              // (w_y)^
+                }
+                if constexpr (F < 2) {
+                    if (te == 0 && lj == 0) o[0] = {F == 0 ? U0 : V0, 0.f};           // the mean flow in the (0, 0) mode
+                }
+                fft_line<float, N, true>(o, tab, tab + N / 2, xb, tv);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int m = 0; m < 16; ++m) { mine[2 * (tv + TPF * m)] = o[m].x; mine[2 * (tv + TPF * m) + 1] = o[m].y; }
+                __syncthreads();
+                if (sok) {
+                    float2* g = G + (size_t)F * a.fstride + sbase;
+                    for (int r = cr; r < N; r += RPI) g[(size_t)r * my1] = make_float2(cp[2 * r], cp[2 * r + 1]);
+                }
+                __syncthreads();
+            };
+            static_for<0, 4>(field);
+        } else {
+            __syncthreads();                            // the next tile's staging overwrites line images other waves may still read
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- init / output (pointwise)
+// W[b][j][i] = M (i kx v^ - i ky u^)   from rfft2 spectra uh, vh [B][nx][nh]; mean[b] = (u^(0,0), v^(0,0)) / (nx ny)
+__global__ void ps_init_kernel(const float2* __restrict__ uh, const float2* __restrict__ vh, float2* __restrict__ W, float* __restrict__ mean,
+                               int batch, int nx, int ny, int my1, float kx1, float ky1, float inv_n) {
+    const long total = (long)batch * my1 * nx, nh = ny / 2 + 1;
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+        const int i = (int)(q % nx), j = (int)((q / nx) % my1);
+        const long b = q / ((long)nx * my1);
+        const int mx = i < nx / 2 ? i : i - nx;
+        const size_t s = ((size_t)b * nx + i) * nh + j;
+        const float2 u = uh[s], v = vh[s];
+        const bool keep = 3 * (mx < 0 ? -mx : mx) < nx && (mx | j) != 0;
+        const float kx = kx1 * (float)mx, ky = ky1 * (float)j;
+        // i kx v - i ky u = (-(kx v.y - ky u.y), kx v.x - ky u.x)
+        W[q] = keep ? make_float2(ky * u.y - kx * v.y, kx * v.x - ky * u.x) : make_float2(0.f, 0.f);
+        if (i == 0 && j == 0) { mean[2 * b] = u.x * inv_n; mean[2 * b + 1] = v.x * inv_n; }
+    }
+}
+
+// rfft2 spectra of u_x, u_y, v_x, v_y, u, v ([6][B][nx][nh]) from W and the means
+__global__ void ps_derivs_kernel(const float2* __restrict__ W, const float* __restrict__ mean, float2* __restrict__ out,
+                                 int batch, int nx, int ny, int my1, float kx1, float ky1) {
+    const long nh = ny / 2 + 1, per = (long)batch * nx * nh;
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < per; q += (long)gridDim.x * blockDim.x) {
+        const int j = (int)(q % nh), i = (int)((q / nh) % nx);
+        const long b = q / ((long)nx * nh);
+        const int mx = i < nx / 2 ? i : i - nx;
+        cf u = {0.f, 0.f}, v = {0.f, 0.f}, ux = u, uy = u, vx = u, vy = u;
+        if (j < my1) {
+            const float2 w2 = W[((size_t)b * my1 + j) * nx + i];
+            const float kx = kx1 * (float)mx, ky = ky1 * (float)j, k2 = kx * kx + ky * ky;
+            const cf psi = k2 > 0.f ? cf{w2.x / k2, w2.y / k2} : cf{0.f, 0.f};
+            u = imul(ky, psi);
+            v = imul(-kx, psi);
+            ux = imul(kx, u); uy = imul(ky, u); vx = imul(kx, v); vy = imul(ky, v);
+            if (i == 0 && j == 0) {
+                const float n = (float)nx * (float)ny;
+                u = {mean[2 * b] * n, 0.f}; v = {mean[2 * b + 1] * n, 0.f};
+            }
+        }
+        const cf f[6] = {ux, uy, vx, vy, u, v};
+#pragma unroll
+        for (int k = 0; k < 6; ++k) out[k * per + q] = make_float2(f[k].x, f[k].y);
+    }
+}
+
+// q = 2 rho (u_x v_y - u_y v_x) from d = [u_x, u_y, v_x, v_y] ([4][n])
+__global__ void ps_source_kernel(const float* d, float* q, long n, float two_rho) {      // q may alias d's first field
+    for (long k = blockIdx.x * (long)blockDim.x + threadIdx.x; k < n; k += (long)gridDim.x * blockDim.x)
+        q[k] = two_rho * (d[k] * d[3 * n + k] - d[n + k] * d[2 * n + k]);
+}
+
+// p^ = -M q^ / |k|^2 in place (rfft2 layout)
+__global__ void ps_pressure_kernel(float2* __restrict__ qh, int batch, int nx, int ny, float kx1, float ky1) {
+    const long nh = ny / 2 + 1, per = (long)batch * nx * nh;
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < per; q += (long)gridDim.x * blockDim.x) {
+        const int j = (int)(q % nh), i = (int)((q / nh) % nx);
+        const int mx = i < nx / 2 ? i : i - nx;
+        const bool keep = 3 * (mx < 0 ? -mx : mx) < nx && 3 * j < ny && (mx | j) != 0;
+        const float kx = kx1 * (float)mx, ky = ky1 * (float)j, k2 = kx * kx + ky * ky;
+        const float2 z = qh[q];
+        qh[q] = keep ? make_float2(-z.x / k2, -z.y / k2) : make_float2(0.f, 0.f);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- host side
+inline bool pow2ok(int n) { return n >= 64 && n <= 1024 && (n & (n - 1)) == 0; }
+inline int kept_y(int ny) { return (ny - 1) / 3 + 1; }
+
+template <typename F>
+int dispatch(int n, F&& f) {
+    switch (n) {
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        case 256: return f(std::integral_constant<int, 256>{});
+        case 512: return f(std::integral_constant<int, 512>{});
+        case 1024: return f(std::integral_constant<int, 1024>{});
+    }
+    return fail(NNS_ERR_UNSUPPORTED, "spec_ns: axis length %d is not a power of two in [64, 1024]", n);
+}
+
+template <typename K>
+int set_lds(K kern, int bytes) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "spec_ns: hipFuncSetAttribute(%d B): %s", bytes, hipGetErrorString(e));
+    return NNS_OK;
+}
+
+inline unsigned grid_of(long work, long per) { const long g = (work + per - 1) / per; return (unsigned)(g < kGridCap ? g : kGridCap); }
+
+template <int N>
+int launch_row(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s) {
+    auto kern = ps_row_kernel<N>;
+    if (int rc = set_lds(kern, PsLds<N>::TOTAL)) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a);
+    return check_launch("spec_ns row pass");
+}
+
+template <int N, int S>
+int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, hipStream_t s) {
+    auto kern = ps_col_kernel<N, S>;
+    if (int rc = set_lds(kern, PsLds<N>::TOTAL)) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit);
+    return check_launch("spec_ns column pass");
+}
+
+template <int N>
+int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, hipStream_t s) {
+    switch (S) {
+        case 0: return launch_col<N, 0>(Ph, G, W, A, mean, a, emit, s);
+        case 1: return launch_col<N, 1>(Ph, G, W, A, mean, a, emit, s);
+        case 2: return launch_col<N, 2>(Ph, G, W, A, mean, a, emit, s);
+        case 3: return launch_col<N, 3>(Ph, G, W, A, mean, a, emit, s);
+        default: return launch_col<N, 4>(Ph, G, W, A, mean, a, emit, s);
+    }
+}
+
+size_t step_bytes(int batch, int nx, int ny) { return (size_t)6 * batch * nx * kept_y(ny) * sizeof(float2); }
+size_t init_bytes(int batch, int nx, int ny) { return (size_t)2 * batch * nx * (ny / 2 + 1) * sizeof(float2); }
+size_t fields_bytes(int batch, int nx, int ny) {
+    return (size_t)6 * batch * nx * (ny / 2 + 1) * sizeof(float2) + (size_t)4 * batch * nx * ny * sizeof(float);
+}
+size_t work_bytes(int batch, int nx, int ny) {
+    size_t b = step_bytes(batch, nx, ny);
+    if (init_bytes(batch, nx, ny) > b) b = init_bytes(batch, nx, ny);
+    if (fields_bytes(batch, nx, ny) > b) b = fields_bytes(batch, nx, ny);
+    return b;
+}
+
+int check_common(const char* what, int batch, int nx, int ny, double Lx, double Ly, const void* work, size_t wbytes) {
+    if (!(Lx > 0) || !(Ly > 0) || !std::isfinite(Lx) || !std::isfinite(Ly))
+        return fail(NNS_ERR_INVALID_ARG, "%s: Lx = %g, Ly = %g must be positive and finite", what, Lx, Ly);
+    if (!pow2ok(nx) || !pow2ok(ny))
+        return fail(NNS_ERR_UNSUPPORTED, "%s: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", what, nx, ny);
+    const size_t need = work_bytes(batch, nx, ny);
+    if (wbytes < need) return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (nns_spec_ns_workspace)", what, wbytes, need);
+    (void)work;
+    return NNS_OK;
+}
+
+inline unsigned pw_grid(long n) { const long g = (n + 255) / 256; return (unsigned)(g < 4096 ? g : 4096); }
+
+}  // namespace
+
+#define S_(stream) reinterpret_cast<hipStream_t>(stream)
+
+NNS_API int nns_spec_ns_workspace(int batch, int nx, int ny, size_t* bytes) {
+    if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
+    if (!pow2ok(nx) || !pow2ok(ny))
+        return fail(NNS_ERR_UNSUPPORTED, "spec_ns_workspace: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", nx, ny);
+    *bytes = work_bytes(batch, nx, ny);
+    return NNS_OK;
+}
+
+NNS_API int nns_spec_ns_init_f32(const float* u, const float* v, float* what, float* mean, void* work, size_t work_bytes_, int batch,
+                                 int nx, int ny, double Lx, double Ly, void* stream) {
+    if (!u || !v || !what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_init: NULL pointer or batch < 1");
+    if (int rc = check_common("spec_ns_init", batch, nx, ny, Lx, Ly, work, work_bytes_)) return rc;
+    hipStream_t s = S_(stream);
+    float* uh = static_cast<float*>(work);
+    float* vh = uh + (size_t)2 * batch * nx * (ny / 2 + 1);
+    if (int rc = nns_spec_rfft2_f32(u, uh, batch, nx, ny, stream)) return rc;
+    if (int rc = nns_spec_rfft2_f32(v, vh, batch, nx, ny, stream)) return rc;
+    const int my1 = kept_y(ny);
+    hipLaunchKernelGGL(ps_init_kernel, dim3(pw_grid((long)batch * my1 * nx)), dim3(256), 0, s, reinterpret_cast<const float2*>(uh),
+                       reinterpret_cast<const float2*>(vh), reinterpret_cast<float2*>(what), mean, batch, nx, ny, my1,
+                       (float)(2.0 * M_PI / Lx), (float)(2.0 * M_PI / Ly), (float)(1.0 / ((double)nx * ny)));
+    return check_launch("spec_ns_init");
+}
+
+NNS_API int nns_spec_ns_step_f32(float* what, const float* mean, void* work, size_t work_bytes_, int batch, int nx, int ny, double Lx,
+                                 double Ly, double dt, double nu, int nsteps, void* stream) {
+    if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step: NULL pointer or batch < 1");
+    if (!(dt > 0) || !std::isfinite(dt) || !(nu >= 0) || !std::isfinite(nu) || nsteps < 0)
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_step: dt = %g must be > 0, nu = %g >= 0, nsteps = %d >= 0", dt, nu, nsteps);
+    if (int rc = check_common("spec_ns_step", batch, nx, ny, Lx, Ly, work, work_bytes_)) return rc;
+    if (nsteps == 0) return NNS_OK;
+    hipStream_t s = S_(stream);
+    const int my1 = kept_y(ny);
+    const long fstride = (long)batch * nx * my1;
+    float2* W = reinterpret_cast<float2*>(what);
+    float2* A = static_cast<float2*>(work);
+    float2* G = A + fstride;
+    float2* Ph = G + 4 * fstride;
+    PsArgs ac{(long)batch * my1, fstride, my1, (float)(2.0 * M_PI / Lx), (float)(2.0 * M_PI / Ly), (float)(-0.5 * nu * dt), (float)dt,
+              (float)(1.0 / ((double)nx * ny))};
+    PsArgs ar = ac;
+    ar.nlines = (long)batch * nx;
+    auto col = [&](int S, int emit) { return dispatch(nx, [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, s); }); };
+    auto row = [&]() { return dispatch(ny, [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, s); }); };
+    if (int rc = col(0, 1)) return rc;
+    for (int k = 0; k < nsteps; ++k) {
+        for (int S = 1; S <= 4; ++S) {
+            if (int rc = row()) return rc;
+            if (int rc = col(S, k + 1 < nsteps)) return rc;
+        }
+    }
+    return NNS_OK;
+}
+
+NNS_API int nns_spec_ns_fields_f32(const float* what, const float* mean, float* u, float* v, float* p, void* work, size_t work_bytes_,
+                                   int batch, int nx, int ny, double Lx, double Ly, double rho, void* stream) {
+    if (!what || !mean || !u || !v || !p || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_fields: NULL pointer or batch < 1");
+    if (!std::isfinite(rho)) return fail(NNS_ERR_INVALID_ARG, "spec_ns_fields: rho = %g must be finite", rho);
+    if (int rc = check_common("spec_ns_fields", batch, nx, ny, Lx, Ly, work, work_bytes_)) return rc;
+    hipStream_t s = S_(stream);
+    const int my1 = kept_y(ny);
+    const long nh = ny / 2 + 1, per = (long)batch * nx * nh, npts = (long)batch * nx * ny;
+    float* spec = static_cast<float*>(work);                 // [6][B][nx][nh] complex: u_x, u_y, v_x, v_y, u, v
+    float* phys = spec + 2 * 6 * per;                        // [4][B][nx][ny]: u_x, u_y, v_x, v_y; then q
+    const float kx1 = (float)(2.0 * M_PI / Lx), ky1 = (float)(2.0 * M_PI / Ly);
+    hipLaunchKernelGGL(ps_derivs_kernel, dim3(pw_grid(per)), dim3(256), 0, s, reinterpret_cast<const float2*>(what), mean,
+                       reinterpret_cast<float2*>(spec), batch, nx, ny, my1, kx1, ky1);
+    if (int rc = check_launch("spec_ns_fields")) return rc;
+    if (int rc = nns_spec_irfft2_f32(spec, phys, 4 * batch, nx, ny, stream)) return rc;
+    if (int rc = nns_spec_irfft2_f32(spec + 2 * 4 * per, u, batch, nx, ny, stream)) return rc;
+    if (int rc = nns_spec_irfft2_f32(spec + 2 * 5 * per, v, batch, nx, ny, stream)) return rc;
+    hipLaunchKernelGGL(ps_source_kernel, dim3(pw_grid(npts)), dim3(256), 0, s, phys, phys, npts, (float)(2.0 * rho));
+    if (int rc = check_launch("spec_ns_fields")) return rc;
+    if (int rc = nns_spec_rfft2_f32(phys, spec, batch, nx, ny, stream)) return rc;
+    hipLaunchKernelGGL(ps_pressure_kernel, dim3(pw_grid(per)), dim3(256), 0, s, reinterpret_cast<float2*>(spec), batch, nx, ny, kx1, ky1);
+    if (int rc = check_launch("spec_ns_fields")) return rc;
+    return nns_spec_irfft2_f32(spec, p, batch, nx, ny, stream);
+}

@@ -75,6 +75,10 @@ _SINGLE = {
     'nns_spec_derivs_f32': [_P] * 4 + [_I] * 3 + [_D, _D, _I, _P],
     'nns_spec_rfft2_f32': [_P, _P, _I, _I, _I, _P],
     'nns_spec_irfft2_f32': [_P, _P, _I, _I, _I, _P],
+    'nns_spec_ns_workspace': [_I, _I, _I, C.POINTER(C.c_size_t)],
+    'nns_spec_ns_init_f32': [_P] * 5 + [_SZ] + [_I] * 3 + [_D, _D, _P],
+    'nns_spec_ns_step_f32': [_P] * 3 + [_SZ] + [_I] * 3 + [_D] * 4 + [_I, _P],
+    'nns_spec_ns_fields_f32': [_P] * 6 + [_SZ] + [_I] * 3 + [_D] * 3 + [_P],
     'nns_pixel_mlp_fwd_f32': [_P] * 4 + [_I, _I, C.POINTER(C.c_int), _I, _I, _P],
     'nns_pixel_mlp_bwd_workspace': [C.POINTER(C.c_int), _I, C.POINTER(C.c_size_t)],
     'nns_pixel_mlp_bwd_f32': [_P] * 7 + [_I, _I, C.POINTER(C.c_int), _I, _I, _P, C.c_size_t, _P],

@@ -856,6 +856,75 @@ def spec_irfft2(spec, ny):
     return f
 
 
+# ----------------------------------------------------------------------------- pseudo-spectral periodic solver (nns_spec_ns_*)
+def spec_ns_kept_y(ny):
+    """Kept y-wavenumbers of the 2/3 rule: j < (ny - 1) // 3 + 1."""
+    return (int(ny) - 1) // 3 + 1
+
+
+def spec_ns_workspace(B, nx, ny):
+    """Bytes of the workspace nns_spec_ns_init / step / fields need for B grids of nx x ny."""
+    import ctypes
+    n = ctypes.c_size_t(0)
+    check(_lib.lib().nns_spec_ns_workspace(int(B), int(nx), int(ny), ctypes.byref(n)), 'nns_spec_ns_workspace')
+    return n.value
+
+
+def _spec_ns_state(what, mean, work):
+    _f32(what, mean)
+    if what.dim() != 4 or what.shape[3] != 2:
+        raise ValueError("spec_ns: what must be float32 [B, my1, nx, 2], got %s" % (tuple(what.shape),))
+    B, my1, nx = what.shape[0], what.shape[1], what.shape[2]
+    if tuple(mean.shape) != (B, 2):
+        raise ValueError("spec_ns: mean must be [B, 2], got %s" % (tuple(mean.shape),))
+    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
+        raise TypeError("spec_ns: work must be a contiguous uint8 device tensor")
+    if what.device != mean.device or what.device != work.device:
+        raise ValueError("spec_ns: state tensors on different devices")
+    return B, my1, nx
+
+
+def spec_ns_init(u, v, what, mean, work, Lx, Ly):
+    """what, mean <- the solver state of velocity (u, v) [B, nx, ny] float32: what = M (i kx v^ - i ky u^) compacted ([B, my1, nx, 2]),
+    mean = the grid means [B, 2].  Divergence-free, band-limited projection of the input."""
+    _f32(u, v)
+    suf, (B, nx, ny) = _chk(u, v)
+    Bw, my1, nxw = _spec_ns_state(what, mean, work)
+    if (Bw, my1, nxw) != (B, spec_ns_kept_y(ny), nx) or u.device != what.device:
+        raise ValueError("spec_ns_init: state [%d, %d, %d] does not match fields [%d, %d, %d]" % (Bw, my1, nxw, B, nx, ny))
+    check(_lib.lib().nns_spec_ns_init_f32(_p(u), _p(v), _p(what), _p(mean), _p(work), work.numel(), B, nx, ny, float(Lx), float(Ly),
+                                          _stream()), 'nns_spec_ns_init_f32')
+    return what, mean
+
+
+def spec_ns_step_(what, mean, work, ny, Lx, Ly, dt, nu, nsteps=1):
+    """nsteps Lawson-RK4 steps on what in place (no allocation, no host synchronisation: capturable)."""
+    B, my1, nx = _spec_ns_state(what, mean, work)
+    if my1 != spec_ns_kept_y(ny):
+        raise ValueError("spec_ns_step_: what has %d kept y-wavenumbers, ny = %d needs %d" % (my1, ny, spec_ns_kept_y(ny)))
+    check(_lib.lib().nns_spec_ns_step_f32(_p(what), _p(mean), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt),
+                                          float(nu), int(nsteps), _stream()), 'nns_spec_ns_step_f32')
+    return what
+
+
+def spec_ns_fields(what, mean, work, ny, Lx, Ly, rho, out=None):
+    """(u, v, p) float32 [B, nx, ny] of the state; out: three preallocated contiguous tensors of that shape."""
+    B, my1, nx = _spec_ns_state(what, mean, work)
+    if my1 != spec_ns_kept_y(ny):
+        raise ValueError("spec_ns_fields: what has %d kept y-wavenumbers, ny = %d needs %d" % (my1, ny, spec_ns_kept_y(ny)))
+    if out is None:
+        out = tuple(torch.empty((B, nx, int(ny)), dtype=torch.float32, device=what.device) for _ in range(3))
+    else:
+        out = tuple(out)
+        _f32(*out)
+        if len(out) != 3 or any(tuple(o.shape) != (B, nx, int(ny)) or o.device != what.device for o in out):
+            raise ValueError("spec_ns_fields: out must be three [%d, %d, %d] tensors on the state's device" % (B, nx, ny))
+    u, v, p = out
+    check(_lib.lib().nns_spec_ns_fields_f32(_p(what), _p(mean), _p(u), _p(v), _p(p), _p(work), work.numel(), B, nx, int(ny), float(Lx),
+                                            float(Ly), float(rho), _stream()), 'nns_spec_ns_fields_f32')
+    return out
+
+
 # ----------------------------------------------------------------------------- physics-informed loss head
 _PINN_WS = {}
 

@@ -1,0 +1,139 @@
+"""Times the pseudo-spectral periodic solver's fused step (nns.periodic.PeriodicSolver.step: 8 launches of csrc/pspec_kernels.hip per step)
+against a COMPOSED step of the same scheme on the same inputs in the same run: the standalone transforms nns.ops.spec_rfft2 /
+spec_irfft2 plus torch elementwise ops on full rfft2-layout spectra.  Writes ONE JSON record to OUTDIR/pspec_run.json and prints it.
+
+    python tools/pspec_run.py OUTDIR [--steps 20] [--reps 5]
+
+Cases: 256^2 x B = 64 and 1024^2 x B = 8, |m| <= 8 initial condition (tests/pspec_oracle.py: random_ic), nu = 1e-3.  Per case: ms per
+step of each (device events around `steps` steps, warmed, median of `reps`), the bytes-per-point model of each (below) and the rel-L2
+difference of the two after `steps` steps (same scheme, float32 both: rounding only)."""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'neural-navier-stokes_amd'), os.path.join(ROOT, 'tests')]
+
+import torch  # noqa: E402
+
+import pspec_oracle as O  # noqa: E402
+from nns import ops  # noqa: E402
+from nns.periodic import PeriodicSolver  # noqa: E402
+
+CASES = [(256, 64), (1024, 8)]
+
+
+def fused_bytes_per_point(nx, ny):
+    """HBM bytes per grid point per step of the fused step, c = one compacted complex field (8 my1 bytes per row of ny points).
+    Per stage the row launch reads 4c (u, v, w_x, w_y) and writes c (the product's kept spectrum); the column launch reads c, moves
+    W / A (2c, 3c, 3c, 2c for stages 1..4) and writes the next stage's 4c.  Per step: 20c + 4c + 10c + 16c = 50c."""
+    return 50 * 8.0 * ops.spec_ns_kept_y(ny) / ny
+
+
+def composed_bytes_per_point(nx, ny):
+    """The composed step, f = one full rfft2 spectrum (8 (ny/2 + 1) bytes per row), r = one real field (4 ny bytes per row), tables ignored.
+    Per evaluation of N: psi (2f), the four spectra (8f), their stack (8f), spec_irfft2's scratch copy (8f), column pass (8f), row pass
+    (4f + 4r), the product (9r), spec_rfft2 (3f + r), the mask (2f): 43f + 14r.  Lawson combinations per step: 31f."""
+    f, r = 8.0 * (ny // 2 + 1) / ny, 4.0
+    return 4 * (43 * f + 14 * r) + 31 * f
+
+
+class Composed(object):
+    """The scheme of tests/pspec_oracle.py on full rfft2-layout complex64 spectra [B, nx, ny/2+1]."""
+
+    def __init__(self, s, what, mean):
+        nx, ny, dev = s.nx, s.ny, what.device
+        kx, ky, k2, M, ik2 = O.grid(nx, ny, s.Lx, s.Ly)
+        t = lambda a, dt=torch.float32: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+        self.s, self.ny = s, ny
+        self.ikx, self.iky = t(1j * kx * np.ones_like(k2), torch.complex64), t(1j * ky * np.ones_like(k2), torch.complex64)
+        self.M, self.ik2 = t(M), t(ik2)
+        self.E, self.E2 = t(np.exp(-s.nu * k2 * s.dt / 2)), t(np.exp(-s.nu * k2 * s.dt))
+        B = what.shape[0]
+        full = torch.zeros(B, nx, ny // 2 + 1, dtype=torch.complex64, device=dev)
+        full[:, :, :s.my1] = torch.view_as_complex(what).transpose(1, 2)
+        self.w = full
+        self.m0 = (mean * float(nx * ny)).to(torch.complex64)
+
+    def N(self, w):
+        psi = w * self.ik2
+        uh, vh = self.iky * psi, -self.ikx * psi
+        uh[:, 0, 0], vh[:, 0, 0] = self.m0[:, 0], self.m0[:, 1]
+        four = torch.stack([uh, vh, self.ikx * w, self.iky * w]).reshape(-1, w.shape[1], w.shape[2])
+        phys = ops.spec_irfft2(four, self.ny).view(4, *w.shape[:2], self.ny)
+        prod = phys[0] * phys[2] + phys[1] * phys[3]
+        return -self.M * ops.spec_rfft2(prod)
+
+    def step(self, nsteps):
+        dt, E, E2 = self.s.dt, self.E, self.E2
+        w = self.w
+        for _ in range(nsteps):
+            a = self.N(w)
+            b = self.N(E * (w + dt / 2 * a))
+            c = self.N(E * w + dt / 2 * b)
+            d = self.N(E2 * w + dt * E * c)
+            w = E2 * w + dt / 6 * (E2 * a + 2 * E * (b + c) + d)
+        self.w = w
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('outdir')
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--reps', type=int, default=5)
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    rec = dict(device=torch.cuda.get_device_name(0), steps=args.steps, reps=args.reps, cases=[])
+    for n, B in CASES:
+        s = PeriodicSolver(n, n, 1e-3, 1.0, 1e-3)
+        u0, v0 = O.random_ic(B, n, n, 8, seed=n + B, umax=1.0)
+        st = s.init(torch.as_tensor(u0, dtype=torch.float32, device='cuda'), torch.as_tensor(v0, dtype=torch.float32, device='cuda'))
+        comp = Composed(s, st.what, st.mean)
+        w0 = st.what.clone()
+        # agreement: the same number of steps from the same state
+        s.step(st, args.steps)
+        comp.step(args.steps)
+        uf = s.fields(st)[0]
+        cw = comp.w[:, :, :s.my1].transpose(1, 2).contiguous()
+        st.what.copy_(torch.view_as_real(cw))
+        uc = s.fields(st)[0]
+        diff = float((uf - uc).norm() / uc.norm())
+        st.what.copy_(w0)
+        ms_fused = timed(lambda: s.step(st, args.steps), args.reps) / args.steps
+        ms_comp = timed(lambda: comp.step(args.steps), args.reps) / args.steps
+        case = dict(nx=n, ny=n, batch=B, ms_per_step_fused=round(ms_fused, 4), ms_per_step_composed=round(ms_comp, 4),
+                    speedup=round(ms_comp / ms_fused, 2),
+                    bytes_per_point_fused=round(fused_bytes_per_point(n, n), 1),
+                    bytes_per_point_composed=round(composed_bytes_per_point(n, n), 1),
+                    fused_GBps=round(fused_bytes_per_point(n, n) * n * n * B / ms_fused / 1e6, 1),
+                    rel_l2_fused_vs_composed_u=float('%.3g' % diff))
+        rec['cases'].append(case)
+        print(json.dumps(case), flush=True)
+        del st, comp
+        torch.cuda.empty_cache()
+    os.makedirs(args.outdir, exist_ok=True)
+    with open(os.path.join(args.outdir, 'pspec_run.json'), 'w') as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
+if __name__ == '__main__':
+    main()
