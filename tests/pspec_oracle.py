@@ -19,6 +19,15 @@ def kept_y(ny):
     return (ny - 1) // 3 + 1
 
 
+def band(nx, ny, widen=(0, 0)):
+    """The 2/3-rule mask [nx, nh] (bool, (0, 0) dropped); widen = (wx, wy) keeps wx more |m_x| and wy more m_y (mutation tests)."""
+    mx = np.fft.fftfreq(nx) * nx
+    my = np.arange(ny // 2 + 1)
+    M = (3 * (np.abs(mx)[:, None] - widen[0]) < nx) & (my[None, :] < kept_y(ny) + widen[1])
+    M[0, 0] = False
+    return M
+
+
 def grid(nx, ny, Lx, Ly):
     """kx [nx, 1], ky [1, nh], |k|^2, mask M (float), 1 / |k|^2 (0 at k = 0)."""
     mx = np.fft.fftfreq(nx) * nx
@@ -26,16 +35,18 @@ def grid(nx, ny, Lx, Ly):
     kx = (2 * np.pi / Lx * mx)[:, None]
     ky = (2 * np.pi / Ly * my)[None, :]
     k2 = kx * kx + ky * ky
-    M = ((3 * np.abs(mx)[:, None] < nx) & (3 * my[None, :] < ny)).astype(np.float64)
-    M[0, 0] = 0.0
+    M = band(nx, ny).astype(np.float64)
     ik2 = np.where(k2 > 0, 1.0 / np.where(k2 > 0, k2, 1.0), 0.0)
     return kx, ky, k2, M, ik2
 
 
 class Scheme(object):
-    def __init__(self, nx, ny, dt, rho, nu, Lx=2 * np.pi, Ly=2 * np.pi):
+    """widen: a deliberately wrong dealiasing mask for the nonlinear term of the step (see band); init and fields keep the 2/3 rule."""
+
+    def __init__(self, nx, ny, dt, rho, nu, Lx=2 * np.pi, Ly=2 * np.pi, widen=(0, 0)):
         self.nx, self.ny, self.dt, self.rho, self.nu, self.Lx, self.Ly = nx, ny, dt, rho, nu, Lx, Ly
         self.kx, self.ky, self.k2, self.M, self.ik2 = grid(nx, ny, Lx, Ly)
+        self.MN = self.M if tuple(widen) == (0, 0) else band(nx, ny, widen).astype(np.float64)
 
     def irfft2(self, f):
         return np.fft.irfft2(f, s=(self.nx, self.ny))
@@ -59,7 +70,7 @@ class Scheme(object):
         uh, vh = self.velocity_hat(w, mean)
         u, v = self.irfft2(uh), self.irfft2(vh)
         wx, wy = self.irfft2(1j * self.kx * w), self.irfft2(1j * self.ky * w)
-        return -self.M * np.fft.rfft2(u * wx + v * wy)
+        return -self.MN * np.fft.rfft2(u * wx + v * wy)
 
     def step(self, w, mean, nsteps=1):
         dt = self.dt
@@ -135,3 +146,40 @@ def random_ic(B, nx, ny, mmax, seed, Lx=2 * np.pi, Ly=2 * np.pi, umax=1.0, mean=
     v = np.fft.irfft2(-1j * kx * psi, s=(nx, ny))
     s = umax / max(np.abs(u).max(), np.abs(v).max())
     return u * s + mean[0], v * s + mean[1]
+
+
+def band_psi(B, nx, ny, seed):
+    """Random streamfunction spectrum [B, nx, nh] over the whole 2/3 band (3|m_x| < nx, 3 m_y < ny, no (0, 0)), amplitude ~ 1/|m|^2 with
+    m_x, m_y scaled to the shorter axis's band, Hermitian on the m_y = 0 column (psi(-m_x, 0) = conj psi(m_x, 0)): irfft2 then keeps
+    every drawn coefficient."""
+    rng = np.random.default_rng(seed)
+    mx = np.fft.fftfreq(nx) * nx
+    my = np.arange(ny // 2 + 1)
+    Kx, Ky = (nx - 1) // 3, kept_y(ny) - 1
+    K = min(Kx, Ky)                     # |m| with each axis rescaled to the shorter band: both edges are equally far out
+    mm = (K * mx[:, None] / Kx) ** 2 + (K * my[None, :] / Ky) ** 2
+    psi = (rng.standard_normal((B, nx, ny // 2 + 1)) + 1j * rng.standard_normal((B, nx, ny // 2 + 1))) * band(nx, ny) / np.maximum(1.0, mm)
+    neg = (-np.arange(nx)) % nx
+    psi[:, :, 0] = np.where((mx < 0)[None, :], np.conj(psi[:, neg, 0]), psi[:, :, 0])
+    return psi
+
+
+def band_ic(B, nx, ny, seed, Lx=2 * np.pi, Ly=2 * np.pi, umax=1.0, mean=(0.0, 0.0)):
+    """Divergence-free velocity [B, nx, ny] whose spectrum fills the whole kept band (band_psi): energy reaches the edge modes of both
+    axes, so the products of the nonlinear term spill past the band and alias.  Scaled to max|u, v| = umax, plus a uniform mean."""
+    psi = band_psi(B, nx, ny, seed)
+    mx = np.fft.fftfreq(nx) * nx
+    my = np.arange(ny // 2 + 1)
+    kx = (2 * np.pi / Lx * mx)[:, None]
+    ky = (2 * np.pi / Ly * my)[None, :]
+    u = np.fft.irfft2(1j * ky * psi, s=(nx, ny))
+    v = np.fft.irfft2(-1j * kx * psi, s=(nx, ny))
+    s = umax / max(np.abs(u).max(), np.abs(v).max())
+    return u * s + mean[0], v * s + mean[1]
+
+
+def cfl_dt(nx, ny, Lx, Ly, umax, cfl=0.5):
+    """dt with dt umax (k_x,max + k_y,max) = cfl over the kept band: RK4 well inside its stability region."""
+    kx = 2 * np.pi / Lx * ((nx - 1) // 3)
+    ky = 2 * np.pi / Ly * (kept_y(ny) - 1)
+    return cfl / (umax * (kx + ky))

@@ -5,6 +5,7 @@ import math
 import numpy as np
 import pytest
 
+import pspec_cases as C
 import pspec_oracle as O
 from conftest import rel_l2
 
@@ -136,3 +137,86 @@ def test_state_layout_helper():
     c = S.compact(w)
     assert c.shape == (3, 43, 64) and np.array_equal(c[1, 5, 7], w[1, 7, 5])
     assert np.abs(w[..., 43:]).max() == 0                           # nothing outside the kept columns
+
+
+# ---------------------------------------------------------------------------------------------------- full-band cases (pspec_cases.py)
+@pytest.mark.parametrize('case', C.FULL_BAND, ids=[C.case_id(c) for c in C.FULL_BAND])
+def test_band_ic_fills_the_band(case):
+    nx, ny, B, Lx, Ly, mean = case
+    u, v = O.band_ic(B, nx, ny, C.seed(case), Lx, Ly, C.UMAX, mean)
+    assert np.isclose(max(np.abs(u - mean[0]).max(), np.abs(v - mean[1]).max()), C.UMAX)
+    assert np.allclose(u.mean(axis=(1, 2)), mean[0]) and np.allclose(v.mean(axis=(1, 2)), mean[1])
+    S = O.Scheme(nx, ny, 0.01, 1.0, 0.0, Lx, Ly)
+    kmax = max(np.pi * nx / Lx, np.pi * ny / Ly)
+    assert np.abs(S.divergence(u, v)).max() <= 1e-12 * kmax
+    # Hermitian-consistent: every drawn coefficient survives irfft2 (the m_y = 0 column is conjugate-symmetric in m_x)
+    psi = O.band_psi(B, nx, ny, C.seed(case))
+    uh = np.fft.rfft2(u - mean[0])
+    want = 1j * S.ky * psi
+    scale = np.vdot(want, uh).real / np.vdot(want, want).real
+    assert np.linalg.norm(uh - scale * want) <= 1e-12 * np.linalg.norm(uh)
+    # band-limited, and the outermost kept shell of each axis (|m_x| = (nx - 1) // 3, m_y = my1 - 1) carries energy: measured over
+    # these shapes 4.0e-4 .. 6.4e-3 of the total in each (random_ic with |m| <= 8 has none there)
+    e = np.abs(uh) ** 2 + np.abs(np.fft.rfft2(v - mean[1])) ** 2
+    inside = O.band(nx, ny)
+    assert e[:, ~inside].sum() <= 1e-28 * e.sum()
+    mx = np.abs(np.fft.fftfreq(nx) * nx)
+    ex = e[:, mx == (nx - 1) // 3].sum() / e.sum()
+    ey = e[:, :, O.kept_y(ny) - 1].sum() / e.sum()
+    assert ex >= 2.5e-4 and ey >= 2.5e-4, (ex, ey)
+
+
+def _mutation_errors(u0, v0, dt, nx, ny, Lx, Ly, nsteps, nu):
+    _, ref = C.oracle_run(u0, v0, dt, nx, ny, Lx, Ly, nsteps, nu)
+    out = {}
+    for name, widen in (('x', (1, 0)), ('y', (0, 1))):
+        _, got = C.oracle_run(u0, v0, dt, nx, ny, Lx, Ly, nsteps, nu, widen)
+        out[name] = [rel_l2(g, r) for g, r in zip(got, ref)]
+    return out
+
+
+# the GPU cases of pspec_cases.FULL_BAND at B = 1 and axes cut to <= 256 (CPU cost), each box, mean and dt rule kept
+REDUCED = sorted(set((min(c[0], 256), min(c[1], 256), 1, c[3], c[4], c[5]) for c in C.FULL_BAND))
+
+
+@pytest.mark.parametrize('case', REDUCED, ids=[C.case_id(c) + '_L%.3g' % c[3] for c in REDUCED])
+def test_full_band_cases_detect_a_mask_one_mode_too_wide(case):
+    # a dealiasing mask that keeps one more mode, in x (3 (|m_x| - 1) < nx) or in y (j < my1 + 1), moves the velocity of these cases by
+    # >= 100x the GPU bound BOUND_UV (2e-6; the GPU measured <= 6.4e-7).  Measured here, the larger of u and v: 7.0e-3 .. 3.2e-2 (x),
+    # 2.7e-3 .. 2.8e-2 (y).
+    # (The stiff case of the GPU tests cannot tell: no energy reaches the band edge there, so the extra mode stays empty.)
+    nx, ny, B, Lx, Ly, mean = case
+    u0, v0, dt = C.full_band_input(*case)
+    errs = _mutation_errors(u0, v0, dt, nx, ny, Lx, Ly, C.NSTEPS, C.NU)
+    print('%dx%d mask one mode too wide: rel-L2 u, v, p  x %s  y %s' % (nx, ny, ['%.1e' % e for e in errs['x']], ['%.1e' % e for e in errs['y']]))
+    for name in errs:
+        assert max(errs[name][:2]) >= 100 * C.BOUND_UV, (name, errs)
+
+
+def test_band_limited_case_cannot_detect_a_mask_one_mode_too_wide():
+    # the case of tests/test_gpu_pspec.py::test_random_band_limited_ic_against_the_oracle (|m| <= 8: products inside |m| <= 16, far
+    # inside the band) moves by 4.2e-6 (x) and 2.6e-6 (y) under the same mask errors: inside its 5e-6 bound, hence the full-band cases
+    u0, v0 = O.random_ic(4, 128, 128, 8, seed=11, umax=2.0)
+    u0, v0 = u0.astype(np.float32), v0.astype(np.float32)
+    errs = _mutation_errors(u0, v0, 0.005, 128, 128, 2 * np.pi, 2 * np.pi, 50, 0.01)
+    print('|m| <= 8 case, mask one mode too wide: x %s  y %s' % (['%.1e' % e for e in errs['x']], ['%.1e' % e for e in errs['y']]))
+    assert max(errs['x']) <= 5e-6 and max(errs['y']) <= 5e-6, errs
+    assert max(errs['x']) >= 1e-6 and max(errs['y']) >= 1e-6, errs             # the variants do run a different scheme
+
+
+def test_inviscid_case_detects_a_mask_one_mode_too_wide():
+    # the inviscid GPU case (tests/test_gpu_pspec_edges.py: 128^2 full band, 200 steps, energy and enstrophy drift <= 5e-6; the GPU
+    # measured 5.7e-7): a mask one mode too wide breaks the conservation of the dealiased scheme.  Measured: the larger drift is
+    # 1.5e-4 (x) and 3.4e-4 (y)
+    n = 128
+    u0, v0 = O.band_ic(1, n, n, seed=5)
+    u0, v0 = u0.astype(np.float32), v0.astype(np.float32)
+    dt = O.cfl_dt(n, n, 2 * np.pi, 2 * np.pi, 1.0)
+    for widen in ((0, 0), (1, 0), (0, 1)):
+        S = O.Scheme(n, n, dt, 1.0, 0.0, widen=widen)
+        w, mean = S.init(u0, v0)
+        e0, z0 = S.energy(w, mean), S.enstrophy(w)
+        w = S.step(w, mean, 200)
+        drift = max((abs(S.energy(w, mean) - e0) / e0).max(), (abs(S.enstrophy(w) - z0) / z0).max())
+        print('inviscid 128^2, widen', widen, 'drift %.2e' % drift)
+        assert drift <= 1e-6 if widen == (0, 0) else drift >= 20 * 5e-6, (widen, drift)
