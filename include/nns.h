@@ -162,6 +162,8 @@ int nns_fd_sor_redblack_f64(double* p, const double* C, double* info, void* work
  * prolongation, restriction = scaled transpose, exact coarsest solve; restatement: tests/mg_oracle.py.  Each grid of the batch stops on its own,
  * on the device, after the cycle in which max|r_k| <= tol max|r_0| or max|r_k| >= 0.9 max|r_(k-1)| (the rounding floor); a grid with
  * max|r_0| = 0 runs no cycle and keeps p bitwise.  info[b] = (cycles done, max|r_k| / max|r_0|) in p's type ((0, 0) for a zero residual).
+ * A NaN or infinite max|r_0| (a NaN or Inf in C, in p's interior or in its boundary ring) is never a zero residual: the grid runs no cycle,
+ * keeps p bitwise and reports (0, NaN).
  * cycles: at most this many cycles are enqueued by this call, no host synchronisation.  resume = 0 starts a solve (measures max|r_0|);
  * resume = 1 continues the solve whose state `work` holds from an earlier call on the same p, C, info.  The first batch int32 of `work` are
  * the grids' active flags (1 = not stopped), readable by the caller between calls.

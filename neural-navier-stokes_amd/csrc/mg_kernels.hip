@@ -212,7 +212,8 @@ __global__ void mg_init_kernel(MgState<T> st, int batch) {
     st.rbits[b] = 0;
 }
 
-// start = 1: max|r_0| has just been measured -> (0, 1) or, for a zero residual, (0, 0) and the grid is off; start = 0: end of a cycle
+// start = 1: max|r_0| has just been measured -> (0, 1); for a zero residual (0, 0) and the grid is off; for a NaN or infinite one (a NaN or
+// Inf in C or p) (0, NaN) and the grid is off; start = 0: end of a cycle
 template <typename T>
 __global__ void mg_finish_kernel(MgState<T> st, T* __restrict__ info, int batch, T tol, int start) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -220,11 +221,12 @@ __global__ void mg_finish_kernel(MgState<T> st, T* __restrict__ info, int batch,
     const T r = __builtin_bit_cast(T, st.rbits[b]);
     st.rbits[b] = 0;
     if (start) {
+        const bool finite = __builtin_isfinite(r);
         st.r0[b] = r;
         st.rprev[b] = r;
-        st.active[b] = r > (T)0 ? 1 : 0;
+        st.active[b] = finite && r > (T)0 ? 1 : 0;
         info[2 * b] = (T)0;
-        info[2 * b + 1] = r > (T)0 ? (T)1 : (T)0;
+        info[2 * b + 1] = !finite ? (T)__builtin_nan("") : (r > (T)0 ? (T)1 : (T)0);
     } else {
         finish_cycle<T>(st, b, r, tol, info);
     }

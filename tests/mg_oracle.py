@@ -13,12 +13,26 @@ level whose cell aspect ratio exceeds 2, a coarsest level with more than 33 node
 Prolongation: per-axis linear interpolation by node coordinate; restriction R = (hx / Hx)(hy / Hy) P^T of the unscaled residual.
 Smoother: red-black Gauss-Seidel, weight 1, colour 0 = (i + j) even.  V(2, 2): pre-smoothing colour 0 then 1, post-smoothing colour 1 then 0.
 Coarsest level: exact solve of the error equation (sine-basis eigen-decomposition).
-Stopping, per grid, after the cycle in which max|r_k| <= tol max|r_0| or max|r_k| >= 0.9 max|r_(k-1)|, or at max_cycles; max|r_0| = 0 runs
-no cycle.  Info: (cycles done, max|r_k| / max|r_0|); (0, 0) for a zero initial residual, (0, 1) for max_cycles = 0.
+Stopping, per grid, after the cycle in which max|r_k| <= tol max|r_0| or max|r_k| >= 0.9 max|r_(k-1)|, or at max_cycles; max|r_0| = 0 or
+non-finite runs no cycle.  Info: (cycles done, max|r_k| / max|r_0|); (0, 0) for a zero initial residual, (0, NaN) for a NaN or infinite one
+(a NaN or Inf in C, in p's interior or in its boundary ring), (0, 1) for max_cycles = 0.
+
+Launch split (host side of the solver, replayed by levels / tail_level / workspace_bytes): the levels from `tail` down to the coarsest run
+in one workgroup's LDS, where tail is the finest level whose LDS (u and f of every level from there on, plus the coarsest solve's sine
+tables and two work arrays) fits LDS_MAX bytes; the finer levels run chip-wide with u and f in the workspace.  The split is counted in
+bytes, so one shape can take different paths in float32 and float64.
+
+mutate= (vcycle, solve_one): a deliberately wrong variant of one operator, for the CPU tests that show a case's bounds would catch it:
+  'post_order'      post-smoothing colours 0 then 1 (the solver: 1 then 0)
+  'prolong_row'     the prolongation's row at fine node nx - 2 (axis 0) halved
+  'restrict_scale'  restriction without the (hx / Hx)(hy / Hy) scale
+  'coarse_mode'     the coarsest solve drops the highest sine mode of each axis (its mode loops one short)
 """
 import numpy as np
 
 MIN_N, STOP_N, MAX_ASPECT, MAX_COARSEST = 5, 9, 2.0, 33
+MAX_LEV, LDS_MAX, INT_MAX = 16, 150 * 1024, 2**31 - 1
+MUTATIONS = ('post_order', 'prolong_row', 'restrict_scale', 'coarse_mode')
 
 
 class UnsupportedGrid(ValueError):
@@ -41,6 +55,55 @@ def hierarchy(nx, ny, dx, dy):
     if max(levs[-1][:2]) > MAX_COARSEST:
         raise UnsupportedGrid("coarsest level %d x %d exceeds %d nodes on an axis" % (levs[-1][0], levs[-1][1], MAX_COARSEST))
     return levs
+
+
+# ---------------------------------------------------------------------------------------------------- the host-side launch split
+def levels(nx, ny):
+    """[(nx, ny)] of every level, finest first: mg_shape of csrc/mg_kernels.hip (no spacings, so no aspect check)."""
+    if min(nx, ny) < MIN_N:
+        raise UnsupportedGrid("multigrid needs at least %d nodes per axis, got %d x %d" % (MIN_N, nx, ny))
+    if nx * ny > INT_MAX // 4:
+        raise UnsupportedGrid("%d x %d grid too large" % (nx, ny))
+    levs = [(nx, ny)]
+    while min(levs[-1]) > STOP_N:
+        if len(levs) == MAX_LEV:
+            raise UnsupportedGrid("more than %d levels" % MAX_LEV)
+        levs.append(((levs[-1][0] - 1) // 2 + 1, (levs[-1][1] - 1) // 2 + 1))
+    if max(levs[-1]) > MAX_COARSEST:
+        raise UnsupportedGrid("coarsest level %d x %d exceeds %d nodes on an axis" % (levs[-1][0], levs[-1][1], MAX_COARSEST))
+    return levs
+
+
+def tail_lds_elems(levs, l):
+    """Elements of LDS of a tail that starts at level l (tail_lds_elems)."""
+    mx, my = levs[-1][0] - 2, levs[-1][1] - 2
+    return sum(2 * a * b for a, b in levs[l:]) + mx * mx + my * my + 2 * mx * my
+
+
+def tail_level(nx, ny, elem_size):
+    """The first level of the LDS tail (tail_level): 0 = the whole cycle in one workgroup."""
+    levs = levels(nx, ny)
+    l = len(levs) - 1
+    while l > 0 and tail_lds_elems(levs, l - 1) * elem_size <= LDS_MAX:
+        l -= 1
+    return l
+
+
+def tail_lds_bytes(nx, ny, elem_size):
+    """Dynamic LDS of the tail launch, in bytes."""
+    return tail_lds_elems(levels(nx, ny), tail_level(nx, ny, elem_size)) * elem_size
+
+
+def _align256(x):
+    return (x + 255) // 256 * 256
+
+
+def workspace_bytes(B, nx, ny, elem_size, tail=None):
+    """nns_fd_poisson_mg_workspace (mg_bytes): the per-grid state, then u and f of every chip-wide level 1 .. tail.  tail: the split to
+    count for (default: the solver's, tail_level)."""
+    levs = levels(nx, ny)
+    t = tail_level(nx, ny, elem_size) if tail is None else tail
+    return _align256(B * (4 + 4 + 8 + 8 + 8)) + sum(2 * _align256(B * a * b * elem_size) for a, b in levs[1:t + 1])
 
 
 def prolongation(n, nc):
@@ -84,8 +147,9 @@ def half_sweep(u, f, hx, hy, mask):
     inner[mask] = nw[mask]
 
 
-def dst_solve(g, hx, hy):
-    """Exact solution of Lap_h e = g on the interior with e = 0 on the boundary ring (g: interior values [nx - 2, ny - 2])."""
+def dst_solve(g, hx, hy, drop_top=False):
+    """Exact solution of Lap_h e = g on the interior with e = 0 on the boundary ring (g: interior values [nx - 2, ny - 2]).
+    drop_top: leave out the highest sine mode of each axis, every mode k = nx - 2 or l = ny - 2 (the 'coarse_mode' mutation)."""
     mx, my = g.shape
     nx, ny = mx + 2, my + 2
     kx, ky = np.arange(1, mx + 1), np.arange(1, my + 1)
@@ -94,6 +158,8 @@ def dst_solve(g, hx, hy):
     lx = -4.0 / (hx * hx) * np.sin(np.pi * kx / (2 * (nx - 1))) ** 2
     ly = -4.0 / (hy * hy) * np.sin(np.pi * ky / (2 * (ny - 1))) ** 2
     gh = Sx @ g @ Sy
+    if drop_top:
+        gh[-1, :] = gh[:, -1] = 0.0
     return (2.0 / (nx - 1)) * (2.0 / (ny - 1)) * (Sx @ (gh / (lx[:, None] + ly[None, :])) @ Sy)
 
 
@@ -112,12 +178,13 @@ def _ring(shape):
     return m
 
 
-def vcycle(levs, us, fs, l=0):
+def vcycle(levs, us, fs, l=0, mutate=None):
+    assert mutate in (None,) + MUTATIONS, mutate
     nx, ny, hx, hy = levs[l]
     u, f = us[l], fs[l]
     if l == len(levs) - 1:
         r = residual(u, f, hx, hy)
-        u[1:-1, 1:-1] += dst_solve(r[1:-1, 1:-1], hx, hy)
+        u[1:-1, 1:-1] += dst_solve(r[1:-1, 1:-1], hx, hy, drop_top=mutate == 'coarse_mode')
         return
     c0, c1 = _colour_masks(nx, ny)
     for _ in range(2):
@@ -127,30 +194,38 @@ def vcycle(levs, us, fs, l=0):
     Px, Py = prolongation(nx, ncx), prolongation(ny, ncy)
     r = residual(u, f, hx, hy)
     fc = np.zeros((ncx, ncy))
-    fc[1:-1, 1:-1] = ((hx / Hx) * (hy / Hy) * (Px.T @ r @ Py))[1:-1, 1:-1]
+    sxy = 1.0 if mutate == 'restrict_scale' else (hx / Hx) * (hy / Hy)
+    fc[1:-1, 1:-1] = (sxy * (Px.T @ r @ Py))[1:-1, 1:-1]
     fs[l + 1] = fc
     us[l + 1] = np.zeros((ncx, ncy))
-    vcycle(levs, us, fs, l + 1)
+    vcycle(levs, us, fs, l + 1, mutate)
+    if mutate == 'prolong_row':
+        Px = Px.copy()
+        Px[nx - 2] *= 0.5
     u[1:-1, 1:-1] += (Px @ us[l + 1] @ Py.T)[1:-1, 1:-1]
+    post = (c0, c1) if mutate == 'post_order' else (c1, c0)
     for _ in range(2):
-        half_sweep(u, f, hx, hy, c1)
-        half_sweep(u, f, hx, hy, c0)
+        half_sweep(u, f, hx, hy, post[0])
+        half_sweep(u, f, hx, hy, post[1])
 
 
-def solve_one(p, C, dx, dy, tol=1e-6, max_cycles=30):
+def solve_one(p, C, dx, dy, tol=1e-6, max_cycles=30, mutate=None):
     """One grid.  Returns (p after the solve, info (cycles, ratio), [max|r_k| for k = 0 .. cycles])."""
     levs = hierarchy(p.shape[0], p.shape[1], dx, dy)
     u = np.array(p, dtype=np.float64)
     f = np.asarray(C, dtype=np.float64) * (1.0 / (dx * dx * dy * dy))
-    rn = [float(np.max(np.abs(residual(u, f, dx, dy))))]
-    if not rn[0] > 0:
+    with np.errstate(invalid='ignore', over='ignore'):
+        rn = [float(np.max(np.abs(residual(u, f, dx, dy))))]     # NaN if any residual is NaN (np.max propagates it)
+    if not np.isfinite(rn[0]):
+        return u, (0, float('nan')), rn
+    if rn[0] == 0:
         return u, (0, 0.0), rn
     if max_cycles <= 0:
         return u, (0, 1.0), rn
     us, fs = [u] + [None] * (len(levs) - 1), [f] + [None] * (len(levs) - 1)
     k = 0
     while k < max_cycles:
-        vcycle(levs, us, fs)
+        vcycle(levs, us, fs, mutate=mutate)
         k += 1
         rn.append(float(np.max(np.abs(residual(u, f, dx, dy)))))
         if not (rn[k] > tol * rn[0] and rn[k] < 0.9 * rn[k - 1]):

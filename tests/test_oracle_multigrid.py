@@ -1,9 +1,15 @@
 """CPU checks of the multigrid restatement (tests/mg_oracle.py) that the GPU solver (csrc/mg_kernels.hip) is compared against: its exact
-discrete solver, its hierarchy, its convergence per cycle and the grids it refuses."""
+discrete solver, its hierarchy, its convergence per cycle, the grids it refuses, its replica of the host's launch split, the edge cases of
+tests/mg_cases.py and how far a wrong operator would move them."""
+import json
+import os
+
 import numpy as np
 import pytest
 
+import mg_cases as K
 import mg_oracle as M
+from conftest import ROOT, rel_l2
 
 SIZES = [(33, 33), (50, 50), (51, 51), (64, 64), (64, 50), (96, 96), (129, 129), (200, 200), (1024, 1024)]
 
@@ -98,3 +104,80 @@ def test_unsupported_grids_are_refused():
     with pytest.raises(M.UnsupportedGrid):
         M.hierarchy(1024, 64, 0.01, 0.01)                              # coarsest 128 x 8
     M.hierarchy(9, 9, 0.25, 0.25)                                      # one level: the exact solve alone
+
+
+# ---------------------------------------------------------------------------------------------------- the launch split and the edge cases
+def test_split_replica_matches_the_recorded_run():
+    """tail_level as profiles/mg_run.json recorded it from the library on the MI355X, in both types."""
+    with open(os.path.join(ROOT, 'profiles', 'mg_run.json')) as fh:
+        run = json.load(fh)
+    seen = set()
+    for c in run['cases']:
+        elem = 4 if c['dtype'] == 'f32' else 8
+        assert [list(l) for l in M.levels(c['n'], c['n'])] == c['levels']
+        assert M.tail_level(c['n'], c['n'], elem) == c['tail_level'], c
+        seen.add((c['n'], elem, c['tail_level']))
+    assert {(64, 4, 0), (64, 8, 0), (512, 4, 3), (512, 8, 3), (1024, 4, 4), (1024, 8, 4)} <= seen
+
+
+def test_split_replica_finds_the_lds_limits():
+    for n, t32, t64 in ((84, 0, 0), (85, 0, 1), (119, 0, 1), (120, 1, 1), (128, 1, 1), (200, 1, 2)):
+        assert (M.tail_level(n, n, 4), M.tail_level(n, n, 8)) == (t32, t64), n
+    whole = lambda n, elem: M.tail_lds_elems(M.levels(n, n), 0) * elem              # the whole cycle in LDS
+    assert whole(84, 8) <= M.LDS_MAX < whole(85, 8) and whole(119, 4) <= M.LDS_MAX < whole(120, 4)
+    assert '%.1f %.1f' % (whole(84, 8) / 1024, whole(119, 4) / 1024) == '147.7 148.6'
+    assert M.workspace_bytes(3, 84, 84, 8) == 256 < M.workspace_bytes(3, 85, 85, 8)   # tail 0: the per-grid state only
+
+
+def test_case_matrix_covers_every_path_and_is_supported():
+    paths = set()
+    for c, why in K.CASES:
+        nx, ny, B, dx, dy = c
+        levs = M.hierarchy(nx, ny, dx, dy)
+        aspect = max(max(h0 / h1, h1 / h0) for _, _, h0, h1 in levs)
+        p32, p64 = K.path(nx, ny, 4), K.path(nx, ny, 8)
+        print('%-22s levels %d  coarsest %2dx%-2d  aspect <= %.3f  f32 %-6s tail %d  f64 %-6s tail %d  (%s)' % (
+            K.case_id(c), len(levs), levs[-1][0], levs[-1][1], aspect, p32, M.tail_level(nx, ny, 4), p64, M.tail_level(nx, ny, 8), why))
+        paths |= {(p32, 4), (p64, 8)}
+    assert paths == {(p, e) for p in ('single', 'lds', 'mixed') for e in (4, 8)}
+    assert max(max(c[:2]) for c, _ in K.CASES if K.path(c[0], c[1], 8) == 'single') == 33          # a 33-node coarsest axis
+    for nx, ny, dx, dy, refused in K.SHAPE_CHECKS:
+        try:
+            M.hierarchy(nx, ny, dx, dy)
+            got = False
+        except M.UnsupportedGrid as e:
+            got = True
+            print('%dx%d dx/dy %.4g refused: %s' % (nx, ny, dx / dy, e))
+        assert got == refused, (nx, ny, dx / dy)
+
+
+@pytest.mark.parametrize('case', [c for c, _ in K.CASES], ids=[K.case_id(c) for c, _ in K.CASES])
+def test_mutations_move_one_cycle_past_the_f32_bound(case):
+    # each deliberately wrong operator moves p after one cycle by >= 10x the case's float32 bound for k = 1 (the float64 bound is 1e-11), so
+    # the GPU comparison would catch it in either type.  On one level only the coarsest solve runs, so only 'coarse_mode' applies there.
+    # Measured here: post_order 2.7e-2 .. 6.0e-2, prolong_row 1.8e-3 .. 3.2e-2, restrict_scale 2.0 .. 1.4e4, coarse_mode 8.1e-5 .. 1.2e-2
+    # (single level 7.2e-2 .. 0.27): at least 54x the bound.
+    nx, ny, B, dx, dy = case
+    P, Cs = K.problem(case)
+    base, _, _ = M.solve_one(P[0], Cs[0], dx, dy, tol=0.0, max_cycles=1)
+    bound = K.BOUND_F32[K.path(nx, ny, 4), 1]
+    muts = M.MUTATIONS if K.path(nx, ny, 8) != 'single' else ('coarse_mode',)
+    moves = {m: rel_l2(M.solve_one(P[0], Cs[0], dx, dy, tol=0.0, max_cycles=1, mutate=m)[0], base) for m in muts}
+    print('%s (f32 bound %.1e): %s' % (K.case_id(case), bound, '  '.join('%s %.1e' % kv for kv in moves.items())))
+    for m, d in moves.items():
+        assert d >= 10 * bound, (m, d, bound)
+
+
+def test_non_finite_data_is_never_a_zero_residual():
+    nx = ny = 33
+    dx, dy = M.spacings(nx, ny)
+    p, C = M.random_problem(nx, ny, seed=6)
+    for name, (a, idx, val) in {'NaN in C': ('C', (16, 9), np.nan), 'Inf in C': ('C', (3, 4), np.inf),
+                                'NaN in the ring': ('p', (0, 7), np.nan), '-Inf inside': ('p', (20, 20), -np.inf)}.items():
+        pp, CC = p.copy(), C.copy()
+        (pp if a == 'p' else CC)[idx] = val
+        u, info, rn = M.solve_one(pp, CC, dx, dy)
+        assert info[0] == 0 and np.isnan(info[1]) and not np.isfinite(rn[0]), name
+        assert np.array_equal(u, pp, equal_nan=True), name
+    u, info, _ = M.solve_one(np.full_like(p, 0.25), np.zeros_like(C), dx, dy)       # a zero residual is still (0, 0)
+    assert info == (0, 0.0)
