@@ -178,9 +178,6 @@ __global__ __launch_bounds__(64) void predictor_adi_kernel(const T* __restrict__
 // agree BITWISE (test).
 // ------------------------------------------------------------------------------------------
 constexpr int kAdiLdsThreads = 512;
-#ifndef NNS_ADI_TIMING
-#define NNS_ADI_TIMING 0            // 1: predictor_adi_lds_kernel prints the cycles of its phases (workgroup 0, threads 0 and 448)
-#endif
 
 // x / den from rcp = RN(1 / den) (Markstein; see div_den in sor_device.h and tools/fastdiv_check.hip); rcp = 0 or an operand out of the safe
 // range: the plain division
@@ -299,15 +296,9 @@ __global__ __launch_bounds__(kAdiLdsThreads) void predictor_adi_lds_kernel(const
     constexpr int UG = 4;                           // points per thread and round of the global-memory phases: their loads are in flight together
                                                     // (one point per round left every round waiting for its own loads: 16 x ~1000 cycles per phase)
     auto inner = [&](int c) { const int i = c / ny, j = c - i * ny; return i >= 1 && i <= nx - 2 && j >= 1 && j <= ny - 2; };
-#if NNS_ADI_TIMING
-    long tq[8]; tq[0] = clock64();
-#endif
     // the factorisations, one lane each, while everyone else starts on the right-hand sides
     if (tid == 0) adi_tables<T>(k.a_diag, lo, up, nx, tab, tab + nx, tab + 2 * nx);
     if (tid == kWave && !FIRST_ONLY) adi_tables<T>(k.b_diag, lo, up, nx, tab + 3 * nx, tab + 4 * nx, tab + 5 * nx);
-#if NNS_ADI_TIMING
-    tq[1] = clock64();
-#endif
     // ---- first solve: A ut = (2/nu dx^2) (dt/2 (3H - H1) + dt nu lap f)        (:126-137)
     for (int e0 = tid; e0 < 2 * n; e0 += UG * kAdiLdsThreads) {
         T v[UG];
@@ -320,17 +311,11 @@ __global__ __launch_bounds__(kAdiLdsThreads) void predictor_adi_lds_kernel(const
         for (int u = 0; u < UG; ++u) { const int e = e0 + u * kAdiLdsThreads; if (e < 2 * n) F[e] = v[u]; }
     }
     __syncthreads();
-#if NNS_ADI_TIMING
-    tq[2] = clock64();
-#endif
     for (int q = tid; q < 2 * (ny - 2); q += kAdiLdsThreads) {
         const int fl = q >= ny - 2, j = 1 + q - fl * (ny - 2);
         adi_column<T>(F + fl * n, j, nx, ny, up, tab, tab + nx, tab + 2 * nx);
     }
     __syncthreads();
-#if NNS_ADI_TIMING
-    tq[3] = clock64();
-#endif
     if (FIRST_ONLY) {                                                  // ut / vt to `work`: the corrected variant's second solve runs along axis 1
         T* ft = work + (size_t)blockIdx.x * 2 * n;
         for (int e = tid; e < 2 * n; e += kAdiLdsThreads) {
@@ -356,17 +341,11 @@ __global__ __launch_bounds__(kAdiLdsThreads) void predictor_adi_lds_kernel(const
         }
     }
     __syncthreads();
-#if NNS_ADI_TIMING
-    tq[4] = clock64();
-#endif
     for (int q = tid; q < 2 * (ny - 2); q += kAdiLdsThreads) {
         const int fl = q >= ny - 2, j = 1 + q - fl * (ny - 2);
         adi_column<T>(F + fl * n, j, nx, ny, up, tab + 3 * nx, tab + 4 * nx, tab + 5 * nx);
     }
     __syncthreads();
-#if NNS_ADI_TIMING
-    tq[5] = clock64();
-#endif
     for (int e0 = tid; e0 < 2 * n; e0 += UG * kAdiLdsThreads) {
         T fv[UG];
 #pragma unroll
@@ -377,10 +356,6 @@ __global__ __launch_bounds__(kAdiLdsThreads) void predictor_adi_lds_kernel(const
             if (e < 2 * n) { const int fl = e >= n, c = e - fl * n; ((fl ? vi : ui) + base)[c] = inner(c) ? F[e] : fv[u]; }     // ui = u.copy() on the edges
         }
     }
-#if NNS_ADI_TIMING
-    __syncthreads(); tq[6] = clock64();
-    if ((tid == 0 || tid == 448) && blockIdx.x == 0) printf("adi lds, thread %d (cycles): tables %ld, rhs1 / load %ld, solve 1 %ld, rhs2 %ld, solve 2 %ld, write %ld\n", tid, tq[1] - tq[0], tq[2] - tq[1], tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4], tq[6] - tq[5]);
-#endif
 }
 
 inline size_t adi_lds_bytes(int nx, int ny, size_t elem) { return (2 * (size_t)nx * ny + 6 * (size_t)nx) * elem; }

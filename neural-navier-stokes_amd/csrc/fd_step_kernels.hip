@@ -17,9 +17,6 @@ using namespace nns::sorlex;
 
 namespace {
 
-#ifndef NNS_STEP_TIMING
-#define NNS_STEP_TIMING 0           // 1: the kernel prints the cycles of its phases (workgroup 0)
-#endif
 
 template <typename T>
 struct StepK { PredK<T> pred; T cu, cv, cx, cy; SorK<T> sor; };
@@ -44,38 +41,20 @@ __global__ __launch_bounds__(kSorThreads) void fd_step_explicit_kernel(const T* 
     T* cl = pl + n;
     T* ui = UV_LDS ? cl + n : u_out + base;
     T* vi = UV_LDS ? cl + 2 * n : v_out + base;
-#if NNS_STEP_TIMING
-    long tq[7]; tq[0] = clock64();
-#endif
     // 1. predictor (:63-91), then the velocity boundary lists (:219-220)
     for (int c = tid; c < n; c += kSorThreads) predictor_explicit_point<T, CORRECT>(un, vn, un1, vn1, ui, vi, c / ny, c % ny, nx, ny, k.pred);
     __syncthreads();
-#if NNS_STEP_TIMING
-    tq[1] = clock64();
-#endif
     bc_apply_list<T>(ui, nx, ny, ubc, tid, kSorThreads);
     bc_apply_list<T>(vi, nx, ny, vbc, tid, kSorThreads);
-#if NNS_STEP_TIMING
-    tq[2] = clock64();
-#endif
     // 2. right-hand side (:186-188) and p into LDS; the solve (:183-200)
     for (int c = tid; c < n; c += kSorThreads) { cl[c] = pressure_rhs_point<T>(ui, vi, c / ny, c % ny, nx, ny, k.cu, k.cv); pl[c] = pg[c]; }
     __syncthreads();
-#if NNS_STEP_TIMING
-    tq[3] = clock64();
-#endif
     int done;
     T err;
     const int expect = hint ? (int)hint[2 * blockIdx.x] : 0;          // (before info is written: the two may be one buffer)
     sor_solve<T, true>(pl, cl, snap + base, nx, ny, max_sweeps, expect, k.sor, errs, s_stop_p, done, err);
-#if NNS_STEP_TIMING
-    tq[4] = clock64();
-#endif
     // 3. the pressure boundary list (:222) on the LDS copy; p out; correction (:204-210)
     bc_apply_list<T>(pl, nx, ny, pbc, tid, kSorThreads);
-#if NNS_STEP_TIMING
-    tq[5] = clock64();
-#endif
     T* pc = p_copy ? p_copy + base : nullptr;
     for (int c = tid; c < n; c += kSorThreads) {
         const T pv = pl[c];
@@ -83,10 +62,6 @@ __global__ __launch_bounds__(kSorThreads) void fd_step_explicit_kernel(const T* 
         if (pc) pc[c] = pv;
         correction_point<T>(ui, vi, pl, ny, u_out + base, v_out + base, c / ny, c % ny, nx, ny, k.cx, k.cy);
     }
-#if NNS_STEP_TIMING
-    __syncthreads(); tq[6] = clock64();
-    if (tid == 0 && blockIdx.x == 0) printf("fused step (cycles): predictor %ld, velocity bcs %ld, rhs + p load %ld, solve %ld (%d sweeps), pressure bcs %ld, write + correction %ld\n", tq[1] - tq[0], tq[2] - tq[1], tq[3] - tq[2], tq[4] - tq[3], done, tq[5] - tq[4], tq[6] - tq[5]);
-#endif
     if (tid == 0) { info[2 * blockIdx.x] = (T)done; info[2 * blockIdx.x + 1] = err; }
 }
 

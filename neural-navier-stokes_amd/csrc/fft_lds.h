@@ -24,10 +24,6 @@
 #include <type_traits>
 #include "nns_common.h"
 
-#ifndef NNS_DFT_SB
-#define NNS_DFT_SB 1      // scheduling barriers between the dft4 groups of a float64 dft16 (bounds register pressure)
-#endif
-
 namespace nns {
 
 template <typename T> struct C2 { T x, y; };
@@ -81,7 +77,7 @@ __device__ __forceinline__ void dft16(C2<T> (&x)[16]) {
 #pragma unroll
     for (int n2 = 0; n2 < 4; ++n2) {
         dft4<T, INV>(x[n2], x[4 + n2], x[8 + n2], x[12 + n2]);   // k1 at x[4*k1+n2]
-        if constexpr (sizeof(T) == 8 && NNS_DFT_SB) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (sizeof(T) == 8) __builtin_amdgcn_sched_barrier(0);      // float64: bounds the register pressure of the four groups
     }
     // x[4*k1 + n2] *= W16^{n2*k1}
     x[5] = mulw<T, INV>(x[5], c1, s1);      // 1
@@ -96,7 +92,7 @@ __device__ __forceinline__ void dft16(C2<T> (&x)[16]) {
 #pragma unroll
     for (int k1 = 0; k1 < 4; ++k1) {
         dft4<T, INV>(x[4 * k1], x[4 * k1 + 1], x[4 * k1 + 2], x[4 * k1 + 3]);  // k2 at x[4*k1+k2]
-        if constexpr (sizeof(T) == 8 && NNS_DFT_SB) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (sizeof(T) == 8) __builtin_amdgcn_sched_barrier(0);
     }
     // y[k1 + 4*k2] = x[4*k1 + k2]: 4x4 transpose
 #pragma unroll
@@ -153,18 +149,12 @@ __device__ __forceinline__ void fft_pass(C2<T> (&x)[16], const C2<T>* __restrict
         C2<T> y[R];
 #pragma unroll
         for (int t = 0; t < R; ++t) y[t] = x[q + NB * t];
-#ifndef NNS_F32_PIN
-#define NNS_F32_PIN 1      // pin float32 pass-2 table reads in groups of 4 (limits hoisting)
-#endif
-#ifndef NNS_TW_LOOKUP
-#define NNS_TW_LOOKUP 0      // 0: float64 twiddles by running product from one table read; 1: grouped table reads
-#endif
         if constexpr (NS == 16) {
             // second pass: twiddle W_N^{t * c * N/(16 R)}, c = j mod 16, from the pass-2 table laid out [t][c]:
             // for a given t the lanes of a wave read 16 CONSECUTIVE entries (conflict-free, broadcast across
             // the lane groups that share c); striding the main table by t*c*N/(16R) was up to 16-way conflicted.
             int c = (int)(j & 15u);
-            if constexpr (sizeof(T) == 8 && !NNS_TW_LOOKUP) {
+            if constexpr (sizeof(T) == 8) {
                 // float64: ONE table read, the other R-2 twiddles by running product (14 roundings of 1e-16 are
                 // irrelevant, and 15 hoisted double2 reads would cost 60 VGPRs).  Grouped table reads (pinned
                 // three at a time) save 56 fp64 ops per pass but measured slower on MI355X (A/B on one box).
@@ -177,9 +167,8 @@ __device__ __forceinline__ void fft_pass(C2<T> (&x)[16], const C2<T>* __restrict
             } else {
 #pragma unroll
                 for (int t = 1; t < R; ++t) {
-                    // table reads pinned in groups (3 for float64, 4 for float32) so they are not all hoisted
-                    if constexpr (sizeof(T) == 8) { if (t % 3 == 1) asm volatile("" : "+v"(c), "+v"(y[t].x)); }
-                    else if (NNS_F32_PIN) { if (t % 4 == 1) asm volatile("" : "+v"(c), "+v"(y[t].x)); }
+                    // float32: table reads pinned in groups of 4 so they are not all hoisted
+                    if (t % 4 == 1) asm volatile("" : "+v"(c), "+v"(y[t].x));
                     C2<T> w = tab2[16 * t + c];
                     if constexpr (INV) w.y = -w.y;
                     y[t] = cmul<T>(y[t], w);
@@ -187,7 +176,7 @@ __device__ __forceinline__ void fft_pass(C2<T> (&x)[16], const C2<T>* __restrict
             }
         } else if constexpr (NS > 1) {
             int jm = (int)((j & (unsigned)(NS - 1)) * (unsigned)(N / (NS * R)));
-            if constexpr (sizeof(T) == 8 && !NNS_TW_LOOKUP) {
+            if constexpr (sizeof(T) == 8) {
                 const C2<T> w = twiddle<T, N, INV>(tab, jm);
                 C2<T> wt = w;
                 y[1] = cmul<T>(y[1], wt);
@@ -195,10 +184,7 @@ __device__ __forceinline__ void fft_pass(C2<T> (&x)[16], const C2<T>* __restrict
                 for (int t = 2; t < R; ++t) { wt = cmul<T>(wt, w); y[t] = cmul<T>(y[t], wt); }
             } else {
 #pragma unroll
-                for (int t = 1; t < R; ++t) {
-                    if constexpr (sizeof(T) == 8) { if (t % 3 == 1) asm volatile("" : "+v"(jm), "+v"(y[t].x)); }
-                    y[t] = cmul<T>(y[t], twiddle<T, N, INV>(tab, t * jm));
-                }
+                for (int t = 1; t < R; ++t) y[t] = cmul<T>(y[t], twiddle<T, N, INV>(tab, t * jm));
             }
         }
         dftR<T, R, INV>(y);

@@ -74,7 +74,7 @@ __device__ __forceinline__ void mma_batched(const float* A, int lda, const float
     };
     // FOUR accumulator chains per wave (k-steps dealt round-robin to NSPLIT partial sums per tile): a dependent v_mfma_f32_16x16x4_f32 issues
     // ~64 cycles after the one it waits for, not 32 -- with two chains one MLP evaluation of a 16-row tile took 9700 cycles for 3100 of MFMA
-    // (s_memtime, NNS_BWD_TIMING)
+    // (in-kernel cycle stamps)
     constexpr int NSPLIT = 4 / NTILE;
     f32x4 part[NTILE][NSPLIT];
 #pragma unroll
@@ -229,12 +229,6 @@ __global__ __launch_bounds__(NT) void ode_mlp_fwd_kernel(const float* __restrict
 // layer is a broadcast read of the activation vector from LDS + an FMA chain per thread, 4 small barriers per evaluation, and batch
 // rows run on different CUs.  Plain float32 FMAs (the sum order differs from the MFMA tile's; both are float32 dot products).
 // ------------------------------------------------------------------------------------------
-#ifndef NNS_BWD_TIMING
-#define NNS_BWD_TIMING 0             // 1: ode_mlp_bwd_kernel prints the cycles of its phases for the last time step of workgroup 0 (s_memtime)
-#endif
-#ifndef NNS_ROW_TIMING
-#define NNS_ROW_TIMING 0             // 1: the row kernel prints the cycles of one evaluation's four phases (s_memtime)
-#endif
 constexpr int RT = 256;            // threads per row workgroup: one wave per SIMD
 // (Round 4, measured and not kept: EIGHT waves -- a quarter row per thread, the quarters of an output in four adjacent lanes meeting in two DPP adds, two waves
 // per SIMD: 324 us per 100 RK4 steps against 296 for this kernel, same box: the three barriers per evaluation get dearer, the shorter FMA chains buy less.)
@@ -284,15 +278,8 @@ __global__ __launch_bounds__(RT) void ode_mlp_fwd_row_kernel(const float* __rest
     };
     // LDS-only barrier: __syncthreads() also waits for the trajectory store of the step before to be acknowledged (vmcnt(0)), ~1 us per RK step
     auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-#if NNS_ROW_TIMING
-    long tq[5] = {0, 0, 0, 0, 0};
-#endif
     for (int it = 0; it < Nt; ++it) {
         for (int s = 0; s < nstage; ++s) {
-#if NNS_ROW_TIMING
-            const bool timed = it == 50 && s == 1;
-            if (timed) tq[0] = clock64();
-#endif
             {   // layer 1: K -> 128, ReLU
                 f2 a0 = {bias0, 0.f}, a1 = {0.f, 0.f};
                 const float* x = S + KP / 2 * half;
@@ -310,9 +297,6 @@ __global__ __launch_bounds__(RT) void ode_mlp_fwd_row_kernel(const float* __rest
                 if (half == 0) h1[n] = fmaxf(z, 0.f);
             }
             lds_barrier();
-#if NNS_ROW_TIMING
-            if (timed) tq[1] = clock64();
-#endif
             {   // layer 2: 128 -> 128, ELU(alpha = 1); four independent chains
                 f2 a[4] = {f2{bias1, 0.f}, f2{0.f, 0.f}, f2{0.f, 0.f}, f2{0.f, 0.f}};
                 const float* x = h1 + H / 2 * half;
@@ -335,9 +319,6 @@ __global__ __launch_bounds__(RT) void ode_mlp_fwd_row_kernel(const float* __rest
                 if (half == 0) h2[n] = elu1(z);
             }
             lds_barrier();
-#if NNS_ROW_TIMING
-            if (timed) tq[2] = clock64();
-#endif
             {   // layer 3: 128 -> K, an eighth of the inputs per lane; then F and the scheme's update of coefficient n3 (scheme.py:21-42)
                 f2 a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
                 const float* x = h2 + 16 * g3;
@@ -372,14 +353,8 @@ __global__ __launch_bounds__(RT) void ode_mlp_fwd_row_kernel(const float* __rest
                 }
             }
             lds_barrier();
-#if NNS_ROW_TIMING
-            if (timed) tq[4] = clock64();
-#endif
         }
     }
-#if NNS_ROW_TIMING
-    if (t == 0 && row == 0) printf("row kernel evaluation: layer1 %ld, layer2 %ld, layer3 + update %ld clk\n", (long)(tq[1] - tq[0]), (long)(tq[2] - tq[1]), (long)(tq[4] - tq[2]));
-#endif
 }
 
 // ------------------------------------------------------------------------------------------
@@ -399,9 +374,6 @@ __global__ __launch_bounds__(NT) void ode_mlp_bwd_kernel(const float* __restrict
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float* lds = reinterpret_cast<float*>(smem_raw);
     const int tid = threadIdx.x, wave = tid / kWave, lane = tid % kWave;
-#if NNS_BWD_TIMING
-    long tq[6] = {0, 0, 0, 0, 0, 0}; tq[0] = clock64();
-#endif
     MlpLds m;
     load_mlp(m, lds, W0, b0, W1, b1, W2, b2, K, tid);
     float* BA = carve(lds, TB * HS); float* BB = carve(lds, TB * HS); float* BC = carve(lds, TB * HS);
@@ -426,9 +398,6 @@ __global__ __launch_bounds__(NT) void ode_mlp_bwd_kernel(const float* __restrict
 
     for (int e = tid; e < TB * KS; e += NT) A[e] = 0.f;
     __syncthreads();
-#if NNS_BWD_TIMING
-    tq[1] = clock64();
-#endif
 
     for (int n = Nt - 1; n >= 0; --n) {
         // adjoint of y_{n+1} += grad of output n; y_n = z0 (n == 0) or states[n-1]
@@ -440,18 +409,9 @@ __global__ __launch_bounds__(NT) void ode_mlp_bwd_kernel(const float* __restrict
             Y[e] = y; S[e] = y;
         }
         __syncthreads();
-#if NNS_BWD_TIMING
-        if (n == Nt - 1) tq[2] = clock64();
-#endif
         // ---- recompute the stages, saving stage inputs and activations
         for (int s = 0; s < nstage; ++s) {
-#if NNS_BWD_TIMING
-            long te0 = clock64();
-#endif
             mlp_eval(m, S, BA, BB, F, wave, lane);
-#if NNS_BWD_TIMING
-            if (n == Nt - 1 && s == 1) tq[5] = clock64() - te0;
-#endif
             float* w = ws + (size_t)s * kStageFloats;
             for (int e = tid; e < TB * KS; e += NT) w[e] = S[e];
             for (int e = tid; e < TB * HS; e += NT) { w[TB * KS + e] = BA[e]; w[TB * KS + TB * HS + e] = BB[e]; }
@@ -463,9 +423,6 @@ __global__ __launch_bounds__(NT) void ode_mlp_bwd_kernel(const float* __restrict
             }
             __syncthreads();
         }
-#if NNS_BWD_TIMING
-        if (n == Nt - 1) tq[3] = clock64();
-#endif
         // ---- output adjoints of the stage increments k_s
         for (int e = tid; e < TB * KS; e += NT) {
             const float a = A[e];
@@ -544,18 +501,12 @@ __global__ __launch_bounds__(NT) void ode_mlp_bwd_kernel(const float* __restrict
         }
         for (int e = tid; e < TB * KS; e += NT) A[e] = GY[e];
         __syncthreads();
-#if NNS_BWD_TIMING
-        if (n == Nt - 1) tq[4] = clock64();
-#endif
     }
     // ---- results: grad z0, and the weight/bias gradients (atomics: several batch tiles may contribute)
     for (int e = tid; e < TB * KS; e += NT) {
         const int b = e / KS, k = e % KS;
         if (row0 + b < mb && k < K) gz0[(size_t)(row0 + b) * K + k] = A[e];
     }
-#if NNS_BWD_TIMING
-    if (blockIdx.x == 0 && tid == 0) printf("ode bwd tile: weights to LDS %ld, first loads %ld, 4 stages forward %ld, 4 stages backward %ld clk (want_pg %d); one mlp_eval %ld\n", (long)(tq[1] - tq[0]), (long)(tq[2] - tq[1]), (long)(tq[3] - tq[2]), (long)(tq[4] - tq[3]), (int)want_pg, tq[5]);
-#endif
     if (!want_pg) return;
     const int c = lane & 15, r0 = 4 * (lane >> 4);
 #pragma unroll
@@ -753,36 +704,29 @@ __global__ __launch_bounds__(256) void basis_loss_kernel(const float* __restrict
 //     top level -- 16 of the 31 exchange steps -- is v_permlane16_swap_b32 (one VALU instruction swaps the odd / even
 //     16-lane rows of two registers in place) instead of two selects and a ds_bpermute per step; the lower levels are
 //     DPP moves.  (Inline asm: this ROCm's __builtin_amdgcn_permlane{16,32}_swap returns the same register for both
-//     results.)  NNS_PK_PART = 64 selects the 64-value butterfly over all lanes (v_permlane32_swap on top): it needs
-//     254+ registers and measured slower (one wave per SIMD or spills).
+//     results.)  (A 64-value butterfly over all lanes, v_permlane32_swap on top, was tried: it needs
+//     254+ registers and measured slower -- one wave per SIMD or spills.)
 // BASELINE config 5 (T = 8192, K = 10, 3 x 256^2): loss backward 4.34 -> 2.92 ms, forward 1.59 -> 1.26 ms.
 // ------------------------------------------------------------------------------------------------------------------
 typedef float v2f __attribute__((ext_vector_type(2)));
-#ifndef NNS_PK_PART
-#define NNS_PK_PART 32               // values per butterfly: 64 (all lanes, TT = 64 / KMAX rows) or 32 (per 32-lane half)
-#endif
-constexpr int kPart64 = NNS_PK_PART;
+constexpr int kPkPart = 32;          // values per butterfly (one per 32-lane half, 32 / KMAX rows)
 
 // Four independent register pairs per asm block.  A VALU write of an operand within the two preceding issue slots is a
 // hazard for these instructions and the compiler does not see inside the block: one leading s_nop 1 covers all four.
-#define NNS_SWAP4(INSN)                                                                                              \
+#define SWAP4(INSN)                                                                                                  \
     asm volatile("s_nop 1\n\t" INSN " %0, %1\n\t" INSN " %2, %3\n\t" INSN " %4, %5\n\t" INSN " %6, %7"               \
                  : "+v"(a0), "+v"(b0), "+v"(a1), "+v"(b1), "+v"(a2), "+v"(b2), "+v"(a3), "+v"(b3))
-__device__ __forceinline__ void swap_halves4(float& a0, float& b0, float& a1, float& b1, float& a2, float& b2, float& a3, float& b3) {
-    NNS_SWAP4("v_permlane32_swap_b32");                                     // a.hi <-> b.lo  (32-lane halves)
-}
 __device__ __forceinline__ void swap_rows4(float& a0, float& b0, float& a1, float& b1, float& a2, float& b2, float& a3, float& b3) {
-    NNS_SWAP4("v_permlane16_swap_b32");                                     // a's odd 16-lane rows <-> b's even rows
+    SWAP4("v_permlane16_swap_b32");                                         // a's odd 16-lane rows <-> b's even rows
 }
-#undef NNS_SWAP4
+#undef SWAP4
 // values [0, 2M) -> [0, M): a lane keeps the half whose index bit matches its lane bit and adds its partner's copy
 template <int M>
-__device__ __forceinline__ void halve64(float (&part)[kPart64], int lane) {
-    if constexpr (M == 32 || M == 16) {
+__device__ __forceinline__ void halve_part(float (&part)[kPkPart], int lane) {
+    if constexpr (M == 16) {
 #pragma unroll
         for (int e = 0; e < M; e += 4) {
-            if constexpr (M == 32) swap_halves4(part[e], part[e + M], part[e + 1], part[e + 1 + M], part[e + 2], part[e + 2 + M], part[e + 3], part[e + 3 + M]);
-            else swap_rows4(part[e], part[e + M], part[e + 1], part[e + 1 + M], part[e + 2], part[e + 2 + M], part[e + 3], part[e + 3 + M]);
+            swap_rows4(part[e], part[e + M], part[e + 1], part[e + 1 + M], part[e + 2], part[e + 2 + M], part[e + 3], part[e + 3 + M]);
 #pragma unroll
             for (int i = 0; i < 4; ++i) part[e + i] += part[e + i + M];
         }
@@ -810,21 +754,13 @@ __device__ __forceinline__ void halve64(float (&part)[kPart64], int lane) {
 // time rows per group: TT1 = rows whose gcoeff partials fill one butterfly (gradient modes); the loss has no butterfly and
 // takes TT0 = 2 TT1 rows (<= 8) per group -- the group is also the depth of the observation prefetch
 template <int KMAX> struct PkGeom {
-    static constexpr int TT1 = (kPart64 / KMAX) < 8 ? (kPart64 / KMAX) : 8;
+    static constexpr int TT1 = (kPkPart / KMAX) < 8 ? (kPkPart / KMAX) : 8;
     static constexpr int TT0 = 2 * TT1 < 8 ? 2 * TT1 : 8;
 };
-inline int pk_rows_per_group(int kmax) { const int t1 = (kPart64 / kmax) < 8 ? (kPart64 / kmax) : 8; return 2 * t1 < 8 ? 2 * t1 : 8; }
+inline int pk_rows_per_group(int kmax) { const int t1 = (kPkPart / kmax) < 8 ? (kPkPart / kmax) : 8; return 2 * t1 < 8 ? 2 * t1 : 8; }
 
-#ifndef NNS_PK_WAVES
-#define NNS_PK_WAVES 0              // >0: __attribute__((amdgpu_waves_per_eu(N, N))) for A/B runs; 0 = let the allocator decide
-#endif
-#if NNS_PK_WAVES
-#define NNS_PK_ATTR __attribute__((amdgpu_waves_per_eu(NNS_PK_WAVES, NNS_PK_WAVES)))
-#else
-#define NNS_PK_ATTR
-#endif
 template <int MODE, int KMAX>
-__global__ __launch_bounds__(256) NNS_PK_ATTR void basis_loss_pk_kernel(const float* __restrict__ coeff, const float* __restrict__ basis,
+__global__ __launch_bounds__(256) void basis_loss_pk_kernel(const float* __restrict__ coeff, const float* __restrict__ basis,
                                                             const float* __restrict__ obs, double* __restrict__ sumsq,
                                                             float* __restrict__ gcoeff, float* __restrict__ gbasis, float scale,
                                                             int T, int K, int C, int P, int TC, int rows_per_split, int nsplit) {
@@ -860,17 +796,16 @@ __global__ __launch_bounds__(256) NNS_PK_ATTR void basis_loss_pk_kernel(const fl
         }
     }
     double local = 0.0;
-    float part[kPart64];
+    float part[kPkPart];
 #pragma unroll
-    for (int e = 0; e < kPart64; ++e) part[e] = 0.f;
+    for (int e = 0; e < kPkPart; ++e) part[e] = 0.f;
     auto flush_part = [&](int t_first) {
-        if constexpr (kPart64 == 64) halve64<32>(part, lane);
-        halve64<16>(part, lane); halve64<8>(part, lane);
-        halve64<4>(part, lane); halve64<2>(part, lane); halve64<1>(part, lane);
-        const int v = lane % kPart64, tt = v / KMAX, k = v % KMAX;     // lane l holds the total of value l mod kPart64 = tt * KMAX + k
+        halve_part<16>(part, lane); halve_part<8>(part, lane);
+        halve_part<4>(part, lane); halve_part<2>(part, lane); halve_part<1>(part, lane);
+        const int v = lane % kPkPart, tt = v / KMAX, k = v % KMAX;     // lane l holds the total of value l mod kPkPart = tt * KMAX + k
         if (tt < RB && k < K && t_first + tt < t_hi) atomicAdd(&gcoeff[((size_t)(t_first + tt) * K + k) * C + c], part[0]);
 #pragma unroll
-        for (int e = 0; e < kPart64; ++e) part[e] = 0.f;
+        for (int e = 0; e < kPkPart; ++e) part[e] = 0.f;
     };
     for (int t0 = t_lo; t0 < t_hi; t0 += TC) {
         const int tn = min(TC, t_hi - t0);
@@ -1002,9 +937,6 @@ __global__ __launch_bounds__(256) NNS_PK_ATTR void basis_loss_pk_kernel(const fl
 // waves' tiles are summed and leave in one burst of global atomics (2.5 wave-instructions per 16 rows x 256 pixels).  Registers: ~100 (4 waves per SIMD), the observations of the next time block are in flight while
 // the current one is multiplied.
 // ------------------------------------------------------------------------------------------------------------------
-#ifndef NNS_MF_EXP
-#define NNS_MF_EXP 0               // timing experiments (wrong results): 1 no observation loads, 2 no coefficient-gradient part, 3 no LDS accumulation
-#endif
 // gcoeff is accumulated with atomics (always), gbasis too when the time rows are split over workgroups: zeroed in ONE launch
 inline int zero_grads(float* gcoeff, float* gbasis, int nsplit, int T, int K, int C, int P, hipStream_t s) {
     void* const bufs[2] = {gcoeff, gbasis};
@@ -1012,19 +944,8 @@ inline int zero_grads(float* gcoeff, float* gbasis, int nsplit, int T, int K, in
     return zero_buffers(bufs, bytes, 2, s);
 }
 constexpr int kMfNPT = 4;                                   // pixel tiles (of 16) per wave
-#ifndef NNS_MF_WAVES
-#define NNS_MF_WAVES 3             // waves per SIMD the register allocation is held to (0: the allocator decides -- 2 at K = 10, no spills)
-#endif
-#if NNS_MF_WAVES
-#define NNS_MF_ATTR __attribute__((amdgpu_waves_per_eu(NNS_MF_WAVES, NNS_MF_WAVES)))
-#else
-#define NNS_MF_ATTR
-#endif
 constexpr int kMfTCMax = 176;                               // time rows per chunk at most (11 blocks of 16)
-#ifndef NNS_MF_SWZ
-#define NNS_MF_SWZ 0               // 1: the 16 x 16 tiles (coefficient blocks, the transposing tile) are XOR-swizzled, 0: rows padded to 20 floats (rounds 2-3)
-#endif
-// A 16 x 16 float tile is touched two ways: an instruction covers rows {r, 4 + r, 8 + r, 12 + r} x all columns ([4 lg + r][lj]), or all rows x
+// A 16 x 16 float tile (coefficient blocks, the transposing tile), rows padded to 20 floats, is touched two ways: an instruction covers rows {r, 4 + r, 8 + r, 12 + r} x all columns ([4 lg + r][lj]), or all rows x
 // columns {4 s .. 4 s + 3} ([lj][4 s + lg]).  ds_read/write_b32 serve a wave as two 32-lane halves on 32 banks.  Padded to 20 floats per row the
 // first pattern is conflict-free, but in the second rows lj and lj + 8 are 160 floats = 5 x 32 banks apart: every such read takes two passes
 // (26-29 % of the kernel's LDS cycles are bank conflicts: profiles/r03_mfma_pmc_final.csv).  Round 4 built the conflict-free form VERDICT r3 asked
@@ -1033,13 +954,14 @@ constexpr int kMfTCMax = 176;                               // time rows per chu
 // keys differ in bits 1..3 -- and MEASURED it (profiles/r04_ab_c5_swizzle.txt, same box, three rounds): conflicts 29 % -> 1.6 % of LDS-active
 // cycles, LDS-active cycles 2.13e8 -> 1.53e8 per launch, sweep 1.690 -> 1.713 ms.  The LDS was never the limit (24 % busy): the sweep is bound by
 // the issue of its 44 dependent float32 MFMAs per 4 KB (matrix pipe 0.60 busy, 58 % of wave-cycles stalled at issue), and the swizzle's index
-// arithmetic costs what the shorter reads save.  Kept behind the macro, off.
-__device__ __forceinline__ int mf_tile(int t, int p) { return NNS_MF_SWZ ? 16 * (t ^ ((t >> 2) & 1)) + (p ^ (t & 14)) : t * 20 + p; }
-constexpr int kMfCwLd = NNS_MF_SWZ ? 16 : 20;               // floats per tile row
+// arithmetic costs what the shorter reads save.  Not kept.
+constexpr int kMfCwLd = 20;                                 // floats per tile row
+__device__ __forceinline__ int mf_tile(int t, int p) { return t * kMfCwLd + p; }
 // MODE as in basis_loss_pk_kernel: 1 = gradients of scale * (pred - obs), 2 = gradients for the upstream gradient passed as `obs`
 // (no prediction), 3 = sum of squares AND the unscaled gradients.
 template <int KQ, int MODE>
-__global__ __launch_bounds__(256) NNS_MF_ATTR void basis_loss_mfma_kernel(const float* __restrict__ coeff, const float* __restrict__ basis,
+// (three waves per SIMD: left to itself the register allocation takes two at K = 10, no spills either way)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void basis_loss_mfma_kernel(const float* __restrict__ coeff, const float* __restrict__ basis,
                                                               const float* __restrict__ obs, double* __restrict__ sumsq,
                                                               float* __restrict__ gcoeff, float* __restrict__ gbasis, float scale,
                                                               int T, int K, int C, int P, int TC, int rows_per_split, int nsplit) {
@@ -1111,7 +1033,8 @@ __global__ __launch_bounds__(256) NNS_MF_ATTR void basis_loss_mfma_kernel(const 
         for (int r = 0; r < 4; ++r) {
             const int tt = 16 * b + 4 * lg + r;
             const size_t row = ((size_t)(t0x + (tt < tnx ? tt : tnx - 1)) * C + c) * P;
-            on[r] = (NNS_MF_EXP == 1) ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(&obs[row + pcl]);
+            const float4 o4 = *reinterpret_cast<const float4*>(&obs[row + pcl]);
+            on[r] = o4;
         }
     };
     for (int e = tid; e < TC * LD; e += 256) cw[e] = 0.f;                         // columns >= KM stay zero for the whole kernel
@@ -1166,7 +1089,6 @@ __global__ __launch_bounds__(256) NNS_MF_ATTR void basis_loss_mfma_kernel(const 
                 // gbasis: padding rows have w = 0, out-of-range pixels are never stored -- no mask on g
 #pragma unroll
                 for (int s = 0; s < 4; ++s) gb[i] = mfma4(AwT[s], g[s], gb[i]);
-                if (NNS_MF_EXP == 2) continue;
                 // gcoeff: g with t on the lanes, through the transposing tile (rows = t, columns = pix)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) gt[mf_tile(4 * lg + r, lj)] = g[r];
@@ -1183,7 +1105,7 @@ __global__ __launch_bounds__(256) NNS_MF_ATTR void basis_loss_mfma_kernel(const 
             // this wave's tile of this time block is parked in LDS (plain stores, no barrier: the waves run free inside a chunk;
             // ds_add_f32 into one shared tile measured 1.4 ms of the kernel's 3.0)
             float* ga = gacc + (size_t)(b * 4 + wave) * 16 * LDG;
-            if (NNS_MF_EXP != 3 && lj < LDG)
+            if (lj < LDG)
 #pragma unroll
             for (int r = 0; r < 4; ++r) ga[(4 * lg + r) * LDG + lj] = gc[r];
         }
@@ -1247,17 +1169,17 @@ inline LossGeom loss_geom(int T, int K, int C, int P) {
 template <int MODE>
 void launch_loss(const LossGeom& g, hipStream_t s, const float* coeff, const float* basis, const float* obs, double* sumsq, float* gcoeff,
                  float* gbasis, float scale, int T, int K, int C, int P) {
-#define NNS_PK(KM) hipLaunchKernelGGL((basis_loss_pk_kernel<MODE, KM>), g.grid, dim3(256), g.lds, s, coeff, basis, obs, sumsq, gcoeff, gbasis, scale, T, K, C, P, g.TC, g.rows_per_split, g.nsplit)
+#define PK_LAUNCH(KM) hipLaunchKernelGGL((basis_loss_pk_kernel<MODE, KM>), g.grid, dim3(256), g.lds, s, coeff, basis, obs, sumsq, gcoeff, gbasis, scale, T, K, C, P, g.TC, g.rows_per_split, g.nsplit)
     switch (g.kmax) {
-        case 4: NNS_PK(4); break;
-        case 8: NNS_PK(8); break;
-        case 10: NNS_PK(10); break;
-        case 12: NNS_PK(12); break;
-        case 16: NNS_PK(16); break;
+        case 4: PK_LAUNCH(4); break;
+        case 8: PK_LAUNCH(8); break;
+        case 10: PK_LAUNCH(10); break;
+        case 12: PK_LAUNCH(12); break;
+        case 16: PK_LAUNCH(16); break;
         default:
             hipLaunchKernelGGL((basis_loss_kernel<MODE, 1, kMaxK>), g.grid, dim3(256), g.lds, s, coeff, basis, obs, sumsq, gcoeff, gbasis, scale, T, K, C, P, g.TC, g.rows_per_split, g.nsplit);
     }
-#undef NNS_PK
+#undef PK_LAUNCH
 }
 
 }  // namespace
@@ -1471,15 +1393,12 @@ NNS_API int nns_basis_loss_fwd_f32(const float* coeff, const float* basis, const
 }
 
 // g = scale * (pred - obs) (scale = upstream / loss).  gcoeff [T][K][C] is zeroed here and accumulated with atomics; gbasis is overwritten.
-#ifndef NNS_LOSS_MFMA
-#define NNS_LOSS_MFMA 1            // 1: basis_loss_mfma_kernel for K <= 16 (P a multiple of 4, 16-byte aligned fields); 0: the packed-FMA kernel
-#endif
 // Returns 1 when the shape is not the matrix-core kernel's (the caller falls back to the packed-FMA kernel), else the launch's status.
 template <int MODE>
 int launch_loss_mfma(const float* coeff, const float* basis, const float* obs, double* sumsq, float* gcoeff, float* gbasis, float scale,
                      int T, int K, int C, int P, hipStream_t s, const char* what) {
     const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-    if (!(NNS_LOSS_MFMA && K <= 16 && P % 4 == 0 && al16(basis) && al16(obs) && al16(gbasis))) return 1;
+    if (!(K <= 16 && P % 4 == 0 && al16(basis) && al16(obs) && al16(gbasis))) return 1;
     // pixel strips of 256 per workgroup; the time axis is split until ~8 workgroups per CU exist (3 run at once), whole 16-row blocks each
     const int bx = (P + 255) / 256;
     int ns = (2048 + bx * C - 1) / (bx * C);
@@ -1497,9 +1416,9 @@ int launch_loss_mfma(const float* coeff, const float* basis, const float* obs, d
     const size_t lds = ((size_t)TC * kMfCwLd + 4 * 16 * kMfCwLd + (size_t)(TC / 16) * 4 * 16 * ldg) * sizeof(float);
     if (int rc = zero_grads(gcoeff, gbasis, ns, T, K, C, P, s); rc != NNS_OK) return rc;
     const dim3 grid(bx, C, ns);
-#define NNS_MF(KQ) hipLaunchKernelGGL((basis_loss_mfma_kernel<KQ, MODE>), grid, dim3(256), lds, s, coeff, basis, obs, sumsq, gcoeff, gbasis, scale, T, K, C, P, TC, rps, ns)
-    if (K <= 4) NNS_MF(1); else if (K <= 8) NNS_MF(2); else if (K <= 12) NNS_MF(3); else NNS_MF(4);
-#undef NNS_MF
+#define MF_LAUNCH(KQ) hipLaunchKernelGGL((basis_loss_mfma_kernel<KQ, MODE>), grid, dim3(256), lds, s, coeff, basis, obs, sumsq, gcoeff, gbasis, scale, T, K, C, P, TC, rps, ns)
+    if (K <= 4) MF_LAUNCH(1); else if (K <= 8) MF_LAUNCH(2); else if (K <= 12) MF_LAUNCH(3); else MF_LAUNCH(4);
+#undef MF_LAUNCH
     return check_launch(what);
 }
 

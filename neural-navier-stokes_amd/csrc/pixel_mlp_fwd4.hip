@@ -27,10 +27,6 @@ __global__ __launch_bounds__(kP4Threads) __attribute__((amdgpu_waves_per_eu(1, 1
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     stage_uniform<OT>(d, W, Bv, lds, threadIdx.x, kP4Threads);
     __syncthreads();
-#ifndef NNS_P4_EXP
-#define NNS_P4_EXP 0               // timing probes (wrong results): 1 = weights staged, nothing else; 2 = no layers (inputs in, accumulators = bias out); 3 = first and last layer only
-#endif
-    if (NNS_P4_EXP == 1) return;
     const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave, r = lane & 31, h = lane >> 5;
     const int nl = d.nlayers, cin0 = d.cin[0], coutL = d.cout[nl - 1];       // cin0, coutL <= 4 (checked on the host)
     const long ngroups = (npix_total + 32 * NT - 1) / (32 * NT);
@@ -147,11 +143,10 @@ __global__ __launch_bounds__(kP4Threads) __attribute__((amdgpu_waves_per_eu(1, 1
             });
         };
         using T_ = std::true_type; using F_ = std::false_type;
-        if (NNS_P4_EXP == 2) {}
-        else if (nl == 1) layer(0, T_{}, T_{});
+        if (nl == 1) layer(0, T_{}, T_{});
         else {
             layer(0, T_{}, F_{});
-            if (NNS_P4_EXP != 3) for (int l = 1; l + 1 < nl; ++l) layer(l, F_{}, F_{});
+            for (int l = 1; l + 1 < nl; ++l) layer(l, F_{}, F_{});
             layer(nl - 1, F_{}, T_{});
         }
 #pragma unroll

@@ -58,15 +58,9 @@ __device__ void stage_weights(const PixelMlpDesc& d, const float* __restrict__ W
 // Round 3, same-box A/B at depth 8 / width 64 / 16 x 512^2 (profiles/r03_ab_pixel_mlp_fwd.log): 256 threads 0.374 ms, 384 threads 0.43 ms, 512 threads
 // 0.355 ms (one staging of the weights per eight waves); requesting the weight fragments 2 or 4 ahead instead of 1: no change (0.372 / 0.376) --
 // the fragment latency is not what keeps the matrix pipe at 34 % busy.
-#ifndef NNS_PM_THREADS
-#define NNS_PM_THREADS 512
-#endif
-constexpr int kFwdThreads = NNS_PM_THREADS, kFwdWaves = kFwdThreads / 64;
+constexpr int kFwdThreads = 512, kFwdWaves = kFwdThreads / 64;
 
-#ifndef NNS_PM_GEN_THREADS
-#define NNS_PM_GEN_THREADS 512
-#endif
-constexpr int kGenThreads = NNS_PM_GEN_THREADS, kGenWaves = kGenThreads / 64;      // the runtime-shaped (float32) kernel: its weights fill LDS, so ONE workgroup per CU -- eight waves of it
+constexpr int kGenThreads = 512, kGenWaves = kGenThreads / 64;      // the runtime-shaped (float32) kernel: its weights fill LDS, so ONE workgroup per CU -- eight waves of it
 
 template <bool BF16>
 __global__ __launch_bounds__(kGenThreads) void pixel_mlp_fwd_kernel(const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ Bv,
@@ -207,10 +201,6 @@ __global__ __launch_bounds__(kFwdThreads) __attribute__((amdgpu_waves_per_eu(2, 
     const long ngroups = (npix_total + 32 * kPT - 1) / (32 * kPT);
     const long gstride = (long)gridDim.x * kFwdWaves;
     const unsigned char* bias0 = lds + nl * U::W_BYTES;
-#ifndef NNS_PM_STAGGER
-#define NNS_PM_STAGGER 0           // s_sleep argument (64-cycle units) for the second half of the workgroup's waves, once, before the tile loop
-#endif
-    if (NNS_PM_STAGGER && wave >= kFwdWaves / 2) __builtin_amdgcn_s_sleep(NNS_PM_STAGGER);
     // input pixels of group g as bf16 operand fragments (zero beyond cin0 / the last pixel)
     auto load_group = [&](long g, bf16x8 (&f)[kPT][SS]) {
 #pragma unroll
@@ -238,10 +228,9 @@ __global__ __launch_bounds__(kFwdThreads) __attribute__((amdgpu_waves_per_eu(2, 
                 for (int i = 0; i < 16; ++i) bn[ot][i] = bl[32 * ot + acc_row(i, h)];
         };
         fetch_bias(0);
-#ifndef NNS_PM_PF
-#define NNS_PM_PF 1                // weight fragments requested ahead of use (1, 2 or 4): the fragments of all layers are one contiguous stream in LDS
-#endif
-        constexpr int NF = OT * SS, PF = (NNS_PM_PF <= NF && NF % NNS_PM_PF == 0) ? NNS_PM_PF : 1;      // the queue is indexed at compile time
+        // weight fragments requested ahead of use (the fragments of all layers are one contiguous stream in LDS; the queue is indexed at compile
+        // time): 2 or 4 ahead measured no change, see above
+        constexpr int NF = OT * SS, PF = 1;
         const int nfr = nl * NF;
         bf16x8 q[PF];
 #pragma unroll
@@ -254,19 +243,13 @@ __global__ __launch_bounds__(kFwdThreads) __attribute__((amdgpu_waves_per_eu(2, 
                 int nn = l * NF + idx + PF;
                 nn = nn < nfr ? nn : nfr - 1;
                 q[idx % PF] = wl0[nn * 64];
-#ifndef NNS_PM_EXP
-#define NNS_PM_EXP 0               // timing probes (wrong results): 1 = no accumulator -> operand conversion between layers, 2 = no MFMAs, 3 = no bias reads
-#endif
 #pragma unroll
-                for (int pt = 0; pt < kPT; ++pt) {
-                    if (NNS_PM_EXP == 2) { asm volatile("" :: "v"(w), "v"(fr[pt][s2])); if (s2 == 0) acc[pt][ot] = bn[ot]; }
-                    else acc[pt][ot] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, fr[pt][s2], s2 == 0 ? bn[ot] : acc[pt][ot], 0, 0, 0);
-                }
+                for (int pt = 0; pt < kPT; ++pt) acc[pt][ot] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, fr[pt][s2], s2 == 0 ? bn[ot] : acc[pt][ot], 0, 0, 0);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);        // one LDS read (fragment n + PF) ...
                 __builtin_amdgcn_sched_group_barrier(0x008, kPT, 0);      // ... ahead of the MFMAs of fragment n
             }
-            if (l + 1 < nl && NNS_PM_EXP != 1) {
-                if (NNS_PM_EXP != 3) fetch_bias(l + 1);
+            if (l + 1 < nl) {
+                fetch_bias(l + 1);
 #pragma unroll
                 for (int pt = 0; pt < kPT; ++pt)
 #pragma unroll
@@ -281,9 +264,6 @@ __global__ __launch_bounds__(kFwdThreads) __attribute__((amdgpu_waves_per_eu(2, 
     }
 }
 
-#ifndef NNS_PM_PIPE
-#define NNS_PM_PIPE 1              // widths 33..64 with <= 4 channels in and out: 1 = pixel_mlp_fwd_pipe4_kernel (pixel_mlp_fwd4.hip), 0 = pixel_mlp_fwd_uniform_kernel<2, true>
-#endif
 template <int OT, bool SMALLIO>
 int launch_fwd_uniform(const float* x, const float* weights, const float* biases, float* y, long npix, int P, const PixelMlpDesc& d, hipStream_t s) {
     const int lds = UniLds<OT>::total(d.nlayers);
@@ -292,7 +272,7 @@ int launch_fwd_uniform(const float* x, const float* weights, const float* biases
     if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "pixel_mlp_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
     const long ngroups = (npix + 32 * kPT - 1) / (32 * kPT);
     // persistent: one generation of workgroups (2 per CU fit by LDS), so the weights are staged once per workgroup
-    const long cap = kFwdThreads > 256 ? 256 : 512;          // workgroups resident at once (8-wave workgroups: one per CU by registers)
+    const long cap = 256;                                    // workgroups resident at once (8-wave workgroups: one per CU by registers)
     long blocks = (ngroups + kFwdWaves - 1) / kFwdWaves; if (blocks > cap) blocks = cap;
     hipLaunchKernelGGL((pixel_mlp_fwd_uniform_kernel<OT, SMALLIO>), dim3((unsigned)blocks), dim3(kFwdThreads), lds, s, x, weights, biases, y, npix, P, d);
     return check_launch("pixel_mlp_fwd");
@@ -328,43 +308,33 @@ int launch_fwd_uniform(const float* x, const float* weights, const float* biases
 // 34-dword spacing -- rows q and q + 2 overlap on 12 of their 16 banks -- so EVERY (b) and (d) read took two LDS passes: 28 % of the
 // kernel's LDS-active cycles were bank conflicts (profiles/r03_mfma_pmc_final.csv) with the LDS 64 % busy.  Now an image is cut into
 // SUB-IMAGES of 16 columns, [column block][row][32 bytes]:
-//     byte(sub, row, slot) = sub * SUB + 32 row + 16 (row >> 3) + 8 (slot ^ ((row >> 2) & 1)),     slot = the 8-byte piece 0..3 of the row
+//     byte(sub, row, slot) = sub * SUB + 32 row + 8 (2 ((slot & 1) ^ row bit 2 ^ row bit 3) + (slot >> 1)),     slot = the 8-byte piece 0..3 of the row
 //   * a transposing read's four rows are 128 contiguous bytes, and the half's second 16-lane group reads the NEXT sub-image, SUB = 32 dwords
 //     (mod 64) further: 64 distinct banks;
-//   * 16 consecutive rows at one slot -- (a) and (c) -- hit 16 distinct bank pairs: 4 (row & 3) from the 32-byte rows, the XOR with row
-//     bit 2 and the 16-byte pad per 8 rows supply the other two bits;
-//   * every compile-time quantity (k-step, output tile, first / second piece, layer) stays an IMMEDIATE offset on one lane address.
-// tools/lds_banks.py replays the four patterns under the hardware's bank rules (old layout: 4 LDS cycles per transposing read, new: 2).
-//
-// NNS_PM_LAYOUT = 2 (second step of round 4): the two 8-byte pieces a forward fragment takes from a row (slots h and 2 + h) sit NEXT to each
-// other, so that (a) is ONE ds_read_b128 (4 LDS cycles per KB) instead of a ds_read2_b64 (8) and (c) one 16-byte store:
-//     byte(sub, row, slot) = sub * SUB + 32 row + 8 (2 ((slot & 1) ^ row bit 2 ^ row bit 3) + (slot >> 1)),        no pad rows
-// The 16-lane groups of a 16-byte read are non-contiguous ({0-3, 12-15, 20-27}, ...): rows 8 apart must differ in their 16-byte half -- row
-// bit 3 in the XOR -- and 8 consecutive rows of a 16-byte store need row bit 2 in it.  In a transposing read row bit 3 is the compile-time
-// "second read" bit, so its XOR cannot be an immediate: such reads keep TWO lane addresses (base, base ^ 16) -- one register more.
-#ifndef NNS_PM_LAYOUT
-#define NNS_PM_LAYOUT 2
-#endif
+//   * the two 8-byte pieces a forward fragment takes from a row (slots h and 2 + h) sit NEXT to each other, so that (a) is ONE ds_read_b128
+//     (4 LDS cycles per KB) instead of a ds_read2_b64 (8) and (c) one 16-byte store.  The 16-lane groups of a 16-byte read are non-contiguous
+//     ({0-3, 12-15, 20-27}, ...): rows 8 apart must differ in their 16-byte half -- row bit 3 in the XOR -- and 8 consecutive rows of a 16-byte
+//     store need row bit 2 in it.  In a transposing read row bit 3 is the compile-time "second read" bit, so its XOR cannot be an immediate:
+//     such reads keep TWO lane addresses (base, base ^ 16) -- one register more;
+//   * every other compile-time quantity (k-step, output tile, first / second piece, layer) stays an IMMEDIATE offset on one lane address.
+// tools/lds_banks.py replays the four patterns under the hardware's bank rules (rounds 2-3: 4 LDS cycles per transposing read, now: 2).
 template <int OT>
 struct BwdLds {
     static constexpr int SS = 2 * OT, CH = 32 * OT;
     static constexpr int NSUB = 2 * OT;                            // 16-column sub-images per image
     static constexpr int sub_bytes(int nrows) {
-        const int b = nrows * 32 + (NNS_PM_LAYOUT == 2 ? 0 : (nrows / 8) * 16);
+        const int b = nrows * 32;
         return b + ((32 - (b / 4) % 64 + 64) % 64) * 4;           // consecutive sub-images 32 banks apart
     }
     static constexpr int W_SUB = sub_bytes(CH), IMG_SUB = sub_bytes(128);
     static constexpr int W_BYTES = NSUB * W_SUB;
     static constexpr int B_BYTES = CH * 4;
     static constexpr int IMG_BYTES = NSUB * IMG_SUB;
-#ifndef NNS_PM_IMGSETS
-#define NNS_PM_IMGSETS 2                                       // 2: the images are double-buffered over the layers (one barrier per layer)
-#endif
-    __host__ __device__ static int total(int nl) { return nl * (W_BYTES + B_BYTES) + NNS_PM_IMGSETS * 2 * IMG_BYTES; }
+    // (two image sets: the images are double-buffered over the layers, one barrier per layer)
+    __host__ __device__ static int total(int nl) { return nl * (W_BYTES + B_BYTES) + 2 * 2 * IMG_BYTES; }
     // byte offset of the 8-byte piece `slot` of row `row` inside one sub-image
     __host__ __device__ static constexpr int piece(int row, int slot) {
-        if (NNS_PM_LAYOUT == 2) return 32 * row + 8 * (2 * ((slot & 1) ^ ((row >> 2) & 1) ^ ((row >> 3) & 1)) + (slot >> 1));
-        return 32 * row + 16 * (row >> 3) + 8 * (slot ^ ((row >> 2) & 1));
+        return 32 * row + 8 * (2 * ((slot & 1) ^ ((row >> 2) & 1) ^ ((row >> 3) & 1)) + (slot >> 1));
     }
     // weight element (row = out, col = in) of a layer's image
     __host__ __device__ static constexpr int w_elem(int row, int col) { return (col >> 4) * W_SUB + piece(row, (col & 15) >> 2) + 2 * (col & 3); }
@@ -377,27 +347,21 @@ __device__ __forceinline__ bf16x8 join8(bf16x4 lo, bf16x4 hi) {
 }
 
 // A fragment of the forward product: rows 32 ot + r of the weight image, k-step s (columns 16 s ..: sub-image s); lane half h takes the
-// pieces h and 2 + h of the row (channels 16 s + 4 h + 0..3 and 16 s + 8 + 4 h + 0..3: the accumulator-as-operand k order).  One ds_read2_b64.
+// pieces h and 2 + h of the row (channels 16 s + 4 h + 0..3 and 16 s + 8 + 4 h + 0..3: the accumulator-as-operand k order).
 template <int OT>
 __device__ __forceinline__ bf16x8 frag_w(const unsigned char* wimg, int r, int h, int ot, int s) {
     using U = BwdLds<OT>;
-    if constexpr (NNS_PM_LAYOUT == 2) {
-        const unsigned char* a = wimg + (32 * r + 16 * (h ^ ((r >> 2) & 1) ^ ((r >> 3) & 1))) + (s * U::W_SUB + ot * (32 * 32));
-        return *reinterpret_cast<const bf16x8*>(a);                               // pieces h and 2 + h, adjacent: one ds_read_b128
-    } else {
-    const unsigned char* a = wimg + (32 * r + 16 * (r >> 3) + 8 * (h ^ ((r >> 2) & 1))) + (s * U::W_SUB + ot * (32 * 32 + 4 * 16));
-    return join8(*reinterpret_cast<const bf16x4*>(a), *reinterpret_cast<const bf16x4*>(a + 16));
-    }
+    const unsigned char* a = wimg + (32 * r + 16 * (h ^ ((r >> 2) & 1) ^ ((r >> 3) & 1))) + (s * U::W_SUB + ot * (32 * 32));
+    return *reinterpret_cast<const bf16x8*>(a);                                   // pieces h and 2 + h, adjacent: one ds_read_b128
 }
 
 // The lane part of a transposing read's address (frag_t, frag_pix): lane 4q+p of a 16-lane group addresses row q, columns 4p..4p+3 of the
 // group's 4 x 16 block; the half's second group (lane bit 4) reads the next sub-image; lane half h' takes rows +4.
 template <int SUB>
-__device__ __forceinline__ int tr_lane(int lane, int second = 0) {
+__device__ __forceinline__ int tr_lane(int lane, int second) {
     const int gl = lane & 15, q = gl >> 2, pp = gl & 3, hp = lane >> 5;
-    if constexpr (NNS_PM_LAYOUT == 2)       // rows 4 hp + q (+ 8 for the second read: row bit 3 joins the XOR): piece pp at 2 ((pp & 1) ^ hp ^ second) + (pp >> 1)
-        return ((lane >> 4) & 1) * SUB + (4 * hp + q) * 32 + 8 * (2 * ((pp & 1) ^ hp ^ second) + (pp >> 1));
-    return ((lane >> 4) & 1) * SUB + (4 * hp + q) * 32 + 8 * (pp ^ hp);
+    // rows 4 hp + q (+ 8 for the second read: row bit 3 joins the XOR): piece pp at 2 ((pp & 1) ^ hp ^ second) + (pp >> 1)
+    return ((lane >> 4) & 1) * SUB + (4 * hp + q) * 32 + 8 * (2 * ((pp & 1) ^ hp ^ second) + (pp >> 1));
 }
 // Transposing fragment read: element j of lane (r, h) = M[16 s + 8 (j>>2) + 4 h + (j&3)][col_block + r] of a weight image (rows = out).
 // Lane i of a group receives column i of the four rows.  EXEC must be all ones here.
@@ -405,14 +369,9 @@ template <int OT>
 __device__ __forceinline__ bf16x8 frag_t(const unsigned char* img, int lane, int s, int col_block) {
     using U = BwdLds<OT>;
     using lds_v4 = __attribute__((address_space(3))) bf16x4;
-    if constexpr (NNS_PM_LAYOUT == 2) {
-        const int off = (col_block >> 4) * U::W_SUB + s * (16 * 32);
-        return join8(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(img + tr_lane<U::W_SUB>(lane, 0) + off)),
-                     __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(img + tr_lane<U::W_SUB>(lane, 1) + off + 8 * 32)));
-    } else {
-    const unsigned char* a0 = img + tr_lane<U::W_SUB>(lane) + ((col_block >> 4) * U::W_SUB + s * (16 * 32 + 2 * 16));
-    return join8(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(a0)), __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(a0 + (8 * 32 + 16))));
-    }
+    const int off = (col_block >> 4) * U::W_SUB + s * (16 * 32);
+    return join8(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(img + tr_lane<U::W_SUB>(lane, 0) + off)),
+                 __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(img + tr_lane<U::W_SUB>(lane, 1) + off + 8 * 32)));
 }
 
 // 8 pixels of channel ch_block + r from a [pix][ch] image for the contraction over pixels: element j of lane (r, h) = pixel
@@ -421,21 +380,15 @@ template <int OT>
 __device__ __forceinline__ bf16x8 frag_pix(const unsigned char* img, int lane, int s, int ch_block) {
     using U = BwdLds<OT>;
     using lds_v4 = __attribute__((address_space(3))) bf16x4;
-    if constexpr (NNS_PM_LAYOUT == 2) {
-        const int off = (ch_block >> 4) * U::IMG_SUB + s * (16 * 32);
-        return join8(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(img + tr_lane<U::IMG_SUB>(lane, 0) + off)),
-                     __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(img + tr_lane<U::IMG_SUB>(lane, 1) + off + 8 * 32)));
-    } else {
-    const unsigned char* a0 = img + tr_lane<U::IMG_SUB>(lane) + (ch_block >> 4) * U::IMG_SUB + s * (16 * 32 + 2 * 16);
-    return join8(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(a0)), __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(a0 + (8 * 32 + 16))));
-    }
+    const int off = (ch_block >> 4) * U::IMG_SUB + s * (16 * 32);
+    return join8(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(img + tr_lane<U::IMG_SUB>(lane, 0) + off)),
+                 __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(img + tr_lane<U::IMG_SUB>(lane, 1) + off + 8 * 32)));
 }
 // The lane part of the chain waves' image row stores: row 32 wave + r, piece h (+ 2 for the fragment's second half), sub-image = k-step
 template <int OT>
 __device__ __forceinline__ int img_row_lane(int wave, int r, int h) {
     const int row = 32 * wave + r;
-    if constexpr (NNS_PM_LAYOUT == 2) return 32 * row + 16 * (h ^ ((row >> 2) & 1) ^ ((row >> 3) & 1));     // the fragment's two pieces: 16 contiguous bytes
-    return 32 * row + 16 * (row >> 3) + 8 * (h ^ ((row >> 2) & 1));
+    return 32 * row + 16 * (h ^ ((row >> 2) & 1) ^ ((row >> 3) & 1));     // the fragment's two pieces: 16 contiguous bytes
 }
 
 template <int OT, bool SMALL>
@@ -465,172 +418,11 @@ __device__ __forceinline__ void load_acc(const float* __restrict__ gb, size_t P,
     }
 }
 
-template <int OT, bool SMALLIO>
-__global__ __launch_bounds__(256) void pixel_mlp_bwd_uniform_kernel(const float* __restrict__ x, const float* __restrict__ gy,
-                                                                     const float* __restrict__ W, const float* __restrict__ Bv,
-                                                                     float* __restrict__ gx, float* __restrict__ ws,
-                                                                     long npix_total, int P, PixelMlpDesc d, int nparams_w, int nparams) {
-    using U = BwdLds<OT>;
-    constexpr int SS = U::SS;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const int nl = d.nlayers;
-    {   // stage: zero everything (pads, images), then scatter the real matrices (coalesced reads)
-        const int total = U::total(nl);
-        for (int e = threadIdx.x; e < total / 16; e += 256) reinterpret_cast<uint4*>(lds)[e] = make_uint4(0u, 0u, 0u, 0u);
-        __syncthreads();
-        for (int l = 0; l < nl; ++l) {
-            const int cin = d.cin[l], cout = d.cout[l], n = cin * cout;
-            const float* Wl = W + d.woff[l];
-            unsigned char* dst = lds + l * U::W_BYTES;
-            int row = threadIdx.x / cin, k = threadIdx.x - row * cin;
-            const int drow = 256 / cin, dk = 256 - drow * cin;
-            for (int e = threadIdx.x; e < n; e += 256) {
-                *reinterpret_cast<unsigned short*>(dst + U::w_elem(row, k)) = f2bf(Wl[e]);
-                row += drow; k += dk;
-                if (k >= cin) { k -= cin; ++row; }
-            }
-            float* bl = reinterpret_cast<float*>(lds + nl * U::W_BYTES + l * U::B_BYTES);
-            for (int e = threadIdx.x; e < cout; e += 256) bl[e] = Bv[d.boff[l] + e];
-        }
-        __syncthreads();
-    }
-    const unsigned char* bias0 = lds + nl * U::W_BYTES;
-    unsigned char* img0 = lds + nl * (U::W_BYTES + U::B_BYTES);
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave, r = lane & 31, h = lane >> 5;
-    const int bo = OT == 2 ? wave >> 1 : 0, bi = OT == 2 ? wave & 1 : 0;       // this wave's gW block
-    constexpr int KS = OT == 2 ? 8 : 2;                                       // its k-steps (of 8 x 16 pixels)
-    const int ks0 = OT == 2 ? 0 : 2 * wave;
-    const bool do_gb = OT == 2 ? bi == 0 : true;
-    const int cin0 = d.cin[0], coutL = d.cout[nl - 1];
-
-    f32x16 gw[kMaxLayers];
-    float gbp[kMaxLayers];
-#pragma unroll
-    for (int l = 0; l < kMaxLayers; ++l) {
-        gbp[l] = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) gw[l][i] = 0.f;
-    }
-    const long nsuper = (npix_total + 127) / 128;
-    for (long sup = blockIdx.x; sup < nsuper; sup += gridDim.x) {
-        const long gp = sup * 128 + wave * 32 + r;
-        const bool ok = gp < npix_total;
-        const long gc = ok ? gp : npix_total - 1;
-        const long b = gc / P, p = gc % P;
-        // ---------------- forward: afrag[l] = input fragments of layer l
-        bf16x8 afrag[kMaxLayers][SS];
-        load_frags<SS, SMALLIO>(x + (size_t)b * cin0 * P + p, (size_t)P, cin0, ok, h, afrag[0]);
-#pragma unroll
-        for (int l = 0; l + 1 < kMaxLayers; ++l) {
-            if (l + 1 < nl) {
-                __builtin_amdgcn_sched_barrier(0);            // phase boundaries: keep fragment loads from being hoisted across
-                const unsigned char* wimg = lds + l * U::W_BYTES;
-                const float* bl = reinterpret_cast<const float*>(bias0 + l * U::B_BYTES);
-                f32x16 acc[OT];
-#pragma unroll
-                for (int ot = 0; ot < OT; ++ot) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) acc[ot][i] = bl[32 * ot + acc_row(i, h)];
-#pragma unroll
-                    for (int s = 0; s < SS; ++s) acc[ot] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_w<OT>(wimg, r, h, ot, s), afrag[l][s], acc[ot], 0, 0, 0);
-                }
-#pragma unroll
-                for (int s = 0; s < SS; ++s) afrag[l + 1][s] = pack8<true>(acc[s >> 1], 8 * (s & 1));
-            }
-        }
-        // ---------------- backward
-        bf16x8 dfrag[SS];
-        {
-            f32x16 dl[OT];
-            load_acc<OT, SMALLIO>(gy + (size_t)b * coutL * P + p, (size_t)P, coutL, ok, h, dl);
-#pragma unroll
-            for (int s = 0; s < SS; ++s) dfrag[s] = pack8<false>(dl[s >> 1], 8 * (s & 1));
-        }
-#pragma unroll
-        for (int l = kMaxLayers - 1; l >= 0; --l) {
-            if (l < nl) {
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned char* wimg = lds + l * U::W_BYTES;
-                // data chain first: its MFMAs run while the images are written
-                f32x16 nd[OT];
-#pragma unroll
-                for (int it = 0; it < OT; ++it) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) nd[it][i] = 0.f;
-#pragma unroll
-                    for (int s = 0; s < SS; ++s) nd[it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_t<OT>(wimg, lane, s, 32 * it), dfrag[s], nd[it], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                // Consecutive layers use alternate image sets: a wave may write layer l-1's images while slower waves still read
-                // layer l's, so a layer needs ONE workgroup barrier (write -> read), not two; the set of layer l+1 is free
-                // again because every wave passed this layer's barrier after reading it.  (One more barrier per super-tile.)
-                unsigned char* imgD = img0 + (NNS_PM_IMGSETS == 2 ? (l & 1) : 0) * 2 * U::IMG_BYTES;
-                unsigned char* imgA = imgD + U::IMG_BYTES;
-                {   // delta_l and a_{l-1} as bf16 rows [32 wave + r] of the images
-                    unsigned char* rowD = imgD + img_row_lane<OT>(wave, r, h);
-                    unsigned char* rowA = imgA + img_row_lane<OT>(wave, r, h);
-#pragma unroll
-                    for (int s = 0; s < SS; ++s) {
-                        // fragment elements 0..3 = channels 16 s + 4 h + (0..3): piece h of sub-image s; elements 4..7 = channels 16 s + 8 + 4 h + (0..3): piece 2 + h
-                        constexpr int P2 = NNS_PM_LAYOUT == 2 ? 8 : 16;          // byte distance of the fragment's second piece
-                        *reinterpret_cast<bf16x4*>(rowD + s * U::IMG_SUB) = __builtin_shufflevector(dfrag[s], dfrag[s], 0, 1, 2, 3);
-                        *reinterpret_cast<bf16x4*>(rowD + s * U::IMG_SUB + P2) = __builtin_shufflevector(dfrag[s], dfrag[s], 4, 5, 6, 7);
-                        *reinterpret_cast<bf16x4*>(rowA + s * U::IMG_SUB) = __builtin_shufflevector(afrag[l][s], afrag[l][s], 0, 1, 2, 3);
-                        *reinterpret_cast<bf16x4*>(rowA + s * U::IMG_SUB + P2) = __builtin_shufflevector(afrag[l][s], afrag[l][s], 4, 5, 6, 7);
-                    }
-                }
-                __syncthreads();
-#pragma unroll
-                for (int kk = 0; kk < KS; ++kk) {
-                    const bf16x8 fa = frag_pix<OT>(imgD, lane, ks0 + kk, 32 * bo);
-                    const bf16x8 fb = frag_pix<OT>(imgA, lane, ks0 + kk, 32 * bi);
-                    gw[l] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, gw[l], 0, 0, 0);
-                    if (kk & 1) __builtin_amdgcn_sched_barrier(0);
-                    if (do_gb) {
-                        const bf16x2v ones = {(__bf16)1.0f, (__bf16)1.0f};
-#pragma unroll
-                        for (int j = 0; j < 8; j += 2) {
-                            const unsigned pr = (unsigned)(unsigned short)fa[j] | ((unsigned)(unsigned short)fa[j + 1] << 16);
-                            gbp[l] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, pr), ones, gbp[l], false);
-                        }
-                    }
-                }
-                if (NNS_PM_IMGSETS != 2) __syncthreads();
-                if (l > 0) {
-                    // ReLU mask a_{l-1} != 0 (activations are >= 0), then the next layer's operand fragments
-#pragma unroll
-                    for (int s = 0; s < SS; ++s) dfrag[s] = pack8_masked(nd[s >> 1], 8 * (s & 1), afrag[l][s]);
-                } else if (ok) {
-                    store_acc<OT, SMALLIO>(gx + (size_t)b * cin0 * P + p, (size_t)P, cin0, h, nd);
-                }
-            }
-        }
-        if (NNS_PM_IMGSETS == 2) __syncthreads();          // the next super-tile's first layer may reuse the set layer 0 just read
-    }
-    // ---------------- partial gradients: workspace slice per workgroup (OT = 2) or per wave (OT = 1)
-    float* wsb = ws + (size_t)(OT == 2 ? blockIdx.x : blockIdx.x * 4 + wave) * nparams;
-#pragma unroll
-    for (int l = 0; l < kMaxLayers; ++l) {
-        if (l < nl) {
-            const int cin = d.cin[l], cout = d.cout[l];
-            const int in = 32 * bi + r;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int out = 32 * bo + acc_row(i, h);
-                if (out < cout && in < cin) wsb[d.woff[l] + out * cin + in] = gw[l][i];
-            }
-            if (do_gb) {
-                const float tot = gbp[l] + __shfl_xor(gbp[l], 32);
-                if (h == 0 && 32 * bo + r < cout) wsb[nparams_w + d.boff[l] + 32 * bo + r] = tot;
-            }
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------
-// The same backward with SPLIT ROLES (round 2): pixel_mlp_bwd_uniform_kernel serialises, in ONE wave per SIMD (455 registers), the
-// forward recompute, the data chain, the image writes, a barrier and the pixel contraction of the weight gradients -- 4500 cycles per
-// layer and tile against 770 of MFMA.  Here a workgroup has EIGHT waves, two per SIMD, each under 256 registers:
+// The backward with SPLIT ROLES (round 2).  Four waves per workgroup that each do all of the above serialise, in ONE wave per SIMD (455
+// registers), the forward recompute, the data chain, the image writes, a barrier and the pixel contraction of the weight gradients -- 4500
+// cycles per layer and tile against 770 of MFMA (that kernel, pixel_mlp_bwd_uniform_kernel, is in the history).  Here a workgroup has EIGHT
+// waves, two per SIMD, each under 256 registers:
 //   * four CHAIN waves (one 32-pixel tile each): forward recompute, data chain, delta_l / a_{l-1} images -- no weight-gradient
 //     accumulators (128 registers less);
 //   * four GRADIENT waves (one 32x32 block of every layer's gW each; OT = 1: a quarter of the pixels each): after the layer's barrier
@@ -640,35 +432,11 @@ __global__ __launch_bounds__(256) void pixel_mlp_bwd_uniform_kernel(const float*
 // before that barrier (layer l+1's).  The two role bodies are separate code paths (separate loops with matching barriers), so that the
 // register allocator sees two small live sets instead of their union.
 // ------------------------------------------------------------------------------------------------------------------
-#ifndef NNS_PMB_DEPTH
-#define NNS_PMB_DEPTH 4            // operand fragments in flight per MFMA stream of the split backward
-#endif
-constexpr int kBwdDepth = NNS_PMB_DEPTH;
-#ifndef NNS_PMB_TIMING
-#define NNS_PMB_TIMING 0           // 1: the two-tile kernel prints the cycles of one super-tile's forward and backward halves (wave 0 of workgroup 0)
-#endif
-#ifndef NNS_PMB_TIMING
-#define NNS_PMB_TIMING 0           // 1: the split backward prints the cycles of one super-tile's phases (s_memtime stamps in wave 0 of workgroup 0)
-#endif
-#ifndef NNS_PMB_PRIO
-#define NNS_PMB_PRIO 0
-#endif
-#ifndef NNS_PMB_ALT
-#define NNS_PMB_ALT 0              // 1: the data chain's MFMAs alternate between the two accumulators
-#endif
-constexpr bool kBwdAlt = NNS_PMB_ALT != 0;
-#ifndef NNS_PMB_OVERLAP
-#define NNS_PMB_OVERLAP 0          // bit 0 (forward recompute) / bit 1 (backward walk): the chain waves convert the FIRST output tile's accumulators (mask / pack,
-                                   // 4 - 8 vector instructions per MFMA gap) under the MFMAs of the second tile instead of after the layer's last MFMA (OT = 2 only).
-                                   // Round 4, same-box A/B (profiles/r04_ab_pixel_mlp_bwd.log): both 0.96 -> 1.04 ms -- the gap's issue slots are taken (2 LDS reads,
-                                   // a store pair and the MFMA's own 8 cycles), the conversion only stretches the MFMA loop
-#endif
-#ifndef NNS_PMB_EXP
-#define NNS_PMB_EXP 0              // timing probes of the split backward (wrong results): 1 = chain waves read no weight fragments from LDS, 2 = no per-layer barriers, 3 = no weight-gradient MFMAs,
-                                   // 4 = gradient waves only keep the barriers, 5 = no forward recompute, 6 = no image writes, 7 = no ReLU' mask
-#endif
-#define PMB(k) (((NNS_PMB_EXP) >> ((k) - 1)) & 1)     // probe k is bit k-1 of NNS_PMB_EXP, so that probes combine; 8 / 9: forward / backward conversion replaced by a register reinterpretation
-__device__ __forceinline__ bf16x8 raw8(const f32x16& a, int base) { const i32x4v r = {__builtin_bit_cast(int, a[base]), __builtin_bit_cast(int, a[base + 1]), __builtin_bit_cast(int, a[base + 2]), __builtin_bit_cast(int, a[base + 3])}; return __builtin_bit_cast(bf16x8, r); }
+constexpr int kBwdDepth = 4;       // operand fragments in flight per MFMA stream of the split backward
+// (Round 4, tried and slower, same-box A/B in profiles/r04_ab_pixel_mlp_bwd.log: the chain waves converting the FIRST output tile's accumulators
+// (mask / pack, 4 - 8 vector instructions per MFMA gap) under the MFMAs of the second tile instead of after the layer's last MFMA: 0.96 -> 1.04 ms in
+// the forward recompute and in the backward walk -- the gap's issue slots are taken (2 LDS reads, a store pair and the MFMA's own 8 cycles), the
+// conversion only stretches the MFMA loop.)
 // Staging of the split backward kernels: zero everything (pads, images), then scatter the real matrices (coalesced reads).  512 threads.
 template <int OT>
 __device__ __forceinline__ void bwd_stage(unsigned char* lds, const float* __restrict__ W, const float* __restrict__ Bv, const PixelMlpDesc& d) {
@@ -728,8 +496,7 @@ __device__ __forceinline__ void bwd_gradient_waves(unsigned char* img0, int wave
             if (l < nl) {
                 const unsigned char* imgD = img0 + (l & 1) * 2 * U::IMG_BYTES;
                 const unsigned char* imgA = imgD + U::IMG_BYTES;
-                if (!PMB(2)) __syncthreads();                      // layer l's images are written
-                if (PMB(4)) continue;
+                __syncthreads();                                   // layer l's images are written
                 // the operand fragments of k-step kk + GD are requested before the MFMA of k-step kk (round 3: an LDS read takes longer than
                 // one MFMA, so one step ahead still left every MFMA waiting)
                 constexpr int GD = KS < kBwdDepth ? KS : kBwdDepth;
@@ -744,7 +511,7 @@ __device__ __forceinline__ void bwd_gradient_waves(unsigned char* img0, int wave
 #pragma unroll
                     for (int kk = 0; kk < KS; ++kk) {
                         const bf16x8 fa = fa_r[kk % GD], fb = fb_r[kk % GD];
-                        if (!PMB(3)) gw[l] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, gw[l], 0, 0, 0);
+                        gw[l] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, gw[l], 0, 0, 0);
                         if (kk + GD < KS) { fa_r[kk % GD] = frag_pix<OT>(imgD, lane, ks0 + kk + GD, 32 * bo); fb_r[kk % GD] = frag_pix<OT>(imgA, lane, ks0 + kk + GD, 32 * bi); }
                         if (kk & 1) __builtin_amdgcn_sched_barrier(0);
                         if constexpr (with_gb) {
@@ -801,7 +568,6 @@ __global__ __launch_bounds__(512) void pixel_mlp_bwd_split_kernel(const float* _
         return;
     }
     // ================= chain waves =================
-    if (NNS_PMB_PRIO) __builtin_amdgcn_s_setprio(NNS_PMB_PRIO);                 // the chain is the critical path; the gradient waves fill its gaps
     const int cin0 = d.cin[0], coutL = d.cout[nl - 1];
     // this lane's pixel in a super-tile: in range?, batch entry, pixel within the field
     auto locate = [&](long sup_, bool& ok_, int& b_, int& p_) {
@@ -822,14 +588,7 @@ __global__ __launch_bounds__(512) void pixel_mlp_bwd_split_kernel(const float* _
     // super-tile's x before the backward walk.
     bool okn = false; int bn_ = 0, pn_ = 0; float xr[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (SMALLIO) { locate(blockIdx.x, okn, bn_, pn_); raw4(x + (size_t)bn_ * cin0 * P + pn_, cin0, xr); }
-#if NNS_PMB_TIMING
-    long tk[4] = {0, 0, 0, 0}, tbody = 0, tbar = 0;
-#endif
     for (long sup = blockIdx.x; sup < nsuper; sup += gridDim.x) {
-#if NNS_PMB_TIMING
-        const bool timed = sup == blockIdx.x + 3 * (long)gridDim.x;
-        if (timed) tk[0] = clock64();
-#endif
         bool ok; int b, p;
         if constexpr (SMALLIO) { ok = okn; b = bn_; p = pn_; } else locate(sup, ok, b, p);
         // ---------------- forward: afrag[l] = input fragments of layer l
@@ -860,31 +619,18 @@ __global__ __launch_bounds__(512) void pixel_mlp_bwd_split_kernel(const float* _
 #pragma unroll
         for (int l = 0; l + 1 < kMaxLayers; ++l) {
             if (l + 1 < nl) {
-                if (PMB(5)) {
-#pragma unroll
-                    for (int s = 0; s < SS; ++s) afrag[l + 1][s] = afrag[l][s];
-                    continue;
-                }
                 __builtin_amdgcn_sched_barrier(0);
                 const unsigned char* wimg = lds + l * U::W_BYTES;
                 const unsigned char* wnext = lds + (l + 2 < nl ? l + 1 : l) * U::W_BYTES;          // the next recomputed layer's image (clamped)
                 f32x16 (&acc)[OT] = accb[l & 1];                                                   // holds this layer's bias already
                 f32x16 (&accn)[OT] = accb[(l + 1) & 1];
-                i32x4v cv[2];                                                                      // NNS_PMB_OVERLAP: tile 0's two fragments, converted under tile 1's MFMAs
                 static_for<0, NM>([&](auto ic) {
                     constexpr int idx = decltype(ic)::value, ot = idx / SS, s2 = idx % SS, nx = idx + D;
-                    acc[ot] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(PMB(1) ? afrag[l][(s2 + 1) % SS] : wr[idx % D], afrag[l][s2], acc[ot], 0, 0, 0);
+                    acc[ot] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[idx % D], afrag[l][s2], acc[ot], 0, 0, 0);
                     if constexpr (nx < NM) wr[idx % D] = frag_w<OT>(wimg, r, h, nx / SS, nx % SS);
                     else wr[idx % D] = frag_w<OT>(wnext, r, h, (nx - NM) / SS, (nx - NM) % SS);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                              // a frag_w is one ds_read2_b64
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                              // a frag_w is one ds_read_b128 
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if constexpr ((NNS_PMB_OVERLAP & 1) && OT == 2 && idx >= SS && !PMB(8)) {
-                        // tile 0's accumulator is complete: a quarter of its conversion per MFMA of tile 1 (fragment (idx - SS) >> 1, its ints 2 q, 2 q + 1)
-                        constexpr int pc = idx - SS, fs = pc >> 1, q = pc & 1;
-                        cv[fs][2 * q] = pack2<true>(acc[0][8 * fs + 4 * q], acc[0][8 * fs + 4 * q + 1]);
-                        cv[fs][2 * q + 1] = pack2<true>(acc[0][8 * fs + 4 * q + 2], acc[0][8 * fs + 4 * q + 3]);
-                        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                    }
                 });
                 {   // the next layer's bias, requested under this layer's conversion (a read placed at its use is the youngest in the queue: lgkmcnt(0))
                     const float* bn = reinterpret_cast<const float*>(bias0 + (l + 2 < nl ? l + 1 : l) * U::B_BYTES);
@@ -895,15 +641,9 @@ __global__ __launch_bounds__(512) void pixel_mlp_bwd_split_kernel(const float* _
                     __builtin_amdgcn_sched_group_barrier(0x100, 4 * OT, 0);
                 }
 #pragma unroll
-                for (int s = 0; s < SS; ++s) {
-                    if ((NNS_PMB_OVERLAP & 1) && OT == 2 && !PMB(8) && s < 2) afrag[l + 1][s] = __builtin_bit_cast(bf16x8, cv[s]);
-                    else afrag[l + 1][s] = PMB(8) ? raw8(acc[s >> 1], 8 * (s & 1)) : pack8<true>(acc[s >> 1], 8 * (s & 1));
-                }
+                for (int s = 0; s < SS; ++s) afrag[l + 1][s] = pack8<true>(acc[s >> 1], 8 * (s & 1));
             }
         }
-#if NNS_PMB_TIMING
-        if (timed) tk[1] = clock64();
-#endif
         // ---------------- backward
         bf16x8 dfrag[SS];
         {
@@ -923,19 +663,12 @@ __global__ __launch_bounds__(512) void pixel_mlp_bwd_split_kernel(const float* _
 #pragma unroll
             for (int s = 0; s < SS; ++s) dfrag[s] = pack8<false>(dl[s >> 1], 8 * (s & 1));
         }
-#if NNS_PMB_TIMING
-        if (timed) tk[2] = clock64();
-#endif
         bf16x8 tr[D];
 #pragma unroll
-        for (int q = 0; q < D; ++q) tr[q] = frag_t<OT>(lds + (nl - 1) * U::W_BYTES, lane, kBwdAlt ? q / OT : q % SS, 32 * (kBwdAlt ? q % OT : q / SS));
+        for (int q = 0; q < D; ++q) tr[q] = frag_t<OT>(lds + (nl - 1) * U::W_BYTES, lane, q % SS, 32 * (q / SS));
 #pragma unroll
         for (int l = kMaxLayers - 1; l >= 0; --l) {
             if (l < nl) {
-#if NNS_PMB_TIMING
-                long tl0 = 0, tl1 = 0;
-                if (timed) tl0 = clock64();
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 const unsigned char* wimg = lds + l * U::W_BYTES;
                 f32x16 nd[OT];
@@ -949,55 +682,31 @@ __global__ __launch_bounds__(512) void pixel_mlp_bwd_split_kernel(const float* _
                 unsigned char* imgD = img0 + (l & 1) * 2 * U::IMG_BYTES;
                 unsigned char* rowD = imgD + img_row_lane<OT>(wave, r, h);
                 unsigned char* rowA = rowD + U::IMG_BYTES;
-                i32x4v dn[2];                                                                      // NNS_PMB_OVERLAP: the next delta's first two fragments (from nd[0])
-                constexpr bool kOvl = (NNS_PMB_OVERLAP & 2) && OT == 2 && !kBwdAlt && !PMB(7) && !PMB(9);
                 static_for<0, NM>([&](auto ic) {
-                    constexpr int idx = decltype(ic)::value, it = kBwdAlt ? idx % OT : idx / SS, s2 = kBwdAlt ? idx / OT : idx % SS, nx = idx + D;
-                    constexpr int nit = kBwdAlt ? nx % OT : (nx % NM) / SS, ns2 = kBwdAlt ? (nx % NM) / OT : nx % SS;
-                    nd[it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(PMB(1) ? dfrag[(s2 + 1) % SS] : tr[idx % D], dfrag[s2], nd[it], 0, 0, 0);
+                    constexpr int idx = decltype(ic)::value, it = idx / SS, s2 = idx % SS, nx = idx + D;
+                    constexpr int nit = (nx % NM) / SS, ns2 = nx % SS;
+                    nd[it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr[idx % D], dfrag[s2], nd[it], 0, 0, 0);
                     tr[idx % D] = frag_t<OT>(nx < NM ? wimg : wprev, lane, ns2, 32 * nit);
                     constexpr int per = 4 * SS / NM;                                                // 8-byte image stores per MFMA
-                    if (!PMB(6)) {
 #pragma unroll
-                        for (int j = 0; j < per; ++j) {
-                            const int k = idx * per + j, s = k >> 2;
-                            const bf16x8 src = (k & 2) ? afrag[l][s] : dfrag[s];
-                            unsigned char* row = (k & 2) ? rowA : rowD;
-                            *reinterpret_cast<bf16x4*>(row + s * U::IMG_SUB + (NNS_PM_LAYOUT == 2 ? 8 : 16) * (k & 1)) = (k & 1) ? __builtin_shufflevector(src, src, 4, 5, 6, 7) : __builtin_shufflevector(src, src, 0, 1, 2, 3);
-                        }
+                    for (int j = 0; j < per; ++j) {
+                        const int k = idx * per + j, s = k >> 2;
+                        const bf16x8 src = (k & 2) ? afrag[l][s] : dfrag[s];
+                        unsigned char* row = (k & 2) ? rowA : rowD;
+                        *reinterpret_cast<bf16x4*>(row + s * U::IMG_SUB + 8 * (k & 1)) = (k & 1) ? __builtin_shufflevector(src, src, 4, 5, 6, 7) : __builtin_shufflevector(src, src, 0, 1, 2, 3);
                     }
                     __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    if (!PMB(6)) __builtin_amdgcn_sched_group_barrier(0x200, per, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x200, per, 0);
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if constexpr (kOvl && idx >= SS) {
-                        // nd[0] is complete: a quarter of its mask / pack step per MFMA of nd[1] (the old delta fragments are still operands and
-                        // image rows of this layer: the new ones go to registers of their own)
-                        if (l > 0) {
-                            constexpr int pc = idx - SS, fs = pc >> 1, q = pc & 1;
-                            const i32x4v m = __builtin_bit_cast(i32x4v, afrag[l][fs]);
-                            dn[fs][2 * q] = mask2(pack2<false>(nd[0][8 * fs + 4 * q], nd[0][8 * fs + 4 * q + 1]), m[2 * q]);
-                            dn[fs][2 * q + 1] = mask2(pack2<false>(nd[0][8 * fs + 4 * q + 2], nd[0][8 * fs + 4 * q + 3]), m[2 * q + 1]);
-                            __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-                        }
-                    }
                 });
                 __builtin_amdgcn_sched_barrier(0);
                 // the mask / convert step does not need the barrier: it runs while the image stores drain and the other waves arrive
                 if (l > 0) {
 #pragma unroll
-                    for (int s = 0; s < SS; ++s) {
-                        if (kOvl && s < 2) dfrag[s] = __builtin_bit_cast(bf16x8, dn[s]);
-                        else dfrag[s] = PMB(9) ? raw8(nd[s >> 1], 8 * (s & 1)) : PMB(7) ? pack8<false>(nd[s >> 1], 8 * (s & 1)) : pack8_masked(nd[s >> 1], 8 * (s & 1), afrag[l][s]);
-                    }
+                    for (int s = 0; s < SS; ++s) dfrag[s] = pack8_masked(nd[s >> 1], 8 * (s & 1), afrag[l][s]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-#if NNS_PMB_TIMING
-                if (timed) { __builtin_amdgcn_s_waitcnt(0xc07f); tl1 = clock64(); tbody += tl1 - tl0; }
-#endif
-                if (!PMB(2)) __syncthreads();                          // layer l's images are written: over to the gradient waves
-#if NNS_PMB_TIMING
-                if (timed) tbar += clock64() - tl1;
-#endif
+                __syncthreads();                                       // layer l's images are written: over to the gradient waves
                 if (l == 0 && ok) {
                     store_acc<OT, SMALLIO>(gx + (size_t)b * cin0 * P + p, (size_t)P, cin0, h, nd);
                 }
@@ -1007,15 +716,7 @@ __global__ __launch_bounds__(512) void pixel_mlp_bwd_split_kernel(const float* _
         // read from (even), and its second ones are written after a barrier the gradient waves only reach once they are done with layer 0:
         // no barrier between super-tiles, the chain waves run ahead into the next forward recompute.  Odd nl: both layers share a set.
         if (nl & 1) __syncthreads();
-#if NNS_PMB_TIMING
-        if (timed) tk[3] = clock64();
-#endif
     }
-#if NNS_PMB_TIMING
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        printf("split backward, one super-tile of wave 0 (cycles): forward recompute %ld, gy convert %ld, backward walk %ld (MFMA loops + mask / convert %ld, barrier waits %ld), whole %ld\n",
-               (long)(tk[1] - tk[0]), (long)(tk[2] - tk[1]), (long)(tk[3] - tk[2]), tbody, tbar, (long)(tk[3] - tk[0]));
-#endif
 }
 
 // (Round 3 also built a TWO-TILE chain on v_mfma_f32_16x16x32_bf16 -- two 16-pixel tiles per chain wave so that one tile's conversion hides
@@ -1225,23 +926,15 @@ int launch_bwd_f32(const float* x, const float* gy, const float* weights, const 
 }
 
 template <int OT, bool SMALLIO>
-int launch_bwd_uniform(const float* x, const float* gy, const float* weights, const float* biases, float* gx, float* gW, float* gB,
+int launch_bwd_split(const float* x, const float* gy, const float* weights, const float* biases, float* gx, float* gW, float* gB,
                        long npix, int P, const PixelMlpDesc& d, int nparams_w, int nparams, float* ws, hipStream_t s) {
     const int lds = BwdLds<OT>::total(d.nlayers);
     if (lds > 160 * 1024) return fail(NNS_ERR_UNSUPPORTED, "pixel_mlp_bwd: needs %d B of LDS (> 160 KiB)", lds);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pixel_mlp_bwd_uniform_kernel<OT, SMALLIO>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pixel_mlp_bwd_split_kernel<OT, SMALLIO>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "pixel_mlp_bwd: hipFuncSetAttribute(%d B): %s", lds, hipGetErrorString(e));
     const long nsuper = (npix + 127) / 128;
     const int blocks = (int)(nsuper < kBwdMaxBlocks ? nsuper : kBwdMaxBlocks);
-#ifndef NNS_PM_SPLIT
-#define NNS_PM_SPLIT 1             // 1: pixel_mlp_bwd_split_kernel (4 chain waves + 4 gradient waves), 0: pixel_mlp_bwd_uniform_kernel
-#endif
-    if (NNS_PM_SPLIT && BwdLds<OT>::total(d.nlayers) == lds && NNS_PM_IMGSETS == 2) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(pixel_mlp_bwd_split_kernel<OT, SMALLIO>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "pixel_mlp_bwd: hipFuncSetAttribute(%d B): %s", lds, hipGetErrorString(e));
-        hipLaunchKernelGGL((pixel_mlp_bwd_split_kernel<OT, SMALLIO>), dim3(blocks), dim3(512), lds, s, x, gy, weights, biases, gx, ws, npix, P, d, nparams_w, nparams);
-    } else
-    hipLaunchKernelGGL((pixel_mlp_bwd_uniform_kernel<OT, SMALLIO>), dim3(blocks), dim3(256), lds, s, x, gy, weights, biases, gx, ws, npix, P, d, nparams_w, nparams);
+    hipLaunchKernelGGL((pixel_mlp_bwd_split_kernel<OT, SMALLIO>), dim3(blocks), dim3(512), lds, s, x, gy, weights, biases, gx, ws, npix, P, d, nparams_w, nparams);
     if (int rc = check_launch("pixel_mlp_bwd")) return rc;
     const int nslices = blocks * (OT == 2 ? 1 : 4);
     hipLaunchKernelGGL(pixel_mlp_reduce_kernel, dim3((nparams + kRedParams - 1) / kRedParams), dim3(kRedParts * kRedParams), 0, s, ws, gW, gB, nslices, nparams_w, nparams);
@@ -1290,7 +983,7 @@ NNS_API int nns_pixel_mlp_fwd_f32(const float* x, const float* weights, const fl
         for (int l = 0; l <= nlayers; ++l) maxw = widths_host[l] > maxw ? widths_host[l] : maxw;
         const bool small = widths_host[0] <= 4 && widths_host[nlayers] <= 4;          // (u, v, p)-sized input and output: straight-line tile I/O
         if (maxw <= 32) return small ? launch_fwd_uniform<1, true>(x, weights, biases, y, npix, P, d, s) : launch_fwd_uniform<1, false>(x, weights, biases, y, npix, P, d, s);
-        if (NNS_PM_PIPE && small) return launch_fwd_pipe4(x, weights, biases, y, npix, P, d, s);             // (generic I/O keeps the kernel above)
+        if (small) return launch_fwd_pipe4(x, weights, biases, y, npix, P, d, s);             // (generic I/O keeps the kernel above)
         return small ? launch_fwd_uniform<2, true>(x, weights, biases, y, npix, P, d, s) : launch_fwd_uniform<2, false>(x, weights, biases, y, npix, P, d, s);
     } else {
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(pixel_mlp_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -1329,8 +1022,8 @@ NNS_API int nns_pixel_mlp_bwd_f32(const float* x, const float* gy, const float* 
         return small ? launch_bwd_f32<true>(x, gy, weights, biases, gx, gW, gB, npix, P, d, nw, np, ws, s)
                      : launch_bwd_f32<false>(x, gy, weights, biases, gx, gW, gB, npix, P, d, nw, np, ws, s);
     if (maxw <= 32)
-        return small ? launch_bwd_uniform<1, true>(x, gy, weights, biases, gx, gW, gB, npix, P, d, nw, np, ws, s)
-                     : launch_bwd_uniform<1, false>(x, gy, weights, biases, gx, gW, gB, npix, P, d, nw, np, ws, s);
-    return small ? launch_bwd_uniform<2, true>(x, gy, weights, biases, gx, gW, gB, npix, P, d, nw, np, ws, s)
-                 : launch_bwd_uniform<2, false>(x, gy, weights, biases, gx, gW, gB, npix, P, d, nw, np, ws, s);
+        return small ? launch_bwd_split<1, true>(x, gy, weights, biases, gx, gW, gB, npix, P, d, nw, np, ws, s)
+                     : launch_bwd_split<1, false>(x, gy, weights, biases, gx, gW, gB, npix, P, d, nw, np, ws, s);
+    return small ? launch_bwd_split<2, true>(x, gy, weights, biases, gx, gW, gB, npix, P, d, nw, np, ws, s)
+                 : launch_bwd_split<2, false>(x, gy, weights, biases, gx, gW, gB, npix, P, d, nw, np, ws, s);
 }

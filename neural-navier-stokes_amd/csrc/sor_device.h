@@ -57,12 +57,6 @@ __device__ __forceinline__ void sor_batch(T* pw, const T* cw, int nx, int ny, in
 //     ones, those already open in sweep s + 16 the LOW ones -- complementary when the two are ny - 2 fronts apart -- so every lane computes a
 //     point in every step and 49 sweeps take 3 (ny - 2) + nfronts steps instead of 4 (nfronts + 45).
 // Same operations on the same operands in the same order as sor_batch: bitwise the same p, errs and sweep count (tools/sor_ab.py).
-#ifndef NNS_SOR_ROWS
-#define NNS_SOR_ROWS 1
-#endif
-#ifndef NNS_SOR_TIMING
-#define NNS_SOR_TIMING 0            // 1: the row-per-lane pipeline prints the cycles of a step's parts (s_memtime stamps, waves 0 and 7)
-#endif
 constexpr int kSorLag = 3;
 
 __device__ __forceinline__ float lane_before(float x) {       // lane l <- lane l - 1 (wave rotate right by one)
@@ -84,21 +78,14 @@ __device__ __forceinline__ double lane_before(double x) {
 // point update this issue-bound kernel is made of.  Used only where no intermediate can leave the normal range (|x| and den guarded; zeros,
 // infinities and NaNs take the plain division: -0 / den must stay -0); tools/fastdiv_check.hip compared it with `/` BITWISE on 1.4e10 random
 // operands per type over 51 divisors (the reference's grids, random ones, significands of nearly all ones): no mismatch.
-#ifndef NNS_SOR_FASTDIV
-#define NNS_SOR_FASTDIV 1
-#endif
 template <typename T>
 __device__ __forceinline__ T div_den(T x, const SorK<T>& k) {
-#if NNS_SOR_FASTDIV
     constexpr T lo = sizeof(T) == 8 ? (T)1e-250 : (T)1e-25, hi = sizeof(T) == 8 ? (T)1e250 : (T)1e25;
     const T ax = fabs(x);
     const T q = x * k.rcp;
     T res = ax == (T)0 ? x : fma(fma(-q, k.den, x), k.rcp, q);              // +-0 / den = +-0 (den > 0): a cavity at rest is zeros for many steps
     if (!(k.rcp != (T)0 && ((ax >= lo && ax <= hi) || ax == (T)0))) res = x / k.den;      // rare: the wave skips it when no lane needs it
     return res;
-#else
-    return x / k.den;
-#endif
 }
 
 template <typename T>
@@ -123,14 +110,7 @@ __device__ __forceinline__ void sor_batch_rows(T* pw, const T* cw, int nx, int n
     };
     bool act = live(pos, sweep);                                               // this step's activity = what last step's request was issued under
     if (act) request(pos);
-#if NNS_SOR_TIMING
-    long tq0 = 0, tq1 = 0, tq2 = 0, tq3 = 0, tcomp = 0, treq = 0, tbar = 0;
-#endif
     for (int t = 0; t < nsteps; ++t) {
-#if NNS_SOR_TIMING
-        const bool timed = t >= 100 && t < 164 && blockIdx.x == 0;
-        if (timed) tq0 = clock64();
-#endif
         if (epos == 0) {                                                       // wave-uniform: every row of sweep esweep is done, no lane has finished another since
             if (esweep < nsw) {
                 T e = edone;
@@ -150,27 +130,14 @@ __device__ __forceinline__ void sor_batch_rows(T* pw, const T* cw, int nx, int n
         }
         ++pos; ++epos;
         if (pos == P) { pos = 0; sweep += kSorWaves; }
-#if NNS_SOR_TIMING
-        if (timed) { __builtin_amdgcn_s_waitcnt(0xc07f); tq1 = clock64(); }
-#endif
         act = live(pos, sweep);
         if (act) request(pos);
-#if NNS_SOR_TIMING
-        if (timed) { __builtin_amdgcn_s_waitcnt(0xc07f); tq2 = clock64(); }
-#endif
         __syncthreads();
-#if NNS_SOR_TIMING
-        if (timed) { tq3 = clock64(); tcomp += tq1 - tq0; treq += tq2 - tq1; tbar += tq3 - tq2; }
-#endif
     }
-#if NNS_SOR_TIMING
-    if (blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 7) && nsw > 40)
-        printf("sor rows, wave %d, mean of steps 100..163 (cycles): compute (to the store's completion) %ld, request + its wait %ld, barrier %ld\n", wave, tcomp / 64, treq / 64, tbar / 64);
-#endif
     __syncthreads();
 }
 
-template <bool IN_LDS> __device__ __forceinline__ bool sor_rows_path(int nx) { return IN_LDS && NNS_SOR_ROWS && nx - 2 <= kWave; }
+template <bool IN_LDS> __device__ __forceinline__ bool sor_rows_path(int nx) { return IN_LDS && nx - 2 <= kWave; }
 template <typename T, bool IN_LDS>
 __device__ __forceinline__ void sor_run_batch(T* pw, const T* cw, int nx, int ny, int nsw, const SorK<T>& k, T* errs) {
     if (sor_rows_path<IN_LDS>(nx)) sor_batch_rows<T>(pw, cw, nx, ny, nsw, k, errs);

@@ -38,10 +38,7 @@ __device__ __forceinline__ void adj_core(const float (&ff)[16], const float (&gf
     C2<TF>* xbF = reinterpret_cast<C2<TF>*>(xb_raw);
     C2<float>* xbI = reinterpret_cast<C2<float>*>(xb_raw);
     C2<float> e[16];
-#ifndef NNS_F32_DIFF
-#define NNS_F32_DIFF 1
-#endif
-    if constexpr (sizeof(TF) == 4 && NNS_F32_DIFF) {
+    if constexpr (sizeof(TF) == 4) {
         // all-float32 mode, as the forward's (spectral_kernels.hip, deriv_core): every packed pair is forward-DIFFERENCED in physical space,
         // FFT(d) = (e^{i theta} - 1) FFT(f), and the spectral multiplies become the bounded filters
         //     i k   FFT(f) = M1 D,  M1 = (k / 2)(cot(theta / 2) - i);      -nu k^2 FFT(f) = (nu k / 2)(k + i k cot(theta / 2)) D
@@ -232,34 +229,24 @@ __global__ __launch_bounds__(kSpecThreads) void spec_bwd_ypass_kernel(const floa
 // x-pass: columns.  A workgroup owns LINES adjacent columns of one grid; the five input fields go through the LDS
 // transpose stage in two rounds (u, v, a then b, d: the stage holds three fields), the three partials come back in one.
 // ------------------------------------------------------------------------------------------------------------------
-// WAVES (round 4): lines -- and waves -- per workgroup.  With 8 a CU holds ONE workgroup whose eight waves walk load / stage / transform / store in
-// lockstep (the barriers of the staging steps): the vector pipe idles while the tile's 80 row pieces per thread are in flight and the memory system
-// idles under the six transforms -- 1.7 TB/s, 34 % of wave-cycles issuing (profiles/r04_specbwd_summary.txt).  With 4 the LDS of a workgroup halves
-// and a CU holds TWO that run out of step, one transforming while the other moves its tile -- but its tiles are 4 columns wide: 16-byte row pieces,
-// twice the row pieces per byte.  MEASURED (profiles/r04_ab_specbwd_xwaves.txt, same box, three rounds): whole backward 2.10 ms with 8, 2.17 with 4:
-// the access shape costs more than the overlap buys.  NNS_BWD_XWAVES=4 in the environment selects it for re-measurement.
-template <int N, typename TF, int WAVES>
-__global__ __launch_bounds__(WAVES * kWave) void spec_bwd_xpass_kernel(const float* __restrict__ u, const float* __restrict__ v,
+// Eight waves (= lines at N = 1024) per workgroup: a CU holds ONE workgroup whose waves walk load / stage / transform / store in lockstep (the barriers
+// of the staging steps): the vector pipe idles while the tile's 80 row pieces per thread are in flight and the memory system idles under the six
+// transforms -- 1.7 TB/s, 34 % of wave-cycles issuing (profiles/r04_specbwd_summary.txt).  (Four waves, two workgroups per CU running out of step on
+// tiles 4 columns wide, were tried: whole backward 2.17 ms against 2.10, profiles/r04_ab_specbwd_xwaves.txt -- 16-byte row pieces cost more than the
+// overlap buys.)
+template <int N, typename TF>
+__global__ __launch_bounds__(kSpecThreads) void spec_bwd_xpass_kernel(const float* __restrict__ u, const float* __restrict__ v,
                                                                        const float* __restrict__ ga, const float* __restrict__ gb, const float* __restrict__ gd,
                                                                        float* __restrict__ gu, float* __restrict__ gv, float* __restrict__ gp,
                                                                        int ny, int tiles_per_grid, long ntiles, AdjK k) {
-    using L = SpecLds<N, TF, WAVES>;
+    using L = SpecLds<N, TF>;
     constexpr int TPF = L::TPF, CW = L::LINES, SF = L::STAGE_F;
-    constexpr int ROWS_PER_IT = WAVES * kWave / CW;
+    constexpr int ROWS_PER_IT = kSpecThreads / CW;
     constexpr int NR = N / ROWS_PER_IT;
     static_assert(NR == 16, "staging geometry");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     C2<TF>* tabF; C2<float>* tabI; unsigned char* lines;
-    spec_setup<N, TF, WAVES * kWave>(smem, tabF, tabI, lines);
-#ifndef NNS_BWDX_TIMING
-#define NNS_BWDX_TIMING 0          // 1: wave 0 of workgroup 0 prints the cycles (s_memtime) of the phases of its fourth tile
-#endif
-#if NNS_BWDX_TIMING
-    long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define BWDX_STAMP(i) if (t == blockIdx.x + 3 * (long)gridDim.x) { __builtin_amdgcn_s_waitcnt(0); tk[i] = clock64(); }
-#else
-#define BWDX_STAMP(i)
-#endif
+    spec_setup<N, TF>(smem, tabF, tabI, lines);
     for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
         int tx = threadIdx.x;
         asm volatile("" : "+v"(tx));
@@ -277,7 +264,6 @@ __global__ __launch_bounds__(WAVES * kWave) void spec_bwd_xpass_kernel(const flo
         int tidv = tid;
         asm volatile("" : "+v"(tidv));
         float uf[16], vf[16], af[16], bf[16], s1[16];
-        BWDX_STAMP(0)
         // round 1: u, v, a
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
@@ -285,7 +271,6 @@ __global__ __launch_bounds__(WAVES * kWave) void spec_bwd_xpass_kernel(const flo
             const size_t q = g + (size_t)r * ny + col;
             cp_stage[0 * SF + r] = u[q]; cp_stage[1 * SF + r] = v[q]; cp_stage[2 * SF + r] = ga[q];
         }
-        BWDX_STAMP(1)
         __syncthreads();
 #pragma unroll
         for (int m = 0; m < 16; ++m) {
@@ -299,18 +284,15 @@ __global__ __launch_bounds__(WAVES * kWave) void spec_bwd_xpass_kernel(const flo
             const size_t q = g + (size_t)r * ny + col;
             cp_stage[0 * SF + r] = gb[q]; cp_stage[1 * SF + r] = gd[q];
         }
-        BWDX_STAMP(2)
         __syncthreads();
 #pragma unroll
         for (int m = 0; m < 16; ++m) { bf[m] = my_stage[0 * SF + tidv + TPF * m]; s1[m] = my_stage[1 * SF + tidv + TPF * m]; }
         __syncthreads();                                                               // the stage aliases the exchange image
-        BWDX_STAMP(3)
         float s2[16], w[16], dax[16];
         C2<float> c[16];
 #pragma unroll
         for (int m = 0; m < 16; ++m) { s1[m] = af[m] * uf[m] + s1[m]; s2[m] = bf[m] * uf[m]; }           // a u + d,  b u
         adj_core<N, TF, true>(uf, vf, af, bf, s1, s2, w, dax, c, tabF, tabI, xb, tidv, k);
-        BWDX_STAMP(4)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -328,16 +310,8 @@ __global__ __launch_bounds__(WAVES * kWave) void spec_bwd_xpass_kernel(const flo
                 gu[q] = cp_stage[0 * SF + r]; gv[q] = cp_stage[1 * SF + r]; gp[q] = cp_stage[2 * SF + r];
             }
         }
-        BWDX_STAMP(5)
         __syncthreads();
-        BWDX_STAMP(6)
     }
-#if NNS_BWDX_TIMING
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        printf("backward column pass, one tile of wave 0 (cycles): round-1 loads + stage %ld, barrier + read + round-2 loads + stage %ld, barrier + read + barrier %ld, six transforms %ld, "
-               "stage results + stores drained %ld, last barrier %ld, whole tile %ld\n", (long)(tk[1] - tk[0]), (long)(tk[2] - tk[1]), (long)(tk[3] - tk[2]), (long)(tk[4] - tk[3]),
-               (long)(tk[5] - tk[4]), (long)(tk[6] - tk[5]), (long)(tk[6] - tk[0]));
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -618,14 +592,10 @@ int launch_bwd(const float* u, const float* v, const float* ga, const float* gb,
     using L = SpecLds<N, TF>;
     const long gmax = spec_grid_cap();
     if (xpass) {
-#ifndef NNS_BWD_XSPLIT
-#define NNS_BWD_XSPLIT 1           // 1: all-float32 mode: spec_bwd_xsplit_kernel (8 transform + 4 memory waves); 0: spec_bwd_xpass_kernel
-#endif
         if constexpr (sizeof(TF) == 4) {
-            static const bool use_split = [] { const char* e = getenv("NNS_BWD_XSPLIT"); return e ? atoi(e) != 0 : NNS_BWD_XSPLIT != 0; }();
             const int ny = nx_or_ny_other;
-            // the memory waves address with a scalar grid base + a 32-bit byte offset per lane
-            if (use_split && (unsigned long long)N * (unsigned long long)ny < (1ull << 30)) {
+            // all-float32 mode: the role-split kernel, whose memory waves address with a scalar grid base + a 32-bit byte offset per lane
+            if ((unsigned long long)N * (unsigned long long)ny < (1ull << 30)) {
                 using SL = SplitLds<N, float>;
                 auto kern = spec_bwd_xsplit_kernel<N>;
                 static bool attr = false;
@@ -640,28 +610,18 @@ int launch_bwd(const float* u, const float* v, const float* ga, const float* gb,
                 return check_launch("spec_residual_bwd_xpass");
             }
         }
-#ifndef NNS_BWD_XWAVES
-#define NNS_BWD_XWAVES 8           // waves (= lines at N = 1024) per workgroup of the backward column pass: 8 = one workgroup per CU, 4 = two out of step (measured slower)
-#endif
-        static const int xw = [] { const char* e = getenv("NNS_BWD_XWAVES"); const int v = e ? atoi(e) : NNS_BWD_XWAVES; return v == 4 ? 4 : 8; }();
-        auto go = [&](auto wc) -> int {
-            constexpr int W = decltype(wc)::value;
-            using LW = SpecLds<N, TF, W>;
-            auto kern = spec_bwd_xpass_kernel<N, TF, W>;
-            static bool attr = false;
-            if (!attr) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LW::TOTAL);
-                if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "spec bwd xpass: hipFuncSetAttribute(%d B): %s", LW::TOTAL, hipGetErrorString(e));
-                attr = true;
-            }
-            const int ny = nx_or_ny_other;
-            const int tiles_per_grid = (ny + LW::LINES - 1) / LW::LINES;
-            const long ntiles = (long)batch * tiles_per_grid;
-            const long cap = gmax * (8 / W);
-            hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < cap ? ntiles : cap)), dim3(W * kWave), LW::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, ny, tiles_per_grid, ntiles, k);
-            return check_launch("spec_residual_bwd_xpass");
-        };
-        return xw == 8 ? go(std::integral_constant<int, 8>{}) : go(std::integral_constant<int, 4>{});
+        auto kern = spec_bwd_xpass_kernel<N, TF>;
+        static bool attr = false;
+        if (!attr) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L::TOTAL);
+            if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "spec bwd xpass: hipFuncSetAttribute(%d B): %s", L::TOTAL, hipGetErrorString(e));
+            attr = true;
+        }
+        const int ny = nx_or_ny_other;
+        const int tiles_per_grid = (ny + L::LINES - 1) / L::LINES;
+        const long ntiles = (long)batch * tiles_per_grid;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < gmax ? ntiles : gmax)), dim3(kSpecThreads), L::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, ny, tiles_per_grid, ntiles, k);
+        return check_launch("spec_residual_bwd_xpass");
     }
     auto kern = spec_bwd_ypass_kernel<N, TF>;
     static bool attr = false;

@@ -10,10 +10,7 @@
 namespace nns {
 namespace spec {
 
-#ifndef NNS_SPEC_THREADS
-#define NNS_SPEC_THREADS 512
-#endif
-constexpr int kSpecThreads = NNS_SPEC_THREADS;      // 8 waves: 2 per SIMD, <= 256 VGPRs each
+constexpr int kSpecThreads = 512;                   // 8 waves: 2 per SIMD, <= 256 VGPRs each
 constexpr int kSpecWaves = kSpecThreads / kWave;
 
 struct SpecK {
@@ -24,11 +21,11 @@ struct SpecK {
     float inv_dt;
 };
 
-template <int N, typename TF, int WAVES = kSpecWaves>
+template <int N, typename TF>
 struct SpecLds {
     static constexpr int TPF = N / 16;
     static constexpr int FPW = kWave / TPF;                       // lines per wave
-    static constexpr int LINES = WAVES * FPW;                     // lines per workgroup
+    static constexpr int LINES = kSpecWaves * FPW;                    // lines per workgroup
     static constexpr int SLOTS = N + N / 16;
     static constexpr int STAGE_F = N + 16;                        // floats per staged field (padded)
     static constexpr int XB_BYTES = SLOTS * (int)sizeof(C2<TF>);
@@ -152,11 +149,8 @@ inline int spec_resolve_precise(int precise, double nu, int nx, double Lx, int n
 }
 
 // workgroups per launch (grid-stride over tiles): 2 generations per CU -- each generation pays the twiddle-table
-// setup and one exposed first-tile load (2048 cost the x-pass 6 %, same-box sweep); NNS_SPEC_GRID overrides it for tuning
-inline long spec_grid_cap() {
-    static const long cap = [] { const char* e = getenv("NNS_SPEC_GRID"); const long v = e ? atol(e) : 0; return v > 0 ? v : 512L; }();
-    return cap;
-}
+// setup and one exposed first-tile load (2048 cost the x-pass 6 %, same-box sweep)
+inline long spec_grid_cap() { return 512L; }
 
 
 // spectral_dense.hip: the same operators on an axis of any length 3 .. 2048 as circulant matrices applied in float64 (O(n) per point;

@@ -53,16 +53,9 @@ __device__ __forceinline__ void deriv_core(const float (&uf)[16], const float (&
     const C2<float>* tabI2 = tabI + N / 2;
     C2<TF>* xbF = reinterpret_cast<C2<TF>*>(xb_raw);
     C2<float>* xbI = reinterpret_cast<C2<float>*>(xb_raw);
-    C2<TF> z[16];
-    // ---- pressure: Z2 = FFT(p); keep only its contribution to b, already scaled, in float
-#ifndef NNS_P32
-#define NNS_P32 1          // 1: the pressure transform in float32 on the forward-DIFFERENCED line (precise mode); 0: float64 FFT(p)
-#endif
-#ifndef NNS_F32_DIFF
-#define NNS_F32_DIFF 1     // 1: the all-float32 mode transforms forward DIFFERENCES of u, v, p (bounded filters, see below); 0: the fields themselves
-#endif
-    constexpr bool DIFF32 = sizeof(TF) == 4 && NNS_F32_DIFF;
-    if constexpr ((sizeof(TF) == 8 && NNS_P32) || DIFF32) {
+    constexpr bool DIFF32 = sizeof(TF) == 4;      // the all-float32 mode transforms forward DIFFERENCES of u, v (bounded filters, see below), not the fields
+    // ---- pressure, in float32 for either TF: keep only its contribution to b, already scaled
+    {
         // p enters the residual only through its FIRST derivative.  FFT(p) in float32 would not do: its rounding noise, white
         // in k, is amplified by k (4e-5 of |p| at N = 1024).  The forward difference d_j = p_{j+1} - p_j (exact or correctly
         // rounded in float32) has FFT(d) = (e^{i theta} - 1) FFT(p), so
@@ -76,6 +69,8 @@ __device__ __forceinline__ void deriv_core(const float (&uf)[16], const float (&
             zf[m].y = 0.f;
         });
         fft_line<float, N, false, 0>(zf, tabI, tabI2, xbI, tid, hook);
+        // The per-element wavenumber factors depend only on the lane id: left alone, instruction selection computes all 16 during the
+        // butterflies above and spills them.  Tie the lane id to the transform's output so they are computed here, where they are used.
         int te = tid;
         asm volatile("" : "+v"(te), "+v"(zf[0].x));
         const float csh = (float)(0.5 * k.cs);
@@ -88,23 +83,6 @@ __device__ __forceinline__ void deriv_core(const float (&uf)[16], const float (&
             const float gx = c * zf[m].x + sh * zf[m].y, gy = c * zf[m].y - sh * zf[m].x;        // G = (i k / rho) FFT(p) / N
             if constexpr (P_IN_REAL) { b[m].x = gx; b[m].y = gy; } else { b[m].x = -gy; b[m].y = gx; }   // i G in the y-pass
         });
-    } else {
-#pragma unroll
-    for (int m = 0; m < 16; ++m) { z[m].x = (TF)pf[m]; z[m].y = (TF)0; }
-    fft_line<TF, N, false, 0>(z, tabF, tabF2, xbF, tid, hook);
-    // The per-element wavenumber factors depend only on the lane id: left alone, instruction selection
-    // computes all 16 (fp64) during the butterflies above and spills them.  Tie the lane id to the
-    // transform's output so they are computed here, where they are used.
-    int te = tid;
-    asm volatile("" : "+v"(te), "+v"(z[0].x));
-    static_for<0, 16>([&](auto mc) {
-        constexpr int m = decltype(mc)::value;
-        int ko, ke;
-        wavenumber<N, m>(te, ko, ke);
-        const TF s = (TF)((double)ko * k.cs);
-        if constexpr (P_IN_REAL) { b[m].x = (float)(-s * z[m].y); b[m].y = (float)(s * z[m].x); }   // (i k/rho) Z2
-        else { b[m].x = (float)(-s * z[m].x); b[m].y = (float)(-s * z[m].y); }                       // i (i k/rho) Z2
-    });
     }
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (DIFF32) {
@@ -138,6 +116,7 @@ __device__ __forceinline__ void deriv_core(const float (&uf)[16], const float (&
         });
     } else {
     // ---- velocity: Z1 = FFT(u + i v)
+    C2<TF> z[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) { z[m].x = (TF)uf[m]; z[m].y = (TF)vf[m]; }
     fft_line<TF, N, false, P>(z, tabF, tabF2, xbF, tid, hook);
@@ -184,12 +163,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t seg_rsrc(const float* base) { 
 template <bool NT> __device__ __forceinline__ float ld_seg(__amdgpu_buffer_rsrc_t r, unsigned row_bytes, int col_bytes) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)row_bytes, col_bytes, NT ? 2 : 0));      // aux bit 1: nt
 }
-#ifndef NNS_YPASS_NT
-#define NNS_YPASS_NT 1            // non-temporal hints on the fused row pass's write-once outputs and read-once streams (0.84 -> 0.78 ms)
-#endif
-#ifndef NNS_YPASS_NT_PLAIN
-#define NNS_YPASS_NT_PLAIN 0      // the same hints in the plain (not fused) row pass
-#endif
+// non-temporal hints: on the fused row pass's write-once outputs and read-once streams (0.84 -> 0.78 ms), not in the plain row pass
 template <bool NT> __device__ __forceinline__ float ld_stream(const float* q) { if constexpr (NT) return __builtin_nontemporal_load(q); else return *q; }
 template <bool NT> __device__ __forceinline__ void st_stream(float* q, float x) { if constexpr (NT) __builtin_nontemporal_store(x, q); else *q = x; }
 
@@ -223,10 +197,7 @@ __global__ __launch_bounds__(kSpecThreads) void spec_ypass_kernel(const float* _
     // Software pipeline: the NEXT line's u, v, p are requested when the inverse transforms start (registers are
     // slack there: the float64 spectra are dead) and are consumed at the top of the next iteration.
     float nu[16], nv[16], np[16];
-#ifndef NNS_YPASS_XCD
-#define NNS_YPASS_XCD 0
-#endif
-    long it = NNS_YPASS_XCD ? (long)xcd_remap(blockIdx.x, gridDim.x) : (long)blockIdx.x;
+    long it = blockIdx.x;
     if (it >= niter) return;
     {
         const size_t b0 = line_base(it);
@@ -275,7 +246,7 @@ __global__ __launch_bounds__(kSpecThreads) void spec_ypass_kernel(const float* _
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const size_t c = base + TPF * (8 * h + i);
-                constexpr bool NT = (FUSE_FD || NNS_YPASS_NT_PLAIN) && NNS_YPASS_NT;
+                constexpr bool NT = FUSE_FD;
                 if constexpr (SEGP) {
                     const int so = seg_col(pk, TPF * (8 * h + i));
                     pu[i] = ld_seg<NT>(seg_rsrc(pk.pu), pbyte, so); pv[i] = ld_seg<NT>(seg_rsrc(pk.pv), pbyte, so); pd[i] = ld_seg<NT>(seg_rsrc(pk.pd), pbyte, so);
@@ -296,7 +267,7 @@ __global__ __launch_bounds__(kSpecThreads) void spec_ypass_kernel(const float* _
                     const int m = 8 * h + i;
                     const size_t c = base + TPF * m;
                     // one fixed rounding sequence (the compiler may not re-associate or contract differently per instantiation)
-                    constexpr bool NT = (FUSE_FD || NNS_YPASS_NT_PLAIN) && NNS_YPASS_NT;
+                    constexpr bool NT = FUSE_FD;
                     st_stream<NT>(ru + c, __fadd_rn(__fmaf_rn(vf[m], a[m].x, __fadd_rn(tu[m], pu[i])), b[m].x));
                     st_stream<NT>(rv + c, __fadd_rn(__fmaf_rn(vf[m], a[m].y, __fadd_rn(tv[m], pv[i])), b[m].y));
                     st_stream<NT>(rd + c, pd[i] + a[m].y);
@@ -313,23 +284,12 @@ __global__ __launch_bounds__(kSpecThreads) void spec_ypass_kernel(const float* _
             const long gi = row / nx, ii = row % nx;
             // one base pointer per stream (lane's first column included), slots at compile-time offsets TPF * m: the loads
             // then take immediate offsets instead of eighty precomputed 64-bit addresses
-            const size_t bm = (size_t)(gi * nx + (ii == 0 ? nx - 1 : ii - 1)) * N + tidv;       // rows i-1, i+1 (periodic in the grid), i
+            const size_t bm = (size_t)(gi * nx + (ii == 0 ? nx - 1 : ii - 1)) * N + tidv;       // rows i-1, i+1 (periodic in the grid)
             const size_t bp = (size_t)(gi * nx + (ii == nx - 1 ? 0 : ii + 1)) * N + tidv;
-            const size_t bc = (size_t)row * N;
-#ifdef NNS_ROWPASS_EXP              // timing experiment (wrong results): the stencil's rows i-1 / i+1 read from row i (no second touch of other rows)
-            const float* um_p = u + bc + tidv; const float* un_p = um_p; const float* vm_p = v + bc + tidv; const float* vn_p = vm_p;
-            const float* pm_p = p + bc + tidv; const float* pn_p = pm_p;
-            (void)bm; (void)bp;
-#else
             const float* um_p = u + bm; const float* un_p = u + bp; const float* vm_p = v + bm; const float* vn_p = v + bp;
             const float* pm_p = p + bm; const float* pn_p = p + bp;
-#endif
             if (hk.top && ii == 0) { const float* h = hk.top + (size_t)gi * N + tidv; um_p = h; vm_p = h + hk.fstride; pm_p = h + 2 * hk.fstride; }
             if (hk.bot && ii == nx - 1) { const float* h = hk.bot + (size_t)gi * N + tidv; un_p = h; vn_p = h + hk.fstride; pn_p = h + 2 * hk.fstride; }
-            const float* pl_p = p + bc + tidv - 1;                          // column - 1: wraps only for column 0 (slot 0 of lane 0)
-            const float* pr_p = p + bc + tidv + 1;                          // column + 1: wraps only for column N-1 (slot 15 of lane 63)
-            const float* pl0_p = p + bc + ((tidv + N - 1) & (N - 1));
-            const float* pr15_p = p + bc + ((tidv + TPF * 15 + 1) & (N - 1));
             static_for<0, 2>([&](auto hc) {
                 constexpr int h = decltype(hc)::value;
                 float um[8], un_[8], vm[8], vn_[8], pm[8], pn_[8], pl[8], pr[8];
@@ -340,14 +300,7 @@ __global__ __launch_bounds__(kSpecThreads) void spec_ypass_kernel(const float* _
                     pm[i] = pm_p[TPF * m]; pn_[i] = pn_p[TPF * m];
                     // p's j-1 / j+1 by lane rotates of the row in registers, like u's and v's (two of the eight re-read streams gone).  With the
                     // float64 Laplacian this spilled 21 registers (0.78 -> 0.91 ms); with the float32 one it fits: 252 VGPRs, 0.765 -> 0.757 ms
-#ifndef NNS_ROWPASS_PROT
-#define NNS_ROWPASS_PROT 1
-#endif
-                    if constexpr (NNS_ROWPASS_PROT) { pl[i] = left_of<m, TPF>(pf, tidv); pr[i] = right_of<m, TPF>(pf, tidv); }
-                    else {
-                    if constexpr (m == 0) pl[i] = pl0_p[0]; else pl[i] = pl_p[TPF * m];
-                    if constexpr (m == 15) pr[i] = pr15_p[0]; else pr[i] = pr_p[TPF * m];
-                    }
+                    pl[i] = left_of<m, TPF>(pf, tidv); pr[i] = right_of<m, TPF>(pf, tidv);
                 });
                 if (valid) {
                     static_for<0, 8>([&](auto ic) {
@@ -360,24 +313,15 @@ __global__ __launch_bounds__(kSpecThreads) void spec_ypass_kernel(const float* _
                         const float ux = (un_[i] - um[i]) * fk.inv_2dx, uy = (ur - ul) * fk.inv_2dy;
                         const float vx = (vn_[i] - vm[i]) * fk.inv_2dx, vy = (vr - vl) * fk.inv_2dy;
                         const float px = (pn_[i] - pm[i]) * fk.inv_2dx, py = (pr[i] - pl[i]) * fk.inv_2dy;
-#ifndef NNS_FUSED_LAP32
-#define NNS_FUSED_LAP32 1         // 1: second differences as differences of (exact) first differences in float32; 0: float64 sums
-#endif
-                        float lu, lv;
-                        if constexpr (NNS_FUSED_LAP32) {
-                            // (a - c) - (c - b): neighbouring values of a resolved field are within a factor 2 of each other, so both
-                            // first differences are EXACT in float32 (Sterbenz) and the only rounding is relative to the second
-                            // difference itself -- the accuracy of the float64 sum without ~28 double-rate instructions per point
-                            // (this pass is VALU-issue-bound, unlike the standalone stencil kernel, which keeps the float64 form)
-                            lu = ((un_[i] - ucc) - (ucc - um[i])) * fk.inv_dx2f + ((ur - ucc) - (ucc - ul)) * fk.inv_dy2f;
-                            lv = ((vn_[i] - vcc) - (vcc - vm[i])) * fk.inv_dx2f + ((vr - vcc) - (vcc - vl)) * fk.inv_dy2f;
-                        } else {
-                            lu = (float)(((double)un_[i] - 2.0 * ucc + (double)um[i]) * fk.inv_dx2 + ((double)ur - 2.0 * ucc + (double)ul) * fk.inv_dy2);
-                            lv = (float)(((double)vn_[i] - 2.0 * vcc + (double)vm[i]) * fk.inv_dx2 + ((double)vr - 2.0 * vcc + (double)vl) * fk.inv_dy2);
-                        }
-                        st_stream<NNS_YPASS_NT>(fu + c, tu[m] + ucc * ux + vcc * uy + px * fk.inv_rho - fk.nu * lu);
-                        st_stream<NNS_YPASS_NT>(fv + c, tv[m] + ucc * vx + vcc * vy + py * fk.inv_rho - fk.nu * lv);
-                        st_stream<NNS_YPASS_NT>(fd + c, ux + vy);
+                        // second differences as (a - c) - (c - b): neighbouring values of a resolved field are within a factor 2 of each
+                        // other, so both first differences are EXACT in float32 (Sterbenz) and the only rounding is relative to the second
+                        // difference itself -- the accuracy of the float64 sum without ~28 double-rate instructions per point
+                        // (this pass is VALU-issue-bound, unlike the standalone stencil kernel, which keeps the float64 form)
+                        const float lu = ((un_[i] - ucc) - (ucc - um[i])) * fk.inv_dx2f + ((ur - ucc) - (ucc - ul)) * fk.inv_dy2f;
+                        const float lv = ((vn_[i] - vcc) - (vcc - vm[i])) * fk.inv_dx2f + ((vr - vcc) - (vcc - vl)) * fk.inv_dy2f;
+                        st_stream<true>(fu + c, tu[m] + ucc * ux + vcc * uy + px * fk.inv_rho - fk.nu * lu);
+                        st_stream<true>(fv + c, tv[m] + ucc * vx + vcc * vy + py * fk.inv_rho - fk.nu * lv);
+                        st_stream<true>(fd + c, ux + vy);
                     });
                 }
             });
@@ -395,9 +339,6 @@ __global__ __launch_bounds__(kSpecThreads) void spec_ypass_kernel(const float* _
 // 8.5 + 8 KB per line), p in 16 registers.  The stencil phase then issues no global load at all; per chunk two extra rows are read
 // (2 / R of three streams).  Lines are independent, no workgroup barrier anywhere, as before.
 // ------------------------------------------------------------------------------------------
-#ifndef NNS_MARCH_NT_IN
-#define NNS_MARCH_NT_IN 1          // non-temporal hint on the row prefetch (each row is read once, bar the chunk edges): +0.5 % (same-box A/B)
-#endif
 template <int N>
 struct MarchLds {
     using L = SpecLds<N, float>;
@@ -474,7 +415,8 @@ __global__ __launch_bounds__(kSpecThreads) void spec_rowmarch_kernel(const float
             auto hook = [&](auto sc) {
                 if constexpr (decltype(sc)::value == 2 * FftPasses<N>::value - 1) {          // after the last forward pass: the row below
 #pragma unroll
-                    for (int m = 0; m < 16; ++m) { nu[m] = ld_stream<NNS_MARCH_NT_IN>(na + TPF * m); nv[m] = ld_stream<NNS_MARCH_NT_IN>(nb + TPF * m); np[m] = ld_stream<NNS_MARCH_NT_IN>(nc + TPF * m); }
+                    // (non-temporal: each row is read once, bar the chunk edges: +0.5 %, same-box A/B)
+                    for (int m = 0; m < 16; ++m) { nu[m] = ld_stream<true>(na + TPF * m); nv[m] = ld_stream<true>(nb + TPF * m); np[m] = ld_stream<true>(nc + TPF * m); }
                 }
             };
             C2<float> a[16], b[16];
@@ -499,11 +441,11 @@ __global__ __launch_bounds__(kSpecThreads) void spec_rowmarch_kernel(const float
                     const size_t c2 = base + TPF * (8 * h + i);
                     if constexpr (SEGP) {
                         const int so = seg_col(pk, TPF * (8 * h + i));
-                        pu[i] = ld_seg<NNS_YPASS_NT>(seg_rsrc(pk.pu), pbyte, so); pv[i] = ld_seg<NNS_YPASS_NT>(seg_rsrc(pk.pv), pbyte, so); pd[i] = ld_seg<NNS_YPASS_NT>(seg_rsrc(pk.pd), pbyte, so);
+                        pu[i] = ld_seg<true>(seg_rsrc(pk.pu), pbyte, so); pv[i] = ld_seg<true>(seg_rsrc(pk.pv), pbyte, so); pd[i] = ld_seg<true>(seg_rsrc(pk.pd), pbyte, so);
                     } else {
-                    pu[i] = ld_stream<NNS_YPASS_NT>(ru + c2); pv[i] = ld_stream<NNS_YPASS_NT>(rv + c2); pd[i] = ld_stream<NNS_YPASS_NT>(rd + c2);
+                    pu[i] = ld_stream<true>(ru + c2); pv[i] = ld_stream<true>(rv + c2); pd[i] = ld_stream<true>(rd + c2);
                     }
-                    qu[i] = ld_stream<NNS_YPASS_NT>(up + c2); qv[i] = ld_stream<NNS_YPASS_NT>(vp + c2);
+                    qu[i] = ld_stream<true>(up + c2); qv[i] = ld_stream<true>(vp + c2);
                 }
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
@@ -515,9 +457,9 @@ __global__ __launch_bounds__(kSpecThreads) void spec_rowmarch_kernel(const float
                     for (int i = 0; i < 8; ++i) {
                         const int m = 8 * h + i;
                         const size_t c2 = base + TPF * m;
-                        st_stream<NNS_YPASS_NT>(ru + c2, __fadd_rn(__fmaf_rn(vf[m], a[m].x, __fadd_rn(tu[m], pu[i])), b[m].x));
-                        st_stream<NNS_YPASS_NT>(rv + c2, __fadd_rn(__fmaf_rn(vf[m], a[m].y, __fadd_rn(tv[m], pv[i])), b[m].y));
-                        st_stream<NNS_YPASS_NT>(rd + c2, pd[i] + a[m].y);
+                        st_stream<true>(ru + c2, __fadd_rn(__fmaf_rn(vf[m], a[m].x, __fadd_rn(tu[m], pu[i])), b[m].x));
+                        st_stream<true>(rv + c2, __fadd_rn(__fmaf_rn(vf[m], a[m].y, __fadd_rn(tv[m], pv[i])), b[m].y));
+                        st_stream<true>(rd + c2, pd[i] + a[m].y);
                     }
                 }
             }
@@ -552,9 +494,9 @@ __global__ __launch_bounds__(kSpecThreads) void spec_rowmarch_kernel(const float
                     const float px = (np[m] - pm[m]) * fk.inv_2dx, py = (pr - pl) * fk.inv_2dy;
                     const float lu = ((nu[m] - ucc) - (ucc - um[i])) * fk.inv_dx2f + ((ur - ucc) - (ucc - ul)) * fk.inv_dy2f;
                     const float lv = ((nv[m] - vcc) - (vcc - vm[i])) * fk.inv_dx2f + ((vr - vcc) - (vcc - vl)) * fk.inv_dy2f;
-                    st_stream<NNS_YPASS_NT>(fu + c2, tu[m] + ucc * ux + vcc * uy + px * fk.inv_rho - fk.nu * lu);
-                    st_stream<NNS_YPASS_NT>(fv + c2, tv[m] + ucc * vx + vcc * vy + py * fk.inv_rho - fk.nu * lv);
-                    st_stream<NNS_YPASS_NT>(fd + c2, ux + vy);
+                    st_stream<true>(fu + c2, tu[m] + ucc * ux + vcc * uy + px * fk.inv_rho - fk.nu * lu);
+                    st_stream<true>(fv + c2, tv[m] + ucc * vx + vcc * vy + py * fk.inv_rho - fk.nu * lv);
+                    st_stream<true>(fd + c2, ux + vy);
                 });
             });
             // this row becomes the row above
@@ -603,11 +545,8 @@ __global__ __launch_bounds__(kSpecThreads) void spec_xpass_kernel(const float* _
     // after the transforms have released it -- global-load latency hides under the FFT phase.
     float su[NR], sv[NR], sp[NR];
     auto tile_coords = [&](long t, int& j0, size_t& g) {
-#ifndef NNS_XPASS_REVERSE
-#define NNS_XPASS_REVERSE 1
-#endif
         // neighbouring tiles -> same XCD (shared lines); tiles are walked from the LAST grid to the first (see launch_xpass)
-        const long lt = NNS_XPASS_REVERSE ? ntiles - 1 - (long)xcd_remap((unsigned)t, (unsigned)ntiles) : (long)xcd_remap((unsigned)t, (unsigned)ntiles);
+        const long lt = ntiles - 1 - (long)xcd_remap((unsigned)t, (unsigned)ntiles);
         j0 = (int)(lt % tiles_per_grid) * CW;
         g = (size_t)(lt / tiles_per_grid) * (SEG ? ((size_t)ny << sg.shift) : (size_t)N * ny);
     };
@@ -744,11 +683,8 @@ __global__ __launch_bounds__(kSplitThreads) void spec_xpass_split_kernel(const f
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     C2<TF>* tabF; C2<float>* tabI; unsigned char* lines;
     spec_setup<N, TF, kSplitThreads>(smem, tabF, tabI, lines);
-#ifndef NNS_SPLIT_EXP
-#define NNS_SPLIT_EXP 0            // timing experiments (wrong results): 1 = no transforms, 2 = no global traffic
-#endif
     auto tile_coords = [&](long t, int& j0, size_t& g) {
-        const long lt = NNS_XPASS_REVERSE ? ntiles - 1 - (long)xcd_remap((unsigned)t, (unsigned)ntiles) : (long)xcd_remap((unsigned)t, (unsigned)ntiles);
+        const long lt = ntiles - 1 - (long)xcd_remap((unsigned)t, (unsigned)ntiles);
         j0 = (int)(lt % tiles_per_grid) * CW;
         g = (size_t)(lt / tiles_per_grid) * (SEG ? ((size_t)ny << sg.shift) : (size_t)N * ny);
     };
@@ -775,19 +711,8 @@ __global__ __launch_bounds__(kSplitThreads) void spec_xpass_split_kernel(const f
         };
         auto at = [](const float* base, unsigned byte_off) -> const float& { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off); };
         auto at_w = [](float* base, unsigned byte_off) -> float& { return *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off); };
-#ifndef NNS_SPLIT_BUF
-#define NNS_SPLIT_BUF 0            // 1: whole grids (not SEG): buffer loads / stores -- descriptor of the grid + ONE lane offset per tile + a scalar row offset per access
-#endif
-        // Round 4: with `global_load_dword v, v_off, s[base]` every row piece still costs two vector instructions (add the row
-        // stride, shift to bytes: 128 per tile, direction and memory wave, on the SIMDs the transform waves compute on).  A buffer access takes
-        // base (descriptor, 4 SGPRs) + lane offset (ONE VGPR per tile) + scalar offset (the row: scalar unit) -- no vector instruction per access
-        // (checked in the ISA: 192 buffer_load_dword / 192 buffer_store_dword per tile loop, `s_off offen`, no v_add / v_lshl between them).
-        // MEASURED, same box, three rounds (profiles/r04_ab_xpass_buffer_addressing.log): column pass 0.493 ms against 0.490 with the global_
-        // form, step 5.17e10 against 5.22e10 -- no gain: the memory waves' vector instructions were not what the roles cost each other.  Kept
-        // behind the macro, off.
-        constexpr bool BUF = NNS_SPLIT_BUF && !SEG;
-        auto rsrc = [&](const float* base) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)((unsigned)N * (unsigned)ny * 4u), 0x00020000); };
-        auto row_soff = [&](int i) -> int { return (4 * MROWS * (i >> 2) + (i & 3)) * ny * 4; };      // wave-uniform: scalar registers
+        // (round 4, VERDICT r3 item 5 (a): buffer loads / stores -- grid descriptor + ONE lane offset per tile + a scalar row offset per access, no vector
+        // instruction per row piece -- were tried: column pass 0.493 ms against 0.490, no gain, profiles/r04_ab_xpass_buffer_addressing.log)
         auto load_tile = [&](long tt) {
             int j0; size_t g;
             tile_coords(tt, j0, g);
@@ -795,22 +720,10 @@ __global__ __launch_bounds__(kSplitThreads) void spec_xpass_split_kernel(const f
             unsigned crv = (unsigned)cr;
             asm volatile("" : "+v"(col), "+v"(crv));
             const float* ug = u + g; const float* vg = v + g; const float* pg = p + g;
-            if constexpr (BUF) {
-                const auto r0 = rsrc(ug), r1 = rsrc(vg), r2 = rsrc(pg);
-                const int voff = (int)((col + 4u * crv * (unsigned)ny) * 4u);
-#pragma unroll
-                for (int i = 0; i < NR; ++i) {
-                    const int so = row_soff(i);
-                    R[0][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r0, voff, so, 0));
-                    R[1][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r1, voff, so, 0));
-                    R[2][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r2, voff, so, 0));
-                }
-            } else {
 #pragma unroll
             for (int i = 0; i < NR; ++i) {
                 const unsigned c = off32(i, col, crv);
                 R[0][i] = at(ug, c); R[1][i] = at(vg, c); R[2][i] = at(pg, c);
-            }
             }
         };
         auto store_tile = [&](long tt) {
@@ -821,22 +734,10 @@ __global__ __launch_bounds__(kSplitThreads) void spec_xpass_split_kernel(const f
                 unsigned crv = (unsigned)cr;
                 asm volatile("" : "+v"(col), "+v"(crv));
                 float* ug = ru + g; float* vg = rv + g; float* pg = rd + g;
-                if constexpr (BUF) {
-                    const auto r0 = rsrc(ug), r1 = rsrc(vg), r2 = rsrc(pg);
-                    const int voff = (int)((col + 4u * crv * (unsigned)ny) * 4u);
-#pragma unroll
-                    for (int i = 0; i < NR; ++i) {
-                        const int so = row_soff(i);
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, R[0][i]), r0, voff, so, 0);
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, R[1][i]), r1, voff, so, 0);
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, R[2][i]), r2, voff, so, 0);
-                    }
-                } else {
 #pragma unroll
                 for (int i = 0; i < NR; ++i) {
                     const unsigned c = off32(i, col, crv);
                     at_w(ug, c) = R[0][i]; at_w(vg, c) = R[1][i]; at_w(pg, c) = R[2][i];
-                }
                 }
             }
         };
@@ -851,16 +752,8 @@ __global__ __launch_bounds__(kSplitThreads) void spec_xpass_split_kernel(const f
         for (; t < ntiles; t += gridDim.x) {
             const long tn = t + gridDim.x;
             const bool has_next = tn < ntiles;
-            if (NNS_SPLIT_EXP != 2) {
-#ifndef NNS_SPLIT_NOST
-#define NNS_SPLIT_NOST 0           // timing experiments (wrong results): no partial stores / no input loads after the first tile
-#endif
-#ifndef NNS_SPLIT_NOLD
-#define NNS_SPLIT_NOLD 0
-#endif
-            if (prev >= 0 && !NNS_SPLIT_NOST) store_tile(prev);                 // under the transforms of tile t: tile t-1's partials out ...
-            if (has_next && !NNS_SPLIT_NOLD) load_tile(tn);                     // ... and tile t+1's inputs in (same registers)
-            }
+            if (prev >= 0) store_tile(prev);                                    // under the transforms of tile t: tile t-1's partials out ...
+            if (has_next) load_tile(tn);                                        // ... and tile t+1's inputs in (same registers)
             __syncthreads();                                                    // (1) the transform waves have written tile t's partials to the staging image
             // the exchange step: results out of the image, next inputs into it, slot for slot
 #pragma unroll
@@ -902,10 +795,6 @@ __global__ __launch_bounds__(kSplitThreads) void spec_xpass_split_kernel(const f
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         C2<float> a[16], b2[16];
-        if (NNS_SPLIT_EXP == 1) {
-#pragma unroll
-            for (int m = 0; m < 16; ++m) { a[m].x = vf[m]; a[m].y = pf[m]; b2[m].x = uf[m]; b2[m].y = vf[m]; }
-        } else
         deriv_core<N, TF, true>(uf, vf, pf, a, b2, tabF, tabI, xb, tidv, k);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -930,16 +819,12 @@ int launch_xpass(const float* u, const float* v, const float* p, float* ru, floa
     using L = SpecLds<N, TF>;
     const int tiles_per_grid = (ny + L::LINES - 1) / L::LINES;
     const long ntiles = (long)batch * tiles_per_grid;
-    // prefetch is disabled where hipcc (ROCm 7.2) spills with it: checked with -Rpass-analysis=kernel-resource-usage
-#ifndef NNS_XPASS_SPLIT
-#define NNS_XPASS_SPLIT 1          // 1: spec_xpass_split_kernel (8 transform waves + 4 memory waves), 0: spec_xpass_kernel
-#endif
     // the role-split kernel's memory waves address with a scalar grid base + a 32-BIT BYTE offset per lane: the largest element offset inside
     // one grid (SEG: across all source-rank segments) must stay below 2^30; beyond that the older kernel (size_t row offsets) takes over
     const unsigned long long max_off = SEG ? (unsigned long long)((N >> sg.shift) - 1) * (unsigned long long)sg.stride + ((unsigned long long)ny << sg.shift)
                                            : (unsigned long long)N * (unsigned long long)ny;
     const bool off32_ok = max_off < (1ull << 30);
-    if (NNS_XPASS_SPLIT && off32_ok) {
+    if (off32_ok) {
         auto kern = spec_xpass_split_kernel<N, TF, SEG>;
         using SL = SplitLds<N, TF>;
         static bool attr_set = false;
@@ -953,6 +838,7 @@ int launch_xpass(const float* u, const float* v, const float* p, float* ru, floa
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kSplitThreads), SL::TOTAL, s, u, v, p, ru, rv, rd, ny, tiles_per_grid, ntiles, k, sg);
         return check_launch("spec_residual_xpass");
     }
+    // prefetch is disabled where hipcc (ROCm 7.2) spills with it: checked with -Rpass-analysis=kernel-resource-usage
     constexpr bool PF = !((N == 128 && sizeof(TF) == 4) || N == 256);
     auto kern = spec_xpass_kernel<N, TF, PF, SEG>;
     static bool attr_set = false;
@@ -990,16 +876,11 @@ inline int device_cus() {
     static const int n = [] { int dev = 0, v = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) v = 256; return v; }();
     return n;
 }
-#ifndef NNS_ROWMARCH
-#define NNS_ROWMARCH 1             // 1: the all-float32 fused row pass marches (spec_rowmarch_kernel); 0: spec_ypass_kernel<N, float, true>
-#endif
 // rows per chunk of the marching row pass: one chunk per line once every CU is busy, a power of two in [1, 64].  Small batches get
 // short chunks (R = 1: three row reads per row, as the non-marching kernel, but those fit the caches); the SAME kernel serves every
 // batch size, so grid b of a large batch equals the same grid evaluated alone bit for bit.
 template <int N>
 int march_chunk_rows(long nrows, int nx) {
-    static const int forced = [] { const char* e = getenv("NNS_MARCH_R"); return e ? atoi(e) : 0; }();      // tuning override (a power of two)
-    if (forced > 0) return forced > nx ? nx : forced;
     const long tl = (long)device_cus() * SpecLds<N, float>::LINES;
     const long r = nrows / tl;
     int R = 1;

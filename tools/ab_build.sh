@@ -1,8 +1,9 @@
 #!/bin/bash
 # Developer helper: build a VARIANT of libnns_hip.so with extra compile flags for same-box A/B timing.
-#   tools/ab_build.sh B "-DNNS_TW_LOOKUP=1"   ->  ab_variants/libnns_hip_B.so     (use with NNS_LIB_PATH=...)
+#   tools/ab_build.sh B "-fno-unroll-loops"   ->  ab_variants/libnns_hip_B.so     (use with NNS_LIB_PATH=...)
+# (the kernels carry no build switches: a code variant is an edited copy of the source, built from its own tree)
 # AB_ONLY="spectral_kernels spectral_bwd_kernels": recompile only these translation units with the flags and link the in-tree objects
-# (make -C neural-navier-stokes_amd/csrc first) for the rest -- minutes faster when a macro touches one file.
+# (make -C neural-navier-stokes_amd/csrc first) for the rest -- minutes faster when the flags matter to one file.
 set -e
 TAG=$1; FLAGS=$2
 C=neural-navier-stokes_amd/csrc; O=ab_variants; mkdir -p $O/$TAG

@@ -94,7 +94,7 @@ print('immediates ok: frag_pix', lane_indep(new_frag_pix, [(s, cb, sec) for s in
       'frag_w', lane_indep(new_frag_w, [(ot, s, sec) for ot in (0, 1) for s in range(4) for sec in (0, 1)]))
 print('sub-image bytes: image', sub_bytes(128), 'x4 =', 4 * sub_bytes(128), ' W', sub_bytes(64), 'x4 =', 4 * sub_bytes(64), '(old: image', 128 * 136, 'W', 64 * 136, ')')
 
-# ---------------- layout 2 as built (csrc/pixel_mlp_kernels.hip, NNS_PM_LAYOUT = 2): the checks the kernel relies on
+# ---------------- layout 2 as built (csrc/pixel_mlp_kernels.hip, BwdLds): the checks the kernel relies on
 def read_b128(addr_fn):        # ds_read_b128: four non-contiguous 16-lane groups, 64 banks, 16 bytes per lane
     return conflict_cycles([addr_fn(l) for l in range(64)], 16, B128, 64)
 def write_b128(addr_fn):       # ds_write_b128: eight groups of 8 contiguous lanes, 32 banks
