@@ -406,7 +406,7 @@ int nns_spec_irfft2_f32(float* spec, float* f, int batch, int nx, int ny, void* 
  * State: what = the vorticity spectrum w^ (numpy.fft.rfft2 convention, M w^ = w^, w^(0,0) = 0), COMPACTED to the kept y-wavenumbers
  * j < my1 = (ny - 1) / 3 + 1 and transposed: interleaved complex64 [batch][my1][nx], element [b][j][i] = w^[b][i][j] (i in fftfreq order);
  * mean = the conserved mean velocity (U0, V0), float32 [batch][2].  u = U0 + irfft2(i ky psi^), v = V0 - irfft2(i kx psi^), psi^ = w^ / |k|^2.
- * work: nns_spec_ns_workspace bytes (one workspace serves all three calls; none of them keeps data in it between calls).
+ * work: nns_spec_ns_workspace bytes (one workspace serves init, step, step_forced and fields; none of them keeps data in it between calls).
  * Errors: NNS_ERR_INVALID_ARG for a NULL pointer, batch < 1, non-positive or non-finite Lx, Ly, dt, negative nu, nsteps < 0;
  * NNS_ERR_UNSUPPORTED for an axis that is not a power of two in [64, 1024]; NNS_ERR_WORKSPACE for work_bytes below the size query. */
 int nns_spec_ns_workspace(int batch, int nx, int ny, size_t* bytes);
@@ -420,6 +420,25 @@ int nns_spec_ns_step_f32(float* what, const float* mean, void* work, size_t work
 /* u, v [batch][nx][ny] as above and p = irfft2(-M rfft2(2 rho (u_x v_y - u_y v_x)) / |k|^2), p^(0,0) = 0 (derivatives from psi^). */
 int nns_spec_ns_fields_f32(const float* what, const float* mean, float* u, float* v, float* p, void* work, size_t work_bytes, int batch,
                            int nx, int ny, double Lx, double Ly, double rho, void* stream);
+/* The step with a body force constant in time and a linear drag (restatement: tests/pspec_forced_oracle.py):
+ *     w_t + u w_x + v w_y = nu lap w - drag w + g,      g^ = M (i kx f_y^ - i ky f_x^)
+ * i.e. u_t + (u . grad) u = -grad p / rho + nu lap u - drag (u - <u>) + f_s with f_s the solenoidal, zero-mean, band-limited part of f; the
+ * mean velocity stays conserved and undamped.  Same Lawson RK4 with L = -(nu |k|^2 + drag) and N(w^) = -M rfft2(u w_x + v w_y) + g^ (the
+ * same g^ in all four stages).  ghat = g^ in the layout of what, float32 [gbatch][my1][nx][2]: it is what nns_spec_ns_init_f32(f_x, f_y, ...)
+ * writes to what.  gbatch = 1: one force shared by every grid; gbatch = batch: one per grid; ghat == NULL requires gbatch == 0 (no force).
+ * NNS_ERR_INVALID_ARG for any other gbatch and for a negative or non-finite drag; otherwise the errors, the workspace and the launch
+ * count (8 per step plus one per call, no allocation, no host synchronisation, capturable) of nns_spec_ns_step_f32, and with ghat == NULL,
+ * gbatch == 0, drag == 0 its result bitwise (the same kernels). */
+int nns_spec_ns_step_forced_f32(float* what, const float* mean, const float* ghat, int gbatch, void* work, size_t work_bytes, int batch,
+                                int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, int nsteps, void* stream);
+/* out [batch][3] float64 (device) = per grid, from what (and ghat, gbatch as above) by Parseval over the stored half spectrum:
+ *     E = 1/2 <|u - <u>|^2> = 1/2 sum wt |w^|^2 / |k|^2    (fluctuation energy; the total is E + (U0^2 + V0^2) / 2)
+ *     Z = 1/2 <w^2>         = 1/2 sum wt |w^|^2
+ *     P = <f_s . u>         =     sum wt Re(psi^ conj g^)   (0 without a force)
+ * wt = 1 on the j = 0 line and 2 on j > 0, all normalised by (nx ny)^2, so that dE/dt = P - 2 nu Z - 2 drag E.  float64 sums in a fixed
+ * order (no atomics): they repeat bitwise and a grid's numbers do not depend on its batch neighbours.  No workspace; one launch. */
+int nns_spec_ns_diag_f32(const float* what, const float* ghat, int gbatch, double* out, int batch, int nx, int ny, double Lx, double Ly,
+                         void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

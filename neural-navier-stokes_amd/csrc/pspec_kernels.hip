@@ -18,6 +18,11 @@
 // (S = 0) that only prepares.  Nothing but the kept third of the spectral columns is ever read, transformed or written.
 // Decay factors are applied as z + expm1(x) z: the float32 rounding of E itself would be a systematic per-step error.
 //
+// Forcing and drag (nns_spec_ns_step_forced_f32; restatement: tests/pspec_forced_oracle.py): w_t + u w_x + v w_y = nu lap w - alpha w + g.
+// ps_col_kernel<nx, S, FORCED = true> adds the constant g^ (the state's layout, one per grid or one shared by the batch) to N^ in every
+// stage and uses L = -(nu |k|^2 + alpha); FORCED = false is the unforced code, argument list included.  ps_diag_kernel: energy,
+// enstrophy and power input per grid from w^ (and g^) by Parseval.
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 #include "nns_common.h"
 #include "fft_lds.h"
@@ -42,6 +47,13 @@ struct PsLds {
     static constexpr int TOTAL = TAB_BYTES + LINES * LINE_BYTES;
     static constexpr int SKEW_MOD = LINES < 32 ? LINES : 32, SKEW_DW = 32 / SKEW_MOD;
 };
+
+struct PsForce {          // the extra argument of the FORCED column kernels
+    const float2* g;      // g^ [gbatch][my1][nx] in the state's layout, or NULL (drag only)
+    int shared;           // 1: one g^ for every grid (gbatch = 1); 0: one per grid
+    float hdrag;          // alpha dt / 2
+};
+struct PsNoForce {};
 
 struct PsArgs {
     long nlines;          // row kernel: B nx rows; column kernel: B my1 columns
@@ -130,9 +142,12 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
 
 // ---------------------------------------------------------------------------------------------------- column pass (axis x)
 // S = 0: prepare stage 1 from W; S = 1..4: consume the RK stage's N (from Ph) and update W / A, then (S < 4 or emit) prepare the next stage.
-template <int N, int S>
+// FORCED (S >= 1): N^ += g^ on the kept modes (lane-owned, coalesced, like W / A) and L dt / 2 = hnudt |k|^2 - alpha dt / 2.
+template <int N, int S, bool FORCED = false>
 __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, float2* __restrict__ W,
-                                                    float2* __restrict__ A, const float* __restrict__ mean, PsArgs a, int emit) {
+                                                    float2* __restrict__ A, const float* __restrict__ mean, PsArgs a, int emit,
+                                                    std::conditional_t<FORCED, PsForce, PsNoForce> fc) {
+    static_assert(!FORCED || S >= 1, "stage 0 only prepares: it has no forced form");
     using L = PsLds<N>;
     constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -159,6 +174,12 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
         const bool lok = lcol < a.nlines;
         const int lb = lok ? (int)(lcol / my1) : 0, lj = lok ? (int)(lcol % my1) : 0;
         const size_t wbase = (size_t)(lok ? lcol : 0) * N;
+        [[maybe_unused]] size_t gbase = 0;
+        [[maybe_unused]] bool gok = false;
+        if constexpr (FORCED) {
+            gbase = fc.shared ? (size_t)lj * N : wbase;
+            gok = lok && fc.g != nullptr;
+        }
         int tv = tid;
         asm volatile("" : "+v"(tv));
         const float ky = a.ky1 * (float)lj;
@@ -189,9 +210,14 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
                 const int mx = m < 8 ? e : e - N;
                 const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (mx | lj) != 0;    // 2/3 rule in x (y: j < my1), no (0, 0)
                 const float kx = a.kx1 * (float)mx;
-                const float x = a.hnudt * (kx * kx + ky * ky);                     // L dt / 2
+                float x = a.hnudt * (kx * kx + ky * ky);                           // L dt / 2
+                if constexpr (FORCED) x -= fc.hdrag;
                 const float em1 = expm1f(x), em2 = expm1f(2.f * x);                // E - 1, E^2 - 1
-                const cf n = keep ? cf{-z[m].x, -z[m].y} : cf{0.f, 0.f};
+                cf n = keep ? cf{-z[m].x, -z[m].y} : cf{0.f, 0.f};
+                if constexpr (FORCED) {
+                    const float2 g = gok ? fc.g[gbase + e] : make_float2(0.f, 0.f);
+                    if (keep) n = {n.x + g.x, n.y + g.y};
+                }
                 const size_t si = wbase + e;
                 if constexpr (S == 1) {                 // a: A = E^2 (w + dt/6 a), next = E (w + dt/2 a)
                     const float2 w2 = lok ? W[si] : make_float2(0.f, 0.f);
@@ -327,6 +353,52 @@ __global__ void ps_pressure_kernel(float2* __restrict__ qh, int batch, int nx, i
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- diagnostics
+// out[b] = (E, Z, P): fluctuation energy 1/2 <|u - <u>|^2>, enstrophy 1/2 <w^2>, power input <f_s . u>, by Parseval over the stored half
+// spectrum (weight 1 on the j = 0 line, 2 on j > 0), normalised by (nx ny)^2.  One workgroup per grid; every lane sums its strided
+// elements in float64, then a wave64 shuffle tree and the waves' partials through LDS in index order: no atomics, so the sums repeat
+// bitwise and a grid's numbers do not depend on its batch neighbours.
+constexpr int kDiagT = 1024;
+
+__global__ __launch_bounds__(kDiagT) void ps_diag_kernel(const float2* __restrict__ W, const float2* __restrict__ Gh, int gshared,
+                                                          double* __restrict__ out, int nx, int my1, double kx1, double ky1, double inv_n2) {
+    __shared__ double part[kDiagT / kWave][3];
+    const long per = (long)my1 * nx;
+    const float2* w = W + (size_t)blockIdx.x * per;
+    const float2* g = Gh ? Gh + (gshared ? 0 : (size_t)blockIdx.x * per) : nullptr;
+    double e = 0., z = 0., p = 0.;
+    for (long q = threadIdx.x; q < per; q += kDiagT) {
+        const int i = (int)(q % nx), j = (int)(q / nx);
+        const int mx = i < nx / 2 ? i : i - nx;
+        const double kx = kx1 * mx, ky = ky1 * j, k2 = kx * kx + ky * ky;
+        const double ik2 = k2 > 0. ? 1. / k2 : 0.;
+        const double wt = j == 0 ? 1. : 2.;
+        const float2 c = w[q];
+        const double ww = (double)c.x * c.x + (double)c.y * c.y;
+        z += wt * ww;
+        e += wt * ww * ik2;
+        if (g) {
+            const float2 f = g[q];
+            p += wt * ik2 * ((double)c.x * f.x + (double)c.y * f.y);      // Re(psi^ conj g^)
+        }
+    }
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+        e += __shfl_xor(e, d, kWave);
+        z += __shfl_xor(z, d, kWave);
+        p += __shfl_xor(p, d, kWave);
+    }
+    const int wave = threadIdx.x / kWave;
+    if (threadIdx.x % kWave == 0) { part[wave][0] = e; part[wave][1] = z; part[wave][2] = p; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double se = 0., sz = 0., sp = 0.;
+        for (int k = 0; k < kDiagT / kWave; ++k) { se += part[k][0]; sz += part[k][1]; sp += part[k][2]; }
+        double* o = out + 3 * (size_t)blockIdx.x;
+        o[0] = 0.5 * se * inv_n2; o[1] = 0.5 * sz * inv_n2; o[2] = sp * inv_n2;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- host side
 inline bool pow2ok(int n) { return n >= 64 && n <= 1024 && (n & (n - 1)) == 0; }
 inline int kept_y(int ny) { return (ny - 1) / 3 + 1; }
@@ -364,12 +436,31 @@ template <int N, int S>
 int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, hipStream_t s) {
     auto kern = ps_col_kernel<N, S>;
     if (int rc = set_lds(kern, PsLds<N>::TOTAL)) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit);
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, PsNoForce{});
     return check_launch("spec_ns column pass");
 }
 
+template <int N, int S>
+int launch_col_forced(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce& fc,
+                      hipStream_t s) {
+    auto kern = ps_col_kernel<N, S, true>;
+    if (int rc = set_lds(kern, PsLds<N>::TOTAL)) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, fc);
+    return check_launch("spec_ns forced column pass");
+}
+
+// fc == nullptr: the unforced kernels (stage 0 has no other form)
 template <int N>
-int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, hipStream_t s) {
+int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
+                     hipStream_t s) {
+    if (fc && S >= 1) {
+        switch (S) {
+            case 1: return launch_col_forced<N, 1>(Ph, G, W, A, mean, a, emit, *fc, s);
+            case 2: return launch_col_forced<N, 2>(Ph, G, W, A, mean, a, emit, *fc, s);
+            case 3: return launch_col_forced<N, 3>(Ph, G, W, A, mean, a, emit, *fc, s);
+            default: return launch_col_forced<N, 4>(Ph, G, W, A, mean, a, emit, *fc, s);
+        }
+    }
     switch (S) {
         case 0: return launch_col<N, 0>(Ph, G, W, A, mean, a, emit, s);
         case 1: return launch_col<N, 1>(Ph, G, W, A, mean, a, emit, s);
@@ -432,12 +523,16 @@ NNS_API int nns_spec_ns_init_f32(const float* u, const float* v, float* what, fl
     return check_launch("spec_ns_init");
 }
 
-NNS_API int nns_spec_ns_step_f32(float* what, const float* mean, void* work, size_t work_bytes_, int batch, int nx, int ny, double Lx,
-                                 double Ly, double dt, double nu, int nsteps, void* stream) {
-    if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step: NULL pointer or batch < 1");
+// The step of both entry points: ghat == NULL and drag == 0 launch the unforced kernels.
+static int spec_ns_step(const char* who, float* what, const float* mean, const float* ghat, int gbatch, void* work, size_t work_bytes_,
+                        int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, int nsteps, void* stream) {
+    if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
     if (!(dt > 0) || !std::isfinite(dt) || !(nu >= 0) || !std::isfinite(nu) || nsteps < 0)
-        return fail(NNS_ERR_INVALID_ARG, "spec_ns_step: dt = %g must be > 0, nu = %g >= 0, nsteps = %d >= 0", dt, nu, nsteps);
-    if (int rc = check_common("spec_ns_step", batch, nx, ny, Lx, Ly, work, work_bytes_)) return rc;
+        return fail(NNS_ERR_INVALID_ARG, "%s: dt = %g must be > 0, nu = %g >= 0, nsteps = %d >= 0", who, dt, nu, nsteps);
+    if (!(drag >= 0) || !std::isfinite(drag)) return fail(NNS_ERR_INVALID_ARG, "%s: drag = %g must be finite and >= 0", who, drag);
+    if (ghat ? (gbatch != 1 && gbatch != batch) : gbatch != 0)
+        return fail(NNS_ERR_INVALID_ARG, "%s: gbatch = %d must be 0 without ghat, 1 or batch = %d with it", who, gbatch, batch);
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work, work_bytes_)) return rc;
     if (nsteps == 0) return NNS_OK;
     hipStream_t s = S_(stream);
     const int my1 = kept_y(ny);
@@ -450,7 +545,9 @@ NNS_API int nns_spec_ns_step_f32(float* what, const float* mean, void* work, siz
               (float)(1.0 / ((double)nx * ny))};
     PsArgs ar = ac;
     ar.nlines = (long)batch * nx;
-    auto col = [&](int S, int emit) { return dispatch(nx, [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, s); }); };
+    const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
+    const PsForce* fc = ghat || drag > 0 ? &force : nullptr;
+    auto col = [&](int S, int emit) { return dispatch(nx, [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, fc, s); }); };
     auto row = [&]() { return dispatch(ny, [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, s); }); };
     if (int rc = col(0, 1)) return rc;
     for (int k = 0; k < nsteps; ++k) {
@@ -460,6 +557,33 @@ NNS_API int nns_spec_ns_step_f32(float* what, const float* mean, void* work, siz
         }
     }
     return NNS_OK;
+}
+
+NNS_API int nns_spec_ns_step_f32(float* what, const float* mean, void* work, size_t work_bytes_, int batch, int nx, int ny, double Lx,
+                                 double Ly, double dt, double nu, int nsteps, void* stream) {
+    return spec_ns_step("spec_ns_step", what, mean, nullptr, 0, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, 0.0, nsteps, stream);
+}
+
+NNS_API int nns_spec_ns_step_forced_f32(float* what, const float* mean, const float* ghat, int gbatch, void* work, size_t work_bytes_,
+                                        int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, int nsteps,
+                                        void* stream) {
+    return spec_ns_step("spec_ns_step_forced", what, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, drag, nsteps, stream);
+}
+
+NNS_API int nns_spec_ns_diag_f32(const float* what, const float* ghat, int gbatch, double* out, int batch, int nx, int ny, double Lx,
+                                 double Ly, void* stream) {
+    if (!what || !out || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_diag: NULL pointer or batch < 1");
+    if (ghat ? (gbatch != 1 && gbatch != batch) : gbatch != 0)
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_diag: gbatch = %d must be 0 without ghat, 1 or batch = %d with it", gbatch, batch);
+    if (!(Lx > 0) || !(Ly > 0) || !std::isfinite(Lx) || !std::isfinite(Ly))
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_diag: Lx = %g, Ly = %g must be positive and finite", Lx, Ly);
+    if (!pow2ok(nx) || !pow2ok(ny))
+        return fail(NNS_ERR_UNSUPPORTED, "spec_ns_diag: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", nx, ny);
+    const double n = (double)nx * ny;
+    hipLaunchKernelGGL(ps_diag_kernel, dim3(batch), dim3(kDiagT), 0, S_(stream), reinterpret_cast<const float2*>(what),
+                       reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, out, nx, kept_y(ny), 2.0 * M_PI / Lx,
+                       2.0 * M_PI / Ly, 1.0 / (n * n));
+    return check_launch("spec_ns_diag");
 }
 
 NNS_API int nns_spec_ns_fields_f32(const float* what, const float* mean, float* u, float* v, float* p, void* work, size_t work_bytes_,

@@ -925,6 +925,51 @@ def spec_ns_fields(what, mean, work, ny, Lx, Ly, rho, out=None):
     return out
 
 
+def _spec_ns_force(who, ghat, what):
+    """gbatch of the force spectrum ghat (None: 0) for the state what: float32 [1 or B, my1, nx, 2] on what's device."""
+    if ghat is None:
+        return 0
+    _f32(ghat)
+    B = what.shape[0]
+    if ghat.dim() != 4 or tuple(ghat.shape[1:]) != tuple(what.shape[1:]) or ghat.shape[0] not in (1, B):
+        raise ValueError("%s: ghat must be float32 [1 or %d, %d, %d, 2], got %s" % (who, B, what.shape[1], what.shape[2], tuple(ghat.shape)))
+    if ghat.device != what.device:
+        raise ValueError("%s: ghat is on %s, the state on %s" % (who, ghat.device, what.device))
+    return int(ghat.shape[0])
+
+
+def spec_ns_step_forced_(what, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, nsteps=1):
+    """nsteps Lawson-RK4 steps with the force spectrum ghat ([1, my1, nx, 2]: shared by the batch, [B, my1, nx, 2]: one per grid, None: no
+    force) and the linear drag `drag` on what in place (no allocation, no host synchronisation: capturable)."""
+    B, my1, nx = _spec_ns_state(what, mean, work)
+    if my1 != spec_ns_kept_y(ny):
+        raise ValueError("spec_ns_step_forced_: what has %d kept y-wavenumbers, ny = %d needs %d" % (my1, ny, spec_ns_kept_y(ny)))
+    gbatch = _spec_ns_force('spec_ns_step_forced_', ghat, what)
+    check(_lib.lib().nns_spec_ns_step_forced_f32(_p(what), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(work), work.numel(), B, nx,
+                                                 int(ny), float(Lx), float(Ly), float(dt), float(nu), float(drag), int(nsteps), _stream()),
+          'nns_spec_ns_step_forced_f32')
+    return what
+
+
+def spec_ns_diag(what, ghat, ny, Lx, Ly, out=None):
+    """float64 [B, 3]: fluctuation energy, enstrophy and power input <f_s . u> (0 with ghat None) of every grid of the state."""
+    _f32(what)
+    if what.dim() != 4 or what.shape[3] != 2:
+        raise ValueError("spec_ns_diag: what must be float32 [B, my1, nx, 2], got %s" % (tuple(what.shape),))
+    B, my1, nx = what.shape[0], what.shape[1], what.shape[2]
+    if my1 != spec_ns_kept_y(ny):
+        raise ValueError("spec_ns_diag: what has %d kept y-wavenumbers, ny = %d needs %d" % (my1, ny, spec_ns_kept_y(ny)))
+    gbatch = _spec_ns_force('spec_ns_diag', ghat, what)
+    if out is None:
+        out = torch.empty((B, 3), dtype=torch.float64, device=what.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (B, 3) and out.is_contiguous()
+              and out.device == what.device):
+        raise ValueError("spec_ns_diag: out must be a contiguous float64 [%d, 3] tensor on the state's device" % B)
+    check(_lib.lib().nns_spec_ns_diag_f32(_p(what), _p(ghat) if gbatch else None, gbatch, _p(out), B, nx, int(ny), float(Lx), float(Ly),
+                                          _stream()), 'nns_spec_ns_diag_f32')
+    return out
+
+
 # ----------------------------------------------------------------------------- physics-informed loss head
 _PINN_WS = {}
 

@@ -16,8 +16,10 @@ library picks that mode while its viscous amplification nu pi N / (sqrt(3) L) st
 otherwise, 2 = float64 forward transforms always.
 
 ``PeriodicSolver`` produces the trajectories such a residual measures: a pseudo-spectral solver of the same equations on the same box
-(csrc/pspec_kernels.hip; scheme in DESIGN.md and tests/pspec_oracle.py).
+(csrc/pspec_kernels.hip; scheme in DESIGN.md and tests/pspec_oracle.py), optionally with a steady body force and a linear drag
+(tests/pspec_forced_oracle.py).
 """
+import collections
 import math
 import numbers
 
@@ -102,6 +104,9 @@ def _count(name, n, minimum):
     return int(n)
 
 
+Diagnostics = collections.namedtuple('Diagnostics', ['energy', 'enstrophy', 'power_in'])
+
+
 class PeriodicState(object):
     """State of a PeriodicSolver run; owns its device buffers.
     what: the vorticity spectrum, compacted to the kept y-wavenumbers and transposed (float32 [B, my1, nx, 2], include/nns.h: nns_spec_ns_*);
@@ -129,14 +134,23 @@ class PeriodicSolver(object):
 
     ``init(u, v)`` PROJECTS the input: the state keeps the vorticity of (u, v) inside the 2/3 band and the grid means (U0, V0), so
     ``fields(init(u, v))`` returns the divergence-free, band-limited part of (u, v) -- equal to it when (u, v) already is one.
-    The mean velocity is conserved.  ``p`` is the pressure of the velocity field: lap p = 2 rho (u_x v_y - u_y v_x), zero mean."""
+    The mean velocity is conserved.  ``p`` is the pressure of the velocity field: lap p = 2 rho (u_x v_y - u_y v_x), zero mean.
 
-    def __init__(self, nx, ny, dt, rho, nu, Lx=2 * math.pi, Ly=2 * math.pi):
+    Forcing and drag: with ``set_forcing(fx, fy)`` (a force constant in time) and ``drag`` = alpha >= 0 the solver integrates
+        u_t + (u . grad) u = -grad p / rho + nu lap u - alpha (u - <u>) + f_s
+    where <.> is the grid mean and f_s the solenoidal, zero-mean, band-limited part of f (``forcing_fields()``): a gradient part of f only
+    shifts the pressure and a mean part only accelerates the frame, so both are dropped, as ``init`` drops them from a velocity.  The mean
+    velocity stays conserved and undamped and ``p`` keeps its definition (div f_s = 0).  ``diagnostics(state)`` gives energy, enstrophy and
+    the power input of the force per grid.  Without a force and with drag == 0 every call takes the unforced path."""
+
+    def __init__(self, nx, ny, dt, rho, nu, Lx=2 * math.pi, Ly=2 * math.pi, drag=0.0):
         self.nx, self.ny = _pow2_axis('nx', nx), _pow2_axis('ny', ny)
         self.dt, self.rho = _real('dt', dt), _real('rho', rho)
         self.nu = _real('nu', nu, positive=False)
         self.Lx, self.Ly = _real('Lx', Lx), _real('Ly', Ly)
+        self.drag = _real('drag', drag, positive=False)
         self.my1 = ops.spec_ns_kept_y(self.ny)
+        self.ghat = None                       # the force's vorticity-equation spectrum g^, float32 [Bg, my1, nx, 2] (set_forcing)
         self.last_simulate_used_graph = False
 
     def _field(self, name, a):
@@ -176,13 +190,81 @@ class PeriodicSolver(object):
         ops.spec_ns_init(u, v, what, mean, work, self.Lx, self.Ly)
         return PeriodicState(what, mean, work)
 
+    # ---- forcing
+    def set_forcing(self, fx, fy=None):
+        """Body force (fx, fy), constant in time: float32 [nx, ny] or [1, nx, ny] (shared by every grid of a batch) or [B, nx, ny] (one per
+        grid; the states stepped afterwards must have that batch).  Only its solenoidal, zero-mean, band-limited part acts
+        (``forcing_fields``); its spectrum g^ = M (i kx fy^ - i ky fx^) is built on the device and kept as ``self.ghat``.
+        ``set_forcing(None)`` removes the force."""
+        if fx is None:
+            if fy is not None:
+                raise ValueError("set_forcing: fx is None but fy is not")
+            self.ghat = None
+            return self
+        fx, fy = self._field('fx', fx), self._field('fy', fy)
+        if fx.shape != fy.shape:
+            raise ValueError("fx and fy must share their shape")
+        self.ghat = self.init(fx, fy).what          # the force is to g^ what the velocity is to w^
+        return self
+
+    def kolmogorov_forcing(self, k=4, amplitude=1.0):
+        """f = (amplitude sin(2 pi k y / Ly), 0), shared by the batch; k an integer wavenumber inside the kept band (1 <= k, 3 k < ny)."""
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+            raise TypeError("k must be an int, got %r" % (k,))
+        if not (1 <= k and 3 * k < self.ny):
+            raise ValueError("k = %d is outside the kept band 1 <= k, 3 k < ny = %d" % (k, self.ny))
+        if isinstance(amplitude, bool) or not isinstance(amplitude, numbers.Real):
+            raise TypeError("amplitude must be a real number, got %r" % (amplitude,))
+        if not math.isfinite(amplitude):
+            raise ValueError("amplitude = %r must be finite" % (amplitude,))
+        y = np.arange(self.ny) / float(self.ny)
+        fx = np.broadcast_to(float(amplitude) * np.sin(2 * np.pi * int(k) * y), (self.nx, self.ny)).astype(np.float32)
+        return self.set_forcing(fx, np.zeros_like(fx))
+
+    def forcing_fields(self):
+        """(f_sx, f_sy) float32 [Bg, nx, ny]: the part of the force that acts (None without a force)."""
+        if self.ghat is None:
+            return None
+        Bg = self.ghat.shape[0]
+        zero = torch.zeros((Bg, 2), dtype=torch.float32, device=self.ghat.device)
+        work = torch.empty(ops.spec_ns_workspace(Bg, self.nx, self.ny), dtype=torch.uint8, device=self.ghat.device)
+        return ops.spec_ns_fields(self.ghat, zero, work, self.ny, self.Lx, self.Ly, self.rho)[:2]
+
+    def _forced(self):
+        return self.ghat is not None or self.drag > 0
+
+    def _force_of(self, state):
+        """The force spectrum for this state (None without one); refuses a per-grid force of another batch or device before any launch."""
+        g = self.ghat
+        if g is not None:
+            if g.shape[0] not in (1, state.batch):
+                raise ValueError("the force is per grid for a batch of %d, the state has %d grids" % (g.shape[0], state.batch))
+            if g.device != state.what.device:
+                raise ValueError("the force is on %s, the state on %s" % (g.device, state.what.device))
+        return g
+
+    def _launch_steps(self, state, nsteps):
+        if self._forced():
+            ops.spec_ns_step_forced_(state.what, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu,
+                                     self.drag, nsteps)
+        else:
+            ops.spec_ns_step_(state.what, state.mean, state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu, nsteps)
+
     def step(self, state, nsteps=1):
         """nsteps time steps in place (no allocation, no host synchronisation)."""
         self._state(state)
         nsteps = _count('nsteps', nsteps, 0)
-        ops.spec_ns_step_(state.what, state.mean, state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu, nsteps)
+        self._launch_steps(state, nsteps)
         state.steps += nsteps
         return state
+
+    def diagnostics(self, state):
+        """Diagnostics(energy, enstrophy, power_in), each float64 [B], computed on the device from the state's spectrum:
+        energy = 1/2 <|u - <u>|^2> (the total is energy + (U0^2 + V0^2) / 2), enstrophy = 1/2 <w^2>, power_in = <f_s . u> (exactly 0
+        without a force), so that d energy / dt = power_in - 2 nu enstrophy - 2 drag energy."""
+        self._state(state)
+        out = ops.spec_ns_diag(state.what, self._force_of(state), self.ny, self.Lx, self.Ly)
+        return Diagnostics(out[:, 0], out[:, 1], out[:, 2])
 
     def fields(self, state, out=None):
         """(u, v, p) float32 [B, nx, ny] of the state (into ``out`` if given)."""
@@ -196,7 +278,11 @@ class PeriodicSolver(object):
         nsteps, save_every = _count('nsteps', nsteps, 0), _count('save_every', save_every, 1)
         if nsteps % save_every:
             raise ValueError("nsteps = %d is not a multiple of save_every = %d" % (nsteps, save_every))
+        if self.ghat is not None and self.ghat.shape[0] not in (1, self._field('u', u0).shape[0]):
+            raise ValueError("the force is per grid for a batch of %d, the initial condition has %d grids"
+                             % (self.ghat.shape[0], self._field('u', u0).shape[0]))
         state = self.init(u0, v0)
+        self._force_of(state)
         T = nsteps // save_every + 1
         U = torch.empty((T, state.batch, self.nx, self.ny), dtype=torch.float32, device=state.what.device)
         V, P = torch.empty_like(U), torch.empty_like(U)
@@ -214,7 +300,7 @@ class PeriodicSolver(object):
                 torch.cuda.current_stream().wait_stream(side)
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
-                    ops.spec_ns_step_(state.what, state.mean, state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu, 1)
+                    self._launch_steps(state, 1)
             except Exception as e:                                   # noqa: BLE001 -- the eager loop is the same computation
                 print('PeriodicSolver: HIP graph capture of the step failed (%r): running eagerly' % (e,))
                 graph = None
@@ -230,6 +316,8 @@ class PeriodicSolver(object):
         return U, V, P
 
     def residual_engine(self, backend='spectral', precise=True, every=1):
-        """A ResidualEngine with this solver's constants, for frames ``every`` steps apart (its dt = every * dt)."""
+        """A ResidualEngine with this solver's constants, for frames ``every`` steps apart (its dt = every * dt).  The engine knows neither
+        force nor drag: on the frames of a forced run its momentum residuals converge (as dt -> 0) to f_s - drag (u - <u>), the right-hand
+        side of the class note, rather than to zero; subtract that (``forcing_fields``) to measure the discretisation alone."""
         every = _count('every', every, 1)
         return ResidualEngine(self.nx, self.ny, self.dt * every, self.rho, self.nu, self.Lx, self.Ly, backend=backend, precise=precise)

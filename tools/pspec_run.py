@@ -3,10 +3,16 @@ against a COMPOSED step of the same scheme on the same inputs in the same run: t
 spec_irfft2 plus torch elementwise ops on full rfft2-layout spectra.  Writes ONE JSON record to OUTDIR/pspec_run.json and prints it.
 
     python tools/pspec_run.py OUTDIR [--steps 20] [--reps 5]
+    python tools/pspec_run.py OUTDIR --forced [--steps 20] [--reps 7] [--commit ID]
 
 Cases: 256^2 x B = 64 and 1024^2 x B = 8, |m| <= 8 initial condition (tests/pspec_oracle.py: random_ic), nu = 1e-3.  Per case: ms per
 step of each (device events around `steps` steps, warmed, median of `reps`), the bytes-per-point model of each (below) and the rel-L2
-difference of the two after `steps` steps (same scheme, float32 both: rounding only)."""
+difference of the two after `steps` steps (same scheme, float32 both: rounding only).
+
+--forced instead times the forced step (Kolmogorov force k = 4, drag 0.1: nns_spec_ns_step_forced_f32) next to the unforced step of the
+same build on the same state, the three variants (unforced, shared force, per-grid force) taking turns within every repetition, and one
+diagnostics call next to one fields call (256^2 x 64 and 1024^2 x 1).  Writes ONE record to OUTDIR/pspec_forced_run.json: per variant the
+median ms per step and the spread (max - min) / median over the repetitions, the ratios to the unforced step and the byte model's 54 / 50."""
 import argparse
 import json
 import math
@@ -94,13 +100,83 @@ def timed(fn, reps):
     return float(np.median(ts))
 
 
+def event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def stats(ts, per=1):
+    med = float(np.median(ts))
+    return dict(ms=round(med / per, 5), spread=round((max(ts) - min(ts)) / med, 4))
+
+
+def forced_main(args):
+    rec = dict(device=torch.cuda.get_device_name(0), commit=args.commit, steps=args.steps, reps=args.reps,
+               byte_model_ratio=round(54 / 50, 3), cases=[], diagnostics=[])
+    dev = lambda a: torch.as_tensor(a, dtype=torch.float32, device='cuda')
+    for n, B in CASES:
+        u0, v0 = O.random_ic(B, n, n, 8, seed=n + B, umax=1.0)
+        fx, fy = O.random_ic(B, n, n, 8, seed=n + B + 1, umax=1.0)
+        plain = PeriodicSolver(n, n, 1e-3, 1.0, 1e-3)
+        shared = PeriodicSolver(n, n, 1e-3, 1.0, 1e-3, drag=0.1).kolmogorov_forcing(4, 1.0)
+        per_grid = PeriodicSolver(n, n, 1e-3, 1.0, 1e-3, drag=0.1).set_forcing(dev(fx), dev(fy))
+        st = plain.init(dev(u0), dev(v0))
+        w0 = st.what.clone()
+        variants = [('unforced', plain), ('forced_shared', shared), ('forced_per_grid', per_grid)]
+        ts = {name: [] for name, _ in variants}
+        for name, s in variants:                                  # warm every kernel of every variant
+            s.step(st, 2)
+        torch.cuda.synchronize()
+        for _ in range(args.reps):
+            for name, s in variants:
+                st.what.copy_(w0)
+                ts[name].append(event_ms(lambda: s.step(st, args.steps)))
+        case = dict(nx=n, ny=n, batch=B)
+        for name, _ in variants:
+            case[name] = stats(ts[name], args.steps)
+        for name in ('forced_shared', 'forced_per_grid'):
+            case[name + '_over_unforced'] = round(case[name]['ms'] / case['unforced']['ms'], 4)
+        rec['cases'].append(case)
+        print(json.dumps(case), flush=True)
+        del st
+        torch.cuda.empty_cache()
+    for n, B in ((256, 64), (1024, 1)):
+        s = PeriodicSolver(n, n, 1e-3, 1.0, 1e-3, drag=0.1).kolmogorov_forcing(4, 1.0)
+        u0, v0 = O.random_ic(B, n, n, 8, seed=n + B, umax=1.0)
+        st = s.init(dev(u0), dev(v0))
+        out = tuple(torch.empty(B, n, n, device='cuda') for _ in range(3))
+        s.diagnostics(st), s.fields(st, out=out)
+        torch.cuda.synchronize()
+        td, tf = [], []
+        for _ in range(args.reps):
+            td.append(event_ms(lambda: [s.diagnostics(st) for _ in range(10)]))
+            tf.append(event_ms(lambda: [s.fields(st, out=out) for _ in range(10)]))
+        d = dict(nx=n, ny=n, batch=B, diagnostics=stats(td, 10), fields=stats(tf, 10))
+        rec['diagnostics'].append(d)
+        print(json.dumps(d), flush=True)
+    os.makedirs(args.outdir, exist_ok=True)
+    with open(os.path.join(args.outdir, 'pspec_forced_run.json'), 'w') as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('outdir')
     ap.add_argument('--steps', type=int, default=20)
-    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--reps', type=int, default=None)
+    ap.add_argument('--forced', action='store_true', help='time the forced step and the diagnostics instead (see the module note)')
+    ap.add_argument('--commit', default='unknown', help='recorded in the --forced record')
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 7 if args.forced else 5
     torch.cuda.set_device(0)
+    if args.forced:
+        return forced_main(args)
     rec = dict(device=torch.cuda.get_device_name(0), steps=args.steps, reps=args.reps, cases=[])
     for n, B in CASES:
         s = PeriodicSolver(n, n, 1e-3, 1.0, 1e-3)
