@@ -78,14 +78,12 @@ __global__ __launch_bounds__(256) void cheb_embed_kernel(const double* sol, cons
 
 }  // namespace
 
-#define S(stream) reinterpret_cast<hipStream_t>(stream)
-
 NNS_API int nns_cheb_gemm_f64(const double* A, int lda, int transA, const double* B, int ldb, int transB, double* C, int ldc,
                               int M, int N, int K, double alpha, double beta, int batch, void* stream) {
     if (!A || !B || !C || M < 1 || N < 1 || K < 1 || batch < 1 || lda < 1 || ldb < 1 || ldc < N)
         return fail(NNS_ERR_INVALID_ARG, "cheb_gemm: bad args (M=%d N=%d K=%d lda=%d ldb=%d ldc=%d)", M, N, K, lda, ldb, ldc);
     if (batch > 65535) return fail(NNS_ERR_UNSUPPORTED, "cheb_gemm: batch > 65535");
-    hipLaunchKernelGGL(cheb_gemm_kernel, dim3((N + 15) / 16, (M + 15) / 16, batch), dim3(64), 0, S(stream), A, lda, transA, B, ldb, transB, C, ldc, M, N, K, alpha, beta);
+    hipLaunchKernelGGL(cheb_gemm_kernel, dim3((N + 15) / 16, (M + 15) / 16, batch), dim3(64), 0, as_stream(stream), A, lda, transA, B, ldb, transB, C, ldc, M, N, K, alpha, beta);
     return check_launch("cheb_gemm");
 }
 
@@ -93,20 +91,20 @@ NNS_API int nns_cheb_helmholtz_rhs_f64(const double* f, const double* un, const 
                                        const double* fx, const double* fy, const double* f1x, const double* f1y, const double* fxx,
                                        const double* fyy, double* F, int n, double dt, void* stream) {
     if (!f || !un || !vn || !un1 || !vn1 || !fx || !fy || !f1x || !f1y || !fxx || !fyy || !F || n < 1) return fail(NNS_ERR_INVALID_ARG, "cheb_helmholtz_rhs: bad args");
-    hipLaunchKernelGGL(cheb_rhs_kernel, dim3((n + 255) / 256), dim3(256), 0, S(stream), f, un, vn, un1, vn1, fx, fy, f1x, f1y, fxx, fyy, F, n, dt);
+    hipLaunchKernelGGL(cheb_rhs_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), f, un, vn, un1, vn1, fx, fy, f1x, f1y, fxx, fyy, F, n, dt);
     return check_launch("cheb_helmholtz_rhs");
 }
 
 NNS_API int nns_cheb_diag_div_f64(const double* Hm, const double* lam_x, const double* lam_y, double* out, int ni, int nj,
                                   double c0, double cx, double cy, void* stream) {
     if (!Hm || !lam_x || !lam_y || !out || ni < 1 || nj < 1) return fail(NNS_ERR_INVALID_ARG, "cheb_diag_div: bad args");
-    hipLaunchKernelGGL(cheb_diag_div_kernel, dim3((ni * nj + 255) / 256), dim3(256), 0, S(stream), Hm, lam_x, lam_y, out, ni, nj, c0, cx, cy);
+    hipLaunchKernelGGL(cheb_diag_div_kernel, dim3((ni * nj + 255) / 256), dim3(256), 0, as_stream(stream), Hm, lam_x, lam_y, out, ni, nj, c0, cx, cy);
     return check_launch("cheb_diag_div");
 }
 
 NNS_API int nns_cheb_embed_f64(const double* sol, const double* x0, const double* xN, const double* y0, const double* yN, double* full,
                                int Nx, int Ny, void* stream) {
     if (!sol || !x0 || !xN || !y0 || !yN || !full || Nx < 3 || Ny < 3) return fail(NNS_ERR_INVALID_ARG, "cheb_embed: bad args");
-    hipLaunchKernelGGL(cheb_embed_kernel, dim3((Nx * Ny + 255) / 256), dim3(256), 0, S(stream), sol, x0, xN, y0, yN, full, Nx, Ny);
+    hipLaunchKernelGGL(cheb_embed_kernel, dim3((Nx * Ny + 255) / 256), dim3(256), 0, as_stream(stream), sol, x0, xN, y0, yN, full, Nx, Ny);
     return check_launch("cheb_embed");
 }

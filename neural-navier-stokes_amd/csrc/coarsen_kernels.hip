@@ -105,9 +105,9 @@ int coarsen(const T* u, const T* v, const T* p, T* cu, T* cv, T* cp, int nt, int
 
 NNS_API int nns_coarsen_f32(const float* u, const float* v, const float* p, float* cu, float* cv, float* cp, int nt, int nx, int ny,
                             int agg_x, int agg_y, int jfill, void* stream) {
-    return coarsen<float>(u, v, p, cu, cv, cp, nt, nx, ny, agg_x, agg_y, jfill, reinterpret_cast<hipStream_t>(stream));
+    return coarsen<float>(u, v, p, cu, cv, cp, nt, nx, ny, agg_x, agg_y, jfill, as_stream(stream));
 }
 NNS_API int nns_coarsen_f64(const double* u, const double* v, const double* p, double* cu, double* cv, double* cp, int nt, int nx, int ny,
                             int agg_x, int agg_y, int jfill, void* stream) {
-    return coarsen<double>(u, v, p, cu, cv, cp, nt, nx, ny, agg_x, agg_y, jfill, reinterpret_cast<hipStream_t>(stream));
+    return coarsen<double>(u, v, p, cu, cv, cp, nt, nx, ny, agg_x, agg_y, jfill, as_stream(stream));
 }

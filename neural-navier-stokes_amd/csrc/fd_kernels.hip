@@ -474,22 +474,19 @@ int predictor_adi(const T* un, const T* vn, const T* un1, const T* vn1, T* ui, T
     const bool small = lds_path && lds_all <= 150 * 1024;
     if (small) {
         // right-hand sides chip-wide, then one workgroup per grid for the two solves (a grid of one row of workgroups would spend 27 us on them)
-        auto solve = [&](auto kern, int slot) -> int {
-            static bool attr2[2] = {false, false};
-            if (!attr2[slot]) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-                if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "fd_predictor_adi: hipFuncSetAttribute: %s", hipGetErrorString(e));
-                attr2[slot] = true;
-            }
-            hipLaunchKernelGGL(adi_rhs1_kernel<T>, dim3((ny + kTX - 1) / kTX, nx, 2 * batch), dim3(kTX), 0, s, un, vn, un1, vn1, work, nx, ny, k);
+        auto solve = [&](auto corr) -> int {
+            constexpr auto rhs = adi_rhs1_kernel<T>;                  // (named in launch order: the object lists its kernels by first use)
+            constexpr auto kern = predictor_adi_lds_kernel<T, decltype(corr)::value, true>;
+            if (int rc = lds_opt_in<kern>(150 * 1024, "fd_predictor_adi")) return rc;
+            hipLaunchKernelGGL(rhs, dim3((ny + kTX - 1) / kTX, nx, 2 * batch), dim3(kTX), 0, s, un, vn, un1, vn1, work, nx, ny, k);
             hipLaunchKernelGGL(kern, dim3(batch), dim3(kAdiLdsThreads), lds_all, s, un, vn, un1, vn1, ui, vi, work, nx, ny, k);
             return NNS_OK;
         };
         if (!corrected) {
-            if (int rc = solve(predictor_adi_lds_kernel<T, false, true>, 0)) return rc;
+            if (int rc = solve(std::false_type{})) return rc;
             return check_launch("fd_predictor_adi");
         }
-        if (int rc = solve(predictor_adi_lds_kernel<T, true, true>, 1)) return rc;
+        if (int rc = solve(std::true_type{})) return rc;
         if (int rc = check_launch("fd_predictor_adi (x solve)")) return rc;
     } else {
         if (!corrected) {
@@ -503,12 +500,7 @@ int predictor_adi(const T* un, const T* vn, const T* un1, const T* vn1, T* ui, T
     }
     const size_t shy = ((size_t)ny + 2 * 64 * 65) * sizeof(T);
     if (shy > 150 * 1024) return fail(NNS_ERR_UNSUPPORTED, "fd_predictor_adi_corrected: ny=%d too large for the LDS diagonal cache", ny);
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(adi_ysolve_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "fd_predictor_adi_corrected: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr = true;
-    }
+    if (int rc = lds_opt_in<adi_ysolve_kernel<T>>(150 * 1024, "fd_predictor_adi_corrected")) return rc;
     hipLaunchKernelGGL(adi_ysolve_kernel<T>, dim3((nx + 63) / 64, 2, batch), dim3(64), shy, s, un, vn, work, ui, vi, nx, ny, k);
     return check_launch("fd_predictor_adi (y solve)");
 }
@@ -663,12 +655,7 @@ int jacobi(T* p, T* tmp, const T* b, int batch, int nx, int ny, double dx, doubl
     const JacK<T> k = make_jac<T>(dx, dy);
     const size_t lds = 3 * (size_t)nx * ny * sizeof(T);
     if (lds <= 150 * 1024) {
-        static bool attr = false;
-        if (!attr) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_lds_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "fd_jacobi: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr = true;
-        }
+        if (int rc = lds_opt_in<jacobi_lds_kernel<T>>(150 * 1024, "fd_jacobi")) return rc;
         hipLaunchKernelGGL(jacobi_lds_kernel<T>, dim3(batch), dim3(1024), lds, s, p, b, nx, ny, nit, k, d);
         return check_launch("fd_jacobi(lds)");
     }
@@ -724,26 +711,25 @@ int direct_update(const T* un, const T* vn, const T* p, T* u, T* v, int batch, i
 }  // namespace
 
 // ---------------------------------------------------------------------------- C ABI
-#define S(stream) reinterpret_cast<hipStream_t>(stream)
 
-NNS_API int nns_bc_apply_f32(float* A, int batch, int nx, int ny, const nns_bc_list* bcs, void* stream) { return bc_apply<float>(A, batch, nx, ny, bcs, S(stream)); }
-NNS_API int nns_bc_apply_f64(double* A, int batch, int nx, int ny, const nns_bc_list* bcs, void* stream) { return bc_apply<double>(A, batch, nx, ny, bcs, S(stream)); }
+NNS_API int nns_bc_apply_f32(float* A, int batch, int nx, int ny, const nns_bc_list* bcs, void* stream) { return bc_apply<float>(A, batch, nx, ny, bcs, as_stream(stream)); }
+NNS_API int nns_bc_apply_f64(double* A, int batch, int nx, int ny, const nns_bc_list* bcs, void* stream) { return bc_apply<double>(A, batch, nx, ny, bcs, as_stream(stream)); }
 
 NNS_API int nns_fd_predictor_explicit_f32(const float* un, const float* vn, const float* un1, const float* vn1, float* ui, float* vi,
                                           int batch, int nx, int ny, double dt, double dx, double dy, double nu, void* stream) {
-    return predictor_explicit<float>(un, vn, un1, vn1, ui, vi, batch, nx, ny, dt, dx, dy, nu, S(stream));
+    return predictor_explicit<float>(un, vn, un1, vn1, ui, vi, batch, nx, ny, dt, dx, dy, nu, as_stream(stream));
 }
 NNS_API int nns_fd_predictor_explicit_corrected_f32(const float* un, const float* vn, const float* un1, const float* vn1, float* ui, float* vi,
                                                     int batch, int nx, int ny, double dt, double dx, double dy, double nu, void* stream) {
-    return predictor_explicit<float>(un, vn, un1, vn1, ui, vi, batch, nx, ny, dt, dx, dy, nu, S(stream), true);
+    return predictor_explicit<float>(un, vn, un1, vn1, ui, vi, batch, nx, ny, dt, dx, dy, nu, as_stream(stream), true);
 }
 NNS_API int nns_fd_predictor_explicit_corrected_f64(const double* un, const double* vn, const double* un1, const double* vn1, double* ui, double* vi,
                                                     int batch, int nx, int ny, double dt, double dx, double dy, double nu, void* stream) {
-    return predictor_explicit<double>(un, vn, un1, vn1, ui, vi, batch, nx, ny, dt, dx, dy, nu, S(stream), true);
+    return predictor_explicit<double>(un, vn, un1, vn1, ui, vi, batch, nx, ny, dt, dx, dy, nu, as_stream(stream), true);
 }
 NNS_API int nns_fd_predictor_explicit_f64(const double* un, const double* vn, const double* un1, const double* vn1, double* ui, double* vi,
                                           int batch, int nx, int ny, double dt, double dx, double dy, double nu, void* stream) {
-    return predictor_explicit<double>(un, vn, un1, vn1, ui, vi, batch, nx, ny, dt, dx, dy, nu, S(stream));
+    return predictor_explicit<double>(un, vn, un1, vn1, ui, vi, batch, nx, ny, dt, dx, dy, nu, as_stream(stream));
 }
 
 NNS_API size_t nns_fd_predictor_adi_workspace(int batch, int nx, int ny, int elem_size) {
@@ -752,62 +738,62 @@ NNS_API size_t nns_fd_predictor_adi_workspace(int batch, int nx, int ny, int ele
 }
 NNS_API int nns_fd_predictor_adi_f32(const float* un, const float* vn, const float* un1, const float* vn1, float* ui, float* vi, float* work,
                                      int batch, int nx, int ny, double dt, double dx, double dy, double nu, void* stream) {
-    return predictor_adi<float>(un, vn, un1, vn1, ui, vi, work, batch, nx, ny, dt, dx, dy, nu, S(stream));
+    return predictor_adi<float>(un, vn, un1, vn1, ui, vi, work, batch, nx, ny, dt, dx, dy, nu, as_stream(stream));
 }
 NNS_API int nns_fd_predictor_adi_corrected_f32(const float* un, const float* vn, const float* un1, const float* vn1, float* ui, float* vi, float* work,
                                                int batch, int nx, int ny, double dt, double dx, double dy, double nu, void* stream) {
-    return predictor_adi<float>(un, vn, un1, vn1, ui, vi, work, batch, nx, ny, dt, dx, dy, nu, S(stream), true);
+    return predictor_adi<float>(un, vn, un1, vn1, ui, vi, work, batch, nx, ny, dt, dx, dy, nu, as_stream(stream), true);
 }
 NNS_API int nns_fd_predictor_adi_corrected_f64(const double* un, const double* vn, const double* un1, const double* vn1, double* ui, double* vi, double* work,
                                                int batch, int nx, int ny, double dt, double dx, double dy, double nu, void* stream) {
-    return predictor_adi<double>(un, vn, un1, vn1, ui, vi, work, batch, nx, ny, dt, dx, dy, nu, S(stream), true);
+    return predictor_adi<double>(un, vn, un1, vn1, ui, vi, work, batch, nx, ny, dt, dx, dy, nu, as_stream(stream), true);
 }
 NNS_API int nns_fd_predictor_adi_f64(const double* un, const double* vn, const double* un1, const double* vn1, double* ui, double* vi, double* work,
                                      int batch, int nx, int ny, double dt, double dx, double dy, double nu, void* stream) {
-    return predictor_adi<double>(un, vn, un1, vn1, ui, vi, work, batch, nx, ny, dt, dx, dy, nu, S(stream));
+    return predictor_adi<double>(un, vn, un1, vn1, ui, vi, work, batch, nx, ny, dt, dx, dy, nu, as_stream(stream));
 }
 NNS_API int nns_fd_predictor_adi_colslab_f32(const float* un, const float* vn, const float* un1, const float* vn1, float* ui, float* vi, float* work,
                                              int batch, int nx, int nyl, double dt, double dx, double dy, double nu, void* stream) {
-    return predictor_adi<float>(un, vn, un1, vn1, ui, vi, work, batch, nx, nyl, dt, dx, dy, nu, S(stream), false, true);
+    return predictor_adi<float>(un, vn, un1, vn1, ui, vi, work, batch, nx, nyl, dt, dx, dy, nu, as_stream(stream), false, true);
 }
 NNS_API int nns_fd_predictor_adi_colslab_f64(const double* un, const double* vn, const double* un1, const double* vn1, double* ui, double* vi, double* work,
                                              int batch, int nx, int nyl, double dt, double dx, double dy, double nu, void* stream) {
-    return predictor_adi<double>(un, vn, un1, vn1, ui, vi, work, batch, nx, nyl, dt, dx, dy, nu, S(stream), false, true);
+    return predictor_adi<double>(un, vn, un1, vn1, ui, vi, work, batch, nx, nyl, dt, dx, dy, nu, as_stream(stream), false, true);
 }
 
 NNS_API int nns_fd_pressure_rhs_f32(const float* ui, const float* vi, float* C, int batch, int nx, int ny, double dt, double dx, double dy, double rho, void* stream) {
-    return pressure_rhs<float>(ui, vi, C, batch, nx, ny, dt, dx, dy, rho, S(stream));
+    return pressure_rhs<float>(ui, vi, C, batch, nx, ny, dt, dx, dy, rho, as_stream(stream));
 }
 NNS_API int nns_fd_pressure_rhs_f64(const double* ui, const double* vi, double* C, int batch, int nx, int ny, double dt, double dx, double dy, double rho, void* stream) {
-    return pressure_rhs<double>(ui, vi, C, batch, nx, ny, dt, dx, dy, rho, S(stream));
+    return pressure_rhs<double>(ui, vi, C, batch, nx, ny, dt, dx, dy, rho, as_stream(stream));
 }
 
 NNS_API int nns_fd_correction_f32(const float* ui, const float* vi, const float* p, float* u, float* v, int batch, int nx, int ny, double dt, double dx, double dy, void* stream) {
-    return correction<float>(ui, vi, p, u, v, batch, nx, ny, dt, dx, dy, S(stream));
+    return correction<float>(ui, vi, p, u, v, batch, nx, ny, dt, dx, dy, as_stream(stream));
 }
 NNS_API int nns_fd_correction_f64(const double* ui, const double* vi, const double* p, double* u, double* v, int batch, int nx, int ny, double dt, double dx, double dy, void* stream) {
-    return correction<double>(ui, vi, p, u, v, batch, nx, ny, dt, dx, dy, S(stream));
+    return correction<double>(ui, vi, p, u, v, batch, nx, ny, dt, dx, dy, as_stream(stream));
 }
 
 NNS_API int nns_fd_build_b_f32(const float* u, const float* v, float* b, int batch, int nx, int ny, double dt, double dx, double dy, double rho, void* stream) {
-    return build_b<float>(u, v, b, batch, nx, ny, dt, dx, dy, rho, S(stream));
+    return build_b<float>(u, v, b, batch, nx, ny, dt, dx, dy, rho, as_stream(stream));
 }
 NNS_API int nns_fd_build_b_f64(const double* u, const double* v, double* b, int batch, int nx, int ny, double dt, double dx, double dy, double rho, void* stream) {
-    return build_b<double>(u, v, b, batch, nx, ny, dt, dx, dy, rho, S(stream));
+    return build_b<double>(u, v, b, batch, nx, ny, dt, dx, dy, rho, as_stream(stream));
 }
 
 NNS_API int nns_fd_jacobi_f32(float* p, float* tmp, const float* b, int batch, int nx, int ny, double dx, double dy, int nit, const nns_bc_list* bc, void* stream) {
-    return jacobi<float>(p, tmp, b, batch, nx, ny, dx, dy, nit, bc, S(stream));
+    return jacobi<float>(p, tmp, b, batch, nx, ny, dx, dy, nit, bc, as_stream(stream));
 }
 NNS_API int nns_fd_jacobi_f64(double* p, double* tmp, const double* b, int batch, int nx, int ny, double dx, double dy, int nit, const nns_bc_list* bc, void* stream) {
-    return jacobi<double>(p, tmp, b, batch, nx, ny, dx, dy, nit, bc, S(stream));
+    return jacobi<double>(p, tmp, b, batch, nx, ny, dx, dy, nit, bc, as_stream(stream));
 }
 
 NNS_API int nns_fd_direct_update_f32(const float* un, const float* vn, const float* p, float* u, float* v, int batch, int nx, int ny,
                                      double dt, double dx, double dy, double rho, double nu, void* stream) {
-    return direct_update<float>(un, vn, p, u, v, batch, nx, ny, dt, dx, dy, rho, nu, S(stream));
+    return direct_update<float>(un, vn, p, u, v, batch, nx, ny, dt, dx, dy, rho, nu, as_stream(stream));
 }
 NNS_API int nns_fd_direct_update_f64(const double* un, const double* vn, const double* p, double* u, double* v, int batch, int nx, int ny,
                                      double dt, double dx, double dy, double rho, double nu, void* stream) {
-    return direct_update<double>(un, vn, p, u, v, batch, nx, ny, dt, dx, dy, rho, nu, S(stream));
+    return direct_update<double>(un, vn, p, u, v, batch, nx, ny, dt, dx, dy, rho, nu, as_stream(stream));
 }

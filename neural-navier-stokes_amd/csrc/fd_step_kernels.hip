@@ -88,21 +88,16 @@ int step_explicit(const T* un, const T* vn, const T* un1, const T* vn1, T* p, co
     const size_t lds4 = lds + 2 * (size_t)nx * ny * sizeof(T);            // with the intermediate velocities in LDS as well
     const bool uv = lds4 <= kSorLdsMax;
     T* snap = reinterpret_cast<T*>(work);
-    auto launch = [&](auto kern, int slot) -> int {
-        static bool attr[4] = {false, false, false, false};
-        if (!attr[slot]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSorLdsMax);
-            if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "fd_step_explicit: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr[slot] = true;
-        }
+    auto launch = [&](auto corr, auto uv_lds) -> int {
+        constexpr auto kern = fd_step_explicit_kernel<T, decltype(corr)::value, decltype(uv_lds)::value>;
+        if (int rc = lds_opt_in<kern>((int)kSorLdsMax, "fd_step_explicit")) return rc;
         hipLaunchKernelGGL(kern, dim3(batch), dim3(kSorThreads), uv ? lds4 : lds, s, un, vn, un1, vn1, p, u_out, v_out, p_copy, info, hint, snap, nx, ny, max_sweeps, k, ub, vb, pb);
-        return NNS_OK;
+        return check_launch("fd_step_explicit");
     };
-    int rc;
-    if (corrected) rc = uv ? launch(fd_step_explicit_kernel<T, true, true>, 0) : launch(fd_step_explicit_kernel<T, true, false>, 1);
-    else rc = uv ? launch(fd_step_explicit_kernel<T, false, true>, 2) : launch(fd_step_explicit_kernel<T, false, false>, 3);
-    if (rc != NNS_OK) return rc;
-    return check_launch("fd_step_explicit");
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (corrected) return uv ? launch(yes, yes) : launch(yes, no);
+    return uv ? launch(no, yes) : launch(no, no);
 }
 
 }  // namespace
@@ -115,12 +110,12 @@ NNS_API int nns_fd_step_explicit_f32(const float* un, const float* vn, const flo
                                      const nns_bc_list* p_bc, float* u_out, float* v_out, float* p_copy, float* info, const float* hint, void* work, int batch, int nx, int ny,
                                      double dt, double dx, double dy, double rho, double nu, double beta, double tol, int max_sweeps, int corrected, void* stream) {
     return step_explicit<float>(un, vn, un1, vn1, p, u_bc, v_bc, p_bc, u_out, v_out, p_copy, info, hint, work, batch, nx, ny, dt, dx, dy, rho, nu, beta, tol, max_sweeps,
-                                corrected, (hipStream_t)stream);
+                                corrected, as_stream(stream));
 }
 NNS_API int nns_fd_step_explicit_f64(const double* un, const double* vn, const double* un1, const double* vn1, double* p, const nns_bc_list* u_bc,
                                      const nns_bc_list* v_bc, const nns_bc_list* p_bc, double* u_out, double* v_out, double* p_copy, double* info, const double* hint, void* work, int batch,
                                      int nx, int ny, double dt, double dx, double dy, double rho, double nu, double beta, double tol, int max_sweeps, int corrected,
                                      void* stream) {
     return step_explicit<double>(un, vn, un1, vn1, p, u_bc, v_bc, p_bc, u_out, v_out, p_copy, info, hint, work, batch, nx, ny, dt, dx, dy, rho, nu, beta, tol, max_sweeps,
-                                 corrected, (hipStream_t)stream);
+                                 corrected, as_stream(stream));
 }

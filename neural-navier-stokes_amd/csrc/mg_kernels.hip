@@ -474,12 +474,7 @@ int mg_solve(T* p, const T* C, T* info, void* work, int batch, int nx, int ny, d
         }
     }
     const size_t lds = tail_lds_elems(sh, k.tail) * sizeof(T);
-    static bool attr = false;                     // set once to the largest size used (no non-stream API calls on later launches)
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mg_tail_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMgLdsMax);
-        if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-        attr = true;
-    }
+    if (int rc = lds_opt_in<mg_tail_kernel<T>>((int)kMgLdsMax, what)) return rc;       // the largest size used: one opt-in for every grid
     const dim3 fin_grid((batch + 255) / 256), fin_block(256);
     auto norm = [&]() {
         const int m = (nx - 2) * (ny - 2);
@@ -532,9 +527,9 @@ NNS_API int nns_fd_poisson_mg_workspace(int batch, int nx, int ny, int elem_size
 }
 NNS_API int nns_fd_poisson_mg_f32(float* p, const float* C, float* info, void* work, int batch, int nx, int ny, double dx, double dy, double tol,
                                   int cycles, int resume, void* stream) {
-    return mg_solve<float>(p, C, info, work, batch, nx, ny, dx, dy, tol, cycles, resume, reinterpret_cast<hipStream_t>(stream));
+    return mg_solve<float>(p, C, info, work, batch, nx, ny, dx, dy, tol, cycles, resume, as_stream(stream));
 }
 NNS_API int nns_fd_poisson_mg_f64(double* p, const double* C, double* info, void* work, int batch, int nx, int ny, double dx, double dy, double tol,
                                   int cycles, int resume, void* stream) {
-    return mg_solve<double>(p, C, info, work, batch, nx, ny, dx, dy, tol, cycles, resume, reinterpret_cast<hipStream_t>(stream));
+    return mg_solve<double>(p, C, info, work, batch, nx, ny, dx, dy, tol, cycles, resume, as_stream(stream));
 }

@@ -1184,8 +1184,6 @@ void launch_loss(const LossGeom& g, hipStream_t s, const float* coeff, const flo
 
 }  // namespace
 
-#define S(stream) reinterpret_cast<hipStream_t>(stream)
-
 NNS_API size_t nns_ode_mlp_bwd_workspace(int mb) {
     if (mb < 1) return 0;
     return (size_t)((mb + TB - 1) / TB) * 4 * kStageFloats * sizeof(float);
@@ -1197,19 +1195,14 @@ NNS_API int nns_ode_mlp_fwd_f32(const float* z0, const float* W0, const float* b
     if (hidden != H) return fail(NNS_ERR_UNSUPPORTED, "ode_mlp_fwd: hidden width %d (the reference's ODEFunc is fixed at %d)", hidden, H);
     if (K < 1 || K > KP) return fail(NNS_ERR_UNSUPPORTED, "ode_mlp_fwd: K=%d not in [1, %d]", K, KP);
     if (method_id(method) < 0) return fail(NNS_ERR_INVALID_ARG, "ode_mlp_fwd: method %d (0 Euler, 1 RK2, 2 RK4)", method);
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ode_mlp_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFwdLds);
-        if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "ode_mlp_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr = true;
-    }
+    if (int rc = lds_opt_in<ode_mlp_fwd_kernel>((int)kFwdLds, "ode_mlp_fwd")) return rc;
     static const int row_max = [] { const char* e = getenv("NNS_ODE_ROW_MAX"); return e ? atoi(e) : 4096; }();      // 0 forces the MFMA tile kernel (A/B, tests)
     if (mb <= row_max) {
         // one row per workgroup, weights in registers: ~2.6 us per RK4 step whatever the batch, against 14 us for a 16-row MFMA tile
-        hipLaunchKernelGGL(ode_mlp_fwd_row_kernel, dim3(mb), dim3(RT), 0, S(stream), z0, W0, b0, W1, b1, W2, b2, out, mb, K, Nt, method);
+        hipLaunchKernelGGL(ode_mlp_fwd_row_kernel, dim3(mb), dim3(RT), 0, as_stream(stream), z0, W0, b0, W1, b1, W2, b2, out, mb, K, Nt, method);
         return check_launch("ode_mlp_fwd");
     }
-    hipLaunchKernelGGL(ode_mlp_fwd_kernel, dim3((mb + TB - 1) / TB), dim3(NT), kFwdLds, S(stream), z0, W0, b0, W1, b1, W2, b2, out, mb, K, Nt, method);
+    hipLaunchKernelGGL(ode_mlp_fwd_kernel, dim3((mb + TB - 1) / TB), dim3(NT), kFwdLds, as_stream(stream), z0, W0, b0, W1, b1, W2, b2, out, mb, K, Nt, method);
     return check_launch("ode_mlp_fwd");
 }
 
@@ -1224,13 +1217,8 @@ static int ode_mlp_bwd_impl(const char* what, const float* z0, const float* W0, 
     if (hidden != H) return fail(NNS_ERR_UNSUPPORTED, "%s: hidden width %d (fixed at %d)", what, hidden, H);
     if (K < 1 || K > KP) return fail(NNS_ERR_UNSUPPORTED, "%s: K=%d not in [1, %d]", what, K, KP);
     if (method_id(method) < 0) return fail(NNS_ERR_INVALID_ARG, "%s: method %d", what, method);
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ode_mlp_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBwdLds);
-        if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-        attr = true;
-    }
-    hipStream_t s = S(stream);
+    if (int rc = lds_opt_in<ode_mlp_bwd_kernel>((int)kBwdLds, what)) return rc;
+    hipStream_t s = as_stream(stream);
     // the parameter gradients are accumulated with atomics: zero them first -- ONE launch for the six buffers (round 4: six memsets before)
     if (all_pg) {
         void* const bufs[6] = {gW0, gb0, gW1, gb1, gW2, gb2};
@@ -1364,13 +1352,15 @@ NNS_API int nns_ode_adjoint_chain_f32(const float* J, const float* g, float* lam
     if (spc < 1) spc = 1;
     const int lds = 2 * spc * (KC * KC + KC) * (int)sizeof(float);
     const int vec4 = (K * K) % 4 == 0 && (reinterpret_cast<uintptr_t>(J) & 15) == 0;
-    auto kern = K <= 32 ? ode_adjoint_chain_kernel<32> : ode_adjoint_chain_kernel<64>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "ode_adjoint_chain: hipFuncSetAttribute(%d B): %s", lds, hipGetErrorString(e));
     auto magic = [](unsigned d) { return d == 1 ? 0u : (unsigned)((1ull << 32) / d + 1); };
     const unsigned mK = magic((unsigned)K), mKK = magic((unsigned)(vec4 ? K * K / 4 : K * K));
-    hipLaunchKernelGGL(kern, dim3(mb), dim3(kChainThreads), lds, S(stream), J, g, lam, Nt, mb, K, spc, vec4, mK, mKK);
-    return check_launch("ode_adjoint_chain");
+    auto launch = [&](auto kc) -> int {
+        constexpr auto kern = ode_adjoint_chain_kernel<decltype(kc)::value>;
+        if (int rc = lds_opt_in<kern>(lds, "ode_adjoint_chain")) return rc;          // lds grows with Nt: one call per increase
+        hipLaunchKernelGGL(kern, dim3(mb), dim3(kChainThreads), lds, as_stream(stream), J, g, lam, Nt, mb, K, spc, vec4, mK, mKK);
+        return check_launch("ode_adjoint_chain");
+    };
+    return K <= 32 ? launch(std::integral_constant<int, 32>{}) : launch(std::integral_constant<int, 64>{});
 }
 
 NNS_API int nns_basis_expand_f32(const float* coeff, const float* basis, float* pred, int T, int K, int C, int P, void* stream) {
@@ -1378,7 +1368,7 @@ NNS_API int nns_basis_expand_f32(const float* coeff, const float* basis, float* 
     if (K > kMaxK) return fail(NNS_ERR_UNSUPPORTED, "basis_expand: K=%d > %d", K, kMaxK);
     if (T > 65535 || C > 65535) return fail(NNS_ERR_UNSUPPORTED, "basis_expand: T, C must be <= 65535");
     int gx = (P + 255) / 256; if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(basis_expand_kernel, dim3(gx, T, C), dim3(256), 0, S(stream), coeff, basis, pred, T, K, C, P);
+    hipLaunchKernelGGL(basis_expand_kernel, dim3(gx, T, C), dim3(256), 0, as_stream(stream), coeff, basis, pred, T, K, C, P);
     return check_launch("basis_expand");
 }
 
@@ -1388,7 +1378,7 @@ NNS_API int nns_basis_loss_fwd_f32(const float* coeff, const float* basis, const
     if (K > kMaxK) return fail(NNS_ERR_UNSUPPORTED, "basis_loss_fwd: K=%d > %d", K, kMaxK);
     if (C > 65535) return fail(NNS_ERR_UNSUPPORTED, "basis_loss_fwd: C must be <= 65535");
     const LossGeom g = loss_geom(T, K, C, P);
-    launch_loss<0>(g, S(stream), coeff, basis, obs, sumsq, nullptr, nullptr, 0.f, T, K, C, P);
+    launch_loss<0>(g, as_stream(stream), coeff, basis, obs, sumsq, nullptr, nullptr, 0.f, T, K, C, P);
     return check_launch("basis_loss_fwd");
 }
 
@@ -1427,10 +1417,10 @@ NNS_API int nns_basis_loss_bwd_f32(const float* coeff, const float* basis, const
     if (!coeff || !basis || !obs || !gcoeff || !gbasis || T < 1 || K < 1 || C < 1 || P < 1) return fail(NNS_ERR_INVALID_ARG, "basis_loss_bwd: bad args");
     if (K > kMaxK) return fail(NNS_ERR_UNSUPPORTED, "basis_loss_bwd: K=%d > %d", K, kMaxK);
     if (C > 65535) return fail(NNS_ERR_UNSUPPORTED, "basis_loss_bwd: C must be <= 65535");
-    if (int rc = launch_loss_mfma<1>(coeff, basis, obs, nullptr, gcoeff, gbasis, scale, T, K, C, P, S(stream), "basis_loss_bwd"); rc != 1) return rc;
+    if (int rc = launch_loss_mfma<1>(coeff, basis, obs, nullptr, gcoeff, gbasis, scale, T, K, C, P, as_stream(stream), "basis_loss_bwd"); rc != 1) return rc;
     const LossGeom g = loss_geom(T, K, C, P);
-    if (int rc = zero_grads(gcoeff, gbasis, g.nsplit, T, K, C, P, S(stream)); rc != NNS_OK) return rc;
-    launch_loss<1>(g, S(stream), coeff, basis, obs, nullptr, gcoeff, gbasis, scale, T, K, C, P);
+    if (int rc = zero_grads(gcoeff, gbasis, g.nsplit, T, K, C, P, as_stream(stream)); rc != NNS_OK) return rc;
+    launch_loss<1>(g, as_stream(stream), coeff, basis, obs, nullptr, gcoeff, gbasis, scale, T, K, C, P);
     return check_launch("basis_loss_bwd");
 }
 
@@ -1442,10 +1432,10 @@ NNS_API int nns_basis_loss_fused_f32(const float* coeff, const float* basis, con
     if (!coeff || !basis || !obs || !sumsq || !gcoeff || !gbasis || T < 1 || K < 1 || C < 1 || P < 1) return fail(NNS_ERR_INVALID_ARG, "basis_loss_fused: bad args");
     if (K > kMaxK) return fail(NNS_ERR_UNSUPPORTED, "basis_loss_fused: K=%d > %d", K, kMaxK);
     if (C > 65535) return fail(NNS_ERR_UNSUPPORTED, "basis_loss_fused: C must be <= 65535");
-    if (int rc = launch_loss_mfma<3>(coeff, basis, obs, sumsq, gcoeff, gbasis, 1.f, T, K, C, P, S(stream), "basis_loss_fused"); rc != 1) return rc;
+    if (int rc = launch_loss_mfma<3>(coeff, basis, obs, sumsq, gcoeff, gbasis, 1.f, T, K, C, P, as_stream(stream), "basis_loss_fused"); rc != 1) return rc;
     const LossGeom g = loss_geom(T, K, C, P);
-    if (int rc = zero_grads(gcoeff, gbasis, g.nsplit, T, K, C, P, S(stream)); rc != NNS_OK) return rc;
-    launch_loss<3>(g, S(stream), coeff, basis, obs, sumsq, gcoeff, gbasis, 1.f, T, K, C, P);
+    if (int rc = zero_grads(gcoeff, gbasis, g.nsplit, T, K, C, P, as_stream(stream)); rc != NNS_OK) return rc;
+    launch_loss<3>(g, as_stream(stream), coeff, basis, obs, sumsq, gcoeff, gbasis, 1.f, T, K, C, P);
     return check_launch("basis_loss_fused");
 }
 
@@ -1455,9 +1445,9 @@ NNS_API int nns_basis_expand_bwd_f32(const float* coeff, const float* basis, con
     if (!coeff || !basis || !grad_pred || !gcoeff || !gbasis || T < 1 || K < 1 || C < 1 || P < 1) return fail(NNS_ERR_INVALID_ARG, "basis_expand_bwd: bad args");
     if (K > kMaxK) return fail(NNS_ERR_UNSUPPORTED, "basis_expand_bwd: K=%d > %d", K, kMaxK);
     if (C > 65535) return fail(NNS_ERR_UNSUPPORTED, "basis_expand_bwd: C must be <= 65535");
-    if (int rc = launch_loss_mfma<2>(coeff, basis, grad_pred, nullptr, gcoeff, gbasis, 1.f, T, K, C, P, S(stream), "basis_expand_bwd"); rc != 1) return rc;
+    if (int rc = launch_loss_mfma<2>(coeff, basis, grad_pred, nullptr, gcoeff, gbasis, 1.f, T, K, C, P, as_stream(stream), "basis_expand_bwd"); rc != 1) return rc;
     const LossGeom g = loss_geom(T, K, C, P);
-    if (int rc = zero_grads(gcoeff, gbasis, g.nsplit, T, K, C, P, S(stream)); rc != NNS_OK) return rc;
-    launch_loss<2>(g, S(stream), coeff, basis, grad_pred, nullptr, gcoeff, gbasis, 1.f, T, K, C, P);
+    if (int rc = zero_grads(gcoeff, gbasis, g.nsplit, T, K, C, P, as_stream(stream)); rc != NNS_OK) return rc;
+    launch_loss<2>(g, as_stream(stream), coeff, basis, grad_pred, nullptr, gcoeff, gbasis, 1.f, T, K, C, P);
     return check_launch("basis_expand_bwd");
 }

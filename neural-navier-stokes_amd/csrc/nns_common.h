@@ -1,9 +1,13 @@
-// Shared host/device helpers for libnns_hip.so (gfx950 / MI355X only).
+// Shared host/device helpers for libnns_hip.so (gfx950 / MI355X only): error reporting, the host launch layer every translation unit
+// uses between its C entry points and hipLaunchKernelGGL (stream cast, dynamic-LDS opt-in, CU count, grid cap, FFT size dispatch),
+// and a few device helpers (XCD remap, boundary lists, static_for).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <type_traits>
 
 #include "../../include/nns.h"
@@ -29,6 +33,49 @@ inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
     return NNS_OK;
+}
+
+// ---- host launch layer ----
+inline hipStream_t as_stream(void* stream) { return reinterpret_cast<hipStream_t>(stream); }
+
+// Raise kernel Kern's dynamic-LDS limit to at least `bytes` (above 64 KB a launch needs the opt-in).  The largest size granted is
+// remembered per kernel -- Kern itself is the key: kernels that share a function-pointer type do not share a flag -- and the runtime
+// is called only for a larger one: once per process for a fixed-size kernel, once per increase for one sized at run time.  Every later
+// launch stays free of non-stream API calls.  Safe against concurrent host threads (the rare slow path is serialised).
+template <auto Kern>
+inline int lds_opt_in(int bytes, const char* what) {
+    static std::atomic<int> granted{0};
+    static std::mutex slow;
+    if (bytes <= granted.load(std::memory_order_acquire)) return NNS_OK;
+    std::lock_guard<std::mutex> lock(slow);
+    if (bytes <= granted.load(std::memory_order_relaxed)) return NNS_OK;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "%s: hipFuncSetAttribute(%d B): %s", what, bytes, hipGetErrorString(e));
+    granted.store(bytes, std::memory_order_release);
+    return NNS_OK;
+}
+
+// CU count of the device, queried once (256, the MI355X's, where the query fails).
+inline int device_cus() {
+    static const int n = [] { int dev = 0, v = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) v = 256; return v; }();
+    return n;
+}
+
+// Workgroups of a grid-stride launch: one per unit of work up to `cap` (the caps are tuned per kernel and stay at the call sites).
+inline unsigned capped_grid(long work, long cap) { return (unsigned)(work < cap ? work : cap); }
+
+// The FFT engine's line lengths: powers of two 64 .. 1024, one kernel instantiation each.
+inline bool pow2_in_range(int n) { return n >= 64 && n <= 1024 && (n & (n - 1)) == 0; }
+template <typename F>
+int dispatch_pow2(int n, const char* what, F&& f) {
+    switch (n) {
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        case 256: return f(std::integral_constant<int, 256>{});
+        case 512: return f(std::integral_constant<int, 512>{});
+        case 1024: return f(std::integral_constant<int, 1024>{});
+    }
+    return fail(NNS_ERR_UNSUPPORTED, "%s: axis length %d is not a power of two in [64, 1024] (the FFT engine's sizes)", what, n);
 }
 
 // bufs[i][0 .. bytes[i]) = 0 for every i, ONE launch per 24 buffers (csrc/optim_kernels.hip); entries with bytes <= 0 are skipped

@@ -131,7 +131,7 @@ NNS_API int nns_adam_step_f32(float* const* params_host, const float* const* gra
             return fail(NNS_ERR_INVALID_ARG, "nns_adam_step_f32: tensor %d has a NULL buffer", i);
         if (sizes_host[i] > (long)kChunk * 0x3fffffffL) return fail(NNS_ERR_UNSUPPORTED, "nns_adam_step_f32: tensor %d too large (%ld)", i, sizes_host[i]);
     }
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = as_stream(stream);
     for (int i0 = 0; i0 < ntensors;) {
         AdamTable t{};
         int c = 0;

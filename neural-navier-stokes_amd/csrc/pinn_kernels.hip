@@ -177,7 +177,7 @@ NNS_API int nns_pinn_assemble_f32(const float* out, const float* state, const fl
     if ((u_prev == nullptr) != (v_prev == nullptr)) return fail(NNS_ERR_INVALID_ARG, "nns_pinn_assemble_f32: u_prev and v_prev come together");
     if (batch < 1 || npix < 1) return fail(NNS_ERR_INVALID_ARG, "nns_pinn_assemble_f32: bad sizes (batch=%d npix=%ld)", batch, npix);
     if (reinterpret_cast<uintptr_t>(ws) & 7) return fail(NNS_ERR_INVALID_ARG, "nns_pinn_assemble_f32: workspace must be 8-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = as_stream(stream);
     if (npix % 4 == 0 && aligned16({out, state, target, u, v, p, u_prev, v_prev}))
         hipLaunchKernelGGL(pinn_assemble_kernel<4>, dim3(kBlocks), dim3(kThreads), 0, s, out, state, target, u, v, p, u_prev, v_prev, (Ws*)ws, (long)batch, npix / 4);
     else
@@ -190,7 +190,7 @@ NNS_API int nns_pinn_loss_f32(const float* r_u, const float* r_v, float* r_div, 
     if (!r_u || !r_v || !r_div || !ws || !out3) return fail(NNS_ERR_INVALID_ARG, "nns_pinn_loss_f32: NULL argument");
     if (n < 1 || n_data < 0) return fail(NNS_ERR_INVALID_ARG, "nns_pinn_loss_f32: bad sizes (n=%ld n_data=%g)", n, n_data);
     if (reinterpret_cast<uintptr_t>(ws) & 7) return fail(NNS_ERR_INVALID_ARG, "nns_pinn_loss_f32: workspace must be 8-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = as_stream(stream);
     const double inv_n = 1.0 / (double)n, inv_nd = n_data > 0 ? 1.0 / n_data : 0.0;
     const int scale = w_div != 1.0;
     if (n % 4 == 0 && aligned16({r_u, r_v, r_div}))
@@ -206,7 +206,7 @@ NNS_API int nns_pinn_combine_f32(const float* g_u, const float* g_v, const float
     if (!g_u || !g_v || !g_p || !up_phys || !grad_out) return fail(NNS_ERR_INVALID_ARG, "nns_pinn_combine_f32: NULL argument");
     if (target && (!u || !v || !p || !up_data)) return fail(NNS_ERR_INVALID_ARG, "nns_pinn_combine_f32: a target needs u, v, p and up_data");
     if (batch < 1 || npix < 1) return fail(NNS_ERR_INVALID_ARG, "nns_pinn_combine_f32: bad sizes (batch=%d npix=%ld)", batch, npix);
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = as_stream(stream);
     const bool vec = npix % 4 == 0 && aligned16({g_u, g_v, g_p, u, v, p, target, grad_out});
     const long items = (long)batch * (vec ? npix / 4 : npix);
     const unsigned grid = (unsigned)(items / kThreads < 1 ? 1 : (items / kThreads > 8192 ? 8192 : items / kThreads));

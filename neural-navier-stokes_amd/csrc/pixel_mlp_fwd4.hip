@@ -166,12 +166,9 @@ __global__ __launch_bounds__(kP4Threads) __attribute__((amdgpu_waves_per_eu(1, 1
 int nns::pm::launch_fwd_pipe4(const float* x, const float* weights, const float* biases, float* y, long npix, int P, const PixelMlpDesc& d, hipStream_t s) {
     const int lds = UniLds<2>::total(d.nlayers);
     if (lds > 160 * 1024) return fail(NNS_ERR_UNSUPPORTED, "pixel_mlp_fwd: weights need %d B of LDS (> 160 KiB)", lds);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pixel_mlp_fwd_pipe4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "pixel_mlp_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    if (int rc = lds_opt_in<pixel_mlp_fwd_pipe4_kernel>(lds, "pixel_mlp_fwd")) return rc;
     const long ngroups = (npix + 127) / 128;
-    int cus = 256;
-    { int dev = 0, v = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
-    long blocks = (ngroups + 3) / 4; if (blocks > cus) blocks = cus;       // persistent: one workgroup (four waves, one per SIMD) per CU
+    const unsigned blocks = capped_grid((ngroups + 3) / 4, device_cus());       // persistent: one workgroup (four waves, one per SIMD) per CU
     // n / P for 32-bit n:  t = umulhi(m, n);  q = (t + ((n - t) >> 1)) >> (l - 1)  with l = ceil(log2 P), m = floor(2^32 (2^l - P) / P) + 1
     unsigned pmagic = 0; int pshift = -1;
     if (npix < (1L << 32) && P >= 2) {
@@ -179,7 +176,7 @@ int nns::pm::launch_fwd_pipe4(const float* x, const float* weights, const float*
         pmagic = (unsigned)((((unsigned long long)1 << 32) * (((unsigned long long)1 << l) - (unsigned long long)P)) / (unsigned long long)P + 1);
         pshift = l - 1;
     }
-    hipLaunchKernelGGL(pixel_mlp_fwd_pipe4_kernel, dim3((unsigned)blocks), dim3(kP4Threads), lds, s, x, weights, biases, y, npix, P, d, pmagic, pshift);
+    hipLaunchKernelGGL(pixel_mlp_fwd_pipe4_kernel, dim3(blocks), dim3(kP4Threads), lds, s, x, weights, biases, y, npix, P, d, pmagic, pshift);
     return check_launch("pixel_mlp_fwd");
 }
 

@@ -268,13 +268,12 @@ template <int OT, bool SMALLIO>
 int launch_fwd_uniform(const float* x, const float* weights, const float* biases, float* y, long npix, int P, const PixelMlpDesc& d, hipStream_t s) {
     const int lds = UniLds<OT>::total(d.nlayers);
     if (lds > 160 * 1024) return fail(NNS_ERR_UNSUPPORTED, "pixel_mlp_fwd: weights need %d B of LDS (> 160 KiB)", lds);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pixel_mlp_fwd_uniform_kernel<OT, SMALLIO>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "pixel_mlp_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    if (int rc = lds_opt_in<pixel_mlp_fwd_uniform_kernel<OT, SMALLIO>>(lds, "pixel_mlp_fwd")) return rc;
     const long ngroups = (npix + 32 * kPT - 1) / (32 * kPT);
     // persistent: one generation of workgroups (2 per CU fit by LDS), so the weights are staged once per workgroup
     const long cap = 256;                                    // workgroups resident at once (8-wave workgroups: one per CU by registers)
-    long blocks = (ngroups + kFwdWaves - 1) / kFwdWaves; if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL((pixel_mlp_fwd_uniform_kernel<OT, SMALLIO>), dim3((unsigned)blocks), dim3(kFwdThreads), lds, s, x, weights, biases, y, npix, P, d);
+    const unsigned blocks = capped_grid((ngroups + kFwdWaves - 1) / kFwdWaves, cap);
+    hipLaunchKernelGGL((pixel_mlp_fwd_uniform_kernel<OT, SMALLIO>), dim3(blocks), dim3(kFwdThreads), lds, s, x, weights, biases, y, npix, P, d);
     return check_launch("pixel_mlp_fwd");
 }
 
@@ -915,10 +914,9 @@ template <bool SMALLIO>
 int launch_bwd_f32(const float* x, const float* gy, const float* weights, const float* biases, float* gx, float* gW, float* gB,
                    long npix, int P, const PixelMlpDesc& d, int nparams_w, int nparams, float* ws, hipStream_t s) {
     const int lds = BwdLdsF32::total(d.nlayers);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pixel_mlp_bwd_f32_kernel<SMALLIO>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "pixel_mlp_bwd: hipFuncSetAttribute(%d B): %s", lds, hipGetErrorString(e));
+    if (int rc = lds_opt_in<pixel_mlp_bwd_f32_kernel<SMALLIO>>(lds, "pixel_mlp_bwd")) return rc;
     const long nsuper = (npix + 127) / 128;
-    const int blocks = (int)(nsuper < kBwdMaxBlocks ? nsuper : kBwdMaxBlocks);
+    const int blocks = (int)capped_grid(nsuper, kBwdMaxBlocks);
     hipLaunchKernelGGL((pixel_mlp_bwd_f32_kernel<SMALLIO>), dim3(blocks), dim3(256), lds, s, x, gy, weights, biases, gx, ws, npix, P, d, nparams_w, nparams);
     if (int rc = check_launch("pixel_mlp_bwd")) return rc;
     hipLaunchKernelGGL(pixel_mlp_reduce_kernel, dim3((nparams + kRedParams - 1) / kRedParams), dim3(kRedParts * kRedParams), 0, s, ws, gW, gB, blocks * 4, nparams_w, nparams);
@@ -930,10 +928,9 @@ int launch_bwd_split(const float* x, const float* gy, const float* weights, cons
                        long npix, int P, const PixelMlpDesc& d, int nparams_w, int nparams, float* ws, hipStream_t s) {
     const int lds = BwdLds<OT>::total(d.nlayers);
     if (lds > 160 * 1024) return fail(NNS_ERR_UNSUPPORTED, "pixel_mlp_bwd: needs %d B of LDS (> 160 KiB)", lds);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pixel_mlp_bwd_split_kernel<OT, SMALLIO>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "pixel_mlp_bwd: hipFuncSetAttribute(%d B): %s", lds, hipGetErrorString(e));
+    if (int rc = lds_opt_in<pixel_mlp_bwd_split_kernel<OT, SMALLIO>>(lds, "pixel_mlp_bwd")) return rc;
     const long nsuper = (npix + 127) / 128;
-    const int blocks = (int)(nsuper < kBwdMaxBlocks ? nsuper : kBwdMaxBlocks);
+    const int blocks = (int)capped_grid(nsuper, kBwdMaxBlocks);
     hipLaunchKernelGGL((pixel_mlp_bwd_split_kernel<OT, SMALLIO>), dim3(blocks), dim3(512), lds, s, x, gy, weights, biases, gx, ws, npix, P, d, nparams_w, nparams);
     if (int rc = check_launch("pixel_mlp_bwd")) return rc;
     const int nslices = blocks * (OT == 2 ? 1 : 4);
@@ -969,15 +966,9 @@ NNS_API int nns_pixel_mlp_fwd_f32(const float* x, const float* weights, const fl
     if (!bf16 && lds > 160 * 1024) return fail(NNS_ERR_UNSUPPORTED, "pixel_mlp_fwd: weights need %d B of LDS (> 160 KiB)", lds);
     const long npix = (long)mb * P;
     const long ntiles = (npix + 31) / 32;
-    long blocks = (ntiles + kGenWaves - 1) / kGenWaves;
-    {   // persistent: the weights are staged once per workgroup (128 KB at depth 8, width 64: a workgroup per CU)
-        int cus = 256, dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        const long cap = (long)cus * (lds > 80 * 1024 ? 1 : 2);
-        if (blocks > cap) blocks = cap;
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e;
+    // persistent: the weights are staged once per workgroup (128 KB at depth 8, width 64: a workgroup per CU)
+    const unsigned blocks = capped_grid((ntiles + kGenWaves - 1) / kGenWaves, (long)device_cus() * (lds > 80 * 1024 ? 1 : 2));
+    hipStream_t s = as_stream(stream);
     if (bf16) {
         int maxw = 0;
         for (int l = 0; l <= nlayers; ++l) maxw = widths_host[l] > maxw ? widths_host[l] : maxw;
@@ -985,11 +976,9 @@ NNS_API int nns_pixel_mlp_fwd_f32(const float* x, const float* weights, const fl
         if (maxw <= 32) return small ? launch_fwd_uniform<1, true>(x, weights, biases, y, npix, P, d, s) : launch_fwd_uniform<1, false>(x, weights, biases, y, npix, P, d, s);
         if (small) return launch_fwd_pipe4(x, weights, biases, y, npix, P, d, s);             // (generic I/O keeps the kernel above)
         return small ? launch_fwd_uniform<2, true>(x, weights, biases, y, npix, P, d, s) : launch_fwd_uniform<2, false>(x, weights, biases, y, npix, P, d, s);
-    } else {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(pixel_mlp_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "pixel_mlp_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(pixel_mlp_fwd_kernel<false>, dim3((unsigned)blocks), dim3(kGenThreads), lds, s, x, weights, biases, y, npix, P, d);
     }
+    if (int rc = lds_opt_in<pixel_mlp_fwd_kernel<false>>(lds, "pixel_mlp_fwd")) return rc;
+    hipLaunchKernelGGL(pixel_mlp_fwd_kernel<false>, dim3(blocks), dim3(kGenThreads), lds, s, x, weights, biases, y, npix, P, d);
     return check_launch("pixel_mlp_fwd");
 }
 
@@ -1014,7 +1003,7 @@ NNS_API int nns_pixel_mlp_bwd_f32(const float* x, const float* gy, const float* 
     if (!bf16 && maxw > 32) return fail(NNS_ERR_UNSUPPORTED, "pixel_mlp_bwd: the float32-operand backward supports widths <= 32 (got %d); use bf16", maxw);
     if (workspace_bytes < (size_t)kBwdMaxBlocks * (maxw <= 32 ? 4 : 1) * np * sizeof(float))
         return fail(NNS_ERR_WORKSPACE, "pixel_mlp_bwd: workspace too small (%zu B, see nns_pixel_mlp_bwd_workspace)", workspace_bytes);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = as_stream(stream);
     const long npix = (long)mb * P;
     float* ws = static_cast<float*>(workspace);
     const bool small = widths_host[0] <= 4 && widths_host[nlayers] <= 4;

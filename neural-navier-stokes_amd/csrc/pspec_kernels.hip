@@ -400,42 +400,22 @@ __global__ __launch_bounds__(kDiagT) void ps_diag_kernel(const float2* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-inline bool pow2ok(int n) { return n >= 64 && n <= 1024 && (n & (n - 1)) == 0; }
 inline int kept_y(int ny) { return (ny - 1) / 3 + 1; }
 
-template <typename F>
-int dispatch(int n, F&& f) {
-    switch (n) {
-        case 64: return f(std::integral_constant<int, 64>{});
-        case 128: return f(std::integral_constant<int, 128>{});
-        case 256: return f(std::integral_constant<int, 256>{});
-        case 512: return f(std::integral_constant<int, 512>{});
-        case 1024: return f(std::integral_constant<int, 1024>{});
-    }
-    return fail(NNS_ERR_UNSUPPORTED, "spec_ns: axis length %d is not a power of two in [64, 1024]", n);
-}
-
-template <typename K>
-int set_lds(K kern, int bytes) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "spec_ns: hipFuncSetAttribute(%d B): %s", bytes, hipGetErrorString(e));
-    return NNS_OK;
-}
-
-inline unsigned grid_of(long work, long per) { const long g = (work + per - 1) / per; return (unsigned)(g < kGridCap ? g : kGridCap); }
+inline unsigned grid_of(long work, long per) { return capped_grid((work + per - 1) / per, kGridCap); }
 
 template <int N>
 int launch_row(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s) {
-    auto kern = ps_row_kernel<N>;
-    if (int rc = set_lds(kern, PsLds<N>::TOTAL)) return rc;
+    constexpr auto kern = ps_row_kernel<N>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
     hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a);
     return check_launch("spec_ns row pass");
 }
 
 template <int N, int S>
 int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, hipStream_t s) {
-    auto kern = ps_col_kernel<N, S>;
-    if (int rc = set_lds(kern, PsLds<N>::TOTAL)) return rc;
+    constexpr auto kern = ps_col_kernel<N, S>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
     hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, PsNoForce{});
     return check_launch("spec_ns column pass");
 }
@@ -443,8 +423,8 @@ int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* m
 template <int N, int S>
 int launch_col_forced(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce& fc,
                       hipStream_t s) {
-    auto kern = ps_col_kernel<N, S, true>;
-    if (int rc = set_lds(kern, PsLds<N>::TOTAL)) return rc;
+    constexpr auto kern = ps_col_kernel<N, S, true>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
     hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, fc);
     return check_launch("spec_ns forced column pass");
 }
@@ -485,7 +465,7 @@ size_t work_bytes(int batch, int nx, int ny) {
 int check_common(const char* what, int batch, int nx, int ny, double Lx, double Ly, const void* work, size_t wbytes) {
     if (!(Lx > 0) || !(Ly > 0) || !std::isfinite(Lx) || !std::isfinite(Ly))
         return fail(NNS_ERR_INVALID_ARG, "%s: Lx = %g, Ly = %g must be positive and finite", what, Lx, Ly);
-    if (!pow2ok(nx) || !pow2ok(ny))
+    if (!pow2_in_range(nx) || !pow2_in_range(ny))
         return fail(NNS_ERR_UNSUPPORTED, "%s: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", what, nx, ny);
     const size_t need = work_bytes(batch, nx, ny);
     if (wbytes < need) return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (nns_spec_ns_workspace)", what, wbytes, need);
@@ -493,15 +473,13 @@ int check_common(const char* what, int batch, int nx, int ny, double Lx, double 
     return NNS_OK;
 }
 
-inline unsigned pw_grid(long n) { const long g = (n + 255) / 256; return (unsigned)(g < 4096 ? g : 4096); }
+inline unsigned pw_grid(long n) { return capped_grid((n + 255) / 256, 4096); }
 
 }  // namespace
 
-#define S_(stream) reinterpret_cast<hipStream_t>(stream)
-
 NNS_API int nns_spec_ns_workspace(int batch, int nx, int ny, size_t* bytes) {
     if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
-    if (!pow2ok(nx) || !pow2ok(ny))
+    if (!pow2_in_range(nx) || !pow2_in_range(ny))
         return fail(NNS_ERR_UNSUPPORTED, "spec_ns_workspace: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", nx, ny);
     *bytes = work_bytes(batch, nx, ny);
     return NNS_OK;
@@ -511,7 +489,7 @@ NNS_API int nns_spec_ns_init_f32(const float* u, const float* v, float* what, fl
                                  int nx, int ny, double Lx, double Ly, void* stream) {
     if (!u || !v || !what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_init: NULL pointer or batch < 1");
     if (int rc = check_common("spec_ns_init", batch, nx, ny, Lx, Ly, work, work_bytes_)) return rc;
-    hipStream_t s = S_(stream);
+    hipStream_t s = as_stream(stream);
     float* uh = static_cast<float*>(work);
     float* vh = uh + (size_t)2 * batch * nx * (ny / 2 + 1);
     if (int rc = nns_spec_rfft2_f32(u, uh, batch, nx, ny, stream)) return rc;
@@ -534,7 +512,7 @@ static int spec_ns_step(const char* who, float* what, const float* mean, const f
         return fail(NNS_ERR_INVALID_ARG, "%s: gbatch = %d must be 0 without ghat, 1 or batch = %d with it", who, gbatch, batch);
     if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work, work_bytes_)) return rc;
     if (nsteps == 0) return NNS_OK;
-    hipStream_t s = S_(stream);
+    hipStream_t s = as_stream(stream);
     const int my1 = kept_y(ny);
     const long fstride = (long)batch * nx * my1;
     float2* W = reinterpret_cast<float2*>(what);
@@ -547,8 +525,8 @@ static int spec_ns_step(const char* who, float* what, const float* mean, const f
     ar.nlines = (long)batch * nx;
     const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
     const PsForce* fc = ghat || drag > 0 ? &force : nullptr;
-    auto col = [&](int S, int emit) { return dispatch(nx, [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, fc, s); }); };
-    auto row = [&]() { return dispatch(ny, [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, s); }); };
+    auto col = [&](int S, int emit) { return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, fc, s); }); };
+    auto row = [&]() { return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, s); }); };
     if (int rc = col(0, 1)) return rc;
     for (int k = 0; k < nsteps; ++k) {
         for (int S = 1; S <= 4; ++S) {
@@ -577,10 +555,10 @@ NNS_API int nns_spec_ns_diag_f32(const float* what, const float* ghat, int gbatc
         return fail(NNS_ERR_INVALID_ARG, "spec_ns_diag: gbatch = %d must be 0 without ghat, 1 or batch = %d with it", gbatch, batch);
     if (!(Lx > 0) || !(Ly > 0) || !std::isfinite(Lx) || !std::isfinite(Ly))
         return fail(NNS_ERR_INVALID_ARG, "spec_ns_diag: Lx = %g, Ly = %g must be positive and finite", Lx, Ly);
-    if (!pow2ok(nx) || !pow2ok(ny))
+    if (!pow2_in_range(nx) || !pow2_in_range(ny))
         return fail(NNS_ERR_UNSUPPORTED, "spec_ns_diag: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", nx, ny);
     const double n = (double)nx * ny;
-    hipLaunchKernelGGL(ps_diag_kernel, dim3(batch), dim3(kDiagT), 0, S_(stream), reinterpret_cast<const float2*>(what),
+    hipLaunchKernelGGL(ps_diag_kernel, dim3(batch), dim3(kDiagT), 0, as_stream(stream), reinterpret_cast<const float2*>(what),
                        reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, out, nx, kept_y(ny), 2.0 * M_PI / Lx,
                        2.0 * M_PI / Ly, 1.0 / (n * n));
     return check_launch("spec_ns_diag");
@@ -591,7 +569,7 @@ NNS_API int nns_spec_ns_fields_f32(const float* what, const float* mean, float* 
     if (!what || !mean || !u || !v || !p || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_fields: NULL pointer or batch < 1");
     if (!std::isfinite(rho)) return fail(NNS_ERR_INVALID_ARG, "spec_ns_fields: rho = %g must be finite", rho);
     if (int rc = check_common("spec_ns_fields", batch, nx, ny, Lx, Ly, work, work_bytes_)) return rc;
-    hipStream_t s = S_(stream);
+    hipStream_t s = as_stream(stream);
     const int my1 = kept_y(ny);
     const long nh = ny / 2 + 1, per = (long)batch * nx * nh, npts = (long)batch * nx * ny;
     float* spec = static_cast<float*>(work);                 // [6][B][nx][nh] complex: u_x, u_y, v_x, v_y, u, v

@@ -395,12 +395,12 @@ int fd_residual_bwd(const T* u, const T* v, const T* ga, const T* gb, const T* g
 NNS_API int nns_fd_residual_f32(const float* u, const float* v, const float* p, const float* u_prev, const float* v_prev,
                                 float* r_u, float* r_v, float* r_div, int batch, int nx, int ny, double dt, double dx, double dy,
                                 double rho, double nu, int stencil, void* stream) {
-    return fd_residual<float>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx, ny, dt, dx, dy, rho, nu, stencil, reinterpret_cast<hipStream_t>(stream));
+    return fd_residual<float>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx, ny, dt, dx, dy, rho, nu, stencil, as_stream(stream));
 }
 NNS_API int nns_fd_residual_f64(const double* u, const double* v, const double* p, const double* u_prev, const double* v_prev,
                                 double* r_u, double* r_v, double* r_div, int batch, int nx, int ny, double dt, double dx, double dy,
                                 double rho, double nu, int stencil, void* stream) {
-    return fd_residual<double>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx, ny, dt, dx, dy, rho, nu, stencil, reinterpret_cast<hipStream_t>(stream));
+    return fd_residual<double>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx, ny, dt, dx, dy, rho, nu, stencil, as_stream(stream));
 }
 
 NNS_API int nns_fd_residual_halo_f32(const float* u, const float* v, const float* p, const float* u_prev, const float* v_prev,
@@ -408,7 +408,7 @@ NNS_API int nns_fd_residual_halo_f32(const float* u, const float* v, const float
                                      int batch, int nx_local, int ny, int row_begin, int row_end, double dt, double dx, double dy,
                                      double rho, double nu, int stencil, void* stream) {
     if (!halo_top || !halo_bot) return fail(NNS_ERR_INVALID_ARG, "fd_residual_halo: halo_top and halo_bot are required");
-    return fd_residual<float>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx_local, ny, dt, dx, dy, rho, nu, stencil, reinterpret_cast<hipStream_t>(stream),
+    return fd_residual<float>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx_local, ny, dt, dx, dy, rho, nu, stencil, as_stream(stream),
                               halo_top, halo_bot, row_begin, row_end);
 }
 NNS_API int nns_fd_residual_halo_f64(const double* u, const double* v, const double* p, const double* u_prev, const double* v_prev,
@@ -416,17 +416,17 @@ NNS_API int nns_fd_residual_halo_f64(const double* u, const double* v, const dou
                                      int batch, int nx_local, int ny, int row_begin, int row_end, double dt, double dx, double dy,
                                      double rho, double nu, int stencil, void* stream) {
     if (!halo_top || !halo_bot) return fail(NNS_ERR_INVALID_ARG, "fd_residual_halo: halo_top and halo_bot are required");
-    return fd_residual<double>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx_local, ny, dt, dx, dy, rho, nu, stencil, reinterpret_cast<hipStream_t>(stream),
+    return fd_residual<double>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx_local, ny, dt, dx, dy, rho, nu, stencil, as_stream(stream),
                                halo_top, halo_bot, row_begin, row_end);
 }
 
 NNS_API int nns_fd_residual_bwd_f32(const float* u, const float* v, const float* g_u, const float* g_v, const float* g_div,
                                     float* grad_u, float* grad_v, float* grad_p, float* grad_u_prev, float* grad_v_prev,
                                     int batch, int nx, int ny, double dt, double dx, double dy, double rho, double nu, int stencil, void* stream) {
-    return fd_residual_bwd<float>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, grad_u_prev, grad_v_prev, batch, nx, ny, dt, dx, dy, rho, nu, stencil, reinterpret_cast<hipStream_t>(stream));
+    return fd_residual_bwd<float>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, grad_u_prev, grad_v_prev, batch, nx, ny, dt, dx, dy, rho, nu, stencil, as_stream(stream));
 }
 NNS_API int nns_fd_residual_bwd_f64(const double* u, const double* v, const double* g_u, const double* g_v, const double* g_div,
                                     double* grad_u, double* grad_v, double* grad_p, double* grad_u_prev, double* grad_v_prev,
                                     int batch, int nx, int ny, double dt, double dx, double dy, double rho, double nu, int stencil, void* stream) {
-    return fd_residual_bwd<double>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, grad_u_prev, grad_v_prev, batch, nx, ny, dt, dx, dy, rho, nu, stencil, reinterpret_cast<hipStream_t>(stream));
+    return fd_residual_bwd<double>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, grad_u_prev, grad_v_prev, batch, nx, ny, dt, dx, dy, rho, nu, stencil, as_stream(stream));
 }

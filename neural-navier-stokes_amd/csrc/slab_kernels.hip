@@ -183,41 +183,39 @@ int transpose(bool pack, const T* const* fields, int nfields, T* buf, int B, int
 
 }  // namespace
 
-#define S(stream) reinterpret_cast<hipStream_t>(stream)
-
 NNS_API int nns_slab_gather_lines_f32(const float* const* fields_host, int nfields, float* msg, long nouter, long outer_stride, long line_off,
                                       long len, long elem_stride, void* stream) {
-    return lines<float>(true, fields_host, nfields, msg, nouter, outer_stride, line_off, len, elem_stride, S(stream));
+    return lines<float>(true, fields_host, nfields, msg, nouter, outer_stride, line_off, len, elem_stride, as_stream(stream));
 }
 NNS_API int nns_slab_gather_lines_f64(const double* const* fields_host, int nfields, double* msg, long nouter, long outer_stride, long line_off,
                                       long len, long elem_stride, void* stream) {
-    return lines<double>(true, fields_host, nfields, msg, nouter, outer_stride, line_off, len, elem_stride, S(stream));
+    return lines<double>(true, fields_host, nfields, msg, nouter, outer_stride, line_off, len, elem_stride, as_stream(stream));
 }
 NNS_API int nns_slab_scatter_lines_f32(const float* msg, float* const* fields_host, int nfields, long nouter, long outer_stride, long line_off,
                                        long len, long elem_stride, void* stream) {
-    return lines<float>(false, fields_host, nfields, const_cast<float*>(msg), nouter, outer_stride, line_off, len, elem_stride, S(stream));
+    return lines<float>(false, fields_host, nfields, const_cast<float*>(msg), nouter, outer_stride, line_off, len, elem_stride, as_stream(stream));
 }
 NNS_API int nns_slab_scatter_lines_f64(const double* msg, double* const* fields_host, int nfields, long nouter, long outer_stride, long line_off,
                                        long len, long elem_stride, void* stream) {
-    return lines<double>(false, fields_host, nfields, const_cast<double*>(msg), nouter, outer_stride, line_off, len, elem_stride, S(stream));
+    return lines<double>(false, fields_host, nfields, const_cast<double*>(msg), nouter, outer_stride, line_off, len, elem_stride, as_stream(stream));
 }
 NNS_API int nns_slab_transpose_pack_f32(const float* const* fields_host, int nfields, float* send, int batch, int nloc, int ny, int nranks, void* stream) {
-    return transpose<float>(true, fields_host, nfields, send, batch, nloc, ny, nranks, S(stream));
+    return transpose<float>(true, fields_host, nfields, send, batch, nloc, ny, nranks, as_stream(stream));
 }
 NNS_API int nns_slab_transpose_pack_f64(const double* const* fields_host, int nfields, double* send, int batch, int nloc, int ny, int nranks, void* stream) {
-    return transpose<double>(true, fields_host, nfields, send, batch, nloc, ny, nranks, S(stream));
+    return transpose<double>(true, fields_host, nfields, send, batch, nloc, ny, nranks, as_stream(stream));
 }
 NNS_API int nns_slab_pack_halo_f32(const float* const* fields_host, int nfields, float* send, float* first, float* last, int batch_total, int grid0, int batch,
                                    int nloc, int ny, int nranks, void* stream) {
-    return pack_halo<float>(fields_host, nfields, send, first, last, batch_total, grid0, batch, nloc, ny, nranks, S(stream));
+    return pack_halo<float>(fields_host, nfields, send, first, last, batch_total, grid0, batch, nloc, ny, nranks, as_stream(stream));
 }
 NNS_API int nns_slab_pack_halo_f64(const double* const* fields_host, int nfields, double* send, double* first, double* last, int batch_total, int grid0, int batch,
                                    int nloc, int ny, int nranks, void* stream) {
-    return pack_halo<double>(fields_host, nfields, send, first, last, batch_total, grid0, batch, nloc, ny, nranks, S(stream));
+    return pack_halo<double>(fields_host, nfields, send, first, last, batch_total, grid0, batch, nloc, ny, nranks, as_stream(stream));
 }
 NNS_API int nns_slab_transpose_unpack_f32(const float* recv, float* const* fields_host, int nfields, int batch, int nloc, int ny, int nranks, void* stream) {
-    return transpose<float>(false, fields_host, nfields, const_cast<float*>(recv), batch, nloc, ny, nranks, S(stream));
+    return transpose<float>(false, fields_host, nfields, const_cast<float*>(recv), batch, nloc, ny, nranks, as_stream(stream));
 }
 NNS_API int nns_slab_transpose_unpack_f64(const double* recv, double* const* fields_host, int nfields, int batch, int nloc, int ny, int nranks, void* stream) {
-    return transpose<double>(false, fields_host, nfields, const_cast<double*>(recv), batch, nloc, ny, nranks, S(stream));
+    return transpose<double>(false, fields_host, nfields, const_cast<double*>(recv), batch, nloc, ny, nranks, as_stream(stream));
 }

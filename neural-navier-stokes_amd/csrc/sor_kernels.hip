@@ -61,12 +61,8 @@ int sor(T* p, const T* C, T* info, const T* hint, void* work, int batch, int nx,
     const size_t lds = sor_lds_bytes(nx, ny, sizeof(T));
     T* snap = reinterpret_cast<T*>(work);
     if (lds <= kSorLdsMax) {
-        static bool attr = false;                     // set once to the largest size used (keeps the launch path free of
-        if (!attr) {                                  // non-stream API calls, e.g. under hipGraph capture)
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sor_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSorLdsMax);
-            if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "fd_sor: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr = true;
-        }
+        // the largest size used, not this grid's: one opt-in, no non-stream API call on any later launch (e.g. under hipGraph capture)
+        if (int rc = lds_opt_in<sor_kernel<T, true>>((int)kSorLdsMax, "fd_sor")) return rc;
         hipLaunchKernelGGL((sor_kernel<T, true>), dim3(batch), dim3(kSorThreads), lds, s, p, C, info, snap, hint, nx, ny, max_sweeps, k);
     } else {
         hipLaunchKernelGGL((sor_kernel<T, false>), dim3(batch), dim3(kSorThreads), kSorHdr, s, p, C, info, snap, hint, nx, ny, max_sweeps, k);
@@ -255,12 +251,7 @@ int sor_redblack(T* p, const T* C, T* info, void* work, int batch, int nx, int n
     SorK<T> k{(T)(dx * dx), (T)(dy * dy), (T)(2 * (dx * dx) + 2 * (dy * dy)), (T)beta, (T)(1 - beta), (T)tol, (T)0};
     if (rb_fits_lds(nx, ny, sizeof(T))) {
         const size_t lds = 2 * (size_t)nx * ny * sizeof(T);
-        static bool attr = false;
-        if (!attr) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sor_redblack_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSorLdsMax);
-            if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "fd_sor_redblack: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr = true;
-        }
+        if (int rc = lds_opt_in<sor_redblack_kernel<T>>((int)kSorLdsMax, "fd_sor_redblack")) return rc;
         hipLaunchKernelGGL((sor_redblack_kernel<T>), dim3(batch), dim3(kRbThreads), lds, s, p, C, info, nx, ny, max_sweeps, k);
         return check_launch("fd_sor_redblack");
     }
@@ -288,19 +279,19 @@ NNS_API size_t nns_fd_sor_workspace(int batch, int nx, int ny, int elem_size) {
 }
 NNS_API int nns_fd_sor_f32(float* p, const float* C, float* info, void* work, int batch, int nx, int ny, double dx, double dy,
                            double beta, double tol, int max_sweeps, void* stream) {
-    return sor<float>(p, C, info, nullptr, work, batch, nx, ny, dx, dy, beta, tol, max_sweeps, reinterpret_cast<hipStream_t>(stream));
+    return sor<float>(p, C, info, nullptr, work, batch, nx, ny, dx, dy, beta, tol, max_sweeps, as_stream(stream));
 }
 NNS_API int nns_fd_sor_f64(double* p, const double* C, double* info, void* work, int batch, int nx, int ny, double dx, double dy,
                            double beta, double tol, int max_sweeps, void* stream) {
-    return sor<double>(p, C, info, nullptr, work, batch, nx, ny, dx, dy, beta, tol, max_sweeps, reinterpret_cast<hipStream_t>(stream));
+    return sor<double>(p, C, info, nullptr, work, batch, nx, ny, dx, dy, beta, tol, max_sweeps, as_stream(stream));
 }
 NNS_API int nns_fd_sor_hint_f32(float* p, const float* C, float* info, const float* hint, void* work, int batch, int nx, int ny, double dx, double dy,
                                 double beta, double tol, int max_sweeps, void* stream) {
-    return sor<float>(p, C, info, hint, work, batch, nx, ny, dx, dy, beta, tol, max_sweeps, reinterpret_cast<hipStream_t>(stream));
+    return sor<float>(p, C, info, hint, work, batch, nx, ny, dx, dy, beta, tol, max_sweeps, as_stream(stream));
 }
 NNS_API int nns_fd_sor_hint_f64(double* p, const double* C, double* info, const double* hint, void* work, int batch, int nx, int ny, double dx, double dy,
                                 double beta, double tol, int max_sweeps, void* stream) {
-    return sor<double>(p, C, info, hint, work, batch, nx, ny, dx, dy, beta, tol, max_sweeps, reinterpret_cast<hipStream_t>(stream));
+    return sor<double>(p, C, info, hint, work, batch, nx, ny, dx, dy, beta, tol, max_sweeps, as_stream(stream));
 }
 
 NNS_API size_t nns_fd_sor_redblack_workspace(int batch, int nx, int ny, int elem_size, int max_sweeps) {
@@ -309,27 +300,27 @@ NNS_API size_t nns_fd_sor_redblack_workspace(int batch, int nx, int ny, int elem
 }
 NNS_API int nns_fd_sor_redblack_f32(float* p, const float* C, float* info, void* work, int batch, int nx, int ny, double dx, double dy,
                                     double beta, double tol, int max_sweeps, void* stream) {
-    return sor_redblack<float>(p, C, info, work, batch, nx, ny, dx, dy, beta, tol, max_sweeps, reinterpret_cast<hipStream_t>(stream));
+    return sor_redblack<float>(p, C, info, work, batch, nx, ny, dx, dy, beta, tol, max_sweeps, as_stream(stream));
 }
 NNS_API int nns_fd_sor_redblack_f64(double* p, const double* C, double* info, void* work, int batch, int nx, int ny, double dx, double dy,
                                     double beta, double tol, int max_sweeps, void* stream) {
-    return sor_redblack<double>(p, C, info, work, batch, nx, ny, dx, dy, beta, tol, max_sweeps, reinterpret_cast<hipStream_t>(stream));
+    return sor_redblack<double>(p, C, info, work, batch, nx, ny, dx, dy, beta, tol, max_sweeps, as_stream(stream));
 }
 
 NNS_API int nns_fd_sor_redblack_halfsweep_f32(float* p, const float* C, void* err_bits, int nxl, int ny, int gi0, int colour,
                                               double dx, double dy, double beta, void* stream) {
-    return sor_rb_halfsweep<float>(p, C, err_bits, nxl, ny, gi0, colour, dx, dy, beta, reinterpret_cast<hipStream_t>(stream));
+    return sor_rb_halfsweep<float>(p, C, err_bits, nxl, ny, gi0, colour, dx, dy, beta, as_stream(stream));
 }
 NNS_API int nns_fd_sor_redblack_halfsweep_f64(double* p, const double* C, void* err_bits, int nxl, int ny, int gi0, int colour,
                                               double dx, double dy, double beta, void* stream) {
-    return sor_rb_halfsweep<double>(p, C, err_bits, nxl, ny, gi0, colour, dx, dy, beta, reinterpret_cast<hipStream_t>(stream));
+    return sor_rb_halfsweep<double>(p, C, err_bits, nxl, ny, gi0, colour, dx, dy, beta, as_stream(stream));
 }
 
 NNS_API int nns_fd_sor_redblack_halfsweep_gated_f32(float* p, const float* C, void* err_bits, const void* prev_err_bits, double tol,
                                                     int nxl, int ny, int gi0, int colour, double dx, double dy, double beta, void* stream) {
-    return sor_rb_halfsweep_gated<float>(p, C, err_bits, prev_err_bits, tol, nxl, ny, gi0, colour, dx, dy, beta, reinterpret_cast<hipStream_t>(stream));
+    return sor_rb_halfsweep_gated<float>(p, C, err_bits, prev_err_bits, tol, nxl, ny, gi0, colour, dx, dy, beta, as_stream(stream));
 }
 NNS_API int nns_fd_sor_redblack_halfsweep_gated_f64(double* p, const double* C, void* err_bits, const void* prev_err_bits, double tol,
                                                     int nxl, int ny, int gi0, int colour, double dx, double dy, double beta, void* stream) {
-    return sor_rb_halfsweep_gated<double>(p, C, err_bits, prev_err_bits, tol, nxl, ny, gi0, colour, dx, dy, beta, reinterpret_cast<hipStream_t>(stream));
+    return sor_rb_halfsweep_gated<double>(p, C, err_bits, prev_err_bits, tol, nxl, ny, gi0, colour, dx, dy, beta, as_stream(stream));
 }

@@ -597,42 +597,27 @@ int launch_bwd(const float* u, const float* v, const float* ga, const float* gb,
             // all-float32 mode: the role-split kernel, whose memory waves address with a scalar grid base + a 32-bit byte offset per lane
             if ((unsigned long long)N * (unsigned long long)ny < (1ull << 30)) {
                 using SL = SplitLds<N, float>;
-                auto kern = spec_bwd_xsplit_kernel<N>;
-                static bool attr = false;
-                if (!attr) {
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SL::TOTAL);
-                    if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "spec bwd xpass: hipFuncSetAttribute(%d B): %s", SL::TOTAL, hipGetErrorString(e));
-                    attr = true;
-                }
+                constexpr auto kern = spec_bwd_xsplit_kernel<N>;
+                if (int rc = lds_opt_in<kern>(SL::TOTAL, "spec bwd xpass")) return rc;
                 const int tiles_per_grid = (ny + L::LINES - 1) / L::LINES;
                 const long ntiles = (long)batch * tiles_per_grid;
-                hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < gmax ? ntiles : gmax)), dim3(kSplitThreads), SL::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, ny, tiles_per_grid, ntiles, k);
+                hipLaunchKernelGGL(kern, dim3(capped_grid(ntiles, gmax)), dim3(kSplitThreads), SL::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, ny, tiles_per_grid, ntiles, k);
                 return check_launch("spec_residual_bwd_xpass");
             }
         }
-        auto kern = spec_bwd_xpass_kernel<N, TF>;
-        static bool attr = false;
-        if (!attr) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L::TOTAL);
-            if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "spec bwd xpass: hipFuncSetAttribute(%d B): %s", L::TOTAL, hipGetErrorString(e));
-            attr = true;
-        }
+        constexpr auto kern = spec_bwd_xpass_kernel<N, TF>;
+        if (int rc = lds_opt_in<kern>(L::TOTAL, "spec bwd xpass")) return rc;
         const int ny = nx_or_ny_other;
         const int tiles_per_grid = (ny + L::LINES - 1) / L::LINES;
         const long ntiles = (long)batch * tiles_per_grid;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < gmax ? ntiles : gmax)), dim3(kSpecThreads), L::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, ny, tiles_per_grid, ntiles, k);
+        hipLaunchKernelGGL(kern, dim3(capped_grid(ntiles, gmax)), dim3(kSpecThreads), L::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, ny, tiles_per_grid, ntiles, k);
         return check_launch("spec_residual_bwd_xpass");
     }
-    auto kern = spec_bwd_ypass_kernel<N, TF>;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L::TOTAL);
-        if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "spec bwd ypass: hipFuncSetAttribute(%d B): %s", L::TOTAL, hipGetErrorString(e));
-        attr = true;
-    }
+    constexpr auto kern = spec_bwd_ypass_kernel<N, TF>;
+    if (int rc = lds_opt_in<kern>(L::TOTAL, "spec bwd ypass")) return rc;
     const long nrows = (long)batch * nx_or_ny_other;
     const long niter = (nrows + L::LINES - 1) / L::LINES;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(niter < gmax ? niter : gmax)), dim3(kSpecThreads), L::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, gup, gvp, nrows, k);
+    hipLaunchKernelGGL(kern, dim3(capped_grid(niter, gmax)), dim3(kSpecThreads), L::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, gup, gvp, nrows, k);
     return check_launch("spec_residual_bwd_ypass");
 }
 
@@ -644,7 +629,7 @@ NNS_API int nns_spec_residual_bwd_f32(const float* u, const float* v, const floa
     if (!u || !v || !g_u || !g_v || !g_div || !grad_u || !grad_v || !grad_p || batch < 1)
         return fail(NNS_ERR_INVALID_ARG, "spec_residual_bwd: bad args");
     if (Lx == 0 || Ly == 0 || rho == 0 || dt == 0) return fail(NNS_ERR_INVALID_ARG, "spec_residual_bwd: Lx, Ly, rho, dt must be non-zero");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = as_stream(stream);
     // per axis: the FFT engine for powers of two in [64, 1024], circulant matrices in float64 for any other length (spectral_dense.hip)
     if (!spec_len_ok(nx) || !spec_len_ok(ny))
         return fail(NNS_ERR_UNSUPPORTED, "spec_residual_bwd: nx=%d, ny=%d: powers of two in [64, 1024] (FFT engine) or any length 3 .. %d (dense fallback)", nx, ny, kDenseMaxLen);
@@ -656,14 +641,14 @@ NNS_API int nns_spec_residual_bwd_f32(const float* u, const float* v, const floa
     const double kx = 2.0 * M_PI / Lx, ky = 2.0 * M_PI / Ly;
     const AdjK kxp{kx / nx, nu * kx * kx / nx, (float)(1.0 / rho), (float)(1.0 / dt)};
     const AdjK kyp{ky / ny, nu * ky * ky / ny, (float)(1.0 / rho), (float)(1.0 / dt)};
-    int rc = x_done ? 0 : dispatch_n(nx, [&](auto n) {
+    int rc = x_done ? 0 : dispatch_pow2(nx, "spectral", [&](auto n) {
         constexpr int N = decltype(n)::value;
         return !spec_f32_mode(precise, nu, nx, Lx) ? launch_bwd<N, double>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, nullptr, nullptr, batch, ny, true, kxp, s)
                                                   : launch_bwd<N, float>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, nullptr, nullptr, batch, ny, true, kxp, s);
     });
     if (rc) return rc;
     if (!pow2_in_range(ny)) return dense_bwd_ypass(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, grad_u_prev, grad_v_prev, batch, nx, ny, dt, Ly, rho, nu, s);
-    return dispatch_n(ny, [&](auto n) {
+    return dispatch_pow2(ny, "spectral", [&](auto n) {
         constexpr int N = decltype(n)::value;
         return !spec_f32_mode(precise, nu, ny, Ly) ? launch_bwd<N, double>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, grad_u_prev, grad_v_prev, batch, nx, false, kyp, s)
                                                   : launch_bwd<N, float>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, grad_u_prev, grad_v_prev, batch, nx, false, kyp, s);

@@ -1,5 +1,5 @@
 // Scaffolding shared by the spectral residual kernels (forward: spectral_kernels.hip, backward:
-// spectral_bwd_kernels.hip): launch geometry, LDS layout, wavenumber helper, table setup, size dispatch.
+// spectral_bwd_kernels.hip): launch geometry, LDS layout, wavenumber helper, table setup.
 #pragma once
 #include "nns_common.h"
 #include "fft_lds.h"
@@ -130,7 +130,6 @@ __device__ __forceinline__ float right_of(const float (&x)[16], int tid) {
 // (1.9 at the headline configuration: 1.1e-6 rel-L2 against the float64 oracle, 4e-6 worst case over nu <= 1 on resolved fields;
 // tools/spec_accuracy_f32.py, profiles/r02_accuracy_f32diff.json).  precise = 1 takes it while that factor is <= 8 and the float64
 // forward transform otherwise; precise = 0 always, precise >= 2 never (NNS_SPEC_F64=1 in the environment: as precise = 2).
-inline bool pow2_in_range(int n) { return n >= 64 && n <= 1024 && (n & (n - 1)) == 0; }
 constexpr double kF32AmpMax = 8.0;
 inline bool spec_f32_mode(int precise, double nu, int n, double len) {
     if (!precise) return true;
@@ -166,19 +165,6 @@ int dense_bwd_xpass(const float* u, const float* v, const float* ga, const float
                     int batch, int nx, int ny, double Lx, double rho, double nu, hipStream_t s);
 int dense_bwd_ypass(const float* u, const float* v, const float* ga, const float* gb, const float* gd, float* gu, float* gv, float* gp,
                     float* gup, float* gvp, int batch, int nx, int ny, double dt, double Ly, double rho, double nu, hipStream_t s);
-
-template <typename F>
-int dispatch_n(int n, F&& f) {
-    switch (n) {
-        case 64: return f(std::integral_constant<int, 64>{});
-        case 128: return f(std::integral_constant<int, 128>{});
-        case 256: return f(std::integral_constant<int, 256>{});
-        case 512: return f(std::integral_constant<int, 512>{});
-        case 1024: return f(std::integral_constant<int, 1024>{});
-    }
-    return fail(NNS_ERR_UNSUPPORTED, "spectral: axis length %d is not a power of two in [64, 1024] (the FFT engine's sizes)", n);
-}
-
 
 }  // namespace spec
 }  // namespace nns

@@ -825,31 +825,17 @@ int launch_xpass(const float* u, const float* v, const float* p, float* ru, floa
                                            : (unsigned long long)N * (unsigned long long)ny;
     const bool off32_ok = max_off < (1ull << 30);
     if (off32_ok) {
-        auto kern = spec_xpass_split_kernel<N, TF, SEG>;
+        constexpr auto kern = spec_xpass_split_kernel<N, TF, SEG>;
         using SL = SplitLds<N, TF>;
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SL::TOTAL);
-            if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "spec xpass: hipFuncSetAttribute(%d B): %s", SL::TOTAL, hipGetErrorString(e));
-            attr_set = true;
-        }
-        const long gmax = spec_grid_cap();
-        const unsigned grid = (unsigned)(ntiles < gmax ? ntiles : gmax);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kSplitThreads), SL::TOTAL, s, u, v, p, ru, rv, rd, ny, tiles_per_grid, ntiles, k, sg);
+        if (int rc = lds_opt_in<kern>(SL::TOTAL, "spec xpass")) return rc;
+        hipLaunchKernelGGL(kern, dim3(capped_grid(ntiles, spec_grid_cap())), dim3(kSplitThreads), SL::TOTAL, s, u, v, p, ru, rv, rd, ny, tiles_per_grid, ntiles, k, sg);
         return check_launch("spec_residual_xpass");
     }
     // prefetch is disabled where hipcc (ROCm 7.2) spills with it: checked with -Rpass-analysis=kernel-resource-usage
     constexpr bool PF = !((N == 128 && sizeof(TF) == 4) || N == 256);
-    auto kern = spec_xpass_kernel<N, TF, PF, SEG>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L::TOTAL);
-        if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "spec xpass: hipFuncSetAttribute(%d B): %s", L::TOTAL, hipGetErrorString(e));
-        attr_set = true;
-    }
-    const long gmax = spec_grid_cap();
-    const unsigned grid = (unsigned)(ntiles < gmax ? ntiles : gmax);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kSpecThreads), L::TOTAL, s, u, v, p, ru, rv, rd, ny, tiles_per_grid, ntiles, k, sg);
+    constexpr auto kern = spec_xpass_kernel<N, TF, PF, SEG>;
+    if (int rc = lds_opt_in<kern>(L::TOTAL, "spec xpass")) return rc;
+    hipLaunchKernelGGL(kern, dim3(capped_grid(ntiles, spec_grid_cap())), dim3(kSpecThreads), L::TOTAL, s, u, v, p, ru, rv, rd, ny, tiles_per_grid, ntiles, k, sg);
     return check_launch("spec_residual_xpass");
 }
 
@@ -858,24 +844,13 @@ int launch_ypass(const float* u, const float* v, const float* p, const float* up
                  long nrows, const SpecK& k, hipStream_t s, float* fu = nullptr, float* fv = nullptr, float* fd = nullptr, int nx = 1,
                  const FdK& fk = FdK{}, const HaloK& hk = HaloK{}, const PartK& pk = PartK{}) {
     using L = SpecLds<N, TF>;
-    auto kern = spec_ypass_kernel<N, TF, FUSE_FD, SEGP>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L::TOTAL);
-        if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "spec ypass: hipFuncSetAttribute(%d B): %s", L::TOTAL, hipGetErrorString(e));
-        attr_set = true;
-    }
+    constexpr auto kern = spec_ypass_kernel<N, TF, FUSE_FD, SEGP>;
+    if (int rc = lds_opt_in<kern>(L::TOTAL, "spec ypass")) return rc;
     const long niter = (nrows + L::LINES - 1) / L::LINES;
-    const long gmax = spec_grid_cap();
-    const unsigned grid = (unsigned)(niter < gmax ? niter : gmax);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kSpecThreads), L::TOTAL, s, u, v, p, up, vp, ru, rv, rd, fu, fv, fd, nx, fk, nrows, k, hk, pk);
+    hipLaunchKernelGGL(kern, dim3(capped_grid(niter, spec_grid_cap())), dim3(kSpecThreads), L::TOTAL, s, u, v, p, up, vp, ru, rv, rd, fu, fv, fd, nx, fk, nrows, k, hk, pk);
     return check_launch("spec_residual_ypass");
 }
 
-inline int device_cus() {
-    static const int n = [] { int dev = 0, v = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) v = 256; return v; }();
-    return n;
-}
 // rows per chunk of the marching row pass: one chunk per line once every CU is busy, a power of two in [1, 64].  Small batches get
 // short chunks (R = 1: three row reads per row, as the non-marching kernel, but those fit the caches); the SAME kernel serves every
 // batch size, so grid b of a large batch equals the same grid evaluated alone bit for bit.
@@ -893,18 +868,12 @@ int launch_rowmarch(const float* u, const float* v, const float* p, const float*
                     float* fu, float* fv, float* fd, int batch, int nx, int R, const SpecK& k, const FdK& fk, const HaloK& hk, hipStream_t s,
                     const PartK& pk = PartK{}) {
     using ML = MarchLds<N>;
-    auto kern = spec_rowmarch_kernel<N, SEGP>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, ML::TOTAL);
-        if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "spec rowmarch: hipFuncSetAttribute(%d B): %s", ML::TOTAL, hipGetErrorString(e));
-        attr_set = true;
-    }
+    constexpr auto kern = spec_rowmarch_kernel<N, SEGP>;
+    if (int rc = lds_opt_in<kern>(ML::TOTAL, "spec rowmarch")) return rc;
     const int chunks_per_grid = (nx + R - 1) / R;
     const long nchunks = (long)batch * chunks_per_grid;
     const long wgs = (nchunks + ML::L::LINES - 1) / ML::L::LINES;
-    const unsigned grid = (unsigned)(wgs < device_cus() ? wgs : device_cus());
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kSpecThreads), ML::TOTAL, s, u, v, p, up, vp, ru, rv, rd, fu, fv, fd, nx, fk, k, hk, R, chunks_per_grid, nchunks, pk);
+    hipLaunchKernelGGL(kern, dim3(capped_grid(wgs, device_cus())), dim3(kSpecThreads), ML::TOTAL, s, u, v, p, up, vp, ru, rv, rd, fu, fv, fd, nx, fk, k, hk, R, chunks_per_grid, nchunks, pk);
     return check_launch("residual_both_rowpass");
 }
 

@@ -15,7 +15,7 @@ int xpass(const float* u, const float* v, const float* p, float* ru, float* rv, 
     const double ks = 2.0 * M_PI / Lx;
     SpecK k{ks / nx, ks / (rho * nx), nu * ks * ks / nx, 0.f};
     const bool f64 = !spec_f32_mode(precise, nu, nx, Lx);
-    return dispatch_n(nx, [&](auto n) {
+    return dispatch_pow2(nx, "spectral", [&](auto n) {
         constexpr int N = decltype(n)::value;
         return f64 ? launch_xpass<N, double>(u, v, p, ru, rv, rd, batch, ny, k, s)
                    : launch_xpass<N, float>(u, v, p, ru, rv, rd, batch, ny, k, s);
@@ -31,7 +31,7 @@ int ypass(const float* u, const float* v, const float* p, const float* up, const
     SpecK k{ks / ny, ks / (rho * ny), nu * ks * ks / ny, (float)(1.0 / dt)};
     const long nrows = (long)batch * nx;
     const bool f64 = !spec_f32_mode(precise, nu, ny, Ly);
-    return dispatch_n(ny, [&](auto n) {
+    return dispatch_pow2(ny, "spectral", [&](auto n) {
         constexpr int N = decltype(n)::value;
         return f64 ? launch_ypass<N, double>(u, v, p, up, vp, ru, rv, rd, nrows, k, s)
                    : launch_ypass<N, float>(u, v, p, up, vp, ru, rv, rd, nrows, k, s);
@@ -67,7 +67,7 @@ int residual_both(const float* u, const float* v, const float* p, const float* u
     const FdK fk{(float)(1.0 / (2 * dx)), (float)(1.0 / (2 * dy)), (float)(1.0 / rho), (float)nu, 1.0 / (dx * dx), 1.0 / (dy * dy),
                  (float)(1.0 / (dx * dx)), (float)(1.0 / (dy * dy))};
     const HaloK hk{halo_top, halo_bot, halo_fstride > 0 ? halo_fstride : (long)batch * ny};
-    return dispatch_n(ny, [&](auto n) {
+    return dispatch_pow2(ny, "spectral", [&](auto n) {
         constexpr int N = decltype(n)::value;
         const long nrows = (long)batch * nx;
         if (!spec_f32_mode(precise, nu, ny, Ly)) return launch_ypass<N, double, true>(u, v, p, up, vp, ru, rv, rd, nrows, k, s, fu, fv, fd, nx, fk, hk);
@@ -77,17 +77,15 @@ int residual_both(const float* u, const float* v, const float* p, const float* u
 
 }  // namespace
 
-#define S(stream) reinterpret_cast<hipStream_t>(stream)
-
 NNS_API int nns_residual_both_f32(const float* u, const float* v, const float* p, const float* u_prev, const float* v_prev,
                                   float* fd_r_u, float* fd_r_v, float* fd_r_div, float* sp_r_u, float* sp_r_v, float* sp_r_div,
                                   int batch, int nx, int ny, double dt, double Lx, double Ly, double rho, double nu, int precise, void* stream) {
-    return residual_both(u, v, p, u_prev, v_prev, fd_r_u, fd_r_v, fd_r_div, sp_r_u, sp_r_v, sp_r_div, batch, nx, ny, dt, Lx, Ly, rho, nu, precise, S(stream), true);
+    return residual_both(u, v, p, u_prev, v_prev, fd_r_u, fd_r_v, fd_r_div, sp_r_u, sp_r_v, sp_r_div, batch, nx, ny, dt, Lx, Ly, rho, nu, precise, as_stream(stream), true);
 }
 NNS_API int nns_residual_both_rowpass_f32(const float* u, const float* v, const float* p, const float* u_prev, const float* v_prev,
                                           float* fd_r_u, float* fd_r_v, float* fd_r_div, float* sp_r_u, float* sp_r_v, float* sp_r_div,
                                           int batch, int nx, int ny, double dt, double Lx, double Ly, double rho, double nu, int precise, void* stream) {
-    return residual_both(u, v, p, u_prev, v_prev, fd_r_u, fd_r_v, fd_r_div, sp_r_u, sp_r_v, sp_r_div, batch, nx, ny, dt, Lx, Ly, rho, nu, precise, S(stream), false);
+    return residual_both(u, v, p, u_prev, v_prev, fd_r_u, fd_r_v, fd_r_div, sp_r_u, sp_r_v, sp_r_div, batch, nx, ny, dt, Lx, Ly, rho, nu, precise, as_stream(stream), false);
 }
 
 NNS_API int nns_residual_both_rowpass_halo_f32(const float* u, const float* v, const float* p, const float* u_prev, const float* v_prev,
@@ -99,16 +97,16 @@ NNS_API int nns_residual_both_rowpass_halo_f32(const float* u, const float* v, c
     if (halo_field_stride != 0 && halo_field_stride < (long)batch * ny)
         return fail(NNS_ERR_INVALID_ARG, "residual_both_rowpass_halo: halo_field_stride=%ld must be 0 (= batch * ny) or >= batch * ny = %ld", halo_field_stride, (long)batch * ny);
     return residual_both(u, v, p, u_prev, v_prev, fd_r_u, fd_r_v, fd_r_div, sp_r_u, sp_r_v, sp_r_div, batch, nx_local, ny, dt, dx, Ly, rho, nu, precise,
-                         S(stream), false, halo_top, halo_bot, halo_field_stride);
+                         as_stream(stream), false, halo_top, halo_bot, halo_field_stride);
 }
 NNS_API int nns_spec_residual_xpass_f32(const float* u, const float* v, const float* p, float* r_u, float* r_v, float* r_div,
                                         int batch, int nx, int ny, double Lx, double rho, double nu, int precise, void* stream) {
-    return xpass(u, v, p, r_u, r_v, r_div, batch, nx, ny, Lx, rho, nu, precise, S(stream));
+    return xpass(u, v, p, r_u, r_v, r_div, batch, nx, ny, Lx, rho, nu, precise, as_stream(stream));
 }
 NNS_API int nns_spec_residual_ypass_f32(const float* u, const float* v, const float* p, const float* u_prev, const float* v_prev,
                                         float* r_u, float* r_v, float* r_div, int batch, int nx, int ny, double dt, double Ly,
                                         double rho, double nu, int precise, void* stream) {
-    return ypass(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx, ny, dt, Ly, rho, nu, precise, S(stream));
+    return ypass(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx, ny, dt, Ly, rho, nu, precise, as_stream(stream));
 }
 NNS_API int nns_spec_residual_f32(const float* u, const float* v, const float* p, const float* u_prev, const float* v_prev,
                                   float* r_u, float* r_v, float* r_div, int batch, int nx, int ny, double dt, double Lx, double Ly,
@@ -116,8 +114,8 @@ NNS_API int nns_spec_residual_f32(const float* u, const float* v, const float* p
     if (!spec_len_ok(nx) || !spec_len_ok(ny))                  // before the first launch: both axes must have an engine
         return fail(NNS_ERR_UNSUPPORTED, "spec_residual: nx=%d, ny=%d: powers of two in [64, 1024] (FFT engine) or any length 3 .. %d (dense fallback)", nx, ny, kDenseMaxLen);
     const int pr = spec_resolve_precise(precise, nu, nx, Lx, ny, Ly);       // one arithmetic for both passes
-    if (int rc = xpass(u, v, p, r_u, r_v, r_div, batch, nx, ny, Lx, rho, nu, pr, S(stream))) return rc;
-    return ypass(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx, ny, dt, Ly, rho, nu, pr, S(stream));
+    if (int rc = xpass(u, v, p, r_u, r_v, r_div, batch, nx, ny, Lx, rho, nu, pr, as_stream(stream))) return rc;
+    return ypass(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx, ny, dt, Ly, rho, nu, pr, as_stream(stream));
 }
 
 // The arithmetic a `precise` request resolves to for a whole evaluation (0 = all-float32 transforms, 2 = float64 forward transforms): hosts that

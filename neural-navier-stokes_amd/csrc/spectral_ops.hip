@@ -215,89 +215,66 @@ __global__ __launch_bounds__(kT) void cols_kernel(const float* __restrict__ in, 
     }
 }
 
-template <typename K>
-int set_lds(K kern, int bytes, const char* what) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return fail(NNS_ERR_LAUNCH, "%s: hipFuncSetAttribute(%d B): %s", what, bytes, hipGetErrorString(e));
-    return NNS_OK;
-}
-
-inline bool pow2ok(int n) { return n >= 64 && n <= 1024 && (n & (n - 1)) == 0; }
-
-template <typename F>
-int dispatch(int n, F&& f) {
-    switch (n) {
-        case 64: return f(std::integral_constant<int, 64>{});
-        case 128: return f(std::integral_constant<int, 128>{});
-        case 256: return f(std::integral_constant<int, 256>{});
-        case 512: return f(std::integral_constant<int, 512>{});
-        case 1024: return f(std::integral_constant<int, 1024>{});
-    }
-    return fail(NNS_ERR_UNSUPPORTED, "spectral op: axis length %d is not a power of two in [64, 1024]", n);
-}
-
 template <int N, typename TF, int MODE>
 int launch_rows(const float* in, float* o0, float* o1, long nrows, double kscale, float scale, hipStream_t s) {
     using L = OpsLds<N, TF>;
-    auto kern = rows_kernel<N, TF, MODE>;
-    if (int rc = set_lds(kern, L::TOTAL, "spectral rows")) return rc;
+    constexpr auto kern = rows_kernel<N, TF, MODE>;
+    if (int rc = lds_opt_in<kern>(L::TOTAL, "spectral rows")) return rc;
     const long niter = (nrows + L::LINES - 1) / L::LINES;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(niter < 2048 ? niter : 2048)), dim3(kT), L::TOTAL, s, in, o0, o1, nrows, kscale, scale);
+    hipLaunchKernelGGL(kern, dim3(capped_grid(niter, 2048)), dim3(kT), L::TOTAL, s, in, o0, o1, nrows, kscale, scale);
     return check_launch("spectral rows");
 }
 
 template <int N, typename TF, int MODE, bool INV>
 int launch_cols(const float* in, float* o0, float* o1, int batch, int ncols, double kscale, hipStream_t s) {
     using L = OpsLds<N, TF>;
-    auto kern = cols_kernel<N, TF, MODE, INV>;
-    if (int rc = set_lds(kern, L::TOTAL, "spectral cols")) return rc;
+    constexpr auto kern = cols_kernel<N, TF, MODE, INV>;
+    if (int rc = lds_opt_in<kern>(L::TOTAL, "spectral cols")) return rc;
     const int tpg = (ncols + L::LINES - 1) / L::LINES;
     const long ntiles = (long)batch * tpg;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(kT), L::TOTAL, s, in, o0, o1, ncols, tpg, ntiles, kscale);
+    hipLaunchKernelGGL(kern, dim3(capped_grid(ntiles, 2048)), dim3(kT), L::TOTAL, s, in, o0, o1, ncols, tpg, ntiles, kscale);
     return check_launch("spectral cols");
 }
 
 }  // namespace
 
-#define S(stream) reinterpret_cast<hipStream_t>(stream)
-
 NNS_API int nns_spec_rfft2_f32(const float* f, float* spec, int batch, int nx, int ny, void* stream) {
     if (!f || !spec || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_rfft2: bad args");
-    if (!pow2ok(nx) || !pow2ok(ny)) return fail(NNS_ERR_UNSUPPORTED, "spec_rfft2: nx=%d, ny=%d must be powers of two in [64, 1024]", nx, ny);
+    if (!pow2_in_range(nx) || !pow2_in_range(ny)) return fail(NNS_ERR_UNSUPPORTED, "spec_rfft2: nx=%d, ny=%d must be powers of two in [64, 1024]", nx, ny);
     const int nh = ny / 2 + 1;
-    int rc = dispatch(ny, [&](auto n) { return launch_rows<decltype(n)::value, float, 0>(f, spec, nullptr, (long)batch * nx, 0.0, 1.f, S(stream)); });
+    int rc = dispatch_pow2(ny, "spectral op", [&](auto n) { return launch_rows<decltype(n)::value, float, 0>(f, spec, nullptr, (long)batch * nx, 0.0, 1.f, as_stream(stream)); });
     if (rc) return rc;
-    return dispatch(nx, [&](auto n) { return launch_cols<decltype(n)::value, float, 0, false>(spec, spec, nullptr, batch, nh, 0.0, S(stream)); });
+    return dispatch_pow2(nx, "spectral op", [&](auto n) { return launch_cols<decltype(n)::value, float, 0, false>(spec, spec, nullptr, batch, nh, 0.0, as_stream(stream)); });
 }
 
 // spec is used as scratch for the column pass (it is overwritten).
 NNS_API int nns_spec_irfft2_f32(float* spec, float* f, int batch, int nx, int ny, void* stream) {
     if (!f || !spec || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_irfft2: bad args");
-    if (!pow2ok(nx) || !pow2ok(ny)) return fail(NNS_ERR_UNSUPPORTED, "spec_irfft2: nx=%d, ny=%d must be powers of two in [64, 1024]", nx, ny);
+    if (!pow2_in_range(nx) || !pow2_in_range(ny)) return fail(NNS_ERR_UNSUPPORTED, "spec_irfft2: nx=%d, ny=%d must be powers of two in [64, 1024]", nx, ny);
     const int nh = ny / 2 + 1;
-    int rc = dispatch(nx, [&](auto n) { return launch_cols<decltype(n)::value, float, 0, true>(spec, spec, nullptr, batch, nh, 0.0, S(stream)); });
+    int rc = dispatch_pow2(nx, "spectral op", [&](auto n) { return launch_cols<decltype(n)::value, float, 0, true>(spec, spec, nullptr, batch, nh, 0.0, as_stream(stream)); });
     if (rc) return rc;
     const float scale = (float)(1.0 / ((double)nx * ny));
-    return dispatch(ny, [&](auto n) { return launch_rows<decltype(n)::value, float, 1>(spec, f, nullptr, (long)batch * nx, 0.0, scale, S(stream)); });
+    return dispatch_pow2(ny, "spectral op", [&](auto n) { return launch_rows<decltype(n)::value, float, 1>(spec, f, nullptr, (long)batch * nx, 0.0, scale, as_stream(stream)); });
 }
 
 NNS_API int nns_spec_derivs_f32(const float* f, float* f_x, float* f_y, float* f_lap, int batch, int nx, int ny, double Lx, double Ly,
                                 int precise, void* stream) {
     if (!f || batch < 1 || Lx == 0 || Ly == 0) return fail(NNS_ERR_INVALID_ARG, "spec_derivs: bad args");
-    if (!pow2ok(nx) || !pow2ok(ny)) return fail(NNS_ERR_UNSUPPORTED, "spec_derivs: nx=%d, ny=%d must be powers of two in [64, 1024]", nx, ny);
+    if (!pow2_in_range(nx) || !pow2_in_range(ny)) return fail(NNS_ERR_UNSUPPORTED, "spec_derivs: nx=%d, ny=%d must be powers of two in [64, 1024]", nx, ny);
     if (!f_x && !f_y && !f_lap) return NNS_OK;
-    hipStream_t s = S(stream);
+    hipStream_t s = as_stream(stream);
     const double kx = 2.0 * M_PI / Lx, ky = 2.0 * M_PI / Ly;
     int rc = NNS_OK;
     if (f_x || f_lap) {
-        rc = dispatch(nx, [&](auto n) {
+        rc = dispatch_pow2(nx, "spectral op", [&](auto n) {
             constexpr int N = decltype(n)::value;
             return precise ? launch_cols<N, double, 2, false>(f, f_x, f_lap, batch, ny, kx, s) : launch_cols<N, float, 2, false>(f, f_x, f_lap, batch, ny, kx, s);
         });
         if (rc) return rc;
     }
     if (f_y || f_lap) {
-        rc = dispatch(ny, [&](auto n) {
+        rc = dispatch_pow2(ny, "spectral op", [&](auto n) {
             constexpr int N = decltype(n)::value;
             return precise ? launch_rows<N, double, 2>(f, f_y, f_lap, (long)batch * nx, ky, 1.f, s) : launch_rows<N, float, 2>(f, f_y, f_lap, (long)batch * nx, ky, 1.f, s);
         });

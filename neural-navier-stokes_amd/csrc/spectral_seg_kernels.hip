@@ -34,8 +34,6 @@ int check_part(const char* what, const float* pu, const float* pv, const float* 
 
 }  // namespace
 
-#define S(stream) reinterpret_cast<hipStream_t>(stream)
-
 NNS_API int nns_spec_residual_xpass_seg_f32(const float* u, const float* v, const float* p, float* r_u, float* r_v, float* r_div,
                                             int batch, int nx, int ny, int seg_rows, long seg_stride, double Lx, double rho, double nu, int precise, void* stream) {
     if (seg_rows < 1) return fail(NNS_ERR_INVALID_ARG, "spec_residual_xpass_seg: seg_rows must be >= 1");
@@ -48,10 +46,10 @@ NNS_API int nns_spec_residual_xpass_seg_f32(const float* u, const float* v, cons
     const SpecK k{ks / nx, ks / (rho * nx), nu * ks * ks / nx, 0.f};
     const bool f64 = !spec_f32_mode(precise, nu, nx, Lx);
     const SegK sg{__builtin_ctz((unsigned)seg_rows), seg_stride};
-    return dispatch_n(nx, [&](auto n) {
+    return dispatch_pow2(nx, "spectral", [&](auto n) {
         constexpr int N = decltype(n)::value;
-        return f64 ? launch_xpass<N, double, true>(u, v, p, r_u, r_v, r_div, batch, ny, k, S(stream), sg)
-                   : launch_xpass<N, float, true>(u, v, p, r_u, r_v, r_div, batch, ny, k, S(stream), sg);
+        return f64 ? launch_xpass<N, double, true>(u, v, p, r_u, r_v, r_div, batch, ny, k, as_stream(stream), sg)
+                   : launch_xpass<N, float, true>(u, v, p, r_u, r_v, r_div, batch, ny, k, as_stream(stream), sg);
     });
 }
 
@@ -67,10 +65,10 @@ NNS_API int nns_spec_residual_ypass_seg_f32(const float* u, const float* v, cons
     const SpecK k{ks / ny, ks / (rho * ny), nu * ks * ks / ny, (float)(1.0 / dt)};
     const long nrows = (long)batch * nx;
     const bool f64 = !spec_f32_mode(precise, nu, ny, Ly);
-    return dispatch_n(ny, [&](auto n) {
+    return dispatch_pow2(ny, "spectral", [&](auto n) {
         constexpr int N = decltype(n)::value;
-        return f64 ? launch_ypass<N, double, false, true>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, nrows, k, S(stream), nullptr, nullptr, nullptr, 1, FdK{}, HaloK{}, pk)
-                   : launch_ypass<N, float, false, true>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, nrows, k, S(stream), nullptr, nullptr, nullptr, 1, FdK{}, HaloK{}, pk);
+        return f64 ? launch_ypass<N, double, false, true>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, nrows, k, as_stream(stream), nullptr, nullptr, nullptr, 1, FdK{}, HaloK{}, pk)
+                   : launch_ypass<N, float, false, true>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, nrows, k, as_stream(stream), nullptr, nullptr, nullptr, 1, FdK{}, HaloK{}, pk);
     });
 }
 
@@ -94,11 +92,11 @@ NNS_API int nns_residual_both_rowpass_halo_seg_f32(const float* u, const float* 
     const FdK fk{(float)(1.0 / (2 * dx)), (float)(1.0 / (2 * dy)), (float)(1.0 / rho), (float)nu, 1.0 / (dx * dx), 1.0 / (dy * dy),
                  (float)(1.0 / (dx * dx)), (float)(1.0 / (dy * dy))};
     const HaloK hk{halo_top, halo_bot, halo_field_stride > 0 ? halo_field_stride : (long)batch * ny};
-    return dispatch_n(ny, [&](auto n) {
+    return dispatch_pow2(ny, "spectral", [&](auto n) {
         constexpr int N = decltype(n)::value;
         const long nrows = (long)batch * nx;
         if (!spec_f32_mode(precise, nu, ny, Ly))
-            return launch_ypass<N, double, true, true>(u, v, p, u_prev, v_prev, sp_r_u, sp_r_v, sp_r_div, nrows, k, S(stream), fd_r_u, fd_r_v, fd_r_div, nx, fk, hk, pk);
-        return launch_rowmarch<N, true>(u, v, p, u_prev, v_prev, sp_r_u, sp_r_v, sp_r_div, fd_r_u, fd_r_v, fd_r_div, batch, nx, march_chunk_rows<N>(nrows, nx), k, fk, hk, S(stream), pk);
+            return launch_ypass<N, double, true, true>(u, v, p, u_prev, v_prev, sp_r_u, sp_r_v, sp_r_div, nrows, k, as_stream(stream), fd_r_u, fd_r_v, fd_r_div, nx, fk, hk, pk);
+        return launch_rowmarch<N, true>(u, v, p, u_prev, v_prev, sp_r_u, sp_r_v, sp_r_div, fd_r_u, fd_r_v, fd_r_div, batch, nx, march_chunk_rows<N>(nrows, nx), k, fk, hk, as_stream(stream), pk);
     });
 }

@@ -6,6 +6,8 @@ hand-written HIP kernels of csrc/.  Every function takes contiguous CUDA(HIP) te
 torch's current stream and returns its outputs as tensors.  Errors raise nns._lib.NnsError with
 the library's message; there is no CPU fallback.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -13,7 +15,6 @@ from ._lib import BcList, check
 
 KIND = {'dirichlet': 0, 'neumann': 1}
 SIDE = {'left': 0, 'right': 1, 'bottom': 2, 'top': 3}
-
 
 
 def _prec(precise):
@@ -80,6 +81,32 @@ def _p(t):
     return t.data_ptr()
 
 
+def _query_bytes(name, *args):
+    """The size a workspace query returns through its trailing size_t* argument."""
+    n = ctypes.c_size_t(0)
+    check(getattr(_lib.lib(), name)(*args, ctypes.byref(n)), name)
+    return n.value
+
+
+def _workspace(nbytes, like):
+    """nbytes of scratch as elements of like's dtype, on its device."""
+    return torch.empty(nbytes // like.element_size(), dtype=like.dtype, device=like.device)
+
+
+def _halo_msgs(who, halo_top, halo_bot, u, B, ny, halo_grid0=None):
+    """The two [3, Bh, ny] halo messages of a row slab of B grids; returns Bh.  halo_grid0 None: Bh = B; otherwise the messages may cover a larger
+    batch, of which the call takes grids halo_grid0 .. halo_grid0 + B - 1."""
+    exact = halo_grid0 is None
+    g0 = 0 if exact else halo_grid0
+    Bh = halo_top.shape[1] if halo_top.dim() == 3 else -1
+    for h in (halo_top, halo_bot):
+        if not (h.is_cuda and h.is_contiguous() and h.dtype == u.dtype and tuple(h.shape) == (3, Bh, ny) and 0 <= g0 and g0 + B <= Bh
+                and (Bh == B or not exact)):
+            raise ValueError("%s: halo messages must be contiguous [3, %s%d, %d] %s" % (
+                who, '' if exact else '>= ', g0 + B, ny, "device tensors of the fields' dtype" if exact else "float32 device tensors"))
+    return Bh
+
+
 # ----------------------------------------------------------------------------- boundary
 def bc_apply_(A, bcs):
     suf, (B, nx, ny) = _chk(A)
@@ -113,8 +140,7 @@ def fd_predictor_adi(un, vn, un1, vn1, dt, dx, dy, nu, corrected=False, column_s
         raise ValueError("fd_predictor_adi: column slabs are for the reference ADI (both solves along axis 0)")
     suf, (B, nx, ny) = _chk(un, vn, un1, vn1)
     ui, vi = torch.empty_like(un), torch.empty_like(vn)
-    nbytes = _lib.lib().nns_fd_predictor_adi_workspace(B, nx, ny, un.element_size())
-    work = torch.empty(nbytes // un.element_size(), dtype=un.dtype, device=un.device)
+    work = _workspace(_lib.lib().nns_fd_predictor_adi_workspace(B, nx, ny, un.element_size()), un)
     _call('nns_fd_predictor_adi_corrected' if corrected else 'nns_fd_predictor_adi_colslab' if column_slab else 'nns_fd_predictor_adi', suf, _p(un), _p(vn), _p(un1), _p(vn1), _p(ui), _p(vi), _p(work), B, nx, ny,
           dt, dx, dy, nu, _stream())
     return ui, vi
@@ -140,8 +166,7 @@ def fd_sor_(p, C, dx, dy, beta, tol, max_sweeps, hint=None):
     grids in a time loop (sizes the first speculative batch of sweeps; the result does not depend on it)."""
     suf, (B, nx, ny) = _chk(p, C)
     info = torch.empty(B, 2, dtype=p.dtype, device=p.device)
-    nbytes = _lib.lib().nns_fd_sor_workspace(B, nx, ny, p.element_size())
-    work = torch.empty(nbytes // p.element_size(), dtype=p.dtype, device=p.device)
+    work = _workspace(_lib.lib().nns_fd_sor_workspace(B, nx, ny, p.element_size()), p)
     _call('nns_fd_sor_hint', suf, _p(p), _p(C), _p(info), _sor_hint(hint, B, p), _p(work), B, nx, ny, dx, dy, beta, tol, int(max_sweeps), _stream())
     return info
 
@@ -151,7 +176,7 @@ def fd_sor_redblack_(p, C, dx, dy, beta, tol, max_sweeps):
     suf, (B, nx, ny) = _chk(p, C)
     info = torch.empty(B, 2, dtype=p.dtype, device=p.device)
     nbytes = _lib.lib().nns_fd_sor_redblack_workspace(B, nx, ny, p.element_size(), int(max_sweeps))     # 0: the grids fit LDS
-    work = torch.empty(nbytes // p.element_size(), dtype=p.dtype, device=p.device) if nbytes else None
+    work = _workspace(nbytes, p) if nbytes else None
     _call('nns_fd_sor_redblack', suf, _p(p), _p(C), _p(info), _p(work) if nbytes else None, B, nx, ny, dx, dy, beta, tol,
           int(max_sweeps), _stream())
     return info
@@ -162,10 +187,7 @@ MG_CHUNK = 2              # cycles per later chunk (the f64 solves of a time loo
 
 
 def fd_poisson_mg_workspace(B, nx, ny, elem_size):
-    import ctypes
-    n = ctypes.c_size_t(0)
-    check(_lib.lib().nns_fd_poisson_mg_workspace(int(B), int(nx), int(ny), int(elem_size), ctypes.byref(n)), 'nns_fd_poisson_mg_workspace')
-    return n.value
+    return _query_bytes('nns_fd_poisson_mg_workspace', int(B), int(nx), int(ny), int(elem_size))
 
 
 def fd_poisson_mg_(p, C, dx, dy, tol=1e-6, max_cycles=30, hint=None):
@@ -200,8 +222,7 @@ def fd_sor_redblack_halfsweep_(p, C, err, gi0, colour, dx, dy, beta):
     err: a zeroed one-element tensor of p's dtype; afterwards err.max-accumulates max|p_new - p_old| (bit pattern)."""
     if p.dim() != 2 or p.shape != C.shape or not p.is_cuda or not p.is_contiguous() or not C.is_contiguous():
         raise ValueError("fd_sor_redblack_halfsweep_: p, C must be contiguous 2-D device tensors of one shape")
-    suf = '_f32' if p.dtype == torch.float32 else '_f64'
-    _call('nns_fd_sor_redblack_halfsweep', suf, _p(p), _p(C), _p(err), p.shape[0], p.shape[1], int(gi0), int(colour), dx, dy, beta, _stream())
+    _call('nns_fd_sor_redblack_halfsweep', _suffix(p), _p(p), _p(C), _p(err), p.shape[0], p.shape[1], int(gi0), int(colour), dx, dy, beta, _stream())
     return err
 
 
@@ -210,8 +231,7 @@ def fd_sor_redblack_halfsweep_gated_(p, C, err, prev_err, tol, gi0, colour, dx, 
     one-element device tensor prev_err (the previous sweep's error, already max-reduced over the ranks) is > tol."""
     if p.dim() != 2 or p.shape != C.shape or not p.is_cuda or not p.is_contiguous() or not C.is_contiguous():
         raise ValueError("fd_sor_redblack_halfsweep_gated_: p, C must be contiguous 2-D device tensors of one shape")
-    suf = '_f32' if p.dtype == torch.float32 else '_f64'
-    _call('nns_fd_sor_redblack_halfsweep_gated', suf, _p(p), _p(C), _p(err), _p(prev_err), float(tol), p.shape[0], p.shape[1], int(gi0), int(colour),
+    _call('nns_fd_sor_redblack_halfsweep_gated', _suffix(p), _p(p), _p(C), _p(err), _p(prev_err), float(tol), p.shape[0], p.shape[1], int(gi0), int(colour),
           dx, dy, beta, _stream())
     return err
 
@@ -237,8 +257,7 @@ def fd_step_explicit(un, vn, un1, vn1, p, u_bcl, v_bcl, p_bcl, dt, dx, dy, rho, 
     if p_copy is not None:
         _chk(un, p_copy)
     info = torch.empty(B, 2, dtype=p.dtype, device=p.device)
-    nbytes = _lib.lib().nns_fd_sor_workspace(B, nx, ny, p.element_size())
-    work = torch.empty(nbytes // p.element_size(), dtype=p.dtype, device=p.device)
+    work = _workspace(_lib.lib().nns_fd_sor_workspace(B, nx, ny, p.element_size()), p)
     _call('nns_fd_step_explicit', suf, _p(un), _p(vn), _p(un1), _p(vn1), _p(p), u_bcl, v_bcl, p_bcl, _p(u), _p(v), _p(p_copy) if p_copy is not None else None,
           _p(info), _sor_hint(hint, B, p), _p(work), B, nx, ny, dt, dx, dy, rho, nu, beta, tol, int(max_sweeps), int(bool(corrected)), _stream())
     return u, v, info
@@ -257,8 +276,7 @@ def coarsen(u, v, p, agg_x, agg_y, jfill=None):
     if agg_x < 1 or agg_y < 1 or nx % agg_x or ny % agg_y:
         raise ValueError("coarsen: nx=%d, ny=%d must be multiples of agg_x=%d, agg_y=%d" % (nx, ny, agg_x, agg_y))
     out = [torch.empty(T, nx // agg_x, ny // agg_y, dtype=u.dtype, device=u.device) for _ in range(3)]
-    suf = '_f32' if u.dtype == torch.float32 else '_f64'
-    _call('nns_coarsen', suf, _p(u), _p(v), _p(p), _p(out[0]), _p(out[1]), _p(out[2]), T, nx, ny, int(agg_x), int(agg_y),
+    _call('nns_coarsen', _suffix(u), _p(u), _p(v), _p(p), _p(out[0]), _p(out[1]), _p(out[2]), T, nx, ny, int(agg_x), int(agg_y),
           ny // agg_y if jfill is None else int(jfill), _stream())
     return tuple(out)
 
@@ -299,9 +317,7 @@ def fd_residual_halo(u, v, p, u_prev, v_prev, halo_top, halo_bot, dt, dx, dy, rh
     """fd_residual on local rows `rows` = (begin, end) of a row slab [B, nloc, ny] whose rows -1 / nloc are the
     [3, B, ny] messages halo_top / halo_bot (nns_fd_residual_halo_*)."""
     suf, (B, nx, ny) = _chk(u, v, p, u_prev, v_prev)
-    for h in (halo_top, halo_bot):
-        if not (h.is_cuda and h.is_contiguous() and h.dtype == u.dtype and tuple(h.shape) == (3, B, ny)):
-            raise ValueError("fd_residual_halo: halo messages must be contiguous [3, %d, %d] device tensors of the fields' dtype" % (B, ny))
+    _halo_msgs('fd_residual_halo', halo_top, halo_bot, u, B, ny)
     ru, rv, rd = out if out is not None else (torch.empty_like(u), torch.empty_like(u), torch.empty_like(u))
     r0, r1 = rows if rows is not None else (0, nx)
     _call('nns_fd_residual_halo', suf, _p(u), _p(v), _p(p), _p(u_prev), _p(v_prev), _p(halo_top), _p(halo_bot), _p(ru), _p(rv), _p(rd),
@@ -399,10 +415,7 @@ def residual_both_rowpass_halo(u, v, p, u_prev, v_prev, halo_top, halo_bot, sp_p
     suf, (B, nx, ny) = _chk(u, v, p, u_prev, v_prev, *sp_partials)
     if suf != '_f32':
         raise TypeError("residual_both_rowpass_halo: float32 fields")
-    Bh = halo_top.shape[1] if halo_top.dim() == 3 else -1
-    for h in (halo_top, halo_bot):
-        if not (h.is_cuda and h.is_contiguous() and h.dtype == u.dtype and tuple(h.shape) == (3, Bh, ny) and 0 <= halo_grid0 and halo_grid0 + B <= Bh):
-            raise ValueError("residual_both_rowpass_halo: halo messages must be contiguous [3, >= %d, %d] float32 device tensors" % (halo_grid0 + B, ny))
+    Bh = _halo_msgs('residual_both_rowpass_halo', halo_top, halo_bot, u, B, ny, halo_grid0)
     fo = out_fd if out_fd is not None else tuple(torch.empty_like(u) for _ in range(3))
     so = sp_partials
     off = halo_grid0 * ny * 4
@@ -429,10 +442,7 @@ def residual_both_rowpass_halo_seg(u, v, p, u_prev, v_prev, halo_top, halo_bot, 
     suf, (B, nx, ny) = _chk(u, v, p, u_prev, v_prev)
     if suf != '_f32':
         raise TypeError("residual_both_rowpass_halo_seg: float32 fields")
-    Bh = halo_top.shape[1] if halo_top.dim() == 3 else -1
-    for h in (halo_top, halo_bot):
-        if not (h.is_cuda and h.is_contiguous() and h.dtype == u.dtype and tuple(h.shape) == (3, Bh, ny) and 0 <= halo_grid0 and halo_grid0 + B <= Bh):
-            raise ValueError("residual_both_rowpass_halo_seg: halo messages must be contiguous [3, >= %d, %d] float32 device tensors" % (halo_grid0 + B, ny))
+    Bh = _halo_msgs('residual_both_rowpass_halo_seg', halo_top, halo_bot, u, B, ny, halo_grid0)
     parts, seg_cols, seg_stride = _seg_parts(got, B, nx, ny, 'residual_both_rowpass_halo_seg')
     fo = out_fd if out_fd is not None else tuple(torch.empty_like(u) for _ in range(3))
     so = out_spec if out_spec is not None else tuple(torch.empty_like(u) for _ in range(3))
@@ -467,7 +477,6 @@ def spec_resolve_precise(precise, nu, nx, Lx, ny, Ly):
 
 # ----------------------------------------------------------------------------- slab message packing (nns/slab.py)
 def _ptr_array(ts):
-    import ctypes
     return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
 
@@ -706,17 +715,7 @@ def cheb_embed(sol, x0, xN, y0, yN):
 def pixel_mlp_fwd(x, weights, biases, bf16=False):
     """x [mb, C_in, nx, ny] (or [mb, C_in, P]); weights: list of [C_out, C_in] (or Conv2d [C_out, C_in, 1, 1]) tensors;
     biases: list of [C_out].  ReLU between layers, none after the last."""
-    import ctypes
-    _f32(x)
-    mb, cin = x.shape[0], x.shape[1]
-    P = x[0, 0].numel()
-    ws = [w.reshape(w.shape[0], w.shape[1]) for w in weights]
-    widths = [cin] + [w.shape[0] for w in ws]
-    for i, w in enumerate(ws):
-        if w.shape[1] != widths[i]:
-            raise ValueError("pixel_mlp_fwd: layer %d expects %d input channels, got %d" % (i, w.shape[1], widths[i]))
-    wp = torch.cat([w.reshape(-1) for w in ws]).to(torch.float32).contiguous()
-    bp = torch.cat([b.reshape(-1) for b in biases]).to(torch.float32).contiguous()
+    mb, P, ws, widths, wp, bp = _pixel_mlp_pack(x, weights, biases, 'pixel_mlp_fwd')
     y = torch.empty((mb, widths[-1]) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
     arr = (ctypes.c_int * len(widths))(*widths)
     check(_lib.lib().nns_pixel_mlp_fwd_f32(_p(x), _p(wp), _p(bp), _p(y), mb, P, arr, len(ws), int(bool(bf16)), _stream()), 'nns_pixel_mlp_fwd_f32')
@@ -740,20 +739,18 @@ def _pixel_mlp_pack(x, weights, biases, what):
 def pixel_mlp_bwd(x, gy, weights, biases, bf16=True):
     """Backward of pixel_mlp_fwd: returns (gx like x, [gW_l like weights[l]], [gb_l like biases[l]]).
     bf16=False (float32 operands) supports widths <= 32."""
-    import ctypes
     mb, P, ws, widths, wp, bp = _pixel_mlp_pack(x, weights, biases, 'pixel_mlp_bwd')
     _f32(gy)
     if tuple(gy.shape) != (mb, widths[-1]) + tuple(x.shape[2:]):
         raise ValueError("pixel_mlp_bwd: gy has shape %s, expected %s" % (tuple(gy.shape), (mb, widths[-1]) + tuple(x.shape[2:])))
     arr = (ctypes.c_int * len(widths))(*widths)
-    nbytes = ctypes.c_size_t(0)
-    check(_lib.lib().nns_pixel_mlp_bwd_workspace(arr, len(ws), ctypes.byref(nbytes)), 'nns_pixel_mlp_bwd_workspace')
-    work = torch.empty(max(nbytes.value // 4, 1), dtype=torch.float32, device=x.device)
+    nbytes = _query_bytes('nns_pixel_mlp_bwd_workspace', arr, len(ws))
+    work = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=x.device)
     gx = torch.empty_like(x)
     gW = torch.empty_like(wp)
     gB = torch.empty_like(bp)
     check(_lib.lib().nns_pixel_mlp_bwd_f32(_p(x), _p(gy), _p(wp), _p(bp), _p(gx), _p(gW), _p(gB), mb, P, arr, len(ws), int(bool(bf16)),
-                                           _p(work), nbytes.value, _stream()), 'nns_pixel_mlp_bwd_f32')
+                                           _p(work), nbytes, _stream()), 'nns_pixel_mlp_bwd_f32')
     gws, gbs, wo, bo = [], [], 0, 0
     for w, b in zip(weights, biases):
         gws.append(gW[wo:wo + w.numel()].reshape(w.shape)); wo += w.numel()
@@ -864,23 +861,26 @@ def spec_ns_kept_y(ny):
 
 def spec_ns_workspace(B, nx, ny):
     """Bytes of the workspace nns_spec_ns_init / step / fields need for B grids of nx x ny."""
-    import ctypes
-    n = ctypes.c_size_t(0)
-    check(_lib.lib().nns_spec_ns_workspace(int(B), int(nx), int(ny), ctypes.byref(n)), 'nns_spec_ns_workspace')
-    return n.value
+    return _query_bytes('nns_spec_ns_workspace', int(B), int(nx), int(ny))
 
 
-def _spec_ns_state(what, mean, work):
-    _f32(what, mean)
+def _spec_ns_state(who, what, mean, work, ny):
+    """(B, my1, nx) of the checked solver state.  mean and work None (spec_ns_diag): the spectrum alone, under the caller's name; ny None
+    (spec_ns_init, which compares the whole shape with its fields): no check of the kept y-wavenumbers."""
+    alone = mean is None
+    _f32(*((what,) if alone else (what, mean)))
     if what.dim() != 4 or what.shape[3] != 2:
-        raise ValueError("spec_ns: what must be float32 [B, my1, nx, 2], got %s" % (tuple(what.shape),))
+        raise ValueError("%s: what must be float32 [B, my1, nx, 2], got %s" % (who if alone else 'spec_ns', tuple(what.shape)))
     B, my1, nx = what.shape[0], what.shape[1], what.shape[2]
-    if tuple(mean.shape) != (B, 2):
-        raise ValueError("spec_ns: mean must be [B, 2], got %s" % (tuple(mean.shape),))
-    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
-        raise TypeError("spec_ns: work must be a contiguous uint8 device tensor")
-    if what.device != mean.device or what.device != work.device:
-        raise ValueError("spec_ns: state tensors on different devices")
+    if not alone:
+        if tuple(mean.shape) != (B, 2):
+            raise ValueError("spec_ns: mean must be [B, 2], got %s" % (tuple(mean.shape),))
+        if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
+            raise TypeError("spec_ns: work must be a contiguous uint8 device tensor")
+        if what.device != mean.device or what.device != work.device:
+            raise ValueError("spec_ns: state tensors on different devices")
+    if ny is not None and my1 != spec_ns_kept_y(ny):
+        raise ValueError("%s: what has %d kept y-wavenumbers, ny = %d needs %d" % (who, my1, ny, spec_ns_kept_y(ny)))
     return B, my1, nx
 
 
@@ -889,7 +889,7 @@ def spec_ns_init(u, v, what, mean, work, Lx, Ly):
     mean = the grid means [B, 2].  Divergence-free, band-limited projection of the input."""
     _f32(u, v)
     suf, (B, nx, ny) = _chk(u, v)
-    Bw, my1, nxw = _spec_ns_state(what, mean, work)
+    Bw, my1, nxw = _spec_ns_state('spec_ns_init', what, mean, work, None)
     if (Bw, my1, nxw) != (B, spec_ns_kept_y(ny), nx) or u.device != what.device:
         raise ValueError("spec_ns_init: state [%d, %d, %d] does not match fields [%d, %d, %d]" % (Bw, my1, nxw, B, nx, ny))
     check(_lib.lib().nns_spec_ns_init_f32(_p(u), _p(v), _p(what), _p(mean), _p(work), work.numel(), B, nx, ny, float(Lx), float(Ly),
@@ -899,9 +899,7 @@ def spec_ns_init(u, v, what, mean, work, Lx, Ly):
 
 def spec_ns_step_(what, mean, work, ny, Lx, Ly, dt, nu, nsteps=1):
     """nsteps Lawson-RK4 steps on what in place (no allocation, no host synchronisation: capturable)."""
-    B, my1, nx = _spec_ns_state(what, mean, work)
-    if my1 != spec_ns_kept_y(ny):
-        raise ValueError("spec_ns_step_: what has %d kept y-wavenumbers, ny = %d needs %d" % (my1, ny, spec_ns_kept_y(ny)))
+    B, my1, nx = _spec_ns_state('spec_ns_step_', what, mean, work, ny)
     check(_lib.lib().nns_spec_ns_step_f32(_p(what), _p(mean), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt),
                                           float(nu), int(nsteps), _stream()), 'nns_spec_ns_step_f32')
     return what
@@ -909,9 +907,7 @@ def spec_ns_step_(what, mean, work, ny, Lx, Ly, dt, nu, nsteps=1):
 
 def spec_ns_fields(what, mean, work, ny, Lx, Ly, rho, out=None):
     """(u, v, p) float32 [B, nx, ny] of the state; out: three preallocated contiguous tensors of that shape."""
-    B, my1, nx = _spec_ns_state(what, mean, work)
-    if my1 != spec_ns_kept_y(ny):
-        raise ValueError("spec_ns_fields: what has %d kept y-wavenumbers, ny = %d needs %d" % (my1, ny, spec_ns_kept_y(ny)))
+    B, my1, nx = _spec_ns_state('spec_ns_fields', what, mean, work, ny)
     if out is None:
         out = tuple(torch.empty((B, nx, int(ny)), dtype=torch.float32, device=what.device) for _ in range(3))
     else:
@@ -941,9 +937,7 @@ def _spec_ns_force(who, ghat, what):
 def spec_ns_step_forced_(what, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, nsteps=1):
     """nsteps Lawson-RK4 steps with the force spectrum ghat ([1, my1, nx, 2]: shared by the batch, [B, my1, nx, 2]: one per grid, None: no
     force) and the linear drag `drag` on what in place (no allocation, no host synchronisation: capturable)."""
-    B, my1, nx = _spec_ns_state(what, mean, work)
-    if my1 != spec_ns_kept_y(ny):
-        raise ValueError("spec_ns_step_forced_: what has %d kept y-wavenumbers, ny = %d needs %d" % (my1, ny, spec_ns_kept_y(ny)))
+    B, my1, nx = _spec_ns_state('spec_ns_step_forced_', what, mean, work, ny)
     gbatch = _spec_ns_force('spec_ns_step_forced_', ghat, what)
     check(_lib.lib().nns_spec_ns_step_forced_f32(_p(what), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(work), work.numel(), B, nx,
                                                  int(ny), float(Lx), float(Ly), float(dt), float(nu), float(drag), int(nsteps), _stream()),
@@ -953,12 +947,7 @@ def spec_ns_step_forced_(what, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, nstep
 
 def spec_ns_diag(what, ghat, ny, Lx, Ly, out=None):
     """float64 [B, 3]: fluctuation energy, enstrophy and power input <f_s . u> (0 with ghat None) of every grid of the state."""
-    _f32(what)
-    if what.dim() != 4 or what.shape[3] != 2:
-        raise ValueError("spec_ns_diag: what must be float32 [B, my1, nx, 2], got %s" % (tuple(what.shape),))
-    B, my1, nx = what.shape[0], what.shape[1], what.shape[2]
-    if my1 != spec_ns_kept_y(ny):
-        raise ValueError("spec_ns_diag: what has %d kept y-wavenumbers, ny = %d needs %d" % (my1, ny, spec_ns_kept_y(ny)))
+    B, my1, nx = _spec_ns_state('spec_ns_diag', what, None, None, ny)
     gbatch = _spec_ns_force('spec_ns_diag', ghat, what)
     if out is None:
         out = torch.empty((B, 3), dtype=torch.float64, device=what.device)
