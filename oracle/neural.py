@@ -119,13 +119,17 @@ def pixel_mlp_backward(weights, biases, grid, gy, bf16=False):
     return d, gWs, gbs
 
 
-def pixel_mlp(weights, biases, grid):
+def pixel_mlp(weights, biases, grid, bf16=False):
     """BasisFunc (:100-119) generalised to any depth: 1x1 convs == per-pixel linears with ReLU
-    between layers, none after the last.  weights[l] [C_out, C_in]; grid [mb, C_in0, nx, ny]."""
+    between layers, none after the last.  weights[l] [C_out, C_in]; grid [mb, C_in0, nx, ny].
+    bf16=True emulates the forward kernel's operand rounding (the forward half of pixel_mlp_backward(bf16=True)):
+    the weights and every layer's input to bfloat16, biases unrounded, accumulation exact in the caller's dtype,
+    the last layer's output not rounded."""
+    rnd = _bf16_round if bf16 else (lambda t: t)
     h = grid
     L = len(weights)
     for l, (W, b) in enumerate(zip(weights, biases)):
-        h = torch.einsum('oc,bcxy->boxy', W, h) + b[None, :, None, None]
+        h = torch.einsum('oc,bcxy->boxy', rnd(W), rnd(h)) + b[None, :, None, None]
         if l < L - 1:
             h = torch.relu(h)
     return h

@@ -108,3 +108,109 @@ def test_pixel_mlp_backward_matches_autograd():
     for l in range(3):
         assert torch.allclose(gWs[l], Ws[l].grad, rtol=1e-12, atol=1e-12)
         assert torch.allclose(gbs[l], bs[l].grad, rtol=1e-12, atol=1e-12)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# pixel_mlp(bf16=True): the forward kernels' operand rounding emulated, and the exact input families of tests/pm_cases.py
+# (what tests/test_gpu_pixel_mlp_forward.py holds the HIP kernels to), on the reference alone.
+def _pixel_mlp_unrounded(weights, biases, grid):
+    """pixel_mlp as it was before it learnt to round."""
+    h = grid
+    for l, (W, b) in enumerate(zip(weights, biases)):
+        h = torch.einsum('oc,bcxy->boxy', W, h) + b[None, :, None, None]
+        if l < len(weights) - 1:
+            h = torch.relu(h)
+    return h
+
+
+def test_pixel_mlp_default_is_unrounded():
+    import pm_cases as PC
+    for dtype in (torch.float32, torch.float64):
+        for dims, shape in PC.RANDOM_STACKS[:3]:
+            Ws, bs, x = PC.random_stack(dims, (1, 9, 7), 4)
+            args = [w.to(dtype) for w in Ws], [b.to(dtype) for b in bs], x.to(dtype)
+            assert torch.equal(ON.pixel_mlp(*args), _pixel_mlp_unrounded(*args))
+            assert torch.equal(ON.pixel_mlp(*args, bf16=False), _pixel_mlp_unrounded(*args))
+
+
+def test_pixel_mlp_bf16_rounds_what_the_backward_oracle_rounds(monkeypatch):
+    """The layer inputs pixel_mlp(bf16=True) multiplies are the `ins` pixel_mlp_backward(bf16=True) builds, and with gy = 1 on one output its
+    bias gradient of the last layer confirms that both see the same forward."""
+    import pm_cases as PC
+    dims, shape = [5, 64, 33, 7], (2, 6, 5)
+    Ws, bs, x = PC.random_stack(dims, shape, 2)
+    Ws, bs, x = [w.double() for w in Ws], [b.double() for b in bs], x.double()
+    seen = {}
+    real = torch.einsum
+
+    def spy(eq, a, b):
+        seen.setdefault(eq, []).append((a, b))
+        return real(eq, a, b)
+    monkeypatch.setattr(torch, 'einsum', spy)
+    y = ON.pixel_mlp(Ws, bs, x, bf16=True)
+    fwd = seen.pop('oc,bcxy->boxy')
+    seen.clear()
+    ON.pixel_mlp_backward(Ws, bs, x, torch.ones_like(y), bf16=True)
+    bwd = seen['oc,bcxy->boxy']
+    monkeypatch.undo()
+    assert len(fwd) == len(bwd) == 3
+    for (Wf, hf), (Wb, hb) in zip(fwd, bwd):
+        assert torch.equal(Wf, Wb) and torch.equal(hf, hb)
+        assert torch.equal(hf, hf.float().bfloat16().double()) and torch.equal(Wf, Wf.float().bfloat16().double())     # they ARE bf16 values
+    assert not torch.equal(y, y.float().bfloat16().double())                                # the last layer's output is not rounded
+    assert not torch.equal(y, ON.pixel_mlp(Ws, bs, x))
+
+
+def test_pixel_mlp_exact_families_hold_their_conditions():
+    """Every exact case the GPU test runs: the operand bounds, the liveness conditions and the routing rules hold on the float64 oracle
+    (pm_cases.build asserts them), and rounding the operands to bf16 changes nothing -- bitwise."""
+    import pm_cases as PC
+    done = set()
+    for cid, fam, dims, bf16, mb, P in PC.exact_cases():
+        if (fam, tuple(dims), mb, P) in done or mb * P > 20000:
+            continue
+        done.add((fam, tuple(dims), mb, P))
+        Ws, bs, x, ref = PC.build(fam, tuple(dims), mb, P)
+        args = [w.double() for w in Ws], [b.double() for b in bs], x.double()
+        assert torch.equal(ON.pixel_mlp(*args, bf16=True), ref), cid
+        assert torch.equal(ON.pixel_mlp(*[[t.float() for t in a] if isinstance(a, list) else a.float() for a in args], bf16=True).double(), ref), cid
+    # every stack on 4096 pixels, where the liveness conditions are asserted whatever the case's own pixel count
+    for dims in sorted(set(tuple(d) for _, _, d, _, _, _ in PC.exact_cases())):
+        for fam in ('sparse', 'routing'):
+            Ws, bs, x, ref = PC.build(fam, dims, 1, 4096)
+            assert torch.equal(ON.pixel_mlp([w.double() for w in Ws], [b.double() for b in bs], x.double(), bf16=True), ref), (fam, dims)
+
+
+def test_pixel_mlp_exact_cases_reach_every_path():
+    """Each dispatch path at a pixel count that ends mid-tile, on a tile boundary and on a group boundary (64 pixels for the uniform
+    kernels, 128 for the four-tile kernel, the 32-pixel tile itself for the float32 kernel), all spanning at least two images."""
+    import pm_cases as PC
+    ends = {p: set() for p in 'ABCDE'}
+    for cid, fam, dims, bf16, mb, P in PC.exact_cases():
+        path = PC.path_of(dims, bf16)
+        assert cid.startswith(path + '-') and mb >= 2
+        n, grp = mb * P, {'C': 128, 'E': 32}.get(path, 64)
+        ends[path].add('mid-tile' if n % 32 else ('group' if n % grp == 0 else 'tile'))
+        if not bf16:
+            assert PC.f32_lds_bytes(dims) <= PC.F32_LDS_LIMIT            # (eight layers of width 64 need 130 KB: every listed stack fits)
+    for p in 'ABCD':
+        assert ends[p] == {'mid-tile', 'tile', 'group'}, (p, ends[p])
+    assert ends['E'] == {'mid-tile', 'group'}
+    assert PC.f32_lds_bytes([64] * 9) == 8 * (4 * 16 * 64 * 4 + 256)
+
+
+def test_pixel_mlp_bf16_rounding_is_visible_on_random_stacks():
+    """On the random float stacks of the GPU test the rounded and the unrounded oracle differ by 5e-4 .. 2e-2 rel-L2 (measured 6.7e-4 ..
+    2.3e-3 on these seeds): above RANDOM_BOUND, so a kernel that does not round cannot pass there.  And the bound itself: ten times the
+    largest rel-L2 between the emulation accumulated in float32 and in float64 (re-measured here on the GPU test's seeds; the docstring of
+    tests/test_gpu_pixel_mlp_forward.py has the ten-seed figures)."""
+    import pm_cases as PC
+    assert PC.RANDOM_BOUND <= 1e-3
+    for dims, shape in PC.RANDOM_STACKS:
+        for seed in PC.RANDOM_SEEDS:
+            Ws, bs, x = PC.random_stack(dims, shape, seed)
+            e64 = PC.emulated(Ws, bs, x, torch.float64).numpy()
+            un = ON.pixel_mlp([w.double() for w in Ws], [b.double() for b in bs], x.double()).numpy()
+            assert 5e-4 < rel_l2(e64, un) < 2e-2, (dims, seed, rel_l2(e64, un))
+            assert rel_l2(e64, un) > 2 * PC.RANDOM_BOUND
+            assert 10 * rel_l2(PC.emulated(Ws, bs, x, torch.float32).numpy(), e64) <= PC.RANDOM_BOUND, (dims, seed)
