@@ -36,6 +36,7 @@ enum { METHOD_EULER = 0, METHOD_RK2 = 1, METHOD_RK4 = 2 };
 // ELU(alpha = 1): z for z > 0, expm1(z) otherwise (ODEFunc, spectral_ode.py:14-34).  Round 3: branch-free, ~14 instructions instead of the
 // ~40 of expm1f (on the ODE kernels' critical path once per hidden unit and evaluation): exp(z) - 1 by v_exp_f32 where z <= -0.35 (the
 // difference is >= 0.3, no cancellation: <= 5e-7 relative), the Taylor polynomial to z^8 above that (truncation 2e-10 at z = -0.35).
+// Read out bit for bit by tests/test_gpu_ode_mlp.py on 2048 values of z in [-110, 2]: 1.25e-7 relative at worst (z = -0.3596), asserted <= 1e-6.
 __device__ __forceinline__ float elu1(float z) {
     const float t = __builtin_amdgcn_exp2f(z * 1.44269504088896340736f) - 1.0f;
     float p = 2.48015873015873016e-5f;                       // 1/8!

@@ -28,27 +28,31 @@ def odefunc(mlp, y):
     return h @ W2.t() + b2
 
 
+def step(mlp, y, dt, method='RK4'):
+    """One step of size dt, y [mb, K] -> y' [mb, K].  scheme.py:21-42."""
+    f = lambda y: odefunc(mlp, y)
+    if method == 'Euler':
+        return y + dt * f(y)
+    if method == 'RK2':
+        k1 = dt * f(y)
+        k2 = dt * f(y + 1.0 / 2.0 * k1)
+        return y + k2
+    if method == 'RK4':
+        k1 = dt * f(y)
+        k2 = dt * f(y + 1.0 / 2.0 * k1)
+        k3 = dt * f(y + 1.0 / 2.0 * k2)
+        k4 = dt * f(y + k3)
+        return y + 1.0 / 6.0 * k1 + 1.0 / 3.0 * k2 + 1.0 / 3.0 * k3 + 1.0 / 6.0 * k4
+    raise ValueError(method)
+
+
 def integrate(mlp, z0, Nt, method='RK4'):
     """Returns [Nt, mb, K].  time_stepper.py:35-45 / scheme.py:21-42."""
     dt = 1. / float(Nt)
-    f = lambda y: odefunc(mlp, y)
     y = z0
     out = []
     for _ in range(Nt):
-        if method == 'Euler':
-            y = y + dt * f(y)
-        elif method == 'RK2':
-            k1 = dt * f(y)
-            k2 = dt * f(y + 1.0 / 2.0 * k1)
-            y = y + k2
-        elif method == 'RK4':
-            k1 = dt * f(y)
-            k2 = dt * f(y + 1.0 / 2.0 * k1)
-            k3 = dt * f(y + 1.0 / 2.0 * k2)
-            k4 = dt * f(y + k3)
-            y = y + 1.0 / 6.0 * k1 + 1.0 / 3.0 * k2 + 1.0 / 3.0 * k3 + 1.0 / 6.0 * k4
-        else:
-            raise ValueError(method)
+        y = step(mlp, y, dt, method)
         out.append(y)
     return torch.stack(out)
 

@@ -214,3 +214,91 @@ def test_pixel_mlp_bf16_rounding_is_visible_on_random_stacks():
             assert 5e-4 < rel_l2(e64, un) < 2e-2, (dims, seed, rel_l2(e64, un))
             assert rel_l2(e64, un) > 2 * PC.RANDOM_BOUND
             assert 10 * rel_l2(PC.emulated(Ws, bs, x, torch.float32).numpy(), e64) <= PC.RANDOM_BOUND, (dims, seed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The fused ODEFunc integrator's cases (tests/ode_cases.py; tests/test_gpu_ode_mlp.py holds the HIP kernels to them), on the reference alone.
+def test_step_is_what_integrate_takes():
+    """integrate is Nt calls of step with dt = 1 / Nt, bitwise; step takes a free dt."""
+    import ode_cases as OC
+    for method in OC.METHODS:
+        mlp, z0, _ = OC.inputs(17, 33, 5)
+        mlp, y = [p.double() for p in mlp], z0.double()
+        traj = ON.integrate(mlp, y, 5, method)
+        for n in range(5):
+            y = ON.step(mlp, y, 1. / 5., method)
+            assert torch.equal(y, traj[n])
+        f = ON.odefunc(mlp, y)
+        assert torch.equal(ON.step(mlp, y, OC.STEP_DT, 'Euler'), y + OC.STEP_DT * f)
+    with pytest.raises(ValueError):
+        ON.step(mlp, y, 0.1, 'RK3')
+
+
+def test_ode_cases_hold_their_conditions():
+    """Every case and scheme of the GPU test: half of the ReLU units live and half of the ELU pre-activations negative at the first stage, and
+    the float32 oracle within 1e-6 of the float64 one on the trajectory and all seven gradients (so that 10 x that is a bound a float32
+    kernel can be held to, and no ReLU kink decides the comparison)."""
+    import ode_cases as OC
+    assert [c[:3] for c in OC.CASES] == [(1, 1, 1), (1, 17, 2), (2, 16, 3), (15, 15, 4), (16, 1, 1), (17, 33, 5), (31, 17, 3), (32, 16, 2), (32, 49, 4),
+                                         (30, 5, 60)]
+    for K, mb, Nt in OC.SHAPES:
+        live, neg = OC.first_stage_shares(K, mb, Nt)
+        print('ode case %s: live ReLU %.3f, negative ELU %.3f' % (OC.case_id(K, mb, Nt), live, neg))
+        assert 0.3 <= live <= 0.7 and 0.3 <= neg <= 0.7, (K, mb, Nt, live, neg)
+        (W0, b0, W1, b1, W2, b2), z0, w = OC.inputs(K, mb, Nt)
+        assert W0.shape == (128, K) and W1.shape == (128, 128) and W2.shape == (K, 128) and z0.shape == (mb, K) and w.shape == (Nt, mb, K)
+        for method in OC.METHODS:
+            e = OC.e32(K, mb, Nt, method)
+            print('ode case %s: e32 %.2e, bound %.2e' % (OC.case_id(K, mb, Nt, method), e, OC.bound(K, mb, Nt, method)))
+            assert 0 < e <= OC.E32_LIMIT, (K, mb, Nt, method, e)
+            assert OC.bound(K, mb, Nt, method) == max(10 * e, 2e-6)
+            ref = OC.oracle(K, mb, Nt, method)
+            assert ref['traj'].shape == (Nt, mb, K) and all(np.abs(ref[q]).max() > 0 for q in OC.QUANTITIES)
+    for K, rows, method in OC.STEP_CASES:
+        e = OC.step_e32(K, rows, method)
+        assert 0 < e <= OC.E32_LIMIT, (K, rows, method, e)
+        assert OC.step_bound(K, rows, method) == max(10 * e, 2e-6)
+
+
+def test_ode_bound_rejects_wrong_oracles():
+    """The bound of every case, applied to three deliberately wrong float64 oracles, fails by at least 100 x on every quantity the mutation
+    acts on: RK4 weights 1/6 and 1/3 exchanged, ELU derivative taken as 1 for z < 0, row mb - 1 left out of the parameter gradients."""
+    import ode_cases as OC
+    acted = {m: 0 for m in OC.MUTATIONS}
+    for K, mb, Nt, method in OC.CASE_METHODS:
+        ref = OC.oracle(K, mb, Nt, method)
+        same = OC.mutant(None, K, mb, Nt, method)
+        assert all(np.array_equal(same[q], ref[q]) for q in OC.QUANTITIES)          # the mutants' integrator, unmutated, IS the oracle
+        for mutation in OC.MUTATIONS:
+            if not OC.mutation_acts(mutation, K, mb, Nt, method):
+                continue
+            acted[mutation] += 1
+            bad = OC.mutant(mutation, K, mb, Nt, method)
+            hit = OC.mutation_quantities(mutation, Nt, method)
+            for q in OC.QUANTITIES:
+                err = rel_l2(bad[q], ref[q])
+                if q in hit:
+                    assert err >= 100 * OC.bound(K, mb, Nt, method), (mutation, K, mb, Nt, method, q, err)
+                elif mutation != 'rk4_weights':
+                    assert err < 1e-14, (mutation, K, mb, Nt, method, q, err)        # and nothing else moves (float64 rounding: the batch is split)
+    assert acted == {'rk4_weights': 10, 'elu_grad': 30, 'drop_row': 24}
+
+
+def test_elu_points_cover_what_elu1_branches_on():
+    import ode_cases as OC
+    z = OC.elu_points().numpy().ravel()
+    assert z.dtype == np.float32 and len(z) == 2048 and z.min() == -110 and z.max() == 2
+    split = np.float32(OC.ELU_SPLIT)
+    for edge in (np.float32(0), split):
+        for side in (-np.inf, np.inf):
+            assert np.nextafter(edge, np.float32(side)) in z
+        assert edge in z
+    assert ((z > split - 0.01) & (z < split + 0.01)).sum() > 500 and (np.abs(z) < 0.005).sum() > 400
+    assert (z <= OC.ELU_EXACT_MINUS_ONE).sum() > 100 and ((z < -17.4) & (z > OC.ELU_EXACT_MINUS_ONE)).sum() >= 1
+    assert np.all(np.float32(OC.elu_expected(z[z <= OC.ELU_EXACT_MINUS_ONE])) == -1)
+    assert (z > 0).sum() > 300 and np.signbit(z[z == 0]).any() and not np.signbit(z[z == 0]).all()
+    # a float32 expm1 is within the read-out's bound of the float64 one; elu taken as z everywhere is not
+    rel, neg = OC.elu_errors(z, np.where(z > 0, z, np.expm1(z)).astype(np.float32))
+    assert rel.max() < 2.4e-7                       # two float32 roundings
+    lin = np.where(z > OC.ELU_EXACT_MINUS_ONE, np.where(z > -1e-3, z, np.expm1(z.astype(np.float64))), -1).astype(np.float32)      # first order near 0
+    assert OC.elu_errors(z, lin)[0].max() > 100 * OC.ELU_REL
