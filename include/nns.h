@@ -439,6 +439,34 @@ int nns_spec_ns_step_forced_f32(float* what, const float* mean, const float* gha
  * order (no atomics): they repeat bitwise and a grid's numbers do not depend on its batch neighbours.  No workspace; one launch. */
 int nns_spec_ns_diag_f32(const float* what, const float* ghat, int gbatch, double* out, int batch, int nx, int ny, double Lx, double Ly,
                          void* stream);
+/* A passive scalar theta (temperature, dye), one per grid, advected by the flow and not acting on it (restatement:
+ * tests/pspec_scalar_oracle.py).  The total field is G . x + theta with a uniform mean gradient G = (gx, gy); theta is its periodic part:
+ *     theta_t + u theta_x + v theta_y = kappa lap theta - (gx u + gy v)
+ * State: that = M_theta rfft2(theta) in the layout of what, float32 [batch][my1][nx][2], where M_theta is the 2/3 mask with the (0, 0) mode
+ * KEPT (the mean of theta is part of the state).  (w^, theta^) is one system under the same Lawson RK4: L_theta = -kappa |k|^2 (the drag does
+ * not act on the scalar), N_theta = -M_theta rfft2(u (theta_x + gx) + v (theta_y + gy)) with every stage's own velocity, means included, so
+ * that d<theta>/dt = -G . (U0, V0) and d/dt 1/2 <theta'^2> = -G . <u theta'> - kappa <|grad theta|^2>.  w^ evolves bitwise as without the scalar.
+ * The scalar calls take a workspace of nns_spec_ns_scalar_workspace bytes (>= nns_spec_ns_workspace; it serves every nns_spec_ns_* call). */
+int nns_spec_ns_scalar_workspace(int batch, int nx, int ny, size_t* bytes);
+/* that = M_theta rfft2(theta), theta float32 [batch][nx][ny]: keeps the band-limited part of theta, its mean included. */
+int nns_spec_ns_scalar_init_f32(const float* theta, float* that, void* work, size_t work_bytes, int batch, int nx, int ny, void* stream);
+/* theta [batch][nx][ny] = irfft2 of the state. */
+int nns_spec_ns_scalar_field_f32(const float* that, float* theta, void* work, size_t work_bytes, int batch, int nx, int ny, void* stream);
+/* nsteps steps of (what, that) in place.  ghat, gbatch, drag as in nns_spec_ns_step_forced_f32 (ghat == NULL, gbatch == 0, drag == 0: the
+ * unforced flow); kappa >= 0 and finite, gx and gy finite, else NNS_ERR_INVALID_ARG; NNS_ERR_WORKSPACE for work_bytes below
+ * nns_spec_ns_scalar_workspace; otherwise the errors of nns_spec_ns_step_forced_f32.  The scalar rides in the flow's launches: 8 per step
+ * plus one per call, no allocation, no host synchronisation (capturable). */
+int nns_spec_ns_step_scalar_f32(float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work, size_t work_bytes,
+                                int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa, double gx,
+                                double gy, int nsteps, void* stream);
+/* out [batch][4] float64 (device) = per grid, by Parseval over the stored half spectrum without its (0, 0) mode (wt and normalisation of
+ * nns_spec_ns_diag_f32; u^ = i ky psi^, v^ = -i kx psi^ from what):
+ *     variance    = 1/2 <theta'^2>            = 1/2 sum wt |theta^|^2
+ *     dissipation = kappa <|grad theta|^2>    = kappa sum wt |k|^2 |theta^|^2
+ *     flux_x      = <u theta'>                = sum wt Re(u^ conj theta^),      flux_y = <v theta'> likewise
+ * so that d variance / dt = -(gx flux_x + gy flux_y) - dissipation.  float64 sums in a fixed order (no atomics); no workspace; one launch. */
+int nns_spec_ns_scalar_diag_f32(const float* what, const float* that, double* out, int batch, int nx, int ny, double Lx, double Ly,
+                                double kappa, void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

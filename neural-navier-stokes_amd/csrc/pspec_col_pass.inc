@@ -1,0 +1,113 @@
+// One field's pass through a column tile of ps_col_kernel (pspec_kernels.hip), which includes this text once per field with TH in scope:
+// TH = false the vorticity (Ph field 0, W / A, G fields 0..3), TH = true the scalar (Ph field 1, theta^ / A_theta, G fields 4 and 5).  Plain
+// text rather than a function or a lambda: the unscalared kernels then compile to the instructions they had before there was a scalar
+// (a lambda's body is optimised on its own before it is inlined, and came out a few instructions and registers different).
+{
+        const float2* ph = TH ? Ph + a.fstride : Ph;
+        float2* Ws = TH ? Th : W;
+        float2* As = TH ? At : A;
+        cf y[16];
+        if constexpr (S == 0) {
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const float2 w = lok ? Ws[wbase + tv + TPF * m] : make_float2(0.f, 0.f);
+                y[m] = {w.x, w.y};
+            }
+        } else {
+            for (int r = cr; r < N; r += RPI) {
+                const float2 v = sok ? ph[sbase + (size_t)r * my1] : make_float2(0.f, 0.f);
+                cp[2 * r] = v.x; cp[2 * r + 1] = v.y;
+            }
+            __syncthreads();
+            cf z[16];
+#pragma unroll
+            for (int m = 0; m < 16; ++m) z[m] = {mine[2 * (tv + TPF * m)], mine[2 * (tv + TPF * m) + 1]};
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            fft_line<float, N, false>(z, tab, tab + N / 2, xb, tv);
+            int te = tv;
+            asm volatile("" : "+v"(te), "+v"(z[0].x));
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const int e = te + TPF * m;
+                const int mx = m < 8 ? e : e - N;
+                // 2/3 rule in x (y: j < my1); the vorticity has no (0, 0) mode, the scalar keeps it (its mean)
+                const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (TH || (mx | lj) != 0);
+                const float kx = a.kx1 * (float)mx;
+                float x = (TH ? hkdt : a.hnudt) * (kx * kx + ky * ky);             // L dt / 2
+                if constexpr (FORCED && !TH) x -= fc.hdrag;
+                const float em1 = expm1f(x), em2 = expm1f(2.f * x);                // E - 1, E^2 - 1
+                cf n = keep ? cf{-z[m].x, -z[m].y} : cf{0.f, 0.f};
+                if constexpr (FORCED && !TH) {
+                    const float2 g = gok ? fc.g[gbase + e] : make_float2(0.f, 0.f);
+                    if (keep) n = {n.x + g.x, n.y + g.y};
+                }
+                const size_t si = wbase + e;
+                if constexpr (S == 1) {                 // a: A = E^2 (w + dt/6 a), next = E (w + dt/2 a)
+                    const float2 w2 = lok ? Ws[si] : make_float2(0.f, 0.f);
+                    const cf w = keep ? cf{w2.x, w2.y} : cf{0.f, 0.f};
+                    const cf acc = scal(em2, axpy(dt6, n, w));
+                    if (lok) As[si] = make_float2(acc.x, acc.y);
+                    y[m] = scal(em1, axpy(dt2, n, w));
+                } else if constexpr (S == 2) {          // b: A += dt/3 E b, next = E w + dt/2 b
+                    const float2 w2 = lok ? Ws[si] : make_float2(0.f, 0.f), a2 = lok ? As[si] : make_float2(0.f, 0.f);
+                    const cf w = keep ? cf{w2.x, w2.y} : cf{0.f, 0.f};
+                    const cf acc = axpy(dt3, scal(em1, n), cf{a2.x, a2.y});
+                    if (lok) As[si] = make_float2(acc.x, acc.y);
+                    y[m] = axpy(dt2, n, scal(em1, w));
+                } else if constexpr (S == 3) {          // c: A += dt/3 E c, next = E^2 w + dt E c
+                    const float2 w2 = lok ? Ws[si] : make_float2(0.f, 0.f), a2 = lok ? As[si] : make_float2(0.f, 0.f);
+                    const cf w = keep ? cf{w2.x, w2.y} : cf{0.f, 0.f};
+                    const cf ec = scal(em1, n);
+                    const cf acc = axpy(dt3, ec, cf{a2.x, a2.y});
+                    if (lok) As[si] = make_float2(acc.x, acc.y);
+                    y[m] = axpy(dt, ec, scal(em2, w));
+                } else {                                // d: w = A + dt/6 d
+                    const float2 a2 = lok ? As[si] : make_float2(0.f, 0.f);
+                    const cf acc = keep ? cf{a2.x, a2.y} : cf{0.f, 0.f};
+                    const cf w = axpy(dt6, n, acc);
+                    if (lok) Ws[si] = make_float2(w.x, w.y);
+                    y[m] = w;
+                }
+            }
+        }
+        if (S < 4 || emit) {
+            const float U0 = !TH && lok ? mean[2 * lb] : 0.f, V0 = !TH && lok ? mean[2 * lb + 1] : 0.f;
+            auto field = [&](auto fc) {
+                constexpr int F = decltype(fc)::value;
+                int te = tv;
+                asm volatile("" : "+v"(te), "+v"(y[0].x));
+                cf o[16];
+#pragma unroll
+                for (int m = 0; m < 16; ++m) {
+                    const int e = te + TPF * m;
+                    const int mx = m < 8 ? e : e - N;
+                    const float kx = a.kx1 * (float)mx;
+                    const float k2 = kx * kx + ky * ky;
+                    const float ik2 = k2 > 0.f ? a.inv_n / k2 : 0.f;
+                    if constexpr (F == 0) o[m] = imul(ky * ik2, y[m]);                 // u^ = i ky psi^
+                    else if constexpr (F == 1) o[m] = imul(-kx * ik2, y[m]);           // v^ = -i kx psi^
+                    else if constexpr (F == 2 || F == 4) o[m] = imul(kx * a.inv_n, y[m]);   // (w_x)^, (theta_x)^
+                    else o[m] = imul(ky * a.inv_n, y[m]);                              // (w_y)^, (theta_y)^
+                }
+                if constexpr (F < 2) {
+                    if (te == 0 && lj == 0) o[0] = {F == 0 ? U0 : V0, 0.f};           // the mean flow in the (0, 0) mode
+                }
+                fft_line<float, N, true>(o, tab, tab + N / 2, xb, tv);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int m = 0; m < 16; ++m) { mine[2 * (tv + TPF * m)] = o[m].x; mine[2 * (tv + TPF * m) + 1] = o[m].y; }
+                __syncthreads();
+                if (sok) {
+                    float2* g = G + (size_t)F * a.fstride + sbase;
+                    for (int r = cr; r < N; r += RPI) g[(size_t)r * my1] = make_float2(cp[2 * r], cp[2 * r + 1]);
+                }
+                __syncthreads();
+            };
+            if constexpr (TH) static_for<4, 6>(field);
+            else static_for<0, 4>(field);
+        } else {
+            __syncthreads();                        // the next staging overwrites line images other waves may still read
+        }
+}

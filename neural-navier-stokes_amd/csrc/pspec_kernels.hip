@@ -23,6 +23,14 @@
 // stage and uses L = -(nu |k|^2 + alpha); FORCED = false is the unforced code, argument list included.  ps_diag_kernel: energy,
 // enstrophy and power input per grid from w^ (and g^) by Parseval.
 //
+// Passive scalar (nns_spec_ns_step_scalar_f32; restatement: tests/pspec_scalar_oracle.py): theta_t + u theta_x + v theta_y = kappa lap theta
+// - (Gx u + Gy v), theta^ = M_theta rfft2(theta) in the layout of W with the (0, 0) mode KEPT (the mean of theta is state), integrated with w^
+// as one system by the same Lawson RK4 (L_theta = -kappa |k|^2: no drag).  SCALAR = true rides in the same launches: the row pass
+// inverse-transforms theta_x + i theta_y as well, forms u (theta_x + Gx) + v (theta_y + Gy) from the u, v it holds in registers and writes its
+// kept modes to a second Ph field; the column pass, after the vorticity's work on a tile, stages that field, updates theta^ and its
+// accumulator and prepares i kx theta^, i ky theta^ as G fields 4 and 5.  The vorticity's arithmetic is the unscalared kernel's, so w^ is
+// bitwise what it is without a scalar; SCALAR = false is the present code, argument list included.
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 #include "nns_common.h"
 #include "fft_lds.h"
@@ -55,9 +63,17 @@ struct PsForce {          // the extra argument of the FORCED column kernels
 };
 struct PsNoForce {};
 
+struct PsScalar {         // the extra argument of the SCALAR column kernels
+    float2* T;            // theta^ [B][my1][nx], the layout of W
+    float2* At;           // its Lawson accumulator
+    float hkdt;           // -kappa dt / 2
+};
+struct PsGrad { float gx, gy; };      // the extra argument of the SCALAR row kernel: the uniform mean gradient
+template <typename T> __device__ __forceinline__ T only(T t) { return t; }     // the one element of a SCALAR kernel's argument pack
+
 struct PsArgs {
     long nlines;          // row kernel: B nx rows; column kernel: B my1 columns
-    long fstride;         // complex elements between the four fields of G (= B nx my1)
+    long fstride;         // complex elements between the fields of G and of Ph (= B nx my1)
     int my1;              // kept y-wavenumbers
     float kx1, ky1;       // 2 pi / Lx, 2 pi / Ly
     float hnudt;          // -nu dt / 2
@@ -80,8 +96,11 @@ __device__ __forceinline__ cf* ps_tables(unsigned char* smem) {
 }
 
 // ---------------------------------------------------------------------------------------------------- row pass (axis y)
-template <int N>
-__global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a) {
+// SCALAR: a third inverse transform (theta_x + i theta_y, G fields 4 and 5) after the vorticity's product has left, so two complex lines
+// are live at a time, as without it; the second product goes to Ph's second field.
+template <int N, bool SCALAR = false, typename... Grad>
+__global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a, Grad... grad) {
+    static_assert(sizeof...(Grad) == (SCALAR ? 1 : 0), "the gradient is the SCALAR kernel's argument");
     using L = PsLds<N>;
     constexpr int TPF = L::TPF;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -125,17 +144,36 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
         __builtin_amdgcn_sched_barrier(0);
         load2(g0 + 2 * a.fstride, g0 + 3 * a.fstride, zw);   // w_x + i w_y
         fft_line<float, N, true>(zw, tab, tab + N / 2, xb, tid);
+        auto store = [&](const cf (&z)[16], float2* o) {
+            if (valid) {
 #pragma unroll
-        for (int m = 0; m < 16; ++m) zu[m] = {zu[m].x * zw[m].x + zu[m].y * zw[m].y, 0.f};    // u w_x + v w_y
-        __builtin_amdgcn_sched_barrier(0);
-        fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
-        if (valid) {
-            float2* o = Ph + (size_t)row * my1;
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const int e = tid + TPF * m;
-                if (e < my1) o[e] = make_float2(zu[m].x, zu[m].y);
+                for (int m = 0; m < 8; ++m) {
+                    const int e = tid + TPF * m;
+                    if (e < my1) o[e] = make_float2(z[m].x, z[m].y);
+                }
             }
+        };
+        if constexpr (!SCALAR) {
+#pragma unroll
+            for (int m = 0; m < 16; ++m) zu[m] = {zu[m].x * zw[m].x + zu[m].y * zw[m].y, 0.f};    // u w_x + v w_y
+            __builtin_amdgcn_sched_barrier(0);
+            fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
+            store(zu, Ph + (size_t)row * my1);
+        } else {
+            const PsGrad gr = only(grad...);
+#pragma unroll
+            for (int m = 0; m < 16; ++m) zw[m] = {zu[m].x * zw[m].x + zu[m].y * zw[m].y, 0.f};    // u w_x + v w_y: u, v stay
+            __builtin_amdgcn_sched_barrier(0);
+            fft_line<float, N, false>(zw, tab, tab + N / 2, xb, tid);
+            store(zw, Ph + (size_t)row * my1);
+            __builtin_amdgcn_sched_barrier(0);
+            load2(g0 + 4 * a.fstride, g0 + 5 * a.fstride, zw);   // theta_x + i theta_y
+            fft_line<float, N, true>(zw, tab, tab + N / 2, xb, tid);
+#pragma unroll
+            for (int m = 0; m < 16; ++m) zw[m] = {zu[m].x * (zw[m].x + gr.gx) + zu[m].y * (zw[m].y + gr.gy), 0.f};   // u (theta_x + Gx) + v (theta_y + Gy)
+            __builtin_amdgcn_sched_barrier(0);
+            fft_line<float, N, false>(zw, tab, tab + N / 2, xb, tid);
+            store(zw, Ph + a.fstride + (size_t)row * my1);
         }
     }
 }
@@ -143,11 +181,14 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
 // ---------------------------------------------------------------------------------------------------- column pass (axis x)
 // S = 0: prepare stage 1 from W; S = 1..4: consume the RK stage's N (from Ph) and update W / A, then (S < 4 or emit) prepare the next stage.
 // FORCED (S >= 1): N^ += g^ on the kept modes (lane-owned, coalesced, like W / A) and L dt / 2 = hnudt |k|^2 - alpha dt / 2.
-template <int N, int S, bool FORCED = false>
+// SCALAR: after the vorticity's work on a tile the same sequence runs once more on the scalar: Ph's second field, theta^ / A_theta with
+// L dt / 2 = hkdt |k|^2 (no drag, no force) and a mask that keeps the (0, 0) mode, then G fields 4 and 5.  One field's registers at a time.
+template <int N, int S, bool FORCED = false, bool SCALAR = false, typename... Sc>
 __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, float2* __restrict__ W,
                                                     float2* __restrict__ A, const float* __restrict__ mean, PsArgs a, int emit,
-                                                    std::conditional_t<FORCED, PsForce, PsNoForce> fc) {
+                                                    std::conditional_t<FORCED, PsForce, PsNoForce> fc, Sc... sc) {
     static_assert(!FORCED || S >= 1, "stage 0 only prepares: it has no forced form");
+    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0), "PsScalar is the SCALAR kernel's argument");
     using L = PsLds<N>;
     constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -156,6 +197,13 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     const int my1 = a.my1;
     const long ntiles = (a.nlines + CW - 1) / CW;
     const float dt = a.dt, dt2 = 0.5f * dt, dt3 = dt / 3.f, dt6 = dt / 6.f;
+    [[maybe_unused]] float2* Th = nullptr;
+    [[maybe_unused]] float2* At = nullptr;
+    [[maybe_unused]] float hkdt = 0.f;
+    if constexpr (SCALAR) {
+        const PsScalar ps = only(sc...);
+        Th = ps.T; At = ps.At; hkdt = ps.hkdt;
+    }
     for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
         int tx = threadIdx.x;
         asm volatile("" : "+v"(tx));
@@ -183,107 +231,14 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
         int tv = tid;
         asm volatile("" : "+v"(tv));
         const float ky = a.ky1 * (float)lj;
-        cf y[16];
-        if constexpr (S == 0) {
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                const float2 w = lok ? W[wbase + tv + TPF * m] : make_float2(0.f, 0.f);
-                y[m] = {w.x, w.y};
-            }
-        } else {
-            for (int r = cr; r < N; r += RPI) {
-                const float2 v = sok ? Ph[sbase + (size_t)r * my1] : make_float2(0.f, 0.f);
-                cp[2 * r] = v.x; cp[2 * r + 1] = v.y;
-            }
-            __syncthreads();
-            cf z[16];
-#pragma unroll
-            for (int m = 0; m < 16; ++m) z[m] = {mine[2 * (tv + TPF * m)], mine[2 * (tv + TPF * m) + 1]};
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            fft_line<float, N, false>(z, tab, tab + N / 2, xb, tv);
-            int te = tv;
-            asm volatile("" : "+v"(te), "+v"(z[0].x));
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                const int e = te + TPF * m;
-                const int mx = m < 8 ? e : e - N;
-                const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (mx | lj) != 0;    // 2/3 rule in x (y: j < my1), no (0, 0)
-                const float kx = a.kx1 * (float)mx;
-                float x = a.hnudt * (kx * kx + ky * ky);                           // L dt / 2
-                if constexpr (FORCED) x -= fc.hdrag;
-                const float em1 = expm1f(x), em2 = expm1f(2.f * x);                // E - 1, E^2 - 1
-                cf n = keep ? cf{-z[m].x, -z[m].y} : cf{0.f, 0.f};
-                if constexpr (FORCED) {
-                    const float2 g = gok ? fc.g[gbase + e] : make_float2(0.f, 0.f);
-                    if (keep) n = {n.x + g.x, n.y + g.y};
-                }
-                const size_t si = wbase + e;
-                if constexpr (S == 1) {                 // a: A = E^2 (w + dt/6 a), next = E (w + dt/2 a)
-                    const float2 w2 = lok ? W[si] : make_float2(0.f, 0.f);
-                    const cf w = keep ? cf{w2.x, w2.y} : cf{0.f, 0.f};
-                    const cf acc = scal(em2, axpy(dt6, n, w));
-                    if (lok) A[si] = make_float2(acc.x, acc.y);
-                    y[m] = scal(em1, axpy(dt2, n, w));
-                } else if constexpr (S == 2) {          // b: A += dt/3 E b, next = E w + dt/2 b
-                    const float2 w2 = lok ? W[si] : make_float2(0.f, 0.f), a2 = lok ? A[si] : make_float2(0.f, 0.f);
-                    const cf w = keep ? cf{w2.x, w2.y} : cf{0.f, 0.f};
-                    const cf acc = axpy(dt3, scal(em1, n), cf{a2.x, a2.y});
-                    if (lok) A[si] = make_float2(acc.x, acc.y);
-                    y[m] = axpy(dt2, n, scal(em1, w));
-                } else if constexpr (S == 3) {          // c: A += dt/3 E c, next = E^2 w + dt E c
-                    const float2 w2 = lok ? W[si] : make_float2(0.f, 0.f), a2 = lok ? A[si] : make_float2(0.f, 0.f);
-                    const cf w = keep ? cf{w2.x, w2.y} : cf{0.f, 0.f};
-                    const cf ec = scal(em1, n);
-                    const cf acc = axpy(dt3, ec, cf{a2.x, a2.y});
-                    if (lok) A[si] = make_float2(acc.x, acc.y);
-                    y[m] = axpy(dt, ec, scal(em2, w));
-                } else {                                // d: w = A + dt/6 d
-                    const float2 a2 = lok ? A[si] : make_float2(0.f, 0.f);
-                    const cf acc = keep ? cf{a2.x, a2.y} : cf{0.f, 0.f};
-                    const cf w = axpy(dt6, n, acc);
-                    if (lok) W[si] = make_float2(w.x, w.y);
-                    y[m] = w;
-                }
-            }
+        // one field through the tile, as plain text per field (see the note in the file): first the vorticity, then the scalar
+        {
+            constexpr bool TH = false;
+#include "pspec_col_pass.inc"
         }
-        if (S < 4 || emit) {
-            const float U0 = lok ? mean[2 * lb] : 0.f, V0 = lok ? mean[2 * lb + 1] : 0.f;
-            auto field = [&](auto fc) {
-                constexpr int F = decltype(fc)::value;
-                int te = tv;
-                asm volatile("" : "+v"(te), "+v"(y[0].x));
-                cf o[16];
-#pragma unroll
-                for (int m = 0; m < 16; ++m) {
-                    const int e = te + TPF * m;
-                    const int mx = m < 8 ? e : e - N;
-                    const float kx = a.kx1 * (float)mx;
-                    const float k2 = kx * kx + ky * ky;
-                    const float ik2 = k2 > 0.f ? a.inv_n / k2 : 0.f;
-                    if constexpr (F == 0) o[m] = imul(ky * ik2, y[m]);                 // u^ = i ky psi^
-                    else if constexpr (F == 1) o[m] = imul(-kx * ik2, y[m]);           // v^ = -i kx psi^
-                    else if constexpr (F == 2) o[m] = imul(kx * a.inv_n, y[m]);        // (w_x)^
-                    else o[m] = imul(ky * a.inv_n, y[m]);                              // (w_y)^
-                }
-                if constexpr (F < 2) {
-                    if (te == 0 && lj == 0) o[0] = {F == 0 ? U0 : V0, 0.f};           // the mean flow in the (0, 0) mode
-                }
-                fft_line<float, N, true>(o, tab, tab + N / 2, xb, tv);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int m = 0; m < 16; ++m) { mine[2 * (tv + TPF * m)] = o[m].x; mine[2 * (tv + TPF * m) + 1] = o[m].y; }
-                __syncthreads();
-                if (sok) {
-                    float2* g = G + (size_t)F * a.fstride + sbase;
-                    for (int r = cr; r < N; r += RPI) g[(size_t)r * my1] = make_float2(cp[2 * r], cp[2 * r + 1]);
-                }
-                __syncthreads();
-            };
-            static_for<0, 4>(field);
-        } else {
-            __syncthreads();                            // the next tile's staging overwrites line images other waves may still read
+        if constexpr (SCALAR) {
+            constexpr bool TH = true;
+#include "pspec_col_pass.inc"
         }
     }
 }
@@ -353,6 +308,27 @@ __global__ void ps_pressure_kernel(float2* __restrict__ qh, int batch, int nx, i
     }
 }
 
+// T[b][j][i] = M_theta th[b][i][j] from the rfft2 spectrum th [B][nx][nh]: the 2/3 rule, the (0, 0) mode kept
+__global__ void ps_scalar_compact_kernel(const float2* __restrict__ th, float2* __restrict__ T, int batch, int nx, int ny, int my1) {
+    const long total = (long)batch * my1 * nx, nh = ny / 2 + 1;
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+        const int i = (int)(q % nx), j = (int)((q / nx) % my1);
+        const long b = q / ((long)nx * my1);
+        const int mx = i < nx / 2 ? i : i - nx;
+        T[q] = 3 * (mx < 0 ? -mx : mx) < nx ? th[((size_t)b * nx + i) * nh + j] : make_float2(0.f, 0.f);
+    }
+}
+
+// the rfft2 spectrum th [B][nx][nh] of T: zero beyond the kept y-wavenumbers
+__global__ void ps_scalar_expand_kernel(const float2* __restrict__ T, float2* __restrict__ th, int batch, int nx, int ny, int my1) {
+    const long nh = ny / 2 + 1, per = (long)batch * nx * nh;
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < per; q += (long)gridDim.x * blockDim.x) {
+        const int j = (int)(q % nh), i = (int)((q / nh) % nx);
+        const long b = q / ((long)nx * nh);
+        th[q] = j < my1 ? T[((size_t)b * my1 + j) * nx + i] : make_float2(0.f, 0.f);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- diagnostics
 // out[b] = (E, Z, P): fluctuation energy 1/2 <|u - <u>|^2>, enstrophy 1/2 <w^2>, power input <f_s . u>, by Parseval over the stored half
 // spectrum (weight 1 on the j = 0 line, 2 on j > 0), normalised by (nx ny)^2.  One workgroup per grid; every lane sums its strided
@@ -399,54 +375,105 @@ __global__ __launch_bounds__(kDiagT) void ps_diag_kernel(const float2* __restric
     }
 }
 
+// out[b] = (variance 1/2 <theta'^2>, dissipation kappa <|grad theta|^2>, flux_x <u theta'>, flux_y <v theta'>) over k != 0, u^ = i ky w^ / |k|^2,
+// v^ = -i kx w^ / |k|^2: the same weights, normalisation, float64 sums and fixed order as ps_diag_kernel.
+__global__ __launch_bounds__(kDiagT) void ps_scalar_diag_kernel(const float2* __restrict__ W, const float2* __restrict__ T, double* __restrict__ out,
+                                                                 int nx, int my1, double kx1, double ky1, double kappa, double inv_n2) {
+    __shared__ double part[kDiagT / kWave][4];
+    const long per = (long)my1 * nx;
+    const float2* w = W + (size_t)blockIdx.x * per;
+    const float2* th = T + (size_t)blockIdx.x * per;
+    double s[4] = {0., 0., 0., 0.};
+    for (long q = threadIdx.x; q < per; q += kDiagT) {
+        const int i = (int)(q % nx), j = (int)(q / nx);
+        const int mx = i < nx / 2 ? i : i - nx;
+        const double kx = kx1 * mx, ky = ky1 * j, k2 = kx * kx + ky * ky;
+        const double ik2 = k2 > 0. ? 1. / k2 : 0.;
+        const double wt = j == 0 ? 1. : 2.;
+        const float2 c = w[q], d = th[q];
+        const double tt = k2 > 0. ? (double)d.x * d.x + (double)d.y * d.y : 0.;
+        const double cr = ((double)c.x * d.y - (double)c.y * d.x) * ik2;      // Re(i psi^ conj theta^)
+        s[0] += wt * tt;
+        s[1] += wt * tt * k2;
+        s[2] += wt * ky * cr;
+        s[3] -= wt * kx * cr;
+    }
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[k] += __shfl_xor(s[k], d, kWave);
+    }
+    const int wave = threadIdx.x / kWave;
+    if (threadIdx.x % kWave == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) part[wave][k] = s[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t[4] = {0., 0., 0., 0.};
+        for (int k = 0; k < kDiagT / kWave; ++k) { t[0] += part[k][0]; t[1] += part[k][1]; t[2] += part[k][2]; t[3] += part[k][3]; }
+        double* o = out + 4 * (size_t)blockIdx.x;
+        o[0] = 0.5 * t[0] * inv_n2; o[1] = kappa * t[1] * inv_n2; o[2] = t[2] * inv_n2; o[3] = t[3] * inv_n2;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- host side
 inline int kept_y(int ny) { return (ny - 1) / 3 + 1; }
 
 inline unsigned grid_of(long work, long per) { return capped_grid((work + per - 1) / per, kGridCap); }
 
+// gr == nullptr: the unscalared kernel
 template <int N>
-int launch_row(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s) {
+int launch_row(const float2* G, float2* Ph, const PsArgs& a, const PsGrad* gr, hipStream_t s) {
+    const dim3 grid(grid_of(a.nlines, PsLds<N>::LINES));
+    if (gr) {
+        constexpr auto kern = ps_row_kernel<N, true, PsGrad>;
+        if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+        hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a, *gr);
+        return check_launch("spec_ns scalar row pass");
+    }
     constexpr auto kern = ps_row_kernel<N>;
     if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a);
+    hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a);
     return check_launch("spec_ns row pass");
 }
 
-template <int N, int S>
-int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, hipStream_t s) {
-    constexpr auto kern = ps_col_kernel<N, S>;
+// fc == nullptr: the unforced kernels (stage 0 has no other form); sc == nullptr: the unscalared ones
+template <int N, int S, bool FORCED>
+int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
+               const PsScalar* sc, hipStream_t s) {
+    const dim3 grid(grid_of(a.nlines, PsLds<N>::LINES));
+    std::conditional_t<FORCED, PsForce, PsNoForce> f{};
+    if constexpr (FORCED) f = *fc;
+    if (sc) {
+        constexpr auto kern = ps_col_kernel<N, S, FORCED, true, PsScalar>;
+        if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+        hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, f, *sc);
+        return check_launch("spec_ns scalar column pass");
+    }
+    constexpr auto kern = ps_col_kernel<N, S, FORCED>;
     if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, PsNoForce{});
-    return check_launch("spec_ns column pass");
+    hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, f);
+    return check_launch(FORCED ? "spec_ns forced column pass" : "spec_ns column pass");
 }
 
-template <int N, int S>
-int launch_col_forced(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce& fc,
-                      hipStream_t s) {
-    constexpr auto kern = ps_col_kernel<N, S, true>;
-    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, fc);
-    return check_launch("spec_ns forced column pass");
-}
-
-// fc == nullptr: the unforced kernels (stage 0 has no other form)
 template <int N>
 int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
-                     hipStream_t s) {
+                     const PsScalar* sc, hipStream_t s) {
     if (fc && S >= 1) {
         switch (S) {
-            case 1: return launch_col_forced<N, 1>(Ph, G, W, A, mean, a, emit, *fc, s);
-            case 2: return launch_col_forced<N, 2>(Ph, G, W, A, mean, a, emit, *fc, s);
-            case 3: return launch_col_forced<N, 3>(Ph, G, W, A, mean, a, emit, *fc, s);
-            default: return launch_col_forced<N, 4>(Ph, G, W, A, mean, a, emit, *fc, s);
+            case 1: return launch_col<N, 1, true>(Ph, G, W, A, mean, a, emit, fc, sc, s);
+            case 2: return launch_col<N, 2, true>(Ph, G, W, A, mean, a, emit, fc, sc, s);
+            case 3: return launch_col<N, 3, true>(Ph, G, W, A, mean, a, emit, fc, sc, s);
+            default: return launch_col<N, 4, true>(Ph, G, W, A, mean, a, emit, fc, sc, s);
         }
     }
     switch (S) {
-        case 0: return launch_col<N, 0>(Ph, G, W, A, mean, a, emit, s);
-        case 1: return launch_col<N, 1>(Ph, G, W, A, mean, a, emit, s);
-        case 2: return launch_col<N, 2>(Ph, G, W, A, mean, a, emit, s);
-        case 3: return launch_col<N, 3>(Ph, G, W, A, mean, a, emit, s);
-        default: return launch_col<N, 4>(Ph, G, W, A, mean, a, emit, s);
+        case 0: return launch_col<N, 0, false>(Ph, G, W, A, mean, a, emit, nullptr, sc, s);
+        case 1: return launch_col<N, 1, false>(Ph, G, W, A, mean, a, emit, nullptr, sc, s);
+        case 2: return launch_col<N, 2, false>(Ph, G, W, A, mean, a, emit, nullptr, sc, s);
+        case 3: return launch_col<N, 3, false>(Ph, G, W, A, mean, a, emit, nullptr, sc, s);
+        default: return launch_col<N, 4, false>(Ph, G, W, A, mean, a, emit, nullptr, sc, s);
     }
 }
 
@@ -462,13 +489,21 @@ size_t work_bytes(int batch, int nx, int ny) {
     return b;
 }
 
-int check_common(const char* what, int batch, int nx, int ny, double Lx, double Ly, const void* work, size_t wbytes) {
+// the scalar step's A, A_theta, G[6], Ph[2]: 10 compacted fields against 6 (its init and field need one rfft2 spectrum: inside work_bytes)
+size_t scalar_work_bytes(int batch, int nx, int ny) {
+    const size_t b = work_bytes(batch, nx, ny), st = (size_t)10 * batch * nx * kept_y(ny) * sizeof(float2);
+    return st > b ? st : b;
+}
+
+int check_common(const char* what, int batch, int nx, int ny, double Lx, double Ly, const void* work, size_t wbytes, bool scalar = false) {
     if (!(Lx > 0) || !(Ly > 0) || !std::isfinite(Lx) || !std::isfinite(Ly))
         return fail(NNS_ERR_INVALID_ARG, "%s: Lx = %g, Ly = %g must be positive and finite", what, Lx, Ly);
     if (!pow2_in_range(nx) || !pow2_in_range(ny))
         return fail(NNS_ERR_UNSUPPORTED, "%s: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", what, nx, ny);
-    const size_t need = work_bytes(batch, nx, ny);
-    if (wbytes < need) return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (nns_spec_ns_workspace)", what, wbytes, need);
+    const size_t need = scalar ? scalar_work_bytes(batch, nx, ny) : work_bytes(batch, nx, ny);
+    if (wbytes < need)
+        return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", what, wbytes, need,
+                    scalar ? "nns_spec_ns_scalar_workspace" : "nns_spec_ns_workspace");
     (void)work;
     return NNS_OK;
 }
@@ -501,32 +536,39 @@ NNS_API int nns_spec_ns_init_f32(const float* u, const float* v, float* what, fl
     return check_launch("spec_ns_init");
 }
 
-// The step of both entry points: ghat == NULL and drag == 0 launch the unforced kernels.
-static int spec_ns_step(const char* who, float* what, const float* mean, const float* ghat, int gbatch, void* work, size_t work_bytes_,
-                        int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, int nsteps, void* stream) {
+// The step of every entry point: ghat == NULL and drag == 0 launch the unforced kernels, that == NULL the unscalared ones.
+static int spec_ns_step(const char* who, float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work,
+                        size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa,
+                        double gx, double gy, int nsteps, void* stream) {
     if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
     if (!(dt > 0) || !std::isfinite(dt) || !(nu >= 0) || !std::isfinite(nu) || nsteps < 0)
         return fail(NNS_ERR_INVALID_ARG, "%s: dt = %g must be > 0, nu = %g >= 0, nsteps = %d >= 0", who, dt, nu, nsteps);
     if (!(drag >= 0) || !std::isfinite(drag)) return fail(NNS_ERR_INVALID_ARG, "%s: drag = %g must be finite and >= 0", who, drag);
+    if (!(kappa >= 0) || !std::isfinite(kappa) || !std::isfinite(gx) || !std::isfinite(gy))
+        return fail(NNS_ERR_INVALID_ARG, "%s: kappa = %g must be finite and >= 0, the gradient (%g, %g) finite", who, kappa, gx, gy);
     if (ghat ? (gbatch != 1 && gbatch != batch) : gbatch != 0)
         return fail(NNS_ERR_INVALID_ARG, "%s: gbatch = %d must be 0 without ghat, 1 or batch = %d with it", who, gbatch, batch);
-    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work, work_bytes_)) return rc;
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work, work_bytes_, that != nullptr)) return rc;
     if (nsteps == 0) return NNS_OK;
     hipStream_t s = as_stream(stream);
     const int my1 = kept_y(ny);
     const long fstride = (long)batch * nx * my1;
     float2* W = reinterpret_cast<float2*>(what);
     float2* A = static_cast<float2*>(work);
-    float2* G = A + fstride;
-    float2* Ph = G + 4 * fstride;
+    float2* G = A + (that ? 2 : 1) * fstride;                // work: A, G[4], Ph; with a scalar A, A_theta, G[6], Ph[2]
+    float2* Ph = G + (that ? 6 : 4) * fstride;
     PsArgs ac{(long)batch * my1, fstride, my1, (float)(2.0 * M_PI / Lx), (float)(2.0 * M_PI / Ly), (float)(-0.5 * nu * dt), (float)dt,
               (float)(1.0 / ((double)nx * ny))};
     PsArgs ar = ac;
     ar.nlines = (long)batch * nx;
     const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
     const PsForce* fc = ghat || drag > 0 ? &force : nullptr;
-    auto col = [&](int S, int emit) { return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, fc, s); }); };
-    auto row = [&]() { return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, s); }); };
+    const PsScalar scalar{reinterpret_cast<float2*>(that), A + fstride, (float)(-0.5 * kappa * dt)};
+    const PsGrad grad{(float)gx, (float)gy};
+    const PsScalar* sc = that ? &scalar : nullptr;
+    const PsGrad* gr = that ? &grad : nullptr;
+    auto col = [&](int S, int emit) { return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, fc, sc, s); }); };
+    auto row = [&]() { return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, gr, s); }); };
     if (int rc = col(0, 1)) return rc;
     for (int k = 0; k < nsteps; ++k) {
         for (int S = 1; S <= 4; ++S) {
@@ -539,13 +581,68 @@ static int spec_ns_step(const char* who, float* what, const float* mean, const f
 
 NNS_API int nns_spec_ns_step_f32(float* what, const float* mean, void* work, size_t work_bytes_, int batch, int nx, int ny, double Lx,
                                  double Ly, double dt, double nu, int nsteps, void* stream) {
-    return spec_ns_step("spec_ns_step", what, mean, nullptr, 0, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, 0.0, nsteps, stream);
+    return spec_ns_step("spec_ns_step", what, nullptr, mean, nullptr, 0, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, 0.0, 0.0, 0.0, 0.0, nsteps,
+                        stream);
 }
 
 NNS_API int nns_spec_ns_step_forced_f32(float* what, const float* mean, const float* ghat, int gbatch, void* work, size_t work_bytes_,
                                         int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, int nsteps,
                                         void* stream) {
-    return spec_ns_step("spec_ns_step_forced", what, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, drag, nsteps, stream);
+    return spec_ns_step("spec_ns_step_forced", what, nullptr, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, drag, 0.0, 0.0,
+                        0.0, nsteps, stream);
+}
+
+NNS_API int nns_spec_ns_step_scalar_f32(float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work,
+                                        size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
+                                        double kappa, double gx, double gy, int nsteps, void* stream) {
+    if (!that) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_scalar: NULL pointer or batch < 1");
+    return spec_ns_step("spec_ns_step_scalar", what, that, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, drag, kappa, gx,
+                        gy, nsteps, stream);
+}
+
+NNS_API int nns_spec_ns_scalar_workspace(int batch, int nx, int ny, size_t* bytes) {
+    if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
+    if (!pow2_in_range(nx) || !pow2_in_range(ny))
+        return fail(NNS_ERR_UNSUPPORTED, "spec_ns_scalar_workspace: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", nx, ny);
+    *bytes = scalar_work_bytes(batch, nx, ny);
+    return NNS_OK;
+}
+
+NNS_API int nns_spec_ns_scalar_init_f32(const float* theta, float* that, void* work, size_t work_bytes_, int batch, int nx, int ny,
+                                        void* stream) {
+    if (!theta || !that || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_init: NULL pointer or batch < 1");
+    if (int rc = check_common("spec_ns_scalar_init", batch, nx, ny, 1.0, 1.0, work, work_bytes_, true)) return rc;
+    float* th = static_cast<float*>(work);
+    if (int rc = nns_spec_rfft2_f32(theta, th, batch, nx, ny, stream)) return rc;
+    const int my1 = kept_y(ny);
+    hipLaunchKernelGGL(ps_scalar_compact_kernel, dim3(pw_grid((long)batch * my1 * nx)), dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const float2*>(th), reinterpret_cast<float2*>(that), batch, nx, ny, my1);
+    return check_launch("spec_ns_scalar_init");
+}
+
+NNS_API int nns_spec_ns_scalar_field_f32(const float* that, float* theta, void* work, size_t work_bytes_, int batch, int nx, int ny,
+                                         void* stream) {
+    if (!that || !theta || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_field: NULL pointer or batch < 1");
+    if (int rc = check_common("spec_ns_scalar_field", batch, nx, ny, 1.0, 1.0, work, work_bytes_, true)) return rc;
+    float* th = static_cast<float*>(work);
+    hipLaunchKernelGGL(ps_scalar_expand_kernel, dim3(pw_grid((long)batch * nx * (ny / 2 + 1))), dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const float2*>(that), reinterpret_cast<float2*>(th), batch, nx, ny, kept_y(ny));
+    if (int rc = check_launch("spec_ns_scalar_field")) return rc;
+    return nns_spec_irfft2_f32(th, theta, batch, nx, ny, stream);
+}
+
+NNS_API int nns_spec_ns_scalar_diag_f32(const float* what, const float* that, double* out, int batch, int nx, int ny, double Lx, double Ly,
+                                        double kappa, void* stream) {
+    if (!what || !that || !out || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_diag: NULL pointer or batch < 1");
+    if (!(Lx > 0) || !(Ly > 0) || !std::isfinite(Lx) || !std::isfinite(Ly))
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_diag: Lx = %g, Ly = %g must be positive and finite", Lx, Ly);
+    if (!(kappa >= 0) || !std::isfinite(kappa)) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_diag: kappa = %g must be finite and >= 0", kappa);
+    if (!pow2_in_range(nx) || !pow2_in_range(ny))
+        return fail(NNS_ERR_UNSUPPORTED, "spec_ns_scalar_diag: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", nx, ny);
+    const double n = (double)nx * ny;
+    hipLaunchKernelGGL(ps_scalar_diag_kernel, dim3(batch), dim3(kDiagT), 0, as_stream(stream), reinterpret_cast<const float2*>(what),
+                       reinterpret_cast<const float2*>(that), out, nx, kept_y(ny), 2.0 * M_PI / Lx, 2.0 * M_PI / Ly, kappa, 1.0 / (n * n));
+    return check_launch("spec_ns_scalar_diag");
 }
 
 NNS_API int nns_spec_ns_diag_f32(const float* what, const float* ghat, int gbatch, double* out, int batch, int nx, int ny, double Lx,

@@ -959,6 +959,88 @@ def spec_ns_diag(what, ghat, ny, Lx, Ly, out=None):
     return out
 
 
+# passive scalar of the periodic solver (nns_spec_ns_scalar_*, nns_spec_ns_step_scalar_f32)
+def spec_ns_scalar_workspace(B, nx, ny):
+    """Bytes of the workspace the scalar calls need for B grids of nx x ny (>= spec_ns_workspace: it serves every spec_ns call)."""
+    return _query_bytes('nns_spec_ns_scalar_workspace', int(B), int(nx), int(ny))
+
+
+def _spec_ns_scalar(who, that, work, ny):
+    """(B, my1, nx) of the checked scalar spectrum that (float32 [B, my1, nx, 2]) and, unless None, its workspace."""
+    _f32(that)
+    if that.dim() != 4 or that.shape[3] != 2:
+        raise ValueError("%s: that must be float32 [B, my1, nx, 2], got %s" % (who, tuple(that.shape)))
+    B, my1, nx = that.shape[0], that.shape[1], that.shape[2]
+    if my1 != spec_ns_kept_y(ny):
+        raise ValueError("%s: that has %d kept y-wavenumbers, ny = %d needs %d" % (who, my1, ny, spec_ns_kept_y(ny)))
+    if work is not None:
+        if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
+            raise TypeError("%s: work must be a contiguous uint8 device tensor" % who)
+        if work.device != that.device:
+            raise ValueError("%s: state tensors on different devices" % who)
+    return B, my1, nx
+
+
+def spec_ns_scalar_init(theta, that, work):
+    """that <- M_theta rfft2(theta) compacted ([B, my1, nx, 2]) for theta [B, nx, ny] float32: its band-limited part, the mean included."""
+    _f32(theta)
+    suf, (B, nx, ny) = _chk(theta)
+    if (B, spec_ns_kept_y(ny), nx) != _spec_ns_scalar('spec_ns_scalar_init', that, work, ny) or theta.device != that.device:
+        raise ValueError("spec_ns_scalar_init: state %s does not match the field [%d, %d, %d]" % (tuple(that.shape), B, nx, ny))
+    check(_lib.lib().nns_spec_ns_scalar_init_f32(_p(theta), _p(that), _p(work), work.numel(), B, nx, ny, _stream()),
+          'nns_spec_ns_scalar_init_f32')
+    return that
+
+
+def spec_ns_scalar_field(that, work, ny, out=None):
+    """theta float32 [B, nx, ny] of the scalar state; out: a preallocated contiguous tensor of that shape."""
+    B, my1, nx = _spec_ns_scalar('spec_ns_scalar_field', that, work, ny)
+    if out is None:
+        out = torch.empty((B, nx, int(ny)), dtype=torch.float32, device=that.device)
+    else:
+        _f32(out)
+        if tuple(out.shape) != (B, nx, int(ny)) or out.device != that.device:
+            raise ValueError("spec_ns_scalar_field: out must be a [%d, %d, %d] tensor on the state's device" % (B, nx, ny))
+    check(_lib.lib().nns_spec_ns_scalar_field_f32(_p(that), _p(out), _p(work), work.numel(), B, nx, int(ny), _stream()),
+          'nns_spec_ns_scalar_field_f32')
+    return out
+
+
+def _spec_ns_same(who, that, what):
+    _f32(that)
+    if tuple(that.shape) != tuple(what.shape) or that.device != what.device:
+        raise ValueError("%s: that must be float32 %s on the state's device, got %s on %s"
+                         % (who, tuple(what.shape), tuple(that.shape), that.device))
+
+
+def spec_ns_step_scalar_(what, that, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, kappa, grad=(0.0, 0.0), nsteps=1):
+    """nsteps Lawson-RK4 steps of the flow and its passive scalar, (what, that) in place: diffusivity kappa, uniform mean gradient grad =
+    (Gx, Gy); ghat and drag as in spec_ns_step_forced_ (None and 0: the unforced flow).  what comes out bitwise as without the scalar.
+    work: spec_ns_scalar_workspace bytes.  No allocation, no host synchronisation: capturable."""
+    B, my1, nx = _spec_ns_state('spec_ns_step_scalar_', what, mean, work, ny)
+    _spec_ns_same('spec_ns_step_scalar_', that, what)
+    gbatch = _spec_ns_force('spec_ns_step_scalar_', ghat, what)
+    gx, gy = grad
+    check(_lib.lib().nns_spec_ns_step_scalar_f32(_p(what), _p(that), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(work), work.numel(), B,
+                                                 nx, int(ny), float(Lx), float(Ly), float(dt), float(nu), float(drag), float(kappa), float(gx),
+                                                 float(gy), int(nsteps), _stream()), 'nns_spec_ns_step_scalar_f32')
+    return what, that
+
+
+def spec_ns_scalar_diag(what, that, ny, Lx, Ly, kappa, out=None):
+    """float64 [B, 4]: variance 1/2 <theta'^2>, dissipation kappa <|grad theta|^2> and the fluxes <u theta'>, <v theta'> of every grid."""
+    B, my1, nx = _spec_ns_state('spec_ns_scalar_diag', what, None, None, ny)
+    _spec_ns_same('spec_ns_scalar_diag', that, what)
+    if out is None:
+        out = torch.empty((B, 4), dtype=torch.float64, device=what.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (B, 4) and out.is_contiguous()
+              and out.device == what.device):
+        raise ValueError("spec_ns_scalar_diag: out must be a contiguous float64 [%d, 4] tensor on the state's device" % B)
+    check(_lib.lib().nns_spec_ns_scalar_diag_f32(_p(what), _p(that), _p(out), B, nx, int(ny), float(Lx), float(Ly), float(kappa), _stream()),
+          'nns_spec_ns_scalar_diag_f32')
+    return out
+
+
 # ----------------------------------------------------------------------------- physics-informed loss head
 _PINN_WS = {}
 

@@ -17,7 +17,8 @@ otherwise, 2 = float64 forward transforms always.
 
 ``PeriodicSolver`` produces the trajectories such a residual measures: a pseudo-spectral solver of the same equations on the same box
 (csrc/pspec_kernels.hip; scheme in DESIGN.md and tests/pspec_oracle.py), optionally with a steady body force and a linear drag
-(tests/pspec_forced_oracle.py).
+(tests/pspec_forced_oracle.py) and with a passive scalar -- temperature, dye -- that the same fused step transports
+(tests/pspec_scalar_oracle.py).
 """
 import collections
 import math
@@ -105,15 +106,17 @@ def _count(name, n, minimum):
 
 
 Diagnostics = collections.namedtuple('Diagnostics', ['energy', 'enstrophy', 'power_in'])
+ScalarDiagnostics = collections.namedtuple('ScalarDiagnostics', ['variance', 'dissipation', 'flux_x', 'flux_y'])
 
 
 class PeriodicState(object):
     """State of a PeriodicSolver run; owns its device buffers.
     what: the vorticity spectrum, compacted to the kept y-wavenumbers and transposed (float32 [B, my1, nx, 2], include/nns.h: nns_spec_ns_*);
-    mean: the conserved mean velocity (U0, V0) per grid, float32 [B, 2]; work: the solver's scratch; steps: steps taken since init."""
+    mean: the conserved mean velocity (U0, V0) per grid, float32 [B, 2]; work: the solver's scratch; steps: steps taken since init;
+    that: the passive scalar's spectrum in the layout of what, its (0, 0) mode (the mean of the scalar) kept, or None without a scalar."""
 
-    def __init__(self, what, mean, work):
-        self.what, self.mean, self.work = what, mean, work
+    def __init__(self, what, mean, work, that=None):
+        self.what, self.mean, self.work, self.that = what, mean, work, that
         self.steps = 0
 
     @property
@@ -122,7 +125,7 @@ class PeriodicState(object):
 
     def clone(self):
         """A copy with its own buffers (a fresh workspace: the solver keeps no data in it between calls)."""
-        c = PeriodicState(self.what.clone(), self.mean.clone(), torch.empty_like(self.work))
+        c = PeriodicState(self.what.clone(), self.mean.clone(), torch.empty_like(self.work), None if self.that is None else self.that.clone())
         c.steps = self.steps
         return c
 
@@ -141,17 +144,40 @@ class PeriodicSolver(object):
     where <.> is the grid mean and f_s the solenoidal, zero-mean, band-limited part of f (``forcing_fields()``): a gradient part of f only
     shifts the pressure and a mean part only accelerates the frame, so both are dropped, as ``init`` drops them from a velocity.  The mean
     velocity stays conserved and undamped and ``p`` keeps its definition (div f_s = 0).  ``diagnostics(state)`` gives energy, enstrophy and
-    the power input of the force per grid.  Without a force and with drag == 0 every call takes the unforced path."""
+    the power input of the force per grid.  Without a force and with drag == 0 every call takes the unforced path.
 
-    def __init__(self, nx, ny, dt, rho, nu, Lx=2 * math.pi, Ly=2 * math.pi, drag=0.0):
+    Passive scalar: with ``kappa`` >= 0 (None: no scalar) and ``init(u, v, theta)`` the state also carries a scalar theta -- temperature,
+    dye, concentration -- that the flow advects and that does not act back on it:
+        theta_t + (u . grad) theta = kappa lap theta - G . u
+    ``scalar_gradient`` = G = (Gx, Gy) is a uniform mean gradient: the total field is G . x + theta and theta its periodic part, whose variance
+    the gradient sustains.  theta is band-limited like the flow but keeps its grid mean, d<theta>/dt = -G . (U0, V0); the drag does not act
+    on it.  It rides in the flow's launches (still 8 per step), each RK stage with that stage's own velocity, and the flow evolves bitwise
+    as without it.  ``scalar(state)`` gives theta, ``scalar_diagnostics(state)`` its variance budget.  A state without a scalar takes exactly
+    the calls it takes on a solver without ``kappa``."""
+
+    def __init__(self, nx, ny, dt, rho, nu, Lx=2 * math.pi, Ly=2 * math.pi, drag=0.0, kappa=None, scalar_gradient=(0.0, 0.0)):
         self.nx, self.ny = _pow2_axis('nx', nx), _pow2_axis('ny', ny)
         self.dt, self.rho = _real('dt', dt), _real('rho', rho)
         self.nu = _real('nu', nu, positive=False)
         self.Lx, self.Ly = _real('Lx', Lx), _real('Ly', Ly)
         self.drag = _real('drag', drag, positive=False)
+        self.kappa = None if kappa is None else _real('kappa', kappa, positive=False)
+        try:
+            gx, gy = scalar_gradient
+        except (TypeError, ValueError):
+            raise TypeError("scalar_gradient must be two real numbers (Gx, Gy), got %r" % (scalar_gradient,))
+        self.scalar_gradient = tuple(self._finite('scalar_gradient', g) for g in (gx, gy))
         self.my1 = ops.spec_ns_kept_y(self.ny)
         self.ghat = None                       # the force's vorticity-equation spectrum g^, float32 [Bg, my1, nx, 2] (set_forcing)
         self.last_simulate_used_graph = False
+
+    @staticmethod
+    def _finite(name, x):
+        if isinstance(x, bool) or not isinstance(x, numbers.Real):
+            raise TypeError("%s must hold real numbers, got %r" % (name, x))
+        if not math.isfinite(x):
+            raise ValueError("%s = %r must be finite" % (name, x))
+        return float(x)
 
     def _field(self, name, a):
         if isinstance(a, np.ndarray):
@@ -173,22 +199,38 @@ class PeriodicSolver(object):
             raise TypeError("a PeriodicState (from init) expected, got %s" % type(state).__name__)
         if tuple(state.what.shape[1:]) != (self.my1, self.nx, 2):
             raise ValueError("state of another grid: what is %s, this solver's is [B, %d, %d, 2]" % (tuple(state.what.shape), self.my1, self.nx))
+        if state.that is not None:
+            if tuple(state.that.shape) != tuple(state.what.shape):
+                raise ValueError("the state's scalar spectrum is %s, its vorticity spectrum %s" % (tuple(state.that.shape), tuple(state.what.shape)))
+            if self.kappa is None:
+                raise ValueError("the state carries a scalar, this solver has no kappa")
         return state
 
-    def init(self, u, v):
-        """State of velocity (u, v) ([B, nx, ny] or [nx, ny], float32): see the class note on the projection."""
+    def init(self, u, v, theta=None):
+        """State of velocity (u, v) ([B, nx, ny] or [nx, ny], float32): see the class note on the projection.  With ``theta`` (same shape) the
+        state also carries the passive scalar: its band-limited part, the grid mean included (the solver needs ``kappa``)."""
         u, v = self._field('u', u), self._field('v', v)
         if u.shape != v.shape:
             raise ValueError("u and v must share their shape")
+        if theta is not None:
+            if self.kappa is None:
+                raise ValueError("init(theta=...) needs a solver built with kappa (the scalar's diffusivity)")
+            theta = self._field('theta', theta)
+            if theta.shape != u.shape:
+                raise ValueError("theta must have the shape of u and v")
         from ._util import default_device
         dev = u.device if u.is_cuda else (v.device if v.is_cuda else default_device())
         u, v = u.to(dev).contiguous(), v.to(dev).contiguous()
         B = u.shape[0]
         what = torch.empty((B, self.my1, self.nx, 2), dtype=torch.float32, device=u.device)
         mean = torch.empty((B, 2), dtype=torch.float32, device=u.device)
-        work = torch.empty(ops.spec_ns_workspace(B, self.nx, self.ny), dtype=torch.uint8, device=u.device)
+        size = ops.spec_ns_workspace if theta is None else ops.spec_ns_scalar_workspace
+        work = torch.empty(size(B, self.nx, self.ny), dtype=torch.uint8, device=u.device)
         ops.spec_ns_init(u, v, what, mean, work, self.Lx, self.Ly)
-        return PeriodicState(what, mean, work)
+        if theta is None:
+            return PeriodicState(what, mean, work)
+        that = ops.spec_ns_scalar_init(theta.to(dev).contiguous(), torch.empty_like(what), work)
+        return PeriodicState(what, mean, work, that)
 
     # ---- forcing
     def set_forcing(self, fx, fy=None):
@@ -244,7 +286,10 @@ class PeriodicSolver(object):
         return g
 
     def _launch_steps(self, state, nsteps):
-        if self._forced():
+        if state.that is not None:
+            ops.spec_ns_step_scalar_(state.what, state.that, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt,
+                                     self.nu, self.drag, self.kappa, self.scalar_gradient, nsteps)
+        elif self._forced():
             ops.spec_ns_step_forced_(state.what, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu,
                                      self.drag, nsteps)
         else:
@@ -266,14 +311,33 @@ class PeriodicSolver(object):
         out = ops.spec_ns_diag(state.what, self._force_of(state), self.ny, self.Lx, self.Ly)
         return Diagnostics(out[:, 0], out[:, 1], out[:, 2])
 
+    def _scalar_state(self, state):
+        self._state(state)
+        if state.that is None:
+            raise ValueError("the state carries no scalar: build it with init(u, v, theta) on a solver with kappa")
+        return state
+
+    def scalar(self, state, out=None):
+        """theta float32 [B, nx, ny] of the state (into ``out`` if given)."""
+        self._scalar_state(state)
+        return ops.spec_ns_scalar_field(state.that, state.work, self.ny, out)
+
+    def scalar_diagnostics(self, state):
+        """ScalarDiagnostics(variance, dissipation, flux_x, flux_y), each float64 [B], computed on the device from the state's spectra:
+        variance = 1/2 <theta'^2> (theta' = theta - <theta>), dissipation = kappa <|grad theta|^2>, flux = <u theta'>, so that
+        d variance / dt = -(Gx flux_x + Gy flux_y) - dissipation."""
+        self._scalar_state(state)
+        out = ops.spec_ns_scalar_diag(state.what, state.that, self.ny, self.Lx, self.Ly, self.kappa)
+        return ScalarDiagnostics(out[:, 0], out[:, 1], out[:, 2], out[:, 3])
+
     def fields(self, state, out=None):
         """(u, v, p) float32 [B, nx, ny] of the state (into ``out`` if given)."""
         self._state(state)
         return ops.spec_ns_fields(state.what, state.mean, state.work, self.ny, self.Lx, self.Ly, self.rho, out)
 
-    def simulate(self, u0, v0, nsteps, save_every=1, use_graph=None):
+    def simulate(self, u0, v0, nsteps, save_every=1, use_graph=None, theta0=None):
         """Frames (U, V, P), each float32 [T, B, nx, ny] with T = nsteps // save_every + 1: the projected initial condition, then every
-        save_every-th step.  By default one step is captured as a HIP graph and replayed (use_graph=False: the eager loop; a capture that
+        save_every-th step; with ``theta0`` (U, V, P, Theta), the scalar's frames as well.  By default one step is captured as a HIP graph and replayed (use_graph=False: the eager loop; a capture that
         fails falls back to it); same kernels in the same order, so the frames are bitwise those of the eager loop."""
         nsteps, save_every = _count('nsteps', nsteps, 0), _count('save_every', save_every, 1)
         if nsteps % save_every:
@@ -281,12 +345,18 @@ class PeriodicSolver(object):
         if self.ghat is not None and self.ghat.shape[0] not in (1, self._field('u', u0).shape[0]):
             raise ValueError("the force is per grid for a batch of %d, the initial condition has %d grids"
                              % (self.ghat.shape[0], self._field('u', u0).shape[0]))
-        state = self.init(u0, v0)
+        state = self.init(u0, v0, theta0)
         self._force_of(state)
         T = nsteps // save_every + 1
         U = torch.empty((T, state.batch, self.nx, self.ny), dtype=torch.float32, device=state.what.device)
         V, P = torch.empty_like(U), torch.empty_like(U)
-        self.fields(state, out=(U[0], V[0], P[0]))
+        Theta = None if theta0 is None else torch.empty_like(U)
+
+        def save(k):
+            self.fields(state, out=(U[k], V[k], P[k]))
+            if Theta is not None:
+                self.scalar(state, out=Theta[k])
+        save(0)
         if use_graph is None:
             use_graph = True
         graph = None
@@ -312,8 +382,8 @@ class PeriodicSolver(object):
                 state.steps += save_every
             else:
                 self.step(state, save_every)
-            self.fields(state, out=(U[k], V[k], P[k]))
-        return U, V, P
+            save(k)
+        return (U, V, P) if Theta is None else (U, V, P, Theta)
 
     def residual_engine(self, backend='spectral', precise=True, every=1):
         """A ResidualEngine with this solver's constants, for frames ``every`` steps apart (its dt = every * dt).  The engine knows neither

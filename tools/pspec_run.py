@@ -4,6 +4,7 @@ spec_irfft2 plus torch elementwise ops on full rfft2-layout spectra.  Writes ONE
 
     python tools/pspec_run.py OUTDIR [--steps 20] [--reps 5]
     python tools/pspec_run.py OUTDIR --forced [--steps 20] [--reps 7] [--commit ID]
+    python tools/pspec_run.py OUTDIR --scalar [--steps 100] [--reps 7] [--commit ID]
 
 Cases: 256^2 x B = 64 and 1024^2 x B = 8, |m| <= 8 initial condition (tests/pspec_oracle.py: random_ic), nu = 1e-3.  Per case: ms per
 step of each (device events around `steps` steps, warmed, median of `reps`), the bytes-per-point model of each (below) and the rel-L2
@@ -12,7 +13,14 @@ difference of the two after `steps` steps (same scheme, float32 both: rounding o
 --forced instead times the forced step (Kolmogorov force k = 4, drag 0.1: nns_spec_ns_step_forced_f32) next to the unforced step of the
 same build on the same state, the three variants (unforced, shared force, per-grid force) taking turns within every repetition, and one
 diagnostics call next to one fields call (256^2 x 64 and 1024^2 x 1).  Writes ONE record to OUTDIR/pspec_forced_run.json: per variant the
-median ms per step and the spread (max - min) / median over the repetitions, the ratios to the unforced step and the byte model's 54 / 50."""
+median ms per step and the spread (max - min) / median over the repetitions, the ratios to the unforced step and the byte model's 54 / 50.
+
+--scalar times the step with a passive scalar (nns_spec_ns_step_scalar_f32: kappa = 1e-3, G = (0.7, -0.4)) next to the flow-only step of the
+same build from the same initial state: flow only, scalar over the unforced flow and scalar under the Kolmogorov force and drag take turns
+within every repetition.  Per case the median ms per step and spread of each, the ratios to the flow-only step next to the byte model's
+84 / 50 and the transform count's 13 / 8, and whether the vorticity spectrum after the timed steps is bitwise the flow-only one; then one
+scalar_diagnostics call and one scalar call.  Writes ONE record to OUTDIR/pspec_scalar_run.json.  With --commit the record also holds the
+flow-only step against the figure the parent commit recorded in profiles/pspec_forced_run.json (another run: compare within the spreads)."""
 import argparse
 import json
 import math
@@ -164,19 +172,89 @@ def forced_main(args):
     print(json.dumps(rec))
 
 
+def scalar_main(args):
+    rec = dict(device=torch.cuda.get_device_name(0), commit=args.commit, steps=args.steps, reps=args.reps,
+               byte_model_ratio=round(84 / 50, 3), byte_model_ratio_forced=round(88 / 50, 3), transform_ratio=round(13 / 8, 3), cases=[], calls=[])
+    dev = lambda a: torch.as_tensor(a, dtype=torch.float32, device='cuda')
+    kw = dict(kappa=1e-3, scalar_gradient=(0.7, -0.4))
+    for n, B in CASES:
+        u0, v0 = O.random_ic(B, n, n, 8, seed=n + B, umax=1.0)
+        th0 = O.random_ic(B, n, n, 8, seed=n + B + 2, umax=1.0)[0] + 0.5
+        plain = PeriodicSolver(n, n, 1e-3, 1.0, 1e-3, **kw)
+        forced = PeriodicSolver(n, n, 1e-3, 1.0, 1e-3, drag=0.1, **kw).kolmogorov_forcing(4, 1.0)
+        flow = plain.init(dev(u0), dev(v0))
+        both = plain.init(dev(u0), dev(v0), dev(th0))
+        w0, t0 = both.what.clone(), both.that.clone()
+        variants = [('flow_only', plain, flow), ('scalar', plain, both), ('scalar_forced', forced, both)]
+        ts = {name: [] for name, _, _ in variants}
+        for name, s, st in variants:                              # warm every kernel of every variant
+            s.step(st, 2)
+        torch.cuda.synchronize()
+        ends = {}
+        for _ in range(args.reps):
+            for name, s, st in variants:
+                st.what.copy_(w0)
+                if st.that is not None:
+                    st.that.copy_(t0)
+                ts[name].append(event_ms(lambda: s.step(st, args.steps)))
+                ends[name] = st.what.clone()
+        case = dict(nx=n, ny=n, batch=B)
+        for name, _, _ in variants:
+            case[name] = stats(ts[name], args.steps)
+        for name in ('scalar', 'scalar_forced'):
+            case[name + '_over_flow_only'] = round(case[name]['ms'] / case['flow_only']['ms'], 4)
+        case['what_bitwise_flow_only'] = bool(torch.equal(ends['flow_only'], ends['scalar']))
+        c = 8.0 * ops.spec_ns_kept_y(n) * n * B                           # bytes of one compacted complex field of the batch
+        case['scalar_GBps_on_84c'] = round(84 * c / case['scalar']['ms'] / 1e6, 1)
+        if args.commit != 'unknown':
+            parent = json.load(open(os.path.join(ROOT, 'profiles', 'pspec_forced_run.json')))
+            pc = [x for x in parent['cases'] if (x['nx'], x['batch']) == (n, B)][0]['unforced']
+            case['flow_only_parent_record'] = dict(commit=parent['commit'], steps=parent['steps'], **pc)
+            case['flow_only_over_parent_record'] = round(case['flow_only']['ms'] / pc['ms'], 4)
+        rec['cases'].append(case)
+        print(json.dumps(case), flush=True)
+        del flow, both, ends
+        torch.cuda.empty_cache()
+    for n, B in ((256, 64), (1024, 1)):
+        s = PeriodicSolver(n, n, 1e-3, 1.0, 1e-3, **kw)
+        u0, v0 = O.random_ic(B, n, n, 8, seed=n + B, umax=1.0)
+        st = s.init(dev(u0), dev(v0), dev(u0 + 0.5))
+        out = torch.empty(B, n, n, device='cuda')
+        s.scalar_diagnostics(st), s.scalar(st, out=out)
+        torch.cuda.synchronize()
+        td, tf = [], []
+        for _ in range(args.reps):
+            td.append(event_ms(lambda: [s.scalar_diagnostics(st) for _ in range(10)]))
+            tf.append(event_ms(lambda: [s.scalar(st, out=out) for _ in range(10)]))
+        d = dict(nx=n, ny=n, batch=B, scalar_diagnostics=stats(td, 10), scalar=stats(tf, 10))
+        rec['calls'].append(d)
+        print(json.dumps(d), flush=True)
+    os.makedirs(args.outdir, exist_ok=True)
+    with open(os.path.join(args.outdir, 'pspec_scalar_run.json'), 'w') as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('outdir')
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=None, help='steps per timing (default 20; 100 with --scalar)')
     ap.add_argument('--reps', type=int, default=None)
     ap.add_argument('--forced', action='store_true', help='time the forced step and the diagnostics instead (see the module note)')
-    ap.add_argument('--commit', default='unknown', help='recorded in the --forced record')
+    ap.add_argument('--scalar', action='store_true', help='time the step with a passive scalar instead (see the module note)')
+    ap.add_argument('--commit', default='unknown', help='recorded in the --forced and --scalar records')
     args = ap.parse_args()
+    if args.forced and args.scalar:
+        ap.error('--forced and --scalar are two runs')
     if args.reps is None:
-        args.reps = 7 if args.forced else 5
+        args.reps = 7 if args.forced or args.scalar else 5
+    if args.steps is None:
+        args.steps = 100 if args.scalar else 20
     torch.cuda.set_device(0)
     if args.forced:
         return forced_main(args)
+    if args.scalar:
+        return scalar_main(args)
     rec = dict(device=torch.cuda.get_device_name(0), steps=args.steps, reps=args.reps, cases=[])
     for n, B in CASES:
         s = PeriodicSolver(n, n, 1e-3, 1.0, 1e-3)
