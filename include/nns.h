@@ -467,6 +467,31 @@ int nns_spec_ns_step_scalar_f32(float* what, float* that, const float* mean, con
  * so that d variance / dt = -(gx flux_x + gy flux_y) - dissipation.  float64 sums in a fixed order (no atomics); no workspace; one launch. */
 int nns_spec_ns_scalar_diag_f32(const float* what, const float* that, double* out, int batch, int nx, int ny, double Lx, double Ly,
                                 double kappa, void* stream);
+/* Shell spectra and spectral transfers (restatement: tests/pspec_spectrum_oracle.py).  Shells of width dk = min(2 pi / Lx, 2 pi / Ly) centred
+ * on k_s = s dk: the stored mode (m_x, j) belongs to shell s = floor(|k| / dk + 1/2), in float64; nshell = the shell of the band's corner
+ * (|m_x| = (nx - 1) / 3, j = my1 - 1) + 1, so an elongated box has many shells.  Shell 0 holds the (0, 0) mode alone, which contributes
+ * nothing.  Every per-shell number is the sum over the shell's stored modes of wt (...) / (nx ny)^2, wt as in nns_spec_ns_diag_f32.
+ * nns_spec_ns_shells: host only.  NNS_ERR_INVALID_ARG for a NULL pointer or a bad Lx, Ly; NNS_ERR_UNSUPPORTED for the axes. */
+int nns_spec_ns_shells(int nx, int ny, double Lx, double Ly, int* nshell, double* dk);
+/* out [batch][4][nshell] float64 (device) = per grid and shell, from what, that (NULL: no scalar) and ghat, gbatch as in nns_spec_ns_diag_f32:
+ *     E = 1/2 sum wt |w^|^2 / |k|^2,   Z = 1/2 sum wt |w^|^2,   F = sum wt Re(psi^ conj g^),   V = 1/2 sum wt |theta^|^2 (k != 0)
+ * whose sums over the shells are the E, Z, P of nns_spec_ns_diag_f32 and the variance of nns_spec_ns_scalar_diag_f32; a row without its source
+ * (F without ghat, V without that) is zeros.  One launch, one wave per (grid, shell), float64 sums in a fixed order (no atomics): a grid's
+ * numbers repeat bitwise and depend neither on the batch nor on the grid's place in it.  No workspace, no allocation, no host
+ * synchronisation (capturable).  NNS_ERR_INVALID_ARG for a NULL what or out, batch < 1, a bad gbatch, Lx, Ly, or an nshell that is not
+ * nns_spec_ns_shells'; NNS_ERR_UNSUPPORTED for the axes. */
+int nns_spec_ns_spectrum_f32(const float* what, const float* that, const float* ghat, int gbatch, double* out, int nshell, int batch, int nx,
+                             int ny, double Lx, double Ly, void* stream);
+/* out [batch][3][nshell] float64 (device) = the nonlinear transfers into every shell, from ONE evaluation of the step's dealiased nonlinear
+ * term in the co-moving frame (U0 = V0 = 0: a uniform flow transfers nothing) and, for the scalar, without the mean gradient:
+ *     T_E = sum wt Re(conj w^ N^) / |k|^2,   T_Z = sum wt Re(conj w^ N^),   T_theta = sum wt Re(conj theta^ N_theta^) (k != 0; zeros with that == NULL)
+ * N^ = -M rfft2(u w_x + v w_y), N_theta^ = -M_theta rfft2(u theta_x + v theta_y); each sums to 0 over the shells, to float32 rounding, and
+ * dE(s)/dt = T_E(s) + F(s) - 2 nu Z(s) - 2 drag E(s).  Four launches plus one that zeroes a corner of work: the step's stage-0 column pass
+ * and row pass, a column pass that forms the per-mode products, and the shell sums of nns_spec_ns_spectrum_f32 (same determinism).  what and
+ * that are only read.  work: nns_spec_ns_workspace bytes, nns_spec_ns_scalar_workspace with that; no allocation, no host synchronisation
+ * (capturable).  Errors as nns_spec_ns_spectrum_f32, plus NULL work and NNS_ERR_WORKSPACE for work_bytes below the size query. */
+int nns_spec_ns_transfer_f32(const float* what, const float* that, double* out, int nshell, void* work, size_t work_bytes, int batch, int nx,
+                             int ny, double Lx, double Ly, void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

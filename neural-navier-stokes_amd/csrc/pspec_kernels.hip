@@ -417,6 +417,160 @@ __global__ __launch_bounds__(kDiagT) void ps_scalar_diag_kernel(const float2* __
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- shell spectra and transfers
+// Shells of width dk = min(kx1, ky1) centred on s dk: the mode (m_x, j) belongs to shell s = floor(|k| / dk + 1/2), in float64 (restatement:
+// tests/pspec_spectrum_oracle.py).  nshell = shell of the band's corner + 1; shell 0 holds the (0, 0) mode alone, which contributes nothing.
+struct PsShells {
+    double kx1, ky1, dk, inv_n2;
+    int nshell, nx, my1, kmx;     // kmx = (nx - 1) / 3: the kept |m_x|
+};
+
+__device__ __forceinline__ int ps_shell_of(const PsShells& g, int m, int j) {
+    const double kx = g.kx1 * m, ky = g.ky1 * j;
+    return (int)floor(sqrt(kx * kx + ky * ky) / g.dk + 0.5);
+}
+
+// The smallest |m_x| in [0, kmx + 1] of row j whose shell is >= sh: an estimate from the radius r = (sh - 1/2) dk, then fixed with the
+// predicate that classifies a mode (ps_shell_of is monotone in |m_x|), so a mode is counted in exactly the shell the predicate names.
+__device__ __forceinline__ int ps_first_in_shell(const PsShells& g, int j, int sh) {
+    const double r = (sh - 0.5) * g.dk, ky = g.ky1 * j, t = r * r - ky * ky;
+    int m = r > 0. && t > 0. ? (int)fmin(sqrt(t) / g.kx1, (double)(g.kmx + 1)) : 0;
+    while (m > 0 && ps_shell_of(g, m - 1, j) >= sh) --m;
+    while (m <= g.kmx && ps_shell_of(g, m, j) < sh) ++m;
+    return m;
+}
+
+// out[b][Q][nshell] (float64) = per-shell sums of a per-mode value over the stored half spectrum [B][my1][nx], weight 1 on the j = 0 line and
+// 2 on j > 0, normalised by (nx ny)^2.  ONE WAVE per (grid, shell): its lanes stride over the rows j that the annulus can reach; on a row
+// the lane walks the |m_x| interval of the annulus (ps_first_in_shell) in ascending order, +m_x then -m_x, summing in float64; then a fixed
+// wave64 shuffle tree.  Every kept mode is read exactly once, by the wave of its shell; no atomics and no partials shared between waves, so
+// a grid's numbers repeat bitwise and depend neither on the batch, nor on the grid's place in it, nor on the launch geometry (which only
+// decides which wave takes which (grid, shell)).  The last shell also takes whatever the predicate puts beyond it (nothing, unless the
+// corner's shell differs by a rounding from the host's count), so the shells always sum to the totals of ps_diag_kernel.
+//   TRANSFER = false: Q = 4, (E, Z, F, V) from w^ (a), theta^ (b, or NULL: V = 0) and g^ (c, or NULL: F = 0; cshared: one for the batch)
+//   TRANSFER = true:  Q = 3, (T_E, T_Z, T_theta) from the real modal fields Re(conj w^ N^) (a) and Re(conj theta^ N_theta^) (b, or NULL)
+template <bool TRANSFER>
+__global__ __launch_bounds__(kT) void ps_shell_kernel(const void* __restrict__ a, const void* __restrict__ b, const void* __restrict__ c, int cshared,
+                                                      double* __restrict__ out, PsShells g, long nunits) {
+    constexpr int Q = TRANSFER ? 3 : 4;
+    const int lane = threadIdx.x % kWave;
+    const long per = (long)g.my1 * g.nx;
+    for (long u = (long)blockIdx.x * kW + threadIdx.x / kWave; u < nunits; u += (long)gridDim.x * kW) {
+        const long gb = u / g.nshell;
+        const int s = (int)(u % g.nshell);
+        const size_t base = (size_t)gb * per;
+        // rows beyond (s + 1/2) dk / ky1 cannot reach the shell (one row of slack: the predicate decides)
+        const double jtop = ((s + 0.5) * g.dk) / g.ky1 + 1.0;
+        const int jend = s == g.nshell - 1 || jtop >= (double)g.my1 ? g.my1 : (int)jtop + 1;
+        double acc[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) acc[q] = 0.;
+        for (int j = lane; j < jend; j += kWave) {
+            const int m0 = ps_first_in_shell(g, j, s);
+            const int m1 = s == g.nshell - 1 ? g.kmx + 1 : ps_first_in_shell(g, j, s + 1);
+            const double ky = g.ky1 * j, wt = j == 0 ? 1. : 2.;
+            const size_t rowb = base + (size_t)j * g.nx;
+            for (int m = m0; m < m1; ++m) {
+                if ((m | j) == 0) continue;
+                const double kx = g.kx1 * m, ik2 = 1. / (kx * kx + ky * ky);
+                for (int sg = 0; sg < (m == 0 ? 1 : 2); ++sg) {
+                    const size_t q = rowb + (sg == 0 ? m : g.nx - m);
+                    if constexpr (TRANSFER) {
+                        const double tw = static_cast<const float*>(a)[q];
+                        acc[0] += wt * tw * ik2;
+                        acc[1] += wt * tw;
+                        if (b) acc[2] += wt * static_cast<const float*>(b)[q];
+                    } else {
+                        const float2 w = static_cast<const float2*>(a)[q];
+                        const double ww = (double)w.x * w.x + (double)w.y * w.y;
+                        acc[0] += wt * ww * ik2;
+                        acc[1] += wt * ww;
+                        if (c) {
+                            const float2 f = static_cast<const float2*>(c)[cshared ? q - base : q];
+                            acc[2] += wt * ik2 * ((double)w.x * f.x + (double)w.y * f.y);      // Re(psi^ conj g^)
+                        }
+                        if (b) {
+                            const float2 d = static_cast<const float2*>(b)[q];
+                            acc[3] += wt * ((double)d.x * d.x + (double)d.y * d.y);
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int d = kWave / 2; d > 0; d >>= 1) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) acc[q] += __shfl_xor(acc[q], d, kWave);
+        }
+        if (lane == 0) {
+            double* o = out + (size_t)gb * Q * g.nshell + s;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const double half = !TRANSFER && q != 2 ? 0.5 : 1.;          // E, Z and V carry the 1/2 of a quadratic mean
+                o[(size_t)q * g.nshell] = half * acc[q] * g.inv_n2;
+            }
+        }
+    }
+}
+
+// The column pass of a transfer evaluation: tiling, LDS staging and forward transform of stages S >= 1 of ps_col_kernel; in place of the
+// Lawson update it forms, per stored mode, Re(conj w^ N^) with N^ = -M P^ (the step's mask: `keep` as in pspec_col_pass.inc) and, SCALAR,
+// Re(conj theta^ N_theta^) from Ph's second field, and writes them as float32 modal fields Tw, Tt [B][my1][nx].  It writes neither W nor Th.
+template <int N, bool SCALAR>
+__global__ __launch_bounds__(kT) void ps_transfer_kernel(const float2* __restrict__ Ph, const float2* __restrict__ W, const float2* __restrict__ Th,
+                                                         float* __restrict__ Tw, float* __restrict__ Tt, PsArgs a) {
+    using L = PsLds<N>;
+    constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const cf* tab = ps_tables<N>(smem);
+    unsigned char* lines = smem + L::TAB_BYTES;
+    const int my1 = a.my1;
+    const long ntiles = (a.nlines + CW - 1) / CW;
+    for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int tx = threadIdx.x;
+        const int wave = tx / kWave, lane = tx % kWave, sub = lane / TPF, tv = lane % TPF;
+        const int line = wave * L::FPW + sub;
+        cf* xb = reinterpret_cast<cf*>(lines + (size_t)line * L::LINE_BYTES);
+        const float* mine = reinterpret_cast<const float*>(xb) + (line % L::SKEW_MOD) * L::SKEW_DW;
+        const int cc = tx % CW, cr = tx / CW;
+        float* cp = reinterpret_cast<float*>(lines + (size_t)cc * L::LINE_BYTES) + (cc % L::SKEW_MOD) * L::SKEW_DW;
+        const long scol = t * CW + cc;
+        const bool sok = scol < a.nlines;
+        const size_t sbase = sok ? (size_t)(scol / my1) * N * my1 + (size_t)(scol % my1) : 0;     // (b, i = 0, j) in [b][i][j]
+        const long lcol = t * CW + line;
+        const bool lok = lcol < a.nlines;
+        const int lj = lok ? (int)(lcol % my1) : 0;
+        const size_t wbase = (size_t)(lok ? lcol : 0) * N;
+        static_for<0, SCALAR ? 2 : 1>([&](auto fld) {
+            constexpr bool TH = decltype(fld)::value == 1;
+            const float2* ph = TH ? Ph + a.fstride : Ph;
+            const float2* Ws = TH ? Th : W;
+            float* To = TH ? Tt : Tw;
+            for (int r = cr; r < N; r += RPI) {
+                const float2 v = sok ? ph[sbase + (size_t)r * my1] : make_float2(0.f, 0.f);
+                cp[2 * r] = v.x; cp[2 * r + 1] = v.y;
+            }
+            __syncthreads();
+            cf z[16];
+#pragma unroll
+            for (int m = 0; m < 16; ++m) z[m] = {mine[2 * (tv + TPF * m)], mine[2 * (tv + TPF * m) + 1]};
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            fft_line<float, N, false>(z, tab, tab + N / 2, xb, tv);
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const int e = tv + TPF * m;
+                const int mx = m < 8 ? e : e - N;
+                const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (TH || (mx | lj) != 0);
+                const float2 w = lok ? Ws[wbase + e] : make_float2(0.f, 0.f);
+                const float v = keep ? -fmaf(w.x, z[m].x, w.y * z[m].y) : 0.f;              // Re(conj w^ N^), N^ = -P^
+                if (lok) To[wbase + e] = v;
+            }
+            __syncthreads();                        // the next staging overwrites line images other waves may still read
+        });
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- host side
 inline int kept_y(int ny) { return (ny - 1) / 3 + 1; }
 
@@ -510,7 +664,124 @@ int check_common(const char* what, int batch, int nx, int ny, double Lx, double 
 
 inline unsigned pw_grid(long n) { return capped_grid((n + 255) / 256, 4096); }
 
+// dk and the shell count of a box: the shell of the band's corner (|m_x| = (nx - 1) / 3, j = my1 - 1) + 1, by the device's predicate
+PsShells shells_of(int nx, int ny, double Lx, double Ly) {
+    PsShells g{};
+    g.kx1 = 2.0 * M_PI / Lx;
+    g.ky1 = 2.0 * M_PI / Ly;
+    g.dk = g.kx1 < g.ky1 ? g.kx1 : g.ky1;
+    const double n = (double)nx * ny;
+    g.inv_n2 = 1.0 / (n * n);
+    g.nx = nx;
+    g.my1 = kept_y(ny);
+    g.kmx = (nx - 1) / 3;
+    const double kx = g.kx1 * g.kmx, ky = g.ky1 * (g.my1 - 1);
+    g.nshell = (int)std::floor(std::sqrt(kx * kx + ky * ky) / g.dk + 0.5) + 1;
+    return g;
+}
+
+// box and axes: what every shell call checks first
+int check_box(const char* what, int nx, int ny, double Lx, double Ly) {
+    if (!(Lx > 0) || !(Ly > 0) || !std::isfinite(Lx) || !std::isfinite(Ly))
+        return fail(NNS_ERR_INVALID_ARG, "%s: Lx = %g, Ly = %g must be positive and finite", what, Lx, Ly);
+    if (!pow2_in_range(nx) || !pow2_in_range(ny))
+        return fail(NNS_ERR_UNSUPPORTED, "%s: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", what, nx, ny);
+    return NNS_OK;
+}
+
+// box, axes, then the shell count: what the spectrum and transfer calls check before they look at a workspace
+int check_shells(const char* what, int nx, int ny, double Lx, double Ly, int nshell, PsShells* g) {
+    if (int rc = check_box(what, nx, ny, Lx, Ly)) return rc;
+    *g = shells_of(nx, ny, Lx, Ly);
+    if (nshell != g->nshell)
+        return fail(NNS_ERR_INVALID_ARG, "%s: nshell = %d, this box has %d shells (nns_spec_ns_shells)", what, nshell, g->nshell);
+    return NNS_OK;
+}
+
+// one wave per (grid, shell): the grid only decides which wave takes which
+template <bool TRANSFER>
+int launch_shells(const void* a, const void* b, const void* c, int cshared, double* out, const PsShells& g, int batch, hipStream_t s) {
+    const long nunits = (long)batch * g.nshell;
+    hipLaunchKernelGGL(ps_shell_kernel<TRANSFER>, dim3(capped_grid((nunits + kW - 1) / kW, 8 * kGridCap)), dim3(kT), 0, s, a, b, c, cshared, out, g,
+                       nunits);
+    return check_launch(TRANSFER ? "spec_ns_transfer shells" : "spec_ns_spectrum");
+}
+
+template <int N>
+int launch_transfer(const float2* Ph, const float2* W, const float2* Th, float* Tw, float* Tt, const PsArgs& a, hipStream_t s) {
+    const dim3 grid(grid_of(a.nlines, PsLds<N>::LINES));
+    if (Th) {
+        constexpr auto kern = ps_transfer_kernel<N, true>;
+        if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+        hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, Ph, W, Th, Tw, Tt, a);
+        return check_launch("spec_ns_transfer scalar column pass");
+    }
+    constexpr auto kern = ps_transfer_kernel<N, false>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, Ph, W, Th, Tw, Tt, a);
+    return check_launch("spec_ns_transfer column pass");
+}
+
 }  // namespace
+
+NNS_API int nns_spec_ns_shells(int nx, int ny, double Lx, double Ly, int* nshell, double* dk) {
+    if (!nshell || !dk) return fail(NNS_ERR_INVALID_ARG, "spec_ns_shells: nshell and dk must be non-NULL");
+    if (int rc = check_box("spec_ns_shells", nx, ny, Lx, Ly)) return rc;
+    const PsShells g = shells_of(nx, ny, Lx, Ly);
+    *nshell = g.nshell;
+    *dk = g.dk;
+    return NNS_OK;
+}
+
+NNS_API int nns_spec_ns_spectrum_f32(const float* what, const float* that, const float* ghat, int gbatch, double* out, int nshell, int batch,
+                                     int nx, int ny, double Lx, double Ly, void* stream) {
+    if (!what || !out || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_spectrum: NULL pointer or batch < 1");
+    if (ghat ? (gbatch != 1 && gbatch != batch) : gbatch != 0)
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_spectrum: gbatch = %d must be 0 without ghat, 1 or batch = %d with it", gbatch, batch);
+    PsShells g;
+    if (int rc = check_shells("spec_ns_spectrum", nx, ny, Lx, Ly, nshell, &g)) return rc;
+    return launch_shells<false>(what, that, ghat, gbatch == 1 && batch > 1 ? 1 : 0, out, g, batch, as_stream(stream));
+}
+
+NNS_API int nns_spec_ns_transfer_f32(const float* what, const float* that, double* out, int nshell, void* work, size_t work_bytes_, int batch,
+                                     int nx, int ny, double Lx, double Ly, void* stream) {
+    if (!what || !out || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_transfer: NULL pointer or batch < 1");
+    PsShells g;
+    if (int rc = check_shells("spec_ns_transfer", nx, ny, Lx, Ly, nshell, &g)) return rc;
+    const size_t need = that ? scalar_work_bytes(batch, nx, ny) : work_bytes(batch, nx, ny);
+    if (work_bytes_ < need)
+        return fail(NNS_ERR_WORKSPACE, "spec_ns_transfer: workspace of %zu bytes, %zu needed (%s)", work_bytes_, need,
+                    that ? "nns_spec_ns_scalar_workspace" : "nns_spec_ns_workspace");
+    hipStream_t s = as_stream(stream);
+    const int my1 = g.my1;
+    const long fstride = (long)batch * nx * my1;
+    // the step's layout of work (A, [A_theta], G, Ph).  The accumulators are free here: the modal fields Re(conj w^ N^), Re(conj theta^ N_theta^)
+    // take the first half of A's and A_theta's slots (float32 against complex), the zero mean of the co-moving frame a corner of A's second half
+    float2* A = static_cast<float2*>(work);
+    float2* G = A + (that ? 2 : 1) * fstride;
+    float2* Ph = G + (that ? 6 : 4) * fstride;
+    float* Tw = reinterpret_cast<float*>(A);
+    float* Tt = that ? reinterpret_cast<float*>(A + fstride) : nullptr;
+    float* zero_mean = Tw + fstride;
+    void* zb[1] = {zero_mean};
+    const long zn[1] = {(long)(2 * batch * sizeof(float))};
+    if (int rc = zero_buffers(zb, zn, 1, s)) return rc;
+    const float2* W = reinterpret_cast<const float2*>(what);
+    const float2* Th = reinterpret_cast<const float2*>(that);
+    PsArgs ac{(long)batch * my1, fstride, my1, (float)g.kx1, (float)g.ky1, 0.f, 0.f, (float)(1.0 / ((double)nx * ny))};
+    PsArgs ar = ac;
+    ar.nlines = (long)batch * nx;
+    // stage 0 only reads W / Th (its signature is the step's: no const); the gradient of the scalar's row pass is 0: advection alone
+    const PsScalar scalar{const_cast<float2*>(Th), nullptr, 0.f};
+    const PsGrad grad{0.f, 0.f};
+    if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
+            return launch_col<decltype(n)::value, 0, false>(Ph, G, const_cast<float2*>(W), nullptr, zero_mean, ac, 1, nullptr, that ? &scalar : nullptr, s);
+        }))
+        return rc;
+    if (int rc = dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, that ? &grad : nullptr, s); })) return rc;
+    if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_transfer<decltype(n)::value>(Ph, W, Th, Tw, Tt, ac, s); })) return rc;
+    return launch_shells<true>(Tw, Tt, nullptr, 0, out, g, batch, s);
+}
 
 NNS_API int nns_spec_ns_workspace(int batch, int nx, int ny, size_t* bytes) {
     if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);

@@ -1041,6 +1041,55 @@ def spec_ns_scalar_diag(what, that, ny, Lx, Ly, kappa, out=None):
     return out
 
 
+# shell spectra and spectral transfers of the periodic solver (nns_spec_ns_shells, nns_spec_ns_spectrum_f32, nns_spec_ns_transfer_f32)
+def spec_ns_shells(nx, ny, Lx, Ly):
+    """(nshell, dk) of the box: shells of width dk = min(2 pi / Lx, 2 pi / Ly) centred on s dk, s = 0 .. nshell - 1 (host only)."""
+    n, dk = ctypes.c_int(0), ctypes.c_double(0.0)
+    check(_lib.lib().nns_spec_ns_shells(int(nx), int(ny), float(Lx), float(Ly), ctypes.byref(n), ctypes.byref(dk)), 'nns_spec_ns_shells')
+    return n.value, dk.value
+
+
+def _spec_ns_shell_out(who, out, B, Q, S, device):
+    if out is None:
+        return torch.empty((B, Q, S), dtype=torch.float64, device=device)
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (B, Q, S) and out.is_contiguous()
+            and out.device == device):
+        raise ValueError("%s: out must be a contiguous float64 [%d, %d, %d] tensor on the state's device" % (who, B, Q, S))
+    return out
+
+
+def spec_ns_spectrum(what, that, ghat, ny, Lx, Ly, out=None):
+    """float64 [B, 4, nshell]: per grid and shell the energy, enstrophy, injection Re(psi^ conj g^) (zeros with ghat None) and scalar variance
+    (zeros with that None); their sums over the shells are spec_ns_diag's and spec_ns_scalar_diag's numbers."""
+    B, my1, nx = _spec_ns_state('spec_ns_spectrum', what, None, None, ny)
+    if that is not None:
+        _spec_ns_same('spec_ns_spectrum', that, what)
+    gbatch = _spec_ns_force('spec_ns_spectrum', ghat, what)
+    S = spec_ns_shells(nx, ny, Lx, Ly)[0]
+    out = _spec_ns_shell_out('spec_ns_spectrum', out, B, 4, S, what.device)
+    check(_lib.lib().nns_spec_ns_spectrum_f32(_p(what), None if that is None else _p(that), _p(ghat) if gbatch else None, gbatch, _p(out), S, B,
+                                              nx, int(ny), float(Lx), float(Ly), _stream()), 'nns_spec_ns_spectrum_f32')
+    return out
+
+
+def spec_ns_transfer(what, that, work, ny, Lx, Ly, out=None):
+    """float64 [B, 3, nshell]: the nonlinear transfer of energy, enstrophy and scalar variance (zeros with that None) into every shell, from
+    one evaluation of the step's nonlinear term in the co-moving frame.  what and that are only read; work: spec_ns_workspace bytes
+    (spec_ns_scalar_workspace with that).  No allocation beyond out, no host synchronisation: capturable with out given."""
+    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
+        raise TypeError("spec_ns_transfer: work must be a contiguous uint8 device tensor")
+    B, my1, nx = _spec_ns_state('spec_ns_transfer', what, None, None, ny)
+    if work.device != what.device:
+        raise ValueError("spec_ns_transfer: state tensors on different devices")
+    if that is not None:
+        _spec_ns_same('spec_ns_transfer', that, what)
+    S = spec_ns_shells(nx, ny, Lx, Ly)[0]
+    out = _spec_ns_shell_out('spec_ns_transfer', out, B, 3, S, what.device)
+    check(_lib.lib().nns_spec_ns_transfer_f32(_p(what), None if that is None else _p(that), _p(out), S, _p(work), work.numel(), B, nx, int(ny),
+                                              float(Lx), float(Ly), _stream()), 'nns_spec_ns_transfer_f32')
+    return out
+
+
 # ----------------------------------------------------------------------------- physics-informed loss head
 _PINN_WS = {}
 

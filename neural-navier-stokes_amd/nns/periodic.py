@@ -18,7 +18,8 @@ otherwise, 2 = float64 forward transforms always.
 ``PeriodicSolver`` produces the trajectories such a residual measures: a pseudo-spectral solver of the same equations on the same box
 (csrc/pspec_kernels.hip; scheme in DESIGN.md and tests/pspec_oracle.py), optionally with a steady body force and a linear drag
 (tests/pspec_forced_oracle.py) and with a passive scalar -- temperature, dye -- that the same fused step transports
-(tests/pspec_scalar_oracle.py).
+(tests/pspec_scalar_oracle.py).  Its ``spectrum`` and ``transfer`` give energy, enstrophy, injection, scalar variance and the nonlinear
+transfers by wavenumber shell (tests/pspec_spectrum_oracle.py).
 """
 import collections
 import math
@@ -107,6 +108,14 @@ def _count(name, n, minimum):
 
 Diagnostics = collections.namedtuple('Diagnostics', ['energy', 'enstrophy', 'power_in'])
 ScalarDiagnostics = collections.namedtuple('ScalarDiagnostics', ['variance', 'dissipation', 'flux_x', 'flux_y'])
+Spectrum = collections.namedtuple('Spectrum', ['k', 'energy', 'enstrophy', 'injection', 'variance'])
+Transfer = collections.namedtuple('Transfer', ['k', 'energy', 'enstrophy', 'variance'])
+
+
+def flux(t):
+    """The spectral flux Pi(s) = -sum_{s' <= s} T(s') of a transfer T [..., S] (a field of ``Transfer``): the rate at which the nonlinear term
+    carries the quantity out of the shells <= s, positive for a cascade towards small scales; Pi(S - 1) = 0 to rounding."""
+    return -torch.cumsum(t, dim=-1)
 
 
 class PeriodicState(object):
@@ -153,7 +162,14 @@ class PeriodicSolver(object):
     the gradient sustains.  theta is band-limited like the flow but keeps its grid mean, d<theta>/dt = -G . (U0, V0); the drag does not act
     on it.  It rides in the flow's launches (still 8 per step), each RK stage with that stage's own velocity, and the flow evolves bitwise
     as without it.  ``scalar(state)`` gives theta, ``scalar_diagnostics(state)`` its variance budget.  A state without a scalar takes exactly
-    the calls it takes on a solver without ``kappa``."""
+    the calls it takes on a solver without ``kappa``.
+
+    By wavenumber: the stored modes are binned into shells of width dk = min(2 pi / Lx, 2 pi / Ly) centred on k_s = s dk (``shells()``; an
+    elongated box has many).  ``spectrum(state)`` gives energy E(s), enstrophy Z(s), the force's injection F(s) and the scalar's variance V(s),
+    whose sums over the shells are the numbers of ``diagnostics`` and ``scalar_diagnostics``; ``transfer(state)`` the nonlinear transfers T(s)
+    of energy, enstrophy and scalar variance from one evaluation of the step's own dealiased nonlinear term (each sums to zero), ``flux`` their
+    cumulative form Pi(s), and ``energy_budget(state)`` dE(s)/dt = T_E + F - 2 nu Z - 2 drag E.  All float64, summed on the device in a fixed
+    order.  The spectrum of arbitrary fields -- a model's prediction, say -- is ``solver.spectrum(solver.init(u, v))``."""
 
     def __init__(self, nx, ny, dt, rho, nu, Lx=2 * math.pi, Ly=2 * math.pi, drag=0.0, kappa=None, scalar_gradient=(0.0, 0.0)):
         self.nx, self.ny = _pow2_axis('nx', nx), _pow2_axis('ny', ny)
@@ -329,6 +345,37 @@ class PeriodicSolver(object):
         self._scalar_state(state)
         out = ops.spec_ns_scalar_diag(state.what, state.that, self.ny, self.Lx, self.Ly, self.kappa)
         return ScalarDiagnostics(out[:, 0], out[:, 1], out[:, 2], out[:, 3])
+
+    # ---- by wavenumber
+    def shells(self):
+        """(k, dk): the shell centres k_s = s dk, a float64 numpy array [S], and the shell width dk = min(2 pi / Lx, 2 pi / Ly).  A stored
+        mode belongs to shell floor(|k| / dk + 1/2); S - 1 is the shell of the kept band's corner and shell 0 is empty."""
+        S, dk = ops.spec_ns_shells(self.nx, self.ny, self.Lx, self.Ly)
+        return dk * np.arange(S, dtype=np.float64), dk
+
+    def spectrum(self, state):
+        """Spectrum(k, energy, enstrophy, injection, variance): k as ``shells()``; the others float64 [B, S] device tensors, per shell the
+        sums that ``diagnostics`` (energy, enstrophy, power_in) and ``scalar_diagnostics`` (variance) take over the whole band.  injection is
+        zeros without a force; variance is None for a state without a scalar.  Only reads the state."""
+        self._state(state)
+        out = ops.spec_ns_spectrum(state.what, state.that, self._force_of(state), self.ny, self.Lx, self.Ly)
+        return Spectrum(self.shells()[0], out[:, 0], out[:, 1], out[:, 2], None if state.that is None else out[:, 3])
+
+    def transfer(self, state):
+        """Transfer(k, energy, enstrophy, variance), float64 [B, S] device tensors: the rate at which the nonlinear term moves energy,
+        enstrophy and scalar variance INTO every shell, T_Z(s) = sum Re(conj w^ N^), T_E with 1 / |k|^2, T_theta(s) = sum Re(conj theta^ N_theta^)
+        (None without a scalar), N^ the step's dealiased nonlinear term evaluated once in the co-moving frame (the mean flow transfers nothing)
+        and, for the scalar, advection alone (no mean gradient).  Each sums to zero over the shells, to float32 rounding.  Uses ``state.work``;
+        leaves what, that, mean and steps untouched."""
+        self._state(state)
+        out = ops.spec_ns_transfer(state.what, state.that, state.work, self.ny, self.Lx, self.Ly)
+        return Transfer(self.shells()[0], out[:, 0], out[:, 1], None if state.that is None else out[:, 2])
+
+    def energy_budget(self, state):
+        """dE(s)/dt = T_E(s) + F(s) - 2 nu Z(s) - 2 drag E(s), float64 [B, S]: the right-hand side of the energy equation per shell (the
+        viscous term is exact per shell: |k|^2 E_mode = Z_mode)."""
+        sp, tr = self.spectrum(state), self.transfer(state)
+        return tr.energy + sp.injection - 2.0 * self.nu * sp.enstrophy - 2.0 * self.drag * sp.energy
 
     def fields(self, state, out=None):
         """(u, v, p) float32 [B, nx, ny] of the state (into ``out`` if given)."""
