@@ -492,6 +492,31 @@ int nns_spec_ns_spectrum_f32(const float* what, const float* that, const float* 
  * (capturable).  Errors as nns_spec_ns_spectrum_f32, plus NULL work and NNS_ERR_WORKSPACE for work_bytes below the size query. */
 int nns_spec_ns_transfer_f32(const float* what, const float* that, double* out, int nshell, void* work, size_t work_bytes, int batch, int nx,
                              int ny, double Lx, double Ly, void* stream);
+/* Boussinesq buoyancy (restatement: tests/pspec_buoyant_oracle.py): the scalar acts on the flow through b theta', b = (bx, by) uniform and
+ * theta' = theta - <theta>:
+ *     u_t + (u . grad) u = -grad p / rho + nu lap u - drag (u - <u>) + f_s + b theta'
+ *     w_t + u w_x + v w_y = nu lap w - drag w + g + (by theta_x - bx theta_y)
+ * Only the periodic fluctuation is buoyant: b <theta> would only accelerate the frame and the background G . x is taken as hydrostatic (its
+ * curl, a constant, cannot exist on a periodic box), so both are dropped.  (w^, theta^) is one system under the same Lawson RK4 with the term
+ * explicit, N_w = -M rfft2(u w_x + v w_y) + g^ + M (i kx by - i ky bx) theta^ with every stage's own theta^; L_w, L_theta and N_theta are those
+ * of nns_spec_ns_step_scalar_f32.  The term rides in the row pass: still 8 launches per step plus one per call, no allocation, no host
+ * synchronisation (capturable).  bx == by == 0 makes exactly the calls of nns_spec_ns_step_scalar_f32.  NNS_ERR_INVALID_ARG for that == NULL
+ * or a non-finite bx, by; otherwise the errors of nns_spec_ns_step_scalar_f32. */
+int nns_spec_ns_step_buoyant_f32(float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work, size_t work_bytes,
+                                 int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa, double gx,
+                                 double gy, double bx, double by, int nsteps, void* stream);
+/* u, v as nns_spec_ns_fields_f32 and the pressure of the buoyant flow: lap p = rho (2 (u_x v_y - u_y v_x) + b . grad theta), that is
+ * p^ = p^ of nns_spec_ns_fields_f32 - rho i (k . b) theta^ / |k|^2 on the kept modes, zero mean.  work: nns_spec_ns_scalar_workspace bytes.
+ * Errors as nns_spec_ns_fields_f32, plus that == NULL and a non-finite bx, by. */
+int nns_spec_ns_fields_buoyant_f32(const float* what, const float* that, const float* mean, float* u, float* v, float* p, void* work,
+                                   size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly, double rho, double bx, double by,
+                                   void* stream);
+/* out [batch][nshell] float64 (device) = the buoyancy production per shell, B(s) = sum wt Re(conj(bx u^ + by v^) theta^) / (nx ny)^2 with
+ * u^ = i ky psi^, v^ = -i kx psi^; its sum over the shells is bx flux_x + by flux_y of nns_spec_ns_scalar_diag_f32 and
+ * dE(s)/dt = T_E(s) + F(s) - 2 nu Z(s) - 2 drag E(s) + B(s).  One launch, the shells, order of summation and determinism of
+ * nns_spec_ns_spectrum_f32; its errors, plus that == NULL and a non-finite bx, by. */
+int nns_spec_ns_buoyancy_spectrum_f32(const float* what, const float* that, double* out, int nshell, int batch, int nx, int ny, double Lx,
+                                      double Ly, double bx, double by, void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

@@ -31,6 +31,13 @@
 // accumulator and prepares i kx theta^, i ky theta^ as G fields 4 and 5.  The vorticity's arithmetic is the unscalared kernel's, so w^ is
 // bitwise what it is without a scalar; SCALAR = false is the present code, argument list included.
 //
+// Buoyancy (nns_spec_ns_step_buoyant_f32; restatement: tests/pspec_buoyant_oracle.py): the scalar acts on the flow through b theta', which adds
+// by theta_x - bx theta_y to the vorticity equation, N^ += M (i kx by - i ky bx) theta^ with every stage's own theta^.  BUOYANT = true (SCALAR only) is
+// the row pass's: the kept y-modes of theta_x and theta_y of a row ARE G fields 4 and 5 of that row (x-physical, y-spectral, scaled by 1 / (nx ny)),
+// and the combination is linear, so -ny (by G4 - bx G5) is added to the forward-transformed product just before it is stored to Ph (ny: an
+// unnormalised inverse then forward transform along y).  No further transform, no further line live across one; the column pass is untouched.
+// b = 0 launches the passive kernels.  ps_pressure_buoyant_kernel adds -rho i (k . b) theta^ / |k|^2 to p^ (div (b theta') != 0).
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 #include "nns_common.h"
 #include "fft_lds.h"
@@ -69,6 +76,10 @@ struct PsScalar {         // the extra argument of the SCALAR column kernels
     float hkdt;           // -kappa dt / 2
 };
 struct PsGrad { float gx, gy; };      // the extra argument of the SCALAR row kernel: the uniform mean gradient
+struct PsBuoyGrad {                   // that of the BUOYANT row kernel: the gradient and the buoyancy as the coefficients of G fields 4 and 5
+    float gx, gy;
+    float c4, c5;                     // -ny by, ny bx
+};
 template <typename T> __device__ __forceinline__ T only(T t) { return t; }     // the one element of a SCALAR kernel's argument pack
 
 struct PsArgs {
@@ -98,9 +109,11 @@ __device__ __forceinline__ cf* ps_tables(unsigned char* smem) {
 // ---------------------------------------------------------------------------------------------------- row pass (axis y)
 // SCALAR: a third inverse transform (theta_x + i theta_y, G fields 4 and 5) after the vorticity's product has left, so two complex lines
 // are live at a time, as without it; the second product goes to Ph's second field.
-template <int N, bool SCALAR = false, typename... Grad>
+// BUOYANT (SCALAR only): c4 G4 + c5 G5 of the row's kept y-modes joins the vorticity's transformed product on its way to Ph.
+template <int N, bool SCALAR = false, bool BUOYANT = false, typename... Grad>
 __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a, Grad... grad) {
     static_assert(sizeof...(Grad) == (SCALAR ? 1 : 0), "the gradient is the SCALAR kernel's argument");
+    static_assert(SCALAR || !BUOYANT, "buoyancy needs the scalar");
     using L = PsLds<N>;
     constexpr int TPF = L::TPF;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -160,11 +173,23 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
             fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
             store(zu, Ph + (size_t)row * my1);
         } else {
-            const PsGrad gr = only(grad...);
+            const auto gr = only(grad...);
 #pragma unroll
             for (int m = 0; m < 16; ++m) zw[m] = {zu[m].x * zw[m].x + zu[m].y * zw[m].y, 0.f};    // u w_x + v w_y: u, v stay
             __builtin_amdgcn_sched_barrier(0);
             fft_line<float, N, false>(zw, tab, tab + N / 2, xb, tid);
+            if constexpr (BUOYANT) {                             // -ny (by theta_x - bx theta_y)^ on the kept modes: the loads of load2 below
+                const float2* t4 = g0 + 4 * a.fstride;
+                const float2* t5 = g0 + 5 * a.fstride;
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    const int e = tid + TPF * m;
+                    if (e < my1) {
+                        const float2 p = t4[e], q = t5[e];
+                        zw[m] = {fmaf(gr.c4, p.x, fmaf(gr.c5, q.x, zw[m].x)), fmaf(gr.c4, p.y, fmaf(gr.c5, q.y, zw[m].y))};
+                    }
+                }
+            }
             store(zw, Ph + (size_t)row * my1);
             __builtin_amdgcn_sched_barrier(0);
             load2(g0 + 4 * a.fstride, g0 + 5 * a.fstride, zw);   // theta_x + i theta_y
@@ -305,6 +330,27 @@ __global__ void ps_pressure_kernel(float2* __restrict__ qh, int batch, int nx, i
         const float kx = kx1 * (float)mx, ky = ky1 * (float)j, k2 = kx * kx + ky * ky;
         const float2 z = qh[q];
         qh[q] = keep ? make_float2(-z.x / k2, -z.y / k2) : make_float2(0.f, 0.f);
+    }
+}
+
+// the same with buoyancy: p^ = -M (q^ + i (k . rho b) theta^) / |k|^2, theta^ read from the compact T [B][my1][nx] (keep implies j < my1)
+__global__ void ps_pressure_buoyant_kernel(float2* __restrict__ qh, const float2* __restrict__ T, int batch, int nx, int ny, int my1, float kx1,
+                                           float ky1, float rbx, float rby) {
+    const long nh = ny / 2 + 1, per = (long)batch * nx * nh;
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < per; q += (long)gridDim.x * blockDim.x) {
+        const int j = (int)(q % nh), i = (int)((q / nh) % nx);
+        const long b = q / ((long)nx * nh);
+        const int mx = i < nx / 2 ? i : i - nx;
+        const bool keep = 3 * (mx < 0 ? -mx : mx) < nx && 3 * j < ny && (mx | j) != 0;
+        const float kx = kx1 * (float)mx, ky = ky1 * (float)j, k2 = kx * kx + ky * ky;
+        const float2 z = qh[q];
+        float2 o = make_float2(0.f, 0.f);
+        if (keep) {
+            const float2 t = T[((size_t)b * my1 + j) * nx + i];
+            const float kb = kx * rbx + ky * rby;
+            o = make_float2(-(z.x - kb * t.y) / k2, -(z.y + kb * t.x) / k2);
+        }
+        qh[q] = o;
     }
 }
 
@@ -513,6 +559,43 @@ __global__ __launch_bounds__(kT) void ps_shell_kernel(const void* __restrict__ a
     }
 }
 
+// out[b][nshell] (float64) = the buoyancy production per shell, B(s) = sum wt Re(conj(bx u^ + by v^) theta^) / (nx ny)^2 with u^ = i ky psi^,
+// v^ = -i kx psi^ from w^: Re(conj(i c psi^) theta^) = c Im(conj(psi^) theta^), c = bx ky - by kx.  ps_shell_kernel's sibling: its walk, its
+// order of summation and its shuffle tree (one wave per (grid, shell), float64, no atomics), so the same determinism; summed over the shells it
+// is bx flux_x + by flux_y of ps_scalar_diag_kernel.
+__global__ __launch_bounds__(kT) void ps_buoyancy_shell_kernel(const float2* __restrict__ W, const float2* __restrict__ T, double* __restrict__ out,
+                                                               PsShells g, long nunits, double bx, double by) {
+    const int lane = threadIdx.x % kWave;
+    const long per = (long)g.my1 * g.nx;
+    for (long u = (long)blockIdx.x * kW + threadIdx.x / kWave; u < nunits; u += (long)gridDim.x * kW) {
+        const long gb = u / g.nshell;
+        const int s = (int)(u % g.nshell);
+        const size_t base = (size_t)gb * per;
+        const double jtop = ((s + 0.5) * g.dk) / g.ky1 + 1.0;
+        const int jend = s == g.nshell - 1 || jtop >= (double)g.my1 ? g.my1 : (int)jtop + 1;
+        double acc = 0.;
+        for (int j = lane; j < jend; j += kWave) {
+            const int m0 = ps_first_in_shell(g, j, s);
+            const int m1 = s == g.nshell - 1 ? g.kmx + 1 : ps_first_in_shell(g, j, s + 1);
+            const double ky = g.ky1 * j, wt = j == 0 ? 1. : 2.;
+            const size_t rowb = base + (size_t)j * g.nx;
+            for (int m = m0; m < m1; ++m) {
+                if ((m | j) == 0) continue;
+                const double kxa = g.kx1 * m, ik2 = 1. / (kxa * kxa + ky * ky);
+                for (int sg = 0; sg < (m == 0 ? 1 : 2); ++sg) {
+                    const size_t q = rowb + (sg == 0 ? m : g.nx - m);
+                    const double kx = sg == 0 ? kxa : -kxa;
+                    const float2 w = W[q], d = T[q];
+                    acc += wt * (bx * ky - by * kx) * ik2 * ((double)w.x * d.y - (double)w.y * d.x);
+                }
+            }
+        }
+#pragma unroll
+        for (int d = kWave / 2; d > 0; d >>= 1) acc += __shfl_xor(acc, d, kWave);
+        if (lane == 0) out[(size_t)gb * g.nshell + s] = acc * g.inv_n2;
+    }
+}
+
 // The column pass of a transfer evaluation: tiling, LDS staging and forward transform of stages S >= 1 of ps_col_kernel; in place of the
 // Lawson update it forms, per stored mode, Re(conj w^ N^) with N^ = -M P^ (the step's mask: `keep` as in pspec_col_pass.inc) and, SCALAR,
 // Re(conj theta^ N_theta^) from Ph's second field, and writes them as float32 modal fields Tw, Tt [B][my1][nx].  It writes neither W nor Th.
@@ -576,12 +659,18 @@ inline int kept_y(int ny) { return (ny - 1) / 3 + 1; }
 
 inline unsigned grid_of(long work, long per) { return capped_grid((work + per - 1) / per, kGridCap); }
 
-// gr == nullptr: the unscalared kernel
+// gr == nullptr: the unscalared kernel; bu != nullptr (with gr): the buoyant one
 template <int N>
-int launch_row(const float2* G, float2* Ph, const PsArgs& a, const PsGrad* gr, hipStream_t s) {
+int launch_row(const float2* G, float2* Ph, const PsArgs& a, const PsGrad* gr, hipStream_t s, const PsBuoyGrad* bu = nullptr) {
     const dim3 grid(grid_of(a.nlines, PsLds<N>::LINES));
+    if (bu) {
+        constexpr auto kern = ps_row_kernel<N, true, true, PsBuoyGrad>;
+        if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+        hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a, *bu);
+        return check_launch("spec_ns buoyant row pass");
+    }
     if (gr) {
-        constexpr auto kern = ps_row_kernel<N, true, PsGrad>;
+        constexpr auto kern = ps_row_kernel<N, true, false, PsGrad>;
         if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a, *gr);
         return check_launch("spec_ns scalar row pass");
@@ -743,6 +832,19 @@ NNS_API int nns_spec_ns_spectrum_f32(const float* what, const float* that, const
     return launch_shells<false>(what, that, ghat, gbatch == 1 && batch > 1 ? 1 : 0, out, g, batch, as_stream(stream));
 }
 
+NNS_API int nns_spec_ns_buoyancy_spectrum_f32(const float* what, const float* that, double* out, int nshell, int batch, int nx, int ny, double Lx,
+                                              double Ly, double bx, double by, void* stream) {
+    if (!what || !that || !out || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_buoyancy_spectrum: NULL pointer or batch < 1");
+    if (!std::isfinite(bx) || !std::isfinite(by))
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_buoyancy_spectrum: the buoyancy (%g, %g) must be finite", bx, by);
+    PsShells g;
+    if (int rc = check_shells("spec_ns_buoyancy_spectrum", nx, ny, Lx, Ly, nshell, &g)) return rc;
+    const long nunits = (long)batch * g.nshell;
+    hipLaunchKernelGGL(ps_buoyancy_shell_kernel, dim3(capped_grid((nunits + kW - 1) / kW, 8 * kGridCap)), dim3(kT), 0, as_stream(stream),
+                       reinterpret_cast<const float2*>(what), reinterpret_cast<const float2*>(that), out, g, nunits, bx, by);
+    return check_launch("spec_ns_buoyancy_spectrum");
+}
+
 NNS_API int nns_spec_ns_transfer_f32(const float* what, const float* that, double* out, int nshell, void* work, size_t work_bytes_, int batch,
                                      int nx, int ny, double Lx, double Ly, void* stream) {
     if (!what || !out || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_transfer: NULL pointer or batch < 1");
@@ -807,16 +909,17 @@ NNS_API int nns_spec_ns_init_f32(const float* u, const float* v, float* what, fl
     return check_launch("spec_ns_init");
 }
 
-// The step of every entry point: ghat == NULL and drag == 0 launch the unforced kernels, that == NULL the unscalared ones.
+// The step of every entry point: ghat == NULL and drag == 0 launch the unforced kernels, that == NULL the unscalared ones, b == 0 the passive ones.
 static int spec_ns_step(const char* who, float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work,
                         size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa,
-                        double gx, double gy, int nsteps, void* stream) {
+                        double gx, double gy, double bx, double by, int nsteps, void* stream) {
     if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
     if (!(dt > 0) || !std::isfinite(dt) || !(nu >= 0) || !std::isfinite(nu) || nsteps < 0)
         return fail(NNS_ERR_INVALID_ARG, "%s: dt = %g must be > 0, nu = %g >= 0, nsteps = %d >= 0", who, dt, nu, nsteps);
     if (!(drag >= 0) || !std::isfinite(drag)) return fail(NNS_ERR_INVALID_ARG, "%s: drag = %g must be finite and >= 0", who, drag);
     if (!(kappa >= 0) || !std::isfinite(kappa) || !std::isfinite(gx) || !std::isfinite(gy))
         return fail(NNS_ERR_INVALID_ARG, "%s: kappa = %g must be finite and >= 0, the gradient (%g, %g) finite", who, kappa, gx, gy);
+    if (!std::isfinite(bx) || !std::isfinite(by)) return fail(NNS_ERR_INVALID_ARG, "%s: the buoyancy (%g, %g) must be finite", who, bx, by);
     if (ghat ? (gbatch != 1 && gbatch != batch) : gbatch != 0)
         return fail(NNS_ERR_INVALID_ARG, "%s: gbatch = %d must be 0 without ghat, 1 or batch = %d with it", who, gbatch, batch);
     if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work, work_bytes_, that != nullptr)) return rc;
@@ -838,8 +941,10 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
     const PsGrad grad{(float)gx, (float)gy};
     const PsScalar* sc = that ? &scalar : nullptr;
     const PsGrad* gr = that ? &grad : nullptr;
+    const PsBuoyGrad buoy{(float)gx, (float)gy, (float)(-(double)ny * by), (float)((double)ny * bx)};
+    const PsBuoyGrad* bu = that && (bx != 0.0 || by != 0.0) ? &buoy : nullptr;
     auto col = [&](int S, int emit) { return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, fc, sc, s); }); };
-    auto row = [&]() { return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, gr, s); }); };
+    auto row = [&]() { return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, gr, s, bu); }); };
     if (int rc = col(0, 1)) return rc;
     for (int k = 0; k < nsteps; ++k) {
         for (int S = 1; S <= 4; ++S) {
@@ -852,15 +957,15 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
 
 NNS_API int nns_spec_ns_step_f32(float* what, const float* mean, void* work, size_t work_bytes_, int batch, int nx, int ny, double Lx,
                                  double Ly, double dt, double nu, int nsteps, void* stream) {
-    return spec_ns_step("spec_ns_step", what, nullptr, mean, nullptr, 0, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, 0.0, 0.0, 0.0, 0.0, nsteps,
-                        stream);
+    return spec_ns_step("spec_ns_step", what, nullptr, mean, nullptr, 0, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0,
+                        nsteps, stream);
 }
 
 NNS_API int nns_spec_ns_step_forced_f32(float* what, const float* mean, const float* ghat, int gbatch, void* work, size_t work_bytes_,
                                         int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, int nsteps,
                                         void* stream) {
     return spec_ns_step("spec_ns_step_forced", what, nullptr, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, drag, 0.0, 0.0,
-                        0.0, nsteps, stream);
+                        0.0, 0.0, 0.0, nsteps, stream);
 }
 
 NNS_API int nns_spec_ns_step_scalar_f32(float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work,
@@ -868,7 +973,15 @@ NNS_API int nns_spec_ns_step_scalar_f32(float* what, float* that, const float* m
                                         double kappa, double gx, double gy, int nsteps, void* stream) {
     if (!that) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_scalar: NULL pointer or batch < 1");
     return spec_ns_step("spec_ns_step_scalar", what, that, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, drag, kappa, gx,
-                        gy, nsteps, stream);
+                        gy, 0.0, 0.0, nsteps, stream);
+}
+
+NNS_API int nns_spec_ns_step_buoyant_f32(float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work,
+                                         size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
+                                         double kappa, double gx, double gy, double bx, double by, int nsteps, void* stream) {
+    if (!that) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_buoyant: NULL pointer or batch < 1");
+    return spec_ns_step("spec_ns_step_buoyant", what, that, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, drag, kappa, gx,
+                        gy, bx, by, nsteps, stream);
 }
 
 NNS_API int nns_spec_ns_scalar_workspace(int batch, int nx, int ny, size_t* bytes) {
@@ -932,11 +1045,13 @@ NNS_API int nns_spec_ns_diag_f32(const float* what, const float* ghat, int gbatc
     return check_launch("spec_ns_diag");
 }
 
-NNS_API int nns_spec_ns_fields_f32(const float* what, const float* mean, float* u, float* v, float* p, void* work, size_t work_bytes_,
-                                   int batch, int nx, int ny, double Lx, double Ly, double rho, void* stream) {
-    if (!what || !mean || !u || !v || !p || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_fields: NULL pointer or batch < 1");
-    if (!std::isfinite(rho)) return fail(NNS_ERR_INVALID_ARG, "spec_ns_fields: rho = %g must be finite", rho);
-    if (int rc = check_common("spec_ns_fields", batch, nx, ny, Lx, Ly, work, work_bytes_)) return rc;
+// The fields of both entry points: that == NULL or b == 0 end in the pressure kernel of the flow alone.
+static int spec_ns_fields(const char* who, const float* what, const float* that, const float* mean, float* u, float* v, float* p, void* work,
+                          size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double rho, double bx, double by, void* stream) {
+    if (!what || !mean || !u || !v || !p || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
+    if (!std::isfinite(rho)) return fail(NNS_ERR_INVALID_ARG, "%s: rho = %g must be finite", who, rho);
+    if (!std::isfinite(bx) || !std::isfinite(by)) return fail(NNS_ERR_INVALID_ARG, "%s: the buoyancy (%g, %g) must be finite", who, bx, by);
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work, work_bytes_, that != nullptr)) return rc;
     hipStream_t s = as_stream(stream);
     const int my1 = kept_y(ny);
     const long nh = ny / 2 + 1, per = (long)batch * nx * nh, npts = (long)batch * nx * ny;
@@ -945,14 +1060,30 @@ NNS_API int nns_spec_ns_fields_f32(const float* what, const float* mean, float* 
     const float kx1 = (float)(2.0 * M_PI / Lx), ky1 = (float)(2.0 * M_PI / Ly);
     hipLaunchKernelGGL(ps_derivs_kernel, dim3(pw_grid(per)), dim3(256), 0, s, reinterpret_cast<const float2*>(what), mean,
                        reinterpret_cast<float2*>(spec), batch, nx, ny, my1, kx1, ky1);
-    if (int rc = check_launch("spec_ns_fields")) return rc;
+    if (int rc = check_launch(who)) return rc;
     if (int rc = nns_spec_irfft2_f32(spec, phys, 4 * batch, nx, ny, stream)) return rc;
     if (int rc = nns_spec_irfft2_f32(spec + 2 * 4 * per, u, batch, nx, ny, stream)) return rc;
     if (int rc = nns_spec_irfft2_f32(spec + 2 * 5 * per, v, batch, nx, ny, stream)) return rc;
     hipLaunchKernelGGL(ps_source_kernel, dim3(pw_grid(npts)), dim3(256), 0, s, phys, phys, npts, (float)(2.0 * rho));
-    if (int rc = check_launch("spec_ns_fields")) return rc;
+    if (int rc = check_launch(who)) return rc;
     if (int rc = nns_spec_rfft2_f32(phys, spec, batch, nx, ny, stream)) return rc;
-    hipLaunchKernelGGL(ps_pressure_kernel, dim3(pw_grid(per)), dim3(256), 0, s, reinterpret_cast<float2*>(spec), batch, nx, ny, kx1, ky1);
-    if (int rc = check_launch("spec_ns_fields")) return rc;
+    if (that && (bx != 0.0 || by != 0.0))
+        hipLaunchKernelGGL(ps_pressure_buoyant_kernel, dim3(pw_grid(per)), dim3(256), 0, s, reinterpret_cast<float2*>(spec),
+                           reinterpret_cast<const float2*>(that), batch, nx, ny, my1, kx1, ky1, (float)(rho * bx), (float)(rho * by));
+    else
+        hipLaunchKernelGGL(ps_pressure_kernel, dim3(pw_grid(per)), dim3(256), 0, s, reinterpret_cast<float2*>(spec), batch, nx, ny, kx1, ky1);
+    if (int rc = check_launch(who)) return rc;
     return nns_spec_irfft2_f32(spec, p, batch, nx, ny, stream);
+}
+
+NNS_API int nns_spec_ns_fields_f32(const float* what, const float* mean, float* u, float* v, float* p, void* work, size_t work_bytes_,
+                                   int batch, int nx, int ny, double Lx, double Ly, double rho, void* stream) {
+    return spec_ns_fields("spec_ns_fields", what, nullptr, mean, u, v, p, work, work_bytes_, batch, nx, ny, Lx, Ly, rho, 0.0, 0.0, stream);
+}
+
+NNS_API int nns_spec_ns_fields_buoyant_f32(const float* what, const float* that, const float* mean, float* u, float* v, float* p, void* work,
+                                           size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double rho, double bx, double by,
+                                           void* stream) {
+    if (!that) return fail(NNS_ERR_INVALID_ARG, "spec_ns_fields_buoyant: NULL pointer or batch < 1");
+    return spec_ns_fields("spec_ns_fields_buoyant", what, that, mean, u, v, p, work, work_bytes_, batch, nx, ny, Lx, Ly, rho, bx, by, stream);
 }

@@ -1090,6 +1090,57 @@ def spec_ns_transfer(what, that, work, ny, Lx, Ly, out=None):
     return out
 
 
+# Boussinesq buoyancy of the periodic solver (nns_spec_ns_step_buoyant_f32, nns_spec_ns_fields_buoyant_f32, nns_spec_ns_buoyancy_spectrum_f32)
+def spec_ns_step_buoyant_(what, that, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, kappa, grad, buoyancy, nsteps=1):
+    """spec_ns_step_scalar_ with the scalar acting on the flow through buoyancy = (bx, by): w_t gains by theta_x - bx theta_y, every stage with
+    its own theta^.  (0, 0) makes exactly the calls of spec_ns_step_scalar_.  No allocation, no host synchronisation: capturable."""
+    B, my1, nx = _spec_ns_state('spec_ns_step_buoyant_', what, mean, work, ny)
+    _spec_ns_same('spec_ns_step_buoyant_', that, what)
+    gbatch = _spec_ns_force('spec_ns_step_buoyant_', ghat, what)
+    (gx, gy), (bx, by) = grad, buoyancy
+    check(_lib.lib().nns_spec_ns_step_buoyant_f32(_p(what), _p(that), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(work), work.numel(), B,
+                                                  nx, int(ny), float(Lx), float(Ly), float(dt), float(nu), float(drag), float(kappa), float(gx),
+                                                  float(gy), float(bx), float(by), int(nsteps), _stream()), 'nns_spec_ns_step_buoyant_f32')
+    return what, that
+
+
+def spec_ns_fields_buoyant(what, that, mean, work, ny, Lx, Ly, rho, buoyancy, out=None):
+    """(u, v, p) float32 [B, nx, ny] of a buoyant state: p also carries -rho i (k . b) theta^ / |k|^2.  work: spec_ns_scalar_workspace bytes;
+    out as in spec_ns_fields."""
+    B, my1, nx = _spec_ns_state('spec_ns_fields_buoyant', what, mean, work, ny)
+    _spec_ns_same('spec_ns_fields_buoyant', that, what)
+    if out is None:
+        out = tuple(torch.empty((B, nx, int(ny)), dtype=torch.float32, device=what.device) for _ in range(3))
+    else:
+        out = tuple(out)
+        _f32(*out)
+        if len(out) != 3 or any(tuple(o.shape) != (B, nx, int(ny)) or o.device != what.device for o in out):
+            raise ValueError("spec_ns_fields_buoyant: out must be three [%d, %d, %d] tensors on the state's device" % (B, nx, ny))
+    u, v, p = out
+    bx, by = buoyancy
+    check(_lib.lib().nns_spec_ns_fields_buoyant_f32(_p(what), _p(that), _p(mean), _p(u), _p(v), _p(p), _p(work), work.numel(), B, nx, int(ny),
+                                                    float(Lx), float(Ly), float(rho), float(bx), float(by), _stream()),
+          'nns_spec_ns_fields_buoyant_f32')
+    return out
+
+
+def spec_ns_buoyancy_spectrum(what, that, ny, Lx, Ly, buoyancy, out=None):
+    """float64 [B, nshell]: the buoyancy production <(b . u) theta'> per shell; its sum over the shells is b . (flux_x, flux_y) of
+    spec_ns_scalar_diag."""
+    B, my1, nx = _spec_ns_state('spec_ns_buoyancy_spectrum', what, None, None, ny)
+    _spec_ns_same('spec_ns_buoyancy_spectrum', that, what)
+    S = spec_ns_shells(nx, ny, Lx, Ly)[0]
+    if out is None:
+        out = torch.empty((B, S), dtype=torch.float64, device=what.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (B, S) and out.is_contiguous()
+              and out.device == what.device):
+        raise ValueError("spec_ns_buoyancy_spectrum: out must be a contiguous float64 [%d, %d] tensor on the state's device" % (B, S))
+    bx, by = buoyancy
+    check(_lib.lib().nns_spec_ns_buoyancy_spectrum_f32(_p(what), _p(that), _p(out), S, B, nx, int(ny), float(Lx), float(Ly), float(bx),
+                                                       float(by), _stream()), 'nns_spec_ns_buoyancy_spectrum_f32')
+    return out
+
+
 # ----------------------------------------------------------------------------- physics-informed loss head
 _PINN_WS = {}
 

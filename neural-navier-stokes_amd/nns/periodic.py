@@ -18,7 +18,7 @@ otherwise, 2 = float64 forward transforms always.
 ``PeriodicSolver`` produces the trajectories such a residual measures: a pseudo-spectral solver of the same equations on the same box
 (csrc/pspec_kernels.hip; scheme in DESIGN.md and tests/pspec_oracle.py), optionally with a steady body force and a linear drag
 (tests/pspec_forced_oracle.py) and with a passive scalar -- temperature, dye -- that the same fused step transports
-(tests/pspec_scalar_oracle.py).  Its ``spectrum`` and ``transfer`` give energy, enstrophy, injection, scalar variance and the nonlinear
+(tests/pspec_scalar_oracle.py) and that, with ``buoyancy``, acts back on the flow (tests/pspec_buoyant_oracle.py).  Its ``spectrum`` and ``transfer`` give energy, enstrophy, injection, scalar variance and the nonlinear
 transfers by wavenumber shell (tests/pspec_spectrum_oracle.py).
 """
 import collections
@@ -156,13 +156,23 @@ class PeriodicSolver(object):
     the power input of the force per grid.  Without a force and with drag == 0 every call takes the unforced path.
 
     Passive scalar: with ``kappa`` >= 0 (None: no scalar) and ``init(u, v, theta)`` the state also carries a scalar theta -- temperature,
-    dye, concentration -- that the flow advects and that does not act back on it:
+    dye, concentration -- that the flow advects and that, without ``buoyancy``, does not act back on it:
         theta_t + (u . grad) theta = kappa lap theta - G . u
     ``scalar_gradient`` = G = (Gx, Gy) is a uniform mean gradient: the total field is G . x + theta and theta its periodic part, whose variance
     the gradient sustains.  theta is band-limited like the flow but keeps its grid mean, d<theta>/dt = -G . (U0, V0); the drag does not act
     on it.  It rides in the flow's launches (still 8 per step), each RK stage with that stage's own velocity, and the flow evolves bitwise
     as without it.  ``scalar(state)`` gives theta, ``scalar_diagnostics(state)`` its variance budget.  A state without a scalar takes exactly
     the calls it takes on a solver without ``kappa``.
+
+    Buoyancy: with ``buoyancy`` = b = (bx, by) != 0 (needs ``kappa``) the scalar of a state acts on its flow (Boussinesq):
+        u_t + (u . grad) u = -grad p / rho + nu lap u - alpha (u - <u>) + f_s + b theta',      theta' = theta - <theta>
+    that is w_t gains by theta_x - bx theta_y, explicit in the same Lawson RK4 with every stage's own theta^, still 8 launches per step.  Only the
+    periodic fluctuation is buoyant: b <theta> would only accelerate the frame, and the background G . x is taken as hydrostatic (its curl, a
+    constant, cannot exist on a periodic box), so both are dropped, as ``init`` and ``set_forcing`` drop such parts.  b . G > 0 gives internal
+    gravity waves and stratified turbulence, b . G < 0 homogeneous Rayleigh-Benard convection.  Now div(b theta') != 0 and ``fields`` returns the
+    pressure of lap p = rho (2 (u_x v_y - u_y v_x) + b . grad theta).  ``buoyancy_power(state)`` = b . <u theta'> closes the energy equation,
+    d energy / dt = power_in - 2 nu enstrophy - 2 drag energy + buoyancy_power; ``buoyancy_spectrum(state)`` gives it per shell and
+    ``energy_budget`` adds it.  With b = (0, 0), and for a state without a scalar (theta = 0), every call is the one it is without the argument.
 
     By wavenumber: the stored modes are binned into shells of width dk = min(2 pi / Lx, 2 pi / Ly) centred on k_s = s dk (``shells()``; an
     elongated box has many).  ``spectrum(state)`` gives energy E(s), enstrophy Z(s), the force's injection F(s) and the scalar's variance V(s),
@@ -171,7 +181,8 @@ class PeriodicSolver(object):
     cumulative form Pi(s), and ``energy_budget(state)`` dE(s)/dt = T_E + F - 2 nu Z - 2 drag E.  All float64, summed on the device in a fixed
     order.  The spectrum of arbitrary fields -- a model's prediction, say -- is ``solver.spectrum(solver.init(u, v))``."""
 
-    def __init__(self, nx, ny, dt, rho, nu, Lx=2 * math.pi, Ly=2 * math.pi, drag=0.0, kappa=None, scalar_gradient=(0.0, 0.0)):
+    def __init__(self, nx, ny, dt, rho, nu, Lx=2 * math.pi, Ly=2 * math.pi, drag=0.0, kappa=None, scalar_gradient=(0.0, 0.0),
+                 buoyancy=(0.0, 0.0)):
         self.nx, self.ny = _pow2_axis('nx', nx), _pow2_axis('ny', ny)
         self.dt, self.rho = _real('dt', dt), _real('rho', rho)
         self.nu = _real('nu', nu, positive=False)
@@ -183,6 +194,13 @@ class PeriodicSolver(object):
         except (TypeError, ValueError):
             raise TypeError("scalar_gradient must be two real numbers (Gx, Gy), got %r" % (scalar_gradient,))
         self.scalar_gradient = tuple(self._finite('scalar_gradient', g) for g in (gx, gy))
+        try:
+            bx, by = buoyancy
+        except (TypeError, ValueError):
+            raise TypeError("buoyancy must be two real numbers (bx, by), got %r" % (buoyancy,))
+        self.buoyancy = tuple(self._finite('buoyancy', b) for b in (bx, by))
+        if self.buoyancy != (0.0, 0.0) and self.kappa is None:
+            raise ValueError("buoyancy = %r needs a solver built with kappa (the diffusivity of the scalar that is buoyant)" % (self.buoyancy,))
         self.my1 = ops.spec_ns_kept_y(self.ny)
         self.ghat = None                       # the force's vorticity-equation spectrum g^, float32 [Bg, my1, nx, 2] (set_forcing)
         self.last_simulate_used_graph = False
@@ -301,8 +319,15 @@ class PeriodicSolver(object):
                 raise ValueError("the force is on %s, the state on %s" % (g.device, state.what.device))
         return g
 
+    def _buoyant(self, state):
+        """The scalar of this state acts on its flow: it has one and b != 0."""
+        return state.that is not None and self.buoyancy != (0.0, 0.0)
+
     def _launch_steps(self, state, nsteps):
-        if state.that is not None:
+        if self._buoyant(state):
+            ops.spec_ns_step_buoyant_(state.what, state.that, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt,
+                                      self.nu, self.drag, self.kappa, self.scalar_gradient, self.buoyancy, nsteps)
+        elif state.that is not None:
             ops.spec_ns_step_scalar_(state.what, state.that, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt,
                                      self.nu, self.drag, self.kappa, self.scalar_gradient, nsteps)
         elif self._forced():
@@ -373,13 +398,29 @@ class PeriodicSolver(object):
 
     def energy_budget(self, state):
         """dE(s)/dt = T_E(s) + F(s) - 2 nu Z(s) - 2 drag E(s), float64 [B, S]: the right-hand side of the energy equation per shell (the
-        viscous term is exact per shell: |k|^2 E_mode = Z_mode)."""
+        viscous term is exact per shell: |k|^2 E_mode = Z_mode); for a buoyant state plus ``buoyancy_spectrum``."""
         sp, tr = self.spectrum(state), self.transfer(state)
-        return tr.energy + sp.injection - 2.0 * self.nu * sp.enstrophy - 2.0 * self.drag * sp.energy
+        rhs = tr.energy + sp.injection - 2.0 * self.nu * sp.enstrophy - 2.0 * self.drag * sp.energy
+        return rhs + self.buoyancy_spectrum(state) if self._buoyant(state) else rhs
+
+    def buoyancy_power(self, state):
+        """b . <u theta'> = bx flux_x + by flux_y of ``scalar_diagnostics``, float64 [B]: the rate at which buoyancy feeds the fluctuation
+        energy (zeros with b = (0, 0))."""
+        d = self.scalar_diagnostics(state)
+        return self.buoyancy[0] * d.flux_x + self.buoyancy[1] * d.flux_y
+
+    def buoyancy_spectrum(self, state):
+        """``buoyancy_power`` by wavenumber shell (``shells()``), float64 [B, S], summed on the device in the fixed order of ``spectrum``; its
+        sum over the shells is ``buoyancy_power``.  Only reads the state."""
+        self._scalar_state(state)
+        return ops.spec_ns_buoyancy_spectrum(state.what, state.that, self.ny, self.Lx, self.Ly, self.buoyancy)
 
     def fields(self, state, out=None):
-        """(u, v, p) float32 [B, nx, ny] of the state (into ``out`` if given)."""
+        """(u, v, p) float32 [B, nx, ny] of the state (into ``out`` if given); p includes the buoyancy's part for a buoyant state."""
         self._state(state)
+        if self._buoyant(state):
+            return ops.spec_ns_fields_buoyant(state.what, state.that, state.mean, state.work, self.ny, self.Lx, self.Ly, self.rho, self.buoyancy,
+                                              out)
         return ops.spec_ns_fields(state.what, state.mean, state.work, self.ny, self.Lx, self.Ly, self.rho, out)
 
     def simulate(self, u0, v0, nsteps, save_every=1, use_graph=None, theta0=None):
@@ -435,6 +476,7 @@ class PeriodicSolver(object):
     def residual_engine(self, backend='spectral', precise=True, every=1):
         """A ResidualEngine with this solver's constants, for frames ``every`` steps apart (its dt = every * dt).  The engine knows neither
         force nor drag: on the frames of a forced run its momentum residuals converge (as dt -> 0) to f_s - drag (u - <u>), the right-hand
-        side of the class note, rather than to zero; subtract that (``forcing_fields``) to measure the discretisation alone."""
+        side of the class note, rather than to zero; subtract that (``forcing_fields``) to measure the discretisation alone.  Likewise on
+        buoyant frames the momentum residual converges to b theta' (plus the forced terms), theta' = ``scalar`` minus its grid mean."""
         every = _count('every', every, 1)
         return ResidualEngine(self.nx, self.ny, self.dt * every, self.rho, self.nu, self.Lx, self.Ly, backend=backend, precise=precise)
