@@ -505,6 +505,24 @@ int nns_spec_ns_transfer_f32(const float* what, const float* that, double* out, 
 int nns_spec_ns_step_buoyant_f32(float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work, size_t work_bytes,
                                  int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa, double gx,
                                  double gy, double bx, double by, int nsteps, void* stream);
+/* White-in-time stochastic forcing (restatement: tests/pspec_stochastic_oracle.py): nns_spec_ns_step_buoyant_f32's step -- drag, steady force,
+ * scalar and buoyancy, whichever are active; that == NULL: no scalar, and kappa, gx, gy, bx, by are ignored -- and after every complete step n
+ *     w^_k  <-  w^_k + sqrt(dt) amp_k xi_k(n, ids[b])        on the kept modes k != (0, 0) (entries of amp elsewhere are ignored)
+ * amp: non-negative float32 [my1][nx] (device), the layout of one grid of what, shared by the batch.  xi: a complex standard normal,
+ * E |xi|^2 = 1, independent over stored modes, steps and ids, from Philox4x32-10 with key (seed low word, seed high word) and counter
+ * (n low, n high, j nx + i, ids[b]); of the outputs x0, x1 are used: u1 = ((x0 >> 8) + 1) 2^-24, u2 = (x1 >> 8) 2^-24,
+ * xi = sqrt(-ln u1) (cos 2 pi u2, sin 2 pi u2).  On the j = 0 line the element of -m_x takes the counter of |m_x| and is conjugated, so the
+ * line stays Hermitian.  The mean energy input is exact and independent of the state: 1/2 sum wt amp_k^2 / (|k|^2 (nx ny)^2), wt as in
+ * nns_spec_ns_diag_f32.  The scalar gets no noise.  clock: int64 [1] (device), the stochastic steps this state has taken, n of the next step;
+ * the step advances it on the device (stage 1's column launch; stage 4's evaluates the generator in registers where amp_k != 0), so the call
+ * is capturable and a replayed step continues the sequence: still 8 launches per step plus one per call, no allocation, no host
+ * synchronisation.  ids: int32 [batch] (device): grids with equal ids get equal noise.  nsteps calls of one step, one call of nsteps steps
+ * and graph replays give the same bits.  NNS_ERR_INVALID_ARG for NULL amp, clock or ids; otherwise the errors of
+ * nns_spec_ns_step_buoyant_f32 (nns_spec_ns_step_forced_f32 with that == NULL; work: nns_spec_ns_workspace bytes then). */
+int nns_spec_ns_step_stochastic_f32(float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work, size_t work_bytes,
+                                    int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa,
+                                    double gx, double gy, double bx, double by, const float* amp, unsigned long long seed, long long* clock,
+                                    const int* ids, int nsteps, void* stream);
 /* u, v as nns_spec_ns_fields_f32 and the pressure of the buoyant flow: lap p = rho (2 (u_x v_y - u_y v_x) + b . grad theta), that is
  * p^ = p^ of nns_spec_ns_fields_f32 - rho i (k . b) theta^ / |k|^2 on the kept modes, zero mean.  work: nns_spec_ns_scalar_workspace bytes.
  * Errors as nns_spec_ns_fields_f32, plus that == NULL and a non-finite bx, by. */

@@ -2,6 +2,7 @@
 // TH = false the vorticity (Ph field 0, W / A, G fields 0..3), TH = true the scalar (Ph field 1, theta^ / A_theta, G fields 4 and 5).  Plain
 // text rather than a function or a lambda: the unscalared kernels then compile to the instructions they had before there was a scalar
 // (a lambda's body is optimised on its own before it is inlined, and came out a few instructions and registers different).
+// STOCH (ps_col_kernel's note) is false in every kernel without a PsStoch argument, whose text below is then what it was.
 {
         const float2* ph = TH ? Ph + a.fstride : Ph;
         float2* Ws = TH ? Th : W;
@@ -65,7 +66,16 @@
                 } else {                                // d: w = A + dt/6 d
                     const float2 a2 = lok ? As[si] : make_float2(0.f, 0.f);
                     const cf acc = keep ? cf{a2.x, a2.y} : cf{0.f, 0.f};
-                    const cf w = axpy(dt6, n, acc);
+                    cf w = axpy(dt6, n, acc);
+                    if constexpr (STOCH && !TH) {       // the kick of the finished step: w += sqrt(dt) a xi, Philox only on the forced ring
+                        const float amp = keep ? samp[(size_t)lj * N + e] : 0.f;
+                        if (amp != 0.f) {
+                            const bool mirror = lj == 0 && mx < 0;                 // the j = 0 line stores -m_x too: |m_x|'s sample, conjugated
+                            const cf xi = ps_normal(sn0, sn1, (unsigned)(lj * N + (mirror ? -mx : e)), sid, sk0, sk1);
+                            const float sa = sqdt * amp;
+                            w = {fmaf(sa, xi.x, w.x), fmaf(mirror ? -sa : sa, xi.y, w.y)};
+                        }
+                    }
                     if (lok) Ws[si] = make_float2(w.x, w.y);
                     y[m] = w;
                 }

@@ -38,6 +38,14 @@
 // unnormalised inverse then forward transform along y).  No further transform, no further line live across one; the column pass is untouched.
 // b = 0 launches the passive kernels.  ps_pressure_buoyant_kernel adds -rho i (k . b) theta^ / |k|^2 to p^ (div (b theta') != 0).
 //
+// Stochastic forcing (nns_spec_ns_step_stochastic_f32; restatement: tests/pspec_stochastic_oracle.py): after the complete deterministic step the
+// vorticity spectrum gets one white-in-time kick, w^ += sqrt(dt) a_k xi_k(n, id_b) on the kept modes, a the amplitude table [my1][nx] shared by
+// the batch and xi a complex standard normal (E |xi|^2 = 1) from Philox4x32-10 keyed by the seed and counted by (step n, stored mode, grid id).
+// A trailing PsStoch in the column kernel's argument pack (STOCH) is the compile-time switch, and only stages 1 and 4 have that form: stage 4
+// evaluates the generator in registers where a_k != 0, just before w^ is stored and handed to the next step's stage 1; stage 1 advances the
+// device-side step count (one lane of one workgroup: nothing in that launch reads it), so stage 4 reads n = clock - 1 and a captured step
+// replays.  No further launch, transform or stream; kernels without the PsStoch keep their names and their code.
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 #include "nns_common.h"
 #include "fft_lds.h"
@@ -80,7 +88,19 @@ struct PsBuoyGrad {                   // that of the BUOYANT row kernel: the gra
     float gx, gy;
     float c4, c5;                     // -ny by, ny bx
 };
+struct PsStoch {          // the last argument of the STOCH column kernels (stages 1 and 4 of a stochastic step)
+    const float* amp;     // a [my1][nx], the layout of one grid of W, shared by the batch
+    unsigned k0, k1;      // the seed's low and high word: the Philox key
+    long long* clock;     // [1]: stochastic steps taken; stage 1 advances it, stage 4 reads n = clock - 1
+    const int* ids;       // [B]: the grid ids, the fourth counter word
+    float sqdt;           // sqrt(dt)
+};
 template <typename T> __device__ __forceinline__ T only(T t) { return t; }     // the one element of a SCALAR kernel's argument pack
+template <typename T, typename... R> __device__ __forceinline__ T first(T t, R...) { return t; }
+template <typename T, typename... R> __device__ __forceinline__ auto last(T t, R... r) {
+    if constexpr (sizeof...(R) == 0) return t;
+    else return last(r...);
+}
 
 struct PsArgs {
     long nlines;          // row kernel: B nx rows; column kernel: B my1 columns
@@ -96,6 +116,24 @@ using cf = C2<float>;
 __device__ __forceinline__ cf scal(float em, cf z) { return {fmaf(em, z.x, z.x), fmaf(em, z.y, z.y)}; }     // (1 + em) z
 __device__ __forceinline__ cf axpy(float a, cf x, cf y) { return {fmaf(a, x.x, y.x), fmaf(a, x.y, y.y)}; }   // a x + y
 __device__ __forceinline__ cf imul(float a, cf z) { return {-a * z.y, a * z.x}; }                            // i a z
+
+// Philox4x32-10 (Salmon et al., SC'11), outputs 0 and 1 of counter (c0, c1, c2, c3) under key (k0, k1), mapped to one complex standard normal
+// with E |xi|^2 = 1: u1 = ((x0 >> 8) + 1) 2^-24 in (0, 1], u2 = (x1 >> 8) 2^-24 in [0, 1), xi = sqrt(-ln u1) (cos 2 pi u2, sin 2 pi u2).
+// 2 u2 is exact in float32 and sincospif reduces its argument exactly.
+__device__ __forceinline__ cf ps_normal(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    const float u1 = (float)((c0 >> 8) + 1u) * 0x1p-24f, u2 = (float)(c1 >> 8) * 0x1p-24f;
+    const float rad = sqrtf(-logf(u1));
+    float sn, cs;
+    sincospif(2.f * u2, &sn, &cs);
+    return {rad * cs, rad * sn};
+}
 
 template <int N>
 __device__ __forceinline__ cf* ps_tables(unsigned char* smem) {
@@ -208,12 +246,15 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
 // FORCED (S >= 1): N^ += g^ on the kept modes (lane-owned, coalesced, like W / A) and L dt / 2 = hnudt |k|^2 - alpha dt / 2.
 // SCALAR: after the vorticity's work on a tile the same sequence runs once more on the scalar: Ph's second field, theta^ / A_theta with
 // L dt / 2 = hkdt |k|^2 (no drag, no force) and a mask that keeps the (0, 0) mode, then G fields 4 and 5.  One field's registers at a time.
+// STOCH (a PsStoch ends the pack; FORCED, S = 1 or 4): S = 1 advances the step count, S = 4 adds the kick to the vorticity's w^ (not the scalar's).
 template <int N, int S, bool FORCED = false, bool SCALAR = false, typename... Sc>
 __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, float2* __restrict__ W,
                                                     float2* __restrict__ A, const float* __restrict__ mean, PsArgs a, int emit,
                                                     std::conditional_t<FORCED, PsForce, PsNoForce> fc, Sc... sc) {
     static_assert(!FORCED || S >= 1, "stage 0 only prepares: it has no forced form");
-    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0), "PsScalar is the SCALAR kernel's argument");
+    constexpr bool STOCH = (std::is_same_v<Sc, PsStoch> || ... || false);
+    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (STOCH ? 1 : 0), "PsScalar is the SCALAR kernel's argument, PsStoch after it the STOCH kernel's");
+    static_assert(!STOCH || (FORCED && (S == 1 || S == 4)), "the kick is stage 4's and the step count stage 1's, both of the forced form");
     using L = PsLds<N>;
     constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -226,8 +267,22 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     [[maybe_unused]] float2* At = nullptr;
     [[maybe_unused]] float hkdt = 0.f;
     if constexpr (SCALAR) {
-        const PsScalar ps = only(sc...);
+        const PsScalar ps = first(sc...);
         Th = ps.T; At = ps.At; hkdt = ps.hkdt;
+    }
+    [[maybe_unused]] const float* samp = nullptr;
+    [[maybe_unused]] const int* sids = nullptr;
+    [[maybe_unused]] unsigned sk0 = 0, sk1 = 0, sn0 = 0, sn1 = 0;
+    [[maybe_unused]] float sqdt = 0.f;
+    if constexpr (STOCH) {
+        const PsStoch st = last(sc...);
+        if constexpr (S == 1) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) *st.clock = *st.clock + 1;      // no workgroup of this launch reads it
+        } else {
+            const unsigned long long n = (unsigned long long)(*st.clock - 1);        // this step's index: stage 1 has counted it
+            samp = st.amp; sids = st.ids; sk0 = st.k0; sk1 = st.k1; sqdt = st.sqdt;
+            sn0 = (unsigned)n; sn1 = (unsigned)(n >> 32);
+        }
     }
     for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
         int tx = threadIdx.x;
@@ -253,6 +308,8 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
             gbase = fc.shared ? (size_t)lj * N : wbase;
             gok = lok && fc.g != nullptr;
         }
+        [[maybe_unused]] unsigned sid = 0;
+        if constexpr (STOCH && S == 4) sid = lok ? (unsigned)sids[lb] : 0u;
         int tv = tid;
         asm volatile("" : "+v"(tv));
         const float ky = a.ky1 * (float)lj;
@@ -700,9 +757,29 @@ int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* m
     return check_launch(FORCED ? "spec_ns forced column pass" : "spec_ns column pass");
 }
 
+// stages 1 and 4 of a stochastic step: the forced kernels with a PsStoch at the end of their argument pack
+template <int N, int S>
+int launch_col_stoch(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce& fc,
+                     const PsScalar* sc, const PsStoch& st, hipStream_t s) {
+    const dim3 grid(grid_of(a.nlines, PsLds<N>::LINES));
+    if (sc) {
+        constexpr auto kern = ps_col_kernel<N, S, true, true, PsScalar, PsStoch>;
+        if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+        hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, fc, *sc, st);
+        return check_launch("spec_ns stochastic scalar column pass");
+    }
+    constexpr auto kern = ps_col_kernel<N, S, true, false, PsStoch>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, fc, st);
+    return check_launch("spec_ns stochastic column pass");
+}
+
+// st != nullptr (with fc): a stochastic step, whose stages 1 and 4 are the STOCH kernels
 template <int N>
 int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
-                     const PsScalar* sc, hipStream_t s) {
+                     const PsScalar* sc, hipStream_t s, const PsStoch* st = nullptr) {
+    if (st && S == 1) return launch_col_stoch<N, 1>(Ph, G, W, A, mean, a, emit, *fc, sc, *st, s);
+    if (st && S == 4) return launch_col_stoch<N, 4>(Ph, G, W, A, mean, a, emit, *fc, sc, *st, s);
     if (fc && S >= 1) {
         switch (S) {
             case 1: return launch_col<N, 1, true>(Ph, G, W, A, mean, a, emit, fc, sc, s);
@@ -909,10 +986,11 @@ NNS_API int nns_spec_ns_init_f32(const float* u, const float* v, float* what, fl
     return check_launch("spec_ns_init");
 }
 
-// The step of every entry point: ghat == NULL and drag == 0 launch the unforced kernels, that == NULL the unscalared ones, b == 0 the passive ones.
+// The step of every entry point: ghat == NULL and drag == 0 launch the unforced kernels, that == NULL the unscalared ones, b == 0 the passive ones;
+// st != NULL (amp, key, clock, ids; its sqdt is set here) takes the forced path, with or without ghat and drag, and kicks after every step.
 static int spec_ns_step(const char* who, float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work,
                         size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa,
-                        double gx, double gy, double bx, double by, int nsteps, void* stream) {
+                        double gx, double gy, double bx, double by, int nsteps, void* stream, const PsStoch* st = nullptr) {
     if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
     if (!(dt > 0) || !std::isfinite(dt) || !(nu >= 0) || !std::isfinite(nu) || nsteps < 0)
         return fail(NNS_ERR_INVALID_ARG, "%s: dt = %g must be > 0, nu = %g >= 0, nsteps = %d >= 0", who, dt, nu, nsteps);
@@ -936,14 +1014,20 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
     PsArgs ar = ac;
     ar.nlines = (long)batch * nx;
     const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
-    const PsForce* fc = ghat || drag > 0 ? &force : nullptr;
+    const PsForce* fc = ghat || drag > 0 || st ? &force : nullptr;
+    PsStoch stoch{};
+    if (st) {
+        stoch = *st;
+        stoch.sqdt = (float)std::sqrt(dt);
+    }
+    const PsStoch* stc = st ? &stoch : nullptr;
     const PsScalar scalar{reinterpret_cast<float2*>(that), A + fstride, (float)(-0.5 * kappa * dt)};
     const PsGrad grad{(float)gx, (float)gy};
     const PsScalar* sc = that ? &scalar : nullptr;
     const PsGrad* gr = that ? &grad : nullptr;
     const PsBuoyGrad buoy{(float)gx, (float)gy, (float)(-(double)ny * by), (float)((double)ny * bx)};
     const PsBuoyGrad* bu = that && (bx != 0.0 || by != 0.0) ? &buoy : nullptr;
-    auto col = [&](int S, int emit) { return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, fc, sc, s); }); };
+    auto col = [&](int S, int emit) { return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, fc, sc, s, stc); }); };
     auto row = [&]() { return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, gr, s, bu); }); };
     if (int rc = col(0, 1)) return rc;
     for (int k = 0; k < nsteps; ++k) {
@@ -982,6 +1066,16 @@ NNS_API int nns_spec_ns_step_buoyant_f32(float* what, float* that, const float* 
     if (!that) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_buoyant: NULL pointer or batch < 1");
     return spec_ns_step("spec_ns_step_buoyant", what, that, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, drag, kappa, gx,
                         gy, bx, by, nsteps, stream);
+}
+
+NNS_API int nns_spec_ns_step_stochastic_f32(float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work,
+                                            size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
+                                            double kappa, double gx, double gy, double bx, double by, const float* amp, unsigned long long seed,
+                                            long long* clock, const int* ids, int nsteps, void* stream) {
+    if (!amp || !clock || !ids) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_stochastic: amp, clock and ids must be non-NULL");
+    const PsStoch st{amp, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), clock, ids, 0.f};
+    return spec_ns_step("spec_ns_step_stochastic", what, that, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, drag,
+                        that ? kappa : 0.0, that ? gx : 0.0, that ? gy : 0.0, that ? bx : 0.0, that ? by : 0.0, nsteps, stream, &st);
 }
 
 NNS_API int nns_spec_ns_scalar_workspace(int batch, int nx, int ny, size_t* bytes) {

@@ -7,6 +7,7 @@ torch's current stream and returns its outputs as tensors.  Errors raise nns._li
 the library's message; there is no CPU fallback.
 """
 import ctypes
+import numbers
 
 import torch
 
@@ -1102,6 +1103,39 @@ def spec_ns_step_buoyant_(what, that, mean, ghat, work, ny, Lx, Ly, dt, nu, drag
                                                   nx, int(ny), float(Lx), float(Ly), float(dt), float(nu), float(drag), float(kappa), float(gx),
                                                   float(gy), float(bx), float(by), int(nsteps), _stream()), 'nns_spec_ns_step_buoyant_f32')
     return what, that
+
+
+# white-in-time stochastic forcing of the periodic solver (nns_spec_ns_step_stochastic_f32)
+def spec_ns_step_stochastic_(what, that, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, kappa, grad, buoyancy, amp, seed, clock, ids, nsteps=1):
+    """nsteps steps of spec_ns_step_buoyant_ (that None: of spec_ns_step_forced_; kappa, grad and buoyancy are then ignored), each followed by
+    the kick w^ += sqrt(dt) amp xi(n, ids[b]): amp float32 [my1, nx] (shared by the batch), seed a 64-bit int, clock int64 [1] (the state's
+    stochastic step count, advanced on the device) and ids int32 [B], all on the state's device.  No allocation, no host synchronisation:
+    capturable, and a replay continues the noise sequence."""
+    who = 'spec_ns_step_stochastic_'
+    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
+    if that is not None:
+        _spec_ns_same(who, that, what)
+    gbatch = _spec_ns_force(who, ghat, what)
+    _f32(amp)
+    if tuple(amp.shape) != (my1, nx):
+        raise ValueError("%s: amp must be float32 [%d, %d], got %s" % (who, my1, nx, tuple(amp.shape)))
+    for name, t, dtype, shape in (('clock', clock, torch.int64, (1,)), ('ids', ids, torch.int32, (B,))):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+            raise TypeError("%s: %s must be a contiguous %s device tensor" % (who, name, dtype))
+        if tuple(t.shape) != shape:
+            raise ValueError("%s: %s must be %s %s, got %s" % (who, name, dtype, list(shape), tuple(t.shape)))
+    if any(t.device != what.device for t in (amp, clock, ids)):
+        raise ValueError("%s: amp, clock and ids must be on the state's device %s" % (who, what.device))
+    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral):
+        raise TypeError("%s: seed must be an int, got %r" % (who, seed))
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("%s: seed = %d must be in [0, 2^64)" % (who, seed))
+    (gx, gy), (bx, by) = grad, buoyancy
+    check(_lib.lib().nns_spec_ns_step_stochastic_f32(_p(what), None if that is None else _p(that), _p(mean), _p(ghat) if gbatch else None, gbatch,
+                                                     _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt), float(nu),
+                                                     float(drag), float(kappa), float(gx), float(gy), float(bx), float(by), _p(amp), int(seed),
+                                                     _p(clock), _p(ids), int(nsteps), _stream()), 'nns_spec_ns_step_stochastic_f32')
+    return what
 
 
 def spec_ns_fields_buoyant(what, that, mean, work, ny, Lx, Ly, rho, buoyancy, out=None):

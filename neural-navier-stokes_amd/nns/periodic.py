@@ -19,7 +19,8 @@ otherwise, 2 = float64 forward transforms always.
 (csrc/pspec_kernels.hip; scheme in DESIGN.md and tests/pspec_oracle.py), optionally with a steady body force and a linear drag
 (tests/pspec_forced_oracle.py) and with a passive scalar -- temperature, dye -- that the same fused step transports
 (tests/pspec_scalar_oracle.py) and that, with ``buoyancy``, acts back on the flow (tests/pspec_buoyant_oracle.py).  Its ``spectrum`` and ``transfer`` give energy, enstrophy, injection, scalar variance and the nonlinear
-transfers by wavenumber shell (tests/pspec_spectrum_oracle.py).
+transfers by wavenumber shell (tests/pspec_spectrum_oracle.py).  ``set_stochastic_forcing`` / ``ring_forcing`` add a Gaussian, white-in-time force
+on chosen shells, generated on the device inside the step (tests/pspec_stochastic_oracle.py).
 """
 import collections
 import math
@@ -122,10 +123,14 @@ class PeriodicState(object):
     """State of a PeriodicSolver run; owns its device buffers.
     what: the vorticity spectrum, compacted to the kept y-wavenumbers and transposed (float32 [B, my1, nx, 2], include/nns.h: nns_spec_ns_*);
     mean: the conserved mean velocity (U0, V0) per grid, float32 [B, 2]; work: the solver's scratch; steps: steps taken since init;
-    that: the passive scalar's spectrum in the layout of what, its (0, 0) mode (the mean of the scalar) kept, or None without a scalar."""
+    that: the passive scalar's spectrum in the layout of what, its (0, 0) mode (the mean of the scalar) kept, or None without a scalar;
+    clock: int64 [1] on the device, the stochastic steps taken (the step index of the next kick; the step advances it on the device, so a
+    captured step replays); noise_ids: int32 [B] on the device, the grid ids of the noise (default arange(B): grids with equal ids get equal
+    noise, and a single grid with id k repeats member k of a batch).  Both None until a stochastic step needs them."""
 
-    def __init__(self, what, mean, work, that=None):
+    def __init__(self, what, mean, work, that=None, clock=None, noise_ids=None):
         self.what, self.mean, self.work, self.that = what, mean, work, that
+        self.clock, self.noise_ids = clock, noise_ids
         self.steps = 0
 
     @property
@@ -134,7 +139,8 @@ class PeriodicState(object):
 
     def clone(self):
         """A copy with its own buffers (a fresh workspace: the solver keeps no data in it between calls)."""
-        c = PeriodicState(self.what.clone(), self.mean.clone(), torch.empty_like(self.work), None if self.that is None else self.that.clone())
+        copy = lambda t: None if t is None else t.clone()
+        c = PeriodicState(self.what.clone(), self.mean.clone(), torch.empty_like(self.work), copy(self.that), copy(self.clock), copy(self.noise_ids))
         c.steps = self.steps
         return c
 
@@ -174,6 +180,16 @@ class PeriodicSolver(object):
     d energy / dt = power_in - 2 nu enstrophy - 2 drag energy + buoyancy_power; ``buoyancy_spectrum(state)`` gives it per shell and
     ``energy_budget`` adds it.  With b = (0, 0), and for a state without a scalar (theta = 0), every call is the one it is without the argument.
 
+    Stochastic forcing: ``set_stochastic_forcing(rate_by_shell, seed)`` (or ``ring_forcing``) adds a Gaussian force, white in time, on the modes of
+    chosen shells: after every complete deterministic step n (drag, steady force, scalar and buoyancy included, whichever are active)
+        w^_k <- w^_k + sqrt(dt) a_k xi_k(n, id)         E |xi|^2 = 1, independent over modes, steps and grid ids
+    with xi from a counter-based generator (Philox4x32-10, keyed by ``seed``) evaluated inside the step's last launch: still 8 launches per
+    step, capturable, and the eager loop, one call of many steps and graph replay give the same bits.  The noise is additive, so there is no
+    Ito / Stratonovich ambiguity, and the MEAN energy input per shell is known in advance and independent of the state
+    (``stochastic_injection``).  ``state.clock`` counts the steps on the device and ``state.noise_ids`` names the noise of every grid.  The
+    scalar gets no noise.  ``_forced()``, ``diagnostics().power_in`` and ``spectrum().injection`` keep their meaning: the STEADY force only.
+    Without a stochastic force every call is the one it is without this feature.
+
     By wavenumber: the stored modes are binned into shells of width dk = min(2 pi / Lx, 2 pi / Ly) centred on k_s = s dk (``shells()``; an
     elongated box has many).  ``spectrum(state)`` gives energy E(s), enstrophy Z(s), the force's injection F(s) and the scalar's variance V(s),
     whose sums over the shells are the numbers of ``diagnostics`` and ``scalar_diagnostics``; ``transfer(state)`` the nonlinear transfers T(s)
@@ -203,6 +219,9 @@ class PeriodicSolver(object):
             raise ValueError("buoyancy = %r needs a solver built with kappa (the diffusivity of the scalar that is buoyant)" % (self.buoyancy,))
         self.my1 = ops.spec_ns_kept_y(self.ny)
         self.ghat = None                       # the force's vorticity-equation spectrum g^, float32 [Bg, my1, nx, 2] (set_forcing)
+        self.stoch_amp = None                  # the stochastic force's amplitude table a, float32 numpy [my1, nx] (set_stochastic_forcing)
+        self.stoch_seed = 0
+        self._stoch_dev = {}                   # its device copies, by device
         self.last_simulate_used_graph = False
 
     @staticmethod
@@ -261,10 +280,11 @@ class PeriodicSolver(object):
         size = ops.spec_ns_workspace if theta is None else ops.spec_ns_scalar_workspace
         work = torch.empty(size(B, self.nx, self.ny), dtype=torch.uint8, device=u.device)
         ops.spec_ns_init(u, v, what, mean, work, self.Lx, self.Ly)
-        if theta is None:
-            return PeriodicState(what, mean, work)
-        that = ops.spec_ns_scalar_init(theta.to(dev).contiguous(), torch.empty_like(what), work)
-        return PeriodicState(what, mean, work, that)
+        that = None if theta is None else ops.spec_ns_scalar_init(theta.to(dev).contiguous(), torch.empty_like(what), work)
+        state = PeriodicState(what, mean, work, that)
+        if self.stoch_amp is not None:
+            self._noise_of(state)
+        return state
 
     # ---- forcing
     def set_forcing(self, fx, fy=None):
@@ -309,6 +329,95 @@ class PeriodicSolver(object):
     def _forced(self):
         return self.ghat is not None or self.drag > 0
 
+    # ---- stochastic forcing
+    def _shell_table(self):
+        """(shell [my1, nx] int, |k|^2 [my1, nx], kept [my1, nx] bool, wt [my1, 1]) of the stored modes, float64 on the host: the shell predicate
+        floor(|k| / dk + 1/2) of ``shells()``, the step's 2/3 mask without (0, 0), and the weights 1 on j = 0, 2 on j > 0."""
+        S, dk = ops.spec_ns_shells(self.nx, self.ny, self.Lx, self.Ly)
+        mx = np.fft.fftfreq(self.nx) * self.nx
+        j = np.arange(self.my1, dtype=np.float64)
+        kx, ky = (2 * np.pi / self.Lx * mx)[None, :], (2 * np.pi / self.Ly * j)[:, None]
+        k2 = kx * kx + ky * ky
+        shell = np.floor(np.sqrt(k2) / dk + 0.5).astype(np.int64)
+        kept = (3 * np.abs(mx)[None, :] < self.nx) & (k2 > 0)
+        wt = np.where(j == 0, 1.0, 2.0)[:, None]
+        return S, shell, k2, kept, wt
+
+    def shell_mode_counts(self):
+        """float64 numpy [S]: N_s, the number of modes of the full spectrum in every shell that the step keeps (a stored mode with j > 0
+        stands for itself and its conjugate)."""
+        S, shell, k2, kept, wt = self._shell_table()
+        return np.bincount(shell[kept], weights=np.broadcast_to(wt, shell.shape)[kept], minlength=S)[:S]
+
+    def set_stochastic_forcing(self, rate_by_shell, seed=0):
+        """Gaussian white-in-time forcing with the mean energy injection rate ``rate_by_shell`` (float64 [S] over ``shells()``, each >= 0): a shell's
+        rate eps_s is spread over its kept modes with equal energy per mode, a_k = |k| nx ny sqrt(2 eps_s / N_s), N_s = ``shell_mode_counts()``.
+        The table is built on the host in float64 with the shell predicate floor(|k| / dk + 1/2) of ``shells()`` and kept as float32
+        (``self.stoch_amp`` [my1, nx], shared by every grid of a batch).  ``seed``: an int in [0, 2^64), the generator's key; states stepped with
+        the same seed, ``clock`` and ``noise_ids`` get the same noise.  A non-zero rate in a shell without a kept mode raises ValueError.
+        ``set_stochastic_forcing(None)`` removes the forcing."""
+        if rate_by_shell is None:
+            self.stoch_amp, self.stoch_seed, self._stoch_dev = None, 0, {}
+            return self
+        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral):
+            raise TypeError("seed must be an int, got %r" % (seed,))
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed = %d must be in [0, 2^64)" % seed)
+        S, shell, k2, kept, wt = self._shell_table()
+        try:
+            rate = np.array(rate_by_shell, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise TypeError("rate_by_shell must be %d real numbers, got %r" % (S, rate_by_shell))
+        if rate.shape != (S,):
+            raise ValueError("rate_by_shell must have one entry per shell, [%d]; got %s" % (S, rate.shape))
+        if not np.all(np.isfinite(rate)) or np.any(rate < 0):
+            raise ValueError("rate_by_shell must be finite and >= 0")
+        count = self.shell_mode_counts()
+        empty = np.nonzero((rate > 0) & (count == 0))[0]
+        if empty.size:
+            raise ValueError("rate_by_shell is non-zero in shell %d, which holds no kept mode" % empty[0])
+        per_mode = np.where(count > 0, 2.0 * rate / np.maximum(count, 1.0), 0.0)            # 2 eps_s / N_s
+        inside = kept & (shell < S)
+        amp = np.where(inside, np.sqrt(k2) * (self.nx * self.ny) * np.sqrt(per_mode[np.minimum(shell, S - 1)]), 0.0)
+        self.stoch_amp, self.stoch_seed, self._stoch_dev = np.ascontiguousarray(amp, dtype=np.float32), int(seed), {}
+        return self
+
+    def ring_forcing(self, rate, k_lo, k_hi, seed=0):
+        """``set_stochastic_forcing`` on the ring k_lo <= k_s <= k_hi of shell centres (``shells()``): the total mean injection ``rate`` > 0 is
+        shared by those shells in proportion to their mode counts, so every forced mode gets the same energy input."""
+        rate = _real('rate', rate)
+        k_lo, k_hi = _real('k_lo', k_lo, positive=False), _real('k_hi', k_hi, positive=False)
+        k = self.shells()[0]
+        count = np.where((k >= k_lo) & (k <= k_hi), self.shell_mode_counts(), 0.0)
+        if count.sum() == 0:
+            raise ValueError("no kept mode lies in a shell with %r <= k_s <= %r" % (k_lo, k_hi))
+        return self.set_stochastic_forcing(rate * count / count.sum(), seed)
+
+    def stochastic_injection(self):
+        """float64 numpy [S]: the exact mean energy injection rate of the stochastic force per shell, 1/2 sum wt a_k^2 / (|k|^2 (nx ny)^2) over the
+        shell's stored kept modes, recomputed from the float32 table (zeros without the force).  Defined by the HOST's binning, the float64
+        predicate floor(|k| / dk + 1/2) in NumPy: on a box where a mode sits within a rounding of a shell boundary the device's ``spectrum`` could
+        bin it one shell over (with Lx = Ly = 2 pi it cannot: the square root of an integer is never s + 1/2)."""
+        S, shell, k2, kept, wt = self._shell_table()
+        if self.stoch_amp is None:
+            return np.zeros(S)
+        a = self.stoch_amp.astype(np.float64)
+        n2 = float(self.nx * self.ny) ** 2
+        e = np.where(kept, 0.5 * wt * a * a / (np.where(kept, k2, 1.0) * n2), 0.0)
+        return np.bincount(np.minimum(shell, S - 1)[kept], weights=e[kept], minlength=S)[:S]
+
+    def _noise_of(self, state):
+        """(amp, clock, noise_ids) on the state's device for a stochastic step; makes the state's clock (0) and ids (arange(B)) on first use --
+        ``init`` does when the force is already set, so nothing is allocated inside a capture."""
+        dev = state.what.device
+        if state.clock is None:
+            state.clock = torch.zeros(1, dtype=torch.int64, device=dev)
+        if state.noise_ids is None:
+            state.noise_ids = torch.arange(state.batch, dtype=torch.int32, device=dev)
+        if dev not in self._stoch_dev:
+            self._stoch_dev[dev] = torch.from_numpy(self.stoch_amp).to(dev)
+        return self._stoch_dev[dev], state.clock, state.noise_ids
+
     def _force_of(self, state):
         """The force spectrum for this state (None without one); refuses a per-grid force of another batch or device before any launch."""
         g = self.ghat
@@ -324,7 +433,12 @@ class PeriodicSolver(object):
         return state.that is not None and self.buoyancy != (0.0, 0.0)
 
     def _launch_steps(self, state, nsteps):
-        if self._buoyant(state):
+        if self.stoch_amp is not None:
+            amp, clock, ids = self._noise_of(state)
+            ops.spec_ns_step_stochastic_(state.what, state.that, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt,
+                                         self.nu, self.drag, 0.0 if self.kappa is None else self.kappa, self.scalar_gradient, self.buoyancy, amp,
+                                         self.stoch_seed, clock, ids, nsteps)
+        elif self._buoyant(state):
             ops.spec_ns_step_buoyant_(state.what, state.that, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt,
                                       self.nu, self.drag, self.kappa, self.scalar_gradient, self.buoyancy, nsteps)
         elif state.that is not None:
@@ -398,9 +512,12 @@ class PeriodicSolver(object):
 
     def energy_budget(self, state):
         """dE(s)/dt = T_E(s) + F(s) - 2 nu Z(s) - 2 drag E(s), float64 [B, S]: the right-hand side of the energy equation per shell (the
-        viscous term is exact per shell: |k|^2 E_mode = Z_mode); for a buoyant state plus ``buoyancy_spectrum``."""
+        viscous term is exact per shell: |k|^2 E_mode = Z_mode); for a buoyant state plus ``buoyancy_spectrum``.  With a stochastic force it adds
+        ``stochastic_injection()``, the MEAN rate of that force (the same for every grid): the budget of the expectation, not of one realisation."""
         sp, tr = self.spectrum(state), self.transfer(state)
         rhs = tr.energy + sp.injection - 2.0 * self.nu * sp.enstrophy - 2.0 * self.drag * sp.energy
+        if self.stoch_amp is not None:
+            rhs = rhs + torch.from_numpy(self.stochastic_injection()).to(rhs.device)
         return rhs + self.buoyancy_spectrum(state) if self._buoyant(state) else rhs
 
     def buoyancy_power(self, state):
