@@ -535,6 +535,27 @@ int nns_spec_ns_fields_buoyant_f32(const float* what, const float* that, const f
  * nns_spec_ns_spectrum_f32; its errors, plus that == NULL and a non-finite bx, by. */
 int nns_spec_ns_buoyancy_spectrum_f32(const float* what, const float* that, double* out, int nshell, int batch, int nx, int ny, double Lx,
                                       double Ly, double bx, double by, void* stream);
+/* General diagonal linear operator (restatement: tests/pspec_linear_oracle.py): hyperviscosity, hypofriction and the beta effect,
+ *     w_t + u w_x + v w_y + beta v' = nu lap w - nu_h (-lap)^p w - drag w - mu (-lap)^-q w + g + (buoyancy) + (noise)       (v' = v - <v>),
+ * i.e. per mode lambda_k = -(nu |k|^2 + drag + nu_h |k|^2p + mu |k|^-2q) + i beta kx / |k|^2, lambda_(0,0) = 0, integrated exactly by the
+ * Lawson RK4 of the other step entries with the complex factors E = exp(lambda dt / 2), E^2 = exp(lambda dt): the step of
+ * nns_spec_ns_step_stochastic_f32 (force, scalar, buoyancy and noise, whichever are active) with that operator on the vorticity.
+ * lin: float32 [my1][nx][2] (device) = (Re, Im)(lambda_k dt / 2), the layout of one grid of what, shared by the batch; entries off the
+ * kept modes and at (0, 0) are ignored.  nu and drag are not arguments: the table holds them.  Re <= 0 is expected, not checked; Im may be
+ * given modulo 2 pi.  that == NULL: no scalar, and kappa, gx, gy, bx, by are ignored (the scalar's operator stays -kappa |k|^2).  amp, clock
+ * and ids: all NULL (no noise; seed is ignored) or all non-NULL (the kick of nns_spec_ns_step_stochastic_f32 after every complete step).
+ * Still 8 launches per step plus one per call, no allocation, no host synchronisation: capturable.  NNS_ERR_INVALID_ARG for a NULL lin and
+ * for a partial (amp, clock, ids); otherwise the errors and the workspace of nns_spec_ns_step_stochastic_f32. */
+int nns_spec_ns_step_linear_f32(float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work, size_t work_bytes,
+                                int batch, int nx, int ny, double Lx, double Ly, double dt, double kappa, double gx, double gy, double bx,
+                                double by, const float* lin, const float* amp, unsigned long long seed, long long* clock, const int* ids,
+                                int nsteps, void* stream);
+/* out [batch][2][nshell] float64 (device) = the linear term's rates per shell: D_E(s) = sum wt rate_k |w^_k|^2 / |k|^2 / (nx ny)^2 and D_Z(s)
+ * the same without 1 / |k|^2, rate = Re(lambda_k) float64 [my1][nx] (device; the layout of one grid of what, shared by the batch), so that
+ * dE/dt|linear = sum_s D_E(s) and dZ/dt|linear = sum_s D_Z(s); with rate = -(nu |k|^2 + drag) they are -2 nu Z(s) - 2 drag E(s).  One launch,
+ * the shells, order of summation and determinism of nns_spec_ns_spectrum_f32; its errors, plus rate == NULL. */
+int nns_spec_ns_linear_spectrum_f32(const float* what, const double* rate, double* out, int nshell, int batch, int nx, int ny, double Lx,
+                                    double Ly, void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

@@ -3,6 +3,7 @@
 // text rather than a function or a lambda: the unscalared kernels then compile to the instructions they had before there was a scalar
 // (a lambda's body is optimised on its own before it is inlined, and came out a few instructions and registers different).
 // STOCH (ps_col_kernel's note) is false in every kernel without a PsStoch argument, whose text below is then what it was.
+// LINEAR likewise (a PsLinear argument): the vorticity's factors E - 1, E^2 - 1 are then complex, from the table lin, and scal's complex form applies.
 {
         const float2* ph = TH ? Ph + a.fstride : Ph;
         float2* Ws = TH ? Th : W;
@@ -34,10 +35,16 @@
                 const int mx = m < 8 ? e : e - N;
                 // 2/3 rule in x (y: j < my1); the vorticity has no (0, 0) mode, the scalar keeps it (its mean)
                 const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (TH || (mx | lj) != 0);
-                const float kx = a.kx1 * (float)mx;
-                float x = (TH ? hkdt : a.hnudt) * (kx * kx + ky * ky);             // L dt / 2
-                if constexpr (FORCED && !TH) x -= fc.hdrag;
-                const float em1 = expm1f(x), em2 = expm1f(2.f * x);                // E - 1, E^2 - 1
+                [[maybe_unused]] const float kx = a.kx1 * (float)mx;
+                std::conditional_t<LINEAR && !TH, cf, float> em1, em2;             // E - 1, E^2 - 1
+                if constexpr (LINEAR && !TH) {
+                    const float2 l = keep ? lin[(size_t)lj * N + e] : make_float2(0.f, 0.f);   // lambda dt / 2: lane-owned, coalesced, like g^
+                    ps_linear_factors(l, em1, em2);
+                } else {
+                    float x = (TH ? hkdt : a.hnudt) * (kx * kx + ky * ky);         // L dt / 2
+                    if constexpr (FORCED && !TH) x -= fc.hdrag;
+                    em1 = expm1f(x); em2 = expm1f(2.f * x);
+                }
                 cf n = keep ? cf{-z[m].x, -z[m].y} : cf{0.f, 0.f};
                 if constexpr (FORCED && !TH) {
                     const float2 g = gok ? fc.g[gbase + e] : make_float2(0.f, 0.f);

@@ -46,6 +46,16 @@
 // device-side step count (one lane of one workgroup: nothing in that launch reads it), so stage 4 reads n = clock - 1 and a captured step
 // replays.  No further launch, transform or stream; kernels without the PsStoch keep their names and their code.
 //
+// General linear operator (nns_spec_ns_step_linear_f32; restatement: tests/pspec_linear_oracle.py): hyperviscosity, hypofriction and the beta
+// effect are diagonal in Fourier space, so they only change the Lawson factor: lambda_k = -(nu |k|^2 + drag + nu_h |k|^2p + mu |k|^-2q)
+// + i beta kx / |k|^2 comes as the float32 table lin = lambda dt / 2 [my1][nx][2], shared by the batch.  A PsLinear in the column kernel's
+// argument pack (LINEAR) is the compile-time switch, and only stages 1-3 have that form (stage 4 applies no factor: a linear step ends in the
+// forced or the stochastic stage-4 kernel).  There the vorticity's E - 1 and E^2 - 1 are complex: one 8-byte load per mode where the real form
+// computes |k|^2, then one expm1 and one sincospi of the half angle where it has two expm1 (ps_linear_factors).  Exact for any stiffness: no
+// launch, transform or stability limit is added.  nns_spec_ns_linear_spectrum_f32 gives the linear term's rates per shell.
+// Measured on the MI355X (profiles/pspec_linear_run.json): linear / steady-forced step 1.016x at 256^2 x 64 and 1.003x at 1024^2 x 8; the
+// LINEAR kernels hold 132 ... 151 VGPRs (3 waves per SIMD where most forced twins run 4; profiles/pspec_linear_isa.txt), no scratch.
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 #include "nns_common.h"
 #include "fft_lds.h"
@@ -95,11 +105,18 @@ struct PsStoch {          // the last argument of the STOCH column kernels (stag
     const int* ids;       // [B]: the grid ids, the fourth counter word
     float sqdt;           // sqrt(dt)
 };
+struct PsLinear {         // the argument of the LINEAR column kernels (stages 1-3 of a linear step), after PsScalar and before PsStoch
+    const float2* lin;    // (Re, Im)(lambda dt / 2) [my1][nx], the layout of one grid of W, shared by the batch
+};
 template <typename T> __device__ __forceinline__ T only(T t) { return t; }     // the one element of a SCALAR kernel's argument pack
 template <typename T, typename... R> __device__ __forceinline__ T first(T t, R...) { return t; }
 template <typename T, typename... R> __device__ __forceinline__ auto last(T t, R... r) {
     if constexpr (sizeof...(R) == 0) return t;
     else return last(r...);
+}
+template <typename U, typename T, typename... R> __device__ __forceinline__ U pick(T t, R... r) {           // the pack's element of type U
+    if constexpr (std::is_same_v<U, T>) return t;
+    else return pick<U>(r...);
 }
 
 struct PsArgs {
@@ -116,6 +133,25 @@ using cf = C2<float>;
 __device__ __forceinline__ cf scal(float em, cf z) { return {fmaf(em, z.x, z.x), fmaf(em, z.y, z.y)}; }     // (1 + em) z
 __device__ __forceinline__ cf axpy(float a, cf x, cf y) { return {fmaf(a, x.x, y.x), fmaf(a, x.y, y.y)}; }   // a x + y
 __device__ __forceinline__ cf imul(float a, cf z) { return {-a * z.y, a * z.x}; }                            // i a z
+
+__device__ __forceinline__ cf scal(cf em, cf z) {                                                            // (1 + em) z, em complex
+    return {fmaf(-em.y, z.y, fmaf(em.x, z.x, z.x)), fmaf(em.y, z.x, fmaf(em.x, z.y, z.y))};
+}
+
+// E - 1 and E^2 - 1 of E = exp(x + i phi), l = (x, phi) = lambda dt / 2, in the z + (E - 1) z form of the real factors: with the half angle
+// (sh, ch) = sincos(phi / 2), t = 2 sh^2 = 1 - cos phi and s = 2 sh ch = sin phi,
+//     Re(E - 1) = expm1(x) cos phi - 2 sin^2(phi / 2) = expm1(x) (1 - t) - t,      Im(E - 1) = exp(x) sin phi = expm1(x) s + s
+// (no cancellation for small phi; phi = 0 gives the real factor exactly), and E^2 - 1 = (E - 1)(E + 1) from e = E - 1:
+//     Re = e.x (e.x + 2) - e.y^2 = |E|^2 cos^2 phi - 1 - e.y^2 (two terms <= 0 for x <= 0: they cannot cancel),      Im = 2 e.y (e.x + 1)
+// sincospif reduces its argument exactly, so a large phi costs nothing and loses only the rounding of phi / pi.
+__device__ __forceinline__ void ps_linear_factors(float2 l, cf& e1, cf& e2) {
+    float sh, ch;
+    sincospif(l.y * 0.15915494309189535f, &sh, &ch);                  // phi / 2 in units of pi
+    const float s = 2.f * sh * ch, t = 2.f * sh * sh;
+    const float x1 = expm1f(l.x);
+    e1 = {fmaf(x1, 1.f - t, -t), fmaf(x1, s, s)};
+    e2 = {fmaf(e1.x, e1.x + 2.f, -e1.y * e1.y), 2.f * e1.y * (e1.x + 1.f)};
+}
 
 // Philox4x32-10 (Salmon et al., SC'11), outputs 0 and 1 of counter (c0, c1, c2, c3) under key (k0, k1), mapped to one complex standard normal
 // with E |xi|^2 = 1: u1 = ((x0 >> 8) + 1) 2^-24 in (0, 1], u2 = (x1 >> 8) 2^-24 in [0, 1), xi = sqrt(-ln u1) (cos 2 pi u2, sin 2 pi u2).
@@ -247,13 +283,18 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
 // SCALAR: after the vorticity's work on a tile the same sequence runs once more on the scalar: Ph's second field, theta^ / A_theta with
 // L dt / 2 = hkdt |k|^2 (no drag, no force) and a mask that keeps the (0, 0) mode, then G fields 4 and 5.  One field's registers at a time.
 // STOCH (a PsStoch ends the pack; FORCED, S = 1 or 4): S = 1 advances the step count, S = 4 adds the kick to the vorticity's w^ (not the scalar's).
+// LINEAR (a PsLinear in the pack, after PsScalar, before PsStoch; FORCED, S = 1..3): the vorticity's L dt / 2 is the complex table entry
+// lin[j][i], not hnudt |k|^2 - alpha dt / 2 (a.hnudt and fc.hdrag are then unused); the scalar's stays hkdt |k|^2.
 template <int N, int S, bool FORCED = false, bool SCALAR = false, typename... Sc>
 __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, float2* __restrict__ W,
                                                     float2* __restrict__ A, const float* __restrict__ mean, PsArgs a, int emit,
                                                     std::conditional_t<FORCED, PsForce, PsNoForce> fc, Sc... sc) {
     static_assert(!FORCED || S >= 1, "stage 0 only prepares: it has no forced form");
     constexpr bool STOCH = (std::is_same_v<Sc, PsStoch> || ... || false);
-    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (STOCH ? 1 : 0), "PsScalar is the SCALAR kernel's argument, PsStoch after it the STOCH kernel's");
+    constexpr bool LINEAR = (std::is_same_v<Sc, PsLinear> || ... || false);
+    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0),
+                  "PsScalar is the SCALAR kernel's argument, PsLinear after it the LINEAR kernel's, PsStoch last the STOCH kernel's");
+    static_assert(!LINEAR || (FORCED && S >= 1 && S <= 3), "the complex factors are those of stages 1-3 of the forced form");
     static_assert(!STOCH || (FORCED && (S == 1 || S == 4)), "the kick is stage 4's and the step count stage 1's, both of the forced form");
     using L = PsLds<N>;
     constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
@@ -284,6 +325,8 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
             sn0 = (unsigned)n; sn1 = (unsigned)(n >> 32);
         }
     }
+    [[maybe_unused]] const float2* lin = nullptr;
+    if constexpr (LINEAR) lin = pick<PsLinear>(sc...).lin;
     for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
         int tx = threadIdx.x;
         asm volatile("" : "+v"(tx));
@@ -653,6 +696,51 @@ __global__ __launch_bounds__(kT) void ps_buoyancy_shell_kernel(const float2* __r
     }
 }
 
+// out[b][2][nshell] (float64) = the linear term's rates per shell, D_E(s) = sum wt Re(lambda_k) |w^_k|^2 / |k|^2 / (nx ny)^2 and D_Z(s) the same
+// without 1 / |k|^2, so that dE/dt|linear = sum_s D_E and dZ/dt|linear = sum_s D_Z (E and Z carry a 1/2, d|w^|^2/dt = 2 Re(lambda) |w^|^2).
+// rate = Re(lambda) float64 [my1][nx], shared by the batch.  ps_shell_kernel's sibling, as ps_buoyancy_shell_kernel is: its walk, its order
+// of summation and its shuffle tree, so the same determinism.
+__global__ __launch_bounds__(kT) void ps_linear_shell_kernel(const float2* __restrict__ W, const double* __restrict__ rate, double* __restrict__ out,
+                                                             PsShells g, long nunits) {
+    const int lane = threadIdx.x % kWave;
+    const long per = (long)g.my1 * g.nx;
+    for (long u = (long)blockIdx.x * kW + threadIdx.x / kWave; u < nunits; u += (long)gridDim.x * kW) {
+        const long gb = u / g.nshell;
+        const int s = (int)(u % g.nshell);
+        const size_t base = (size_t)gb * per;
+        const double jtop = ((s + 0.5) * g.dk) / g.ky1 + 1.0;
+        const int jend = s == g.nshell - 1 || jtop >= (double)g.my1 ? g.my1 : (int)jtop + 1;
+        double accE = 0., accZ = 0.;
+        for (int j = lane; j < jend; j += kWave) {
+            const int m0 = ps_first_in_shell(g, j, s);
+            const int m1 = s == g.nshell - 1 ? g.kmx + 1 : ps_first_in_shell(g, j, s + 1);
+            const double ky = g.ky1 * j, wt = j == 0 ? 1. : 2.;
+            const size_t row = (size_t)j * g.nx;
+            for (int m = m0; m < m1; ++m) {
+                if ((m | j) == 0) continue;
+                const double kx = g.kx1 * m, ik2 = 1. / (kx * kx + ky * ky);
+                for (int sg = 0; sg < (m == 0 ? 1 : 2); ++sg) {
+                    const size_t q = row + (sg == 0 ? m : g.nx - m);
+                    const float2 w = W[base + q];
+                    const double d = wt * rate[q] * ((double)w.x * w.x + (double)w.y * w.y);
+                    accE += d * ik2;
+                    accZ += d;
+                }
+            }
+        }
+#pragma unroll
+        for (int d = kWave / 2; d > 0; d >>= 1) {
+            accE += __shfl_xor(accE, d, kWave);
+            accZ += __shfl_xor(accZ, d, kWave);
+        }
+        if (lane == 0) {
+            double* o = out + (size_t)gb * 2 * g.nshell + s;
+            o[0] = accE * g.inv_n2;
+            o[g.nshell] = accZ * g.inv_n2;
+        }
+    }
+}
+
 // The column pass of a transfer evaluation: tiling, LDS staging and forward transform of stages S >= 1 of ps_col_kernel; in place of the
 // Lawson update it forms, per stored mode, Re(conj w^ N^) with N^ = -M P^ (the step's mask: `keep` as in pspec_col_pass.inc) and, SCALAR,
 // Re(conj theta^ N_theta^) from Ph's second field, and writes them as float32 modal fields Tw, Tt [B][my1][nx].  It writes neither W nor Th.
@@ -774,10 +862,38 @@ int launch_col_stoch(const float2* Ph, float2* G, float2* W, float2* A, const fl
     return check_launch("spec_ns stochastic column pass");
 }
 
-// st != nullptr (with fc): a stochastic step, whose stages 1 and 4 are the STOCH kernels
+// stages 1-3 of a linear step: the forced kernels with PsScalar (sc), PsLinear and, at stage 1 of a stochastic step, PsStoch (st) in the pack
+template <int N, int S, typename... X>
+int launch_col_pack(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce& fc,
+                    hipStream_t s, X... x) {
+    constexpr bool SC = (std::is_same_v<X, PsScalar> || ... || false);
+    constexpr auto kern = ps_col_kernel<N, S, true, SC, X...>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, fc, x...);
+    return check_launch(SC ? "spec_ns linear scalar column pass" : "spec_ns linear column pass");
+}
+
+template <int N, int S>
+int launch_col_linear(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce& fc,
+                      const PsScalar* sc, const PsLinear& li, const PsStoch* st, hipStream_t s) {
+    if constexpr (S == 1) {
+        if (st) {
+            if (sc) return launch_col_pack<N, S>(Ph, G, W, A, mean, a, emit, fc, s, *sc, li, *st);
+            return launch_col_pack<N, S>(Ph, G, W, A, mean, a, emit, fc, s, li, *st);
+        }
+    }
+    if (sc) return launch_col_pack<N, S>(Ph, G, W, A, mean, a, emit, fc, s, *sc, li);
+    return launch_col_pack<N, S>(Ph, G, W, A, mean, a, emit, fc, s, li);
+}
+
+// st != nullptr (with fc): a stochastic step, whose stages 1 and 4 are the STOCH kernels; li != nullptr (with fc): a linear step, whose
+// stages 1-3 are the LINEAR kernels (stage 4 applies no factor and stays the forced or the STOCH kernel)
 template <int N>
 int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
-                     const PsScalar* sc, hipStream_t s, const PsStoch* st = nullptr) {
+                     const PsScalar* sc, hipStream_t s, const PsStoch* st = nullptr, const PsLinear* li = nullptr) {
+    if (li && S == 1) return launch_col_linear<N, 1>(Ph, G, W, A, mean, a, emit, *fc, sc, *li, st, s);
+    if (li && S == 2) return launch_col_linear<N, 2>(Ph, G, W, A, mean, a, emit, *fc, sc, *li, nullptr, s);
+    if (li && S == 3) return launch_col_linear<N, 3>(Ph, G, W, A, mean, a, emit, *fc, sc, *li, nullptr, s);
     if (st && S == 1) return launch_col_stoch<N, 1>(Ph, G, W, A, mean, a, emit, *fc, sc, *st, s);
     if (st && S == 4) return launch_col_stoch<N, 4>(Ph, G, W, A, mean, a, emit, *fc, sc, *st, s);
     if (fc && S >= 1) {
@@ -922,6 +1038,17 @@ NNS_API int nns_spec_ns_buoyancy_spectrum_f32(const float* what, const float* th
     return check_launch("spec_ns_buoyancy_spectrum");
 }
 
+NNS_API int nns_spec_ns_linear_spectrum_f32(const float* what, const double* rate, double* out, int nshell, int batch, int nx, int ny, double Lx,
+                                            double Ly, void* stream) {
+    if (!what || !rate || !out || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_linear_spectrum: NULL pointer or batch < 1");
+    PsShells g;
+    if (int rc = check_shells("spec_ns_linear_spectrum", nx, ny, Lx, Ly, nshell, &g)) return rc;
+    const long nunits = (long)batch * g.nshell;
+    hipLaunchKernelGGL(ps_linear_shell_kernel, dim3(capped_grid((nunits + kW - 1) / kW, 8 * kGridCap)), dim3(kT), 0, as_stream(stream),
+                       reinterpret_cast<const float2*>(what), rate, out, g, nunits);
+    return check_launch("spec_ns_linear_spectrum");
+}
+
 NNS_API int nns_spec_ns_transfer_f32(const float* what, const float* that, double* out, int nshell, void* work, size_t work_bytes_, int batch,
                                      int nx, int ny, double Lx, double Ly, void* stream) {
     if (!what || !out || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_transfer: NULL pointer or batch < 1");
@@ -987,10 +1114,12 @@ NNS_API int nns_spec_ns_init_f32(const float* u, const float* v, float* what, fl
 }
 
 // The step of every entry point: ghat == NULL and drag == 0 launch the unforced kernels, that == NULL the unscalared ones, b == 0 the passive ones;
-// st != NULL (amp, key, clock, ids; its sqdt is set here) takes the forced path, with or without ghat and drag, and kicks after every step.
+// st != NULL (amp, key, clock, ids; its sqdt is set here) takes the forced path, with or without ghat and drag, and kicks after every step;
+// lin != NULL takes the forced path too, with the table's factors in stages 1-3 (nu and drag are then unused: the table holds them).
 static int spec_ns_step(const char* who, float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work,
                         size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa,
-                        double gx, double gy, double bx, double by, int nsteps, void* stream, const PsStoch* st = nullptr) {
+                        double gx, double gy, double bx, double by, int nsteps, void* stream, const PsStoch* st = nullptr,
+                        const float* lin = nullptr) {
     if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
     if (!(dt > 0) || !std::isfinite(dt) || !(nu >= 0) || !std::isfinite(nu) || nsteps < 0)
         return fail(NNS_ERR_INVALID_ARG, "%s: dt = %g must be > 0, nu = %g >= 0, nsteps = %d >= 0", who, dt, nu, nsteps);
@@ -1014,7 +1143,9 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
     PsArgs ar = ac;
     ar.nlines = (long)batch * nx;
     const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
-    const PsForce* fc = ghat || drag > 0 || st ? &force : nullptr;
+    const PsForce* fc = ghat || drag > 0 || st || lin ? &force : nullptr;
+    const PsLinear linear{reinterpret_cast<const float2*>(lin)};
+    const PsLinear* li = lin ? &linear : nullptr;
     PsStoch stoch{};
     if (st) {
         stoch = *st;
@@ -1027,7 +1158,7 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
     const PsGrad* gr = that ? &grad : nullptr;
     const PsBuoyGrad buoy{(float)gx, (float)gy, (float)(-(double)ny * by), (float)((double)ny * bx)};
     const PsBuoyGrad* bu = that && (bx != 0.0 || by != 0.0) ? &buoy : nullptr;
-    auto col = [&](int S, int emit) { return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, fc, sc, s, stc); }); };
+    auto col = [&](int S, int emit) { return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, fc, sc, s, stc, li); }); };
     auto row = [&]() { return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, gr, s, bu); }); };
     if (int rc = col(0, 1)) return rc;
     for (int k = 0; k < nsteps; ++k) {
@@ -1076,6 +1207,20 @@ NNS_API int nns_spec_ns_step_stochastic_f32(float* what, float* that, const floa
     const PsStoch st{amp, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), clock, ids, 0.f};
     return spec_ns_step("spec_ns_step_stochastic", what, that, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, nu, drag,
                         that ? kappa : 0.0, that ? gx : 0.0, that ? gy : 0.0, that ? bx : 0.0, that ? by : 0.0, nsteps, stream, &st);
+}
+
+NNS_API int nns_spec_ns_step_linear_f32(float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work, size_t work_bytes_,
+                                        int batch, int nx, int ny, double Lx, double Ly, double dt, double kappa, double gx, double gy, double bx,
+                                        double by, const float* lin, const float* amp, unsigned long long seed, long long* clock, const int* ids,
+                                        int nsteps, void* stream) {
+    if (!lin) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_linear: lin must be non-NULL");
+    const bool noise = amp && clock && ids;
+    if (!noise && (amp || clock || ids))
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_linear: amp, clock and ids must be all NULL (no noise) or all non-NULL");
+    const PsStoch st{amp, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), clock, ids, 0.f};
+    return spec_ns_step("spec_ns_step_linear", what, that, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, 0.0, 0.0,
+                        that ? kappa : 0.0, that ? gx : 0.0, that ? gy : 0.0, that ? bx : 0.0, that ? by : 0.0, nsteps, stream,
+                        noise ? &st : nullptr, lin);
 }
 
 NNS_API int nns_spec_ns_scalar_workspace(int batch, int nx, int ny, size_t* bytes) {

@@ -93,6 +93,8 @@ _SINGLE = {
     'nns_spec_ns_step_stochastic_f32': [_P] * 4 + [_I, _P, _SZ] + [_I] * 3 + [_D] * 10 + [_P, C.c_uint64, _P, _P, _I, _P],
     'nns_spec_ns_fields_buoyant_f32': [_P] * 7 + [_SZ] + [_I] * 3 + [_D] * 5 + [_P],
     'nns_spec_ns_buoyancy_spectrum_f32': [_P] * 3 + [_I] * 4 + [_D] * 4 + [_P],
+    'nns_spec_ns_step_linear_f32': [_P] * 4 + [_I, _P, _SZ] + [_I] * 3 + [_D] * 8 + [_P, _P, C.c_uint64, _P, _P, _I, _P],
+    'nns_spec_ns_linear_spectrum_f32': [_P] * 3 + [_I] * 4 + [_D] * 2 + [_P],
     'nns_pixel_mlp_fwd_f32': [_P] * 4 + [_I, _I, C.POINTER(C.c_int), _I, _I, _P],
     'nns_pixel_mlp_bwd_workspace': [C.POINTER(C.c_int), _I, C.POINTER(C.c_size_t)],
     'nns_pixel_mlp_bwd_f32': [_P] * 7 + [_I, _I, C.POINTER(C.c_int), _I, _I, _P, C.c_size_t, _P],

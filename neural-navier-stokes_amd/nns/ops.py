@@ -1175,6 +1175,70 @@ def spec_ns_buoyancy_spectrum(what, that, ny, Lx, Ly, buoyancy, out=None):
     return out
 
 
+# general linear operator of the periodic solver (nns_spec_ns_step_linear_f32, nns_spec_ns_linear_spectrum_f32)
+def spec_ns_step_linear_(what, that, mean, ghat, work, ny, Lx, Ly, dt, kappa, grad, buoyancy, lin, amp=None, seed=0, clock=None, ids=None,
+                         nsteps=1):
+    """nsteps steps of spec_ns_step_stochastic_ (that None: no scalar; amp, clock and ids all None: no noise) with the vorticity's linear
+    operator taken from lin, float32 [my1, nx, 2] = (Re, Im)(lambda dt / 2) on the state's device (shared by the batch), which holds viscosity
+    and drag: neither is an argument.  No allocation, no host synchronisation: capturable."""
+    who = 'spec_ns_step_linear_'
+    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
+    if that is not None:
+        _spec_ns_same(who, that, what)
+    gbatch = _spec_ns_force(who, ghat, what)
+    _f32(lin)
+    if tuple(lin.shape) != (my1, nx, 2):
+        raise ValueError("%s: lin must be float32 [%d, %d, 2], got %s" % (who, my1, nx, tuple(lin.shape)))
+    if lin.device != what.device:
+        raise ValueError("%s: lin must be on the state's device %s" % (who, what.device))
+    noise = (amp, clock, ids)
+    if any(t is None for t in noise):
+        if any(t is not None for t in noise):
+            raise ValueError("%s: amp, clock and ids must be all None (no noise) or all given" % who)
+    else:
+        _f32(amp)
+        if tuple(amp.shape) != (my1, nx):
+            raise ValueError("%s: amp must be float32 [%d, %d], got %s" % (who, my1, nx, tuple(amp.shape)))
+        for name, t, dtype, shape in (('clock', clock, torch.int64, (1,)), ('ids', ids, torch.int32, (B,))):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+                raise TypeError("%s: %s must be a contiguous %s device tensor" % (who, name, dtype))
+            if tuple(t.shape) != shape:
+                raise ValueError("%s: %s must be %s %s, got %s" % (who, name, dtype, list(shape), tuple(t.shape)))
+        if any(t.device != what.device for t in noise):
+            raise ValueError("%s: amp, clock and ids must be on the state's device %s" % (who, what.device))
+        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral):
+            raise TypeError("%s: seed must be an int, got %r" % (who, seed))
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("%s: seed = %d must be in [0, 2^64)" % (who, seed))
+    (gx, gy), (bx, by) = grad, buoyancy
+    opt = lambda t: None if t is None else _p(t)
+    check(_lib.lib().nns_spec_ns_step_linear_f32(_p(what), opt(that), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(work), work.numel(), B,
+                                                 nx, int(ny), float(Lx), float(Ly), float(dt), float(kappa), float(gx), float(gy), float(bx),
+                                                 float(by), _p(lin), opt(amp), int(seed), opt(clock), opt(ids), int(nsteps), _stream()),
+          'nns_spec_ns_step_linear_f32')
+    return what
+
+
+def spec_ns_linear_spectrum(what, rate, ny, Lx, Ly, out=None):
+    """float64 [B, 2, nshell]: (D_E, D_Z) per shell, the rates at which the linear term changes energy and enstrophy; rate = Re(lambda)
+    float64 [my1, nx] on the state's device."""
+    who = 'spec_ns_linear_spectrum'
+    B, my1, nx = _spec_ns_state(who, what, None, None, ny)
+    if not (isinstance(rate, torch.Tensor) and rate.is_cuda and rate.dtype == torch.float64 and rate.is_contiguous()):
+        raise TypeError("%s: rate must be a contiguous float64 device tensor" % who)
+    if tuple(rate.shape) != (my1, nx) or rate.device != what.device:
+        raise ValueError("%s: rate must be float64 [%d, %d] on the state's device, got %s on %s" % (who, my1, nx, tuple(rate.shape), rate.device))
+    S = spec_ns_shells(nx, ny, Lx, Ly)[0]
+    if out is None:
+        out = torch.empty((B, 2, S), dtype=torch.float64, device=what.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (B, 2, S) and out.is_contiguous()
+              and out.device == what.device):
+        raise ValueError("%s: out must be a contiguous float64 [%d, 2, %d] tensor on the state's device" % (who, B, S))
+    check(_lib.lib().nns_spec_ns_linear_spectrum_f32(_p(what), _p(rate), _p(out), S, B, nx, int(ny), float(Lx), float(Ly), _stream()),
+          'nns_spec_ns_linear_spectrum_f32')
+    return out
+
+
 # ----------------------------------------------------------------------------- physics-informed loss head
 _PINN_WS = {}
 

@@ -20,7 +20,9 @@ otherwise, 2 = float64 forward transforms always.
 (tests/pspec_forced_oracle.py) and with a passive scalar -- temperature, dye -- that the same fused step transports
 (tests/pspec_scalar_oracle.py) and that, with ``buoyancy``, acts back on the flow (tests/pspec_buoyant_oracle.py).  Its ``spectrum`` and ``transfer`` give energy, enstrophy, injection, scalar variance and the nonlinear
 transfers by wavenumber shell (tests/pspec_spectrum_oracle.py).  ``set_stochastic_forcing`` / ``ring_forcing`` add a Gaussian, white-in-time force
-on chosen shells, generated on the device inside the step (tests/pspec_stochastic_oracle.py).
+on chosen shells, generated on the device inside the step (tests/pspec_stochastic_oracle.py).  ``hyperviscosity``, ``hypofriction`` and ``beta``
+generalise the linear operator that the Lawson factor integrates exactly, at no launch, transform or stability limit (tests/pspec_linear_oracle.py;
+measured on the MI355X 1.016x the steady-forced step at 256^2 x 64 and 1.003x at 1024^2 x 8, profiles/pspec_linear_run.json).
 """
 import collections
 import math
@@ -111,6 +113,7 @@ Diagnostics = collections.namedtuple('Diagnostics', ['energy', 'enstrophy', 'pow
 ScalarDiagnostics = collections.namedtuple('ScalarDiagnostics', ['variance', 'dissipation', 'flux_x', 'flux_y'])
 Spectrum = collections.namedtuple('Spectrum', ['k', 'energy', 'enstrophy', 'injection', 'variance'])
 Transfer = collections.namedtuple('Transfer', ['k', 'energy', 'enstrophy', 'variance'])
+LinearRates = collections.namedtuple('LinearRates', ['k', 'energy', 'enstrophy'])
 
 
 def flux(t):
@@ -190,15 +193,28 @@ class PeriodicSolver(object):
     scalar gets no noise.  ``_forced()``, ``diagnostics().power_in`` and ``spectrum().injection`` keep their meaning: the STEADY force only.
     Without a stochastic force every call is the one it is without this feature.
 
+    Linear operator: ``hyperviscosity`` = (nu_h, p), ``hypofriction`` = (mu, q) and ``beta`` add the three standard linear terms of forced 2-D and
+    geophysical turbulence to the vorticity equation,
+        w_t + u w_x + v w_y + beta v' = nu lap w - nu_h (-lap)^p w - drag w - mu (-lap)^-q w + g + (buoyancy) + (noise),      v' = v - <v>
+    (beta <v> would be a constant source in the (0, 0) mode, which the periodic box cannot hold: it is dropped, as ``init`` and ``set_forcing``
+    drop such parts, and the mean velocity stays conserved).  All three are diagonal in Fourier space: mode k has
+        lambda_k = -(nu |k|^2 + drag + nu_h |k|^2p + mu |k|^-2q) + i beta kx / |k|^2,        lambda_(0,0) = 0       (``linear_operator()``)
+    and the Lawson RK4 integrates it exactly with the complex factors exp(lambda dt / 2), exp(lambda dt): no stiffness limit on nu_h K^2p dt or
+    beta dt / k, no further launch (still 8 per step) or transform.  A plane wave is an exact solution: a Rossby wave of frequency
+    -beta kx / |k|^2 (westward) and amplitude exp(Re(lambda) t).  The scalar keeps its operator kappa |k|^2.  The step reads lambda dt / 2 from
+    a float32 table made at construction from the arguments as they are then, shared by the batch.  ``linear_spectrum(state)`` gives the
+    linear term's energy and enstrophy rates per shell (beta contributes to neither) and ``energy_budget`` uses it.  With nu_h = 0, mu = 0 and
+    beta = 0 every call is the one it is without these arguments.
+
     By wavenumber: the stored modes are binned into shells of width dk = min(2 pi / Lx, 2 pi / Ly) centred on k_s = s dk (``shells()``; an
     elongated box has many).  ``spectrum(state)`` gives energy E(s), enstrophy Z(s), the force's injection F(s) and the scalar's variance V(s),
     whose sums over the shells are the numbers of ``diagnostics`` and ``scalar_diagnostics``; ``transfer(state)`` the nonlinear transfers T(s)
     of energy, enstrophy and scalar variance from one evaluation of the step's own dealiased nonlinear term (each sums to zero), ``flux`` their
-    cumulative form Pi(s), and ``energy_budget(state)`` dE(s)/dt = T_E + F - 2 nu Z - 2 drag E.  All float64, summed on the device in a fixed
+    cumulative form Pi(s), and ``energy_budget(state)`` dE(s)/dt = T_E + F - 2 nu Z - 2 drag E (T_E + F + D_E with the general linear operator).  All float64, summed on the device in a fixed
     order.  The spectrum of arbitrary fields -- a model's prediction, say -- is ``solver.spectrum(solver.init(u, v))``."""
 
     def __init__(self, nx, ny, dt, rho, nu, Lx=2 * math.pi, Ly=2 * math.pi, drag=0.0, kappa=None, scalar_gradient=(0.0, 0.0),
-                 buoyancy=(0.0, 0.0)):
+                 buoyancy=(0.0, 0.0), hyperviscosity=None, hypofriction=None, beta=0.0):
         self.nx, self.ny = _pow2_axis('nx', nx), _pow2_axis('ny', ny)
         self.dt, self.rho = _real('dt', dt), _real('rho', rho)
         self.nu = _real('nu', nu, positive=False)
@@ -217,7 +233,12 @@ class PeriodicSolver(object):
         self.buoyancy = tuple(self._finite('buoyancy', b) for b in (bx, by))
         if self.buoyancy != (0.0, 0.0) and self.kappa is None:
             raise ValueError("buoyancy = %r needs a solver built with kappa (the diffusivity of the scalar that is buoyant)" % (self.buoyancy,))
+        self.hyperviscosity = self._power_term('hyperviscosity', hyperviscosity, 'nu_h', 'p', 2, 8)
+        self.hypofriction = self._power_term('hypofriction', hypofriction, 'mu', 'q', 1, 4)
+        self.beta = self._finite('beta', beta)
         self.my1 = ops.spec_ns_kept_y(self.ny)
+        self._lin = self._linear_table() if self._linear() else None      # (Re, Im)(lambda dt / 2), float32 numpy [my1, nx, 2]
+        self._lin_dev, self._rate_dev = {}, {}                              # its device copies and those of Re(lambda) (float64), by device
         self.ghat = None                       # the force's vorticity-equation spectrum g^, float32 [Bg, my1, nx, 2] (set_forcing)
         self.stoch_amp = None                  # the stochastic force's amplitude table a, float32 numpy [my1, nx] (set_stochastic_forcing)
         self.stoch_seed = 0
@@ -231,6 +252,22 @@ class PeriodicSolver(object):
         if not math.isfinite(x):
             raise ValueError("%s = %r must be finite" % (name, x))
         return float(x)
+
+    @staticmethod
+    def _power_term(name, term, coef, power, lo, hi):
+        """(coefficient, exponent) of ``hyperviscosity`` / ``hypofriction``; None: (0.0, lo)."""
+        if term is None:
+            return 0.0, lo
+        try:
+            c, n = term
+        except (TypeError, ValueError):
+            raise TypeError("%s must be None or (%s, %s), got %r" % (name, coef, power, term))
+        c = _real('%s of %s' % (coef, name), c, positive=False)
+        if isinstance(n, bool) or not isinstance(n, numbers.Integral):
+            raise TypeError("%s of %s must be an int, got %r" % (power, name, n))
+        if not lo <= n <= hi:
+            raise ValueError("%s of %s = %d must be in [%d, %d]" % (power, name, n, lo, hi))
+        return c, int(n)
 
     def _field(self, name, a):
         if isinstance(a, np.ndarray):
@@ -284,6 +321,8 @@ class PeriodicSolver(object):
         state = PeriodicState(what, mean, work, that)
         if self.stoch_amp is not None:
             self._noise_of(state)
+        if self._linear():
+            self._linear_of(state)
         return state
 
     # ---- forcing
@@ -418,6 +457,58 @@ class PeriodicSolver(object):
             self._stoch_dev[dev] = torch.from_numpy(self.stoch_amp).to(dev)
         return self._stoch_dev[dev], state.clock, state.noise_ids
 
+    # ---- linear operator
+    def _linear(self):
+        """Hyperviscosity, hypofriction or beta is active: the step takes the general linear form."""
+        return self.hyperviscosity[0] > 0 or self.hypofriction[0] > 0 or self.beta != 0.0
+
+    def linear_operator(self):
+        """complex128 numpy [my1, nx], the layout of one grid of ``what``: lambda_k of the class note on the kept modes, 0 elsewhere and at (0, 0).
+        Built on the host in float64; without the new terms it is -(nu |k|^2 + drag)."""
+        S, shell, k2, kept, wt = self._shell_table()
+        kx = np.broadcast_to((2 * np.pi / self.Lx * (np.fft.fftfreq(self.nx) * self.nx))[None, :], k2.shape)
+        k2 = np.where(kept, k2, 1.0)
+        (nu_h, p), (mu, q) = self.hyperviscosity, self.hypofriction
+        with np.errstate(over='ignore', invalid='ignore'):
+            damp = self.nu * k2 + self.drag
+            if nu_h > 0:
+                damp = damp + nu_h * k2 ** p
+            if mu > 0:
+                damp = damp + mu * k2 ** (-q)
+            lam = -damp + 1j * (self.beta * kx / k2)
+        return np.where(kept, lam, 0.0)
+
+    def _linear_table(self):
+        """float32 numpy [my1, nx, 2] = (Re, Im)(lambda dt / 2), what the step reads; the angle is taken into [-pi, pi] in float64 first, which
+        exp(lambda dt / 2) and exp(lambda dt) do not see and which keeps its float32 rounding small where beta dt / k is large."""
+        with np.errstate(over='ignore', invalid='ignore'):
+            half = self.linear_operator() * (0.5 * self.dt)
+            table = np.stack([half.real, np.remainder(half.imag + np.pi, 2 * np.pi) - np.pi], axis=-1).astype(np.float32)
+        if not np.all(np.isfinite(table)):
+            raise ValueError("hyperviscosity = %r, hypofriction = %r, beta = %r: lambda dt / 2 is not finite in float32 on some kept mode"
+                             % (self.hyperviscosity, self.hypofriction, self.beta))
+        return np.ascontiguousarray(table)
+
+    def _linear_of(self, state):
+        """The table on the state's device (``init`` makes it, so nothing is allocated inside a capture)."""
+        dev = state.what.device
+        if dev not in self._lin_dev:
+            self._lin_dev[dev] = torch.from_numpy(self._lin).to(dev)
+        return self._lin_dev[dev]
+
+    def linear_spectrum(self, state):
+        """LinearRates(k, energy, enstrophy), float64 [B, S] device tensors over ``shells()``: the rates at which the linear term changes the
+        energy and the enstrophy of every shell, D_E(s) = sum wt Re(lambda_k) |w^_k|^2 / |k|^2 / (nx ny)^2 and D_Z(s) the same without 1 / |k|^2
+        (weights and order of summation those of ``spectrum``), so that dE/dt|linear = sum_s D_E and dZ/dt|linear = sum_s D_Z.  beta contributes
+        to neither (Im(lambda) only rotates a mode).  Works on any solver: without the new terms it is -2 nu Z(s) - 2 drag E(s) to rounding.
+        Re(lambda) is taken from ``linear_operator()`` when first needed on a device.  Only reads the state."""
+        self._state(state)
+        dev = state.what.device
+        if dev not in self._rate_dev:
+            self._rate_dev[dev] = torch.from_numpy(np.ascontiguousarray(self.linear_operator().real)).to(dev)
+        out = ops.spec_ns_linear_spectrum(state.what, self._rate_dev[dev], self.ny, self.Lx, self.Ly)
+        return LinearRates(self.shells()[0], out[:, 0], out[:, 1])
+
     def _force_of(self, state):
         """The force spectrum for this state (None without one); refuses a per-grid force of another batch or device before any launch."""
         g = self.ghat
@@ -433,7 +524,12 @@ class PeriodicSolver(object):
         return state.that is not None and self.buoyancy != (0.0, 0.0)
 
     def _launch_steps(self, state, nsteps):
-        if self.stoch_amp is not None:
+        if self._linear():
+            amp, clock, ids = (None, None, None) if self.stoch_amp is None else self._noise_of(state)
+            ops.spec_ns_step_linear_(state.what, state.that, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt,
+                                     0.0 if self.kappa is None else self.kappa, self.scalar_gradient, self.buoyancy, self._linear_of(state), amp,
+                                     self.stoch_seed, clock, ids, nsteps)
+        elif self.stoch_amp is not None:
             amp, clock, ids = self._noise_of(state)
             ops.spec_ns_step_stochastic_(state.what, state.that, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt,
                                          self.nu, self.drag, 0.0 if self.kappa is None else self.kappa, self.scalar_gradient, self.buoyancy, amp,
@@ -461,7 +557,8 @@ class PeriodicSolver(object):
     def diagnostics(self, state):
         """Diagnostics(energy, enstrophy, power_in), each float64 [B], computed on the device from the state's spectrum:
         energy = 1/2 <|u - <u>|^2> (the total is energy + (U0^2 + V0^2) / 2), enstrophy = 1/2 <w^2>, power_in = <f_s . u> (exactly 0
-        without a force), so that d energy / dt = power_in - 2 nu enstrophy - 2 drag energy."""
+        without a force), so that d energy / dt = power_in - 2 nu enstrophy - 2 drag energy; with the general linear operator of the class note
+        d energy / dt = power_in + sum_s D_E(s), D_E of ``linear_spectrum``, which holds on every solver."""
         self._state(state)
         out = ops.spec_ns_diag(state.what, self._force_of(state), self.ny, self.Lx, self.Ly)
         return Diagnostics(out[:, 0], out[:, 1], out[:, 2])
@@ -513,9 +610,13 @@ class PeriodicSolver(object):
     def energy_budget(self, state):
         """dE(s)/dt = T_E(s) + F(s) - 2 nu Z(s) - 2 drag E(s), float64 [B, S]: the right-hand side of the energy equation per shell (the
         viscous term is exact per shell: |k|^2 E_mode = Z_mode); for a buoyant state plus ``buoyancy_spectrum``.  With a stochastic force it adds
-        ``stochastic_injection()``, the MEAN rate of that force (the same for every grid): the budget of the expectation, not of one realisation."""
+        ``stochastic_injection()``, the MEAN rate of that force (the same for every grid): the budget of the expectation, not of one realisation.
+        With hyperviscosity, hypofriction or beta the linear terms are D_E(s) of ``linear_spectrum``: dE(s)/dt = T_E(s) + F(s) + D_E(s) (+ ...)."""
         sp, tr = self.spectrum(state), self.transfer(state)
-        rhs = tr.energy + sp.injection - 2.0 * self.nu * sp.enstrophy - 2.0 * self.drag * sp.energy
+        if self._linear():
+            rhs = tr.energy + sp.injection + self.linear_spectrum(state).energy
+        else:
+            rhs = tr.energy + sp.injection - 2.0 * self.nu * sp.enstrophy - 2.0 * self.drag * sp.energy
         if self.stoch_amp is not None:
             rhs = rhs + torch.from_numpy(self.stochastic_injection()).to(rhs.device)
         return rhs + self.buoyancy_spectrum(state) if self._buoyant(state) else rhs
@@ -594,6 +695,8 @@ class PeriodicSolver(object):
         """A ResidualEngine with this solver's constants, for frames ``every`` steps apart (its dt = every * dt).  The engine knows neither
         force nor drag: on the frames of a forced run its momentum residuals converge (as dt -> 0) to f_s - drag (u - <u>), the right-hand
         side of the class note, rather than to zero; subtract that (``forcing_fields``) to measure the discretisation alone.  Likewise on
-        buoyant frames the momentum residual converges to b theta' (plus the forced terms), theta' = ``scalar`` minus its grid mean."""
+        buoyant frames the momentum residual converges to b theta' (plus the forced terms), theta' = ``scalar`` minus its grid mean, and on
+        frames of a run with hyperviscosity, hypofriction or beta to those extra linear terms: -(nu_h (-lap)^p + mu (-lap)^-q) (u - <u>) and
+        the solenoidal part of (0, beta psi), psi the streamfunction (u = psi_y, v = -psi_x), the force whose curl is -beta v'."""
         every = _count('every', every, 1)
         return ResidualEngine(self.nx, self.ny, self.dt * every, self.rho, self.nu, self.Lx, self.Ly, backend=backend, precise=precise)
