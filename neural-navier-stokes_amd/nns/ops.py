@@ -737,19 +737,30 @@ def _pixel_mlp_pack(x, weights, biases, what):
     return mb, P, ws, widths, wp, bp
 
 
-def pixel_mlp_bwd(x, gy, weights, biases, bf16=True):
+def pixel_mlp_bwd(x, gy, weights, biases, bf16=True, out=None, workspace=None):
     """Backward of pixel_mlp_fwd: returns (gx like x, [gW_l like weights[l]], [gb_l like biases[l]]).
-    bf16=False (float32 operands) supports widths <= 32."""
+    bf16=False (float32 operands) supports widths <= 32.
+    out: (gx like x, gW and gB packed like the weights and the biases) to write into instead of new tensors -- overwritten, not accumulated;
+    workspace: a contiguous tensor to use as scratch, whatever it holds (nns_pixel_mlp_bwd_workspace bytes at least: a smaller one is an error)."""
     mb, P, ws, widths, wp, bp = _pixel_mlp_pack(x, weights, biases, 'pixel_mlp_bwd')
     _f32(gy)
     if tuple(gy.shape) != (mb, widths[-1]) + tuple(x.shape[2:]):
         raise ValueError("pixel_mlp_bwd: gy has shape %s, expected %s" % (tuple(gy.shape), (mb, widths[-1]) + tuple(x.shape[2:])))
     arr = (ctypes.c_int * len(widths))(*widths)
-    nbytes = _query_bytes('nns_pixel_mlp_bwd_workspace', arr, len(ws))
-    work = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=x.device)
-    gx = torch.empty_like(x)
-    gW = torch.empty_like(wp)
-    gB = torch.empty_like(bp)
+    if workspace is None:
+        nbytes = _query_bytes('nns_pixel_mlp_bwd_workspace', arr, len(ws))
+        work = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=x.device)
+    else:
+        if not (workspace.is_cuda and workspace.is_contiguous()):
+            raise TypeError("pixel_mlp_bwd: workspace must be a contiguous CUDA/HIP tensor")
+        work, nbytes = workspace, workspace.numel() * workspace.element_size()
+    if out is None:
+        gx, gW, gB = torch.empty_like(x), torch.empty_like(wp), torch.empty_like(bp)
+    else:
+        gx, gW, gB = out
+        _f32(gx, gW, gB)
+        if gx.shape != x.shape or gW.shape != wp.shape or gB.shape != bp.shape:
+            raise ValueError("pixel_mlp_bwd: out must be (gx like x, gW [%d], gB [%d])" % (wp.numel(), bp.numel()))
     check(_lib.lib().nns_pixel_mlp_bwd_f32(_p(x), _p(gy), _p(wp), _p(bp), _p(gx), _p(gW), _p(gB), mb, P, arr, len(ws), int(bool(bf16)),
                                            _p(work), nbytes, _stream()), 'nns_pixel_mlp_bwd_f32')
     gws, gbs, wo, bo = [], [], 0, 0
@@ -766,6 +777,7 @@ class PixelMlpFn(torch.autograd.Function):
     def forward(ctx, x, nlayers, bf16, *params):
         weights, biases = params[:nlayers], params[nlayers:]
         ctx.nlayers, ctx.bf16 = nlayers, bool(bf16)
+        x = x.contiguous()
         ctx.save_for_backward(x, *params)
         return pixel_mlp_fwd(x, weights, biases, bf16=bf16)
 

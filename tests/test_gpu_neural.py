@@ -236,7 +236,8 @@ def test_pixel_mlp_backward_random_and_autograd(gpu_device):
     with the kernel's bf16 operand rounding emulated -- what is left (5e-3 at depth 8) are operands that fall on the
     other side of a bf16 rounding boundary, or a ReLU mask that flips, because the kernel accumulates in float32 and the
     oracle exactly; a loose sanity bound against the unrounded oracle; then the autograd node used for training.
-    (Indexing is pinned bit-exactly by test_pixel_mlp_backward_exact_integers.)"""
+    (Indexing is pinned bit-exactly by test_pixel_mlp_backward_exact_integers and, on every kernel path, pixel-count edge and
+    reduce slice count, by tests/test_gpu_pixel_mlp_backward.py, which also holds random data to bounds derived from the reference.)"""
     from nns import ops
     from nns.neural_spectral.spectral_ode import PixelMLP
     from oracle import neural as ON

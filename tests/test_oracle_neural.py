@@ -302,3 +302,111 @@ def test_elu_points_cover_what_elu1_branches_on():
     assert rel.max() < 2.4e-7                       # two float32 roundings
     lin = np.where(z > OC.ELU_EXACT_MINUS_ONE, np.where(z > -1e-3, z, np.expm1(z.astype(np.float64))), -1).astype(np.float32)      # first order near 0
     assert OC.elu_errors(z, lin)[0].max() > 100 * OC.ELU_REL
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The per-pixel MLP backward's cases (tests/pm_bwd_cases.py; tests/test_gpu_pixel_mlp_backward.py holds the HIP kernels to them), on the
+# reference alone.
+def test_pixel_mlp_bwd_cases_reach_every_path():
+    """path_of_bwd puts every listed stack on the path it is listed under; each path has its primary stack at every pixel count in both
+    families, an odd and an even layer count at 131 074 pixels, and the reduce kernel's slice counts."""
+    import pm_bwd_cases as BC
+    import pm_cases as PC
+    for path in BC.PATHS:
+        bf16 = path[0] == 'S'
+        for dims in [d for d, _ in BC.STACKS[path]] + list(BC.MULTI_STACKS[path]) + [BC.REDUCE_STACKS[path]] + [d for p, d in BC.MULTI_ONE_LAYER.items() if p == path]:
+            assert BC.path_of_bwd(dims, bf16) == path, (path, dims)
+            assert (max(dims) <= 32) == (path[:2] in ('S1', 'Fs', 'Fg')) and (dims[0] <= 4 and dims[-1] <= 4) == (path[-1] == 's')
+        mine = [c for c in BC.exact_cases() if c[1] == path]
+        assert set((f, mb, P) for _, _, f, d, mb, P in mine if d == BC.PRIMARY[path]) == set((f, mb, P) for f in ('sparse', 'routing') for mb, P, _ in PC.PIXELS)
+        assert all(sum(1 for c in mine if c[3] == d) == 6 for d, _ in BC.STACKS[path][1:])
+        odd, even = BC.MULTI_STACKS[path]
+        assert (len(odd) - 1) % 2 == 1 and (len(even) - 1) % 2 == 0
+        assert [len(c[3]) for c in BC.multi_cases() if c[1] == path].count(2) == (0 if path == 'S2s' else 2)      # one layer, both families
+        slices = [BC.nslices_of(path, P) for _, p, _, _, _, P in BC.reduce_cases() if p == path]
+        unit = 1 if path[:2] == 'S2' else 4
+        assert slices == [unit * min(k, 256) for k in (1, 4, 12, 13, 16, 17, 49, 64, 65, 255, 256, 257)]
+        assert BC.nparams(BC.REDUCE_STACKS[path]) % 64
+    assert sorted(BC.path_of_bwd(d, True) for d, _ in PC.RANDOM_STACKS) == ['S1s', 'S1s', 'S2g', 'S2g', 'S2s', 'S2s']
+    assert sorted(BC.path_of_bwd(d, False) for d, _ in BC.F32_RANDOM_STACKS) == ['Fg', 'Fs', 'Fs']
+    ids = [c[0] for c in BC.all_exact_cases()]
+    assert len(set(ids)) == len(ids)
+
+
+def test_pixel_mlp_bwd_exact_cases_hold_their_conditions():
+    """Every exact case the GPU test runs -- pixel-count edges, 131 074 pixels, reduce slice counts, overwrite -- passes the conditions of
+    pm_bwd_cases.exact_backward_reference: building the reference is the test (one build per stack, family and pixel count).  The margins:
+    no delta above 92, no absolute sum above 2^24 / 3, and the routing family's primary stacks keep 3/4 of the delta channels and 2/3 of
+    every gW_l's entries alive."""
+    import pm_bwd_cases as BC
+    done, worst = set(), dict(max_delta=0.0, max_sum=0.0)
+    for cid, path, fam, dims, mb, P in BC.all_exact_cases():
+        key = (fam, tuple(dims), mb, P)
+        if key in done:
+            continue
+        done.add(key)
+        Ws, bs, x, gy, (gx, gWs, gbs), st = BC.build(*key)
+        assert gx.shape == x.shape and [g.shape for g in gWs] == [w.shape for w in Ws] and gx.dtype == torch.float64, cid
+        assert float(gy.abs().max()) <= 2
+        worst = {k: max(v, st[k]) for k, v in worst.items()}
+        if fam == 'routing' and dims in BC.PRIMARY.values() and mb * P >= 1024:
+            assert st['live_delta'] >= 0.75 and st['dense_gw'] >= 2. / 3., (cid, st)
+        # and rounding the operands to bf16 changes nothing, bitwise
+        if mb * P <= 20000:
+            e = ON.pixel_mlp_backward([w.double() for w in Ws], [b.double() for b in bs], x.double(), gy.double(), bf16=True)
+            assert torch.equal(e[0], gx) and all(torch.equal(a, b) for a, b in zip(e[1] + e[2], gWs + gbs)), cid
+    print('pixel_mlp_bwd exact cases: %d references, largest |delta| %g, largest absolute sum %g' % (len(done), worst['max_delta'], worst['max_sum']))
+    assert worst['max_delta'] <= 92 and 3 * worst['max_sum'] < 2 ** 24
+    assert not BC.NARROW_GY
+
+
+def test_pixel_mlp_bwd_reference_rejects_cases_that_are_not_exact():
+    """The conditions bite: an upstream gradient of 300 (above what bf16 holds exactly), a half (no integer), a 3 (outside [-2, 2]) and an
+    all-zero one (dead deltas) are refused."""
+    import pm_bwd_cases as BC
+    import pm_cases as PC
+    dims = [5, 32, 32, 7]
+    Ws, bs, routes, seed = PC.stack('routing', tuple(dims))
+    x = PC.routing_input(dims, 2, 1517, seed)
+    gy = BC.upstream('routing', dims, 2, 1517, seed)
+    BC.exact_backward_reference('routing', dims, Ws, bs, x, gy, routes, primary=True)
+    for bad in (300., 0.5, 3.):
+        g2 = gy.clone()
+        g2[1, 3, 700, 0] = bad
+        with pytest.raises(AssertionError):
+            BC.exact_backward_reference('routing', dims, Ws, bs, x, g2, routes, primary=True)
+    with pytest.raises(AssertionError):
+        BC.exact_backward_reference('routing', dims, Ws, bs, x, torch.zeros_like(gy), routes, primary=True)
+
+
+def test_pixel_mlp_backward_matches_autograd_on_generic_stacks():
+    """oracle.neural.pixel_mlp_backward equals torch autograd in float64 on two of the backward test's stacks (generic I/O, widths that
+    are no multiple of 16)."""
+    import pm_bwd_cases as BC
+    for dims, shape in (([5, 32, 32, 7], (2, 9, 7)), ([3, 64, 33, 17, 50, 64, 40, 3], (2, 5, 11))):
+        Ws, bs, x, gy = [[u.double().requires_grad_(True) for u in t] if isinstance(t, list) else t.double() for t in BC.random_case(dims, shape, 3)]
+        x.requires_grad_(True)
+        ON.pixel_mlp(Ws, bs, x).backward(gy)
+        gx, gWs, gbs = ON.pixel_mlp_backward([w.detach() for w in Ws], [b.detach() for b in bs], x.detach(), gy)
+        assert torch.allclose(gx, x.grad, rtol=1e-12, atol=1e-12)
+        for l in range(len(Ws)):
+            assert torch.allclose(gWs[l], Ws[l].grad, rtol=1e-12, atol=1e-12) and torch.allclose(gbs[l], bs[l].grad, rtol=1e-12, atol=1e-12)
+            assert float(Ws[l].grad.abs().max()) > 0
+
+
+def test_pixel_mlp_bwd_random_bounds_come_from_the_reference():
+    """RANDOM_BOUNDS are ten times the reference's own float32-vs-float64 spread (re-measured here on the GPU test's seeds; pm_bwd_cases has the
+    ten-seed figures), and at least 10 x below what separates the rounded from the unrounded oracle there."""
+    import pm_bwd_cases as BC
+    import pm_cases as PC
+    assert BC.RANDOM_BOUNDS == {'gx': 1.60e-3, 'gW': 2.04e-3, 'gb': 1.74e-3} and BC.ROW_COSINE == 0.999 and BC.F32_BOUND == 2e-5
+    for dims, shape in PC.RANDOM_STACKS:
+        for seed in BC.RANDOM_SEEDS:
+            Ws, bs, x, gy = BC.random_case(dims, shape, seed)
+            e64 = BC.emulated_backward(Ws, bs, x, gy, torch.float64)
+            e32 = BC.emulated_backward(Ws, bs, x, gy, torch.float32)
+            un = ON.pixel_mlp_backward([w.double() for w in Ws], [b.double() for b in bs], x.double(), gy.double())
+            for name, own, gap in zip(('gx', 'gW', 'gb'), BC.spread(e32, e64), BC.spread(e64, un)):
+                assert 10 * own <= BC.RANDOM_BOUNDS[name], (dims, seed, name, own)
+                assert gap > 10 * BC.RANDOM_BOUNDS[name], (dims, seed, name, gap)
+            assert min(float(BC.row_cosines(a, b).min()) for a, b in zip(e32[1], e64[1])) > 0.99999
