@@ -108,12 +108,6 @@ struct PsStoch {          // the last argument of the STOCH column kernels (stag
 struct PsLinear {         // the argument of the LINEAR column kernels (stages 1-3 of a linear step), after PsScalar and before PsStoch
     const float2* lin;    // (Re, Im)(lambda dt / 2) [my1][nx], the layout of one grid of W, shared by the batch
 };
-template <typename T> __device__ __forceinline__ T only(T t) { return t; }     // the one element of a SCALAR kernel's argument pack
-template <typename T, typename... R> __device__ __forceinline__ T first(T t, R...) { return t; }
-template <typename T, typename... R> __device__ __forceinline__ auto last(T t, R... r) {
-    if constexpr (sizeof...(R) == 0) return t;
-    else return last(r...);
-}
 template <typename U, typename T, typename... R> __device__ __forceinline__ U pick(T t, R... r) {           // the pack's element of type U
     if constexpr (std::is_same_v<U, T>) return t;
     else return pick<U>(r...);
@@ -247,7 +241,7 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
             fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
             store(zu, Ph + (size_t)row * my1);
         } else {
-            const auto gr = only(grad...);
+            const auto gr = pick<Grad...>(grad...);
 #pragma unroll
             for (int m = 0; m < 16; ++m) zw[m] = {zu[m].x * zw[m].x + zu[m].y * zw[m].y, 0.f};    // u w_x + v w_y: u, v stay
             __builtin_amdgcn_sched_barrier(0);
@@ -308,7 +302,7 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     [[maybe_unused]] float2* At = nullptr;
     [[maybe_unused]] float hkdt = 0.f;
     if constexpr (SCALAR) {
-        const PsScalar ps = first(sc...);
+        const PsScalar ps = pick<PsScalar>(sc...);
         Th = ps.T; At = ps.At; hkdt = ps.hkdt;
     }
     [[maybe_unused]] const float* samp = nullptr;
@@ -316,7 +310,7 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     [[maybe_unused]] unsigned sk0 = 0, sk1 = 0, sn0 = 0, sn1 = 0;
     [[maybe_unused]] float sqdt = 0.f;
     if constexpr (STOCH) {
-        const PsStoch st = last(sc...);
+        const PsStoch st = pick<PsStoch>(sc...);
         if constexpr (S == 1) {
             if (blockIdx.x == 0 && threadIdx.x == 0) *st.clock = *st.clock + 1;      // no workgroup of this launch reads it
         } else {
@@ -804,112 +798,66 @@ inline int kept_y(int ny) { return (ny - 1) / 3 + 1; }
 
 inline unsigned grid_of(long work, long per) { return capped_grid((work + per - 1) / per, kGridCap); }
 
-// gr == nullptr: the unscalared kernel; bu != nullptr (with gr): the buoyant one
-template <int N>
-int launch_row(const float2* G, float2* Ph, const PsArgs& a, const PsGrad* gr, hipStream_t s, const PsBuoyGrad* bu = nullptr) {
-    const dim3 grid(grid_of(a.nlines, PsLds<N>::LINES));
-    if (bu) {
-        constexpr auto kern = ps_row_kernel<N, true, true, PsBuoyGrad>;
-        if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a, *bu);
-        return check_launch("spec_ns buoyant row pass");
-    }
-    if (gr) {
-        constexpr auto kern = ps_row_kernel<N, true, false, PsGrad>;
-        if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a, *gr);
-        return check_launch("spec_ns scalar row pass");
-    }
-    constexpr auto kern = ps_row_kernel<N>;
+template <typename T, typename... X> constexpr bool has = (std::is_same_v<T, X> || ... || false);
+
+// gr: nothing (the unscalared kernel), a PsGrad (the scalar one) or a PsBuoyGrad (the buoyant one)
+template <int N, typename... Gr>
+int launch_row(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s, Gr... gr) {
+    constexpr bool SC = sizeof...(Gr) == 1, BU = has<PsBuoyGrad, Gr...>;
+    constexpr auto kern = ps_row_kernel<N, SC, BU, Gr...>;
     if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-    hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a);
-    return check_launch("spec_ns row pass");
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a, gr...);
+    return check_launch(BU ? "spec_ns buoyant row pass" : SC ? "spec_ns scalar row pass" : "spec_ns row pass");
 }
 
-// fc == nullptr: the unforced kernels (stage 0 has no other form); sc == nullptr: the unscalared ones
-template <int N, int S, bool FORCED>
+// The column kernel of stage S whose argument pack ends in x...: a PsScalar (the SCALAR kernels), a PsLinear, a PsStoch, in that order, each or
+// none.  fc is read only by the FORCED kernels.
+template <int N, int S, bool FORCED, typename... X>
 int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
-               const PsScalar* sc, hipStream_t s) {
-    const dim3 grid(grid_of(a.nlines, PsLds<N>::LINES));
+               hipStream_t s, X... x) {
+    constexpr bool SC = has<PsScalar, X...>, LI = has<PsLinear, X...>, ST = has<PsStoch, X...>;
+    constexpr auto kern = ps_col_kernel<N, S, FORCED, SC, X...>;
     std::conditional_t<FORCED, PsForce, PsNoForce> f{};
     if constexpr (FORCED) f = *fc;
-    if (sc) {
-        constexpr auto kern = ps_col_kernel<N, S, FORCED, true, PsScalar>;
-        if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, f, *sc);
-        return check_launch("spec_ns scalar column pass");
-    }
-    constexpr auto kern = ps_col_kernel<N, S, FORCED>;
     if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-    hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, f);
-    return check_launch(FORCED ? "spec_ns forced column pass" : "spec_ns column pass");
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, f, x...);
+    return check_launch(LI       ? (SC ? "spec_ns linear scalar column pass" : "spec_ns linear column pass")
+                        : ST     ? (SC ? "spec_ns stochastic scalar column pass" : "spec_ns stochastic column pass")
+                        : SC     ? "spec_ns scalar column pass"
+                        : FORCED ? "spec_ns forced column pass"
+                                 : "spec_ns column pass");
 }
 
-// stages 1 and 4 of a stochastic step: the forced kernels with a PsStoch at the end of their argument pack
-template <int N, int S>
-int launch_col_stoch(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce& fc,
-                     const PsScalar* sc, const PsStoch& st, hipStream_t s) {
-    const dim3 grid(grid_of(a.nlines, PsLds<N>::LINES));
-    if (sc) {
-        constexpr auto kern = ps_col_kernel<N, S, true, true, PsScalar, PsStoch>;
-        if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, fc, *sc, st);
-        return check_launch("spec_ns stochastic scalar column pass");
-    }
-    constexpr auto kern = ps_col_kernel<N, S, true, false, PsStoch>;
-    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-    hipLaunchKernelGGL(kern, grid, dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, fc, st);
-    return check_launch("spec_ns stochastic column pass");
-}
-
-// stages 1-3 of a linear step: the forced kernels with PsScalar (sc), PsLinear and, at stage 1 of a stochastic step, PsStoch (st) in the pack
-template <int N, int S, typename... X>
-int launch_col_pack(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce& fc,
-                    hipStream_t s, X... x) {
-    constexpr bool SC = (std::is_same_v<X, PsScalar> || ... || false);
-    constexpr auto kern = ps_col_kernel<N, S, true, SC, X...>;
-    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, fc, x...);
-    return check_launch(SC ? "spec_ns linear scalar column pass" : "spec_ns linear column pass");
-}
-
-template <int N, int S>
-int launch_col_linear(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce& fc,
-                      const PsScalar* sc, const PsLinear& li, const PsStoch* st, hipStream_t s) {
-    if constexpr (S == 1) {
-        if (st) {
-            if (sc) return launch_col_pack<N, S>(Ph, G, W, A, mean, a, emit, fc, s, *sc, li, *st);
-            return launch_col_pack<N, S>(Ph, G, W, A, mean, a, emit, fc, s, li, *st);
-        }
-    }
-    if (sc) return launch_col_pack<N, S>(Ph, G, W, A, mean, a, emit, fc, s, *sc, li);
-    return launch_col_pack<N, S>(Ph, G, W, A, mean, a, emit, fc, s, li);
-}
-
-// st != nullptr (with fc): a stochastic step, whose stages 1 and 4 are the STOCH kernels; li != nullptr (with fc): a linear step, whose
-// stages 1-3 are the LINEAR kernels (stage 4 applies no factor and stays the forced or the STOCH kernel)
+// The one place where a stage's run-time facts become a kernel.  fc == nullptr: the unforced kernels (stage 0 has no other form); sc: the
+// SCALAR ones; li (with fc): a linear step, whose stages 1-3 are the LINEAR kernels (stage 4 applies no factor); st (with fc): a stochastic
+// step, whose stages 1 and 4 are the STOCH kernels.  The pack grows in the kernel's order, and a form no step has is never named.
 template <int N>
 int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
                      const PsScalar* sc, hipStream_t s, const PsStoch* st = nullptr, const PsLinear* li = nullptr) {
-    if (li && S == 1) return launch_col_linear<N, 1>(Ph, G, W, A, mean, a, emit, *fc, sc, *li, st, s);
-    if (li && S == 2) return launch_col_linear<N, 2>(Ph, G, W, A, mean, a, emit, *fc, sc, *li, nullptr, s);
-    if (li && S == 3) return launch_col_linear<N, 3>(Ph, G, W, A, mean, a, emit, *fc, sc, *li, nullptr, s);
-    if (st && S == 1) return launch_col_stoch<N, 1>(Ph, G, W, A, mean, a, emit, *fc, sc, *st, s);
-    if (st && S == 4) return launch_col_stoch<N, 4>(Ph, G, W, A, mean, a, emit, *fc, sc, *st, s);
-    if (fc && S >= 1) {
-        switch (S) {
-            case 1: return launch_col<N, 1, true>(Ph, G, W, A, mean, a, emit, fc, sc, s);
-            case 2: return launch_col<N, 2, true>(Ph, G, W, A, mean, a, emit, fc, sc, s);
-            case 3: return launch_col<N, 3, true>(Ph, G, W, A, mean, a, emit, fc, sc, s);
-            default: return launch_col<N, 4, true>(Ph, G, W, A, mean, a, emit, fc, sc, s);
-        }
-    }
+    auto stage = [&](auto stage_c) {
+        constexpr int K = decltype(stage_c)::value;
+        auto stoch = [&](auto forced, auto... x) {
+            constexpr bool F = decltype(forced)::value;
+            if constexpr (F && (K == 1 || K == 4))
+                if (st) return launch_col<N, K, F>(Ph, G, W, A, mean, a, emit, fc, s, x..., *st);
+            return launch_col<N, K, F>(Ph, G, W, A, mean, a, emit, fc, s, x...);
+        };
+        auto linear = [&](auto forced, auto... x) {
+            if constexpr (decltype(forced)::value && K >= 1 && K <= 3)
+                if (li) return stoch(forced, x..., *li);
+            return stoch(forced, x...);
+        };
+        auto scalar = [&](auto forced) { return sc ? linear(forced, *sc) : linear(forced); };
+        if constexpr (K >= 1)
+            if (fc) return scalar(std::true_type{});
+        return scalar(std::false_type{});
+    };
     switch (S) {
-        case 0: return launch_col<N, 0, false>(Ph, G, W, A, mean, a, emit, nullptr, sc, s);
-        case 1: return launch_col<N, 1, false>(Ph, G, W, A, mean, a, emit, nullptr, sc, s);
-        case 2: return launch_col<N, 2, false>(Ph, G, W, A, mean, a, emit, nullptr, sc, s);
-        case 3: return launch_col<N, 3, false>(Ph, G, W, A, mean, a, emit, nullptr, sc, s);
-        default: return launch_col<N, 4, false>(Ph, G, W, A, mean, a, emit, nullptr, sc, s);
+        case 0: return stage(std::integral_constant<int, 0>{});
+        case 1: return stage(std::integral_constant<int, 1>{});
+        case 2: return stage(std::integral_constant<int, 2>{});
+        case 3: return stage(std::integral_constant<int, 3>{});
+        default: return stage(std::integral_constant<int, 4>{});
     }
 }
 
@@ -931,16 +879,63 @@ size_t scalar_work_bytes(int batch, int nx, int ny) {
     return st > b ? st : b;
 }
 
-int check_common(const char* what, int batch, int nx, int ny, double Lx, double Ly, const void* work, size_t wbytes, bool scalar = false) {
+// The step's layout of work, compacted fields of fstride complex each: A, G[4], Ph; with a scalar A, A_theta, G[6], Ph[2]; and the arguments
+// of the column pass (col) and of the row pass (row).
+struct PsWork {
+    float2 *A, *At, *G, *Ph;
+    PsArgs col, row;
+    PsWork(void* work, int batch, int nx, int ny, bool scalar, double Lx, double Ly, float hnudt, float dt) {
+        const int my1 = kept_y(ny);
+        const long fstride = (long)batch * nx * my1;
+        A = static_cast<float2*>(work);
+        At = A + fstride;
+        G = A + (scalar ? 2 : 1) * fstride;
+        Ph = G + (scalar ? 6 : 4) * fstride;
+        col = PsArgs{(long)batch * my1, fstride, my1, (float)(2.0 * M_PI / Lx), (float)(2.0 * M_PI / Ly), hnudt, dt, (float)(1.0 / ((double)nx * ny))};
+        row = col;
+        row.nlines = (long)batch * nx;
+    }
+};
+
+int check_lengths(const char* what, double Lx, double Ly) {
     if (!(Lx > 0) || !(Ly > 0) || !std::isfinite(Lx) || !std::isfinite(Ly))
         return fail(NNS_ERR_INVALID_ARG, "%s: Lx = %g, Ly = %g must be positive and finite", what, Lx, Ly);
+    return NNS_OK;
+}
+
+int check_axes(const char* what, int nx, int ny) {
     if (!pow2_in_range(nx) || !pow2_in_range(ny))
         return fail(NNS_ERR_UNSUPPORTED, "%s: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", what, nx, ny);
+    return NNS_OK;
+}
+
+// box and axes: what every call checks before it looks at a workspace or a shell count
+int check_box(const char* what, int nx, int ny, double Lx, double Ly) {
+    if (int rc = check_lengths(what, Lx, Ly)) return rc;
+    return check_axes(what, nx, ny);
+}
+
+int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, bool scalar) {
     const size_t need = scalar ? scalar_work_bytes(batch, nx, ny) : work_bytes(batch, nx, ny);
     if (wbytes < need)
         return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", what, wbytes, need,
                     scalar ? "nns_spec_ns_scalar_workspace" : "nns_spec_ns_workspace");
-    (void)work;
+    return NNS_OK;
+}
+
+int check_common(const char* what, int batch, int nx, int ny, double Lx, double Ly, size_t wbytes, bool scalar = false) {
+    if (int rc = check_box(what, nx, ny, Lx, Ly)) return rc;
+    return check_work(what, batch, nx, ny, wbytes, scalar);
+}
+
+int check_gbatch(const char* what, const float* ghat, int gbatch, int batch) {
+    if (ghat ? (gbatch != 1 && gbatch != batch) : gbatch != 0)
+        return fail(NNS_ERR_INVALID_ARG, "%s: gbatch = %d must be 0 without ghat, 1 or batch = %d with it", what, gbatch, batch);
+    return NNS_OK;
+}
+
+int check_buoyancy(const char* what, double bx, double by) {
+    if (!std::isfinite(bx) || !std::isfinite(by)) return fail(NNS_ERR_INVALID_ARG, "%s: the buoyancy (%g, %g) must be finite", what, bx, by);
     return NNS_OK;
 }
 
@@ -962,15 +957,6 @@ PsShells shells_of(int nx, int ny, double Lx, double Ly) {
     return g;
 }
 
-// box and axes: what every shell call checks first
-int check_box(const char* what, int nx, int ny, double Lx, double Ly) {
-    if (!(Lx > 0) || !(Ly > 0) || !std::isfinite(Lx) || !std::isfinite(Ly))
-        return fail(NNS_ERR_INVALID_ARG, "%s: Lx = %g, Ly = %g must be positive and finite", what, Lx, Ly);
-    if (!pow2_in_range(nx) || !pow2_in_range(ny))
-        return fail(NNS_ERR_UNSUPPORTED, "%s: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", what, nx, ny);
-    return NNS_OK;
-}
-
 // box, axes, then the shell count: what the spectrum and transfer calls check before they look at a workspace
 int check_shells(const char* what, int nx, int ny, double Lx, double Ly, int nshell, PsShells* g) {
     if (int rc = check_box(what, nx, ny, Lx, Ly)) return rc;
@@ -981,11 +967,12 @@ int check_shells(const char* what, int nx, int ny, double Lx, double Ly, int nsh
 }
 
 // one wave per (grid, shell): the grid only decides which wave takes which
+inline dim3 shell_grid(long nunits) { return dim3(capped_grid((nunits + kW - 1) / kW, 8 * kGridCap)); }
+
 template <bool TRANSFER>
 int launch_shells(const void* a, const void* b, const void* c, int cshared, double* out, const PsShells& g, int batch, hipStream_t s) {
     const long nunits = (long)batch * g.nshell;
-    hipLaunchKernelGGL(ps_shell_kernel<TRANSFER>, dim3(capped_grid((nunits + kW - 1) / kW, 8 * kGridCap)), dim3(kT), 0, s, a, b, c, cshared, out, g,
-                       nunits);
+    hipLaunchKernelGGL(ps_shell_kernel<TRANSFER>, shell_grid(nunits), dim3(kT), 0, s, a, b, c, cshared, out, g, nunits);
     return check_launch(TRANSFER ? "spec_ns_transfer shells" : "spec_ns_spectrum");
 }
 
@@ -1018,8 +1005,7 @@ NNS_API int nns_spec_ns_shells(int nx, int ny, double Lx, double Ly, int* nshell
 NNS_API int nns_spec_ns_spectrum_f32(const float* what, const float* that, const float* ghat, int gbatch, double* out, int nshell, int batch,
                                      int nx, int ny, double Lx, double Ly, void* stream) {
     if (!what || !out || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_spectrum: NULL pointer or batch < 1");
-    if (ghat ? (gbatch != 1 && gbatch != batch) : gbatch != 0)
-        return fail(NNS_ERR_INVALID_ARG, "spec_ns_spectrum: gbatch = %d must be 0 without ghat, 1 or batch = %d with it", gbatch, batch);
+    if (int rc = check_gbatch("spec_ns_spectrum", ghat, gbatch, batch)) return rc;
     PsShells g;
     if (int rc = check_shells("spec_ns_spectrum", nx, ny, Lx, Ly, nshell, &g)) return rc;
     return launch_shells<false>(what, that, ghat, gbatch == 1 && batch > 1 ? 1 : 0, out, g, batch, as_stream(stream));
@@ -1028,13 +1014,11 @@ NNS_API int nns_spec_ns_spectrum_f32(const float* what, const float* that, const
 NNS_API int nns_spec_ns_buoyancy_spectrum_f32(const float* what, const float* that, double* out, int nshell, int batch, int nx, int ny, double Lx,
                                               double Ly, double bx, double by, void* stream) {
     if (!what || !that || !out || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_buoyancy_spectrum: NULL pointer or batch < 1");
-    if (!std::isfinite(bx) || !std::isfinite(by))
-        return fail(NNS_ERR_INVALID_ARG, "spec_ns_buoyancy_spectrum: the buoyancy (%g, %g) must be finite", bx, by);
+    if (int rc = check_buoyancy("spec_ns_buoyancy_spectrum", bx, by)) return rc;
     PsShells g;
     if (int rc = check_shells("spec_ns_buoyancy_spectrum", nx, ny, Lx, Ly, nshell, &g)) return rc;
     const long nunits = (long)batch * g.nshell;
-    hipLaunchKernelGGL(ps_buoyancy_shell_kernel, dim3(capped_grid((nunits + kW - 1) / kW, 8 * kGridCap)), dim3(kT), 0, as_stream(stream),
-                       reinterpret_cast<const float2*>(what), reinterpret_cast<const float2*>(that), out, g, nunits, bx, by);
+    hipLaunchKernelGGL(ps_buoyancy_shell_kernel, shell_grid(nunits), dim3(kT), 0, as_stream(stream), reinterpret_cast<const float2*>(what), reinterpret_cast<const float2*>(that), out, g, nunits, bx, by);
     return check_launch("spec_ns_buoyancy_spectrum");
 }
 
@@ -1044,8 +1028,7 @@ NNS_API int nns_spec_ns_linear_spectrum_f32(const float* what, const double* rat
     PsShells g;
     if (int rc = check_shells("spec_ns_linear_spectrum", nx, ny, Lx, Ly, nshell, &g)) return rc;
     const long nunits = (long)batch * g.nshell;
-    hipLaunchKernelGGL(ps_linear_shell_kernel, dim3(capped_grid((nunits + kW - 1) / kW, 8 * kGridCap)), dim3(kT), 0, as_stream(stream),
-                       reinterpret_cast<const float2*>(what), rate, out, g, nunits);
+    hipLaunchKernelGGL(ps_linear_shell_kernel, shell_grid(nunits), dim3(kT), 0, as_stream(stream), reinterpret_cast<const float2*>(what), rate, out, g, nunits);
     return check_launch("spec_ns_linear_spectrum");
 }
 
@@ -1054,45 +1037,36 @@ NNS_API int nns_spec_ns_transfer_f32(const float* what, const float* that, doubl
     if (!what || !out || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_transfer: NULL pointer or batch < 1");
     PsShells g;
     if (int rc = check_shells("spec_ns_transfer", nx, ny, Lx, Ly, nshell, &g)) return rc;
-    const size_t need = that ? scalar_work_bytes(batch, nx, ny) : work_bytes(batch, nx, ny);
-    if (work_bytes_ < need)
-        return fail(NNS_ERR_WORKSPACE, "spec_ns_transfer: workspace of %zu bytes, %zu needed (%s)", work_bytes_, need,
-                    that ? "nns_spec_ns_scalar_workspace" : "nns_spec_ns_workspace");
+    if (int rc = check_work("spec_ns_transfer", batch, nx, ny, work_bytes_, that != nullptr)) return rc;
     hipStream_t s = as_stream(stream);
-    const int my1 = g.my1;
-    const long fstride = (long)batch * nx * my1;
-    // the step's layout of work (A, [A_theta], G, Ph).  The accumulators are free here: the modal fields Re(conj w^ N^), Re(conj theta^ N_theta^)
-    // take the first half of A's and A_theta's slots (float32 against complex), the zero mean of the co-moving frame a corner of A's second half
-    float2* A = static_cast<float2*>(work);
-    float2* G = A + (that ? 2 : 1) * fstride;
-    float2* Ph = G + (that ? 6 : 4) * fstride;
-    float* Tw = reinterpret_cast<float*>(A);
-    float* Tt = that ? reinterpret_cast<float*>(A + fstride) : nullptr;
-    float* zero_mean = Tw + fstride;
+    // the step's layout of work.  The accumulators are free here: the modal fields Re(conj w^ N^), Re(conj theta^ N_theta^) take the first
+    // half of A's and A_theta's slots (float32 against complex), the zero mean of the co-moving frame a corner of A's second half
+    const PsWork L(work, batch, nx, ny, that != nullptr, Lx, Ly, 0.f, 0.f);
+    float* Tw = reinterpret_cast<float*>(L.A);
+    float* Tt = that ? reinterpret_cast<float*>(L.At) : nullptr;
+    float* zero_mean = Tw + L.col.fstride;
     void* zb[1] = {zero_mean};
     const long zn[1] = {(long)(2 * batch * sizeof(float))};
     if (int rc = zero_buffers(zb, zn, 1, s)) return rc;
-    const float2* W = reinterpret_cast<const float2*>(what);
+    float2* W = const_cast<float2*>(reinterpret_cast<const float2*>(what));       // stage 0 only reads W / Th (its signature is the step's)
     const float2* Th = reinterpret_cast<const float2*>(that);
-    PsArgs ac{(long)batch * my1, fstride, my1, (float)g.kx1, (float)g.ky1, 0.f, 0.f, (float)(1.0 / ((double)nx * ny))};
-    PsArgs ar = ac;
-    ar.nlines = (long)batch * nx;
-    // stage 0 only reads W / Th (its signature is the step's: no const); the gradient of the scalar's row pass is 0: advection alone
     const PsScalar scalar{const_cast<float2*>(Th), nullptr, 0.f};
-    const PsGrad grad{0.f, 0.f};
+    const PsGrad grad{0.f, 0.f};                                                  // the scalar's row pass without a gradient: advection alone
     if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
-            return launch_col<decltype(n)::value, 0, false>(Ph, G, const_cast<float2*>(W), nullptr, zero_mean, ac, 1, nullptr, that ? &scalar : nullptr, s);
+            return launch_col_stage<decltype(n)::value>(0, L.Ph, L.G, W, nullptr, zero_mean, L.col, 1, nullptr, that ? &scalar : nullptr, s);
         }))
         return rc;
-    if (int rc = dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, that ? &grad : nullptr, s); })) return rc;
-    if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_transfer<decltype(n)::value>(Ph, W, Th, Tw, Tt, ac, s); })) return rc;
+    if (int rc = dispatch_pow2(ny, "spec_ns", [&](auto n) {
+            return that ? launch_row<decltype(n)::value>(L.G, L.Ph, L.row, s, grad) : launch_row<decltype(n)::value>(L.G, L.Ph, L.row, s);
+        }))
+        return rc;
+    if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_transfer<decltype(n)::value>(L.Ph, W, Th, Tw, Tt, L.col, s); })) return rc;
     return launch_shells<true>(Tw, Tt, nullptr, 0, out, g, batch, s);
 }
 
 NNS_API int nns_spec_ns_workspace(int batch, int nx, int ny, size_t* bytes) {
     if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
-    if (!pow2_in_range(nx) || !pow2_in_range(ny))
-        return fail(NNS_ERR_UNSUPPORTED, "spec_ns_workspace: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", nx, ny);
+    if (int rc = check_axes("spec_ns_workspace", nx, ny)) return rc;
     *bytes = work_bytes(batch, nx, ny);
     return NNS_OK;
 }
@@ -1100,7 +1074,7 @@ NNS_API int nns_spec_ns_workspace(int batch, int nx, int ny, size_t* bytes) {
 NNS_API int nns_spec_ns_init_f32(const float* u, const float* v, float* what, float* mean, void* work, size_t work_bytes_, int batch,
                                  int nx, int ny, double Lx, double Ly, void* stream) {
     if (!u || !v || !what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_init: NULL pointer or batch < 1");
-    if (int rc = check_common("spec_ns_init", batch, nx, ny, Lx, Ly, work, work_bytes_)) return rc;
+    if (int rc = check_common("spec_ns_init", batch, nx, ny, Lx, Ly, work_bytes_)) return rc;
     hipStream_t s = as_stream(stream);
     float* uh = static_cast<float*>(work);
     float* vh = uh + (size_t)2 * batch * nx * (ny / 2 + 1);
@@ -1126,22 +1100,13 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
     if (!(drag >= 0) || !std::isfinite(drag)) return fail(NNS_ERR_INVALID_ARG, "%s: drag = %g must be finite and >= 0", who, drag);
     if (!(kappa >= 0) || !std::isfinite(kappa) || !std::isfinite(gx) || !std::isfinite(gy))
         return fail(NNS_ERR_INVALID_ARG, "%s: kappa = %g must be finite and >= 0, the gradient (%g, %g) finite", who, kappa, gx, gy);
-    if (!std::isfinite(bx) || !std::isfinite(by)) return fail(NNS_ERR_INVALID_ARG, "%s: the buoyancy (%g, %g) must be finite", who, bx, by);
-    if (ghat ? (gbatch != 1 && gbatch != batch) : gbatch != 0)
-        return fail(NNS_ERR_INVALID_ARG, "%s: gbatch = %d must be 0 without ghat, 1 or batch = %d with it", who, gbatch, batch);
-    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work, work_bytes_, that != nullptr)) return rc;
+    if (int rc = check_buoyancy(who, bx, by)) return rc;
+    if (int rc = check_gbatch(who, ghat, gbatch, batch)) return rc;
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, that != nullptr)) return rc;
     if (nsteps == 0) return NNS_OK;
     hipStream_t s = as_stream(stream);
-    const int my1 = kept_y(ny);
-    const long fstride = (long)batch * nx * my1;
     float2* W = reinterpret_cast<float2*>(what);
-    float2* A = static_cast<float2*>(work);
-    float2* G = A + (that ? 2 : 1) * fstride;                // work: A, G[4], Ph; with a scalar A, A_theta, G[6], Ph[2]
-    float2* Ph = G + (that ? 6 : 4) * fstride;
-    PsArgs ac{(long)batch * my1, fstride, my1, (float)(2.0 * M_PI / Lx), (float)(2.0 * M_PI / Ly), (float)(-0.5 * nu * dt), (float)dt,
-              (float)(1.0 / ((double)nx * ny))};
-    PsArgs ar = ac;
-    ar.nlines = (long)batch * nx;
+    const PsWork L(work, batch, nx, ny, that != nullptr, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);
     const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
     const PsForce* fc = ghat || drag > 0 || st || lin ? &force : nullptr;
     const PsLinear linear{reinterpret_cast<const float2*>(lin)};
@@ -1152,14 +1117,20 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
         stoch.sqdt = (float)std::sqrt(dt);
     }
     const PsStoch* stc = st ? &stoch : nullptr;
-    const PsScalar scalar{reinterpret_cast<float2*>(that), A + fstride, (float)(-0.5 * kappa * dt)};
+    const PsScalar scalar{reinterpret_cast<float2*>(that), L.At, (float)(-0.5 * kappa * dt)};
     const PsGrad grad{(float)gx, (float)gy};
     const PsScalar* sc = that ? &scalar : nullptr;
-    const PsGrad* gr = that ? &grad : nullptr;
     const PsBuoyGrad buoy{(float)gx, (float)gy, (float)(-(double)ny * by), (float)((double)ny * bx)};
     const PsBuoyGrad* bu = that && (bx != 0.0 || by != 0.0) ? &buoy : nullptr;
-    auto col = [&](int S, int emit) { return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, Ph, G, W, A, mean, ac, emit, fc, sc, s, stc, li); }); };
-    auto row = [&]() { return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row<decltype(n)::value>(G, Ph, ar, gr, s, bu); }); };
+    auto col = [&](int S, int emit) {
+        return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, emit, fc, sc, s, stc, li); });
+    };
+    auto row = [&]() {
+        return dispatch_pow2(ny, "spec_ns", [&](auto n) {
+            constexpr int N = decltype(n)::value;
+            return bu ? launch_row<N>(L.G, L.Ph, L.row, s, *bu) : that ? launch_row<N>(L.G, L.Ph, L.row, s, grad) : launch_row<N>(L.G, L.Ph, L.row, s);
+        });
+    };
     if (int rc = col(0, 1)) return rc;
     for (int k = 0; k < nsteps; ++k) {
         for (int S = 1; S <= 4; ++S) {
@@ -1225,8 +1196,7 @@ NNS_API int nns_spec_ns_step_linear_f32(float* what, float* that, const float* m
 
 NNS_API int nns_spec_ns_scalar_workspace(int batch, int nx, int ny, size_t* bytes) {
     if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
-    if (!pow2_in_range(nx) || !pow2_in_range(ny))
-        return fail(NNS_ERR_UNSUPPORTED, "spec_ns_scalar_workspace: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", nx, ny);
+    if (int rc = check_axes("spec_ns_scalar_workspace", nx, ny)) return rc;
     *bytes = scalar_work_bytes(batch, nx, ny);
     return NNS_OK;
 }
@@ -1234,7 +1204,7 @@ NNS_API int nns_spec_ns_scalar_workspace(int batch, int nx, int ny, size_t* byte
 NNS_API int nns_spec_ns_scalar_init_f32(const float* theta, float* that, void* work, size_t work_bytes_, int batch, int nx, int ny,
                                         void* stream) {
     if (!theta || !that || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_init: NULL pointer or batch < 1");
-    if (int rc = check_common("spec_ns_scalar_init", batch, nx, ny, 1.0, 1.0, work, work_bytes_, true)) return rc;
+    if (int rc = check_common("spec_ns_scalar_init", batch, nx, ny, 1.0, 1.0, work_bytes_, true)) return rc;
     float* th = static_cast<float*>(work);
     if (int rc = nns_spec_rfft2_f32(theta, th, batch, nx, ny, stream)) return rc;
     const int my1 = kept_y(ny);
@@ -1246,7 +1216,7 @@ NNS_API int nns_spec_ns_scalar_init_f32(const float* theta, float* that, void* w
 NNS_API int nns_spec_ns_scalar_field_f32(const float* that, float* theta, void* work, size_t work_bytes_, int batch, int nx, int ny,
                                          void* stream) {
     if (!that || !theta || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_field: NULL pointer or batch < 1");
-    if (int rc = check_common("spec_ns_scalar_field", batch, nx, ny, 1.0, 1.0, work, work_bytes_, true)) return rc;
+    if (int rc = check_common("spec_ns_scalar_field", batch, nx, ny, 1.0, 1.0, work_bytes_, true)) return rc;
     float* th = static_cast<float*>(work);
     hipLaunchKernelGGL(ps_scalar_expand_kernel, dim3(pw_grid((long)batch * nx * (ny / 2 + 1))), dim3(256), 0, as_stream(stream),
                        reinterpret_cast<const float2*>(that), reinterpret_cast<float2*>(th), batch, nx, ny, kept_y(ny));
@@ -1257,11 +1227,9 @@ NNS_API int nns_spec_ns_scalar_field_f32(const float* that, float* theta, void* 
 NNS_API int nns_spec_ns_scalar_diag_f32(const float* what, const float* that, double* out, int batch, int nx, int ny, double Lx, double Ly,
                                         double kappa, void* stream) {
     if (!what || !that || !out || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_diag: NULL pointer or batch < 1");
-    if (!(Lx > 0) || !(Ly > 0) || !std::isfinite(Lx) || !std::isfinite(Ly))
-        return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_diag: Lx = %g, Ly = %g must be positive and finite", Lx, Ly);
+    if (int rc = check_lengths("spec_ns_scalar_diag", Lx, Ly)) return rc;
     if (!(kappa >= 0) || !std::isfinite(kappa)) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_diag: kappa = %g must be finite and >= 0", kappa);
-    if (!pow2_in_range(nx) || !pow2_in_range(ny))
-        return fail(NNS_ERR_UNSUPPORTED, "spec_ns_scalar_diag: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", nx, ny);
+    if (int rc = check_axes("spec_ns_scalar_diag", nx, ny)) return rc;
     const double n = (double)nx * ny;
     hipLaunchKernelGGL(ps_scalar_diag_kernel, dim3(batch), dim3(kDiagT), 0, as_stream(stream), reinterpret_cast<const float2*>(what),
                        reinterpret_cast<const float2*>(that), out, nx, kept_y(ny), 2.0 * M_PI / Lx, 2.0 * M_PI / Ly, kappa, 1.0 / (n * n));
@@ -1271,12 +1239,8 @@ NNS_API int nns_spec_ns_scalar_diag_f32(const float* what, const float* that, do
 NNS_API int nns_spec_ns_diag_f32(const float* what, const float* ghat, int gbatch, double* out, int batch, int nx, int ny, double Lx,
                                  double Ly, void* stream) {
     if (!what || !out || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_diag: NULL pointer or batch < 1");
-    if (ghat ? (gbatch != 1 && gbatch != batch) : gbatch != 0)
-        return fail(NNS_ERR_INVALID_ARG, "spec_ns_diag: gbatch = %d must be 0 without ghat, 1 or batch = %d with it", gbatch, batch);
-    if (!(Lx > 0) || !(Ly > 0) || !std::isfinite(Lx) || !std::isfinite(Ly))
-        return fail(NNS_ERR_INVALID_ARG, "spec_ns_diag: Lx = %g, Ly = %g must be positive and finite", Lx, Ly);
-    if (!pow2_in_range(nx) || !pow2_in_range(ny))
-        return fail(NNS_ERR_UNSUPPORTED, "spec_ns_diag: nx = %d, ny = %d: each axis must be a power of two in [64, 1024]", nx, ny);
+    if (int rc = check_gbatch("spec_ns_diag", ghat, gbatch, batch)) return rc;
+    if (int rc = check_box("spec_ns_diag", nx, ny, Lx, Ly)) return rc;
     const double n = (double)nx * ny;
     hipLaunchKernelGGL(ps_diag_kernel, dim3(batch), dim3(kDiagT), 0, as_stream(stream), reinterpret_cast<const float2*>(what),
                        reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, out, nx, kept_y(ny), 2.0 * M_PI / Lx,
@@ -1289,8 +1253,8 @@ static int spec_ns_fields(const char* who, const float* what, const float* that,
                           size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double rho, double bx, double by, void* stream) {
     if (!what || !mean || !u || !v || !p || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
     if (!std::isfinite(rho)) return fail(NNS_ERR_INVALID_ARG, "%s: rho = %g must be finite", who, rho);
-    if (!std::isfinite(bx) || !std::isfinite(by)) return fail(NNS_ERR_INVALID_ARG, "%s: the buoyancy (%g, %g) must be finite", who, bx, by);
-    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work, work_bytes_, that != nullptr)) return rc;
+    if (int rc = check_buoyancy(who, bx, by)) return rc;
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, that != nullptr)) return rc;
     hipStream_t s = as_stream(stream);
     const int my1 = kept_y(ny);
     const long nh = ny / 2 + 1, per = (long)batch * nx * nh, npts = (long)batch * nx * ny;

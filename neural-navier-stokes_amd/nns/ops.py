@@ -877,6 +877,34 @@ def spec_ns_workspace(B, nx, ny):
     return _query_bytes('nns_spec_ns_workspace', int(B), int(nx), int(ny))
 
 
+def _spec_ns_work(who, work):
+    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
+        raise TypeError("%s: work must be a contiguous uint8 device tensor" % who)
+
+
+def _spec_ns_out(who, out, shape, device):
+    """The float64 result of `shape` on the state's device: a fresh one (out None) or the checked out."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float64, device=device)
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == shape and out.is_contiguous()
+            and out.device == device):
+        raise ValueError("%s: out must be a contiguous float64 %s tensor on the state's device" % (who, list(shape)))
+    return out
+
+
+def _spec_ns_field_out(who, out, shape, device, three=True):
+    """Its float32 twin for the physical fields: a tuple of three of `shape`, or (three False) one bare tensor."""
+    n = 3 if three else 1
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=torch.float32, device=device) for _ in range(n))
+    else:
+        out = tuple(out) if three else (out,)
+        _f32(*out)
+        if len(out) != n or any(tuple(o.shape) != shape or o.device != device for o in out):
+            raise ValueError("%s: out must be %s %s tensor%s on the state's device" % (who, "three" if three else "a", list(shape), "s" if three else ""))
+    return out if three else out[0]
+
+
 def _spec_ns_state(who, what, mean, work, ny):
     """(B, my1, nx) of the checked solver state.  mean and work None (spec_ns_diag): the spectrum alone, under the caller's name; ny None
     (spec_ns_init, which compares the whole shape with its fields): no check of the kept y-wavenumbers."""
@@ -888,8 +916,7 @@ def _spec_ns_state(who, what, mean, work, ny):
     if not alone:
         if tuple(mean.shape) != (B, 2):
             raise ValueError("spec_ns: mean must be [B, 2], got %s" % (tuple(mean.shape),))
-        if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
-            raise TypeError("spec_ns: work must be a contiguous uint8 device tensor")
+        _spec_ns_work('spec_ns', work)
         if what.device != mean.device or what.device != work.device:
             raise ValueError("spec_ns: state tensors on different devices")
     if ny is not None and my1 != spec_ns_kept_y(ny):
@@ -921,14 +948,7 @@ def spec_ns_step_(what, mean, work, ny, Lx, Ly, dt, nu, nsteps=1):
 def spec_ns_fields(what, mean, work, ny, Lx, Ly, rho, out=None):
     """(u, v, p) float32 [B, nx, ny] of the state; out: three preallocated contiguous tensors of that shape."""
     B, my1, nx = _spec_ns_state('spec_ns_fields', what, mean, work, ny)
-    if out is None:
-        out = tuple(torch.empty((B, nx, int(ny)), dtype=torch.float32, device=what.device) for _ in range(3))
-    else:
-        out = tuple(out)
-        _f32(*out)
-        if len(out) != 3 or any(tuple(o.shape) != (B, nx, int(ny)) or o.device != what.device for o in out):
-            raise ValueError("spec_ns_fields: out must be three [%d, %d, %d] tensors on the state's device" % (B, nx, ny))
-    u, v, p = out
+    u, v, p = out = _spec_ns_field_out('spec_ns_fields', out, (B, nx, int(ny)), what.device)
     check(_lib.lib().nns_spec_ns_fields_f32(_p(what), _p(mean), _p(u), _p(v), _p(p), _p(work), work.numel(), B, nx, int(ny), float(Lx),
                                             float(Ly), float(rho), _stream()), 'nns_spec_ns_fields_f32')
     return out
@@ -962,11 +982,7 @@ def spec_ns_diag(what, ghat, ny, Lx, Ly, out=None):
     """float64 [B, 3]: fluctuation energy, enstrophy and power input <f_s . u> (0 with ghat None) of every grid of the state."""
     B, my1, nx = _spec_ns_state('spec_ns_diag', what, None, None, ny)
     gbatch = _spec_ns_force('spec_ns_diag', ghat, what)
-    if out is None:
-        out = torch.empty((B, 3), dtype=torch.float64, device=what.device)
-    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (B, 3) and out.is_contiguous()
-              and out.device == what.device):
-        raise ValueError("spec_ns_diag: out must be a contiguous float64 [%d, 3] tensor on the state's device" % B)
+    out = _spec_ns_out('spec_ns_diag', out, (B, 3), what.device)
     check(_lib.lib().nns_spec_ns_diag_f32(_p(what), _p(ghat) if gbatch else None, gbatch, _p(out), B, nx, int(ny), float(Lx), float(Ly),
                                           _stream()), 'nns_spec_ns_diag_f32')
     return out
@@ -987,8 +1003,7 @@ def _spec_ns_scalar(who, that, work, ny):
     if my1 != spec_ns_kept_y(ny):
         raise ValueError("%s: that has %d kept y-wavenumbers, ny = %d needs %d" % (who, my1, ny, spec_ns_kept_y(ny)))
     if work is not None:
-        if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
-            raise TypeError("%s: work must be a contiguous uint8 device tensor" % who)
+        _spec_ns_work(who, work)
         if work.device != that.device:
             raise ValueError("%s: state tensors on different devices" % who)
     return B, my1, nx
@@ -1008,12 +1023,7 @@ def spec_ns_scalar_init(theta, that, work):
 def spec_ns_scalar_field(that, work, ny, out=None):
     """theta float32 [B, nx, ny] of the scalar state; out: a preallocated contiguous tensor of that shape."""
     B, my1, nx = _spec_ns_scalar('spec_ns_scalar_field', that, work, ny)
-    if out is None:
-        out = torch.empty((B, nx, int(ny)), dtype=torch.float32, device=that.device)
-    else:
-        _f32(out)
-        if tuple(out.shape) != (B, nx, int(ny)) or out.device != that.device:
-            raise ValueError("spec_ns_scalar_field: out must be a [%d, %d, %d] tensor on the state's device" % (B, nx, ny))
+    out = _spec_ns_field_out('spec_ns_scalar_field', out, (B, nx, int(ny)), that.device, three=False)
     check(_lib.lib().nns_spec_ns_scalar_field_f32(_p(that), _p(out), _p(work), work.numel(), B, nx, int(ny), _stream()),
           'nns_spec_ns_scalar_field_f32')
     return out
@@ -1044,11 +1054,7 @@ def spec_ns_scalar_diag(what, that, ny, Lx, Ly, kappa, out=None):
     """float64 [B, 4]: variance 1/2 <theta'^2>, dissipation kappa <|grad theta|^2> and the fluxes <u theta'>, <v theta'> of every grid."""
     B, my1, nx = _spec_ns_state('spec_ns_scalar_diag', what, None, None, ny)
     _spec_ns_same('spec_ns_scalar_diag', that, what)
-    if out is None:
-        out = torch.empty((B, 4), dtype=torch.float64, device=what.device)
-    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (B, 4) and out.is_contiguous()
-              and out.device == what.device):
-        raise ValueError("spec_ns_scalar_diag: out must be a contiguous float64 [%d, 4] tensor on the state's device" % B)
+    out = _spec_ns_out('spec_ns_scalar_diag', out, (B, 4), what.device)
     check(_lib.lib().nns_spec_ns_scalar_diag_f32(_p(what), _p(that), _p(out), B, nx, int(ny), float(Lx), float(Ly), float(kappa), _stream()),
           'nns_spec_ns_scalar_diag_f32')
     return out
@@ -1062,15 +1068,6 @@ def spec_ns_shells(nx, ny, Lx, Ly):
     return n.value, dk.value
 
 
-def _spec_ns_shell_out(who, out, B, Q, S, device):
-    if out is None:
-        return torch.empty((B, Q, S), dtype=torch.float64, device=device)
-    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (B, Q, S) and out.is_contiguous()
-            and out.device == device):
-        raise ValueError("%s: out must be a contiguous float64 [%d, %d, %d] tensor on the state's device" % (who, B, Q, S))
-    return out
-
-
 def spec_ns_spectrum(what, that, ghat, ny, Lx, Ly, out=None):
     """float64 [B, 4, nshell]: per grid and shell the energy, enstrophy, injection Re(psi^ conj g^) (zeros with ghat None) and scalar variance
     (zeros with that None); their sums over the shells are spec_ns_diag's and spec_ns_scalar_diag's numbers."""
@@ -1079,7 +1076,7 @@ def spec_ns_spectrum(what, that, ghat, ny, Lx, Ly, out=None):
         _spec_ns_same('spec_ns_spectrum', that, what)
     gbatch = _spec_ns_force('spec_ns_spectrum', ghat, what)
     S = spec_ns_shells(nx, ny, Lx, Ly)[0]
-    out = _spec_ns_shell_out('spec_ns_spectrum', out, B, 4, S, what.device)
+    out = _spec_ns_out('spec_ns_spectrum', out, (B, 4, S), what.device)
     check(_lib.lib().nns_spec_ns_spectrum_f32(_p(what), None if that is None else _p(that), _p(ghat) if gbatch else None, gbatch, _p(out), S, B,
                                               nx, int(ny), float(Lx), float(Ly), _stream()), 'nns_spec_ns_spectrum_f32')
     return out
@@ -1089,15 +1086,14 @@ def spec_ns_transfer(what, that, work, ny, Lx, Ly, out=None):
     """float64 [B, 3, nshell]: the nonlinear transfer of energy, enstrophy and scalar variance (zeros with that None) into every shell, from
     one evaluation of the step's nonlinear term in the co-moving frame.  what and that are only read; work: spec_ns_workspace bytes
     (spec_ns_scalar_workspace with that).  No allocation beyond out, no host synchronisation: capturable with out given."""
-    if not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
-        raise TypeError("spec_ns_transfer: work must be a contiguous uint8 device tensor")
+    _spec_ns_work('spec_ns_transfer', work)
     B, my1, nx = _spec_ns_state('spec_ns_transfer', what, None, None, ny)
     if work.device != what.device:
         raise ValueError("spec_ns_transfer: state tensors on different devices")
     if that is not None:
         _spec_ns_same('spec_ns_transfer', that, what)
     S = spec_ns_shells(nx, ny, Lx, Ly)[0]
-    out = _spec_ns_shell_out('spec_ns_transfer', out, B, 3, S, what.device)
+    out = _spec_ns_out('spec_ns_transfer', out, (B, 3, S), what.device)
     check(_lib.lib().nns_spec_ns_transfer_f32(_p(what), None if that is None else _p(that), _p(out), S, _p(work), work.numel(), B, nx, int(ny),
                                               float(Lx), float(Ly), _stream()), 'nns_spec_ns_transfer_f32')
     return out
@@ -1118,6 +1114,24 @@ def spec_ns_step_buoyant_(what, that, mean, ghat, work, ny, Lx, Ly, dt, nu, drag
 
 
 # white-in-time stochastic forcing of the periodic solver (nns_spec_ns_step_stochastic_f32)
+def _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, device):
+    """The checked noise arguments of a step: amp float32 [my1, nx], clock int64 [1] and ids int32 [B] on the state's device, seed a 64-bit int."""
+    _f32(amp)
+    if tuple(amp.shape) != (my1, nx):
+        raise ValueError("%s: amp must be float32 [%d, %d], got %s" % (who, my1, nx, tuple(amp.shape)))
+    for name, t, dtype, shape in (('clock', clock, torch.int64, (1,)), ('ids', ids, torch.int32, (B,))):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+            raise TypeError("%s: %s must be a contiguous %s device tensor" % (who, name, dtype))
+        if tuple(t.shape) != shape:
+            raise ValueError("%s: %s must be %s %s, got %s" % (who, name, dtype, list(shape), tuple(t.shape)))
+    if any(t.device != device for t in (amp, clock, ids)):
+        raise ValueError("%s: amp, clock and ids must be on the state's device %s" % (who, device))
+    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral):
+        raise TypeError("%s: seed must be an int, got %r" % (who, seed))
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("%s: seed = %d must be in [0, 2^64)" % (who, seed))
+
+
 def spec_ns_step_stochastic_(what, that, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, kappa, grad, buoyancy, amp, seed, clock, ids, nsteps=1):
     """nsteps steps of spec_ns_step_buoyant_ (that None: of spec_ns_step_forced_; kappa, grad and buoyancy are then ignored), each followed by
     the kick w^ += sqrt(dt) amp xi(n, ids[b]): amp float32 [my1, nx] (shared by the batch), seed a 64-bit int, clock int64 [1] (the state's
@@ -1128,20 +1142,7 @@ def spec_ns_step_stochastic_(what, that, mean, ghat, work, ny, Lx, Ly, dt, nu, d
     if that is not None:
         _spec_ns_same(who, that, what)
     gbatch = _spec_ns_force(who, ghat, what)
-    _f32(amp)
-    if tuple(amp.shape) != (my1, nx):
-        raise ValueError("%s: amp must be float32 [%d, %d], got %s" % (who, my1, nx, tuple(amp.shape)))
-    for name, t, dtype, shape in (('clock', clock, torch.int64, (1,)), ('ids', ids, torch.int32, (B,))):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
-            raise TypeError("%s: %s must be a contiguous %s device tensor" % (who, name, dtype))
-        if tuple(t.shape) != shape:
-            raise ValueError("%s: %s must be %s %s, got %s" % (who, name, dtype, list(shape), tuple(t.shape)))
-    if any(t.device != what.device for t in (amp, clock, ids)):
-        raise ValueError("%s: amp, clock and ids must be on the state's device %s" % (who, what.device))
-    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral):
-        raise TypeError("%s: seed must be an int, got %r" % (who, seed))
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError("%s: seed = %d must be in [0, 2^64)" % (who, seed))
+    _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
     (gx, gy), (bx, by) = grad, buoyancy
     check(_lib.lib().nns_spec_ns_step_stochastic_f32(_p(what), None if that is None else _p(that), _p(mean), _p(ghat) if gbatch else None, gbatch,
                                                      _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt), float(nu),
@@ -1155,14 +1156,7 @@ def spec_ns_fields_buoyant(what, that, mean, work, ny, Lx, Ly, rho, buoyancy, ou
     out as in spec_ns_fields."""
     B, my1, nx = _spec_ns_state('spec_ns_fields_buoyant', what, mean, work, ny)
     _spec_ns_same('spec_ns_fields_buoyant', that, what)
-    if out is None:
-        out = tuple(torch.empty((B, nx, int(ny)), dtype=torch.float32, device=what.device) for _ in range(3))
-    else:
-        out = tuple(out)
-        _f32(*out)
-        if len(out) != 3 or any(tuple(o.shape) != (B, nx, int(ny)) or o.device != what.device for o in out):
-            raise ValueError("spec_ns_fields_buoyant: out must be three [%d, %d, %d] tensors on the state's device" % (B, nx, ny))
-    u, v, p = out
+    u, v, p = out = _spec_ns_field_out('spec_ns_fields_buoyant', out, (B, nx, int(ny)), what.device)
     bx, by = buoyancy
     check(_lib.lib().nns_spec_ns_fields_buoyant_f32(_p(what), _p(that), _p(mean), _p(u), _p(v), _p(p), _p(work), work.numel(), B, nx, int(ny),
                                                     float(Lx), float(Ly), float(rho), float(bx), float(by), _stream()),
@@ -1176,11 +1170,7 @@ def spec_ns_buoyancy_spectrum(what, that, ny, Lx, Ly, buoyancy, out=None):
     B, my1, nx = _spec_ns_state('spec_ns_buoyancy_spectrum', what, None, None, ny)
     _spec_ns_same('spec_ns_buoyancy_spectrum', that, what)
     S = spec_ns_shells(nx, ny, Lx, Ly)[0]
-    if out is None:
-        out = torch.empty((B, S), dtype=torch.float64, device=what.device)
-    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (B, S) and out.is_contiguous()
-              and out.device == what.device):
-        raise ValueError("spec_ns_buoyancy_spectrum: out must be a contiguous float64 [%d, %d] tensor on the state's device" % (B, S))
+    out = _spec_ns_out('spec_ns_buoyancy_spectrum', out, (B, S), what.device)
     bx, by = buoyancy
     check(_lib.lib().nns_spec_ns_buoyancy_spectrum_f32(_p(what), _p(that), _p(out), S, B, nx, int(ny), float(Lx), float(Ly), float(bx),
                                                        float(by), _stream()), 'nns_spec_ns_buoyancy_spectrum_f32')
@@ -1208,20 +1198,7 @@ def spec_ns_step_linear_(what, that, mean, ghat, work, ny, Lx, Ly, dt, kappa, gr
         if any(t is not None for t in noise):
             raise ValueError("%s: amp, clock and ids must be all None (no noise) or all given" % who)
     else:
-        _f32(amp)
-        if tuple(amp.shape) != (my1, nx):
-            raise ValueError("%s: amp must be float32 [%d, %d], got %s" % (who, my1, nx, tuple(amp.shape)))
-        for name, t, dtype, shape in (('clock', clock, torch.int64, (1,)), ('ids', ids, torch.int32, (B,))):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
-                raise TypeError("%s: %s must be a contiguous %s device tensor" % (who, name, dtype))
-            if tuple(t.shape) != shape:
-                raise ValueError("%s: %s must be %s %s, got %s" % (who, name, dtype, list(shape), tuple(t.shape)))
-        if any(t.device != what.device for t in noise):
-            raise ValueError("%s: amp, clock and ids must be on the state's device %s" % (who, what.device))
-        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral):
-            raise TypeError("%s: seed must be an int, got %r" % (who, seed))
-        if not 0 <= seed < 2 ** 64:
-            raise ValueError("%s: seed = %d must be in [0, 2^64)" % (who, seed))
+        _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
     (gx, gy), (bx, by) = grad, buoyancy
     opt = lambda t: None if t is None else _p(t)
     check(_lib.lib().nns_spec_ns_step_linear_f32(_p(what), opt(that), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(work), work.numel(), B,
@@ -1241,11 +1218,7 @@ def spec_ns_linear_spectrum(what, rate, ny, Lx, Ly, out=None):
     if tuple(rate.shape) != (my1, nx) or rate.device != what.device:
         raise ValueError("%s: rate must be float64 [%d, %d] on the state's device, got %s on %s" % (who, my1, nx, tuple(rate.shape), rate.device))
     S = spec_ns_shells(nx, ny, Lx, Ly)[0]
-    if out is None:
-        out = torch.empty((B, 2, S), dtype=torch.float64, device=what.device)
-    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (B, 2, S) and out.is_contiguous()
-              and out.device == what.device):
-        raise ValueError("%s: out must be a contiguous float64 [%d, 2, %d] tensor on the state's device" % (who, B, S))
+    out = _spec_ns_out(who, out, (B, 2, S), what.device)
     check(_lib.lib().nns_spec_ns_linear_spectrum_f32(_p(what), _p(rate), _p(out), S, B, nx, int(ny), float(Lx), float(Ly), _stream()),
           'nns_spec_ns_linear_spectrum_f32')
     return out

@@ -84,29 +84,54 @@ class ResidualEngine(object):
         return (self.fd(u, v, p, u_prev, v_prev, stencil, out_fd), self.spectral(u, v, p, u_prev, v_prev, out_spec))
 
 
-def _pow2_axis(name, n):
+def _int(name, n):
     if isinstance(n, bool) or not isinstance(n, numbers.Integral):
         raise TypeError("%s must be an int, got %r" % (name, n))
-    if not (64 <= n <= 1024 and n & (n - 1) == 0):
-        raise ValueError("%s = %d: each axis must be a power of two in [64, 1024]" % (name, n))
     return int(n)
 
 
-def _real(name, x, positive=True):
+def _real(name, x, bound=None, kind='be a real number'):
+    """x as a finite float; bound '> 0' or '>= 0' also restricts its sign."""
     if isinstance(x, bool) or not isinstance(x, numbers.Real):
-        raise TypeError("%s must be a real number, got %r" % (name, x))
+        raise TypeError("%s must %s, got %r" % (name, kind, x))
+    if bound is None:
+        if not math.isfinite(x):
+            raise ValueError("%s = %r must be finite" % (name, x))
+        return float(x)
     x = float(x)
-    if not math.isfinite(x) or (x <= 0 if positive else x < 0):
-        raise ValueError("%s = %r must be finite and %s" % (name, x, "> 0" if positive else ">= 0"))
+    if not math.isfinite(x) or (x <= 0 if bound == '> 0' else x < 0):
+        raise ValueError("%s = %r must be finite and %s" % (name, x, bound))
     return x
 
 
+def _pair(name, x, parts):
+    """The two finite reals of ``scalar_gradient`` / ``buoyancy``."""
+    try:
+        a, b = x
+    except (TypeError, ValueError):
+        raise TypeError("%s must be two real numbers %s, got %r" % (name, parts, x))
+    return tuple(_real(name, c, kind='hold real numbers') for c in (a, b))
+
+
+def _pow2_axis(name, n):
+    n = _int(name, n)
+    if not (64 <= n <= 1024 and n & (n - 1) == 0):
+        raise ValueError("%s = %d: each axis must be a power of two in [64, 1024]" % (name, n))
+    return n
+
+
 def _count(name, n, minimum):
-    if isinstance(n, bool) or not isinstance(n, numbers.Integral):
-        raise TypeError("%s must be an int, got %r" % (name, n))
+    n = _int(name, n)
     if n < minimum:
         raise ValueError("%s = %d must be >= %d" % (name, n, minimum))
-    return int(n)
+    return n
+
+
+def _seed(seed):
+    seed = _int('seed', seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed = %d must be in [0, 2^64)" % seed)
+    return seed
 
 
 Diagnostics = collections.namedtuple('Diagnostics', ['energy', 'enstrophy', 'power_in'])
@@ -216,42 +241,35 @@ class PeriodicSolver(object):
     def __init__(self, nx, ny, dt, rho, nu, Lx=2 * math.pi, Ly=2 * math.pi, drag=0.0, kappa=None, scalar_gradient=(0.0, 0.0),
                  buoyancy=(0.0, 0.0), hyperviscosity=None, hypofriction=None, beta=0.0):
         self.nx, self.ny = _pow2_axis('nx', nx), _pow2_axis('ny', ny)
-        self.dt, self.rho = _real('dt', dt), _real('rho', rho)
-        self.nu = _real('nu', nu, positive=False)
-        self.Lx, self.Ly = _real('Lx', Lx), _real('Ly', Ly)
-        self.drag = _real('drag', drag, positive=False)
-        self.kappa = None if kappa is None else _real('kappa', kappa, positive=False)
-        try:
-            gx, gy = scalar_gradient
-        except (TypeError, ValueError):
-            raise TypeError("scalar_gradient must be two real numbers (Gx, Gy), got %r" % (scalar_gradient,))
-        self.scalar_gradient = tuple(self._finite('scalar_gradient', g) for g in (gx, gy))
-        try:
-            bx, by = buoyancy
-        except (TypeError, ValueError):
-            raise TypeError("buoyancy must be two real numbers (bx, by), got %r" % (buoyancy,))
-        self.buoyancy = tuple(self._finite('buoyancy', b) for b in (bx, by))
+        self.dt, self.rho = _real('dt', dt, '> 0'), _real('rho', rho, '> 0')
+        self.nu = _real('nu', nu, '>= 0')
+        self.Lx, self.Ly = _real('Lx', Lx, '> 0'), _real('Ly', Ly, '> 0')
+        self.drag = _real('drag', drag, '>= 0')
+        self.kappa = None if kappa is None else _real('kappa', kappa, '>= 0')
+        self.scalar_gradient = _pair('scalar_gradient', scalar_gradient, '(Gx, Gy)')
+        self.buoyancy = _pair('buoyancy', buoyancy, '(bx, by)')
         if self.buoyancy != (0.0, 0.0) and self.kappa is None:
             raise ValueError("buoyancy = %r needs a solver built with kappa (the diffusivity of the scalar that is buoyant)" % (self.buoyancy,))
         self.hyperviscosity = self._power_term('hyperviscosity', hyperviscosity, 'nu_h', 'p', 2, 8)
         self.hypofriction = self._power_term('hypofriction', hypofriction, 'mu', 'q', 1, 4)
-        self.beta = self._finite('beta', beta)
+        self.beta = _real('beta', beta, kind='hold real numbers')
         self.my1 = ops.spec_ns_kept_y(self.ny)
         self._lin = self._linear_table() if self._linear() else None      # (Re, Im)(lambda dt / 2), float32 numpy [my1, nx, 2]
-        self._lin_dev, self._rate_dev = {}, {}                              # its device copies and those of Re(lambda) (float64), by device
+        self._dev = collections.defaultdict(dict)                           # device copies of the host tables, by table ('lin', 'rate', 'stoch') and device
         self.ghat = None                       # the force's vorticity-equation spectrum g^, float32 [Bg, my1, nx, 2] (set_forcing)
         self.stoch_amp = None                  # the stochastic force's amplitude table a, float32 numpy [my1, nx] (set_stochastic_forcing)
         self.stoch_seed = 0
-        self._stoch_dev = {}                   # its device copies, by device
         self.last_simulate_used_graph = False
 
-    @staticmethod
-    def _finite(name, x):
-        if isinstance(x, bool) or not isinstance(x, numbers.Real):
-            raise TypeError("%s must hold real numbers, got %r" % (name, x))
-        if not math.isfinite(x):
-            raise ValueError("%s = %r must be finite" % (name, x))
-        return float(x)
+    def _on_device(self, key, dev, make):
+        """Table ``key`` on device dev, from the host array make() when first needed there."""
+        if dev not in self._dev[key]:
+            self._dev[key][dev] = torch.from_numpy(np.ascontiguousarray(make())).to(dev)
+        return self._dev[key][dev]
+
+    @property
+    def _lin_dev(self):                        # the linear table's device copies, by device (empty on a solver without the linear form)
+        return self._dev['lin']
 
     @staticmethod
     def _power_term(name, term, coef, power, lo, hi):
@@ -262,12 +280,10 @@ class PeriodicSolver(object):
             c, n = term
         except (TypeError, ValueError):
             raise TypeError("%s must be None or (%s, %s), got %r" % (name, coef, power, term))
-        c = _real('%s of %s' % (coef, name), c, positive=False)
-        if isinstance(n, bool) or not isinstance(n, numbers.Integral):
-            raise TypeError("%s of %s must be an int, got %r" % (power, name, n))
+        c, n = _real('%s of %s' % (coef, name), c, '>= 0'), _int('%s of %s' % (power, name), n)
         if not lo <= n <= hi:
             raise ValueError("%s of %s = %d must be in [%d, %d]" % (power, name, n, lo, hi))
-        return c, int(n)
+        return c, n
 
     def _field(self, name, a):
         if isinstance(a, np.ndarray):
@@ -344,16 +360,11 @@ class PeriodicSolver(object):
 
     def kolmogorov_forcing(self, k=4, amplitude=1.0):
         """f = (amplitude sin(2 pi k y / Ly), 0), shared by the batch; k an integer wavenumber inside the kept band (1 <= k, 3 k < ny)."""
-        if isinstance(k, bool) or not isinstance(k, numbers.Integral):
-            raise TypeError("k must be an int, got %r" % (k,))
+        k = _int('k', k)
         if not (1 <= k and 3 * k < self.ny):
             raise ValueError("k = %d is outside the kept band 1 <= k, 3 k < ny = %d" % (k, self.ny))
-        if isinstance(amplitude, bool) or not isinstance(amplitude, numbers.Real):
-            raise TypeError("amplitude must be a real number, got %r" % (amplitude,))
-        if not math.isfinite(amplitude):
-            raise ValueError("amplitude = %r must be finite" % (amplitude,))
         y = np.arange(self.ny) / float(self.ny)
-        fx = np.broadcast_to(float(amplitude) * np.sin(2 * np.pi * int(k) * y), (self.nx, self.ny)).astype(np.float32)
+        fx = np.broadcast_to(_real('amplitude', amplitude) * np.sin(2 * np.pi * k * y), (self.nx, self.ny)).astype(np.float32)
         return self.set_forcing(fx, np.zeros_like(fx))
 
     def forcing_fields(self):
@@ -370,7 +381,7 @@ class PeriodicSolver(object):
 
     # ---- stochastic forcing
     def _shell_table(self):
-        """(shell [my1, nx] int, |k|^2 [my1, nx], kept [my1, nx] bool, wt [my1, 1]) of the stored modes, float64 on the host: the shell predicate
+        """(S, shell [my1, nx] int, |k|^2 [my1, nx], kept [my1, nx] bool, wt [my1, 1], kx [1, nx]) of the stored modes, float64 on the host: the shell predicate
         floor(|k| / dk + 1/2) of ``shells()``, the step's 2/3 mask without (0, 0), and the weights 1 on j = 0, 2 on j > 0."""
         S, dk = ops.spec_ns_shells(self.nx, self.ny, self.Lx, self.Ly)
         mx = np.fft.fftfreq(self.nx) * self.nx
@@ -380,12 +391,12 @@ class PeriodicSolver(object):
         shell = np.floor(np.sqrt(k2) / dk + 0.5).astype(np.int64)
         kept = (3 * np.abs(mx)[None, :] < self.nx) & (k2 > 0)
         wt = np.where(j == 0, 1.0, 2.0)[:, None]
-        return S, shell, k2, kept, wt
+        return S, shell, k2, kept, wt, kx
 
     def shell_mode_counts(self):
         """float64 numpy [S]: N_s, the number of modes of the full spectrum in every shell that the step keeps (a stored mode with j > 0
         stands for itself and its conjugate)."""
-        S, shell, k2, kept, wt = self._shell_table()
+        S, shell, k2, kept, wt, kx = self._shell_table()
         return np.bincount(shell[kept], weights=np.broadcast_to(wt, shell.shape)[kept], minlength=S)[:S]
 
     def set_stochastic_forcing(self, rate_by_shell, seed=0):
@@ -396,13 +407,11 @@ class PeriodicSolver(object):
         the same seed, ``clock`` and ``noise_ids`` get the same noise.  A non-zero rate in a shell without a kept mode raises ValueError.
         ``set_stochastic_forcing(None)`` removes the forcing."""
         if rate_by_shell is None:
-            self.stoch_amp, self.stoch_seed, self._stoch_dev = None, 0, {}
+            self.stoch_amp, self.stoch_seed = None, 0
+            self._dev.pop('stoch', None)
             return self
-        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral):
-            raise TypeError("seed must be an int, got %r" % (seed,))
-        if not 0 <= seed < 2 ** 64:
-            raise ValueError("seed = %d must be in [0, 2^64)" % seed)
-        S, shell, k2, kept, wt = self._shell_table()
+        seed = _seed(seed)
+        S, shell, k2, kept, wt, kx = self._shell_table()
         try:
             rate = np.array(rate_by_shell, dtype=np.float64)
         except (TypeError, ValueError):
@@ -418,14 +427,15 @@ class PeriodicSolver(object):
         per_mode = np.where(count > 0, 2.0 * rate / np.maximum(count, 1.0), 0.0)            # 2 eps_s / N_s
         inside = kept & (shell < S)
         amp = np.where(inside, np.sqrt(k2) * (self.nx * self.ny) * np.sqrt(per_mode[np.minimum(shell, S - 1)]), 0.0)
-        self.stoch_amp, self.stoch_seed, self._stoch_dev = np.ascontiguousarray(amp, dtype=np.float32), int(seed), {}
+        self.stoch_amp, self.stoch_seed = np.ascontiguousarray(amp, dtype=np.float32), seed
+        self._dev.pop('stoch', None)
         return self
 
     def ring_forcing(self, rate, k_lo, k_hi, seed=0):
         """``set_stochastic_forcing`` on the ring k_lo <= k_s <= k_hi of shell centres (``shells()``): the total mean injection ``rate`` > 0 is
         shared by those shells in proportion to their mode counts, so every forced mode gets the same energy input."""
-        rate = _real('rate', rate)
-        k_lo, k_hi = _real('k_lo', k_lo, positive=False), _real('k_hi', k_hi, positive=False)
+        rate = _real('rate', rate, '> 0')
+        k_lo, k_hi = _real('k_lo', k_lo, '>= 0'), _real('k_hi', k_hi, '>= 0')
         k = self.shells()[0]
         count = np.where((k >= k_lo) & (k <= k_hi), self.shell_mode_counts(), 0.0)
         if count.sum() == 0:
@@ -437,7 +447,7 @@ class PeriodicSolver(object):
         shell's stored kept modes, recomputed from the float32 table (zeros without the force).  Defined by the HOST's binning, the float64
         predicate floor(|k| / dk + 1/2) in NumPy: on a box where a mode sits within a rounding of a shell boundary the device's ``spectrum`` could
         bin it one shell over (with Lx = Ly = 2 pi it cannot: the square root of an integer is never s + 1/2)."""
-        S, shell, k2, kept, wt = self._shell_table()
+        S, shell, k2, kept, wt, kx = self._shell_table()
         if self.stoch_amp is None:
             return np.zeros(S)
         a = self.stoch_amp.astype(np.float64)
@@ -453,9 +463,7 @@ class PeriodicSolver(object):
             state.clock = torch.zeros(1, dtype=torch.int64, device=dev)
         if state.noise_ids is None:
             state.noise_ids = torch.arange(state.batch, dtype=torch.int32, device=dev)
-        if dev not in self._stoch_dev:
-            self._stoch_dev[dev] = torch.from_numpy(self.stoch_amp).to(dev)
-        return self._stoch_dev[dev], state.clock, state.noise_ids
+        return self._on_device('stoch', dev, lambda: self.stoch_amp), state.clock, state.noise_ids
 
     # ---- linear operator
     def _linear(self):
@@ -465,8 +473,7 @@ class PeriodicSolver(object):
     def linear_operator(self):
         """complex128 numpy [my1, nx], the layout of one grid of ``what``: lambda_k of the class note on the kept modes, 0 elsewhere and at (0, 0).
         Built on the host in float64; without the new terms it is -(nu |k|^2 + drag)."""
-        S, shell, k2, kept, wt = self._shell_table()
-        kx = np.broadcast_to((2 * np.pi / self.Lx * (np.fft.fftfreq(self.nx) * self.nx))[None, :], k2.shape)
+        S, shell, k2, kept, wt, kx = self._shell_table()
         k2 = np.where(kept, k2, 1.0)
         (nu_h, p), (mu, q) = self.hyperviscosity, self.hypofriction
         with np.errstate(over='ignore', invalid='ignore'):
@@ -491,10 +498,7 @@ class PeriodicSolver(object):
 
     def _linear_of(self, state):
         """The table on the state's device (``init`` makes it, so nothing is allocated inside a capture)."""
-        dev = state.what.device
-        if dev not in self._lin_dev:
-            self._lin_dev[dev] = torch.from_numpy(self._lin).to(dev)
-        return self._lin_dev[dev]
+        return self._on_device('lin', state.what.device, lambda: self._lin)
 
     def linear_spectrum(self, state):
         """LinearRates(k, energy, enstrophy), float64 [B, S] device tensors over ``shells()``: the rates at which the linear term changes the
@@ -503,10 +507,8 @@ class PeriodicSolver(object):
         to neither (Im(lambda) only rotates a mode).  Works on any solver: without the new terms it is -2 nu Z(s) - 2 drag E(s) to rounding.
         Re(lambda) is taken from ``linear_operator()`` when first needed on a device.  Only reads the state."""
         self._state(state)
-        dev = state.what.device
-        if dev not in self._rate_dev:
-            self._rate_dev[dev] = torch.from_numpy(np.ascontiguousarray(self.linear_operator().real)).to(dev)
-        out = ops.spec_ns_linear_spectrum(state.what, self._rate_dev[dev], self.ny, self.Lx, self.Ly)
+        rate = self._on_device('rate', state.what.device, lambda: self.linear_operator().real)
+        out = ops.spec_ns_linear_spectrum(state.what, rate, self.ny, self.Lx, self.Ly)
         return LinearRates(self.shells()[0], out[:, 0], out[:, 1])
 
     def _force_of(self, state):
@@ -524,27 +526,24 @@ class PeriodicSolver(object):
         return state.that is not None and self.buoyancy != (0.0, 0.0)
 
     def _launch_steps(self, state, nsteps):
+        what, that = state.what, state.that
+        box = (self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt)      # what every forced form takes after the mean
+        kappa = 0.0 if self.kappa is None else self.kappa
+        amp, clock, ids = (None, None, None) if self.stoch_amp is None else self._noise_of(state)
         if self._linear():
-            amp, clock, ids = (None, None, None) if self.stoch_amp is None else self._noise_of(state)
-            ops.spec_ns_step_linear_(state.what, state.that, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt,
-                                     0.0 if self.kappa is None else self.kappa, self.scalar_gradient, self.buoyancy, self._linear_of(state), amp,
+            ops.spec_ns_step_linear_(what, that, state.mean, *box, kappa, self.scalar_gradient, self.buoyancy, self._linear_of(state), amp,
                                      self.stoch_seed, clock, ids, nsteps)
         elif self.stoch_amp is not None:
-            amp, clock, ids = self._noise_of(state)
-            ops.spec_ns_step_stochastic_(state.what, state.that, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt,
-                                         self.nu, self.drag, 0.0 if self.kappa is None else self.kappa, self.scalar_gradient, self.buoyancy, amp,
+            ops.spec_ns_step_stochastic_(what, that, state.mean, *box, self.nu, self.drag, kappa, self.scalar_gradient, self.buoyancy, amp,
                                          self.stoch_seed, clock, ids, nsteps)
         elif self._buoyant(state):
-            ops.spec_ns_step_buoyant_(state.what, state.that, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt,
-                                      self.nu, self.drag, self.kappa, self.scalar_gradient, self.buoyancy, nsteps)
-        elif state.that is not None:
-            ops.spec_ns_step_scalar_(state.what, state.that, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt,
-                                     self.nu, self.drag, self.kappa, self.scalar_gradient, nsteps)
+            ops.spec_ns_step_buoyant_(what, that, state.mean, *box, self.nu, self.drag, self.kappa, self.scalar_gradient, self.buoyancy, nsteps)
+        elif that is not None:
+            ops.spec_ns_step_scalar_(what, that, state.mean, *box, self.nu, self.drag, self.kappa, self.scalar_gradient, nsteps)
         elif self._forced():
-            ops.spec_ns_step_forced_(state.what, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu,
-                                     self.drag, nsteps)
+            ops.spec_ns_step_forced_(what, state.mean, *box, self.nu, self.drag, nsteps)
         else:
-            ops.spec_ns_step_(state.what, state.mean, state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu, nsteps)
+            ops.spec_ns_step_(what, state.mean, *box[1:], self.nu, nsteps)
 
     def step(self, state, nsteps=1):
         """nsteps time steps in place (no allocation, no host synchronisation)."""
@@ -648,9 +647,6 @@ class PeriodicSolver(object):
         nsteps, save_every = _count('nsteps', nsteps, 0), _count('save_every', save_every, 1)
         if nsteps % save_every:
             raise ValueError("nsteps = %d is not a multiple of save_every = %d" % (nsteps, save_every))
-        if self.ghat is not None and self.ghat.shape[0] not in (1, self._field('u', u0).shape[0]):
-            raise ValueError("the force is per grid for a batch of %d, the initial condition has %d grids"
-                             % (self.ghat.shape[0], self._field('u', u0).shape[0]))
         state = self.init(u0, v0, theta0)
         self._force_of(state)
         T = nsteps // save_every + 1
