@@ -556,6 +556,28 @@ int nns_spec_ns_step_linear_f32(float* what, float* that, const float* mean, con
  * the shells, order of summation and determinism of nns_spec_ns_spectrum_f32; its errors, plus rate == NULL. */
 int nns_spec_ns_linear_spectrum_f32(const float* what, const double* rate, double* out, int nshell, int batch, int nx, int ny, double Lx,
                                     double Ly, void* stream);
+/* Reverse mode of nns_spec_ns_step_forced_f32 (restatement: tests/pspec_adjoint_oracle.py): the vector-Jacobian product of nsteps steps, as
+ * fused kernels in the layout of what.  Cotangents are real band-limited fields paired by the plain grid sum <a, b> = sum a b and stored as
+ * their spectra (rfft2 convention, unnormalised, the layout of what): no half-spectrum weights.  With N'(s)^T kappa = M [u kappa_x + v kappa_y]
+ * - M [kappa_x w_y - kappa_y w_x]^ / |k|^2 (u, v, w_x, w_y of the stage state s), E = exp(-(nu |k|^2 + drag) dt / 2) and lam the cotangent of a
+ * step's result, one step backwards is
+ *     k4 = dt/6 lam                   r = N'(s3)^T k4    wbar  = E^2 lam + E^2 r
+ *     k3 = dt/3 E lam + dt E r        r = N'(s2)^T k3    wbar += E r
+ *     k2 = dt/3 E lam + dt/2 r        r = N'(s1)^T k2    wbar += E r
+ *     k1 = dt/6 E^2 lam + dt/2 E r    r = N'(s0)^T k1    wbar += r              gbar += k1 + k2 + k3 + k4
+ * what0: float32 [nsteps][batch][my1][nx][2], the spectrum at the START of every step (only read); the stage states s1, s2, s3 are recomputed
+ * from it by the forward's own kernels, bitwise the forward's.  mean, ghat, gbatch, dt, nu, drag: those of the forward call (the mean flow and
+ * g enter as constants; the mean is not differentiated).  lam: float32 [batch][my1][nx][2], in the cotangent of the state after the last step
+ * (its part outside the 2/3 band and its (0, 0) mode are ignored), out the cotangent of the state before the first.  gbar: float32
+ * [batch][my1][nx][2] or NULL, out the cotangent of g^, ALWAYS one per grid and summed over the steps of the call (a force shared by the batch:
+ * sum it over the batch); overwritten, not added to.  Results are zero outside the band and at (0, 0).  A grid's result does not depend on
+ * its batch neighbours, and nsteps steps in one call are bitwise nsteps calls of one step, last first.  work: nns_spec_ns_adjoint_workspace
+ * bytes (13 compacted fields: it also serves every unscalared nns_spec_ns_* call).  16 launches per step (7 recompute, 9 adjoint), no
+ * allocation, no host synchronisation (capturable).  Errors as nns_spec_ns_step_forced_f32. */
+int nns_spec_ns_adjoint_workspace(int batch, int nx, int ny, size_t* bytes);
+int nns_spec_ns_step_adjoint_f32(const float* what0, const float* mean, const float* ghat, int gbatch, float* lam, float* gbar, void* work,
+                                 size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
+                                 int nsteps, void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

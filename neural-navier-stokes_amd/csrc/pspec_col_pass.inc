@@ -4,6 +4,7 @@
 // (a lambda's body is optimised on its own before it is inlined, and came out a few instructions and registers different).
 // STOCH (ps_col_kernel's note) is false in every kernel without a PsStoch argument, whose text below is then what it was.
 // LINEAR likewise (a PsLinear argument): the vorticity's factors E - 1, E^2 - 1 are then complex, from the table lin, and scal's complex form applies.
+// STAGES likewise (a PsKeep argument): stages 1-3 also store the next stage's input to stage_out.
 {
         const float2* ph = TH ? Ph + a.fstride : Ph;
         float2* Ws = TH ? Th : W;
@@ -85,6 +86,9 @@
                     }
                     if (lok) Ws[si] = make_float2(w.x, w.y);
                     y[m] = w;
+                }
+                if constexpr (STAGES) {
+                    if (lok) stage_out[si] = make_float2(y[m].x, y[m].y);
                 }
             }
         }

@@ -56,6 +56,14 @@
 // Measured on the MI355X (profiles/pspec_linear_run.json): linear / steady-forced step 1.016x at 256^2 x 64 and 1.003x at 1024^2 x 8; the
 // LINEAR kernels hold 132 ... 151 VGPRs (3 waves per SIMD where most forced twins run 4; profiles/pspec_linear_isa.txt), no scratch.
 //
+// Reverse mode (nns_spec_ns_step_adjoint_f32; restatement: tests/pspec_adjoint_oracle.py): the vector-Jacobian product of the forced step, last
+// step first, in the same layout (cotangents are spectra of real fields paired by the grid sum).  Per step the stage states are recomputed
+// from the step's saved start spectrum by the forward's own launches, whose column kernels of stages 1-3 take a trailing PsKeep (STAGES) and
+// also store the next stage's input; then ps_col_adj_kernel<nx, S>, S = 4 .. 0, and ps_row_adj_kernel<ny> between them apply N'(s)^T and the
+// transposed Lawson update (their notes below).  7 + 9 launches per step; kernels without the PsKeep keep their names and their code.
+// Measured on the MI355X (profiles/pspec_adjoint_run.json): adjoint / forward step 2.57x at 256^2 x 64 and 2.72x at 1024^2 x 8; the new kernels
+// hold 99 ... 184 VGPRs, no scratch.
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 #include "nns_common.h"
 #include "fft_lds.h"
@@ -107,6 +115,17 @@ struct PsStoch {          // the last argument of the STOCH column kernels (stag
 };
 struct PsLinear {         // the argument of the LINEAR column kernels (stages 1-3 of a linear step), after PsScalar and before PsStoch
     const float2* lin;    // (Re, Im)(lambda dt / 2) [my1][nx], the layout of one grid of W, shared by the batch
+};
+struct PsKeep {           // the last argument of the STAGES column kernels (stages 1-3 of the adjoint's recomputation; no scalar, noise or table)
+    float2* stage;        // [B][my1][nx], the layout of W: receives the next stage's input spectrum (s1, s2 or s3)
+};
+struct PsAdj {            // the argument of the adjoint column kernels
+    float2* lam;          // [B][my1][nx]: the cotangent of the step's result; stage 0 writes the cotangent of its input over it
+    float2* wbar;         // [B][my1][nx]: the cotangent of the step's input while it is summed (stages 3..0)
+    float2* gbar;         // [B][my1][nx] or NULL: the cotangent of g^, summed over stages and steps
+    const float2* state;  // [B][my1][nx]: the stage state the NEXT adjoint stage linearises about (S = 4: s3, 3: s2, 2: s1, 1: s0), unused by S = 0
+    float hdrag;          // alpha dt / 2
+    int ginit;            // S = 4: 1 starts gbar (the first step a call takes), 0 adds to it
 };
 template <typename U, typename T, typename... R> __device__ __forceinline__ U pick(T t, R... r) {           // the pack's element of type U
     if constexpr (std::is_same_v<U, T>) return t;
@@ -279,6 +298,8 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
 // STOCH (a PsStoch ends the pack; FORCED, S = 1 or 4): S = 1 advances the step count, S = 4 adds the kick to the vorticity's w^ (not the scalar's).
 // LINEAR (a PsLinear in the pack, after PsScalar, before PsStoch; FORCED, S = 1..3): the vorticity's L dt / 2 is the complex table entry
 // lin[j][i], not hnudt |k|^2 - alpha dt / 2 (a.hnudt and fc.hdrag are then unused); the scalar's stays hkdt |k|^2.
+// STAGES (a PsKeep alone in the pack; S = 1..3): the next stage's input spectrum is also stored, lane-owned and coalesced like W / A, for the
+// adjoint (ps_col_adj_kernel) to linearise about; the arithmetic is untouched, so the recomputed stages are the forward's bits.
 template <int N, int S, bool FORCED = false, bool SCALAR = false, typename... Sc>
 __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, float2* __restrict__ W,
                                                     float2* __restrict__ A, const float* __restrict__ mean, PsArgs a, int emit,
@@ -286,8 +307,10 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     static_assert(!FORCED || S >= 1, "stage 0 only prepares: it has no forced form");
     constexpr bool STOCH = (std::is_same_v<Sc, PsStoch> || ... || false);
     constexpr bool LINEAR = (std::is_same_v<Sc, PsLinear> || ... || false);
-    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0),
+    constexpr bool STAGES = (std::is_same_v<Sc, PsKeep> || ... || false);
+    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0) + (STAGES ? 1 : 0),
                   "PsScalar is the SCALAR kernel's argument, PsLinear after it the LINEAR kernel's, PsStoch last the STOCH kernel's");
+    static_assert(!STAGES || (S >= 1 && S <= 3 && !SCALAR && !STOCH && !LINEAR), "the stage store is that of stages 1-3 of the plain and the forced form");
     static_assert(!LINEAR || (FORCED && S >= 1 && S <= 3), "the complex factors are those of stages 1-3 of the forced form");
     static_assert(!STOCH || (FORCED && (S == 1 || S == 4)), "the kick is stage 4's and the step count stage 1's, both of the forced form");
     using L = PsLds<N>;
@@ -321,6 +344,8 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     }
     [[maybe_unused]] const float2* lin = nullptr;
     if constexpr (LINEAR) lin = pick<PsLinear>(sc...).lin;
+    [[maybe_unused]] float2* stage_out = nullptr;
+    if constexpr (STAGES) stage_out = pick<PsKeep>(sc...).stage;
     for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
         int tx = threadIdx.x;
         asm volatile("" : "+v"(tx));
@@ -358,6 +383,255 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
         if constexpr (SCALAR) {
             constexpr bool TH = true;
 #include "pspec_col_pass.inc"
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- reverse mode (restatement: tests/pspec_adjoint_oracle.py)
+// The vector-Jacobian product of the forced step.  Cotangents are real band-limited fields paired by the grid sum, kept as spectra in the
+// layout of W, so E and the mask are their own adjoints.  With kappa the cotangent of a stage's N and s that stage's state,
+//     N'(s)^T kappa = M [u kappa_x + v kappa_y] - M [kappa_x w_y - kappa_y w_x]^ / |k|^2       (u, v, w_x, w_y of s; the means in u, v)
+// ps_row_adj_kernel is the SCALAR row kernel's twin: three inverse transforms along y (u + i v and w_x + i w_y from G fields 0-3 of s,
+// kappa_x + i kappa_y from G fields 4 and 5), the two products in registers, two forward transforms, the kept modes to Ph fields 0 and 1.  Two
+// complex lines are live at a time, as there.
+template <int N>
+__global__ __launch_bounds__(kT) void ps_row_adj_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a) {
+    using L = PsLds<N>;
+    constexpr int TPF = L::TPF;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const cf* tab = ps_tables<N>(smem);
+    unsigned char* lines = smem + L::TAB_BYTES;
+    const int my1 = a.my1;
+    const long niter = (a.nlines + L::LINES - 1) / L::LINES;
+    for (long it = blockIdx.x; it < niter; it += gridDim.x) {
+        int tx = threadIdx.x;
+        asm volatile("" : "+v"(tx));
+        const int wave = tx / kWave, lane = tx % kWave, sub = lane / TPF, tid = lane % TPF;
+        const int line = wave * L::FPW + sub;
+        cf* xb = reinterpret_cast<cf*>(lines + (size_t)line * L::LINE_BYTES);
+        const long row_raw = it * L::LINES + line;
+        const bool valid = row_raw < a.nlines;
+        const long row = valid ? row_raw : a.nlines - 1;
+        const float2* g0 = G + (size_t)row * my1;
+        auto load2 = [&](const float2* ga, const float2* gb, cf (&z)[16]) {          // ps_row_kernel's Hermitian fill
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const int e = tid + TPF * m;
+                z[m] = {0.f, 0.f};
+                if (m < 8) {
+                    if (e < my1) {
+                        const float2 p = ga[e], q = gb[e];
+                        z[m] = e == 0 ? cf{p.x, q.x} : cf{p.x - q.y, p.y + q.x};
+                    }
+                } else {
+                    const int r = N - e;
+                    if (r < my1) {
+                        const float2 p = ga[r], q = gb[r];
+                        z[m] = {p.x + q.y, q.x - p.y};
+                    }
+                }
+            }
+        };
+        auto store = [&](const cf (&z)[16], float2* o) {
+            if (valid) {
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    const int e = tid + TPF * m;
+                    if (e < my1) o[e] = make_float2(z[m].x, z[m].y);
+                }
+            }
+        };
+        cf zu[16], zk[16];
+        load2(g0, g0 + a.fstride, zu);                           // u + i v
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
+        __builtin_amdgcn_sched_barrier(0);
+        load2(g0 + 4 * a.fstride, g0 + 5 * a.fstride, zk);       // kappa_x + i kappa_y: stays
+        fft_line<float, N, true>(zk, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zu[m] = {zu[m].x * zk[m].x + zu[m].y * zk[m].y, 0.f};        // u kappa_x + v kappa_y
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
+        store(zu, Ph + (size_t)row * my1);
+        __builtin_amdgcn_sched_barrier(0);
+        load2(g0 + 2 * a.fstride, g0 + 3 * a.fstride, zu);       // w_x + i w_y
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zu[m] = {zk[m].x * zu[m].y - zk[m].y * zu[m].x, 0.f};        // kappa_x w_y - kappa_y w_x
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
+        store(zu, Ph + a.fstride + (size_t)row * my1);
+    }
+}
+
+// The adjoint column pass, S = 4 .. 0 in the order it runs (tiling and LDS staging of ps_col_kernel).  With lam the cotangent of the step's
+// result, r = N'(s)^T kappa of the stage just evaluated by the row pass (S < 4: Ph fields 0 and 1 staged and forward-transformed along x,
+// r = keep ? Q1 - Q2 / |k|^2 : 0) and E - 1, E^2 - 1 in the forward's expm1 form:
+//     S = 4                                    kappa4 = dt/6 lam                      prepares s3
+//     S = 3   wbar  = E^2 lam + E^2 r          kappa3 = dt/3 E lam + dt E r           prepares s2
+//     S = 2   wbar += E r                      kappa2 = dt/3 E lam + dt/2 r           prepares s1
+//     S = 1   wbar += E r                      kappa1 = dt/6 E^2 lam + dt/2 E r       prepares s0
+//     S = 0   lam   = wbar + r                 (the cotangent of the step's input, the lam of the step before)
+// gbar += kappa in every stage that makes one.  lam, wbar and gbar are lane-owned and coalesced, like W / A.  Preparing: the four spectra of
+// the state (ad.state, the forward's field<0..3> arithmetic, the mean in the (0, 0) mode) inverse-transformed along x to G fields 0-3, and
+// i kx kappa^, i ky kappa^ to G fields 4 and 5 (these first: kappa's registers are free before the state is loaded).
+template <int N, int S>
+__global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, const float* __restrict__ mean,
+                                                        PsArgs a, PsAdj ad) {
+    static_assert(S >= 0 && S <= 4, "adjoint stages 4 .. 0");
+    using L = PsLds<N>;
+    constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const cf* tab = ps_tables<N>(smem);
+    unsigned char* lines = smem + L::TAB_BYTES;
+    const int my1 = a.my1;
+    const long ntiles = (a.nlines + CW - 1) / CW;
+    const float dt = a.dt, dt2 = 0.5f * dt, dt3 = dt / 3.f, dt6 = dt / 6.f;
+    for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        int tx = threadIdx.x;
+        asm volatile("" : "+v"(tx));
+        const int wave = tx / kWave, lane = tx % kWave, sub = lane / TPF, tid = lane % TPF;
+        const int line = wave * L::FPW + sub;
+        cf* xb = reinterpret_cast<cf*>(lines + (size_t)line * L::LINE_BYTES);
+        float* mine = reinterpret_cast<float*>(xb) + (line % L::SKEW_MOD) * L::SKEW_DW;
+        const int cc = tx % CW, cr = tx / CW;
+        float* cp = reinterpret_cast<float*>(lines + (size_t)cc * L::LINE_BYTES) + (cc % L::SKEW_MOD) * L::SKEW_DW;
+        const long scol = t * CW + cc;
+        const bool sok = scol < a.nlines;
+        const size_t sbase = sok ? (size_t)(scol / my1) * N * my1 + (size_t)(scol % my1) : 0;     // (b, i = 0, j) in [b][i][j]
+        const long lcol = t * CW + line;
+        const bool lok = lcol < a.nlines;
+        const int lb = lok ? (int)(lcol / my1) : 0, lj = lok ? (int)(lcol % my1) : 0;
+        const size_t wbase = (size_t)(lok ? lcol : 0) * N;
+        int tv = tid;
+        asm volatile("" : "+v"(tv));
+        const float ky = a.ky1 * (float)lj;
+        // Ph's field `ph` of the tile through the LDS transpose, forward-transformed along x
+        auto consume = [&](const float2* ph, cf (&z)[16]) {
+            for (int r = cr; r < N; r += RPI) {
+                const float2 v = sok ? ph[sbase + (size_t)r * my1] : make_float2(0.f, 0.f);
+                cp[2 * r] = v.x; cp[2 * r + 1] = v.y;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int m = 0; m < 16; ++m) z[m] = {mine[2 * (tv + TPF * m)], mine[2 * (tv + TPF * m) + 1]};
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            fft_line<float, N, false>(z, tab, tab + N / 2, xb, tv);
+        };
+        [[maybe_unused]] cf kap[16];
+        if constexpr (S < 4) {
+            cf r[16], z[16];
+            consume(Ph, r);
+            __syncthreads();                        // the next staging overwrites line images other waves may still read
+            consume(Ph + a.fstride, z);
+            int te = tv;
+            asm volatile("" : "+v"(te), "+v"(z[0].x));
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const int e = te + TPF * m;
+                const int mx = m < 8 ? e : e - N;
+                const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (mx | lj) != 0;
+                const float kx = a.kx1 * (float)mx;
+                const float k2 = kx * kx + ky * ky;
+                const float x = a.hnudt * k2 - ad.hdrag;                             // L dt / 2
+                const float em1 = expm1f(x), em2 = expm1f(2.f * x);
+                const float ik2 = k2 > 0.f ? 1.f / k2 : 0.f;
+                const cf rr = keep ? cf{fmaf(-ik2, z[m].x, r[m].x), fmaf(-ik2, z[m].y, r[m].y)} : cf{0.f, 0.f};
+                const size_t si = wbase + e;
+                const float2 l2 = lok ? ad.lam[si] : make_float2(0.f, 0.f);
+                const cf lam = keep ? cf{l2.x, l2.y} : cf{0.f, 0.f};
+                cf wb;
+                if constexpr (S == 3) {
+                    wb = scal(em2, cf{lam.x + rr.x, lam.y + rr.y});
+                    kap[m] = scal(em1, axpy(dt, rr, cf{dt3 * lam.x, dt3 * lam.y}));
+                } else {
+                    const float2 w2 = lok ? ad.wbar[si] : make_float2(0.f, 0.f);
+                    if constexpr (S == 0) {
+                        wb = {w2.x + rr.x, w2.y + rr.y};
+                    } else {
+                        const cf er = scal(em1, rr);
+                        wb = {w2.x + er.x, w2.y + er.y};
+                        if constexpr (S == 2) {
+                            const cf el = scal(em1, lam);
+                            kap[m] = axpy(dt2, rr, cf{dt3 * el.x, dt3 * el.y});
+                        } else {
+                            const cf el = scal(em2, lam);
+                            kap[m] = axpy(dt2, er, cf{dt6 * el.x, dt6 * el.y});
+                        }
+                    }
+                }
+                if (lok) {
+                    if constexpr (S == 0) {
+                        ad.lam[si] = make_float2(wb.x, wb.y);
+                    } else {
+                        ad.wbar[si] = make_float2(wb.x, wb.y);
+                        if (ad.gbar) {
+                            const float2 g2 = ad.gbar[si];
+                            ad.gbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
+                        }
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const int e = tv + TPF * m;
+                const int mx = m < 8 ? e : e - N;
+                const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (mx | lj) != 0;
+                const size_t si = wbase + e;
+                const float2 l2 = lok ? ad.lam[si] : make_float2(0.f, 0.f);
+                kap[m] = keep ? cf{dt6 * l2.x, dt6 * l2.y} : cf{0.f, 0.f};
+                if (lok && ad.gbar) {
+                    const float2 g2 = ad.ginit ? make_float2(0.f, 0.f) : ad.gbar[si];
+                    ad.gbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
+                }
+            }
+        }
+        if constexpr (S >= 1) {
+            const float U0 = lok ? mean[2 * lb] : 0.f, V0 = lok ? mean[2 * lb + 1] : 0.f;
+            // field F of the spectrum y (ps_col_kernel's): transformed along x and written to G through the LDS transpose
+            auto field = [&](auto fc, const cf (&y)[16]) {
+                constexpr int F = decltype(fc)::value;
+                int te = tv;
+                asm volatile("" : "+v"(te));
+                cf o[16];
+#pragma unroll
+                for (int m = 0; m < 16; ++m) {
+                    const int e = te + TPF * m;
+                    const int mx = m < 8 ? e : e - N;
+                    const float kx = a.kx1 * (float)mx;
+                    const float k2 = kx * kx + ky * ky;
+                    const float ik2 = k2 > 0.f ? a.inv_n / k2 : 0.f;
+                    if constexpr (F == 0) o[m] = imul(ky * ik2, y[m]);                 // u^ = i ky psi^
+                    else if constexpr (F == 1) o[m] = imul(-kx * ik2, y[m]);           // v^ = -i kx psi^
+                    else if constexpr (F == 2 || F == 4) o[m] = imul(kx * a.inv_n, y[m]);   // (w_x)^, (kappa_x)^
+                    else o[m] = imul(ky * a.inv_n, y[m]);                              // (w_y)^, (kappa_y)^
+                }
+                if constexpr (F < 2) {
+                    if (te == 0 && lj == 0) o[0] = {F == 0 ? U0 : V0, 0.f};           // the mean flow in the (0, 0) mode
+                }
+                fft_line<float, N, true>(o, tab, tab + N / 2, xb, tv);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int m = 0; m < 16; ++m) { mine[2 * (tv + TPF * m)] = o[m].x; mine[2 * (tv + TPF * m) + 1] = o[m].y; }
+                __syncthreads();
+                if (sok) {
+                    float2* g = G + (size_t)F * a.fstride + sbase;
+                    for (int r = cr; r < N; r += RPI) g[(size_t)r * my1] = make_float2(cp[2 * r], cp[2 * r + 1]);
+                }
+                __syncthreads();
+            };
+            static_for<4, 6>([&](auto fc) { field(fc, kap); });
+            cf y[16];
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const float2 w = lok ? ad.state[wbase + tv + TPF * m] : make_float2(0.f, 0.f);
+                y[m] = {w.x, w.y};
+            }
+            static_for<0, 4>([&](auto fc) { field(fc, y); });
+        } else {
+            __syncthreads();                        // the next staging overwrites line images other waves may still read
         }
     }
 }
@@ -815,13 +1089,14 @@ int launch_row(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s, Gr..
 template <int N, int S, bool FORCED, typename... X>
 int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
                hipStream_t s, X... x) {
-    constexpr bool SC = has<PsScalar, X...>, LI = has<PsLinear, X...>, ST = has<PsStoch, X...>;
+    constexpr bool SC = has<PsScalar, X...>, LI = has<PsLinear, X...>, ST = has<PsStoch, X...>, KE = has<PsKeep, X...>;
     constexpr auto kern = ps_col_kernel<N, S, FORCED, SC, X...>;
     std::conditional_t<FORCED, PsForce, PsNoForce> f{};
     if constexpr (FORCED) f = *fc;
     if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
     hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, f, x...);
-    return check_launch(LI       ? (SC ? "spec_ns linear scalar column pass" : "spec_ns linear column pass")
+    return check_launch(KE       ? "spec_ns stage-keeping column pass"
+                        : LI     ? (SC ? "spec_ns linear scalar column pass" : "spec_ns linear column pass")
                         : ST     ? (SC ? "spec_ns stochastic scalar column pass" : "spec_ns stochastic column pass")
                         : SC     ? "spec_ns scalar column pass"
                         : FORCED ? "spec_ns forced column pass"
@@ -861,6 +1136,47 @@ int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, c
     }
 }
 
+// Stage S = 1..3 of the adjoint's recomputation: the plain or the forced kernel with the stage store (launch_col_stage never names this form)
+template <int N>
+int launch_col_keep(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, const PsForce* fc,
+                    float2* stage, hipStream_t s) {
+    const PsKeep ke{stage};
+    auto go = [&](auto stage_c) {
+        constexpr int K = decltype(stage_c)::value;
+        return fc ? launch_col<N, K, true>(Ph, G, W, A, mean, a, 1, fc, s, ke) : launch_col<N, K, false>(Ph, G, W, A, mean, a, 1, fc, s, ke);
+    };
+    switch (S) {
+        case 1: return go(std::integral_constant<int, 1>{});
+        case 2: return go(std::integral_constant<int, 2>{});
+        default: return go(std::integral_constant<int, 3>{});
+    }
+}
+
+template <int N>
+int launch_row_adj(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s) {
+    constexpr auto kern = ps_row_adj_kernel<N>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a);
+    return check_launch("spec_ns adjoint row pass");
+}
+
+template <int N>
+int launch_col_adj(int S, const float2* Ph, float2* G, const float* mean, const PsArgs& a, const PsAdj& ad, hipStream_t s) {
+    auto go = [&](auto stage_c) {
+        constexpr auto kern = ps_col_adj_kernel<N, decltype(stage_c)::value>;
+        if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+        hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, mean, a, ad);
+        return check_launch("spec_ns adjoint column pass");
+    };
+    switch (S) {
+        case 0: return go(std::integral_constant<int, 0>{});
+        case 1: return go(std::integral_constant<int, 1>{});
+        case 2: return go(std::integral_constant<int, 2>{});
+        case 3: return go(std::integral_constant<int, 3>{});
+        default: return go(std::integral_constant<int, 4>{});
+    }
+}
+
 size_t step_bytes(int batch, int nx, int ny) { return (size_t)6 * batch * nx * kept_y(ny) * sizeof(float2); }
 size_t init_bytes(int batch, int nx, int ny) { return (size_t)2 * batch * nx * (ny / 2 + 1) * sizeof(float2); }
 size_t fields_bytes(int batch, int nx, int ny) {
@@ -876,6 +1192,12 @@ size_t work_bytes(int batch, int nx, int ny) {
 // the scalar step's A, A_theta, G[6], Ph[2]: 10 compacted fields against 6 (its init and field need one rfft2 spectrum: inside work_bytes)
 size_t scalar_work_bytes(int batch, int nx, int ny) {
     const size_t b = work_bytes(batch, nx, ny), st = (size_t)10 * batch * nx * kept_y(ny) * sizeof(float2);
+    return st > b ? st : b;
+}
+
+// the adjoint's A, wbar, G[6], Ph[2] (the scalar step's layout, wbar in A_theta's place) and the stage states s1, s2, s3: 13 compacted fields
+size_t adjoint_work_bytes(int batch, int nx, int ny) {
+    const size_t b = work_bytes(batch, nx, ny), st = (size_t)13 * batch * nx * kept_y(ny) * sizeof(float2);
     return st > b ? st : b;
 }
 
@@ -915,17 +1237,29 @@ int check_box(const char* what, int nx, int ny, double Lx, double Ly) {
     return check_axes(what, nx, ny);
 }
 
-int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, bool scalar) {
-    const size_t need = scalar ? scalar_work_bytes(batch, nx, ny) : work_bytes(batch, nx, ny);
+enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2 };      // a bool converts: false the flow's workspace, true the scalar's
+
+int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int kind) {
+    const size_t need = kind == kWorkAdjoint ? adjoint_work_bytes(batch, nx, ny)
+                        : kind == kWorkScalar ? scalar_work_bytes(batch, nx, ny)
+                                              : work_bytes(batch, nx, ny);
     if (wbytes < need)
         return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", what, wbytes, need,
-                    scalar ? "nns_spec_ns_scalar_workspace" : "nns_spec_ns_workspace");
+                    kind == kWorkAdjoint ? "nns_spec_ns_adjoint_workspace" : kind == kWorkScalar ? "nns_spec_ns_scalar_workspace" : "nns_spec_ns_workspace");
     return NNS_OK;
 }
 
-int check_common(const char* what, int batch, int nx, int ny, double Lx, double Ly, size_t wbytes, bool scalar = false) {
+int check_common(const char* what, int batch, int nx, int ny, double Lx, double Ly, size_t wbytes, int kind = kWorkFlow) {
     if (int rc = check_box(what, nx, ny, Lx, Ly)) return rc;
-    return check_work(what, batch, nx, ny, wbytes, scalar);
+    return check_work(what, batch, nx, ny, wbytes, kind);
+}
+
+// dt, nu, drag and nsteps of a step, forward or adjoint
+int check_step_numbers(const char* who, double dt, double nu, double drag, int nsteps) {
+    if (!(dt > 0) || !std::isfinite(dt) || !(nu >= 0) || !std::isfinite(nu) || nsteps < 0)
+        return fail(NNS_ERR_INVALID_ARG, "%s: dt = %g must be > 0, nu = %g >= 0, nsteps = %d >= 0", who, dt, nu, nsteps);
+    if (!(drag >= 0) || !std::isfinite(drag)) return fail(NNS_ERR_INVALID_ARG, "%s: drag = %g must be finite and >= 0", who, drag);
+    return NNS_OK;
 }
 
 int check_gbatch(const char* what, const float* ghat, int gbatch, int batch) {
@@ -1095,9 +1429,7 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
                         double gx, double gy, double bx, double by, int nsteps, void* stream, const PsStoch* st = nullptr,
                         const float* lin = nullptr) {
     if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
-    if (!(dt > 0) || !std::isfinite(dt) || !(nu >= 0) || !std::isfinite(nu) || nsteps < 0)
-        return fail(NNS_ERR_INVALID_ARG, "%s: dt = %g must be > 0, nu = %g >= 0, nsteps = %d >= 0", who, dt, nu, nsteps);
-    if (!(drag >= 0) || !std::isfinite(drag)) return fail(NNS_ERR_INVALID_ARG, "%s: drag = %g must be finite and >= 0", who, drag);
+    if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
     if (!(kappa >= 0) || !std::isfinite(kappa) || !std::isfinite(gx) || !std::isfinite(gy))
         return fail(NNS_ERR_INVALID_ARG, "%s: kappa = %g must be finite and >= 0, the gradient (%g, %g) finite", who, kappa, gx, gy);
     if (int rc = check_buoyancy(who, bx, by)) return rc;
@@ -1192,6 +1524,64 @@ NNS_API int nns_spec_ns_step_linear_f32(float* what, float* that, const float* m
     return spec_ns_step("spec_ns_step_linear", what, that, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, 0.0, 0.0,
                         that ? kappa : 0.0, that ? gx : 0.0, that ? gy : 0.0, that ? bx : 0.0, that ? by : 0.0, nsteps, stream,
                         noise ? &st : nullptr, lin);
+}
+
+NNS_API int nns_spec_ns_adjoint_workspace(int batch, int nx, int ny, size_t* bytes) {
+    if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_adjoint_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
+    if (int rc = check_axes("spec_ns_adjoint_workspace", nx, ny)) return rc;
+    *bytes = adjoint_work_bytes(batch, nx, ny);
+    return NNS_OK;
+}
+
+// The reverse mode of spec_ns_step's forced form, last step first.  Per step: the stage states s1, s2, s3 recomputed from the step's saved start
+// spectrum by the forward's own launches (stage 0, then three row / column pairs whose column kernels also store the next stage's input: 7),
+// then the adjoint's stage 4 column launch and four row / column pairs (9).  No allocation, no host synchronisation.
+NNS_API int nns_spec_ns_step_adjoint_f32(const float* what0, const float* mean, const float* ghat, int gbatch, float* lam, float* gbar, void* work,
+                                         size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
+                                         int nsteps, void* stream) {
+    const char* who = "spec_ns_step_adjoint";
+    if (!what0 || !mean || !lam || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
+    if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
+    if (int rc = check_gbatch(who, ghat, gbatch, batch)) return rc;
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, kWorkAdjoint)) return rc;
+    if (nsteps == 0) {
+        if (!gbar) return NNS_OK;
+        void* zb[1] = {gbar};
+        const long zn[1] = {(long)((size_t)batch * kept_y(ny) * nx * sizeof(float2))};
+        return zero_buffers(zb, zn, 1, as_stream(stream));
+    }
+    hipStream_t s = as_stream(stream);
+    const PsWork L(work, batch, nx, ny, true, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);      // A, wbar (A_theta's place), G[6], Ph[2]
+    const long fstride = L.col.fstride;
+    float2* stages = L.Ph + 2 * fstride;                                                       // s1, s2, s3
+    const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
+    const PsForce* fc = ghat || drag > 0 ? &force : nullptr;                                   // the forward's choice of kernels: its bits
+    PsAdj ad{reinterpret_cast<float2*>(lam), L.At, reinterpret_cast<float2*>(gbar), nullptr, force.hdrag, 0};
+    auto row = [&]() { return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row<decltype(n)::value>(L.G, L.Ph, L.row, s); }); };
+    auto row_adj = [&]() { return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row_adj<decltype(n)::value>(L.G, L.Ph, L.row, s); }); };
+    for (int k = nsteps - 1; k >= 0; --k) {
+        float2* W = const_cast<float2*>(reinterpret_cast<const float2*>(what0)) + (size_t)k * fstride;      // stages 0-3 only read W
+        if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
+                return launch_col_stage<decltype(n)::value>(0, L.Ph, L.G, W, L.A, mean, L.col, 1, nullptr, nullptr, s);
+            }))
+            return rc;
+        for (int S = 1; S <= 3; ++S) {
+            if (int rc = row()) return rc;
+            if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
+                    return launch_col_keep<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, fc, stages + (size_t)(S - 1) * fstride, s);
+                }))
+                return rc;
+        }
+        for (int S = 4; S >= 0; --S) {
+            if (S < 4)
+                if (int rc = row_adj()) return rc;
+            ad.state = S >= 2 ? stages + (size_t)(S - 2) * fstride : W;
+            ad.ginit = k == nsteps - 1;
+            if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_adj<decltype(n)::value>(S, L.Ph, L.G, mean, L.col, ad, s); }))
+                return rc;
+        }
+    }
+    return NNS_OK;
 }
 
 NNS_API int nns_spec_ns_scalar_workspace(int batch, int nx, int ny, size_t* bytes) {

@@ -1298,3 +1298,29 @@ class PinnHeadFn(torch.autograd.Function):
                                               _p(up_d), _p(up_p), 2.0 / n_data if n_data else 0.0, c_phys, _p(grad), batch, npix, _stream()),
               'nns_pinn_combine_f32')
         return grad, None, None, None, None, None, None
+
+
+# reverse mode of the periodic solver's forced step (nns_spec_ns_adjoint_workspace, nns_spec_ns_step_adjoint_f32)
+def spec_ns_adjoint_workspace(B, nx, ny):
+    """Bytes of the workspace spec_ns_step_adjoint_ needs for B grids of nx x ny (>= spec_ns_workspace)."""
+    return _query_bytes('nns_spec_ns_adjoint_workspace', int(B), int(nx), int(ny))
+
+
+def spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, work, ny, Lx, Ly, dt, nu, drag):
+    """The vector-Jacobian product of the nsteps forced steps whose start spectra are what0 (float32 [nsteps, B, my1, nx, 2], only read): lam
+    ([B, my1, nx, 2]) holds, in, the cotangent of the state after the last step and, out, that of the state before the first; gbar (the same
+    shape, or None) receives the cotangent of g^, one per grid, summed over the steps.  mean, ghat, dt, nu, drag: the forward's.  Cotangents
+    are spectra of real fields paired by the grid sum.  work: spec_ns_adjoint_workspace bytes.  16 launches per step, no allocation, no host
+    synchronisation."""
+    who = 'spec_ns_step_adjoint_'
+    B, my1, nx = _spec_ns_state(who, lam, mean, work, ny)
+    _f32(what0)
+    if what0.dim() != 5 or tuple(what0.shape[1:]) != tuple(lam.shape) or what0.device != lam.device:
+        raise ValueError("%s: what0 must be float32 [nsteps, %d, %d, %d, 2] on the state's device, got %s" % (who, B, my1, nx, tuple(what0.shape)))
+    gbatch = _spec_ns_force(who, ghat, lam)
+    if gbar is not None:
+        _spec_ns_same(who, gbar, lam)
+    check(_lib.lib().nns_spec_ns_step_adjoint_f32(_p(what0), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(lam),
+                                                  None if gbar is None else _p(gbar), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly),
+                                                  float(dt), float(nu), float(drag), int(what0.shape[0]), _stream()), 'nns_spec_ns_step_adjoint_f32')
+    return lam, gbar

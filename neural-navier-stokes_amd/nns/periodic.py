@@ -23,6 +23,8 @@ transfers by wavenumber shell (tests/pspec_spectrum_oracle.py).  ``set_stochasti
 on chosen shells, generated on the device inside the step (tests/pspec_stochastic_oracle.py).  ``hyperviscosity``, ``hypofriction`` and ``beta``
 generalise the linear operator that the Lawson factor integrates exactly, at no launch, transform or stability limit (tests/pspec_linear_oracle.py;
 measured on the MI355X 1.016x the steady-forced step at 256^2 x 64 and 1.003x at 1024^2 x 8, profiles/pspec_linear_run.json).
+``advance`` / ``advance_velocity`` make the forced, damped flow differentiable: an autograd node whose backward is the adjoint of the step as
+HIP kernels (tests/pspec_adjoint_oracle.py; measured 2.57x a forward step at 256^2 x 64 and 2.72x at 1024^2 x 8, profiles/pspec_adjoint_run.json).
 """
 import collections
 import math
@@ -171,6 +173,65 @@ class PeriodicState(object):
         c = PeriodicState(self.what.clone(), self.mean.clone(), torch.empty_like(self.work), copy(self.that), copy(self.clock), copy(self.noise_ids))
         c.steps = self.steps
         return c
+
+
+class _AdvanceFn(torch.autograd.Function):
+    """``PeriodicSolver.advance`` / ``advance_velocity`` as one autograd node: forward the solver's own step on a fresh state, with the spectrum at
+    the start of every step kept (one device copy between one-step calls: the step itself is untouched); backward the adjoint call
+    (ops.spec_ns_step_adjoint_) between the compact and expand kernels.  ``velocity``: the ends are init / fields instead of the vorticity's."""
+
+    @staticmethod
+    def forward(ctx, solver, nsteps, mean, velocity, forcing, *fields):
+        s = solver
+        if velocity:
+            state = s.init(fields[0].detach(), fields[1].detach())
+        else:
+            state = s.init_vorticity(fields[0].detach(), mean)
+        ghat = s._force_of(state) if forcing is None else s._source_spectrum(forcing.detach(), state)
+        what0 = torch.empty((nsteps,) + tuple(state.what.shape), dtype=torch.float32, device=state.what.device)
+        for k in range(nsteps):
+            what0[k].copy_(state.what)
+            if ghat is not None or s.drag > 0:
+                ops.spec_ns_step_forced_(state.what, state.mean, ghat, state.work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag, 1)
+            else:
+                ops.spec_ns_step_(state.what, state.mean, state.work, s.ny, s.Lx, s.Ly, s.dt, s.nu, 1)
+        ctx.solver, ctx.velocity, ctx.squeeze = s, velocity, fields[0].dim() == 2
+        ctx.shared = forcing is not None and forcing.shape[0] == 1 and state.batch > 1
+        ctx.force_shape = None if forcing is None else tuple(forcing.shape)
+        ctx.save_for_backward(what0, state.mean, *(() if ghat is None else (ghat,)))
+        out = s.fields(state)[:2] if velocity else (s.vorticity(state),)
+        return tuple(o[0] for o in out) if ctx.squeeze else tuple(out)
+
+    @staticmethod
+    def backward(ctx, *gout):
+        s = ctx.solver
+        what0, mean = ctx.saved_tensors[:2]
+        ghat = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        B, dev = what0.shape[1], what0.device
+        shape = (B, s.nx, s.ny)
+        gout = [torch.zeros(shape, dtype=torch.float32, device=dev) if g is None else g.reshape(shape).contiguous() for g in gout]
+        zero = torch.zeros((B, 2), dtype=torch.float32, device=dev)
+        if ctx.velocity:                                  # K^T (ubar, vbar)^ = curl(ubar, vbar)^ / |k|^2
+            lam = s.init(gout[0], gout[1]).what * s._k2_table(dev, -1)
+        else:
+            lam = s.init_vorticity(gout[0]).what
+        need_g = ctx.force_shape is not None and ctx.needs_input_grad[4]
+        gbar = torch.empty_like(lam) if need_g else None
+        work = torch.empty(ops.spec_ns_adjoint_workspace(B, s.nx, s.ny), dtype=torch.uint8, device=dev)
+        ops.spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag)
+        if ctx.velocity:                                  # init^T (lam) = (lam_y, -lam_x): the velocity of the streamfunction lam
+            grads = s.fields(PeriodicState(lam * s._k2_table(dev, 1), zero, work))[:2]
+        else:
+            grads = (s.vorticity(PeriodicState(lam, zero, work)),)
+        if ctx.squeeze:
+            grads = tuple(g[0] for g in grads)
+        gf = None
+        if need_g:
+            gf = s.vorticity(PeriodicState(gbar, zero, work))
+            if ctx.shared:
+                gf = torch.sum(gf, dim=0, keepdim=True)
+            gf = gf.reshape(ctx.force_shape)
+        return (None, None, None, None, gf) + tuple(grads)
 
 
 class PeriodicSolver(object):
@@ -552,6 +613,97 @@ class PeriodicSolver(object):
         self._launch_steps(state, nsteps)
         state.steps += nsteps
         return state
+
+    # ---- reverse mode
+    def _refuse_unsupported(self, who):
+        """The adjoint covers the forced, damped flow; name the argument that puts a solver outside it."""
+        for name, on in (('buoyancy', self.buoyancy != (0.0, 0.0)), ('kappa', self.kappa is not None),
+                         ('set_stochastic_forcing', self.stoch_amp is not None), ('hyperviscosity', self.hyperviscosity[0] > 0),
+                         ('hypofriction', self.hypofriction[0] > 0), ('beta', self.beta != 0.0)):
+            if on:
+                raise NotImplementedError("%s: no reverse mode yet for a solver with %s" % (who, name))
+
+    def _grad_field(self, name, a):
+        """A float32 device tensor [B, nx, ny] (or [nx, ny]) that autograd can follow: no copy from the host or another dtype."""
+        if not isinstance(a, torch.Tensor):
+            raise TypeError("%s: a torch tensor expected, got %s" % (name, type(a).__name__))
+        if not a.is_cuda:
+            raise TypeError("%s: a CUDA/HIP tensor expected (the HIP path has no CPU fallback)" % name)
+        self._field(name, a)
+        return a
+
+    def _k2_table(self, dev, sign):
+        """|k|^2 (sign 1) or 1 / |k|^2 (sign -1; 0 at (0, 0)) of the stored modes, float32 [my1, nx, 1] on dev, from float64 on the host."""
+        def make():
+            k2 = self._shell_table()[2]
+            return (k2 if sign > 0 else np.where(k2 > 0, 1.0 / np.where(k2 > 0, k2, 1.0), 0.0)).astype(np.float32)[:, :, None]
+        return self._on_device('k2' if sign > 0 else 'ik2', dev, make)
+
+    def _source_spectrum(self, g, state):
+        """g^ in the layout of what for the vorticity source g(x) [1 or B, nx, ny] of ``advance``: its band-limited, zero-mean part."""
+        if g.shape[0] not in (1, state.batch) or g.device != state.what.device:
+            raise ValueError("forcing: [1 or %d, %d, %d] on the state's device expected, got %s on %s"
+                             % (state.batch, self.nx, self.ny, tuple(g.shape), g.device))
+        return self.init_vorticity(g).what
+
+    def init_vorticity(self, w, mean=None):
+        """State of the vorticity field w ([B, nx, ny] or [nx, ny], float32) and the mean velocity ``mean`` ([B, 2] or a pair; None: at rest):
+        keeps the band-limited part of w and zeroes its (0, 0) mode (a periodic velocity has a zero-mean vorticity)."""
+        w = self._field('w', w)
+        from ._util import default_device
+        w = w.to(w.device if w.is_cuda else default_device()).contiguous()
+        B, dev = w.shape[0], w.device
+        what = torch.empty((B, self.my1, self.nx, 2), dtype=torch.float32, device=dev)
+        work = torch.empty(ops.spec_ns_scalar_workspace(B, self.nx, self.ny), dtype=torch.uint8, device=dev)
+        ops.spec_ns_scalar_init(w, what, work)
+        what[:, 0, 0, :] = 0.0
+        if mean is None:
+            mean = torch.zeros((B, 2), dtype=torch.float32, device=dev)
+        else:
+            mean = torch.as_tensor(mean, dtype=torch.float32).to(dev).reshape(-1, 2).expand(B, 2).contiguous()
+        return PeriodicState(what, mean, work)
+
+    def vorticity(self, state, out=None):
+        """w float32 [B, nx, ny] of the state (into ``out`` if given)."""
+        self._state(state)
+        need = ops.spec_ns_scalar_workspace(state.batch, self.nx, self.ny)
+        work = state.work if state.work.numel() >= need else torch.empty(need, dtype=torch.uint8, device=state.what.device)
+        return ops.spec_ns_scalar_field(state.what, work, self.ny, out)
+
+    def advance(self, w, nsteps=1, mean=None, forcing=None):
+        """The vorticity field after ``nsteps`` steps from the vorticity field w (float32 device tensor [B, nx, ny] or [nx, ny]), differentiable:
+        an autograd node whose backward is the adjoint of the Lawson RK4 step as HIP kernels (csrc/pspec_kernels.hip: ps_row_adj_kernel,
+        ps_col_adj_kernel; derivation in DESIGN.md section 4.2), so a closure, a learned forcing or an initial condition can be trained THROUGH
+        the solver.  ``forcing``: a vorticity source g(x), float32 device tensor [B or 1, nx, ny], constant over the call, differentiable too
+        (for a shared one the per-grid gradients are summed, one deterministic torch.sum); None: the force of ``set_forcing``, a constant.
+        ``mean``: the mean velocity ([B, 2] or a pair; None: at rest), a constant of the motion that is not differentiated.  The forward is
+        bitwise ``vorticity(step(init_vorticity(w, mean), nsteps))``.  Memory kept for the backward: the spectrum at the start of every step,
+        nsteps x B x my1 x nx x 8 bytes (my1 = (ny - 1) // 3 + 1: a third of a field per step and grid); the stages inside a step are recomputed.
+        Not yet for a solver with kappa, buoyancy, a stochastic force, hyperviscosity, hypofriction or beta: NotImplementedError."""
+        self._refuse_unsupported('advance')
+        nsteps = _count('nsteps', nsteps, 1)
+        w = self._grad_field('w', w)
+        if forcing is not None:
+            forcing = self._grad_field('forcing', forcing)
+            if forcing.dim() == 2:
+                forcing = forcing.unsqueeze(0)
+        return _AdvanceFn.apply(self, nsteps, mean, False, forcing, w)[0]
+
+    def advance_velocity(self, u0, v0, nsteps=1, forcing=None):
+        """(u, v) after ``nsteps`` steps from the velocity (u0, v0), differentiable like ``advance`` (and in ``forcing``, a vorticity source as
+        there): ``fields(step(init(u0, v0), nsteps))[:2]`` forward; backward through the velocity by K^T (ubar, vbar)^ = curl(ubar, vbar)^ / |k|^2,
+        the step's adjoint, and init^T (lam) = (lam_y, -lam_x), built from the init / fields kernels and one |k|^-2, |k|^2 table multiply each.
+        The grid means (U0, V0) of (u0, v0) are constants of the motion and are not differentiated.  No pressure output."""
+        self._refuse_unsupported('advance_velocity')
+        nsteps = _count('nsteps', nsteps, 1)
+        u0, v0 = self._grad_field('u0', u0), self._grad_field('v0', v0)
+        if u0.shape != v0.shape:
+            raise ValueError("u0 and v0 must share their shape")
+        if forcing is not None:
+            forcing = self._grad_field('forcing', forcing)
+            if forcing.dim() == 2:
+                forcing = forcing.unsqueeze(0)
+        return _AdvanceFn.apply(self, nsteps, None, True, forcing, u0, v0)
 
     def diagnostics(self, state):
         """Diagnostics(energy, enstrophy, power_in), each float64 [B], computed on the device from the state's spectrum:
