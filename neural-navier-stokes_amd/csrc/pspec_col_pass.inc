@@ -5,6 +5,8 @@
 // STOCH (ps_col_kernel's note) is false in every kernel without a PsStoch argument, whose text below is then what it was.
 // LINEAR likewise (a PsLinear argument): the vorticity's factors E - 1, E^2 - 1 are then complex, from the table lin, and scal's complex form applies.
 // STAGES likewise (a PsKeep argument): stages 1-3 also store the next stage's input to stage_out.
+// The staged forward transform and the field emit are text of their own (pspec_stage.inc, pspec_field.inc), shared with ps_col_adj_kernel and
+// ps_transfer_kernel; the tile's names (lok, lj, wbase, sok, ...) are those of pspec_col_tile.inc.
 {
         const float2* ph = TH ? Ph + a.fstride : Ph;
         float2* Ws = TH ? Th : W;
@@ -17,17 +19,8 @@
                 y[m] = {w.x, w.y};
             }
         } else {
-            for (int r = cr; r < N; r += RPI) {
-                const float2 v = sok ? ph[sbase + (size_t)r * my1] : make_float2(0.f, 0.f);
-                cp[2 * r] = v.x; cp[2 * r + 1] = v.y;
-            }
-            __syncthreads();
             cf z[16];
-#pragma unroll
-            for (int m = 0; m < 16; ++m) z[m] = {mine[2 * (tv + TPF * m)], mine[2 * (tv + TPF * m) + 1]};
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            fft_line<float, N, false>(z, tab, tab + N / 2, xb, tv);
+#include "pspec_stage.inc"
             int te = tv;
             asm volatile("" : "+v"(te), "+v"(z[0].x));
 #pragma unroll
@@ -98,33 +91,7 @@
                 constexpr int F = decltype(fc)::value;
                 int te = tv;
                 asm volatile("" : "+v"(te), "+v"(y[0].x));
-                cf o[16];
-#pragma unroll
-                for (int m = 0; m < 16; ++m) {
-                    const int e = te + TPF * m;
-                    const int mx = m < 8 ? e : e - N;
-                    const float kx = a.kx1 * (float)mx;
-                    const float k2 = kx * kx + ky * ky;
-                    const float ik2 = k2 > 0.f ? a.inv_n / k2 : 0.f;
-                    if constexpr (F == 0) o[m] = imul(ky * ik2, y[m]);                 // u^ = i ky psi^
-                    else if constexpr (F == 1) o[m] = imul(-kx * ik2, y[m]);           // v^ = -i kx psi^
-                    else if constexpr (F == 2 || F == 4) o[m] = imul(kx * a.inv_n, y[m]);   // (w_x)^, (theta_x)^
-                    else o[m] = imul(ky * a.inv_n, y[m]);                              // (w_y)^, (theta_y)^
-                }
-                if constexpr (F < 2) {
-                    if (te == 0 && lj == 0) o[0] = {F == 0 ? U0 : V0, 0.f};           // the mean flow in the (0, 0) mode
-                }
-                fft_line<float, N, true>(o, tab, tab + N / 2, xb, tv);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int m = 0; m < 16; ++m) { mine[2 * (tv + TPF * m)] = o[m].x; mine[2 * (tv + TPF * m) + 1] = o[m].y; }
-                __syncthreads();
-                if (sok) {
-                    float2* g = G + (size_t)F * a.fstride + sbase;
-                    for (int r = cr; r < N; r += RPI) g[(size_t)r * my1] = make_float2(cp[2 * r], cp[2 * r + 1]);
-                }
-                __syncthreads();
+#include "pspec_field.inc"
             };
             if constexpr (TH) static_for<4, 6>(field);
             else static_for<0, 4>(field);

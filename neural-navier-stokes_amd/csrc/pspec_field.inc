@@ -1,0 +1,30 @@
+// The body of a column kernel's `field` lambda after its pin of te: field F of the spectrum y inverse-transformed along x and written to G through
+// the LDS transpose.  Text of ps_col_kernel (through pspec_col_pass.inc; F = 4, 5: the scalar's gradient) and ps_col_adj_kernel (F = 4, 5: kappa's).
+// In scope: the names of pspec_col_tile.inc, F, y, te, tv, ky, U0, V0, a, tab, G, my1, TPF, RPI.
+                cf o[16];
+#pragma unroll
+                for (int m = 0; m < 16; ++m) {
+                    const int e = te + TPF * m;
+                    const int mx = m < 8 ? e : e - N;
+                    const float kx = a.kx1 * (float)mx;
+                    const float k2 = kx * kx + ky * ky;
+                    const float ik2 = k2 > 0.f ? a.inv_n / k2 : 0.f;
+                    if constexpr (F == 0) o[m] = imul(ky * ik2, y[m]);                 // u^ = i ky psi^
+                    else if constexpr (F == 1) o[m] = imul(-kx * ik2, y[m]);           // v^ = -i kx psi^
+                    else if constexpr (F == 2 || F == 4) o[m] = imul(kx * a.inv_n, y[m]);   // (w_x)^, (theta_x)^
+                    else o[m] = imul(ky * a.inv_n, y[m]);                              // (w_y)^, (theta_y)^
+                }
+                if constexpr (F < 2) {
+                    if (te == 0 && lj == 0) o[0] = {F == 0 ? U0 : V0, 0.f};           // the mean flow in the (0, 0) mode
+                }
+                fft_line<float, N, true>(o, tab, tab + N / 2, xb, tv);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int m = 0; m < 16; ++m) { mine[2 * (tv + TPF * m)] = o[m].x; mine[2 * (tv + TPF * m) + 1] = o[m].y; }
+                __syncthreads();
+                if (sok) {
+                    float2* g = G + (size_t)F * a.fstride + sbase;
+                    for (int r = cr; r < N; r += RPI) g[(size_t)r * my1] = make_float2(cp[2 * r], cp[2 * r + 1]);
+                }
+                __syncthreads();

@@ -65,29 +65,19 @@
 // hold 99 ... 184 VGPRs, no scratch.
 //
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
-#include "nns_common.h"
-#include "fft_lds.h"
+//
+// What the row and column kernels share has one copy each: the LDS layout, PsArgs and the row pass's Hermitian fill and kept-mode store in
+// pspec_device.h; the line and tile geometry, the staged forward transform and the field emit as text included at each site
+// (pspec_row_line.inc, pspec_col_tile.inc, pspec_stage.inc, pspec_field.inc), the way pspec_col_pass.inc serves the vorticity and the scalar:
+// a function, a lambda or a type in their place compiles the column kernels to other registers, and their code is pinned
+// (tools/isa_listing.py).  The mode predicate (mx, keep, kx, k2) stays spelt out where it is used, for the same reason.
+#include "pspec_device.h"
 #include <type_traits>
 #include <cmath>
 
-using namespace nns;
-
 namespace {
 
-constexpr int kT = 256;                    // threads per workgroup (4 waves): more workgroups for the B my1 column lines
-constexpr int kW = kT / kWave;
 constexpr long kGridCap = 2048;
-
-template <int N>
-struct PsLds {
-    static constexpr int TPF = N / 16, FPW = kWave / TPF, LINES = kW * FPW;
-    static constexpr int XB_BYTES = (N + N / 16) * 8;                             // exchange image
-    static constexpr int STAGE_BYTES = (N + 16) * 8 + 128;                        // one staged complex line + skew
-    static constexpr int LINE_BYTES = ((XB_BYTES > STAGE_BYTES ? XB_BYTES : STAGE_BYTES) + 127) / 128 * 128;
-    static constexpr int TAB_BYTES = (N / 2 + Pass2<N>::ENTRIES) * 8;
-    static constexpr int TOTAL = TAB_BYTES + LINES * LINE_BYTES;
-    static constexpr int SKEW_MOD = LINES < 32 ? LINES : 32, SKEW_DW = 32 / SKEW_MOD;
-};
 
 struct PsForce {          // the extra argument of the FORCED column kernels
     const float2* g;      // g^ [gbatch][my1][nx] in the state's layout, or NULL (drag only)
@@ -132,21 +122,6 @@ template <typename U, typename T, typename... R> __device__ __forceinline__ U pi
     else return pick<U>(r...);
 }
 
-struct PsArgs {
-    long nlines;          // row kernel: B nx rows; column kernel: B my1 columns
-    long fstride;         // complex elements between the fields of G and of Ph (= B nx my1)
-    int my1;              // kept y-wavenumbers
-    float kx1, ky1;       // 2 pi / Lx, 2 pi / Ly
-    float hnudt;          // -nu dt / 2
-    float dt;
-    float inv_n;          // 1 / (nx ny)
-};
-
-using cf = C2<float>;
-__device__ __forceinline__ cf scal(float em, cf z) { return {fmaf(em, z.x, z.x), fmaf(em, z.y, z.y)}; }     // (1 + em) z
-__device__ __forceinline__ cf axpy(float a, cf x, cf y) { return {fmaf(a, x.x, y.x), fmaf(a, x.y, y.y)}; }   // a x + y
-__device__ __forceinline__ cf imul(float a, cf z) { return {-a * z.y, a * z.x}; }                            // i a z
-
 __device__ __forceinline__ cf scal(cf em, cf z) {                                                            // (1 + em) z, em complex
     return {fmaf(-em.y, z.y, fmaf(em.x, z.x, z.x)), fmaf(em.y, z.x, fmaf(em.x, z.y, z.y))};
 }
@@ -184,15 +159,6 @@ __device__ __forceinline__ cf ps_normal(unsigned c0, unsigned c1, unsigned c2, u
     return {rad * cs, rad * sn};
 }
 
-template <int N>
-__device__ __forceinline__ cf* ps_tables(unsigned char* smem) {
-    cf* tab = reinterpret_cast<cf*>(smem);
-    fill_twiddles<float, N>(tab, threadIdx.x, kT);
-    fill_twiddles2<float, N>(tab + N / 2, threadIdx.x, kT);
-    __syncthreads();
-    return tab;
-}
-
 // ---------------------------------------------------------------------------------------------------- row pass (axis y)
 // SCALAR: a third inverse transform (theta_x + i theta_y, G fields 4 and 5) after the vorticity's product has left, so two complex lines
 // are live at a time, as without it; the second product goes to Ph's second field.
@@ -209,56 +175,19 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
     const int my1 = a.my1;
     const long niter = (a.nlines + L::LINES - 1) / L::LINES;
     for (long it = blockIdx.x; it < niter; it += gridDim.x) {
-        int tx = threadIdx.x;
-        asm volatile("" : "+v"(tx));
-        const int wave = tx / kWave, lane = tx % kWave, sub = lane / TPF, tid = lane % TPF;
-        const int line = wave * L::FPW + sub;
-        cf* xb = reinterpret_cast<cf*>(lines + (size_t)line * L::LINE_BYTES);
-        const long row_raw = it * L::LINES + line;
-        const bool valid = row_raw < a.nlines;
-        const long row = valid ? row_raw : a.nlines - 1;
-        const float2* g0 = G + (size_t)row * my1;
-        // Hermitian fill of two half spectra A, B into Z = A + i B (ifft(Z) = irfft(A) + i irfft(B)); j = 0 takes the real parts
-        auto load2 = [&](const float2* ga, const float2* gb, cf (&z)[16]) {
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                const int e = tid + TPF * m;
-                z[m] = {0.f, 0.f};
-                if (m < 8) {
-                    if (e < my1) {
-                        const float2 p = ga[e], q = gb[e];
-                        z[m] = e == 0 ? cf{p.x, q.x} : cf{p.x - q.y, p.y + q.x};
-                    }
-                } else {
-                    const int r = N - e;
-                    if (r < my1) {
-                        const float2 p = ga[r], q = gb[r];
-                        z[m] = {p.x + q.y, q.x - p.y};
-                    }
-                }
-            }
-        };
+#include "pspec_row_line.inc"
         cf zu[16], zw[16];
-        load2(g0, g0 + a.fstride, zu);                       // u + i v
+        ps_row_load2<N>(g0, g0 + a.fstride, tid, my1, zu);                       // u + i v
         fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
         __builtin_amdgcn_sched_barrier(0);
-        load2(g0 + 2 * a.fstride, g0 + 3 * a.fstride, zw);   // w_x + i w_y
+        ps_row_load2<N>(g0 + 2 * a.fstride, g0 + 3 * a.fstride, tid, my1, zw);   // w_x + i w_y
         fft_line<float, N, true>(zw, tab, tab + N / 2, xb, tid);
-        auto store = [&](const cf (&z)[16], float2* o) {
-            if (valid) {
-#pragma unroll
-                for (int m = 0; m < 8; ++m) {
-                    const int e = tid + TPF * m;
-                    if (e < my1) o[e] = make_float2(z[m].x, z[m].y);
-                }
-            }
-        };
         if constexpr (!SCALAR) {
 #pragma unroll
             for (int m = 0; m < 16; ++m) zu[m] = {zu[m].x * zw[m].x + zu[m].y * zw[m].y, 0.f};    // u w_x + v w_y
             __builtin_amdgcn_sched_barrier(0);
             fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
-            store(zu, Ph + (size_t)row * my1);
+            ps_row_store<N>(zu, Ph + (size_t)row * my1, tid, my1, valid);
         } else {
             const auto gr = pick<Grad...>(grad...);
 #pragma unroll
@@ -277,15 +206,15 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
                     }
                 }
             }
-            store(zw, Ph + (size_t)row * my1);
+            ps_row_store<N>(zw, Ph + (size_t)row * my1, tid, my1, valid);
             __builtin_amdgcn_sched_barrier(0);
-            load2(g0 + 4 * a.fstride, g0 + 5 * a.fstride, zw);   // theta_x + i theta_y
+            ps_row_load2<N>(g0 + 4 * a.fstride, g0 + 5 * a.fstride, tid, my1, zw);   // theta_x + i theta_y
             fft_line<float, N, true>(zw, tab, tab + N / 2, xb, tid);
 #pragma unroll
             for (int m = 0; m < 16; ++m) zw[m] = {zu[m].x * (zw[m].x + gr.gx) + zu[m].y * (zw[m].y + gr.gy), 0.f};   // u (theta_x + Gx) + v (theta_y + Gy)
             __builtin_amdgcn_sched_barrier(0);
             fft_line<float, N, false>(zw, tab, tab + N / 2, xb, tid);
-            store(zw, Ph + a.fstride + (size_t)row * my1);
+            ps_row_store<N>(zw, Ph + a.fstride + (size_t)row * my1, tid, my1, valid);
         }
     }
 }
@@ -349,21 +278,7 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
         int tx = threadIdx.x;
         asm volatile("" : "+v"(tx));
-        const int wave = tx / kWave, lane = tx % kWave, sub = lane / TPF, tid = lane % TPF;
-        const int line = wave * L::FPW + sub;
-        cf* xb = reinterpret_cast<cf*>(lines + (size_t)line * L::LINE_BYTES);
-        float* mine = reinterpret_cast<float*>(xb) + (line % L::SKEW_MOD) * L::SKEW_DW;
-        // staging role: thread (cc, cr) moves rows cr, cr + RPI, ... of tile column cc
-        const int cc = tx % CW, cr = tx / CW;
-        float* cp = reinterpret_cast<float*>(lines + (size_t)cc * L::LINE_BYTES) + (cc % L::SKEW_MOD) * L::SKEW_DW;
-        const long scol = t * CW + cc;
-        const bool sok = scol < a.nlines;
-        const size_t sbase = sok ? (size_t)(scol / my1) * N * my1 + (size_t)(scol % my1) : 0;     // (b, i = 0, j) in [b][i][j]
-        // transform role: this line is column lcol = (b, j)
-        const long lcol = t * CW + line;
-        const bool lok = lcol < a.nlines;
-        const int lb = lok ? (int)(lcol / my1) : 0, lj = lok ? (int)(lcol % my1) : 0;
-        const size_t wbase = (size_t)(lok ? lcol : 0) * N;
+#include "pspec_col_tile.inc"
         [[maybe_unused]] size_t gbase = 0;
         [[maybe_unused]] bool gok = false;
         if constexpr (FORCED) {
@@ -375,7 +290,7 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
         int tv = tid;
         asm volatile("" : "+v"(tv));
         const float ky = a.ky1 * (float)lj;
-        // one field through the tile, as plain text per field (see the note in the file): first the vorticity, then the scalar
+        // one field through the tile, as plain text per field (the note in pspec_col_pass.inc): first the vorticity, then the scalar
         {
             constexpr bool TH = false;
 #include "pspec_col_pass.inc"
@@ -404,66 +319,30 @@ __global__ __launch_bounds__(kT) void ps_row_adj_kernel(const float2* __restrict
     const int my1 = a.my1;
     const long niter = (a.nlines + L::LINES - 1) / L::LINES;
     for (long it = blockIdx.x; it < niter; it += gridDim.x) {
-        int tx = threadIdx.x;
-        asm volatile("" : "+v"(tx));
-        const int wave = tx / kWave, lane = tx % kWave, sub = lane / TPF, tid = lane % TPF;
-        const int line = wave * L::FPW + sub;
-        cf* xb = reinterpret_cast<cf*>(lines + (size_t)line * L::LINE_BYTES);
-        const long row_raw = it * L::LINES + line;
-        const bool valid = row_raw < a.nlines;
-        const long row = valid ? row_raw : a.nlines - 1;
-        const float2* g0 = G + (size_t)row * my1;
-        auto load2 = [&](const float2* ga, const float2* gb, cf (&z)[16]) {          // ps_row_kernel's Hermitian fill
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                const int e = tid + TPF * m;
-                z[m] = {0.f, 0.f};
-                if (m < 8) {
-                    if (e < my1) {
-                        const float2 p = ga[e], q = gb[e];
-                        z[m] = e == 0 ? cf{p.x, q.x} : cf{p.x - q.y, p.y + q.x};
-                    }
-                } else {
-                    const int r = N - e;
-                    if (r < my1) {
-                        const float2 p = ga[r], q = gb[r];
-                        z[m] = {p.x + q.y, q.x - p.y};
-                    }
-                }
-            }
-        };
-        auto store = [&](const cf (&z)[16], float2* o) {
-            if (valid) {
-#pragma unroll
-                for (int m = 0; m < 8; ++m) {
-                    const int e = tid + TPF * m;
-                    if (e < my1) o[e] = make_float2(z[m].x, z[m].y);
-                }
-            }
-        };
+#include "pspec_row_line.inc"
         cf zu[16], zk[16];
-        load2(g0, g0 + a.fstride, zu);                           // u + i v
+        ps_row_load2<N>(g0, g0 + a.fstride, tid, my1, zu);                           // u + i v
         fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
         __builtin_amdgcn_sched_barrier(0);
-        load2(g0 + 4 * a.fstride, g0 + 5 * a.fstride, zk);       // kappa_x + i kappa_y: stays
+        ps_row_load2<N>(g0 + 4 * a.fstride, g0 + 5 * a.fstride, tid, my1, zk);       // kappa_x + i kappa_y: stays
         fft_line<float, N, true>(zk, tab, tab + N / 2, xb, tid);
 #pragma unroll
         for (int m = 0; m < 16; ++m) zu[m] = {zu[m].x * zk[m].x + zu[m].y * zk[m].y, 0.f};        // u kappa_x + v kappa_y
         __builtin_amdgcn_sched_barrier(0);
         fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
-        store(zu, Ph + (size_t)row * my1);
+        ps_row_store<N>(zu, Ph + (size_t)row * my1, tid, my1, valid);
         __builtin_amdgcn_sched_barrier(0);
-        load2(g0 + 2 * a.fstride, g0 + 3 * a.fstride, zu);       // w_x + i w_y
+        ps_row_load2<N>(g0 + 2 * a.fstride, g0 + 3 * a.fstride, tid, my1, zu);       // w_x + i w_y
         fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
 #pragma unroll
         for (int m = 0; m < 16; ++m) zu[m] = {zk[m].x * zu[m].y - zk[m].y * zu[m].x, 0.f};        // kappa_x w_y - kappa_y w_x
         __builtin_amdgcn_sched_barrier(0);
         fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
-        store(zu, Ph + a.fstride + (size_t)row * my1);
+        ps_row_store<N>(zu, Ph + a.fstride + (size_t)row * my1, tid, my1, valid);
     }
 }
 
-// The adjoint column pass, S = 4 .. 0 in the order it runs (tiling and LDS staging of ps_col_kernel).  With lam the cotangent of the step's
+// The adjoint column pass, S = 4 .. 0 in the order it runs (ps_col_kernel's tile: pspec_col_tile.inc, pspec_stage.inc).  With lam the cotangent of the step's
 // result, r = N'(s)^T kappa of the stage just evaluated by the row pass (S < 4: Ph fields 0 and 1 staged and forward-transformed along x,
 // r = keep ? Q1 - Q2 / |k|^2 : 0) and E - 1, E^2 - 1 in the forward's expm1 form:
 //     S = 4                                    kappa4 = dt/6 lam                      prepares s3
@@ -472,7 +351,7 @@ __global__ __launch_bounds__(kT) void ps_row_adj_kernel(const float2* __restrict
 //     S = 1   wbar += E r                      kappa1 = dt/6 E^2 lam + dt/2 E r       prepares s0
 //     S = 0   lam   = wbar + r                 (the cotangent of the step's input, the lam of the step before)
 // gbar += kappa in every stage that makes one.  lam, wbar and gbar are lane-owned and coalesced, like W / A.  Preparing: the four spectra of
-// the state (ad.state, the forward's field<0..3> arithmetic, the mean in the (0, 0) mode) inverse-transformed along x to G fields 0-3, and
+// the state (ad.state, the forward's field<0..3>: pspec_field.inc, the mean in the (0, 0) mode) inverse-transformed along x to G fields 0-3, and
 // i kx kappa^, i ky kappa^ to G fields 4 and 5 (these first: kappa's registers are free before the state is loaded).
 template <int N, int S>
 __global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, const float* __restrict__ mean,
@@ -489,34 +368,13 @@ __global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict
     for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
         int tx = threadIdx.x;
         asm volatile("" : "+v"(tx));
-        const int wave = tx / kWave, lane = tx % kWave, sub = lane / TPF, tid = lane % TPF;
-        const int line = wave * L::FPW + sub;
-        cf* xb = reinterpret_cast<cf*>(lines + (size_t)line * L::LINE_BYTES);
-        float* mine = reinterpret_cast<float*>(xb) + (line % L::SKEW_MOD) * L::SKEW_DW;
-        const int cc = tx % CW, cr = tx / CW;
-        float* cp = reinterpret_cast<float*>(lines + (size_t)cc * L::LINE_BYTES) + (cc % L::SKEW_MOD) * L::SKEW_DW;
-        const long scol = t * CW + cc;
-        const bool sok = scol < a.nlines;
-        const size_t sbase = sok ? (size_t)(scol / my1) * N * my1 + (size_t)(scol % my1) : 0;     // (b, i = 0, j) in [b][i][j]
-        const long lcol = t * CW + line;
-        const bool lok = lcol < a.nlines;
-        const int lb = lok ? (int)(lcol / my1) : 0, lj = lok ? (int)(lcol % my1) : 0;
-        const size_t wbase = (size_t)(lok ? lcol : 0) * N;
+#include "pspec_col_tile.inc"
         int tv = tid;
         asm volatile("" : "+v"(tv));
         const float ky = a.ky1 * (float)lj;
         // Ph's field `ph` of the tile through the LDS transpose, forward-transformed along x
         auto consume = [&](const float2* ph, cf (&z)[16]) {
-            for (int r = cr; r < N; r += RPI) {
-                const float2 v = sok ? ph[sbase + (size_t)r * my1] : make_float2(0.f, 0.f);
-                cp[2 * r] = v.x; cp[2 * r + 1] = v.y;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int m = 0; m < 16; ++m) z[m] = {mine[2 * (tv + TPF * m)], mine[2 * (tv + TPF * m) + 1]};
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            fft_line<float, N, false>(z, tab, tab + N / 2, xb, tv);
+#include "pspec_stage.inc"
         };
         [[maybe_unused]] cf kap[16];
         if constexpr (S < 4) {
@@ -589,38 +447,12 @@ __global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict
         }
         if constexpr (S >= 1) {
             const float U0 = lok ? mean[2 * lb] : 0.f, V0 = lok ? mean[2 * lb + 1] : 0.f;
-            // field F of the spectrum y (ps_col_kernel's): transformed along x and written to G through the LDS transpose
+            // field F of the spectrum y, transformed along x and written to G through the LDS transpose: ps_col_kernel's, without its pin of y
             auto field = [&](auto fc, const cf (&y)[16]) {
                 constexpr int F = decltype(fc)::value;
                 int te = tv;
                 asm volatile("" : "+v"(te));
-                cf o[16];
-#pragma unroll
-                for (int m = 0; m < 16; ++m) {
-                    const int e = te + TPF * m;
-                    const int mx = m < 8 ? e : e - N;
-                    const float kx = a.kx1 * (float)mx;
-                    const float k2 = kx * kx + ky * ky;
-                    const float ik2 = k2 > 0.f ? a.inv_n / k2 : 0.f;
-                    if constexpr (F == 0) o[m] = imul(ky * ik2, y[m]);                 // u^ = i ky psi^
-                    else if constexpr (F == 1) o[m] = imul(-kx * ik2, y[m]);           // v^ = -i kx psi^
-                    else if constexpr (F == 2 || F == 4) o[m] = imul(kx * a.inv_n, y[m]);   // (w_x)^, (kappa_x)^
-                    else o[m] = imul(ky * a.inv_n, y[m]);                              // (w_y)^, (kappa_y)^
-                }
-                if constexpr (F < 2) {
-                    if (te == 0 && lj == 0) o[0] = {F == 0 ? U0 : V0, 0.f};           // the mean flow in the (0, 0) mode
-                }
-                fft_line<float, N, true>(o, tab, tab + N / 2, xb, tv);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int m = 0; m < 16; ++m) { mine[2 * (tv + TPF * m)] = o[m].x; mine[2 * (tv + TPF * m) + 1] = o[m].y; }
-                __syncthreads();
-                if (sok) {
-                    float2* g = G + (size_t)F * a.fstride + sbase;
-                    for (int r = cr; r < N; r += RPI) g[(size_t)r * my1] = make_float2(cp[2 * r], cp[2 * r + 1]);
-                }
-                __syncthreads();
+#include "pspec_field.inc"
             };
             static_for<4, 6>([&](auto fc) { field(fc, kap); });
             cf y[16];
@@ -1009,9 +841,10 @@ __global__ __launch_bounds__(kT) void ps_linear_shell_kernel(const float2* __res
     }
 }
 
-// The column pass of a transfer evaluation: tiling, LDS staging and forward transform of stages S >= 1 of ps_col_kernel; in place of the
-// Lawson update it forms, per stored mode, Re(conj w^ N^) with N^ = -M P^ (the step's mask: `keep` as in pspec_col_pass.inc) and, SCALAR,
-// Re(conj theta^ N_theta^) from Ph's second field, and writes them as float32 modal fields Tw, Tt [B][my1][nx].  It writes neither W nor Th.
+// The column pass of a transfer evaluation: the tile and the staged forward transform of stages S >= 1 of ps_col_kernel (pspec_col_tile.inc
+// without the pins of tx and tv, pspec_stage.inc); in place of the Lawson update it forms, per stored mode, Re(conj w^ N^) with N^ = -M P^
+// (the step's mask: `keep` as in pspec_col_pass.inc) and, SCALAR, Re(conj theta^ N_theta^) from Ph's second field, and writes them as float32
+// modal fields Tw, Tt [B][my1][nx].  It writes neither W nor Th.
 template <int N, bool SCALAR>
 __global__ __launch_bounds__(kT) void ps_transfer_kernel(const float2* __restrict__ Ph, const float2* __restrict__ W, const float2* __restrict__ Th,
                                                          float* __restrict__ Tw, float* __restrict__ Tt, PsArgs a) {
@@ -1024,35 +857,15 @@ __global__ __launch_bounds__(kT) void ps_transfer_kernel(const float2* __restric
     const long ntiles = (a.nlines + CW - 1) / CW;
     for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const int tx = threadIdx.x;
-        const int wave = tx / kWave, lane = tx % kWave, sub = lane / TPF, tv = lane % TPF;
-        const int line = wave * L::FPW + sub;
-        cf* xb = reinterpret_cast<cf*>(lines + (size_t)line * L::LINE_BYTES);
-        const float* mine = reinterpret_cast<const float*>(xb) + (line % L::SKEW_MOD) * L::SKEW_DW;
-        const int cc = tx % CW, cr = tx / CW;
-        float* cp = reinterpret_cast<float*>(lines + (size_t)cc * L::LINE_BYTES) + (cc % L::SKEW_MOD) * L::SKEW_DW;
-        const long scol = t * CW + cc;
-        const bool sok = scol < a.nlines;
-        const size_t sbase = sok ? (size_t)(scol / my1) * N * my1 + (size_t)(scol % my1) : 0;     // (b, i = 0, j) in [b][i][j]
-        const long lcol = t * CW + line;
-        const bool lok = lcol < a.nlines;
-        const int lj = lok ? (int)(lcol % my1) : 0;
-        const size_t wbase = (size_t)(lok ? lcol : 0) * N;
+#include "pspec_col_tile.inc"
+        const int tv = tid;
         static_for<0, SCALAR ? 2 : 1>([&](auto fld) {
             constexpr bool TH = decltype(fld)::value == 1;
             const float2* ph = TH ? Ph + a.fstride : Ph;
             const float2* Ws = TH ? Th : W;
             float* To = TH ? Tt : Tw;
-            for (int r = cr; r < N; r += RPI) {
-                const float2 v = sok ? ph[sbase + (size_t)r * my1] : make_float2(0.f, 0.f);
-                cp[2 * r] = v.x; cp[2 * r + 1] = v.y;
-            }
-            __syncthreads();
             cf z[16];
-#pragma unroll
-            for (int m = 0; m < 16; ++m) z[m] = {mine[2 * (tv + TPF * m)], mine[2 * (tv + TPF * m) + 1]};
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            fft_line<float, N, false>(z, tab, tab + N / 2, xb, tv);
+#include "pspec_stage.inc"
 #pragma unroll
             for (int m = 0; m < 16; ++m) {
                 const int e = tv + TPF * m;
@@ -1103,6 +916,13 @@ int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* m
                                  : "spec_ns column pass");
 }
 
+// f(std::integral_constant<int, S>) of a run-time stage S in [LO, HI]; a stage beyond takes HI
+template <int LO, int HI, typename F>
+int with_stage(int S, F&& f) {
+    if constexpr (LO == HI) return f(std::integral_constant<int, HI>{});
+    else return S == LO ? f(std::integral_constant<int, LO>{}) : with_stage<LO + 1, HI>(S, f);
+}
+
 // The one place where a stage's run-time facts become a kernel.  fc == nullptr: the unforced kernels (stage 0 has no other form); sc: the
 // SCALAR ones; li (with fc): a linear step, whose stages 1-3 are the LINEAR kernels (stage 4 applies no factor); st (with fc): a stochastic
 // step, whose stages 1 and 4 are the STOCH kernels.  The pack grows in the kernel's order, and a form no step has is never named.
@@ -1127,13 +947,7 @@ int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, c
             if (fc) return scalar(std::true_type{});
         return scalar(std::false_type{});
     };
-    switch (S) {
-        case 0: return stage(std::integral_constant<int, 0>{});
-        case 1: return stage(std::integral_constant<int, 1>{});
-        case 2: return stage(std::integral_constant<int, 2>{});
-        case 3: return stage(std::integral_constant<int, 3>{});
-        default: return stage(std::integral_constant<int, 4>{});
-    }
+    return with_stage<0, 4>(S, stage);
 }
 
 // Stage S = 1..3 of the adjoint's recomputation: the plain or the forced kernel with the stage store (launch_col_stage never names this form)
@@ -1145,11 +959,7 @@ int launch_col_keep(int S, const float2* Ph, float2* G, float2* W, float2* A, co
         constexpr int K = decltype(stage_c)::value;
         return fc ? launch_col<N, K, true>(Ph, G, W, A, mean, a, 1, fc, s, ke) : launch_col<N, K, false>(Ph, G, W, A, mean, a, 1, fc, s, ke);
     };
-    switch (S) {
-        case 1: return go(std::integral_constant<int, 1>{});
-        case 2: return go(std::integral_constant<int, 2>{});
-        default: return go(std::integral_constant<int, 3>{});
-    }
+    return with_stage<1, 3>(S, go);
 }
 
 template <int N>
@@ -1168,13 +978,7 @@ int launch_col_adj(int S, const float2* Ph, float2* G, const float* mean, const 
         hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, mean, a, ad);
         return check_launch("spec_ns adjoint column pass");
     };
-    switch (S) {
-        case 0: return go(std::integral_constant<int, 0>{});
-        case 1: return go(std::integral_constant<int, 1>{});
-        case 2: return go(std::integral_constant<int, 2>{});
-        case 3: return go(std::integral_constant<int, 3>{});
-        default: return go(std::integral_constant<int, 4>{});
-    }
+    return with_stage<0, 4>(S, go);
 }
 
 size_t step_bytes(int batch, int nx, int ny) { return (size_t)6 * batch * nx * kept_y(ny) * sizeof(float2); }
