@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void zero_list_kernel(ZeroTable t) {
 }  // namespace
 
 namespace nns {
-// (used by the ODE-MLP backward: csrc/neural_kernels.hip)
+// (used by the ODE-MLP backward: csrc/ode_mlp_kernels.hip)
 int zero_buffers(void* const* bufs, const long* bytes, int count, hipStream_t s) {
     for (int i = 0; i < count;) {
         ZeroTable t{};

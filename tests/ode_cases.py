@@ -1,7 +1,7 @@
 """Cases of the fused ODEFunc integrator (tests/test_gpu_ode_mlp.py runs them on the GPU; tests/test_oracle_neural.py runs every condition
 on the reference alone, without one).
 
-Dispatch (csrc/neural_kernels.hip, nns/neural_spectral/anode.py), restated:
+Dispatch (csrc/ode_mlp_kernels.hip, nns/neural_spectral/anode.py), restated:
   forward   nns_ode_mlp_fwd_f32: mb <= NNS_ODE_ROW_MAX (environment, read once per process, default 4096) -> ode_mlp_fwd_row_kernel, one batch
             row per workgroup, weights in registers; otherwise ode_mlp_fwd_kernel, 16-row MFMA tiles.  NNS_ODE_ROW_MAX=0 forces the tile kernel.
   backward  _OdeMlpFn.backward: Nt > 1 and mb * Nt * K <= anode._parallel_rows (2 * cu_count * 16 unless set) -> TIME-PARALLEL: the step

@@ -1,4 +1,4 @@
-"""The fused ODEFunc integrator (csrc/neural_kernels.hip) pinned on each of its paths, at the cases, the bound and the exact read-outs of
+"""The fused ODEFunc integrator (csrc/ode_mlp_kernels.hip) pinned on each of its paths, at the cases, the bound and the exact read-outs of
 tests/ode_cases.py (its docstring has the dispatch rules, the reasoning behind the bound and the figures measured on an MI355X):
 
   * row forward (ops.ode_mlp_fwd) and tile forward (the same call in ONE child process with NNS_ODE_ROW_MAX=0) against the oracle trajectory;
