@@ -578,6 +578,25 @@ int nns_spec_ns_adjoint_workspace(int batch, int nx, int ny, size_t* bytes);
 int nns_spec_ns_step_adjoint_f32(const float* what0, const float* mean, const float* ghat, int gbatch, float* lam, float* gbar, void* work,
                                  size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
                                  int nsteps, void* stream);
+/* Reverse mode of nns_spec_ns_step_scalar_f32 and nns_spec_ns_step_buoyant_f32 (restatement: tests/pspec_scalar_adjoint_oracle.py): the
+ * vector-Jacobian product of nsteps steps of the system (w^, theta^), the scalar riding in the launches of nns_spec_ns_step_adjoint_f32.  With
+ * (kappa, m) the cotangents of a stage's (N_w, N_theta) and u, v, w, theta of that stage's state,
+ *   r_w     = M [u kappa_x + v kappa_y]^ - M [kappa_x w_y - kappa_y w_x + m_x (theta_y + Gy) - m_y (theta_x + Gx)]^ / |k|^2
+ *   r_theta = M_theta [u m_x + v m_y - by kappa_x + bx kappa_y]^                       (M_theta keeps the (0, 0) mode)
+ * and the Lawson recurrences of nns_spec_ns_step_adjoint_f32 run twice: with E = exp(-(nu |k|^2 + drag) dt / 2) on (lam, kappa, r_w) and with
+ * E_theta = exp(-kappa |k|^2 dt / 2), no drag, on (mu, m, r_theta).  what0, that0: [nsteps][batch][my1][nx][2], the spectra at the START of
+ * every step (only read; a step's stages are recomputed from them by the forward's own kernels).  lam, mu: [batch][my1][nx][2], in the
+ * cotangents of (w^, theta^) after the last step, out those of the pair before the first.  gbar as in nns_spec_ns_step_adjoint_f32 (the
+ * vorticity source; the scalar has none); mean, ghat, gbatch, dt, nu, drag, kappa, (gx, gy), (bx, by): the forward's, constants that are not
+ * differentiated.  b = (0, 0) is the passive scalar's adjoint.  A grid's result does not depend on its batch neighbours, and nsteps steps in
+ * one call are bitwise nsteps calls of one step, last first.  work: nns_spec_ns_scalar_adjoint_workspace bytes (21 compacted fields: it also
+ * serves every other nns_spec_ns_* call).  16 launches per step (7 recompute, 9 adjoint), no allocation, no host synchronisation
+ * (capturable).  Errors as nns_spec_ns_step_buoyant_f32. */
+int nns_spec_ns_scalar_adjoint_workspace(int batch, int nx, int ny, size_t* bytes);
+int nns_spec_ns_step_scalar_adjoint_f32(const float* what0, const float* that0, const float* mean, const float* ghat, int gbatch, float* lam,
+                                        float* mu, float* gbar, void* work, size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly,
+                                        double dt, double nu, double drag, double kappa, double gx, double gy, double bx, double by, int nsteps,
+                                        void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

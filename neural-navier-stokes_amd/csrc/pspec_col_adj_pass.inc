@@ -1,0 +1,98 @@
+// One spectrum's pass through a column tile of ps_col_adj_scalar_kernel (pspec_kernels.hip), which includes this text once per spectrum with
+// TH in scope, the way ps_col_kernel includes pspec_col_pass.inc: TH = false the vorticity (Ph fields 0 and 1, lam / wbar / gbar, grad kappa to
+// G fields 4 and 5), TH = true the scalar (Ph field 2, mu / thetabar, grad m to G fields 8 and 9).  The vorticity's arithmetic is that of
+// ps_col_adj_kernel (its note has the recurrences); the scalar's differs in three places: L dt / 2 = hkdt |k|^2 without the drag, the mask keeps
+// the (0, 0) mode, and r_theta is Ph's third field as it stands (no inverse Laplacian, no source to sum a cotangent for).
+// In scope: the names of pspec_col_tile.inc, consume, field, ad (PsAdjScalar), tv, ky, dt, dt2, dt3, dt6.
+{
+        float2* lamp = TH ? ad.mu : ad.w.lam;
+        float2* barp = TH ? ad.tbar : ad.w.wbar;
+        [[maybe_unused]] cf kap[16];
+        if constexpr (S < 4) {
+            cf r[16];
+            [[maybe_unused]] cf z[16];
+            if constexpr (TH) {
+                consume(Ph + 2 * a.fstride, r);
+            } else {
+                consume(Ph, r);
+                __syncthreads();                    // the next staging overwrites line images other waves may still read
+                consume(Ph + a.fstride, z);
+            }
+            int te = tv;
+            asm volatile("" : "+v"(te), "+v"(r[0].x));
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const int e = te + TPF * m;
+                const int mx = m < 8 ? e : e - N;
+                const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (TH || (mx | lj) != 0);
+                const float kx = a.kx1 * (float)mx;
+                const float k2 = kx * kx + ky * ky;
+                const float x = TH ? ad.hkdt * k2 : a.hnudt * k2 - ad.w.hdrag;      // L dt / 2
+                const float em1 = expm1f(x), em2 = expm1f(2.f * x);
+                cf rr = {0.f, 0.f};
+                if constexpr (TH) {
+                    if (keep) rr = r[m];
+                } else {
+                    const float ik2 = k2 > 0.f ? 1.f / k2 : 0.f;
+                    if (keep) rr = {fmaf(-ik2, z[m].x, r[m].x), fmaf(-ik2, z[m].y, r[m].y)};
+                }
+                const size_t si = wbase + e;
+                const float2 l2 = lok ? lamp[si] : make_float2(0.f, 0.f);
+                const cf lam = keep ? cf{l2.x, l2.y} : cf{0.f, 0.f};
+                cf wb;
+                if constexpr (S == 3) {
+                    wb = scal(em2, cf{lam.x + rr.x, lam.y + rr.y});
+                    kap[m] = scal(em1, axpy(dt, rr, cf{dt3 * lam.x, dt3 * lam.y}));
+                } else {
+                    const float2 w2 = lok ? barp[si] : make_float2(0.f, 0.f);
+                    if constexpr (S == 0) {
+                        wb = {w2.x + rr.x, w2.y + rr.y};
+                    } else {
+                        const cf er = scal(em1, rr);
+                        wb = {w2.x + er.x, w2.y + er.y};
+                        if constexpr (S == 2) {
+                            const cf el = scal(em1, lam);
+                            kap[m] = axpy(dt2, rr, cf{dt3 * el.x, dt3 * el.y});
+                        } else {
+                            const cf el = scal(em2, lam);
+                            kap[m] = axpy(dt2, er, cf{dt6 * el.x, dt6 * el.y});
+                        }
+                    }
+                }
+                if (lok) {
+                    if constexpr (S == 0) {
+                        lamp[si] = make_float2(wb.x, wb.y);
+                    } else {
+                        barp[si] = make_float2(wb.x, wb.y);
+                        if constexpr (!TH) {
+                            if (ad.w.gbar) {
+                                const float2 g2 = ad.w.gbar[si];
+                                ad.w.gbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
+                            }
+                        }
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const int e = tv + TPF * m;
+                const int mx = m < 8 ? e : e - N;
+                const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (TH || (mx | lj) != 0);
+                const size_t si = wbase + e;
+                const float2 l2 = lok ? lamp[si] : make_float2(0.f, 0.f);
+                kap[m] = keep ? cf{dt6 * l2.x, dt6 * l2.y} : cf{0.f, 0.f};
+                if constexpr (!TH) {
+                    if (lok && ad.w.gbar) {
+                        const float2 g2 = ad.w.ginit ? make_float2(0.f, 0.f) : ad.w.gbar[si];
+                        ad.w.gbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
+                    }
+                }
+            }
+        }
+        if constexpr (S >= 1) {
+            static_for<TH ? 8 : 4, TH ? 10 : 6>([&](auto fc) { field(fc, kap); });
+        } else {
+            __syncthreads();                        // the next staging overwrites line images other waves may still read
+        }
+}

@@ -1,5 +1,6 @@
 // The body of a column kernel's `field` lambda after its pin of te: field F of the spectrum y inverse-transformed along x and written to G through
-// the LDS transpose.  Text of ps_col_kernel (through pspec_col_pass.inc; F = 4, 5: the scalar's gradient) and ps_col_adj_kernel (F = 4, 5: kappa's).
+// the LDS transpose.  Text of ps_col_kernel (through pspec_col_pass.inc; F = 4, 5: the scalar's gradient), ps_col_adj_kernel (F = 4, 5: kappa's) and
+// ps_col_adj_scalar_kernel (F = 6, 7: the state's scalar; 8, 9: its cotangent m).
 // In scope: the names of pspec_col_tile.inc, F, y, te, tv, ky, U0, V0, a, tab, G, my1, TPF, RPI.
                 cf o[16];
 #pragma unroll
@@ -11,8 +12,8 @@
                     const float ik2 = k2 > 0.f ? a.inv_n / k2 : 0.f;
                     if constexpr (F == 0) o[m] = imul(ky * ik2, y[m]);                 // u^ = i ky psi^
                     else if constexpr (F == 1) o[m] = imul(-kx * ik2, y[m]);           // v^ = -i kx psi^
-                    else if constexpr (F == 2 || F == 4) o[m] = imul(kx * a.inv_n, y[m]);   // (w_x)^, (theta_x)^
-                    else o[m] = imul(ky * a.inv_n, y[m]);                              // (w_y)^, (theta_y)^
+                    else if constexpr (F % 2 == 0) o[m] = imul(kx * a.inv_n, y[m]);    // (w_x)^, (theta_x)^: the even fields from 2 on
+                    else o[m] = imul(ky * a.inv_n, y[m]);                              // (w_y)^, (theta_y)^: the odd ones
                 }
                 if constexpr (F < 2) {
                     if (te == 0 && lj == 0) o[0] = {F == 0 ? U0 : V0, 0.f};           // the mean flow in the (0, 0) mode

@@ -64,11 +64,23 @@
 // Measured on the MI355X (profiles/pspec_adjoint_run.json): adjoint / forward step 2.57x at 256^2 x 64 and 2.72x at 1024^2 x 8; the new kernels
 // hold 99 ... 184 VGPRs, no scratch.
 //
+// Reverse mode of the scalar and the buoyant step (nns_spec_ns_step_scalar_adjoint_f32; restatement: tests/pspec_scalar_adjoint_oracle.py): the
+// vector-Jacobian product of the system (w^, theta^), the scalar riding in the flow adjoint's launches as it rides in the step's: still 7 + 9
+// per step.  The recomputation is the forward's scalar (b != 0: buoyant) launches, whose column kernels of stages 1-3 take a PsKeepScalar after
+// the PsScalar and store the next stage's w^ and theta^; ps_row_adj_scalar_kernel<ny> runs five inverse transforms and three products (the
+// scalar's cotangent joins the vorticity's under the one inverse Laplacian; the buoyancy's adjoint is two multiply-adds in physical space), and
+// ps_col_adj_scalar_kernel<nx, S> does per tile the vorticity's work, then the scalar's with E_theta and the mask that keeps (0, 0)
+// (pspec_col_adj_pass.inc, once per spectrum).  G has 10 fields there and Ph 3.  ps_row_adj_kernel, ps_col_adj_kernel and every forward kernel
+// keep their names, arguments and code.  The new kernels hold 108 ... 191 VGPRs, no scratch (profiles/pspec_scalar_adjoint_isa.txt).
+// Measured on the MI355X (profiles/pspec_scalar_adjoint_run.json): adjoint / forward scalar step 2.59x (passive) and 2.48x (buoyant) at
+// 256^2 x 64, 2.60x and 2.56x at 1024^2 x 8; adjoint / flow adjoint 1.71x ... 1.73x and 1.79x ... 1.80x, where the byte model (219 against 132
+// compacted fields moved per step) says 1.66x.
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 //
 // What the row and column kernels share has one copy each: the LDS layout, PsArgs and the row pass's Hermitian fill and kept-mode store in
 // pspec_device.h; the line and tile geometry, the staged forward transform and the field emit as text included at each site
-// (pspec_row_line.inc, pspec_col_tile.inc, pspec_stage.inc, pspec_field.inc), the way pspec_col_pass.inc serves the vorticity and the scalar:
+// (pspec_row_line.inc, pspec_col_tile.inc, pspec_stage.inc, pspec_field.inc), the way pspec_col_pass.inc and pspec_col_adj_pass.inc serve the vorticity and the scalar:
 // a function, a lambda or a type in their place compiles the column kernels to other registers, and their code is pinned
 // (tools/isa_listing.py).  The mode predicate (mx, keep, kx, k2) stays spelt out where it is used, for the same reason.
 #include "pspec_device.h"
@@ -109,6 +121,10 @@ struct PsLinear {         // the argument of the LINEAR column kernels (stages 1
 struct PsKeep {           // the last argument of the STAGES column kernels (stages 1-3 of the adjoint's recomputation; no scalar, noise or table)
     float2* stage;        // [B][my1][nx], the layout of W: receives the next stage's input spectrum (s1, s2 or s3)
 };
+struct PsKeepScalar {     // PsKeep of the SCALAR kernels (after PsScalar): the adjoint of the scalar and the buoyant step recomputes both spectra
+    float2* stage;        // [B][my1][nx]: the next stage's w^
+    float2* tstage;       // [B][my1][nx]: the next stage's theta^
+};
 struct PsAdj {            // the argument of the adjoint column kernels
     float2* lam;          // [B][my1][nx]: the cotangent of the step's result; stage 0 writes the cotangent of its input over it
     float2* wbar;         // [B][my1][nx]: the cotangent of the step's input while it is summed (stages 3..0)
@@ -116,6 +132,16 @@ struct PsAdj {            // the argument of the adjoint column kernels
     const float2* state;  // [B][my1][nx]: the stage state the NEXT adjoint stage linearises about (S = 4: s3, 3: s2, 2: s1, 1: s0), unused by S = 0
     float hdrag;          // alpha dt / 2
     int ginit;            // S = 4: 1 starts gbar (the first step a call takes), 0 adds to it
+};
+struct PsAdjScalar {      // the argument of the scalar adjoint column kernels: PsAdj and its twin for theta^ (no source, so no gbar of its own)
+    PsAdj w;
+    float2* mu;           // [B][my1][nx]: the cotangent of the step's theta^; stage 0 writes the cotangent of its input over it
+    float2* tbar;         // [B][my1][nx]: the cotangent of the step's input theta^ while it is summed (stages 3..0)
+    const float2* tstate; // [B][my1][nx]: theta^ of the stage state w.state belongs to
+    float hkdt;           // -kappa dt / 2
+};
+struct PsAdjGrad {        // the argument of the scalar adjoint row kernel: the uniform mean gradient and the buoyancy
+    float gx, gy, bx, by;
 };
 template <typename U, typename T, typename... R> __device__ __forceinline__ U pick(T t, R... r) {           // the pack's element of type U
     if constexpr (std::is_same_v<U, T>) return t;
@@ -228,7 +254,8 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
 // LINEAR (a PsLinear in the pack, after PsScalar, before PsStoch; FORCED, S = 1..3): the vorticity's L dt / 2 is the complex table entry
 // lin[j][i], not hnudt |k|^2 - alpha dt / 2 (a.hnudt and fc.hdrag are then unused); the scalar's stays hkdt |k|^2.
 // STAGES (a PsKeep alone in the pack; S = 1..3): the next stage's input spectrum is also stored, lane-owned and coalesced like W / A, for the
-// adjoint (ps_col_adj_kernel) to linearise about; the arithmetic is untouched, so the recomputed stages are the forward's bits.
+// adjoint (ps_col_adj_kernel) to linearise about; the arithmetic is untouched, so the recomputed stages are the forward's bits.  With a scalar
+// the pack ends in a PsKeepScalar after the PsScalar, and theta^'s next stage input is stored as well (ps_col_adj_scalar_kernel).
 template <int N, int S, bool FORCED = false, bool SCALAR = false, typename... Sc>
 __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, float2* __restrict__ W,
                                                     float2* __restrict__ A, const float* __restrict__ mean, PsArgs a, int emit,
@@ -236,10 +263,12 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     static_assert(!FORCED || S >= 1, "stage 0 only prepares: it has no forced form");
     constexpr bool STOCH = (std::is_same_v<Sc, PsStoch> || ... || false);
     constexpr bool LINEAR = (std::is_same_v<Sc, PsLinear> || ... || false);
-    constexpr bool STAGES = (std::is_same_v<Sc, PsKeep> || ... || false);
+    constexpr bool KEEP_W = (std::is_same_v<Sc, PsKeep> || ... || false), KEEP_WT = (std::is_same_v<Sc, PsKeepScalar> || ... || false);
+    constexpr bool STAGES = KEEP_W || KEEP_WT;
     static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0) + (STAGES ? 1 : 0),
                   "PsScalar is the SCALAR kernel's argument, PsLinear after it the LINEAR kernel's, PsStoch last the STOCH kernel's");
-    static_assert(!STAGES || (S >= 1 && S <= 3 && !SCALAR && !STOCH && !LINEAR), "the stage store is that of stages 1-3 of the plain and the forced form");
+    static_assert(!STAGES || (S >= 1 && S <= 3 && KEEP_WT == SCALAR && !STOCH && !LINEAR),
+                  "the stage store is that of stages 1-3 of the steady forms: a PsKeep without a scalar, a PsKeepScalar with one");
     static_assert(!LINEAR || (FORCED && S >= 1 && S <= 3), "the complex factors are those of stages 1-3 of the forced form");
     static_assert(!STOCH || (FORCED && (S == 1 || S == 4)), "the kick is stage 4's and the step count stage 1's, both of the forced form");
     using L = PsLds<N>;
@@ -274,7 +303,12 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     [[maybe_unused]] const float2* lin = nullptr;
     if constexpr (LINEAR) lin = pick<PsLinear>(sc...).lin;
     [[maybe_unused]] float2* stage_out = nullptr;
-    if constexpr (STAGES) stage_out = pick<PsKeep>(sc...).stage;
+    [[maybe_unused]] float2* tstage_out = nullptr;
+    if constexpr (KEEP_W) stage_out = pick<PsKeep>(sc...).stage;
+    if constexpr (KEEP_WT) {
+        const PsKeepScalar ke = pick<PsKeepScalar>(sc...);
+        stage_out = ke.stage; tstage_out = ke.tstage;
+    }
     for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
         int tx = threadIdx.x;
         asm volatile("" : "+v"(tx));
@@ -342,6 +376,62 @@ __global__ __launch_bounds__(kT) void ps_row_adj_kernel(const float2* __restrict
     }
 }
 
+// Its scalar twin (restatement: tests/pspec_scalar_adjoint_oracle.py).  With mu the cotangent of a stage's N_theta beside kappa, that of its N_w:
+//     r_w     = M [u kappa_x + v kappa_y]^ - M [kappa_x w_y - kappa_y w_x + mu_x (theta_y + Gy) - mu_y (theta_x + Gx)]^ / |k|^2
+//     r_theta = M_theta [u mu_x + v mu_y - by kappa_x + bx kappa_y]^
+// Five inverse transforms along y (G fields 0-3: u, v, w_x, w_y; 4, 5: grad kappa; 6, 7: grad theta; 8, 9: grad mu), three products, three
+// forward transforms, the kept modes to Ph fields 0 (u . grad kappa), 1 (the sum the inverse Laplacian takes) and 2 (the scalar's).  The
+// buoyancy's adjoint is linear in grad kappa, which the row holds in physical space: two fused multiply-adds, no transform; b = 0 is the
+// passive scalar's.  Three complex lines are live at a time: u, grad kappa and grad mu while the first and the third product leave, then the
+// line of u takes grad w and that of grad kappa takes grad theta.
+template <int N>
+__global__ __launch_bounds__(kT) void ps_row_adj_scalar_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a, PsAdjGrad gr) {
+    using L = PsLds<N>;
+    constexpr int TPF = L::TPF;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const cf* tab = ps_tables<N>(smem);
+    unsigned char* lines = smem + L::TAB_BYTES;
+    const int my1 = a.my1;
+    const long niter = (a.nlines + L::LINES - 1) / L::LINES;
+    for (long it = blockIdx.x; it < niter; it += gridDim.x) {
+#include "pspec_row_line.inc"
+        cf zu[16], zk[16], zm[16];
+        ps_row_load2<N>(g0, g0 + a.fstride, tid, my1, zu);                           // u + i v
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 4 * a.fstride, g0 + 5 * a.fstride, tid, my1, zk);       // kappa_x + i kappa_y: stays
+        fft_line<float, N, true>(zk, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zm[m] = {zu[m].x * zk[m].x + zu[m].y * zk[m].y, 0.f};        // u kappa_x + v kappa_y: u, v stay
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zm, tab, tab + N / 2, xb, tid);
+        ps_row_store<N>(zm, Ph + (size_t)row * my1, tid, my1, valid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 8 * a.fstride, g0 + 9 * a.fstride, tid, my1, zm);       // mu_x + i mu_y: stays
+        fft_line<float, N, true>(zm, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m)                                                 // u mu_x + v mu_y - by kappa_x + bx kappa_y
+            zu[m] = {fmaf(zu[m].x, zm[m].x, fmaf(zu[m].y, zm[m].y, fmaf(-gr.by, zk[m].x, gr.bx * zk[m].y))), 0.f};
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
+        ps_row_store<N>(zu, Ph + 2 * a.fstride + (size_t)row * my1, tid, my1, valid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 2 * a.fstride, g0 + 3 * a.fstride, tid, my1, zu);       // w_x + i w_y
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zu[m] = {zk[m].x * zu[m].y - zk[m].y * zu[m].x, 0.f};        // kappa_x w_y - kappa_y w_x
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 6 * a.fstride, g0 + 7 * a.fstride, tid, my1, zk);       // theta_x + i theta_y
+        fft_line<float, N, true>(zk, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m)                                                 // + mu_x (theta_y + Gy) - mu_y (theta_x + Gx)
+            zu[m].x = fmaf(zm[m].x, zk[m].y + gr.gy, fmaf(-zm[m].y, zk[m].x + gr.gx, zu[m].x));
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
+        ps_row_store<N>(zu, Ph + a.fstride + (size_t)row * my1, tid, my1, valid);
+    }
+}
+
 // The adjoint column pass, S = 4 .. 0 in the order it runs (ps_col_kernel's tile: pspec_col_tile.inc, pspec_stage.inc).  With lam the cotangent of the step's
 // result, r = N'(s)^T kappa of the stage just evaluated by the row pass (S < 4: Ph fields 0 and 1 staged and forward-transformed along x,
 // r = keep ? Q1 - Q2 / |k|^2 : 0) and E - 1, E^2 - 1 in the forward's expm1 form:
@@ -353,6 +443,8 @@ __global__ __launch_bounds__(kT) void ps_row_adj_kernel(const float2* __restrict
 // gbar += kappa in every stage that makes one.  lam, wbar and gbar are lane-owned and coalesced, like W / A.  Preparing: the four spectra of
 // the state (ad.state, the forward's field<0..3>: pspec_field.inc, the mean in the (0, 0) mode) inverse-transformed along x to G fields 0-3, and
 // i kx kappa^, i ky kappa^ to G fields 4 and 5 (these first: kappa's registers are free before the state is loaded).
+// These recurrences have a second copy: the vorticity's pass of ps_col_adj_scalar_kernel (pspec_col_adj_pass.inc with TH = false), kept apart so
+// that this kernel's code stays what it was.  A fix to either belongs in both.
 template <int N, int S>
 __global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, const float* __restrict__ mean,
                                                         PsArgs a, PsAdj ad) {
@@ -464,6 +556,73 @@ __global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict
             static_for<0, 4>([&](auto fc) { field(fc, y); });
         } else {
             __syncthreads();                        // the next staging overwrites line images other waves may still read
+        }
+    }
+}
+
+// Its scalar twin: after the vorticity's work on a tile the same sequence runs on the scalar (pspec_col_adj_pass.inc, once per spectrum), with
+// E_theta = exp(-kappa |k|^2 dt / 2) and mu, m, thetabar where the vorticity has E, lam, kappa, wbar:
+//     S = 4                                             m4 = dt/6 mu
+//     S = 3   thetabar  = E_theta^2 (mu + r_theta)      m3 = dt/3 E_theta mu + dt E_theta r_theta
+//     S = 2   thetabar += E_theta r_theta               m2 = dt/3 E_theta mu + dt/2 r_theta
+//     S = 1   thetabar += E_theta r_theta               m1 = dt/6 E_theta^2 mu + dt/2 E_theta r_theta
+//     S = 0   mu        = thetabar + r_theta
+// r_w takes Ph fields 0 and 1 as in ps_col_adj_kernel (field 1 now also holds the scalar's share), r_theta = keep_theta ? Ph field 2 : 0.
+// Preparing: i kx kappa^, i ky kappa^ to G fields 4 and 5 and i kx m^, i ky m^ to 8 and 9 (each while its registers are still there), then the
+// state's four spectra to G fields 0-3 and i kx theta^, i ky theta^ of the state's scalar to 6 and 7.  One spectrum's registers at a time.
+template <int N, int S>
+__global__ __launch_bounds__(kT) void ps_col_adj_scalar_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, const float* __restrict__ mean,
+                                                               PsArgs a, PsAdjScalar ad) {
+    static_assert(S >= 0 && S <= 4, "adjoint stages 4 .. 0");
+    using L = PsLds<N>;
+    constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const cf* tab = ps_tables<N>(smem);
+    unsigned char* lines = smem + L::TAB_BYTES;
+    const int my1 = a.my1;
+    const long ntiles = (a.nlines + CW - 1) / CW;
+    [[maybe_unused]] const float dt = a.dt, dt2 = 0.5f * dt, dt3 = dt / 3.f, dt6 = dt / 6.f;
+    for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        int tx = threadIdx.x;
+        asm volatile("" : "+v"(tx));
+#include "pspec_col_tile.inc"
+        int tv = tid;
+        asm volatile("" : "+v"(tv));
+        const float ky = a.ky1 * (float)lj;
+        // Ph's field `ph` of the tile through the LDS transpose, forward-transformed along x
+        [[maybe_unused]] auto consume = [&](const float2* ph, cf (&z)[16]) {
+#include "pspec_stage.inc"
+        };
+        [[maybe_unused]] const float U0 = S >= 1 && lok ? mean[2 * lb] : 0.f, V0 = S >= 1 && lok ? mean[2 * lb + 1] : 0.f;
+        // field F of the spectrum y, transformed along x and written to G through the LDS transpose: ps_col_adj_kernel's
+        [[maybe_unused]] auto field = [&](auto fc, const cf (&y)[16]) {
+            constexpr int F = decltype(fc)::value;
+            int te = tv;
+            asm volatile("" : "+v"(te));
+#include "pspec_field.inc"
+        };
+        {
+            constexpr bool TH = false;
+#include "pspec_col_adj_pass.inc"
+        }
+        {
+            constexpr bool TH = true;
+#include "pspec_col_adj_pass.inc"
+        }
+        if constexpr (S >= 1) {
+            cf y[16];
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const float2 w = lok ? ad.w.state[wbase + tv + TPF * m] : make_float2(0.f, 0.f);
+                y[m] = {w.x, w.y};
+            }
+            static_for<0, 4>([&](auto fc) { field(fc, y); });
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const float2 w = lok ? ad.tstate[wbase + tv + TPF * m] : make_float2(0.f, 0.f);
+                y[m] = {w.x, w.y};
+            }
+            static_for<6, 8>([&](auto fc) { field(fc, y); });
         }
     }
 }
@@ -902,7 +1061,7 @@ int launch_row(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s, Gr..
 template <int N, int S, bool FORCED, typename... X>
 int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
                hipStream_t s, X... x) {
-    constexpr bool SC = has<PsScalar, X...>, LI = has<PsLinear, X...>, ST = has<PsStoch, X...>, KE = has<PsKeep, X...>;
+    constexpr bool SC = has<PsScalar, X...>, LI = has<PsLinear, X...>, ST = has<PsStoch, X...>, KE = has<PsKeep, X...> || has<PsKeepScalar, X...>;
     constexpr auto kern = ps_col_kernel<N, S, FORCED, SC, X...>;
     std::conditional_t<FORCED, PsForce, PsNoForce> f{};
     if constexpr (FORCED) f = *fc;
@@ -962,6 +1121,36 @@ int launch_col_keep(int S, const float2* Ph, float2* G, float2* W, float2* A, co
     return with_stage<1, 3>(S, go);
 }
 
+// The same with a scalar: the SCALAR kernels, whose pack is the PsScalar and a PsKeepScalar
+template <int N>
+int launch_col_keep_scalar(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, const PsForce* fc,
+                           const PsScalar& sc, const PsKeepScalar& ke, hipStream_t s) {
+    auto go = [&](auto stage_c) {
+        constexpr int K = decltype(stage_c)::value;
+        return fc ? launch_col<N, K, true>(Ph, G, W, A, mean, a, 1, fc, s, sc, ke) : launch_col<N, K, false>(Ph, G, W, A, mean, a, 1, fc, s, sc, ke);
+    };
+    return with_stage<1, 3>(S, go);
+}
+
+template <int N>
+int launch_row_adj_scalar(const float2* G, float2* Ph, const PsArgs& a, const PsAdjGrad& gr, hipStream_t s) {
+    constexpr auto kern = ps_row_adj_scalar_kernel<N>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a, gr);
+    return check_launch("spec_ns scalar adjoint row pass");
+}
+
+template <int N>
+int launch_col_adj_scalar(int S, const float2* Ph, float2* G, const float* mean, const PsArgs& a, const PsAdjScalar& ad, hipStream_t s) {
+    auto go = [&](auto stage_c) {
+        constexpr auto kern = ps_col_adj_scalar_kernel<N, decltype(stage_c)::value>;
+        if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+        hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, mean, a, ad);
+        return check_launch("spec_ns scalar adjoint column pass");
+    };
+    return with_stage<0, 4>(S, go);
+}
+
 template <int N>
 int launch_row_adj(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s) {
     constexpr auto kern = ps_row_adj_kernel<N>;
@@ -1005,6 +1194,13 @@ size_t adjoint_work_bytes(int batch, int nx, int ny) {
     return st > b ? st : b;
 }
 
+// the scalar adjoint's A, A_theta (wbar and thetabar once the stages are recomputed), G[10], Ph[3] and the stage states s1, s2, s3 of w^ and
+// of theta^: 21 compacted fields
+size_t scalar_adjoint_work_bytes(int batch, int nx, int ny) {
+    const size_t b = work_bytes(batch, nx, ny), st = (size_t)21 * batch * nx * kept_y(ny) * sizeof(float2);
+    return st > b ? st : b;
+}
+
 // The step's layout of work, compacted fields of fstride complex each: A, G[4], Ph; with a scalar A, A_theta, G[6], Ph[2]; and the arguments
 // of the column pass (col) and of the row pass (row).
 struct PsWork {
@@ -1041,15 +1237,19 @@ int check_box(const char* what, int nx, int ny, double Lx, double Ly) {
     return check_axes(what, nx, ny);
 }
 
-enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2 };      // a bool converts: false the flow's workspace, true the scalar's
+enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2, kWorkScalarAdjoint = 3 };      // a bool converts: false the flow's workspace, true the scalar's
 
 int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int kind) {
-    const size_t need = kind == kWorkAdjoint ? adjoint_work_bytes(batch, nx, ny)
-                        : kind == kWorkScalar ? scalar_work_bytes(batch, nx, ny)
-                                              : work_bytes(batch, nx, ny);
+    const size_t need = kind == kWorkScalarAdjoint ? scalar_adjoint_work_bytes(batch, nx, ny)
+                        : kind == kWorkAdjoint     ? adjoint_work_bytes(batch, nx, ny)
+                        : kind == kWorkScalar      ? scalar_work_bytes(batch, nx, ny)
+                                                   : work_bytes(batch, nx, ny);
     if (wbytes < need)
         return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", what, wbytes, need,
-                    kind == kWorkAdjoint ? "nns_spec_ns_adjoint_workspace" : kind == kWorkScalar ? "nns_spec_ns_scalar_workspace" : "nns_spec_ns_workspace");
+                    kind == kWorkScalarAdjoint ? "nns_spec_ns_scalar_adjoint_workspace"
+                    : kind == kWorkAdjoint     ? "nns_spec_ns_adjoint_workspace"
+                    : kind == kWorkScalar      ? "nns_spec_ns_scalar_workspace"
+                                               : "nns_spec_ns_workspace");
     return NNS_OK;
 }
 
@@ -1074,6 +1274,13 @@ int check_gbatch(const char* what, const float* ghat, int gbatch, int batch) {
 
 int check_buoyancy(const char* what, double bx, double by) {
     if (!std::isfinite(bx) || !std::isfinite(by)) return fail(NNS_ERR_INVALID_ARG, "%s: the buoyancy (%g, %g) must be finite", what, bx, by);
+    return NNS_OK;
+}
+
+// kappa and G of a step with a scalar, forward or adjoint
+int check_scalar_numbers(const char* who, double kappa, double gx, double gy) {
+    if (!(kappa >= 0) || !std::isfinite(kappa) || !std::isfinite(gx) || !std::isfinite(gy))
+        return fail(NNS_ERR_INVALID_ARG, "%s: kappa = %g must be finite and >= 0, the gradient (%g, %g) finite", who, kappa, gx, gy);
     return NNS_OK;
 }
 
@@ -1234,8 +1441,7 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
                         const float* lin = nullptr) {
     if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
     if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
-    if (!(kappa >= 0) || !std::isfinite(kappa) || !std::isfinite(gx) || !std::isfinite(gy))
-        return fail(NNS_ERR_INVALID_ARG, "%s: kappa = %g must be finite and >= 0, the gradient (%g, %g) finite", who, kappa, gx, gy);
+    if (int rc = check_scalar_numbers(who, kappa, gx, gy)) return rc;
     if (int rc = check_buoyancy(who, bx, by)) return rc;
     if (int rc = check_gbatch(who, ghat, gbatch, batch)) return rc;
     if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, that != nullptr)) return rc;
@@ -1382,6 +1588,88 @@ NNS_API int nns_spec_ns_step_adjoint_f32(const float* what0, const float* mean, 
             ad.state = S >= 2 ? stages + (size_t)(S - 2) * fstride : W;
             ad.ginit = k == nsteps - 1;
             if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_adj<decltype(n)::value>(S, L.Ph, L.G, mean, L.col, ad, s); }))
+                return rc;
+        }
+    }
+    return NNS_OK;
+}
+
+NNS_API int nns_spec_ns_scalar_adjoint_workspace(int batch, int nx, int ny, size_t* bytes) {
+    if (!bytes || batch < 1)
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_adjoint_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
+    if (int rc = check_axes("spec_ns_scalar_adjoint_workspace", nx, ny)) return rc;
+    *bytes = scalar_adjoint_work_bytes(batch, nx, ny);
+    return NNS_OK;
+}
+
+// The reverse mode of spec_ns_step's scalar and buoyant forms, last step first: nns_spec_ns_step_adjoint_f32 with the scalar riding in its
+// launches.  Per step the stage states of w^ and theta^ are recomputed from the saved pair by the forward's own launches (b != 0: the buoyant
+// row kernel), stages 1-3 with the PsKeepScalar (7); then ps_col_adj_scalar_kernel, S = 4 .. 0, and ps_row_adj_scalar_kernel between them (9).
+NNS_API int nns_spec_ns_step_scalar_adjoint_f32(const float* what0, const float* that0, const float* mean, const float* ghat, int gbatch,
+                                                float* lam, float* mu, float* gbar, void* work, size_t work_bytes_, int batch, int nx, int ny,
+                                                double Lx, double Ly, double dt, double nu, double drag, double kappa, double gx, double gy,
+                                                double bx, double by, int nsteps, void* stream) {
+    const char* who = "spec_ns_step_scalar_adjoint";
+    if (!what0 || !that0 || !mean || !lam || !mu || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
+    if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
+    if (int rc = check_scalar_numbers(who, kappa, gx, gy)) return rc;
+    if (int rc = check_buoyancy(who, bx, by)) return rc;
+    if (int rc = check_gbatch(who, ghat, gbatch, batch)) return rc;
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, kWorkScalarAdjoint)) return rc;
+    if (nsteps == 0) {
+        if (!gbar) return NNS_OK;
+        void* zb[1] = {gbar};
+        const long zn[1] = {(long)((size_t)batch * kept_y(ny) * nx * sizeof(float2))};
+        return zero_buffers(zb, zn, 1, as_stream(stream));
+    }
+    hipStream_t s = as_stream(stream);
+    PsWork L(work, batch, nx, ny, true, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);           // A, A_theta, then G[10], Ph[3] (the forward's
+    const long fstride = L.col.fstride;                                                        // launches use the first 6 and 2 of them)
+    L.Ph = L.G + 10 * fstride;
+    float2* wstages = L.Ph + 3 * fstride;                                                      // s1, s2, s3 of w^
+    float2* tstages = wstages + 3 * fstride;                                                   // and of theta^
+    const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
+    const PsForce* fc = ghat || drag > 0 ? &force : nullptr;                                   // the forward's choice of kernels: its bits
+    const float hkdt = (float)(-0.5 * kappa * dt);
+    const PsGrad grad{(float)gx, (float)gy};
+    const PsBuoyGrad buoy{(float)gx, (float)gy, (float)(-(double)ny * by), (float)((double)ny * bx)};
+    const bool buoyant = bx != 0.0 || by != 0.0;
+    const PsAdjGrad agrad{(float)gx, (float)gy, (float)bx, (float)by};
+    // wbar and thetabar take the accumulators' places: the recomputation is over when adjoint stage 3 first writes them
+    PsAdjScalar ad{PsAdj{reinterpret_cast<float2*>(lam), L.A, reinterpret_cast<float2*>(gbar), nullptr, force.hdrag, 0},
+                   reinterpret_cast<float2*>(mu), L.At, nullptr, hkdt};
+    auto row = [&]() {
+        return dispatch_pow2(ny, "spec_ns", [&](auto n) {
+            constexpr int N = decltype(n)::value;
+            return buoyant ? launch_row<N>(L.G, L.Ph, L.row, s, buoy) : launch_row<N>(L.G, L.Ph, L.row, s, grad);
+        });
+    };
+    auto row_adj = [&]() {
+        return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row_adj_scalar<decltype(n)::value>(L.G, L.Ph, L.row, agrad, s); });
+    };
+    for (int k = nsteps - 1; k >= 0; --k) {
+        float2* W = const_cast<float2*>(reinterpret_cast<const float2*>(what0)) + (size_t)k * fstride;      // stages 0-3 only read W and T
+        float2* T = const_cast<float2*>(reinterpret_cast<const float2*>(that0)) + (size_t)k * fstride;
+        const PsScalar scalar{T, L.At, hkdt};
+        if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
+                return launch_col_stage<decltype(n)::value>(0, L.Ph, L.G, W, L.A, mean, L.col, 1, nullptr, &scalar, s);
+            }))
+            return rc;
+        for (int S = 1; S <= 3; ++S) {
+            if (int rc = row()) return rc;
+            const PsKeepScalar ke{wstages + (size_t)(S - 1) * fstride, tstages + (size_t)(S - 1) * fstride};
+            if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
+                    return launch_col_keep_scalar<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, fc, scalar, ke, s);
+                }))
+                return rc;
+        }
+        for (int S = 4; S >= 0; --S) {
+            if (S < 4)
+                if (int rc = row_adj()) return rc;
+            ad.w.state = S >= 2 ? wstages + (size_t)(S - 2) * fstride : W;
+            ad.tstate = S >= 2 ? tstages + (size_t)(S - 2) * fstride : T;
+            ad.w.ginit = k == nsteps - 1;
+            if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_adj_scalar<decltype(n)::value>(S, L.Ph, L.G, mean, L.col, ad, s); }))
                 return rc;
         }
     }

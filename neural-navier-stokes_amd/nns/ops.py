@@ -1324,3 +1324,35 @@ def spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, work, ny, Lx, Ly, dt, nu
                                                   None if gbar is None else _p(gbar), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly),
                                                   float(dt), float(nu), float(drag), int(what0.shape[0]), _stream()), 'nns_spec_ns_step_adjoint_f32')
     return lam, gbar
+
+
+# reverse mode of the periodic solver's scalar and buoyant step (nns_spec_ns_scalar_adjoint_workspace, nns_spec_ns_step_scalar_adjoint_f32)
+def spec_ns_scalar_adjoint_workspace(B, nx, ny):
+    """Bytes of the workspace spec_ns_step_scalar_adjoint_ needs for B grids of nx x ny (>= every other spec_ns workspace)."""
+    return _query_bytes('nns_spec_ns_scalar_adjoint_workspace', int(B), int(nx), int(ny))
+
+
+def spec_ns_step_scalar_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, ny, Lx, Ly, dt, nu, drag, kappa, grad=(0.0, 0.0),
+                                 buoyancy=(0.0, 0.0)):
+    """spec_ns_step_adjoint_ for the system (w^, theta^) of spec_ns_step_scalar_ / spec_ns_step_buoyant_: what0, that0 (float32
+    [nsteps, B, my1, nx, 2], only read) are the spectra at the start of every step; lam and mu ([B, my1, nx, 2]) hold, in, the cotangents of
+    (w^, theta^) after the last step and, out, those of the pair before the first; gbar (the same shape, or None) receives the cotangent of the
+    vorticity source g^, one per grid, summed over the steps.  mean, ghat, dt, nu, drag, kappa, grad, buoyancy: the forward's (buoyancy
+    (0, 0): the passive scalar).  work: spec_ns_scalar_adjoint_workspace bytes.  16 launches per step, no allocation, no host synchronisation."""
+    who = 'spec_ns_step_scalar_adjoint_'
+    B, my1, nx = _spec_ns_state(who, lam, mean, work, ny)
+    _spec_ns_same(who, mu, lam)
+    for name, t in (('what0', what0), ('that0', that0)):
+        _f32(t)
+        if t.dim() != 5 or tuple(t.shape[1:]) != tuple(lam.shape) or t.device != lam.device or t.shape[0] != what0.shape[0]:
+            raise ValueError("%s: %s must be float32 [nsteps, %d, %d, %d, 2] on the state's device, got %s" % (who, name, B, my1, nx, tuple(t.shape)))
+    gbatch = _spec_ns_force(who, ghat, lam)
+    if gbar is not None:
+        _spec_ns_same(who, gbar, lam)
+    (gx, gy), (bx, by) = grad, buoyancy
+    check(_lib.lib().nns_spec_ns_step_scalar_adjoint_f32(_p(what0), _p(that0), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(lam), _p(mu),
+                                                         None if gbar is None else _p(gbar), _p(work), work.numel(), B, nx, int(ny), float(Lx),
+                                                         float(Ly), float(dt), float(nu), float(drag), float(kappa), float(gx), float(gy),
+                                                         float(bx), float(by), int(what0.shape[0]), _stream()),
+          'nns_spec_ns_step_scalar_adjoint_f32')
+    return lam, mu, gbar

@@ -25,6 +25,8 @@ generalise the linear operator that the Lawson factor integrates exactly, at no 
 measured on the MI355X 1.016x the steady-forced step at 256^2 x 64 and 1.003x at 1024^2 x 8, profiles/pspec_linear_run.json).
 ``advance`` / ``advance_velocity`` make the forced, damped flow differentiable: an autograd node whose backward is the adjoint of the step as
 HIP kernels (tests/pspec_adjoint_oracle.py; measured 2.57x a forward step at 256^2 x 64 and 2.72x at 1024^2 x 8, profiles/pspec_adjoint_run.json).
+``advance_scalar`` / ``advance_velocity_scalar`` do the same for the flow with its scalar and buoyancy (tests/pspec_scalar_adjoint_oracle.py; measured
+2.5-2.6x a forward scalar step and 1.7-1.8x the flow's adjoint, profiles/pspec_scalar_adjoint_run.json).
 """
 import collections
 import math
@@ -232,6 +234,74 @@ class _AdvanceFn(torch.autograd.Function):
                 gf = torch.sum(gf, dim=0, keepdim=True)
             gf = gf.reshape(ctx.force_shape)
         return (None, None, None, None, gf) + tuple(grads)
+
+
+class _AdvanceScalarFn(torch.autograd.Function):
+    """``PeriodicSolver.advance_scalar`` / ``advance_velocity_scalar`` as one autograd node, _AdvanceFn's sibling for the system (w, theta): forward
+    the solver's own scalar step (the buoyant one with b != 0) on a fresh state, both spectra at the start of every step kept; backward the
+    adjoint call (ops.spec_ns_step_scalar_adjoint_) between the compact and expand kernels, theta's ends being spec_ns_scalar_init /
+    spec_ns_scalar_field.  ``fields``: (w, theta), or with ``velocity`` (u0, v0, theta0)."""
+
+    @staticmethod
+    def forward(ctx, solver, nsteps, mean, velocity, forcing, *fields):
+        s = solver
+        theta = fields[-1].detach()
+        if velocity:
+            state = s.init(fields[0].detach(), fields[1].detach(), theta)
+        else:
+            state = s.init_vorticity(fields[0].detach(), mean)
+            state.that = ops.spec_ns_scalar_init(s._field('theta', theta).contiguous(), torch.empty_like(state.what), state.work)
+        ghat = s._force_of(state) if forcing is None else s._source_spectrum(forcing.detach(), state)
+        what0 = torch.empty((nsteps,) + tuple(state.what.shape), dtype=torch.float32, device=state.what.device)
+        that0 = torch.empty_like(what0)
+        box = (state.mean, ghat, state.work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag, s.kappa, s.scalar_gradient)
+        for k in range(nsteps):
+            what0[k].copy_(state.what)
+            that0[k].copy_(state.that)
+            if s._buoyant(state):
+                ops.spec_ns_step_buoyant_(state.what, state.that, *box, s.buoyancy, 1)
+            else:
+                ops.spec_ns_step_scalar_(state.what, state.that, *box, 1)
+        ctx.solver, ctx.velocity, ctx.squeeze = s, velocity, fields[0].dim() == 2
+        ctx.shared = forcing is not None and forcing.shape[0] == 1 and state.batch > 1
+        ctx.force_shape = None if forcing is None else tuple(forcing.shape)
+        ctx.save_for_backward(what0, that0, state.mean, *(() if ghat is None else (ghat,)))
+        out = (s.fields(state)[:2] if velocity else (s.vorticity(state),)) + (s.scalar(state),)
+        return tuple(o[0] for o in out) if ctx.squeeze else tuple(out)
+
+    @staticmethod
+    def backward(ctx, *gout):
+        s = ctx.solver
+        what0, that0, mean = ctx.saved_tensors[:3]
+        ghat = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        B, dev = what0.shape[1], what0.device
+        shape = (B, s.nx, s.ny)
+        gout = [torch.zeros(shape, dtype=torch.float32, device=dev) if g is None else g.reshape(shape).contiguous() for g in gout]
+        zero = torch.zeros((B, 2), dtype=torch.float32, device=dev)
+        work = torch.empty(ops.spec_ns_scalar_adjoint_workspace(B, s.nx, s.ny), dtype=torch.uint8, device=dev)
+        if ctx.velocity:                                  # K^T (ubar, vbar)^ = curl(ubar, vbar)^ / |k|^2
+            lam = s.init(gout[0], gout[1]).what * s._k2_table(dev, -1)
+        else:
+            lam = s.init_vorticity(gout[0]).what
+        mu = ops.spec_ns_scalar_init(gout[-1], torch.empty_like(lam), work)
+        need_g = ctx.force_shape is not None and ctx.needs_input_grad[4]
+        gbar = torch.empty_like(lam) if need_g else None
+        ops.spec_ns_step_scalar_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag, s.kappa,
+                                         s.scalar_gradient, s.buoyancy)
+        if ctx.velocity:                                  # init^T (lam) = (lam_y, -lam_x): the velocity of the streamfunction lam
+            grads = s.fields(PeriodicState(lam * s._k2_table(dev, 1), zero, work))[:2]
+        else:
+            grads = (s.vorticity(PeriodicState(lam, zero, work)),)
+        grads = tuple(grads) + (ops.spec_ns_scalar_field(mu, work, s.ny),)
+        if ctx.squeeze:
+            grads = tuple(g[0] for g in grads)
+        gf = None
+        if need_g:
+            gf = s.vorticity(PeriodicState(gbar, zero, work))
+            if ctx.shared:
+                gf = torch.sum(gf, dim=0, keepdim=True)
+            gf = gf.reshape(ctx.force_shape)
+        return (None, None, None, None, gf) + grads
 
 
 class PeriodicSolver(object):
@@ -615,9 +685,10 @@ class PeriodicSolver(object):
         return state
 
     # ---- reverse mode
-    def _refuse_unsupported(self, who):
-        """The adjoint covers the forced, damped flow; name the argument that puts a solver outside it."""
-        for name, on in (('buoyancy', self.buoyancy != (0.0, 0.0)), ('kappa', self.kappa is not None),
+    def _refuse_unsupported(self, who, scalar=False):
+        """The adjoint covers the forced, damped flow and, through the ``scalar`` entry points, its scalar and buoyancy; name the argument that
+        puts a solver outside it."""
+        for name, on in (('buoyancy', self.buoyancy != (0.0, 0.0) and not scalar), ('kappa', self.kappa is not None and not scalar),
                          ('set_stochastic_forcing', self.stoch_amp is not None), ('hyperviscosity', self.hyperviscosity[0] > 0),
                          ('hypofriction', self.hypofriction[0] > 0), ('beta', self.beta != 0.0)):
             if on:
@@ -679,7 +750,8 @@ class PeriodicSolver(object):
         ``mean``: the mean velocity ([B, 2] or a pair; None: at rest), a constant of the motion that is not differentiated.  The forward is
         bitwise ``vorticity(step(init_vorticity(w, mean), nsteps))``.  Memory kept for the backward: the spectrum at the start of every step,
         nsteps x B x my1 x nx x 8 bytes (my1 = (ny - 1) // 3 + 1: a third of a field per step and grid); the stages inside a step are recomputed.
-        Not yet for a solver with kappa, buoyancy, a stochastic force, hyperviscosity, hypofriction or beta: NotImplementedError."""
+        Not for a solver with kappa or buoyancy (``advance_scalar`` / ``advance_velocity_scalar`` take and return the scalar) and not yet for a
+        stochastic force, hyperviscosity, hypofriction or beta: NotImplementedError."""
         self._refuse_unsupported('advance')
         nsteps = _count('nsteps', nsteps, 1)
         w = self._grad_field('w', w)
@@ -704,6 +776,44 @@ class PeriodicSolver(object):
             if forcing.dim() == 2:
                 forcing = forcing.unsqueeze(0)
         return _AdvanceFn.apply(self, nsteps, None, True, forcing, u0, v0)
+
+    def _scalar_advance_args(self, who, nsteps, forcing, *fields):
+        """The checked arguments of ``advance_scalar`` / ``advance_velocity_scalar``: the refusals, then the tensor checks of ``advance``."""
+        if self.kappa is None:
+            raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use %s"
+                             % (who, who.replace('_scalar', '')))
+        self._refuse_unsupported(who, scalar=True)
+        nsteps = _count('nsteps', nsteps, 1)
+        fields = [self._grad_field(name, f) for name, f in fields]
+        if any(f.shape != fields[0].shape for f in fields[1:]):
+            raise ValueError("%s: the fields must share their shape" % who)
+        if forcing is not None:
+            forcing = self._grad_field('forcing', forcing)
+            if forcing.dim() == 2:
+                forcing = forcing.unsqueeze(0)
+        return nsteps, forcing, fields
+
+    def advance_scalar(self, w, theta, nsteps=1, mean=None, forcing=None):
+        """(w, theta) after ``nsteps`` steps from the vorticity field w and the scalar theta (float32 device tensors [B, nx, ny] or [nx, ny]) on a
+        solver with ``kappa``, differentiable in w, theta and ``forcing`` like ``advance``: one autograd node whose backward is the adjoint of
+        the scalar step -- of the buoyant one with ``buoyancy`` != 0 -- as HIP kernels (csrc/pspec_kernels.hip: ps_row_adj_scalar_kernel,
+        ps_col_adj_scalar_kernel; derivation in DESIGN.md section 4.2), the scalar riding in the launches of the flow's adjoint as it does in
+        the step.  So an initial temperature can be recovered from a late one, a closure trained through a buoyant flow, a vorticity source
+        fitted to scalar observations.  ``forcing`` and ``mean`` as in ``advance``; the scalar has no source.  The forward is bitwise ``step``
+        on ``init_vorticity(w, mean)`` with ``that`` from ``ops.spec_ns_scalar_init(theta)``, read by ``vorticity`` and ``scalar``.  Memory kept
+        for the backward: both spectra at the start of every step, nsteps x B x my1 x nx x 16 bytes.  kappa, the gradient G, b, nu, the drag and
+        the mean flow are constants and are not differentiated.  ValueError on a solver without kappa; not yet for a stochastic force,
+        hyperviscosity, hypofriction or beta: NotImplementedError."""
+        nsteps, forcing, (w, theta) = self._scalar_advance_args('advance_scalar', nsteps, forcing, ('w', w), ('theta', theta))
+        return _AdvanceScalarFn.apply(self, nsteps, mean, False, forcing, w, theta)
+
+    def advance_velocity_scalar(self, u0, v0, theta0, nsteps=1, forcing=None):
+        """(u, v, theta) after ``nsteps`` steps from the velocity (u0, v0) and the scalar theta0, differentiable like ``advance_scalar``:
+        ``fields(step(init(u0, v0, theta0), nsteps))[:2]`` and ``scalar`` of it forward; backward through the velocity's ends as in
+        ``advance_velocity``.  No pressure output."""
+        nsteps, forcing, (u0, v0, theta0) = self._scalar_advance_args('advance_velocity_scalar', nsteps, forcing, ('u0', u0), ('v0', v0),
+                                                                      ('theta0', theta0))
+        return _AdvanceScalarFn.apply(self, nsteps, None, True, forcing, u0, v0, theta0)
 
     def diagnostics(self, state):
         """Diagnostics(energy, enstrophy, power_in), each float64 [B], computed on the device from the state's spectrum:
