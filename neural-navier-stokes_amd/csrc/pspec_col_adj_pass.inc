@@ -1,12 +1,19 @@
-// One spectrum's pass through a column tile of ps_col_adj_scalar_kernel (pspec_kernels.hip), which includes this text once per spectrum with
-// TH in scope, the way ps_col_kernel includes pspec_col_pass.inc: TH = false the vorticity (Ph fields 0 and 1, lam / wbar / gbar, grad kappa to
-// G fields 4 and 5), TH = true the scalar (Ph field 2, mu / thetabar, grad m to G fields 8 and 9).  The vorticity's arithmetic is that of
-// ps_col_adj_kernel (its note has the recurrences); the scalar's differs in three places: L dt / 2 = hkdt |k|^2 without the drag, the mask keeps
-// the (0, 0) mode, and r_theta is Ph's third field as it stands (no inverse Laplacian, no source to sum a cotangent for).
-// In scope: the names of pspec_col_tile.inc, consume, field, ad (PsAdjScalar), tv, ky, dt, dt2, dt3, dt6.
+// One spectrum's pass through a column tile of ps_col_adj_kernel (pspec_kernels.hip; its note has the recurrences), which includes this text
+// once per spectrum with TH in scope, the way ps_col_kernel includes pspec_col_pass.inc: TH = false the vorticity (Ph fields 0 and 1,
+// lam / wbar / gbar, grad kappa to G fields 4 and 5), TH = true the scalar (a PsAdjScalar's; Ph field 2, mu / thetabar, grad m to G fields 8
+// and 9).  The scalar's arithmetic differs in three places: L dt / 2 = hkdt |k|^2 without the drag, the mask keeps the (0, 0) mode, and
+// r_theta is Ph's third field as it stands (no inverse Laplacian, no source to sum a cotangent for).
+// In scope: the names of pspec_col_tile.inc, consume, field, ad (PsAdj, or PsAdjScalar where TH is true), tv, ky, dt, dt2, dt3, dt6.
 {
-        float2* lamp = TH ? ad.mu : ad.w.lam;
-        float2* barp = TH ? ad.tbar : ad.w.wbar;
+        float2* lamp;
+        float2* barp;
+        if constexpr (TH) {
+            lamp = ad.mu;
+            barp = ad.tbar;
+        } else {
+            lamp = ad.lam;
+            barp = ad.wbar;
+        }
         [[maybe_unused]] cf kap[16];
         if constexpr (S < 4) {
             cf r[16];
@@ -27,7 +34,9 @@
                 const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (TH || (mx | lj) != 0);
                 const float kx = a.kx1 * (float)mx;
                 const float k2 = kx * kx + ky * ky;
-                const float x = TH ? ad.hkdt * k2 : a.hnudt * k2 - ad.w.hdrag;      // L dt / 2
+                float x;                                                             // L dt / 2
+                if constexpr (TH) x = ad.hkdt * k2;
+                else x = a.hnudt * k2 - ad.hdrag;
                 const float em1 = expm1f(x), em2 = expm1f(2.f * x);
                 cf rr = {0.f, 0.f};
                 if constexpr (TH) {
@@ -65,9 +74,9 @@
                     } else {
                         barp[si] = make_float2(wb.x, wb.y);
                         if constexpr (!TH) {
-                            if (ad.w.gbar) {
-                                const float2 g2 = ad.w.gbar[si];
-                                ad.w.gbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
+                            if (ad.gbar) {
+                                const float2 g2 = ad.gbar[si];
+                                ad.gbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
                             }
                         }
                     }
@@ -83,9 +92,9 @@
                 const float2 l2 = lok ? lamp[si] : make_float2(0.f, 0.f);
                 kap[m] = keep ? cf{dt6 * l2.x, dt6 * l2.y} : cf{0.f, 0.f};
                 if constexpr (!TH) {
-                    if (lok && ad.w.gbar) {
-                        const float2 g2 = ad.w.ginit ? make_float2(0.f, 0.f) : ad.w.gbar[si];
-                        ad.w.gbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
+                    if (lok && ad.gbar) {
+                        const float2 g2 = ad.ginit ? make_float2(0.f, 0.f) : ad.gbar[si];
+                        ad.gbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
                     }
                 }
             }

@@ -1,6 +1,6 @@
 // The body of a column kernel's `field` lambda after its pin of te: field F of the spectrum y inverse-transformed along x and written to G through
-// the LDS transpose.  Text of ps_col_kernel (through pspec_col_pass.inc; F = 4, 5: the scalar's gradient), ps_col_adj_kernel (F = 4, 5: kappa's) and
-// ps_col_adj_scalar_kernel (F = 6, 7: the state's scalar; 8, 9: its cotangent m).
+// the LDS transpose.  Text of ps_col_kernel (through pspec_col_pass.inc; F = 4, 5: the scalar's gradient), ps_col_adj_kernel (F = 4, 5: kappa's;
+// with a PsAdjScalar F = 6, 7: the state's scalar; 8, 9: its cotangent m).
 // In scope: the names of pspec_col_tile.inc, F, y, te, tv, ky, U0, V0, a, tab, G, my1, TPF, RPI.
                 cf o[16];
 #pragma unroll

@@ -67,11 +67,12 @@
 // Reverse mode of the scalar and the buoyant step (nns_spec_ns_step_scalar_adjoint_f32; restatement: tests/pspec_scalar_adjoint_oracle.py): the
 // vector-Jacobian product of the system (w^, theta^), the scalar riding in the flow adjoint's launches as it rides in the step's: still 7 + 9
 // per step.  The recomputation is the forward's scalar (b != 0: buoyant) launches, whose column kernels of stages 1-3 take a PsKeepScalar after
-// the PsScalar and store the next stage's w^ and theta^; ps_row_adj_scalar_kernel<ny> runs five inverse transforms and three products (the
-// scalar's cotangent joins the vorticity's under the one inverse Laplacian; the buoyancy's adjoint is two multiply-adds in physical space), and
-// ps_col_adj_scalar_kernel<nx, S> does per tile the vorticity's work, then the scalar's with E_theta and the mask that keeps (0, 0)
-// (pspec_col_adj_pass.inc, once per spectrum).  G has 10 fields there and Ph 3.  ps_row_adj_kernel, ps_col_adj_kernel and every forward kernel
-// keep their names, arguments and code.  The new kernels hold 108 ... 191 VGPRs, no scratch (profiles/pspec_scalar_adjoint_isa.txt).
+// the PsScalar and store the next stage's w^ and theta^; ps_row_adj_kernel<ny, true, PsAdjGrad> runs five inverse transforms and three products
+// (the scalar's cotangent joins the vorticity's under the one inverse Laplacian; the buoyancy's adjoint is two multiply-adds in physical space),
+// and ps_col_adj_kernel<nx, S, PsAdjScalar> does per tile the vorticity's work, then the scalar's with E_theta and the mask that keeps (0, 0):
+// the recurrences have one text for both spectra and both steps (pspec_col_adj_pass.inc).  G has 10 fields there and Ph 3; one host driver
+// (spec_ns_step_adjoint) and one table of workspace layouts (PsLayout) serve both entry points.  These kernels hold 108 ... 191 VGPRs, no
+// scratch (profiles/pspec_scalar_adjoint_isa.txt; the flow's column kernels after the merge: profiles/pspec_adjoint_unify_isa.txt).
 // Measured on the MI355X (profiles/pspec_scalar_adjoint_run.json): adjoint / forward scalar step 2.59x (passive) and 2.48x (buoyant) at
 // 256^2 x 64, 2.60x and 2.56x at 1024^2 x 8; adjoint / flow adjoint 1.71x ... 1.73x and 1.79x ... 1.80x, where the byte model (219 against 132
 // compacted fields moved per step) says 1.66x.
@@ -133,11 +134,10 @@ struct PsAdj {            // the argument of the adjoint column kernels
     float hdrag;          // alpha dt / 2
     int ginit;            // S = 4: 1 starts gbar (the first step a call takes), 0 adds to it
 };
-struct PsAdjScalar {      // the argument of the scalar adjoint column kernels: PsAdj and its twin for theta^ (no source, so no gbar of its own)
-    PsAdj w;
-    float2* mu;           // [B][my1][nx]: the cotangent of the step's theta^; stage 0 writes the cotangent of its input over it
+struct PsAdjScalar : PsAdj {      // with a scalar: PsAdj and its twin for theta^ (no source, so no gbar of its own)
+    float2* mu;          // [B][my1][nx]: the cotangent of the step's theta^; stage 0 writes the cotangent of its input over it
     float2* tbar;         // [B][my1][nx]: the cotangent of the step's input theta^ while it is summed (stages 3..0)
-    const float2* tstate; // [B][my1][nx]: theta^ of the stage state w.state belongs to
+    const float2* tstate; // [B][my1][nx]: theta^ of the stage state that state belongs to
     float hkdt;           // -kappa dt / 2
 };
 struct PsAdjGrad {        // the argument of the scalar adjoint row kernel: the uniform mean gradient and the buoyancy
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
 // lin[j][i], not hnudt |k|^2 - alpha dt / 2 (a.hnudt and fc.hdrag are then unused); the scalar's stays hkdt |k|^2.
 // STAGES (a PsKeep alone in the pack; S = 1..3): the next stage's input spectrum is also stored, lane-owned and coalesced like W / A, for the
 // adjoint (ps_col_adj_kernel) to linearise about; the arithmetic is untouched, so the recomputed stages are the forward's bits.  With a scalar
-// the pack ends in a PsKeepScalar after the PsScalar, and theta^'s next stage input is stored as well (ps_col_adj_scalar_kernel).
+// the pack ends in a PsKeepScalar after the PsScalar, and theta^'s next stage input is stored as well (ps_col_adj_kernel with a PsAdjScalar).
 template <int N, int S, bool FORCED = false, bool SCALAR = false, typename... Sc>
 __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, float2* __restrict__ W,
                                                     float2* __restrict__ A, const float* __restrict__ mean, PsArgs a, int emit,
@@ -343,8 +343,17 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
 // ps_row_adj_kernel is the SCALAR row kernel's twin: three inverse transforms along y (u + i v and w_x + i w_y from G fields 0-3 of s,
 // kappa_x + i kappa_y from G fields 4 and 5), the two products in registers, two forward transforms, the kept modes to Ph fields 0 and 1.  Two
 // complex lines are live at a time, as there.
-template <int N>
-__global__ __launch_bounds__(kT) void ps_row_adj_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a) {
+// SCALAR (a PsAdjGrad is then the last argument; restatement: tests/pspec_scalar_adjoint_oracle.py).  With mu the cotangent of a stage's N_theta beside kappa, that of its N_w:
+//     r_w     = M [u kappa_x + v kappa_y]^ - M [kappa_x w_y - kappa_y w_x + mu_x (theta_y + Gy) - mu_y (theta_x + Gx)]^ / |k|^2
+//     r_theta = M_theta [u mu_x + v mu_y - by kappa_x + bx kappa_y]^
+// Five inverse transforms along y (G fields 0-3: u, v, w_x, w_y; 4, 5: grad kappa; 6, 7: grad theta; 8, 9: grad mu), three products, three
+// forward transforms, the kept modes to Ph fields 0 (u . grad kappa), 1 (the sum the inverse Laplacian takes) and 2 (the scalar's).  The
+// buoyancy's adjoint is linear in grad kappa, which the row holds in physical space: two fused multiply-adds, no transform; b = 0 is the
+// passive scalar's.  Three complex lines are live at a time: u, grad kappa and grad mu while the first and the third product leave, then the
+// line of u takes grad w and that of grad kappa takes grad theta.
+template <int N, bool SCALAR = false, typename... Gr>
+__global__ __launch_bounds__(kT) void ps_row_adj_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a, Gr... grad) {
+    static_assert(sizeof...(Gr) == (SCALAR ? 1 : 0), "the PsAdjGrad is the SCALAR kernel's argument");
     using L = PsLds<N>;
     constexpr int TPF = L::TPF;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -360,73 +369,48 @@ __global__ __launch_bounds__(kT) void ps_row_adj_kernel(const float2* __restrict
         __builtin_amdgcn_sched_barrier(0);
         ps_row_load2<N>(g0 + 4 * a.fstride, g0 + 5 * a.fstride, tid, my1, zk);       // kappa_x + i kappa_y: stays
         fft_line<float, N, true>(zk, tab, tab + N / 2, xb, tid);
+        if constexpr (!SCALAR) {
 #pragma unroll
-        for (int m = 0; m < 16; ++m) zu[m] = {zu[m].x * zk[m].x + zu[m].y * zk[m].y, 0.f};        // u kappa_x + v kappa_y
-        __builtin_amdgcn_sched_barrier(0);
-        fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
-        ps_row_store<N>(zu, Ph + (size_t)row * my1, tid, my1, valid);
-        __builtin_amdgcn_sched_barrier(0);
-        ps_row_load2<N>(g0 + 2 * a.fstride, g0 + 3 * a.fstride, tid, my1, zu);       // w_x + i w_y
-        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
+            for (int m = 0; m < 16; ++m) zu[m] = {zu[m].x * zk[m].x + zu[m].y * zk[m].y, 0.f};    // u kappa_x + v kappa_y
+            __builtin_amdgcn_sched_barrier(0);
+            fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
+            ps_row_store<N>(zu, Ph + (size_t)row * my1, tid, my1, valid);
+            __builtin_amdgcn_sched_barrier(0);
+            ps_row_load2<N>(g0 + 2 * a.fstride, g0 + 3 * a.fstride, tid, my1, zu);   // w_x + i w_y
+            fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
 #pragma unroll
-        for (int m = 0; m < 16; ++m) zu[m] = {zk[m].x * zu[m].y - zk[m].y * zu[m].x, 0.f};        // kappa_x w_y - kappa_y w_x
-        __builtin_amdgcn_sched_barrier(0);
-        fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
-        ps_row_store<N>(zu, Ph + a.fstride + (size_t)row * my1, tid, my1, valid);
-    }
-}
-
-// Its scalar twin (restatement: tests/pspec_scalar_adjoint_oracle.py).  With mu the cotangent of a stage's N_theta beside kappa, that of its N_w:
-//     r_w     = M [u kappa_x + v kappa_y]^ - M [kappa_x w_y - kappa_y w_x + mu_x (theta_y + Gy) - mu_y (theta_x + Gx)]^ / |k|^2
-//     r_theta = M_theta [u mu_x + v mu_y - by kappa_x + bx kappa_y]^
-// Five inverse transforms along y (G fields 0-3: u, v, w_x, w_y; 4, 5: grad kappa; 6, 7: grad theta; 8, 9: grad mu), three products, three
-// forward transforms, the kept modes to Ph fields 0 (u . grad kappa), 1 (the sum the inverse Laplacian takes) and 2 (the scalar's).  The
-// buoyancy's adjoint is linear in grad kappa, which the row holds in physical space: two fused multiply-adds, no transform; b = 0 is the
-// passive scalar's.  Three complex lines are live at a time: u, grad kappa and grad mu while the first and the third product leave, then the
-// line of u takes grad w and that of grad kappa takes grad theta.
-template <int N>
-__global__ __launch_bounds__(kT) void ps_row_adj_scalar_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a, PsAdjGrad gr) {
-    using L = PsLds<N>;
-    constexpr int TPF = L::TPF;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const cf* tab = ps_tables<N>(smem);
-    unsigned char* lines = smem + L::TAB_BYTES;
-    const int my1 = a.my1;
-    const long niter = (a.nlines + L::LINES - 1) / L::LINES;
-    for (long it = blockIdx.x; it < niter; it += gridDim.x) {
-#include "pspec_row_line.inc"
-        cf zu[16], zk[16], zm[16];
-        ps_row_load2<N>(g0, g0 + a.fstride, tid, my1, zu);                           // u + i v
-        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
-        __builtin_amdgcn_sched_barrier(0);
-        ps_row_load2<N>(g0 + 4 * a.fstride, g0 + 5 * a.fstride, tid, my1, zk);       // kappa_x + i kappa_y: stays
-        fft_line<float, N, true>(zk, tab, tab + N / 2, xb, tid);
+            for (int m = 0; m < 16; ++m) zu[m] = {zk[m].x * zu[m].y - zk[m].y * zu[m].x, 0.f};    // kappa_x w_y - kappa_y w_x
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            const PsAdjGrad gr = pick<PsAdjGrad>(grad...);
+            cf zm[16];
 #pragma unroll
-        for (int m = 0; m < 16; ++m) zm[m] = {zu[m].x * zk[m].x + zu[m].y * zk[m].y, 0.f};        // u kappa_x + v kappa_y: u, v stay
-        __builtin_amdgcn_sched_barrier(0);
-        fft_line<float, N, false>(zm, tab, tab + N / 2, xb, tid);
-        ps_row_store<N>(zm, Ph + (size_t)row * my1, tid, my1, valid);
-        __builtin_amdgcn_sched_barrier(0);
-        ps_row_load2<N>(g0 + 8 * a.fstride, g0 + 9 * a.fstride, tid, my1, zm);       // mu_x + i mu_y: stays
-        fft_line<float, N, true>(zm, tab, tab + N / 2, xb, tid);
+            for (int m = 0; m < 16; ++m) zm[m] = {zu[m].x * zk[m].x + zu[m].y * zk[m].y, 0.f};    // u kappa_x + v kappa_y: u, v stay
+            __builtin_amdgcn_sched_barrier(0);
+            fft_line<float, N, false>(zm, tab, tab + N / 2, xb, tid);
+            ps_row_store<N>(zm, Ph + (size_t)row * my1, tid, my1, valid);
+            __builtin_amdgcn_sched_barrier(0);
+            ps_row_load2<N>(g0 + 8 * a.fstride, g0 + 9 * a.fstride, tid, my1, zm);   // mu_x + i mu_y: stays
+            fft_line<float, N, true>(zm, tab, tab + N / 2, xb, tid);
 #pragma unroll
-        for (int m = 0; m < 16; ++m)                                                 // u mu_x + v mu_y - by kappa_x + bx kappa_y
-            zu[m] = {fmaf(zu[m].x, zm[m].x, fmaf(zu[m].y, zm[m].y, fmaf(-gr.by, zk[m].x, gr.bx * zk[m].y))), 0.f};
-        __builtin_amdgcn_sched_barrier(0);
-        fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
-        ps_row_store<N>(zu, Ph + 2 * a.fstride + (size_t)row * my1, tid, my1, valid);
-        __builtin_amdgcn_sched_barrier(0);
-        ps_row_load2<N>(g0 + 2 * a.fstride, g0 + 3 * a.fstride, tid, my1, zu);       // w_x + i w_y
-        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
+            for (int m = 0; m < 16; ++m)                                             // u mu_x + v mu_y - by kappa_x + bx kappa_y
+                zu[m] = {fmaf(zu[m].x, zm[m].x, fmaf(zu[m].y, zm[m].y, fmaf(-gr.by, zk[m].x, gr.bx * zk[m].y))), 0.f};
+            __builtin_amdgcn_sched_barrier(0);
+            fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
+            ps_row_store<N>(zu, Ph + 2 * a.fstride + (size_t)row * my1, tid, my1, valid);
+            __builtin_amdgcn_sched_barrier(0);
+            ps_row_load2<N>(g0 + 2 * a.fstride, g0 + 3 * a.fstride, tid, my1, zu);   // w_x + i w_y
+            fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
 #pragma unroll
-        for (int m = 0; m < 16; ++m) zu[m] = {zk[m].x * zu[m].y - zk[m].y * zu[m].x, 0.f};        // kappa_x w_y - kappa_y w_x
-        __builtin_amdgcn_sched_barrier(0);
-        ps_row_load2<N>(g0 + 6 * a.fstride, g0 + 7 * a.fstride, tid, my1, zk);       // theta_x + i theta_y
-        fft_line<float, N, true>(zk, tab, tab + N / 2, xb, tid);
+            for (int m = 0; m < 16; ++m) zu[m] = {zk[m].x * zu[m].y - zk[m].y * zu[m].x, 0.f};    // kappa_x w_y - kappa_y w_x
+            __builtin_amdgcn_sched_barrier(0);
+            ps_row_load2<N>(g0 + 6 * a.fstride, g0 + 7 * a.fstride, tid, my1, zk);   // theta_x + i theta_y
+            fft_line<float, N, true>(zk, tab, tab + N / 2, xb, tid);
 #pragma unroll
-        for (int m = 0; m < 16; ++m)                                                 // + mu_x (theta_y + Gy) - mu_y (theta_x + Gx)
-            zu[m].x = fmaf(zm[m].x, zk[m].y + gr.gy, fmaf(-zm[m].y, zk[m].x + gr.gx, zu[m].x));
-        __builtin_amdgcn_sched_barrier(0);
+            for (int m = 0; m < 16; ++m)                                             // + mu_x (theta_y + Gy) - mu_y (theta_x + Gx)
+                zu[m].x = fmaf(zm[m].x, zk[m].y + gr.gy, fmaf(-zm[m].y, zk[m].x + gr.gx, zu[m].x));
+            __builtin_amdgcn_sched_barrier(0);
+        }
         fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tid);
         ps_row_store<N>(zu, Ph + a.fstride + (size_t)row * my1, tid, my1, valid);
     }
@@ -443,137 +427,23 @@ __global__ __launch_bounds__(kT) void ps_row_adj_scalar_kernel(const float2* __r
 // gbar += kappa in every stage that makes one.  lam, wbar and gbar are lane-owned and coalesced, like W / A.  Preparing: the four spectra of
 // the state (ad.state, the forward's field<0..3>: pspec_field.inc, the mean in the (0, 0) mode) inverse-transformed along x to G fields 0-3, and
 // i kx kappa^, i ky kappa^ to G fields 4 and 5 (these first: kappa's registers are free before the state is loaded).
-// These recurrences have a second copy: the vorticity's pass of ps_col_adj_scalar_kernel (pspec_col_adj_pass.inc with TH = false), kept apart so
-// that this kernel's code stays what it was.  A fix to either belongs in both.
-template <int N, int S>
-__global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, const float* __restrict__ mean,
-                                                        PsArgs a, PsAdj ad) {
-    static_assert(S >= 0 && S <= 4, "adjoint stages 4 .. 0");
-    using L = PsLds<N>;
-    constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const cf* tab = ps_tables<N>(smem);
-    unsigned char* lines = smem + L::TAB_BYTES;
-    const int my1 = a.my1;
-    const long ntiles = (a.nlines + CW - 1) / CW;
-    const float dt = a.dt, dt2 = 0.5f * dt, dt3 = dt / 3.f, dt6 = dt / 6.f;
-    for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        int tx = threadIdx.x;
-        asm volatile("" : "+v"(tx));
-#include "pspec_col_tile.inc"
-        int tv = tid;
-        asm volatile("" : "+v"(tv));
-        const float ky = a.ky1 * (float)lj;
-        // Ph's field `ph` of the tile through the LDS transpose, forward-transformed along x
-        auto consume = [&](const float2* ph, cf (&z)[16]) {
-#include "pspec_stage.inc"
-        };
-        [[maybe_unused]] cf kap[16];
-        if constexpr (S < 4) {
-            cf r[16], z[16];
-            consume(Ph, r);
-            __syncthreads();                        // the next staging overwrites line images other waves may still read
-            consume(Ph + a.fstride, z);
-            int te = tv;
-            asm volatile("" : "+v"(te), "+v"(z[0].x));
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                const int e = te + TPF * m;
-                const int mx = m < 8 ? e : e - N;
-                const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (mx | lj) != 0;
-                const float kx = a.kx1 * (float)mx;
-                const float k2 = kx * kx + ky * ky;
-                const float x = a.hnudt * k2 - ad.hdrag;                             // L dt / 2
-                const float em1 = expm1f(x), em2 = expm1f(2.f * x);
-                const float ik2 = k2 > 0.f ? 1.f / k2 : 0.f;
-                const cf rr = keep ? cf{fmaf(-ik2, z[m].x, r[m].x), fmaf(-ik2, z[m].y, r[m].y)} : cf{0.f, 0.f};
-                const size_t si = wbase + e;
-                const float2 l2 = lok ? ad.lam[si] : make_float2(0.f, 0.f);
-                const cf lam = keep ? cf{l2.x, l2.y} : cf{0.f, 0.f};
-                cf wb;
-                if constexpr (S == 3) {
-                    wb = scal(em2, cf{lam.x + rr.x, lam.y + rr.y});
-                    kap[m] = scal(em1, axpy(dt, rr, cf{dt3 * lam.x, dt3 * lam.y}));
-                } else {
-                    const float2 w2 = lok ? ad.wbar[si] : make_float2(0.f, 0.f);
-                    if constexpr (S == 0) {
-                        wb = {w2.x + rr.x, w2.y + rr.y};
-                    } else {
-                        const cf er = scal(em1, rr);
-                        wb = {w2.x + er.x, w2.y + er.y};
-                        if constexpr (S == 2) {
-                            const cf el = scal(em1, lam);
-                            kap[m] = axpy(dt2, rr, cf{dt3 * el.x, dt3 * el.y});
-                        } else {
-                            const cf el = scal(em2, lam);
-                            kap[m] = axpy(dt2, er, cf{dt6 * el.x, dt6 * el.y});
-                        }
-                    }
-                }
-                if (lok) {
-                    if constexpr (S == 0) {
-                        ad.lam[si] = make_float2(wb.x, wb.y);
-                    } else {
-                        ad.wbar[si] = make_float2(wb.x, wb.y);
-                        if (ad.gbar) {
-                            const float2 g2 = ad.gbar[si];
-                            ad.gbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
-                        }
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                const int e = tv + TPF * m;
-                const int mx = m < 8 ? e : e - N;
-                const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (mx | lj) != 0;
-                const size_t si = wbase + e;
-                const float2 l2 = lok ? ad.lam[si] : make_float2(0.f, 0.f);
-                kap[m] = keep ? cf{dt6 * l2.x, dt6 * l2.y} : cf{0.f, 0.f};
-                if (lok && ad.gbar) {
-                    const float2 g2 = ad.ginit ? make_float2(0.f, 0.f) : ad.gbar[si];
-                    ad.gbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
-                }
-            }
-        }
-        if constexpr (S >= 1) {
-            const float U0 = lok ? mean[2 * lb] : 0.f, V0 = lok ? mean[2 * lb + 1] : 0.f;
-            // field F of the spectrum y, transformed along x and written to G through the LDS transpose: ps_col_kernel's, without its pin of y
-            auto field = [&](auto fc, const cf (&y)[16]) {
-                constexpr int F = decltype(fc)::value;
-                int te = tv;
-                asm volatile("" : "+v"(te));
-#include "pspec_field.inc"
-            };
-            static_for<4, 6>([&](auto fc) { field(fc, kap); });
-            cf y[16];
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                const float2 w = lok ? ad.state[wbase + tv + TPF * m] : make_float2(0.f, 0.f);
-                y[m] = {w.x, w.y};
-            }
-            static_for<0, 4>([&](auto fc) { field(fc, y); });
-        } else {
-            __syncthreads();                        // the next staging overwrites line images other waves may still read
-        }
-    }
-}
-
-// Its scalar twin: after the vorticity's work on a tile the same sequence runs on the scalar (pspec_col_adj_pass.inc, once per spectrum), with
+// With a PsAdjScalar (the scalar and the buoyant step; restatement: tests/pspec_scalar_adjoint_oracle.py) the same sequence runs on the scalar
+// after the vorticity's work on a tile (pspec_col_adj_pass.inc holds the recurrences, included once per spectrum), with
 // E_theta = exp(-kappa |k|^2 dt / 2) and mu, m, thetabar where the vorticity has E, lam, kappa, wbar:
 //     S = 4                                             m4 = dt/6 mu
 //     S = 3   thetabar  = E_theta^2 (mu + r_theta)      m3 = dt/3 E_theta mu + dt E_theta r_theta
 //     S = 2   thetabar += E_theta r_theta               m2 = dt/3 E_theta mu + dt/2 r_theta
 //     S = 1   thetabar += E_theta r_theta               m1 = dt/6 E_theta^2 mu + dt/2 E_theta r_theta
 //     S = 0   mu        = thetabar + r_theta
-// r_w takes Ph fields 0 and 1 as in ps_col_adj_kernel (field 1 now also holds the scalar's share), r_theta = keep_theta ? Ph field 2 : 0.
+// r_w takes Ph fields 0 and 1 as without the scalar (field 1 now also holds the scalar's share), r_theta = keep_theta ? Ph field 2 : 0.
 // Preparing: i kx kappa^, i ky kappa^ to G fields 4 and 5 and i kx m^, i ky m^ to 8 and 9 (each while its registers are still there), then the
 // state's four spectra to G fields 0-3 and i kx theta^, i ky theta^ of the state's scalar to 6 and 7.  One spectrum's registers at a time.
-template <int N, int S>
-__global__ __launch_bounds__(kT) void ps_col_adj_scalar_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, const float* __restrict__ mean,
-                                                               PsArgs a, PsAdjScalar ad) {
+template <int N, int S, typename Ad>
+__global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, const float* __restrict__ mean,
+                                                        PsArgs a, Ad ad) {
     static_assert(S >= 0 && S <= 4, "adjoint stages 4 .. 0");
+    constexpr bool SCALAR = std::is_same_v<Ad, PsAdjScalar>;
+    static_assert(SCALAR || std::is_same_v<Ad, PsAdj>, "a PsAdj, or a PsAdjScalar for the step with a scalar");
     using L = PsLds<N>;
     constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -594,7 +464,7 @@ __global__ __launch_bounds__(kT) void ps_col_adj_scalar_kernel(const float2* __r
 #include "pspec_stage.inc"
         };
         [[maybe_unused]] const float U0 = S >= 1 && lok ? mean[2 * lb] : 0.f, V0 = S >= 1 && lok ? mean[2 * lb + 1] : 0.f;
-        // field F of the spectrum y, transformed along x and written to G through the LDS transpose: ps_col_adj_kernel's
+        // field F of the spectrum y, transformed along x and written to G through the LDS transpose: ps_col_kernel's, without its pin of y
         [[maybe_unused]] auto field = [&](auto fc, const cf (&y)[16]) {
             constexpr int F = decltype(fc)::value;
             int te = tv;
@@ -605,7 +475,7 @@ __global__ __launch_bounds__(kT) void ps_col_adj_scalar_kernel(const float2* __r
             constexpr bool TH = false;
 #include "pspec_col_adj_pass.inc"
         }
-        {
+        if constexpr (SCALAR) {
             constexpr bool TH = true;
 #include "pspec_col_adj_pass.inc"
         }
@@ -613,16 +483,18 @@ __global__ __launch_bounds__(kT) void ps_col_adj_scalar_kernel(const float2* __r
             cf y[16];
 #pragma unroll
             for (int m = 0; m < 16; ++m) {
-                const float2 w = lok ? ad.w.state[wbase + tv + TPF * m] : make_float2(0.f, 0.f);
+                const float2 w = lok ? ad.state[wbase + tv + TPF * m] : make_float2(0.f, 0.f);
                 y[m] = {w.x, w.y};
             }
             static_for<0, 4>([&](auto fc) { field(fc, y); });
+            if constexpr (SCALAR) {
 #pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                const float2 w = lok ? ad.tstate[wbase + tv + TPF * m] : make_float2(0.f, 0.f);
-                y[m] = {w.x, w.y};
+                for (int m = 0; m < 16; ++m) {
+                    const float2 w = lok ? ad.tstate[wbase + tv + TPF * m] : make_float2(0.f, 0.f);
+                    y[m] = {w.x, w.y};
+                }
+                static_for<6, 8>([&](auto fc) { field(fc, y); });
             }
-            static_for<6, 8>([&](auto fc) { field(fc, y); });
         }
     }
 }
@@ -1109,63 +981,36 @@ int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, c
     return with_stage<0, 4>(S, stage);
 }
 
-// Stage S = 1..3 of the adjoint's recomputation: the plain or the forced kernel with the stage store (launch_col_stage never names this form)
-template <int N>
-int launch_col_keep(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, const PsForce* fc,
-                    float2* stage, hipStream_t s) {
-    const PsKeep ke{stage};
+// Stage S = 1..3 of the adjoint's recomputation: the plain or the forced kernel with the stage store (launch_col_stage never names this form).
+// ke: a PsKeep, or with a scalar the PsScalar and a PsKeepScalar
+template <int N, typename... Ke>
+int launch_col_keep(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, const PsForce* fc, hipStream_t s,
+                    Ke... ke) {
     auto go = [&](auto stage_c) {
         constexpr int K = decltype(stage_c)::value;
-        return fc ? launch_col<N, K, true>(Ph, G, W, A, mean, a, 1, fc, s, ke) : launch_col<N, K, false>(Ph, G, W, A, mean, a, 1, fc, s, ke);
+        return fc ? launch_col<N, K, true>(Ph, G, W, A, mean, a, 1, fc, s, ke...) : launch_col<N, K, false>(Ph, G, W, A, mean, a, 1, fc, s, ke...);
     };
     return with_stage<1, 3>(S, go);
 }
 
-// The same with a scalar: the SCALAR kernels, whose pack is the PsScalar and a PsKeepScalar
-template <int N>
-int launch_col_keep_scalar(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, const PsForce* fc,
-                           const PsScalar& sc, const PsKeepScalar& ke, hipStream_t s) {
-    auto go = [&](auto stage_c) {
-        constexpr int K = decltype(stage_c)::value;
-        return fc ? launch_col<N, K, true>(Ph, G, W, A, mean, a, 1, fc, s, sc, ke) : launch_col<N, K, false>(Ph, G, W, A, mean, a, 1, fc, s, sc, ke);
-    };
-    return with_stage<1, 3>(S, go);
-}
-
-template <int N>
-int launch_row_adj_scalar(const float2* G, float2* Ph, const PsArgs& a, const PsAdjGrad& gr, hipStream_t s) {
-    constexpr auto kern = ps_row_adj_scalar_kernel<N>;
+// gr: nothing, or with a scalar a PsAdjGrad
+template <int N, typename... Gr>
+int launch_row_adj(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s, Gr... gr) {
+    constexpr bool SC = sizeof...(Gr) == 1;
+    constexpr auto kern = ps_row_adj_kernel<N, SC, Gr...>;
     if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a, gr);
-    return check_launch("spec_ns scalar adjoint row pass");
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a, gr...);
+    return check_launch(SC ? "spec_ns scalar adjoint row pass" : "spec_ns adjoint row pass");
 }
 
-template <int N>
-int launch_col_adj_scalar(int S, const float2* Ph, float2* G, const float* mean, const PsArgs& a, const PsAdjScalar& ad, hipStream_t s) {
+// ad: a PsAdj, or with a scalar a PsAdjScalar
+template <int N, typename Ad>
+int launch_col_adj(int S, const float2* Ph, float2* G, const float* mean, const PsArgs& a, const Ad& ad, hipStream_t s) {
     auto go = [&](auto stage_c) {
-        constexpr auto kern = ps_col_adj_scalar_kernel<N, decltype(stage_c)::value>;
+        constexpr auto kern = ps_col_adj_kernel<N, decltype(stage_c)::value, Ad>;
         if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
         hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, mean, a, ad);
-        return check_launch("spec_ns scalar adjoint column pass");
-    };
-    return with_stage<0, 4>(S, go);
-}
-
-template <int N>
-int launch_row_adj(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s) {
-    constexpr auto kern = ps_row_adj_kernel<N>;
-    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a);
-    return check_launch("spec_ns adjoint row pass");
-}
-
-template <int N>
-int launch_col_adj(int S, const float2* Ph, float2* G, const float* mean, const PsArgs& a, const PsAdj& ad, hipStream_t s) {
-    auto go = [&](auto stage_c) {
-        constexpr auto kern = ps_col_adj_kernel<N, decltype(stage_c)::value>;
-        if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
-        hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, mean, a, ad);
-        return check_launch("spec_ns adjoint column pass");
+        return check_launch(std::is_same_v<Ad, PsAdjScalar> ? "spec_ns scalar adjoint column pass" : "spec_ns adjoint column pass");
     };
     return with_stage<0, 4>(S, go);
 }
@@ -1188,35 +1033,42 @@ size_t scalar_work_bytes(int batch, int nx, int ny) {
     return st > b ? st : b;
 }
 
-// the adjoint's A, wbar, G[6], Ph[2] (the scalar step's layout, wbar in A_theta's place) and the stage states s1, s2, s3: 13 compacted fields
-size_t adjoint_work_bytes(int batch, int nx, int ny) {
-    const size_t b = work_bytes(batch, nx, ny), st = (size_t)13 * batch * nx * kept_y(ny) * sizeof(float2);
+// A layout of work in compacted fields of fstride complex each, in this order: the accumulators, G, Ph, the adjoint's kept stage states.
+//   the step:            A, G[4], Ph;   with a scalar A, A_theta, G[6], Ph[2]
+//   the flow's adjoint:  A, wbar in A_theta's place, G[6], Ph[2] (the recomputation's launches use the first 4 and 1 of them), s1, s2, s3: 13
+//   the scalar adjoint:  A, A_theta (wbar and thetabar once the stages are recomputed), G[10], Ph[3] (the recomputation's: 6 and 2), s1, s2, s3
+//                        of w^, then of theta^: 21
+struct PsLayout {
+    int acc, g, ph, keep;
+    constexpr int fields() const { return acc + g + ph + keep; }
+};
+constexpr PsLayout kLayFlow{1, 4, 1, 0}, kLayScalar{2, 6, 2, 0}, kLayAdjoint{2, 6, 2, 3}, kLayScalarAdjoint{2, 10, 3, 6};
+
+size_t layout_work_bytes(const PsLayout& lay, int batch, int nx, int ny) {
+    const size_t b = work_bytes(batch, nx, ny), st = (size_t)lay.fields() * batch * nx * kept_y(ny) * sizeof(float2);
     return st > b ? st : b;
 }
+size_t adjoint_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayAdjoint, batch, nx, ny); }
+size_t scalar_adjoint_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayScalarAdjoint, batch, nx, ny); }
 
-// the scalar adjoint's A, A_theta (wbar and thetabar once the stages are recomputed), G[10], Ph[3] and the stage states s1, s2, s3 of w^ and
-// of theta^: 21 compacted fields
-size_t scalar_adjoint_work_bytes(int batch, int nx, int ny) {
-    const size_t b = work_bytes(batch, nx, ny), st = (size_t)21 * batch * nx * kept_y(ny) * sizeof(float2);
-    return st > b ? st : b;
-}
-
-// The step's layout of work, compacted fields of fstride complex each: A, G[4], Ph; with a scalar A, A_theta, G[6], Ph[2]; and the arguments
-// of the column pass (col) and of the row pass (row).
+// The fields of a layout in work, and the arguments of the column pass (col) and of the row pass (row).
 struct PsWork {
-    float2 *A, *At, *G, *Ph;
+    float2 *A, *At, *G, *Ph, *keep;
     PsArgs col, row;
-    PsWork(void* work, int batch, int nx, int ny, bool scalar, double Lx, double Ly, float hnudt, float dt) {
+    PsWork(void* work, int batch, int nx, int ny, const PsLayout& lay, double Lx, double Ly, float hnudt, float dt) {
         const int my1 = kept_y(ny);
         const long fstride = (long)batch * nx * my1;
         A = static_cast<float2*>(work);
         At = A + fstride;
-        G = A + (scalar ? 2 : 1) * fstride;
-        Ph = G + (scalar ? 6 : 4) * fstride;
+        G = A + lay.acc * fstride;
+        Ph = G + lay.g * fstride;
+        keep = Ph + lay.ph * fstride;
         col = PsArgs{(long)batch * my1, fstride, my1, (float)(2.0 * M_PI / Lx), (float)(2.0 * M_PI / Ly), hnudt, dt, (float)(1.0 / ((double)nx * ny))};
         row = col;
         row.nlines = (long)batch * nx;
     }
+    PsWork(void* work, int batch, int nx, int ny, bool scalar, double Lx, double Ly, float hnudt, float dt)
+        : PsWork(work, batch, nx, ny, scalar ? kLayScalar : kLayFlow, Lx, Ly, hnudt, dt) {}
 };
 
 int check_lengths(const char* what, double Lx, double Ly) {
@@ -1543,55 +1395,93 @@ NNS_API int nns_spec_ns_adjoint_workspace(int batch, int nx, int ny, size_t* byt
     return NNS_OK;
 }
 
-// The reverse mode of spec_ns_step's forced form, last step first.  Per step: the stage states s1, s2, s3 recomputed from the step's saved start
-// spectrum by the forward's own launches (stage 0, then three row / column pairs whose column kernels also store the next stage's input: 7),
-// then the adjoint's stage 4 column launch and four row / column pairs (9).  No allocation, no host synchronisation.
-NNS_API int nns_spec_ns_step_adjoint_f32(const float* what0, const float* mean, const float* ghat, int gbatch, float* lam, float* gbar, void* work,
-                                         size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
-                                         int nsteps, void* stream) {
-    const char* who = "spec_ns_step_adjoint";
+// The reverse mode of spec_ns_step's steady forms, last step first; that0 == NULL: the forced flow's, else the scalar's and the buoyant one's
+// (b != 0), the scalar riding in the flow adjoint's launches.  Per step: the stage states s1, s2, s3 (of w^, and of theta^) recomputed from the
+// step's saved start spectra by the forward's own launches (stage 0, then three row / column pairs whose column kernels also store the next
+// stage's input: 7), then the adjoint's stage 4 column launch and four row / column pairs (9).  No allocation, no host synchronisation.
+static int spec_ns_step_adjoint(const char* who, const float* what0, const float* that0, const float* mean, const float* ghat, int gbatch,
+                                float* lam, float* mu, float* gbar, void* work, size_t work_bytes_, int batch, int nx, int ny, double Lx,
+                                double Ly, double dt, double nu, double drag, double kappa, double gx, double gy, double bx, double by,
+                                int nsteps, void* stream) {
+    const bool scalar = that0 != nullptr;
     if (!what0 || !mean || !lam || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
     if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
+    if (int rc = check_scalar_numbers(who, kappa, gx, gy)) return rc;
+    if (int rc = check_buoyancy(who, bx, by)) return rc;
     if (int rc = check_gbatch(who, ghat, gbatch, batch)) return rc;
-    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, kWorkAdjoint)) return rc;
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, scalar ? kWorkScalarAdjoint : kWorkAdjoint)) return rc;
+    hipStream_t s = as_stream(stream);
     if (nsteps == 0) {
         if (!gbar) return NNS_OK;
         void* zb[1] = {gbar};
         const long zn[1] = {(long)((size_t)batch * kept_y(ny) * nx * sizeof(float2))};
-        return zero_buffers(zb, zn, 1, as_stream(stream));
+        return zero_buffers(zb, zn, 1, s);
     }
-    hipStream_t s = as_stream(stream);
-    const PsWork L(work, batch, nx, ny, true, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);      // A, wbar (A_theta's place), G[6], Ph[2]
+    const PsWork L(work, batch, nx, ny, scalar ? kLayScalarAdjoint : kLayAdjoint, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);
     const long fstride = L.col.fstride;
-    float2* stages = L.Ph + 2 * fstride;                                                       // s1, s2, s3
+    float2* wstages = L.keep;                                                                  // s1, s2, s3 of w^
+    float2* tstages = scalar ? wstages + 3 * fstride : nullptr;                                // and of theta^
     const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
     const PsForce* fc = ghat || drag > 0 ? &force : nullptr;                                   // the forward's choice of kernels: its bits
-    PsAdj ad{reinterpret_cast<float2*>(lam), L.At, reinterpret_cast<float2*>(gbar), nullptr, force.hdrag, 0};
-    auto row = [&]() { return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row<decltype(n)::value>(L.G, L.Ph, L.row, s); }); };
-    auto row_adj = [&]() { return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row_adj<decltype(n)::value>(L.G, L.Ph, L.row, s); }); };
+    const float hkdt = (float)(-0.5 * kappa * dt);
+    const PsGrad grad{(float)gx, (float)gy};
+    const PsBuoyGrad buoy{(float)gx, (float)gy, (float)(-(double)ny * by), (float)((double)ny * bx)};
+    const bool buoyant = scalar && (bx != 0.0 || by != 0.0);
+    const PsAdjGrad agrad{(float)gx, (float)gy, (float)bx, (float)by};
+    // wbar and thetabar take the accumulators' places (PsLayout's note): the recomputation is over when adjoint stage 3 first writes them
+    PsAdjScalar ad{PsAdj{reinterpret_cast<float2*>(lam), scalar ? L.A : L.At, reinterpret_cast<float2*>(gbar), nullptr, force.hdrag, 0},
+                   reinterpret_cast<float2*>(mu), L.At, nullptr, hkdt};
+    auto row = [&]() {
+        return dispatch_pow2(ny, "spec_ns", [&](auto n) {
+            constexpr int N = decltype(n)::value;
+            return buoyant ? launch_row<N>(L.G, L.Ph, L.row, s, buoy) : scalar ? launch_row<N>(L.G, L.Ph, L.row, s, grad) : launch_row<N>(L.G, L.Ph, L.row, s);
+        });
+    };
+    auto row_adj = [&]() {
+        return dispatch_pow2(ny, "spec_ns", [&](auto n) {
+            constexpr int N = decltype(n)::value;
+            return scalar ? launch_row_adj<N>(L.G, L.Ph, L.row, s, agrad) : launch_row_adj<N>(L.G, L.Ph, L.row, s);
+        });
+    };
     for (int k = nsteps - 1; k >= 0; --k) {
-        float2* W = const_cast<float2*>(reinterpret_cast<const float2*>(what0)) + (size_t)k * fstride;      // stages 0-3 only read W
+        float2* W = const_cast<float2*>(reinterpret_cast<const float2*>(what0)) + (size_t)k * fstride;      // stages 0-3 only read W and T
+        float2* T = scalar ? const_cast<float2*>(reinterpret_cast<const float2*>(that0)) + (size_t)k * fstride : nullptr;
+        const PsScalar sc{T, L.At, hkdt};
         if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
-                return launch_col_stage<decltype(n)::value>(0, L.Ph, L.G, W, L.A, mean, L.col, 1, nullptr, nullptr, s);
+                return launch_col_stage<decltype(n)::value>(0, L.Ph, L.G, W, L.A, mean, L.col, 1, nullptr, scalar ? &sc : nullptr, s);
             }))
             return rc;
         for (int S = 1; S <= 3; ++S) {
             if (int rc = row()) return rc;
+            const size_t off = (size_t)(S - 1) * fstride;
             if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
-                    return launch_col_keep<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, fc, stages + (size_t)(S - 1) * fstride, s);
+                    constexpr int N = decltype(n)::value;
+                    return scalar ? launch_col_keep<N>(S, L.Ph, L.G, W, L.A, mean, L.col, fc, s, sc, PsKeepScalar{wstages + off, tstages + off})
+                                  : launch_col_keep<N>(S, L.Ph, L.G, W, L.A, mean, L.col, fc, s, PsKeep{wstages + off});
                 }))
                 return rc;
         }
         for (int S = 4; S >= 0; --S) {
             if (S < 4)
                 if (int rc = row_adj()) return rc;
-            ad.state = S >= 2 ? stages + (size_t)(S - 2) * fstride : W;
+            ad.state = S >= 2 ? wstages + (size_t)(S - 2) * fstride : W;
+            ad.tstate = scalar && S >= 2 ? tstages + (size_t)(S - 2) * fstride : T;
             ad.ginit = k == nsteps - 1;
-            if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_adj<decltype(n)::value>(S, L.Ph, L.G, mean, L.col, ad, s); }))
+            if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
+                    constexpr int N = decltype(n)::value;
+                    return scalar ? launch_col_adj<N>(S, L.Ph, L.G, mean, L.col, ad, s) : launch_col_adj<N, PsAdj>(S, L.Ph, L.G, mean, L.col, ad, s);
+                }))
                 return rc;
         }
     }
     return NNS_OK;
+}
+
+NNS_API int nns_spec_ns_step_adjoint_f32(const float* what0, const float* mean, const float* ghat, int gbatch, float* lam, float* gbar, void* work,
+                                         size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
+                                         int nsteps, void* stream) {
+    return spec_ns_step_adjoint("spec_ns_step_adjoint", what0, nullptr, mean, ghat, gbatch, lam, nullptr, gbar, work, work_bytes_, batch, nx, ny, Lx,
+                                Ly, dt, nu, drag, 0.0, 0.0, 0.0, 0.0, 0.0, nsteps, stream);
 }
 
 NNS_API int nns_spec_ns_scalar_adjoint_workspace(int batch, int nx, int ny, size_t* bytes) {
@@ -1602,78 +1492,13 @@ NNS_API int nns_spec_ns_scalar_adjoint_workspace(int batch, int nx, int ny, size
     return NNS_OK;
 }
 
-// The reverse mode of spec_ns_step's scalar and buoyant forms, last step first: nns_spec_ns_step_adjoint_f32 with the scalar riding in its
-// launches.  Per step the stage states of w^ and theta^ are recomputed from the saved pair by the forward's own launches (b != 0: the buoyant
-// row kernel), stages 1-3 with the PsKeepScalar (7); then ps_col_adj_scalar_kernel, S = 4 .. 0, and ps_row_adj_scalar_kernel between them (9).
 NNS_API int nns_spec_ns_step_scalar_adjoint_f32(const float* what0, const float* that0, const float* mean, const float* ghat, int gbatch,
                                                 float* lam, float* mu, float* gbar, void* work, size_t work_bytes_, int batch, int nx, int ny,
                                                 double Lx, double Ly, double dt, double nu, double drag, double kappa, double gx, double gy,
                                                 double bx, double by, int nsteps, void* stream) {
-    const char* who = "spec_ns_step_scalar_adjoint";
-    if (!what0 || !that0 || !mean || !lam || !mu || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
-    if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
-    if (int rc = check_scalar_numbers(who, kappa, gx, gy)) return rc;
-    if (int rc = check_buoyancy(who, bx, by)) return rc;
-    if (int rc = check_gbatch(who, ghat, gbatch, batch)) return rc;
-    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, kWorkScalarAdjoint)) return rc;
-    if (nsteps == 0) {
-        if (!gbar) return NNS_OK;
-        void* zb[1] = {gbar};
-        const long zn[1] = {(long)((size_t)batch * kept_y(ny) * nx * sizeof(float2))};
-        return zero_buffers(zb, zn, 1, as_stream(stream));
-    }
-    hipStream_t s = as_stream(stream);
-    PsWork L(work, batch, nx, ny, true, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);           // A, A_theta, then G[10], Ph[3] (the forward's
-    const long fstride = L.col.fstride;                                                        // launches use the first 6 and 2 of them)
-    L.Ph = L.G + 10 * fstride;
-    float2* wstages = L.Ph + 3 * fstride;                                                      // s1, s2, s3 of w^
-    float2* tstages = wstages + 3 * fstride;                                                   // and of theta^
-    const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
-    const PsForce* fc = ghat || drag > 0 ? &force : nullptr;                                   // the forward's choice of kernels: its bits
-    const float hkdt = (float)(-0.5 * kappa * dt);
-    const PsGrad grad{(float)gx, (float)gy};
-    const PsBuoyGrad buoy{(float)gx, (float)gy, (float)(-(double)ny * by), (float)((double)ny * bx)};
-    const bool buoyant = bx != 0.0 || by != 0.0;
-    const PsAdjGrad agrad{(float)gx, (float)gy, (float)bx, (float)by};
-    // wbar and thetabar take the accumulators' places: the recomputation is over when adjoint stage 3 first writes them
-    PsAdjScalar ad{PsAdj{reinterpret_cast<float2*>(lam), L.A, reinterpret_cast<float2*>(gbar), nullptr, force.hdrag, 0},
-                   reinterpret_cast<float2*>(mu), L.At, nullptr, hkdt};
-    auto row = [&]() {
-        return dispatch_pow2(ny, "spec_ns", [&](auto n) {
-            constexpr int N = decltype(n)::value;
-            return buoyant ? launch_row<N>(L.G, L.Ph, L.row, s, buoy) : launch_row<N>(L.G, L.Ph, L.row, s, grad);
-        });
-    };
-    auto row_adj = [&]() {
-        return dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row_adj_scalar<decltype(n)::value>(L.G, L.Ph, L.row, agrad, s); });
-    };
-    for (int k = nsteps - 1; k >= 0; --k) {
-        float2* W = const_cast<float2*>(reinterpret_cast<const float2*>(what0)) + (size_t)k * fstride;      // stages 0-3 only read W and T
-        float2* T = const_cast<float2*>(reinterpret_cast<const float2*>(that0)) + (size_t)k * fstride;
-        const PsScalar scalar{T, L.At, hkdt};
-        if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
-                return launch_col_stage<decltype(n)::value>(0, L.Ph, L.G, W, L.A, mean, L.col, 1, nullptr, &scalar, s);
-            }))
-            return rc;
-        for (int S = 1; S <= 3; ++S) {
-            if (int rc = row()) return rc;
-            const PsKeepScalar ke{wstages + (size_t)(S - 1) * fstride, tstages + (size_t)(S - 1) * fstride};
-            if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
-                    return launch_col_keep_scalar<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, fc, scalar, ke, s);
-                }))
-                return rc;
-        }
-        for (int S = 4; S >= 0; --S) {
-            if (S < 4)
-                if (int rc = row_adj()) return rc;
-            ad.w.state = S >= 2 ? wstages + (size_t)(S - 2) * fstride : W;
-            ad.tstate = S >= 2 ? tstages + (size_t)(S - 2) * fstride : T;
-            ad.w.ginit = k == nsteps - 1;
-            if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_adj_scalar<decltype(n)::value>(S, L.Ph, L.G, mean, L.col, ad, s); }))
-                return rc;
-        }
-    }
-    return NNS_OK;
+    if (!that0 || !mu) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_scalar_adjoint: NULL pointer or batch < 1");
+    return spec_ns_step_adjoint("spec_ns_step_scalar_adjoint", what0, that0, mean, ghat, gbatch, lam, mu, gbar, work, work_bytes_, batch, nx, ny,
+                                Lx, Ly, dt, nu, drag, kappa, gx, gy, bx, by, nsteps, stream);
 }
 
 NNS_API int nns_spec_ns_scalar_workspace(int batch, int nx, int ny, size_t* bytes) {

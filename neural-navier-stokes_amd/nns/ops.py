@@ -1306,6 +1306,21 @@ def spec_ns_adjoint_workspace(B, nx, ny):
     return _query_bytes('nns_spec_ns_adjoint_workspace', int(B), int(nx), int(ny))
 
 
+def _spec_ns_adjoint_tensors(who, lam, ghat, gbar, **starts):
+    """gbatch of an adjoint call after the checks of its start spectra (what0, that0: [nsteps] + lam's shape, equal nsteps), ghat and gbar."""
+    nsteps = None
+    for name, t in starts.items():
+        _f32(t)
+        nsteps = t.shape[0] if nsteps is None and t.dim() else nsteps
+        if t.dim() != 5 or tuple(t.shape[1:]) != tuple(lam.shape) or t.device != lam.device or t.shape[0] != nsteps:
+            raise ValueError("%s: %s must be float32 [nsteps, %d, %d, %d, 2] on the state's device, got %s"
+                             % ((who, name) + tuple(lam.shape[:3]) + (tuple(t.shape),)))
+    gbatch = _spec_ns_force(who, ghat, lam)
+    if gbar is not None:
+        _spec_ns_same(who, gbar, lam)
+    return gbatch
+
+
 def spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, work, ny, Lx, Ly, dt, nu, drag):
     """The vector-Jacobian product of the nsteps forced steps whose start spectra are what0 (float32 [nsteps, B, my1, nx, 2], only read): lam
     ([B, my1, nx, 2]) holds, in, the cotangent of the state after the last step and, out, that of the state before the first; gbar (the same
@@ -1314,12 +1329,7 @@ def spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, work, ny, Lx, Ly, dt, nu
     synchronisation."""
     who = 'spec_ns_step_adjoint_'
     B, my1, nx = _spec_ns_state(who, lam, mean, work, ny)
-    _f32(what0)
-    if what0.dim() != 5 or tuple(what0.shape[1:]) != tuple(lam.shape) or what0.device != lam.device:
-        raise ValueError("%s: what0 must be float32 [nsteps, %d, %d, %d, 2] on the state's device, got %s" % (who, B, my1, nx, tuple(what0.shape)))
-    gbatch = _spec_ns_force(who, ghat, lam)
-    if gbar is not None:
-        _spec_ns_same(who, gbar, lam)
+    gbatch = _spec_ns_adjoint_tensors(who, lam, ghat, gbar, what0=what0)
     check(_lib.lib().nns_spec_ns_step_adjoint_f32(_p(what0), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(lam),
                                                   None if gbar is None else _p(gbar), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly),
                                                   float(dt), float(nu), float(drag), int(what0.shape[0]), _stream()), 'nns_spec_ns_step_adjoint_f32')
@@ -1342,13 +1352,7 @@ def spec_ns_step_scalar_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, 
     who = 'spec_ns_step_scalar_adjoint_'
     B, my1, nx = _spec_ns_state(who, lam, mean, work, ny)
     _spec_ns_same(who, mu, lam)
-    for name, t in (('what0', what0), ('that0', that0)):
-        _f32(t)
-        if t.dim() != 5 or tuple(t.shape[1:]) != tuple(lam.shape) or t.device != lam.device or t.shape[0] != what0.shape[0]:
-            raise ValueError("%s: %s must be float32 [nsteps, %d, %d, %d, 2] on the state's device, got %s" % (who, name, B, my1, nx, tuple(t.shape)))
-    gbatch = _spec_ns_force(who, ghat, lam)
-    if gbar is not None:
-        _spec_ns_same(who, gbar, lam)
+    gbatch = _spec_ns_adjoint_tensors(who, lam, ghat, gbar, what0=what0, that0=that0)
     (gx, gy), (bx, by) = grad, buoyancy
     check(_lib.lib().nns_spec_ns_step_scalar_adjoint_f32(_p(what0), _p(that0), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(lam), _p(mu),
                                                          None if gbar is None else _p(gbar), _p(work), work.numel(), B, nx, int(ny), float(Lx),

@@ -178,53 +178,79 @@ class PeriodicState(object):
 
 
 class _AdvanceFn(torch.autograd.Function):
-    """``PeriodicSolver.advance`` / ``advance_velocity`` as one autograd node: forward the solver's own step on a fresh state, with the spectrum at
-    the start of every step kept (one device copy between one-step calls: the step itself is untouched); backward the adjoint call
-    (ops.spec_ns_step_adjoint_) between the compact and expand kernels.  ``velocity``: the ends are init / fields instead of the vorticity's."""
+    """``PeriodicSolver.advance`` / ``advance_velocity`` and, with ``scalar``, ``advance_scalar`` / ``advance_velocity_scalar`` as one autograd
+    node: forward the solver's own step on a fresh state (with a scalar the scalar step, the buoyant one with b != 0), with the spectra at the
+    start of every step kept (one device copy each between one-step calls: the step itself is untouched); backward the adjoint call
+    (ops.spec_ns_step_adjoint_ / ops.spec_ns_step_scalar_adjoint_) between the compact and expand kernels.  ``velocity``: the flow's ends are
+    init / fields instead of the vorticity's; theta's are spec_ns_scalar_init / spec_ns_scalar_field.  ``fields``: (w,) or (u0, v0), then
+    with ``scalar`` theta."""
 
     @staticmethod
-    def forward(ctx, solver, nsteps, mean, velocity, forcing, *fields):
+    def forward(ctx, solver, nsteps, mean, velocity, scalar, forcing, *fields):
         s = solver
+        theta = fields[-1].detach() if scalar else None
         if velocity:
-            state = s.init(fields[0].detach(), fields[1].detach())
+            state = s.init(fields[0].detach(), fields[1].detach(), theta)
         else:
             state = s.init_vorticity(fields[0].detach(), mean)
+            if scalar:
+                state.that = ops.spec_ns_scalar_init(s._field('theta', theta).contiguous(), torch.empty_like(state.what), state.work)
         ghat = s._force_of(state) if forcing is None else s._source_spectrum(forcing.detach(), state)
         what0 = torch.empty((nsteps,) + tuple(state.what.shape), dtype=torch.float32, device=state.what.device)
+        that0 = torch.empty_like(what0) if scalar else None
+        box = (state.mean, ghat, state.work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag)
         for k in range(nsteps):
             what0[k].copy_(state.what)
-            if ghat is not None or s.drag > 0:
-                ops.spec_ns_step_forced_(state.what, state.mean, ghat, state.work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag, 1)
+            if scalar:
+                that0[k].copy_(state.that)
+                if s._buoyant(state):
+                    ops.spec_ns_step_buoyant_(state.what, state.that, *box, s.kappa, s.scalar_gradient, s.buoyancy, 1)
+                else:
+                    ops.spec_ns_step_scalar_(state.what, state.that, *box, s.kappa, s.scalar_gradient, 1)
+            elif ghat is not None or s.drag > 0:
+                ops.spec_ns_step_forced_(state.what, *box, 1)
             else:
                 ops.spec_ns_step_(state.what, state.mean, state.work, s.ny, s.Lx, s.Ly, s.dt, s.nu, 1)
-        ctx.solver, ctx.velocity, ctx.squeeze = s, velocity, fields[0].dim() == 2
+        ctx.solver, ctx.velocity, ctx.scalar, ctx.squeeze = s, velocity, scalar, fields[0].dim() == 2
         ctx.shared = forcing is not None and forcing.shape[0] == 1 and state.batch > 1
         ctx.force_shape = None if forcing is None else tuple(forcing.shape)
-        ctx.save_for_backward(what0, state.mean, *(() if ghat is None else (ghat,)))
+        ctx.save_for_backward(what0, state.mean, *(t for t in (that0, ghat) if t is not None))
         out = s.fields(state)[:2] if velocity else (s.vorticity(state),)
+        if scalar:
+            out = tuple(out) + (s.scalar(state),)
         return tuple(o[0] for o in out) if ctx.squeeze else tuple(out)
 
     @staticmethod
     def backward(ctx, *gout):
         s = ctx.solver
         what0, mean = ctx.saved_tensors[:2]
-        ghat = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        rest = list(ctx.saved_tensors[2:])
+        that0 = rest.pop(0) if ctx.scalar else None
+        ghat = rest[0] if rest else None
         B, dev = what0.shape[1], what0.device
         shape = (B, s.nx, s.ny)
         gout = [torch.zeros(shape, dtype=torch.float32, device=dev) if g is None else g.reshape(shape).contiguous() for g in gout]
         zero = torch.zeros((B, 2), dtype=torch.float32, device=dev)
+        workspace = ops.spec_ns_scalar_adjoint_workspace if ctx.scalar else ops.spec_ns_adjoint_workspace
+        work = torch.empty(workspace(B, s.nx, s.ny), dtype=torch.uint8, device=dev)
         if ctx.velocity:                                  # K^T (ubar, vbar)^ = curl(ubar, vbar)^ / |k|^2
             lam = s.init(gout[0], gout[1]).what * s._k2_table(dev, -1)
         else:
             lam = s.init_vorticity(gout[0]).what
-        need_g = ctx.force_shape is not None and ctx.needs_input_grad[4]
+        need_g = ctx.force_shape is not None and ctx.needs_input_grad[5]
         gbar = torch.empty_like(lam) if need_g else None
-        work = torch.empty(ops.spec_ns_adjoint_workspace(B, s.nx, s.ny), dtype=torch.uint8, device=dev)
-        ops.spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag)
+        if ctx.scalar:
+            mu = ops.spec_ns_scalar_init(gout[-1], torch.empty_like(lam), work)
+            ops.spec_ns_step_scalar_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag, s.kappa,
+                                             s.scalar_gradient, s.buoyancy)
+        else:
+            ops.spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag)
         if ctx.velocity:                                  # init^T (lam) = (lam_y, -lam_x): the velocity of the streamfunction lam
-            grads = s.fields(PeriodicState(lam * s._k2_table(dev, 1), zero, work))[:2]
+            grads = tuple(s.fields(PeriodicState(lam * s._k2_table(dev, 1), zero, work))[:2])
         else:
             grads = (s.vorticity(PeriodicState(lam, zero, work)),)
+        if ctx.scalar:
+            grads = grads + (ops.spec_ns_scalar_field(mu, work, s.ny),)
         if ctx.squeeze:
             grads = tuple(g[0] for g in grads)
         gf = None
@@ -233,75 +259,7 @@ class _AdvanceFn(torch.autograd.Function):
             if ctx.shared:
                 gf = torch.sum(gf, dim=0, keepdim=True)
             gf = gf.reshape(ctx.force_shape)
-        return (None, None, None, None, gf) + tuple(grads)
-
-
-class _AdvanceScalarFn(torch.autograd.Function):
-    """``PeriodicSolver.advance_scalar`` / ``advance_velocity_scalar`` as one autograd node, _AdvanceFn's sibling for the system (w, theta): forward
-    the solver's own scalar step (the buoyant one with b != 0) on a fresh state, both spectra at the start of every step kept; backward the
-    adjoint call (ops.spec_ns_step_scalar_adjoint_) between the compact and expand kernels, theta's ends being spec_ns_scalar_init /
-    spec_ns_scalar_field.  ``fields``: (w, theta), or with ``velocity`` (u0, v0, theta0)."""
-
-    @staticmethod
-    def forward(ctx, solver, nsteps, mean, velocity, forcing, *fields):
-        s = solver
-        theta = fields[-1].detach()
-        if velocity:
-            state = s.init(fields[0].detach(), fields[1].detach(), theta)
-        else:
-            state = s.init_vorticity(fields[0].detach(), mean)
-            state.that = ops.spec_ns_scalar_init(s._field('theta', theta).contiguous(), torch.empty_like(state.what), state.work)
-        ghat = s._force_of(state) if forcing is None else s._source_spectrum(forcing.detach(), state)
-        what0 = torch.empty((nsteps,) + tuple(state.what.shape), dtype=torch.float32, device=state.what.device)
-        that0 = torch.empty_like(what0)
-        box = (state.mean, ghat, state.work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag, s.kappa, s.scalar_gradient)
-        for k in range(nsteps):
-            what0[k].copy_(state.what)
-            that0[k].copy_(state.that)
-            if s._buoyant(state):
-                ops.spec_ns_step_buoyant_(state.what, state.that, *box, s.buoyancy, 1)
-            else:
-                ops.spec_ns_step_scalar_(state.what, state.that, *box, 1)
-        ctx.solver, ctx.velocity, ctx.squeeze = s, velocity, fields[0].dim() == 2
-        ctx.shared = forcing is not None and forcing.shape[0] == 1 and state.batch > 1
-        ctx.force_shape = None if forcing is None else tuple(forcing.shape)
-        ctx.save_for_backward(what0, that0, state.mean, *(() if ghat is None else (ghat,)))
-        out = (s.fields(state)[:2] if velocity else (s.vorticity(state),)) + (s.scalar(state),)
-        return tuple(o[0] for o in out) if ctx.squeeze else tuple(out)
-
-    @staticmethod
-    def backward(ctx, *gout):
-        s = ctx.solver
-        what0, that0, mean = ctx.saved_tensors[:3]
-        ghat = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
-        B, dev = what0.shape[1], what0.device
-        shape = (B, s.nx, s.ny)
-        gout = [torch.zeros(shape, dtype=torch.float32, device=dev) if g is None else g.reshape(shape).contiguous() for g in gout]
-        zero = torch.zeros((B, 2), dtype=torch.float32, device=dev)
-        work = torch.empty(ops.spec_ns_scalar_adjoint_workspace(B, s.nx, s.ny), dtype=torch.uint8, device=dev)
-        if ctx.velocity:                                  # K^T (ubar, vbar)^ = curl(ubar, vbar)^ / |k|^2
-            lam = s.init(gout[0], gout[1]).what * s._k2_table(dev, -1)
-        else:
-            lam = s.init_vorticity(gout[0]).what
-        mu = ops.spec_ns_scalar_init(gout[-1], torch.empty_like(lam), work)
-        need_g = ctx.force_shape is not None and ctx.needs_input_grad[4]
-        gbar = torch.empty_like(lam) if need_g else None
-        ops.spec_ns_step_scalar_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag, s.kappa,
-                                         s.scalar_gradient, s.buoyancy)
-        if ctx.velocity:                                  # init^T (lam) = (lam_y, -lam_x): the velocity of the streamfunction lam
-            grads = s.fields(PeriodicState(lam * s._k2_table(dev, 1), zero, work))[:2]
-        else:
-            grads = (s.vorticity(PeriodicState(lam, zero, work)),)
-        grads = tuple(grads) + (ops.spec_ns_scalar_field(mu, work, s.ny),)
-        if ctx.squeeze:
-            grads = tuple(g[0] for g in grads)
-        gf = None
-        if need_g:
-            gf = s.vorticity(PeriodicState(gbar, zero, work))
-            if ctx.shared:
-                gf = torch.sum(gf, dim=0, keepdim=True)
-            gf = gf.reshape(ctx.force_shape)
-        return (None, None, None, None, gf) + grads
+        return (None, None, None, None, None, gf) + grads
 
 
 class PeriodicSolver(object):
@@ -741,6 +699,23 @@ class PeriodicSolver(object):
         work = state.work if state.work.numel() >= need else torch.empty(need, dtype=torch.uint8, device=state.what.device)
         return ops.spec_ns_scalar_field(state.what, work, self.ny, out)
 
+    def _advance_args(self, who, scalar, nsteps, forcing, *fields):
+        """The checked arguments of ``advance`` / ``advance_velocity`` and, with ``scalar``, of ``advance_scalar`` / ``advance_velocity_scalar``:
+        the refusals, then the tensor checks.  ``fields``: (name, tensor) pairs."""
+        if scalar and self.kappa is None:
+            raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use %s"
+                             % (who, who.replace('_scalar', '')))
+        self._refuse_unsupported(who, scalar)
+        nsteps = _count('nsteps', nsteps, 1)
+        fields = [self._grad_field(name, f) for name, f in fields]
+        if any(f.shape != fields[0].shape for f in fields[1:]):
+            raise ValueError("%s: the fields must share their shape" % who if scalar else "u0 and v0 must share their shape")
+        if forcing is not None:
+            forcing = self._grad_field('forcing', forcing)
+            if forcing.dim() == 2:
+                forcing = forcing.unsqueeze(0)
+        return nsteps, forcing, fields
+
     def advance(self, w, nsteps=1, mean=None, forcing=None):
         """The vorticity field after ``nsteps`` steps from the vorticity field w (float32 device tensor [B, nx, ny] or [nx, ny]), differentiable:
         an autograd node whose backward is the adjoint of the Lawson RK4 step as HIP kernels (csrc/pspec_kernels.hip: ps_row_adj_kernel,
@@ -752,68 +727,38 @@ class PeriodicSolver(object):
         nsteps x B x my1 x nx x 8 bytes (my1 = (ny - 1) // 3 + 1: a third of a field per step and grid); the stages inside a step are recomputed.
         Not for a solver with kappa or buoyancy (``advance_scalar`` / ``advance_velocity_scalar`` take and return the scalar) and not yet for a
         stochastic force, hyperviscosity, hypofriction or beta: NotImplementedError."""
-        self._refuse_unsupported('advance')
-        nsteps = _count('nsteps', nsteps, 1)
-        w = self._grad_field('w', w)
-        if forcing is not None:
-            forcing = self._grad_field('forcing', forcing)
-            if forcing.dim() == 2:
-                forcing = forcing.unsqueeze(0)
-        return _AdvanceFn.apply(self, nsteps, mean, False, forcing, w)[0]
+        nsteps, forcing, (w,) = self._advance_args('advance', False, nsteps, forcing, ('w', w))
+        return _AdvanceFn.apply(self, nsteps, mean, False, False, forcing, w)[0]
 
     def advance_velocity(self, u0, v0, nsteps=1, forcing=None):
         """(u, v) after ``nsteps`` steps from the velocity (u0, v0), differentiable like ``advance`` (and in ``forcing``, a vorticity source as
         there): ``fields(step(init(u0, v0), nsteps))[:2]`` forward; backward through the velocity by K^T (ubar, vbar)^ = curl(ubar, vbar)^ / |k|^2,
         the step's adjoint, and init^T (lam) = (lam_y, -lam_x), built from the init / fields kernels and one |k|^-2, |k|^2 table multiply each.
         The grid means (U0, V0) of (u0, v0) are constants of the motion and are not differentiated.  No pressure output."""
-        self._refuse_unsupported('advance_velocity')
-        nsteps = _count('nsteps', nsteps, 1)
-        u0, v0 = self._grad_field('u0', u0), self._grad_field('v0', v0)
-        if u0.shape != v0.shape:
-            raise ValueError("u0 and v0 must share their shape")
-        if forcing is not None:
-            forcing = self._grad_field('forcing', forcing)
-            if forcing.dim() == 2:
-                forcing = forcing.unsqueeze(0)
-        return _AdvanceFn.apply(self, nsteps, None, True, forcing, u0, v0)
-
-    def _scalar_advance_args(self, who, nsteps, forcing, *fields):
-        """The checked arguments of ``advance_scalar`` / ``advance_velocity_scalar``: the refusals, then the tensor checks of ``advance``."""
-        if self.kappa is None:
-            raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use %s"
-                             % (who, who.replace('_scalar', '')))
-        self._refuse_unsupported(who, scalar=True)
-        nsteps = _count('nsteps', nsteps, 1)
-        fields = [self._grad_field(name, f) for name, f in fields]
-        if any(f.shape != fields[0].shape for f in fields[1:]):
-            raise ValueError("%s: the fields must share their shape" % who)
-        if forcing is not None:
-            forcing = self._grad_field('forcing', forcing)
-            if forcing.dim() == 2:
-                forcing = forcing.unsqueeze(0)
-        return nsteps, forcing, fields
+        nsteps, forcing, (u0, v0) = self._advance_args('advance_velocity', False, nsteps, forcing, ('u0', u0), ('v0', v0))
+        return _AdvanceFn.apply(self, nsteps, None, True, False, forcing, u0, v0)
 
     def advance_scalar(self, w, theta, nsteps=1, mean=None, forcing=None):
         """(w, theta) after ``nsteps`` steps from the vorticity field w and the scalar theta (float32 device tensors [B, nx, ny] or [nx, ny]) on a
         solver with ``kappa``, differentiable in w, theta and ``forcing`` like ``advance``: one autograd node whose backward is the adjoint of
-        the scalar step -- of the buoyant one with ``buoyancy`` != 0 -- as HIP kernels (csrc/pspec_kernels.hip: ps_row_adj_scalar_kernel,
-        ps_col_adj_scalar_kernel; derivation in DESIGN.md section 4.2), the scalar riding in the launches of the flow's adjoint as it does in
+        the scalar step -- of the buoyant one with ``buoyancy`` != 0 -- as HIP kernels (csrc/pspec_kernels.hip: ps_row_adj_kernel and
+        ps_col_adj_kernel in their scalar forms; derivation in DESIGN.md section 4.2), the scalar riding in the launches of the flow's adjoint as it does in
         the step.  So an initial temperature can be recovered from a late one, a closure trained through a buoyant flow, a vorticity source
         fitted to scalar observations.  ``forcing`` and ``mean`` as in ``advance``; the scalar has no source.  The forward is bitwise ``step``
         on ``init_vorticity(w, mean)`` with ``that`` from ``ops.spec_ns_scalar_init(theta)``, read by ``vorticity`` and ``scalar``.  Memory kept
         for the backward: both spectra at the start of every step, nsteps x B x my1 x nx x 16 bytes.  kappa, the gradient G, b, nu, the drag and
         the mean flow are constants and are not differentiated.  ValueError on a solver without kappa; not yet for a stochastic force,
         hyperviscosity, hypofriction or beta: NotImplementedError."""
-        nsteps, forcing, (w, theta) = self._scalar_advance_args('advance_scalar', nsteps, forcing, ('w', w), ('theta', theta))
-        return _AdvanceScalarFn.apply(self, nsteps, mean, False, forcing, w, theta)
+        nsteps, forcing, (w, theta) = self._advance_args('advance_scalar', True, nsteps, forcing, ('w', w), ('theta', theta))
+        return _AdvanceFn.apply(self, nsteps, mean, False, True, forcing, w, theta)
 
     def advance_velocity_scalar(self, u0, v0, theta0, nsteps=1, forcing=None):
         """(u, v, theta) after ``nsteps`` steps from the velocity (u0, v0) and the scalar theta0, differentiable like ``advance_scalar``:
         ``fields(step(init(u0, v0, theta0), nsteps))[:2]`` and ``scalar`` of it forward; backward through the velocity's ends as in
         ``advance_velocity``.  No pressure output."""
-        nsteps, forcing, (u0, v0, theta0) = self._scalar_advance_args('advance_velocity_scalar', nsteps, forcing, ('u0', u0), ('v0', v0),
-                                                                      ('theta0', theta0))
-        return _AdvanceScalarFn.apply(self, nsteps, None, True, forcing, u0, v0, theta0)
+        nsteps, forcing, (u0, v0, theta0) = self._advance_args('advance_velocity_scalar', True, nsteps, forcing, ('u0', u0), ('v0', v0),
+                                                               ('theta0', theta0))
+        return _AdvanceFn.apply(self, nsteps, None, True, True, forcing, u0, v0, theta0)
 
     def diagnostics(self, state):
         """Diagnostics(energy, enstrophy, power_in), each float64 [B], computed on the device from the state's spectrum:

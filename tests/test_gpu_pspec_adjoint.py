@@ -40,13 +40,14 @@ def forward(s, state, ghat, nsteps):
     return what0
 
 
-def adjoint(s, what0, mean, ghat, lam, want_g=True):
-    """(wbar, gbar) of the direct adjoint call; lam is not modified."""
+def adjoint(s, what0, mean, ghat, lam, want_g=True, work=None):
+    """(wbar, gbar) of the direct adjoint call; lam is not modified.  work: the workspace (None: a fresh one of the queried size)."""
     from nns import ops
     B = lam.shape[0]
     lam = lam.clone()
     gbar = torch.full_like(lam, float('nan')) if want_g else None            # overwritten, not added to
-    work = torch.empty(ops.spec_ns_adjoint_workspace(B, s.nx, s.ny), dtype=torch.uint8, device='cuda')
+    if work is None:
+        work = torch.empty(ops.spec_ns_adjoint_workspace(B, s.nx, s.ny), dtype=torch.uint8, device='cuda')
     ops.spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag)
     return lam, gbar
 
@@ -241,6 +242,19 @@ def test_grid_stride(gpu_device):
     (wb, gb), (w01, g01), (w23, g23) = outs
     assert torch.equal(wb[:2], w01) and torch.equal(gb[:2], g01) and torch.equal(wb[-2:], w23) and torch.equal(gb[-2:], g23)
     assert float(wb.abs().max()) > 0
+
+
+def test_the_call_stays_inside_its_workspace(gpu_device):
+    """64 x 64 (the smallest grid on both axes: 22 kept columns in one 64-line tile), one grid, 2 steps, gbar wanted: the bytes after the
+    queried size keep their fill, and the results are those of a plain workspace of that size."""
+    from nns import ops
+    s, d, start, ghat, lam, wbar, gbar = direct(AC.CASES[0], nsteps=2, grids=slice(0, 1))
+    what0 = forward(s, start.clone(), ghat, 2)
+    need = ops.spec_ns_adjoint_workspace(1, s.nx, s.ny)
+    buf = torch.full((need + 4096,), 0xA5, dtype=torch.uint8, device='cuda')
+    w2, g2 = adjoint(s, what0, start.mean, ghat, lam, work=buf[:need])
+    assert bool((buf[need:] == 0xA5).all())
+    assert torch.equal(w2, wbar) and torch.equal(g2, gbar) and float(gbar.abs().max()) > 0
 
 
 # ---------------------------------------------------------------------------------------------------- 5. refusals

@@ -1,5 +1,5 @@
 """GPU checks of the reverse mode of the periodic solver's scalar and buoyant step (csrc/pspec_kernels.hip:
-nns_spec_ns_step_scalar_adjoint_f32, ps_row_adj_scalar_kernel, ps_col_adj_scalar_kernel; nns.periodic.PeriodicSolver.advance_scalar /
+nns_spec_ns_step_scalar_adjoint_f32, ps_row_adj_kernel and ps_col_adj_kernel in their scalar forms; nns.periodic.PeriodicSolver.advance_scalar /
 advance_velocity_scalar) against the float64 restatement tests/pspec_scalar_adjoint_oracle.py, the flow's own adjoint, an analytic gradient and
 its own bit identities.  Inputs fill the whole 2/3 band (tests/pspec_scalar_adjoint_cases.py)."""
 import ctypes
@@ -47,13 +47,15 @@ def forward(s, state, ghat, nsteps):
     return what0, that0
 
 
-def adjoint(s, what0, that0, mean, ghat, lam, mu, want_g=True):
-    """(wbar, thetabar, gbar) of the direct adjoint call; lam and mu are not modified."""
+def adjoint(s, what0, that0, mean, ghat, lam, mu, want_g=True, work=None):
+    """(wbar, thetabar, gbar) of the direct adjoint call; lam and mu are not modified.  work: the workspace (None: a fresh one of the queried
+    size)."""
     from nns import ops
     B = lam.shape[0]
     lam, mu = lam.clone(), mu.clone()
     gbar = torch.full_like(lam, float('nan')) if want_g else None            # overwritten, not added to
-    work = torch.empty(ops.spec_ns_scalar_adjoint_workspace(B, s.nx, s.ny), dtype=torch.uint8, device='cuda')
+    if work is None:
+        work = torch.empty(ops.spec_ns_scalar_adjoint_workspace(B, s.nx, s.ny), dtype=torch.uint8, device='cuda')
     ops.spec_ns_step_scalar_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag, s.kappa,
                                      s.scalar_gradient, s.buoyancy)
     return lam, mu, gbar
@@ -180,6 +182,7 @@ def test_without_buoyancy_and_scalar_cotangent_the_flow_adjoint_is_the_parents(g
     ew, eg = AC.rel(cplx(wbar), cplx(pl)), AC.rel(cplx(gbar), cplx(pg))
     print('against the flow adjoint: wbar %.2e gbar %.2e, bitwise %s' % (ew, eg, torch.equal(wbar, pl) and torch.equal(gbar, pg)))
     assert ew <= AC.BOUND and eg <= AC.BOUND
+    assert torch.equal(wbar, pl) and torch.equal(gbar, pg)                   # one text of the recurrences serves both calls
     assert float(tbar.abs().max()) == 0.0 and float(that0.abs().max()) > 0
     s0 = solver(c, d['dt'], grad=(0.0, 0.0))
     rest = start.clone()
@@ -254,6 +257,21 @@ def test_grid_stride(gpu_device):
     whole, first, last = outs
     for a, f, l in zip(whole, first, last):
         assert torch.equal(a[:2], f) and torch.equal(a[-2:], l) and float(a.abs().max()) > 0
+
+
+def test_the_call_stays_inside_its_workspace(gpu_device):
+    """64 x 64 (the smallest grid on both axes: 22 kept columns in one 64-line tile), one grid of the buoyant case, 2 steps, gbar wanted: the
+    bytes after the queried size keep their fill, and the results are those of a plain workspace of that size."""
+    from nns import ops
+    c = AC.CASES[0]
+    assert c[6] == AC.UNSTABLE
+    s, d, start, ghat, lam, mu, wbar, tbar, gbar = direct(c, nsteps=2, grids=slice(0, 1))
+    what0, that0 = forward(s, start.clone(), ghat, 2)
+    need = ops.spec_ns_scalar_adjoint_workspace(1, s.nx, s.ny)
+    buf = torch.full((need + 4096,), 0xA5, dtype=torch.uint8, device='cuda')
+    w2, t2, g2 = adjoint(s, what0, that0, start.mean, ghat, lam, mu, work=buf[:need])
+    assert bool((buf[need:] == 0xA5).all())
+    assert torch.equal(w2, wbar) and torch.equal(t2, tbar) and torch.equal(g2, gbar) and float(gbar.abs().max()) > 0
 
 
 # ---------------------------------------------------------------------------------------------------- 6. refusals

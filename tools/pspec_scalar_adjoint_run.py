@@ -1,14 +1,15 @@
 """Measures the reverse mode of the periodic spectral solver's scalar and buoyant step (nns.periodic.PeriodicSolver.advance_scalar:
 nns_spec_ns_step_scalar_adjoint_f32 of csrc/pspec_kernels.hip).  Writes ONE JSON record to OUTDIR/pspec_scalar_adjoint_run.json and prints it.
 
-    python tools/pspec_scalar_adjoint_run.py OUTDIR [--steps 20] [--reps 7] [--commit ID] [--parent-lib PATH] [--isa-notes FILE] [--no-accuracy] [--no-torch]
+    python tools/pspec_scalar_adjoint_run.py OUTDIR [--steps 20] [--reps 7] [--commit ID] [--parent-lib PATH] [--name NAME] [--isa-notes FILE] [--no-accuracy] [--no-torch]
 
 Timing: at 256^2 x 64 and 1024^2 x 8 (|m| <= 8 flow and scalar, Kolmogorov force k = 4, drag 0.1, kappa = nu, G = (0, 1); buoyant: b = (0, 1))
 these take turns within every repetition, each from the same saved state: the flow's forced step and its adjoint call (the parent's kernels,
 in this process), then for the passive and for the buoyant scalar the forward step, the adjoint call alone and forward + backward through
 ``advance_scalar`` (autograd, a differentiable forcing) and, unless --no-torch, forward + backward of the buoyant scheme composed from torch.fft
 ops in float32 under torch autograd.  With --parent-lib also whether the forward steps and the flow's adjoint of another build of the library
-(the parent commit's) loaded into the same process give the same bits.  A timing is device events around the work, reported per step as the
+(the parent commit's) loaded into the same process give the same bits, and the flow's adjoint call of this build against the parent's in the
+same rotation, the parent's twice: the ratio of its two turns is the noise the A/B ratio is read against.  A timing is device events around the work, reported per step as the
 median over the repetitions with the spread (max - min) / median; ratios are medians of the per-repetition ratios.
 
 The byte model to compare against, in compacted fields c moved per step (DESIGN.md section 4.2 has the count): the flow's adjoint 132c, the
@@ -32,7 +33,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, 'neural-navier-stokes_amd'), os.path.jo
 import torch  # noqa: E402
 
 import pspec_oracle as O  # noqa: E402
-from nns import ops  # noqa: E402
+from nns import _lib, ops  # noqa: E402
 from nns.periodic import PeriodicSolver, PeriodicState  # noqa: E402
 from pspec_adjoint_run import event_ms, stats, ratio, dev  # noqa: E402
 
@@ -104,7 +105,13 @@ def parent_calls(path):
     def adjoint(s, what0, mean, lam, gbar, work):
         check(L.nns_spec_ns_step_adjoint_f32(p(what0), p(mean), p(s.ghat), 1, p(lam), p(gbar), p(work), work.numel(), lam.shape[0], s.nx, s.ny, s.Lx,
                                              s.Ly, s.dt, s.nu, s.drag, what0.shape[0], stream()))
-    return dict(forced=forced, buoyant=buoyant, adjoint=adjoint)
+    L.nns_spec_ns_step_scalar_adjoint_f32.argtypes = [P] * 4 + [I] + [P] * 4 + [Z] + [I] * 3 + [D] * 10 + [I, P]
+
+    def scalar_adjoint(s, what0, that0, mean, lam, mu, gbar, work):
+        check(L.nns_spec_ns_step_scalar_adjoint_f32(p(what0), p(that0), p(mean), p(s.ghat), 1, p(lam), p(mu), p(gbar), p(work), work.numel(),
+                                                    lam.shape[0], s.nx, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag, s.kappa, s.scalar_gradient[0],
+                                                    s.scalar_gradient[1], s.buoyancy[0], s.buoyancy[1], what0.shape[0], stream()))
+    return dict(forced=forced, buoyant=buoyant, adjoint=adjoint, scalar_adjoint=scalar_adjoint)
 
 
 def timing(args):
@@ -188,6 +195,20 @@ def timing(args):
             lam.copy_(lam0)
             parent['adjoint'](flow, what0, st.mean, lam, gbar, awork)
             case['flow_adjoint_bitwise_parent_lib'] = bool(torch.equal(mine[0], lam) and torch.equal(mine[1], gbar))
+            for kind in ('passive', 'buoyant'):
+                adjoint(sol[kind])
+                mine = (lam.clone(), mu.clone(), gbar.clone())
+                lam.copy_(lam0)
+                mu.copy_(mu0)
+                parent['scalar_adjoint'](sol[kind], what0, that0, st.mean, lam, mu, gbar, awork)
+                case[kind + '_adjoint_bitwise_parent_lib'] = bool(all(torch.equal(a, b) for a, b in zip(mine, (lam, mu, gbar))))
+            # the flow's adjoint of this build and of the parent's under the same direct call, the parent's twice: the A/A ratio is the noise
+            this = parent_calls(_lib.LIB_PATH)
+            for name, calls in (('flow_adjoint_direct', this), ('flow_adjoint_direct_parent_lib', parent), ('flow_adjoint_direct_parent_lib_again', parent)):
+                def direct(calls=calls):
+                    lam.copy_(lam0)
+                    calls['adjoint'](flow, what0, st.mean, lam, gbar, awork)
+                variants.insert(2, (name, direct))
         for _, fn in variants:
             restore()
             fn()
@@ -201,6 +222,11 @@ def timing(args):
         for name, _ in variants:
             case[name] = stats(ts[name], steps)
         case['flow_adjoint_over_flow_step'] = ratio(ts['flow_adjoint_call'], ts['flow_step'])
+        if parent:
+            ab = ratio(ts['flow_adjoint_direct'], ts['flow_adjoint_direct_parent_lib'])
+            aa = ratio(ts['flow_adjoint_direct_parent_lib_again'], ts['flow_adjoint_direct_parent_lib'])
+            case['flow_adjoint_over_parent_lib'], case['parent_lib_again_over_parent_lib'] = ab, aa
+            case['flow_adjoint_median_inside_parent_lib_noise'] = bool(aa['min'] <= ab['median'] <= aa['max'])
         for kind in ('passive', 'buoyant'):
             case[kind + '_adjoint_over_step'] = ratio(ts[kind + '_adjoint_call'], ts[kind + '_step'])
             case[kind + '_adjoint_over_flow_adjoint'] = ratio(ts[kind + '_adjoint_call'], ts['flow_adjoint_call'])
@@ -255,7 +281,7 @@ def kernel_resources(path):
     for blk in open(path).read().split('- .agpr_count')[1:]:
         name = re.search(r'\.name:\s+(\S+)', blk)
         vg, sc = re.search(r'\.vgpr_count:\s+(\d+)', blk), re.search(r'\.private_segment_fixed_size:\s+(\d+)', blk)
-        if name and vg and sc and ('adj_scalar' in name.group(1) or 'PsKeepScalar' in name.group(1)):
+        if name and vg and sc and any(k in name.group(1) for k in ('PsAdjScalar', 'PsAdjGrad', 'PsKeepScalar')):
             res[name.group(1)] = dict(vgprs=int(vg.group(1)), scratch_bytes=int(sc.group(1)))
     return res
 
@@ -268,6 +294,7 @@ def main():
     ap.add_argument('--commit', default='unknown')
     ap.add_argument('--parent-lib', default=None, help="another build of libnns_hip.so (the parent commit's) for the same-process comparison")
     ap.add_argument('--isa-notes', default=None, help='text of llvm-readelf --notes on libnns_hip.so (registers and scratch per kernel)')
+    ap.add_argument('--name', default='pspec_scalar_adjoint_run', help='the record is OUTDIR/NAME.json')
     ap.add_argument('--no-accuracy', action='store_true')
     ap.add_argument('--no-torch', action='store_true')
     args = ap.parse_args()
@@ -278,7 +305,7 @@ def main():
     rec['timing'] = timing(args)
     rec['kernels'] = kernel_resources(args.isa_notes)
     os.makedirs(args.outdir, exist_ok=True)
-    with open(os.path.join(args.outdir, 'pspec_scalar_adjoint_run.json'), 'w') as f:
+    with open(os.path.join(args.outdir, args.name + '.json'), 'w') as f:
         json.dump(rec, f, indent=1)
     print(json.dumps(rec))
 
