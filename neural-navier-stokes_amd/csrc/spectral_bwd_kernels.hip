@@ -39,29 +39,18 @@ __device__ __forceinline__ void adj_core(const float (&ff)[16], const float (&gf
     C2<float>* xbI = reinterpret_cast<C2<float>*>(xb_raw);
     C2<float> e[16];
     if constexpr (sizeof(TF) == 4) {
-        // all-float32 mode, as the forward's (spectral_kernels.hip, deriv_core): every packed pair is forward-DIFFERENCED in physical space,
-        // FFT(d) = (e^{i theta} - 1) FFT(f), and the spectral multiplies become the bounded filters
-        //     i k   FFT(f) = M1 D,  M1 = (k / 2)(cot(theta / 2) - i);      -nu k^2 FFT(f) = (nu k / 2)(k + i k cot(theta / 2)) D
+        // all-float32 mode, as the forward's (deriv_core): every packed pair is forward-DIFFERENCED in physical space and the spectral
+        // multiplies become the bounded filters M1 and -F2 (diff_fft: spectral_common.h; spectral_filter_m1.inc, spectral_filter_f2.inc)
         const float* ctab = reinterpret_cast<const float*>(tabI + N / 2 + Pass2<N>::ENTRIES);
         const float c1h = (float)(0.5 * k.c1), c2h = (float)(0.5 * k.c2);
-        auto diff_fft = [&](const float (&p)[16], const float (&q)[16], C2<float> (&zv)[16]) {
-            static_for<0, 16>([&](auto mc) {
-                constexpr int m = decltype(mc)::value;
-                zv[m].x = right_of<m, N / 16>(p, tid) - p[m];
-                zv[m].y = right_of<m, N / 16>(q, tid) - q[m];
-            });
-            fft_line<float, N, false>(zv, tabI, tabI2, xbI, tid);
-        };
         C2<float> zv[16];
         // ---- (f', g')
-        diff_fft(ff, gf, zv);
+        diff_fft<N>(ff, gf, zv, tabI, xbI, tid);
         int te = tid;
         asm volatile("" : "+v"(te), "+v"(zv[0].x));
         static_for<0, 16>([&](auto mc) {
             constexpr int m = decltype(mc)::value;
-            int ko, ke;
-            wavenumber<N, m>(te, ko, ke);
-            const float ar = ctab[ke < 0 ? -ke : ke] * c1h, ai = (float)ko * c1h;
+#include "spectral_filter_m1.inc"
             e[m].x = ar * zv[m].x + ai * zv[m].y; e[m].y = ar * zv[m].y - ai * zv[m].x;
         });
         __builtin_amdgcn_sched_barrier(0);
@@ -70,19 +59,15 @@ __device__ __forceinline__ void adj_core(const float (&ff)[16], const float (&gf
         for (int m = 0; m < 16; ++m) w[m] = af[m] * e[m].x + bf[m] * e[m].y;
         __builtin_amdgcn_sched_barrier(0);
         // ---- a', b' and the viscous term  -nu k^2 Z2  (kept in c)
-        diff_fft(af, bf, zv);
+        diff_fft<N>(af, bf, zv, tabI, xbI, tid);
         te = tid;
         asm volatile("" : "+v"(te), "+v"(zv[0].x));
         static_for<0, 16>([&](auto mc) {
             constexpr int m = decltype(mc)::value;
-            int ko, ke;
-            wavenumber<N, m>(te, ko, ke);
-            const float ct = ctab[ke < 0 ? -ke : ke];
-            const float ar = ct * c1h, ai = (float)ko * c1h;
+#include "spectral_filter_m1.inc"
             e[m].x = ar * zv[m].x + ai * zv[m].y; e[m].y = ar * zv[m].y - ai * zv[m].x;
-            const float kf = (float)ke * c2h;
-            const float br = kf * (float)ke, bi = kf * ct;                   // -nu k^2 Z2 = (br + i bi) D
-            c[m].x = br * zv[m].x - bi * zv[m].y; c[m].y = br * zv[m].y + bi * zv[m].x;
+#include "spectral_filter_f2.inc"
+            c[m].x = br * zv[m].x - bi * zv[m].y; c[m].y = br * zv[m].y + bi * zv[m].x;        // -nu k^2 Z2
         });
         __builtin_amdgcn_sched_barrier(0);
         fft_line<float, N, true>(e, tabI, tabI2, xbI, tid);
@@ -90,14 +75,12 @@ __device__ __forceinline__ void adj_core(const float (&ff)[16], const float (&gf
         for (int m = 0; m < 16; ++m) da[m] = USE_A ? e[m].x : e[m].y;
         __builtin_amdgcn_sched_barrier(0);
         // ---- D s1 + nu L a,  D s2 + nu L b
-        diff_fft(s1, s2, zv);
+        diff_fft<N>(s1, s2, zv, tabI, xbI, tid);
         te = tid;
         asm volatile("" : "+v"(te), "+v"(zv[0].x));
         static_for<0, 16>([&](auto mc) {
             constexpr int m = decltype(mc)::value;
-            int ko, ke;
-            wavenumber<N, m>(te, ko, ke);
-            const float ar = ctab[ke < 0 ? -ke : ke] * c1h, ai = (float)ko * c1h;
+#include "spectral_filter_m1.inc"
             c[m].x += ar * zv[m].x + ai * zv[m].y; c[m].y += ar * zv[m].y - ai * zv[m].x;
         });
         __builtin_amdgcn_sched_barrier(0);
@@ -240,6 +223,7 @@ __global__ __launch_bounds__(kSpecThreads) void spec_bwd_xpass_kernel(const floa
                                                                        float* __restrict__ gu, float* __restrict__ gv, float* __restrict__ gp,
                                                                        int ny, int tiles_per_grid, long ntiles, AdjK k) {
     using L = SpecLds<N, TF>;
+    using CL = L;
     constexpr int TPF = L::TPF, CW = L::LINES, SF = L::STAGE_F;
     constexpr int ROWS_PER_IT = kSpecThreads / CW;
     constexpr int NR = N / ROWS_PER_IT;
@@ -248,15 +232,9 @@ __global__ __launch_bounds__(kSpecThreads) void spec_bwd_xpass_kernel(const floa
     C2<TF>* tabF; C2<float>* tabI; unsigned char* lines;
     spec_setup<N, TF>(smem, tabF, tabI, lines);
     for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        int tx = threadIdx.x;
-        asm volatile("" : "+v"(tx));
-        const int wave = tx / kWave, lane = tx % kWave;
-        const int sub = lane / TPF, tid = lane % TPF;
-        const int line = wave * L::FPW + sub;
-        unsigned char* xb = lines + (size_t)line * L::LINE_BYTES;
-        float* my_stage = reinterpret_cast<float*>(xb) + (line % L::SKEW_MOD) * L::SKEW_DW;
-        const long lt = ntiles - 1 - (long)xcd_remap((unsigned)t, (unsigned)ntiles);      // last grid first: see spectral_kernels.hip launch_xpass
-        const int j0 = (int)(lt % tiles_per_grid) * CW;
+#include "spectral_col_line.inc"
+        int j0;
+#include "spectral_tile_coords.inc"
         const size_t g = (size_t)(lt / tiles_per_grid) * N * ny;
         const int cc = tx % CW, cr = tx / CW;
         const int col = j0 + cc < ny ? j0 + cc : ny - 1;                               // clamped: loads need no mask
@@ -343,6 +321,7 @@ __global__ __launch_bounds__(kSplitThreads) void spec_bwd_xsplit_kernel(const fl
                                                                          int ny, int tiles_per_grid, long ntiles, AdjK k) {
     using L = SpecLds<N, float>;
     using SL = SplitLds<N, float>;
+    using CL = SL;
     constexpr int TPF = L::TPF, CW = L::LINES, SF = L::STAGE_F;
     constexpr int MROWS = 256 / CW;                       // rows of the tile one memory-wave instruction step covers
     constexpr int NR = N / MROWS;                         // elements per memory lane and field (= 32 for every N)
@@ -352,27 +331,21 @@ __global__ __launch_bounds__(kSplitThreads) void spec_bwd_xsplit_kernel(const fl
     C2<float>* tabF; C2<float>* tabI; unsigned char* lines;
     spec_setup<N, float, kSplitThreads>(smem, tabF, tabI, lines);
     auto tile_coords = [&](long t, int& j0, size_t& g) {
-        const long lt = ntiles - 1 - (long)xcd_remap((unsigned)t, (unsigned)ntiles);       // last grid first, neighbouring tiles on one XCD (as the forward)
-        j0 = (int)(lt % tiles_per_grid) * CW;
+#include "spectral_tile_coords.inc"
         g = (size_t)(lt / tiles_per_grid) * (size_t)N * ny;
     };
     long t = blockIdx.x;
     if (t >= ntiles) return;                               // uniform over the workgroup (the launch never has more workgroups than tiles)
     if (threadIdx.x >= kSpecThreads) {
         // ================= memory waves =================
-        int mt = threadIdx.x - kSpecThreads;
-        asm volatile("" : "+v"(mt));
-        const int cc = mt % CW, cr = mt / CW;
-        float* stage = reinterpret_cast<float*>(lines + (size_t)cc * SL::LINE_BYTES) + (cc % 8) * SL::SKEW_DW + 4 * cr;       // [field][row]
+#include "spectral_split_mem.inc"
         float R[4][NR];                                                        // fields 0..2: a tile's inputs / GU, GV; field 3: GP until its store window
-        // a lane owns rows 4 cr .. 4 cr + 3 of every block of 4 MROWS rows (element i <-> row 4 cr + (i & 3) + 4 MROWS (i >> 2)): four consecutive
-        // rows move through LDS as ONE 16-byte access; addresses = scalar grid base + 32-bit lane byte offset (spectral_fwd.h, the same scheme)
+        // byte offset of element i of this lane (at_byte): no segments here, so (i & 3) folds into the row -- the forward's off32 keeps it apart for
+        // its segmented branch, and the two compile to different address arithmetic: two texts
         auto off32 = [&](int i, unsigned col, unsigned crv) -> unsigned {
             const unsigned r0 = 4u * crv + 4u * MROWS * (unsigned)(i >> 2) + (unsigned)(i & 3);
             return (col + r0 * (unsigned)ny) * 4u;
         };
-        auto at = [](const float* base, unsigned byte_off) -> const float& { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off); };
-        auto at_w = [](float* base, unsigned byte_off) -> float& { return *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off); };
         auto load3 = [&](long tt, const float* f0, const float* f1, const float* f2) {            // f2 == nullptr: two fields
             int j0; size_t g;
             tile_coords(tt, j0, g);
@@ -382,8 +355,8 @@ __global__ __launch_bounds__(kSplitThreads) void spec_bwd_xsplit_kernel(const fl
 #pragma unroll
             for (int i = 0; i < NR; ++i) {
                 const unsigned c = off32(i, col, crv);
-                R[0][i] = at(f0 + g, c); R[1][i] = at(f1 + g, c);
-                if (f2) R[2][i] = at(f2 + g, c);
+                R[0][i] = at_byte(f0 + g, c); R[1][i] = at_byte(f1 + g, c);
+                if (f2) R[2][i] = at_byte(f2 + g, c);
             }
         };
         // The tile's traffic is spread over the two windows the transform phases leave (phase 1 = 2 transforms, phase 2 = 4): GU, GV leave in the
@@ -399,7 +372,7 @@ __global__ __launch_bounds__(kSplitThreads) void spec_bwd_xsplit_kernel(const fl
 #pragma unroll
                 for (int i = 0; i < NR; ++i) {
                     const unsigned c = off32(i, col, crv);
-                    at_w(gu + g, c) = R[0][i]; at_w(gv + g, c) = R[1][i];
+                    at_byte(gu + g, c) = R[0][i]; at_byte(gv + g, c) = R[1][i];
                 }
             }
         };
@@ -411,16 +384,11 @@ __global__ __launch_bounds__(kSplitThreads) void spec_bwd_xsplit_kernel(const fl
                 unsigned crv = (unsigned)cr;
                 asm volatile("" : "+v"(col), "+v"(crv));
 #pragma unroll
-                for (int i = 0; i < NR; ++i) at_w(gp + g, off32(i, col, crv)) = R[3][i];
+                for (int i = 0; i < NR; ++i) at_byte(gp + g, off32(i, col, crv)) = R[3][i];
             }
         };
         load3(t, u, v, ga);
-#pragma unroll
-        for (int q = 0; q < NR / 4; ++q)
-#pragma unroll
-            for (int f = 0; f < 3; ++f)
-                *reinterpret_cast<float4*>(stage + f * SF + 4 * MROWS * q) = make_float4(R[f][4 * q], R[f][4 * q + 1], R[f][4 * q + 2], R[f][4 * q + 3]);
-        __syncthreads();                                                        // u, v, a of the first tile are staged
+#include "spectral_split_stage.inc"
         long prev = -1;
         for (; t < ntiles; t += gridDim.x) {
             const long tn = t + gridDim.x;
@@ -462,29 +430,14 @@ __global__ __launch_bounds__(kSplitThreads) void spec_bwd_xsplit_kernel(const fl
     const float c1h = (float)(0.5 * k.c1), c2h = (float)(0.5 * k.c2);
     __syncthreads();                                                            // u, v, a of the first tile are staged
     for (; t < ntiles; t += gridDim.x) {
-        int tx = threadIdx.x;
-        asm volatile("" : "+v"(tx));
-        const int wave = tx / kWave, lane = tx % kWave;
-        const int sub = lane / TPF, tid = lane % TPF;
-        const int line = wave * L::FPW + sub;
-        unsigned char* xb = lines + (size_t)line * SL::LINE_BYTES;
+#include "spectral_col_line.inc"
         C2<float>* xbI = reinterpret_cast<C2<float>*>(xb);
-        float* my_stage = reinterpret_cast<float*>(xb) + (line % 8) * SL::SKEW_DW;
         // behind the exchange image the line area has room for ONE lane-private array of 16 floats (LINE_BYTES - XB_BYTES >= 64 TPF bytes for every N): w waits
         // there over phase 2 -- 16 registers fewer at the kernel's register peak (52 bytes of scratch per lane at N = 1024 without it)
         static_assert(SL::LINE_BYTES - (L::XB_BYTES + 15) / 16 * 16 >= 64 * TPF, "park area");
         float4* parkw = reinterpret_cast<float4*>(xb + (L::XB_BYTES + 15) / 16 * 16) + tid;
         int tidv = tid;
         asm volatile("" : "+v"(tidv));
-        // forward transform of the forward-DIFFERENCED packed pair (p, q): FFT(d) = (e^{i theta} - 1) FFT(p + i q) (adj_core, all-float32 mode)
-        auto diff_fft = [&](const float (&p)[16], const float (&q)[16], C2<float> (&zv)[16]) {
-            static_for<0, 16>([&](auto mc) {
-                constexpr int m = decltype(mc)::value;
-                zv[m].x = right_of<m, N / 16>(p, tidv) - p[m];
-                zv[m].y = right_of<m, N / 16>(q, tidv) - q[m];
-            });
-            fft_line<float, N, false>(zv, tabI, tabI2, xbI, tidv);
-        };
         float uf[16], af[16], w[16], vx[16];
         {   // ---- phase 1: (u_x, v_x), w1 = a u_x
             float vf[16];
@@ -495,14 +448,12 @@ __global__ __launch_bounds__(kSplitThreads) void spec_bwd_xsplit_kernel(const fl
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             C2<float> zv[16], e[16];
-            diff_fft(uf, vf, zv);
+            diff_fft<N>(uf, vf, zv, tabI, xbI, tidv);
             int te = tidv;
             asm volatile("" : "+v"(te), "+v"(zv[0].x));
             static_for<0, 16>([&](auto mc) {
                 constexpr int m = decltype(mc)::value;
-                int ko, ke;
-                wavenumber<N, m>(te, ko, ke);
-                const float ar = ctab[ke < 0 ? -ke : ke] * c1h, ai = (float)ko * c1h;
+#include "spectral_filter_m1.inc"
                 e[m].x = ar * zv[m].x + ai * zv[m].y; e[m].y = ar * zv[m].y - ai * zv[m].x;
             });
             __builtin_amdgcn_sched_barrier(0);
@@ -530,14 +481,12 @@ __global__ __launch_bounds__(kSplitThreads) void spec_bwd_xsplit_kernel(const fl
         float gpo[16];
         {   // ---- phase 2a: c = D s1 + i D s2 in spectral space (the transform that needs u first: u, d are dead after it)
             C2<float> zv[16];
-            diff_fft(s1, s2, zv);
+            diff_fft<N>(s1, s2, zv, tabI, xbI, tidv);
             int te = tidv;
             asm volatile("" : "+v"(te), "+v"(zv[0].x));
             static_for<0, 16>([&](auto mc) {
                 constexpr int m = decltype(mc)::value;
-                int ko, ke;
-                wavenumber<N, m>(te, ko, ke);
-                const float ar = ctab[ke < 0 ? -ke : ke] * c1h, ai = (float)ko * c1h;
+#include "spectral_filter_m1.inc"
                 c[m].x = ar * zv[m].x + ai * zv[m].y; c[m].y = ar * zv[m].y - ai * zv[m].x;
             });
         }
@@ -545,19 +494,15 @@ __global__ __launch_bounds__(kSplitThreads) void spec_bwd_xsplit_kernel(const fl
         {   // ---- phase 2b: a_x (-> GP); the viscous term -nu k^2 FFT(a + i b) joins c; then the one inverse transform of c
             // (adj_core adds the two contributions of c in the other order: the results differ from spec_bwd_xpass_kernel's in the last bit)
             C2<float> zv[16], e[16];
-            diff_fft(af, bf, zv);
+            diff_fft<N>(af, bf, zv, tabI, xbI, tidv);
             int te = tidv;
             asm volatile("" : "+v"(te), "+v"(zv[0].x));
             static_for<0, 16>([&](auto mc) {
                 constexpr int m = decltype(mc)::value;
-                int ko, ke;
-                wavenumber<N, m>(te, ko, ke);
-                const float ct = ctab[ke < 0 ? -ke : ke];
-                const float ar = ct * c1h, ai = (float)ko * c1h;
+#include "spectral_filter_m1.inc"
                 e[m].x = ar * zv[m].x + ai * zv[m].y; e[m].y = ar * zv[m].y - ai * zv[m].x;
-                const float kf = (float)ke * c2h;
-                const float br = kf * (float)ke, bi = kf * ct;                   // -nu k^2 Z2 = (br + i bi) D
-                c[m].x += br * zv[m].x - bi * zv[m].y; c[m].y += br * zv[m].y + bi * zv[m].x;
+#include "spectral_filter_f2.inc"
+                c[m].x += br * zv[m].x - bi * zv[m].y; c[m].y += br * zv[m].y + bi * zv[m].x;        // -nu k^2 Z2 joins c
             });
             __builtin_amdgcn_sched_barrier(0);
             fft_line<float, N, true>(e, tabI, tabI2, xbI, tidv);
@@ -586,38 +531,39 @@ __global__ __launch_bounds__(kSplitThreads) void spec_bwd_xsplit_kernel(const fl
     }
 }
 
+// Column pass.  All-float32 mode: the role-split kernel, whose memory waves address with a scalar grid base + a 32-bit byte offset per lane
+// (N * ny < 2^30: always, through the C ABI -- spec_len_ok keeps ny <= kDenseMaxLen); float64 forward transforms: spec_bwd_xpass_kernel<N, double>.
 template <int N, typename TF>
-int launch_bwd(const float* u, const float* v, const float* ga, const float* gb, const float* gd, float* gu, float* gv, float* gp,
-               float* gup, float* gvp, int batch, int nx_or_ny_other, bool xpass, const AdjK& k, hipStream_t s) {
+int launch_bwd_xpass(const float* u, const float* v, const float* ga, const float* gb, const float* gd, float* gu, float* gv, float* gp,
+                     int batch, int ny, const AdjK& k, hipStream_t s) {
     using L = SpecLds<N, TF>;
-    const long gmax = spec_grid_cap();
-    if (xpass) {
-        if constexpr (sizeof(TF) == 4) {
-            const int ny = nx_or_ny_other;
-            // all-float32 mode: the role-split kernel, whose memory waves address with a scalar grid base + a 32-bit byte offset per lane
-            if ((unsigned long long)N * (unsigned long long)ny < (1ull << 30)) {
-                using SL = SplitLds<N, float>;
+    const int tiles_per_grid = (ny + L::LINES - 1) / L::LINES;
+    const long ntiles = (long)batch * tiles_per_grid;
+    const dim3 grid(capped_grid(ntiles, spec_grid_cap()));
+    if constexpr (sizeof(TF) == 4) {
+        if ((unsigned long long)N * (unsigned long long)ny >= (1ull << 30))
+            return fail(NNS_ERR_UNSUPPORTED, "spec_residual_bwd: nx=%d, ny=%d: a grid beyond the 32-bit byte offsets of the float32 column pass", N, ny);
+        using SL = SplitLds<N, float>;
                 constexpr auto kern = spec_bwd_xsplit_kernel<N>;
                 if (int rc = lds_opt_in<kern>(SL::TOTAL, "spec bwd xpass")) return rc;
-                const int tiles_per_grid = (ny + L::LINES - 1) / L::LINES;
-                const long ntiles = (long)batch * tiles_per_grid;
-                hipLaunchKernelGGL(kern, dim3(capped_grid(ntiles, gmax)), dim3(kSplitThreads), SL::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, ny, tiles_per_grid, ntiles, k);
-                return check_launch("spec_residual_bwd_xpass");
-            }
-        }
+        hipLaunchKernelGGL(kern, grid, dim3(kSplitThreads), SL::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, ny, tiles_per_grid, ntiles, k);
+    } else {
         constexpr auto kern = spec_bwd_xpass_kernel<N, TF>;
         if (int rc = lds_opt_in<kern>(L::TOTAL, "spec bwd xpass")) return rc;
-        const int ny = nx_or_ny_other;
-        const int tiles_per_grid = (ny + L::LINES - 1) / L::LINES;
-        const long ntiles = (long)batch * tiles_per_grid;
-        hipLaunchKernelGGL(kern, dim3(capped_grid(ntiles, gmax)), dim3(kSpecThreads), L::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, ny, tiles_per_grid, ntiles, k);
-        return check_launch("spec_residual_bwd_xpass");
+        hipLaunchKernelGGL(kern, grid, dim3(kSpecThreads), L::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, ny, tiles_per_grid, ntiles, k);
     }
+    return check_launch("spec_residual_bwd_xpass");
+}
+
+template <int N, typename TF>
+int launch_bwd_ypass(const float* u, const float* v, const float* ga, const float* gb, const float* gd, float* gu, float* gv, float* gp,
+                     float* gup, float* gvp, int batch, int nx, const AdjK& k, hipStream_t s) {
+    using L = SpecLds<N, TF>;
     constexpr auto kern = spec_bwd_ypass_kernel<N, TF>;
     if (int rc = lds_opt_in<kern>(L::TOTAL, "spec bwd ypass")) return rc;
-    const long nrows = (long)batch * nx_or_ny_other;
+    const long nrows = (long)batch * nx;
     const long niter = (nrows + L::LINES - 1) / L::LINES;
-    hipLaunchKernelGGL(kern, dim3(capped_grid(niter, gmax)), dim3(kSpecThreads), L::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, gup, gvp, nrows, k);
+    hipLaunchKernelGGL(kern, dim3(capped_grid(niter, spec_grid_cap())), dim3(kSpecThreads), L::TOTAL, s, u, v, ga, gb, gd, gu, gv, gp, gup, gvp, nrows, k);
     return check_launch("spec_residual_bwd_ypass");
 }
 
@@ -641,16 +587,12 @@ NNS_API int nns_spec_residual_bwd_f32(const float* u, const float* v, const floa
     const double kx = 2.0 * M_PI / Lx, ky = 2.0 * M_PI / Ly;
     const AdjK kxp{kx / nx, nu * kx * kx / nx, (float)(1.0 / rho), (float)(1.0 / dt)};
     const AdjK kyp{ky / ny, nu * ky * ky / ny, (float)(1.0 / rho), (float)(1.0 / dt)};
-    int rc = x_done ? 0 : dispatch_pow2(nx, "spectral", [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        return !spec_f32_mode(precise, nu, nx, Lx) ? launch_bwd<N, double>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, nullptr, nullptr, batch, ny, true, kxp, s)
-                                                  : launch_bwd<N, float>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, nullptr, nullptr, batch, ny, true, kxp, s);
+    int rc = x_done ? 0 : dispatch_spec(nx, precise, nu, Lx, [&](auto n, auto tf) {
+        return launch_bwd_xpass<decltype(n)::value, decltype(tf)>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, batch, ny, kxp, s);
     });
     if (rc) return rc;
     if (!pow2_in_range(ny)) return dense_bwd_ypass(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, grad_u_prev, grad_v_prev, batch, nx, ny, dt, Ly, rho, nu, s);
-    return dispatch_pow2(ny, "spectral", [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        return !spec_f32_mode(precise, nu, ny, Ly) ? launch_bwd<N, double>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, grad_u_prev, grad_v_prev, batch, nx, false, kyp, s)
-                                                  : launch_bwd<N, float>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, grad_u_prev, grad_v_prev, batch, nx, false, kyp, s);
+    return dispatch_spec(ny, precise, nu, Ly, [&](auto n, auto tf) {
+        return launch_bwd_ypass<decltype(n)::value, decltype(tf)>(u, v, g_u, g_v, g_div, grad_u, grad_v, grad_p, grad_u_prev, grad_v_prev, batch, nx, kyp, s);
     });
 }

@@ -1,5 +1,5 @@
-// Scaffolding shared by the spectral residual kernels (forward: spectral_kernels.hip, backward:
-// spectral_bwd_kernels.hip): launch geometry, LDS layout, wavenumber helper, table setup.
+// Scaffolding shared by the spectral residual kernels (forward: spectral_fwd.h, backward: spectral_bwd_kernels.hip): launch geometry, LDS
+// layout, wavenumber helper, table setup, the differenced transform of the all-float32 mode, the choice of arithmetic.
 #pragma once
 #include "nns_common.h"
 #include "fft_lds.h"
@@ -46,6 +46,7 @@ constexpr int kSplitThreads = kSpecThreads + 256;
 template <int N, typename TF>
 struct SplitLds {
     using L = SpecLds<N, TF>;
+    static constexpr int SKEW_MOD = 8;
     static constexpr int SKEW_DW = N == 64 ? 4 : 8;      // dwords of skew per line (mod 8 lines): the 16-lane groups of the memory waves' b128 exchange hit 64 distinct banks
                                                          // (N = 64: 128 lines per workgroup, half the skew keeps the image inside 160 KB)
     static constexpr int STAGE_BYTES = 3 * L::STAGE_F * 4 + 8 * SKEW_DW * 4;
@@ -125,6 +126,27 @@ __device__ __forceinline__ float right_of(const float (&x)[16], int tid) {
     return tid == TPF - 1 ? w : r;
 }
 
+// ---- column passes (forward: spec_xpass_kernel, spec_xpass_split_kernel; backward: spec_bwd_xpass_kernel, spec_bwd_xsplit_kernel) ----
+// (their shared text: spectral_col_line.inc, spectral_tile_coords.inc, spectral_split_mem.inc, spectral_split_stage.inc)
+// The memory waves of the role-split kernels address with a uniform grid base (scalar registers) + a 32-bit BYTE offset per lane: a load is
+// `global_load_dword v, v_off, s[base]`, with no 64-bit shift-and-add per access.
+__device__ __forceinline__ const float& at_byte(const float* base, unsigned byte_off) { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off); }
+__device__ __forceinline__ float& at_byte(float* base, unsigned byte_off) { return *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off); }
+
+// ---- the all-float32 mode's transform and filters (forward: deriv_core; backward: adj_core, spec_bwd_xsplit_kernel) ----
+// Forward transform of the forward-DIFFERENCED packed pair: zv = FFT(d), d_j = (p + i q)_{j+1} - (p + i q)_j, so FFT(d) = (e^{i theta} - 1) FFT(p + i q).
+template <int N, int SLOT0 = 0, typename Hook = NoHook>
+__device__ __forceinline__ void diff_fft(const float (&p)[16], const float (&q)[16], C2<float> (&zv)[16], const C2<float>* tab, C2<float>* xb, int tid,
+                                         Hook&& hook = Hook{}) {
+    static_for<0, 16>([&](auto mc) {
+        constexpr int m = decltype(mc)::value;
+        zv[m].x = right_of<m, N / 16>(p, tid) - p[m];
+        zv[m].y = right_of<m, N / 16>(q, tid) - q[m];
+    });
+    fft_line<float, N, false, SLOT0>(zv, tab, tab + N / 2, xb, tid, hook);
+}
+// (the filters applied to zv: spectral_filter_m1.inc, spectral_filter_f2.inc)
+
 // Which arithmetic a `precise` request gets.  The all-float32 mode (deriv_core, DIFF32) computes first derivatives at float32 accuracy
 // for any input; its viscous term carries an amplification of nu |k| relative to them, rms nu pi N / (sqrt(3) L) over the spectrum
 // (1.9 at the headline configuration: 1.1e-6 rel-L2 against the float64 oracle, 4e-6 worst case over nu <= 1 on resolved fields;
@@ -145,6 +167,14 @@ inline int spec_resolve_precise(int precise, double nu, int nx, double Lx, int n
     const bool fx = !pow2_in_range(nx) || spec_f32_mode(precise, nu, nx, Lx);
     const bool fy = !pow2_in_range(ny) || spec_f32_mode(precise, nu, ny, Ly);
     return fx && fy ? 0 : 2;
+}
+
+// One pass along an axis of length n, a power of two in [64, 1024]: f(integral_constant<int, n>, TF{}) with the forward transforms' type TF the
+// arithmetic of the `precise` request -- double (float64 forward transforms) or float (the all-float32 mode).
+template <typename F>
+int dispatch_spec(int n, int precise, double nu, double len, F&& f) {
+    const bool f32 = spec_f32_mode(precise, nu, n, len);
+    return dispatch_pow2(n, "spectral", [&](auto nc) { return f32 ? f(nc, float{}) : f(nc, double{}); });
 }
 
 // workgroups per launch (grid-stride over tiles): 2 generations per CU -- each generation pays the twiddle-table

@@ -1,7 +1,11 @@
 // Kernel templates and launchers of the Fourier-spectral residual (forward direction), shared by the two translation units that
 // instantiate them: spectral_kernels.hip (whole grids: the single-GPU entry points) and spectral_seg_kernels.hip (the slab-decomposed
 // forms that read / write the all-to-all buffers in place).  Two units so that the instantiations of one do not disturb the register
-// allocation of the other (the marching row pass runs at 252 of 256 VGPRs) and build in parallel.
+// allocation of the other (the marching row pass was written to run at 252 of 256 VGPRs) and build in parallel.
+// What the compiler gives the marching kernel today (hipcc of ROCm 7.2, tools/resusage.py; VGPRs / bytes of scratch per lane), N = 64, 128, 256,
+// 512, 1024:  whole grids 256 / 12, 12, 12, 20, 24;  SEGP 256 / 20, 20, 20, 24, 40 -- it sits AT the register limit and spills a few values.
+// Text that two kernels share stands once: as functions where the assembly listing stayed the same (diff_fft, at_byte: spectral_common.h), as
+// included fragments (spectral_*.inc) where a function changed registers or schedule (DESIGN_HISTORY.md).
 //
 // Fourier-spectral back-end of the periodic Navier-Stokes residual, gfx950.
 // Operator definition: oracle/periodic.py (spectral_residual); no reference symbol exists
@@ -94,25 +98,16 @@ __device__ __forceinline__ void deriv_core(const float (&uf)[16], const float (&
         // amplification of nu |k| relative to the first derivatives (rms nu pi N / (sqrt(3) L)); the host picks this mode for a
         // `precise` request only while that factor is small (spec_precise_in_f32), and the float64 forward transform otherwise.
         C2<float> zv[16];
-        static_for<0, 16>([&](auto mc) {
-            constexpr int m = decltype(mc)::value;
-            zv[m].x = right_of<m, N / 16>(uf, tid) - uf[m];
-            zv[m].y = right_of<m, N / 16>(vf, tid) - vf[m];
-        });
-        fft_line<float, N, false, P>(zv, tabI, tabI2, xbI, tid, hook);
+        diff_fft<N, P>(uf, vf, zv, tabI, xbI, tid, hook);
         int te = tid;
         asm volatile("" : "+v"(te), "+v"(zv[0].x));
         const float c1h = (float)(0.5 * k.c1), c2h = (float)(0.5 * k.c2);
         static_for<0, 16>([&](auto mc) {
             constexpr int m = decltype(mc)::value;
-            int ko, ke;
-            wavenumber<N, m>(te, ko, ke);
-            const float ct = ctab[ke < 0 ? -ke : ke];                        // k cot(pi k / N), even in k, 0 at k = 0 and at the Nyquist mode
-            const float ar = ct * c1h, ai = (float)ko * c1h;                 // M1 = ar - i ai
-            a[m].x = ar * zv[m].x + ai * zv[m].y; a[m].y = ar * zv[m].y - ai * zv[m].x;
-            const float kf = (float)ke * c2h;
-            const float br = kf * (float)ke, bi = kf * ct;                   // F2 = -(br + i bi)
-            b[m].x -= br * zv[m].x - bi * zv[m].y; b[m].y -= br * zv[m].y + bi * zv[m].x;
+#include "spectral_filter_m1.inc"
+            a[m].x = ar * zv[m].x + ai * zv[m].y; a[m].y = ar * zv[m].y - ai * zv[m].x;        // i k FFT(u + i v) = M1 D
+#include "spectral_filter_f2.inc"
+            b[m].x -= br * zv[m].x - bi * zv[m].y; b[m].y -= br * zv[m].y + bi * zv[m].x;        // nu k^2 FFT(u + i v) = F2 D
         });
     } else {
     // ---- velocity: Z1 = FFT(u + i v)
@@ -237,43 +232,8 @@ __global__ __launch_bounds__(kSpecThreads) void spec_ypass_kernel(const float* _
         deriv_core<N, TF, false>(uf, vf, pf, a, b, tabF, tabI, xb, tidv, k, hook);
         // (touching the epilogue's five streams one transform ahead, one dword per 64 bytes, to have the lines in L2 when the
         //  epilogue asks: 0.783 -> 0.805 ms at every slot tried, round-2 A/B -- the second wave of the SIMD already covers that latency)
-        // epilogue in two halves (bounds the registers in flight next to the prefetched line): u_prev, v_prev and the
-        // x-pass partials in, residuals out
-        float tu[16], tv[16];                                            // (u - u_prev)/dt, (v - v_prev)/dt: shared by both back-ends
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            float pu[8], pv[8], pd[8], qu[8], qv[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const size_t c = base + TPF * (8 * h + i);
-                constexpr bool NT = FUSE_FD;
-                if constexpr (SEGP) {
-                    const int so = seg_col(pk, TPF * (8 * h + i));
-                    pu[i] = ld_seg<NT>(seg_rsrc(pk.pu), pbyte, so); pv[i] = ld_seg<NT>(seg_rsrc(pk.pv), pbyte, so); pd[i] = ld_seg<NT>(seg_rsrc(pk.pd), pbyte, so);
-                } else {
-                pu[i] = ld_stream<NT>(ru + c); pv[i] = ld_stream<NT>(rv + c); pd[i] = ld_stream<NT>(rd + c);
-                }
-                qu[i] = ld_stream<NT>(up + c); qv[i] = ld_stream<NT>(vp + c);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int m = 8 * h + i;
-                // explicitly rounded products: the fused and the plain instantiation must not differ by an FMA contraction here
-                tu[m] = __fmul_rn(uf[m] - qu[i], k.inv_dt); tv[m] = __fmul_rn(vf[m] - qv[i], k.inv_dt);
-            }
-            if (valid) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int m = 8 * h + i;
-                    const size_t c = base + TPF * m;
-                    // one fixed rounding sequence (the compiler may not re-associate or contract differently per instantiation)
-                    constexpr bool NT = FUSE_FD;
-                    st_stream<NT>(ru + c, __fadd_rn(__fmaf_rn(vf[m], a[m].x, __fadd_rn(tu[m], pu[i])), b[m].x));
-                    st_stream<NT>(rv + c, __fadd_rn(__fmaf_rn(vf[m], a[m].y, __fadd_rn(tv[m], pv[i])), b[m].y));
-                    st_stream<NT>(rd + c, pd[i] + a[m].y);
-                }
-            }
-        }
+        constexpr bool NT = FUSE_FD;        // non-temporal streams: in the fused pass only (see ld_stream)
+#include "spectral_row_epilogue.inc"
         if constexpr (FUSE_FD) {
             // The stencil back-end, AFTER the spectral epilogue: the spectral derivatives (64 registers) are dead by now,
             // which is what lets eight slots of eight streams be in flight per phase; the time-derivative terms are kept
@@ -306,22 +266,12 @@ __global__ __launch_bounds__(kSpecThreads) void spec_ypass_kernel(const float* _
                     static_for<0, 8>([&](auto ic) {
                         constexpr int i = decltype(ic)::value;
                         constexpr int m = 8 * h + i;
-                        const size_t c = base + TPF * m;
+                        const size_t co = base + TPF * m;
                         const float ucc = uf[m], vcc = vf[m];
                         const float ul = left_of<m, TPF>(uf, tidv), ur = right_of<m, TPF>(uf, tidv);
                         const float vl = left_of<m, TPF>(vf, tidv), vr = right_of<m, TPF>(vf, tidv);
-                        const float ux = (un_[i] - um[i]) * fk.inv_2dx, uy = (ur - ul) * fk.inv_2dy;
-                        const float vx = (vn_[i] - vm[i]) * fk.inv_2dx, vy = (vr - vl) * fk.inv_2dy;
-                        const float px = (pn_[i] - pm[i]) * fk.inv_2dx, py = (pr[i] - pl[i]) * fk.inv_2dy;
-                        // second differences as (a - c) - (c - b): neighbouring values of a resolved field are within a factor 2 of each
-                        // other, so both first differences are EXACT in float32 (Sterbenz) and the only rounding is relative to the second
-                        // difference itself -- the accuracy of the float64 sum without ~28 double-rate instructions per point
-                        // (this pass is VALU-issue-bound, unlike the standalone stencil kernel, which keeps the float64 form)
-                        const float lu = ((un_[i] - ucc) - (ucc - um[i])) * fk.inv_dx2f + ((ur - ucc) - (ucc - ul)) * fk.inv_dy2f;
-                        const float lv = ((vn_[i] - vcc) - (vcc - vm[i])) * fk.inv_dx2f + ((vr - vcc) - (vcc - vl)) * fk.inv_dy2f;
-                        st_stream<true>(fu + c, tu[m] + ucc * ux + vcc * uy + px * fk.inv_rho - fk.nu * lu);
-                        st_stream<true>(fv + c, tv[m] + ucc * vx + vcc * vy + py * fk.inv_rho - fk.nu * lv);
-                        st_stream<true>(fd + c, ux + vy);
+                        const float u_m = um[i], u_n = un_[i], v_m = vm[i], v_n = vn_[i], p_m = pm[i], p_n = pn_[i], p_l = pl[i], p_r = pr[i];
+#include "spectral_fd_point.inc"
                     });
                 }
             });
@@ -432,37 +382,8 @@ __global__ __launch_bounds__(kSpecThreads) void spec_rowmarch_kernel(const float
             const size_t base = gbase + (size_t)ii * N;
             unsigned pbyte = 0;                                                 // SEGP: this lane's first column of row ii inside one source rank's block
             if constexpr (SEGP) pbyte = (unsigned)((((size_t)g * nx + (size_t)ii) << pk.shift) + (size_t)tid) * 4u;
-            float tu[16], tv[16];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                float pu[8], pv[8], pd[8], qu[8], qv[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const size_t c2 = base + TPF * (8 * h + i);
-                    if constexpr (SEGP) {
-                        const int so = seg_col(pk, TPF * (8 * h + i));
-                        pu[i] = ld_seg<true>(seg_rsrc(pk.pu), pbyte, so); pv[i] = ld_seg<true>(seg_rsrc(pk.pv), pbyte, so); pd[i] = ld_seg<true>(seg_rsrc(pk.pd), pbyte, so);
-                    } else {
-                    pu[i] = ld_stream<true>(ru + c2); pv[i] = ld_stream<true>(rv + c2); pd[i] = ld_stream<true>(rd + c2);
-                    }
-                    qu[i] = ld_stream<true>(up + c2); qv[i] = ld_stream<true>(vp + c2);
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int m = 8 * h + i;
-                    tu[m] = __fmul_rn(uf[m] - qu[i], k.inv_dt); tv[m] = __fmul_rn(vf[m] - qv[i], k.inv_dt);
-                }
-                if (valid) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const int m = 8 * h + i;
-                        const size_t c2 = base + TPF * m;
-                        st_stream<true>(ru + c2, __fadd_rn(__fmaf_rn(vf[m], a[m].x, __fadd_rn(tu[m], pu[i])), b[m].x));
-                        st_stream<true>(rv + c2, __fadd_rn(__fmaf_rn(vf[m], a[m].y, __fadd_rn(tv[m], pv[i])), b[m].y));
-                        st_stream<true>(rd + c2, pd[i] + a[m].y);
-                    }
-                }
-            }
+            constexpr bool NT = true;
+#include "spectral_row_epilogue.inc"
             __builtin_amdgcn_sched_barrier(0);
             // the stencil: row i-1 from the park image / pm, row i+1 = the prefetched next row, columns j-1 / j+1 by lane rotates
             {
@@ -484,19 +405,13 @@ __global__ __launch_bounds__(kSpecThreads) void spec_rowmarch_kernel(const float
                 if (valid) static_for<0, 8>([&](auto ic) {
                     constexpr int i = decltype(ic)::value;
                     constexpr int m = 8 * h + i;
-                    const size_t c2 = base + TPF * m;
+                    const size_t co = base + TPF * m;
                     const float ucc = uf[m], vcc = vf[m];
                     const float ul = left_of<m, TPF>(uf, tidv), ur = right_of<m, TPF>(uf, tidv);
                     const float vl = left_of<m, TPF>(vf, tidv), vr = right_of<m, TPF>(vf, tidv);
-                    const float pl = left_of<m, TPF>(pf, tidv), pr = right_of<m, TPF>(pf, tidv);
-                    const float ux = (nu[m] - um[i]) * fk.inv_2dx, uy = (ur - ul) * fk.inv_2dy;
-                    const float vx = (nv[m] - vm[i]) * fk.inv_2dx, vy = (vr - vl) * fk.inv_2dy;
-                    const float px = (np[m] - pm[m]) * fk.inv_2dx, py = (pr - pl) * fk.inv_2dy;
-                    const float lu = ((nu[m] - ucc) - (ucc - um[i])) * fk.inv_dx2f + ((ur - ucc) - (ucc - ul)) * fk.inv_dy2f;
-                    const float lv = ((nv[m] - vcc) - (vcc - vm[i])) * fk.inv_dx2f + ((vr - vcc) - (vcc - vl)) * fk.inv_dy2f;
-                    st_stream<true>(fu + c2, tu[m] + ucc * ux + vcc * uy + px * fk.inv_rho - fk.nu * lu);
-                    st_stream<true>(fv + c2, tv[m] + ucc * vx + vcc * vy + py * fk.inv_rho - fk.nu * lv);
-                    st_stream<true>(fd + c2, ux + vy);
+                    const float p_l = left_of<m, TPF>(pf, tidv), p_r = right_of<m, TPF>(pf, tidv);
+                    const float u_m = um[i], u_n = nu[m], v_m = vm[i], v_n = nv[m], p_m = pm[m], p_n = np[m];
+#include "spectral_fd_point.inc"
                 });
             });
             // this row becomes the row above
@@ -532,6 +447,7 @@ __global__ __launch_bounds__(kSpecThreads) void spec_xpass_kernel(const float* _
         else return (size_t)r * ny;
     };
     using L = SpecLds<N, TF>;
+    using CL = L;
     constexpr int TPF = L::TPF, CW = L::LINES, SF = L::STAGE_F;
     constexpr int ROWS_PER_IT = kSpecThreads / CW;
     constexpr int NR = N / ROWS_PER_IT;                 // staged elements per thread and field (= 16 for every N)
@@ -545,9 +461,7 @@ __global__ __launch_bounds__(kSpecThreads) void spec_xpass_kernel(const float* _
     // after the transforms have released it -- global-load latency hides under the FFT phase.
     float su[NR], sv[NR], sp[NR];
     auto tile_coords = [&](long t, int& j0, size_t& g) {
-        // neighbouring tiles -> same XCD (shared lines); tiles are walked from the LAST grid to the first (see launch_xpass)
-        const long lt = ntiles - 1 - (long)xcd_remap((unsigned)t, (unsigned)ntiles);
-        j0 = (int)(lt % tiles_per_grid) * CW;
+#include "spectral_tile_coords.inc"
         g = (size_t)(lt / tiles_per_grid) * (SEG ? ((size_t)ny << sg.shift) : (size_t)N * ny);
     };
     auto issue_loads = [&](long t) {
@@ -567,15 +481,7 @@ __global__ __launch_bounds__(kSpecThreads) void spec_xpass_kernel(const float* _
     if (PREFETCH && t < ntiles) issue_loads(t);
     for (; t < ntiles; t += gridDim.x) {
         if (!PREFETCH) issue_loads(t);
-        // thread-constant indices are recomputed per tile from an opaque copy of the thread id: cheaper than the
-        // spill/reload the compiler otherwise chooses for values that are live across the whole tile body
-        int tx = threadIdx.x;
-        asm volatile("" : "+v"(tx));
-        const int wave = tx / kWave, lane = tx % kWave;
-        const int sub = lane / TPF, tid = lane % TPF;
-        const int line = wave * L::FPW + sub;
-        unsigned char* xb = lines + (size_t)line * L::LINE_BYTES;
-        float* my_stage = reinterpret_cast<float*>(xb) + (line % L::SKEW_MOD) * L::SKEW_DW;   // skewed: conflict-free staging
+#include "spectral_col_line.inc"
         int j0; size_t g;
         tile_coords(t, j0, g);
         {   // ---- staged registers -> LDS [line][field][row]
@@ -673,29 +579,24 @@ __global__ __launch_bounds__(kSplitThreads) void spec_xpass_split_kernel(const f
                                                                           int ny, int tiles_per_grid, long ntiles, SpecK k, SegK sg) {
     using L = SpecLds<N, TF>;
     using SL = SplitLds<N, TF>;
+    using CL = SL;
     constexpr int TPF = L::TPF, CW = L::LINES, SF = L::STAGE_F;
     constexpr int MROWS = 256 / CW;                       // rows of the tile one memory-wave instruction step covers
     constexpr int NR = N / MROWS;                         // elements per memory lane and field (= 32 for every N)
     static_assert(NR == 32, "tile geometry");
-    // a memory lane owns rows 4 cr .. 4 cr + 3 of every block of 4 MROWS rows: element i <-> row 4 cr + (i & 3) + 4 MROWS (i >> 2), so
-    // that its four consecutive rows move through LDS as ONE 16-byte access (24 + 24 LDS instructions per exchange instead of 96 + 96)
     static_assert(SL::TOTAL <= 160 * 1024, "LDS budget");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     C2<TF>* tabF; C2<float>* tabI; unsigned char* lines;
     spec_setup<N, TF, kSplitThreads>(smem, tabF, tabI, lines);
     auto tile_coords = [&](long t, int& j0, size_t& g) {
-        const long lt = ntiles - 1 - (long)xcd_remap((unsigned)t, (unsigned)ntiles);
-        j0 = (int)(lt % tiles_per_grid) * CW;
+#include "spectral_tile_coords.inc"
         g = (size_t)(lt / tiles_per_grid) * (SEG ? ((size_t)ny << sg.shift) : (size_t)N * ny);
     };
     long t = blockIdx.x;
     if (t >= ntiles) return;                               // uniform over the workgroup (the launch never has more workgroups than tiles)
     if (threadIdx.x >= kSpecThreads) {
         // ================= memory waves =================
-        int mt = threadIdx.x - kSpecThreads;
-        asm volatile("" : "+v"(mt));
-        const int cc = mt % CW, cr = mt / CW;
-        float* stage = reinterpret_cast<float*>(lines + (size_t)cc * SL::LINE_BYTES) + (cc % 8) * SL::SKEW_DW + 4 * cr;       // [field][row]
+#include "spectral_split_mem.inc"
         float R[3][NR];
         // addresses: a uniform grid base (scalar registers) + a 32-bit BYTE offset per lane, recomputed per tile from an opaque
         // seed (left alone, the compiler keeps 32 precomputed 64-bit row offsets alive across the whole loop and spills them)
@@ -709,8 +610,6 @@ __global__ __launch_bounds__(kSplitThreads) void spec_xpass_split_kernel(const f
             else o = r0 * (unsigned)ny;
             return (seed + o + (unsigned)(i & 3) * (unsigned)ny) * 4u;
         };
-        auto at = [](const float* base, unsigned byte_off) -> const float& { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off); };
-        auto at_w = [](float* base, unsigned byte_off) -> float& { return *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off); };
         // (round 4, VERDICT r3 item 5 (a): buffer loads / stores -- grid descriptor + ONE lane offset per tile + a scalar row offset per access, no vector
         // instruction per row piece -- were tried: column pass 0.493 ms against 0.490, no gain, profiles/r04_ab_xpass_buffer_addressing.log)
         auto load_tile = [&](long tt) {
@@ -723,7 +622,7 @@ __global__ __launch_bounds__(kSplitThreads) void spec_xpass_split_kernel(const f
 #pragma unroll
             for (int i = 0; i < NR; ++i) {
                 const unsigned c = off32(i, col, crv);
-                R[0][i] = at(ug, c); R[1][i] = at(vg, c); R[2][i] = at(pg, c);
+                R[0][i] = at_byte(ug, c); R[1][i] = at_byte(vg, c); R[2][i] = at_byte(pg, c);
             }
         };
         auto store_tile = [&](long tt) {
@@ -737,17 +636,12 @@ __global__ __launch_bounds__(kSplitThreads) void spec_xpass_split_kernel(const f
 #pragma unroll
                 for (int i = 0; i < NR; ++i) {
                     const unsigned c = off32(i, col, crv);
-                    at_w(ug, c) = R[0][i]; at_w(vg, c) = R[1][i]; at_w(pg, c) = R[2][i];
+                    at_byte(ug, c) = R[0][i]; at_byte(vg, c) = R[1][i]; at_byte(pg, c) = R[2][i];
                 }
             }
         };
         load_tile(t);
-#pragma unroll
-        for (int q = 0; q < NR / 4; ++q)
-#pragma unroll
-            for (int f = 0; f < 3; ++f)
-                *reinterpret_cast<float4*>(stage + f * SF + 4 * MROWS * q) = make_float4(R[f][4 * q], R[f][4 * q + 1], R[f][4 * q + 2], R[f][4 * q + 3]);
-        __syncthreads();                                                        // inputs of the first tile are staged
+#include "spectral_split_stage.inc"
         long prev = -1;
         for (; t < ntiles; t += gridDim.x) {
             const long tn = t + gridDim.x;
@@ -778,13 +672,7 @@ __global__ __launch_bounds__(kSplitThreads) void spec_xpass_split_kernel(const f
     //  the two transform waves of a SIMD run out of step: 0.520 -> 0.535 ms; static s_setprio 1 for waves 4..7: 0.520 -> 0.535 ms)
     __syncthreads();                                                            // inputs of the first tile are staged
     for (; t < ntiles; t += gridDim.x) {
-        int tx = threadIdx.x;
-        asm volatile("" : "+v"(tx));
-        const int wave = tx / kWave, lane = tx % kWave;
-        const int sub = lane / TPF, tid = lane % TPF;
-        const int line = wave * L::FPW + sub;
-        unsigned char* xb = lines + (size_t)line * SL::LINE_BYTES;
-        float* my_stage = reinterpret_cast<float*>(xb) + (line % 8) * SL::SKEW_DW;
+#include "spectral_col_line.inc"
         int tidv = tid;
         asm volatile("" : "+v"(tidv));
         float uf[16], vf[16], pf[16];
@@ -875,6 +763,58 @@ int launch_rowmarch(const float* u, const float* v, const float* p, const float*
     const long wgs = (nchunks + ML::L::LINES - 1) / ML::L::LINES;
     hipLaunchKernelGGL(kern, dim3(capped_grid(wgs, device_cus())), dim3(kSpecThreads), ML::TOTAL, s, u, v, p, up, vp, ru, rv, rd, fu, fv, fd, nx, fk, k, hk, R, chunks_per_grid, nchunks, pk);
     return check_launch("residual_both_rowpass");
+}
+
+// ---- host side shared by the two translation units: the constants folded once, one choice of arithmetic, one body per pass ----
+// (each entry point keeps its own argument checks and messages: spectral_kernels.hip, spectral_seg_kernels.hip)
+inline SpecK make_spec_k(double len, int n, double rho, double nu, double dt_or_0) {       // dt_or_0 = 0: the column pass, which has no time term
+    const double ks = 2.0 * M_PI / len;
+    return SpecK{ks / n, ks / (rho * n), nu * ks * ks / n, dt_or_0 != 0 ? (float)(1.0 / dt_or_0) : 0.f};
+}
+inline FdK make_fd_k(double dx, double dy, double rho, double nu) {
+    return FdK{(float)(1.0 / (2 * dx)), (float)(1.0 / (2 * dy)), (float)(1.0 / rho), (float)nu, 1.0 / (dx * dx), 1.0 / (dy * dy),
+               (float)(1.0 / (dx * dx)), (float)(1.0 / (dy * dy))};
+}
+inline HaloK make_halo_k(const float* top, const float* bot, long fstride, int batch, int ny) {
+    return HaloK{top, bot, fstride > 0 ? fstride : (long)batch * ny};
+}
+inline int check_halo(const char* what, const float* top, const float* bot, long fstride, int batch, int ny) {
+    if (!top || !bot) return fail(NNS_ERR_INVALID_ARG, "%s: halo_top and halo_bot are required", what);
+    if (fstride != 0 && fstride < (long)batch * ny)
+        return fail(NNS_ERR_INVALID_ARG, "%s: halo_field_stride=%ld must be 0 (= batch * ny) or >= batch * ny = %ld", what, fstride, (long)batch * ny);
+    return NNS_OK;
+}
+
+template <bool SEG>
+int xpass_fft(const float* u, const float* v, const float* p, float* ru, float* rv, float* rd, int batch, int nx, int ny,
+              double Lx, double rho, double nu, int precise, hipStream_t s, const SegK& sg = SegK{}) {
+    const SpecK k = make_spec_k(Lx, nx, rho, nu, 0);
+    return dispatch_spec(nx, precise, nu, Lx, [&](auto n, auto tf) {
+        return launch_xpass<decltype(n)::value, decltype(tf), SEG>(u, v, p, ru, rv, rd, batch, ny, k, s, sg);
+    });
+}
+template <bool SEGP>
+int ypass_fft(const float* u, const float* v, const float* p, const float* up, const float* vp, float* ru, float* rv, float* rd,
+              int batch, int nx, int ny, double dt, double Ly, double rho, double nu, int precise, hipStream_t s, const PartK& pk = PartK{}) {
+    const SpecK k = make_spec_k(Ly, ny, rho, nu, dt);
+    return dispatch_spec(ny, precise, nu, Ly, [&](auto n, auto tf) {
+        return launch_ypass<decltype(n)::value, decltype(tf), false, SEGP>(u, v, p, up, vp, ru, rv, rd, (long)batch * nx, k, s, nullptr, nullptr, nullptr, 1,
+                                                                           FdK{}, HaloK{}, pk);
+    });
+}
+// The fused row pass (stencil + spectral finish): the float64-forward spec_ypass_kernel, or the marching kernel in the all-float32 mode.
+template <bool SEGP>
+int fused_rowpass(const float* u, const float* v, const float* p, const float* up, const float* vp, float* fu, float* fv, float* fd,
+                  float* ru, float* rv, float* rd, int batch, int nx, int ny, double dt, double dx, double Ly, double rho, double nu, int precise,
+                  const HaloK& hk, hipStream_t s, const PartK& pk = PartK{}) {
+    const SpecK k = make_spec_k(Ly, ny, rho, nu, dt);
+    const FdK fk = make_fd_k(dx, Ly / ny, rho, nu);
+    return dispatch_spec(ny, precise, nu, Ly, [&](auto n, auto tf) {
+        constexpr int N = decltype(n)::value;
+        const long nrows = (long)batch * nx;
+        if constexpr (sizeof(tf) == 8) return launch_ypass<N, double, true, SEGP>(u, v, p, up, vp, ru, rv, rd, nrows, k, s, fu, fv, fd, nx, fk, hk, pk);
+        else return launch_rowmarch<N, SEGP>(u, v, p, up, vp, ru, rv, rd, fu, fv, fd, batch, nx, march_chunk_rows<N>(nrows, nx), k, fk, hk, s, pk);
+    });
 }
 
 }  // namespace

@@ -12,14 +12,7 @@ int xpass(const float* u, const float* v, const float* p, float* ru, float* rv, 
     if (!u || !v || !p || !ru || !rv || !rd || batch < 1 || ny < 1) return fail(NNS_ERR_INVALID_ARG, "spec_residual_xpass: bad args");
     if (Lx == 0 || rho == 0) return fail(NNS_ERR_INVALID_ARG, "spec_residual_xpass: Lx, rho must be non-zero");
     if (!pow2_in_range(nx)) return dense_xpass(u, v, p, ru, rv, rd, batch, nx, ny, Lx, rho, nu, s);          // any other length 3 .. 2048: circulant matrices, float64
-    const double ks = 2.0 * M_PI / Lx;
-    SpecK k{ks / nx, ks / (rho * nx), nu * ks * ks / nx, 0.f};
-    const bool f64 = !spec_f32_mode(precise, nu, nx, Lx);
-    return dispatch_pow2(nx, "spectral", [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        return f64 ? launch_xpass<N, double>(u, v, p, ru, rv, rd, batch, ny, k, s)
-                   : launch_xpass<N, float>(u, v, p, ru, rv, rd, batch, ny, k, s);
-    });
+    return xpass_fft<false>(u, v, p, ru, rv, rd, batch, nx, ny, Lx, rho, nu, precise, s);
 }
 
 int ypass(const float* u, const float* v, const float* p, const float* up, const float* vp, float* ru, float* rv, float* rd,
@@ -27,15 +20,7 @@ int ypass(const float* u, const float* v, const float* p, const float* up, const
     if (!u || !v || !p || !up || !vp || !ru || !rv || !rd || batch < 1 || nx < 1) return fail(NNS_ERR_INVALID_ARG, "spec_residual_ypass: bad args");
     if (Ly == 0 || rho == 0 || dt == 0) return fail(NNS_ERR_INVALID_ARG, "spec_residual_ypass: Ly, rho, dt must be non-zero");
     if (!pow2_in_range(ny)) return dense_ypass(u, v, p, up, vp, ru, rv, rd, batch, nx, ny, dt, Ly, rho, nu, s);
-    const double ks = 2.0 * M_PI / Ly;
-    SpecK k{ks / ny, ks / (rho * ny), nu * ks * ks / ny, (float)(1.0 / dt)};
-    const long nrows = (long)batch * nx;
-    const bool f64 = !spec_f32_mode(precise, nu, ny, Ly);
-    return dispatch_pow2(ny, "spectral", [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        return f64 ? launch_ypass<N, double>(u, v, p, up, vp, ru, rv, rd, nrows, k, s)
-                   : launch_ypass<N, float>(u, v, p, up, vp, ru, rv, rd, nrows, k, s);
-    });
+    return ypass_fft<false>(u, v, p, up, vp, ru, rv, rd, batch, nx, ny, dt, Ly, rho, nu, precise, s);
 }
 
 // FD 5-point + spectral residual of the same inputs: spectral x-pass, then the row pass with the stencil fused in.
@@ -62,17 +47,9 @@ int residual_both(const float* u, const float* v, const float* p, const float* u
         // profiles/r04_grouped_launches.txt)
         if (int rc = xpass(u, v, p, ru, rv, rd, batch, nx, ny, Lx, rho, nu, precise, s)) return rc;
     }
-    const double ks = 2.0 * M_PI / Ly, dx = slab ? Lx : Lx / nx, dy = Ly / ny;          // a row slab passes the grid spacing itself in Lx
-    const SpecK k{ks / ny, ks / (rho * ny), nu * ks * ks / ny, (float)(1.0 / dt)};
-    const FdK fk{(float)(1.0 / (2 * dx)), (float)(1.0 / (2 * dy)), (float)(1.0 / rho), (float)nu, 1.0 / (dx * dx), 1.0 / (dy * dy),
-                 (float)(1.0 / (dx * dx)), (float)(1.0 / (dy * dy))};
-    const HaloK hk{halo_top, halo_bot, halo_fstride > 0 ? halo_fstride : (long)batch * ny};
-    return dispatch_pow2(ny, "spectral", [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        const long nrows = (long)batch * nx;
-        if (!spec_f32_mode(precise, nu, ny, Ly)) return launch_ypass<N, double, true>(u, v, p, up, vp, ru, rv, rd, nrows, k, s, fu, fv, fd, nx, fk, hk);
-        return launch_rowmarch<N>(u, v, p, up, vp, ru, rv, rd, fu, fv, fd, batch, nx, march_chunk_rows<N>(nrows, nx), k, fk, hk, s);
-    });
+    const double dx = slab ? Lx : Lx / nx;                                              // a row slab passes the grid spacing itself in Lx
+    return fused_rowpass<false>(u, v, p, up, vp, fu, fv, fd, ru, rv, rd, batch, nx, ny, dt, dx, Ly, rho, nu, precise,
+                                make_halo_k(halo_top, halo_bot, halo_fstride, batch, ny), s);
 }
 
 }  // namespace
@@ -93,9 +70,7 @@ NNS_API int nns_residual_both_rowpass_halo_f32(const float* u, const float* v, c
                                                float* fd_r_u, float* fd_r_v, float* fd_r_div, float* sp_r_u, float* sp_r_v, float* sp_r_div,
                                                int batch, int nx_local, int ny, long halo_field_stride, double dt, double dx, double Ly, double rho, double nu,
                                                int precise, void* stream) {
-    if (!halo_top || !halo_bot) return fail(NNS_ERR_INVALID_ARG, "residual_both_rowpass_halo: halo_top and halo_bot are required");
-    if (halo_field_stride != 0 && halo_field_stride < (long)batch * ny)
-        return fail(NNS_ERR_INVALID_ARG, "residual_both_rowpass_halo: halo_field_stride=%ld must be 0 (= batch * ny) or >= batch * ny = %ld", halo_field_stride, (long)batch * ny);
+    if (int rc = check_halo("residual_both_rowpass_halo", halo_top, halo_bot, halo_field_stride, batch, ny)) return rc;
     return residual_both(u, v, p, u_prev, v_prev, fd_r_u, fd_r_v, fd_r_div, sp_r_u, sp_r_v, sp_r_div, batch, nx_local, ny, dt, dx, Ly, rho, nu, precise,
                          as_stream(stream), false, halo_top, halo_bot, halo_field_stride);
 }

@@ -42,15 +42,7 @@ NNS_API int nns_spec_residual_xpass_seg_f32(const float* u, const float* v, cons
     if (!pow2_in_range(nx)) return fail(NNS_ERR_UNSUPPORTED, "spec_residual_xpass_seg: nx=%d must be a power of two in [64, 1024] (the segmented layout exists for the FFT engine only)", nx);
     if (seg_rows < 4 || seg_rows > nx || (seg_rows & (seg_rows - 1)) || seg_stride < (long)seg_rows * ny)
         return fail(NNS_ERR_INVALID_ARG, "spec_residual_xpass_seg: seg_rows=%d must be a power of two in [4, nx=%d] and seg_stride=%ld >= seg_rows * ny", seg_rows, nx, seg_stride);
-    const double ks = 2.0 * M_PI / Lx;
-    const SpecK k{ks / nx, ks / (rho * nx), nu * ks * ks / nx, 0.f};
-    const bool f64 = !spec_f32_mode(precise, nu, nx, Lx);
-    const SegK sg{__builtin_ctz((unsigned)seg_rows), seg_stride};
-    return dispatch_pow2(nx, "spectral", [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        return f64 ? launch_xpass<N, double, true>(u, v, p, r_u, r_v, r_div, batch, ny, k, as_stream(stream), sg)
-                   : launch_xpass<N, float, true>(u, v, p, r_u, r_v, r_div, batch, ny, k, as_stream(stream), sg);
-    });
+    return xpass_fft<true>(u, v, p, r_u, r_v, r_div, batch, nx, ny, Lx, rho, nu, precise, as_stream(stream), SegK{__builtin_ctz((unsigned)seg_rows), seg_stride});
 }
 
 NNS_API int nns_spec_residual_ypass_seg_f32(const float* u, const float* v, const float* p, const float* u_prev, const float* v_prev,
@@ -61,15 +53,7 @@ NNS_API int nns_spec_residual_ypass_seg_f32(const float* u, const float* v, cons
     if (Ly == 0 || rho == 0 || dt == 0) return fail(NNS_ERR_INVALID_ARG, "spec_residual_ypass_seg: Ly, rho, dt must be non-zero");
     PartK pk;
     if (int rc = check_part("spec_residual_ypass_seg", part_u, part_v, part_div, ny, seg_cols, seg_stride, batch, nx, pk)) return rc;
-    const double ks = 2.0 * M_PI / Ly;
-    const SpecK k{ks / ny, ks / (rho * ny), nu * ks * ks / ny, (float)(1.0 / dt)};
-    const long nrows = (long)batch * nx;
-    const bool f64 = !spec_f32_mode(precise, nu, ny, Ly);
-    return dispatch_pow2(ny, "spectral", [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        return f64 ? launch_ypass<N, double, false, true>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, nrows, k, as_stream(stream), nullptr, nullptr, nullptr, 1, FdK{}, HaloK{}, pk)
-                   : launch_ypass<N, float, false, true>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, nrows, k, as_stream(stream), nullptr, nullptr, nullptr, 1, FdK{}, HaloK{}, pk);
-    });
+    return ypass_fft<true>(u, v, p, u_prev, v_prev, r_u, r_v, r_div, batch, nx, ny, dt, Ly, rho, nu, precise, as_stream(stream), pk);
 }
 
 NNS_API int nns_residual_both_rowpass_halo_seg_f32(const float* u, const float* v, const float* p, const float* u_prev, const float* v_prev,
@@ -80,23 +64,10 @@ NNS_API int nns_residual_both_rowpass_halo_seg_f32(const float* u, const float* 
                                                    int precise, void* stream) {
     if (!u || !v || !p || !u_prev || !v_prev || !fd_r_u || !fd_r_v || !fd_r_div || !sp_r_u || !sp_r_v || !sp_r_div || batch < 1 || nx_local < 3)
         return fail(NNS_ERR_INVALID_ARG, "residual_both_rowpass_halo_seg: bad args");
-    if (!halo_top || !halo_bot) return fail(NNS_ERR_INVALID_ARG, "residual_both_rowpass_halo_seg: halo_top and halo_bot are required");
-    if (halo_field_stride != 0 && halo_field_stride < (long)batch * ny)
-        return fail(NNS_ERR_INVALID_ARG, "residual_both_rowpass_halo_seg: halo_field_stride=%ld must be 0 (= batch * ny) or >= batch * ny = %ld", halo_field_stride, (long)batch * ny);
+    if (int rc = check_halo("residual_both_rowpass_halo_seg", halo_top, halo_bot, halo_field_stride, batch, ny)) return rc;
     if (Ly == 0 || rho == 0 || dt == 0 || dx == 0) return fail(NNS_ERR_INVALID_ARG, "residual_both_rowpass_halo_seg: dx, Ly, rho, dt must be non-zero");
     PartK pk;
     if (int rc = check_part("residual_both_rowpass_halo_seg", part_u, part_v, part_div, ny, seg_cols, seg_stride, batch, nx_local, pk)) return rc;
-    const int nx = nx_local;
-    const double ks = 2.0 * M_PI / Ly, dy = Ly / ny;
-    const SpecK k{ks / ny, ks / (rho * ny), nu * ks * ks / ny, (float)(1.0 / dt)};
-    const FdK fk{(float)(1.0 / (2 * dx)), (float)(1.0 / (2 * dy)), (float)(1.0 / rho), (float)nu, 1.0 / (dx * dx), 1.0 / (dy * dy),
-                 (float)(1.0 / (dx * dx)), (float)(1.0 / (dy * dy))};
-    const HaloK hk{halo_top, halo_bot, halo_field_stride > 0 ? halo_field_stride : (long)batch * ny};
-    return dispatch_pow2(ny, "spectral", [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        const long nrows = (long)batch * nx;
-        if (!spec_f32_mode(precise, nu, ny, Ly))
-            return launch_ypass<N, double, true, true>(u, v, p, u_prev, v_prev, sp_r_u, sp_r_v, sp_r_div, nrows, k, as_stream(stream), fd_r_u, fd_r_v, fd_r_div, nx, fk, hk, pk);
-        return launch_rowmarch<N, true>(u, v, p, u_prev, v_prev, sp_r_u, sp_r_v, sp_r_div, fd_r_u, fd_r_v, fd_r_div, batch, nx, march_chunk_rows<N>(nrows, nx), k, fk, hk, as_stream(stream), pk);
-    });
+    return fused_rowpass<true>(u, v, p, u_prev, v_prev, fd_r_u, fd_r_v, fd_r_div, sp_r_u, sp_r_v, sp_r_div, batch, nx_local, ny, dt, dx, Ly, rho, nu, precise,
+                               make_halo_k(halo_top, halo_bot, halo_field_stride, batch, ny), as_stream(stream), pk);
 }

@@ -12,7 +12,7 @@ all-to-all (all seven links of a GPU at once).
 STATUS of the "nccl" branch: a one-GPU lease cannot hold two RCCL ranks, so what has run on hardware is (a) the world-1 LOOPBACK
 form (`Transport(loopback=True)` or NNS_COMM_LOOPBACK=1: a rank's messages to "its neighbours" and its all-to-all go through the
 RCCL process group to itself -- device buffers, grouped send/recv, async all_to_all_single, stream-ordered wait(), the int-view
-all-reduce -- tests/test_gpu_rccl_loopback.py) and (b) every multi-rank path on the gloo-staged branch.  Transfers between two
+all-reduce -- tests/test_gpu_multirank.py) and (b) every multi-rank path on the gloo-staged branch.  Transfers between two
 GPUs over xGMI, and the overlap they allow, are first exercised by the driver's multi-GPU bench.
 """
 import os

@@ -8,8 +8,8 @@ Dispatch (csrc/spectral_bwd_kernels.hip, csrc/spectral_common.h), restated in `d
   x-pass     a tile is LINES = 8192 / nx columns of one grid, ceil(ny / LINES) tiles per grid, min(tiles, 512) workgroups stride over them
              (spec_grid_cap).  float32: spec_bwd_xsplit_kernel, memory waves and transform waves; float64: spec_bwd_xpass_kernel<N, double>;
   y-pass     a row group is LINES = 8192 / ny rows of the batch * nx rows, min(groups, 512) workgroups stride over them: spec_bwd_ypass_kernel.
-spec_bwd_xpass_kernel<N, float> is unreachable through the C ABI: launch_bwd hands every float32 x-pass with N * ny < 2^30 to the role-split
-kernel, and ny <= 2048 (kDenseMaxLen) keeps N * ny <= 2^21.  It is compiled and never launched.
+spec_bwd_xpass_kernel exists for float64 forward transforms only: launch_bwd_xpass hands every float32 x-pass to the role-split kernel, whose
+32-bit byte offsets need N * ny < 2^30, and ny <= 2048 (kDenseMaxLen) keeps N * ny <= 2^21 through the C ABI (beyond: NNS_ERR_UNSUPPORTED).
 
 Inputs: grid b of an nx x ny case is five fields (u, v, g_u, g_v, g_div) from one torch.Generator seeded from (nx, ny, b): white noise (N(0, 1), drawn in
 float32), its rfft2 multiplied by (1 + |m|)^-1 (m the integer wavenumber vector), transformed back, scaled to max-abs 1, cast to float32 -- energy up to and

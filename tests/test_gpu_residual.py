@@ -575,21 +575,17 @@ def test_marching_row_pass_chunk_lengths(B, gpu_device):
         assert rel_l2(fo[k].cpu().numpy(), fd[k].cpu().numpy()) < 1e-6
 
 
-@pytest.mark.parametrize('precise', [0, 2])
-def test_column_pass_segments_beyond_32bit_offsets(precise, gpu_device):
-    """The role-split column pass addresses with 32-bit lane offsets inside a grid; a segmented (slab) layout whose source-rank
-    blocks lie >= 2^32 elements apart (the library then takes the kernel with 64-bit row offsets) must give the same numbers as the
-    plain column pass.  Also the float64-forward instantiation of the segmented layout (precise = 2)."""
+def _column_pass_segments_beyond_32bit_offsets(precise, nx, seg):
     import ctypes
     from nns import ops, _lib
-    B, nx, ny, seg = 2, 64, 64, 32
+    B, ny = 2, 64
     stride = (1 << 32) + 4096                                 # elements between the two source-rank blocks of one field
     per = B * seg * ny                                        # one field of one source rank
     need = stride + 3 * per + 64
     free, _ = torch.cuda.mem_get_info()
     if free < 2 * need * 4 + (1 << 30):
         pytest.skip("needs 2 x %.1f GB of device memory" % (need * 4 / 1e9))
-    f = [dev(a) for a in inputs(B, nx)[:3]]
+    f = [dev(a[:, :, :ny]) for a in inputs(B, nx)[:3]]
     ref = ops.spec_residual_xpass(*f, L, RHO, NU, precise=precise)
     big_in = torch.empty(need, dtype=torch.float32, device='cuda')
     big_out = torch.empty(need, dtype=torch.float32, device='cuda')
@@ -604,6 +600,21 @@ def test_column_pass_segments_beyond_32bit_offsets(precise, gpu_device):
         for src in range(nx // seg):
             got = big_out[src * stride + k * per: src * stride + (k + 1) * per].view(B, seg, ny)
             assert torch.equal(got, ref[k][:, src * seg:(src + 1) * seg]), (k, src)
+
+
+@pytest.mark.parametrize('precise', [0, 2])
+def test_column_pass_segments_beyond_32bit_offsets(precise, gpu_device):
+    """The role-split column pass addresses with 32-bit lane offsets inside a grid; a segmented (slab) layout whose source-rank
+    blocks lie >= 2^32 elements apart (the library then takes the kernel with 64-bit row offsets) must give the same numbers as the
+    plain column pass.  Also the float64-forward instantiation of the segmented layout (precise = 2)."""
+    _column_pass_segments_beyond_32bit_offsets(precise, nx=64, seg=32)
+
+
+@pytest.mark.parametrize('precise', [0, 2])
+def test_column_pass_segments_beyond_32bit_offsets_nx256(precise, gpu_device):
+    """The same at nx = 256, two source ranks of 128 rows: the 64-bit-offset column kernel's instantiation WITHOUT the register prefetch of
+    the next tile (launch_xpass: N = 256), where nx = 64 runs the one with it."""
+    _column_pass_segments_beyond_32bit_offsets(precise, nx=256, seg=128)
 
 
 @pytest.mark.parametrize('B,nloc,ny,P,dtype', [(3, 5, 64, 4, torch.float32), (2, 7, 24, 4, torch.float32), (1, 4, 30, 3, torch.float64), (2, 3, 16, 2, torch.float64),
@@ -631,7 +642,8 @@ def _to_seg(parts, P):
     return torch.stack([torch.stack([t[:, :, s * nyl:(s + 1) * nyl] for t in parts]) for s in range(P)]).contiguous()
 
 
-@pytest.mark.parametrize('ny,P,B', [(1024, 8, 5), (1024, 8, 800), (1024, 2, 5), (1024, 16, 5), (256, 4, 5), (256, 4, 3000), (64, 16, 5), (128, 1, 5)])
+@pytest.mark.parametrize('ny,P,B', [(1024, 8, 5), (1024, 8, 800), (1024, 2, 5), (1024, 16, 5), (256, 4, 5), (256, 4, 3000), (64, 16, 5), (128, 1, 5),
+                                    (512, 4, 5)])
 @pytest.mark.parametrize('precise', [0, 2])
 def test_row_passes_read_segmented_partials_in_place(ny, P, B, precise, gpu_device):
     """Round 4: the slab step's row passes read the column-pass partials where the return all-to-all delivers them -- [src][field][grid][row]

@@ -110,7 +110,7 @@ def test_residual_vjp_is_the_adjoint_of_the_jacobian():
 
 @pytest.mark.parametrize('n', [16, 64, 256])
 def test_forward_difference_filters_reproduce_the_spectral_derivatives(n):
-    """The identity behind the all-float32 device mode (csrc/spectral_kernels.hip, deriv_core DIFF32), in float64 where it is exact to
+    """The identity behind the all-float32 device mode (csrc/spectral_fwd.h, deriv_core DIFF32), in float64 where it is exact to
     rounding: with D = FFT(d), d_j = f_{j+1} - f_j (periodic) and theta = 2 pi k / n,
         i k FFT(f) = M1 D,     M1 = (k/2) (cot(theta/2) - i)          (0 at k = 0 and, for odd derivatives, at the Nyquist mode)
         -k^2 FFT(f) = F2 D,    F2 = (k/2) (k + i k cot(theta/2))      (Nyquist mode kept: cot(pi/2) = 0)
