@@ -597,6 +597,21 @@ int nns_spec_ns_step_scalar_adjoint_f32(const float* what0, const float* that0, 
                                         float* mu, float* gbar, void* work, size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly,
                                         double dt, double nu, double drag, double kappa, double gx, double gy, double bx, double by, int nsteps,
                                         void* stream);
+/* Reverse mode of nns_spec_ns_step_linear_f32, with or without its scalar, buoyancy and noise (restatement:
+ * tests/pspec_linear_adjoint_oracle.py).  The Lawson factor E_k = exp(lambda_k dt / 2) is complex with E(-k) = conj(E(k)); under the grid
+ * sum's pairing of real fields its transpose is multiplication by conj(E_k), so the recurrences of nns_spec_ns_step_adjoint_f32 (and, for the
+ * scalar, of nns_spec_ns_step_scalar_adjoint_f32 with the real E_theta) hold with conj(E), conj(E^2) read from the forward's table lin.  The
+ * white-in-time kick of a stochastic step is added after the step and does not depend on the state: its Jacobian is the identity and the
+ * saved start spectra carry it, so the adjoint of a stochastic step is this call (or, without a table, the two above) on the spectra the
+ * noisy forward saved; the generator is never run.  that0 == NULL and mu == NULL: no scalar (kappa, gx, gy, bx, by are ignored; work:
+ * nns_spec_ns_adjoint_workspace bytes); both non-NULL: the scalar's, buoyant with b != 0 (work: nns_spec_ns_scalar_adjoint_workspace bytes).
+ * nu and drag are not arguments: the table holds them.  Every other argument as in those two calls; 16 launches per step (7 recompute, 9
+ * adjoint), no allocation, no host synchronisation (capturable).  NNS_ERR_INVALID_ARG for a NULL lin and when exactly one of that0, mu is
+ * NULL; otherwise the errors of nns_spec_ns_step_adjoint_f32 / nns_spec_ns_step_scalar_adjoint_f32. */
+int nns_spec_ns_step_linear_adjoint_f32(const float* what0, const float* that0, const float* mean, const float* ghat, int gbatch, float* lam,
+                                        float* mu, float* gbar, void* work, size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly,
+                                        double dt, double kappa, double gx, double gy, double bx, double by, const float* lin, int nsteps,
+                                        void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

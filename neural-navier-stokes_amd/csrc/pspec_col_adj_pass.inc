@@ -3,6 +3,8 @@
 // lam / wbar / gbar, grad kappa to G fields 4 and 5), TH = true the scalar (a PsAdjScalar's; Ph field 2, mu / thetabar, grad m to G fields 8
 // and 9).  The scalar's arithmetic differs in three places: L dt / 2 = hkdt |k|^2 without the drag, the mask keeps the (0, 0) mode, and
 // r_theta is Ph's third field as it stands (no inverse Laplacian, no source to sum a cotangent for).
+// LINEAR (ps_col_adj_kernel's note) is false in every kernel without a table, whose text below is then what it was; with one the vorticity's
+// factors are conj(E) - 1, conj(E^2) - 1 from the table and scal's complex form applies.  The scalar's stay real.
 // In scope: the names of pspec_col_tile.inc, consume, field, ad (PsAdj, or PsAdjScalar where TH is true), tv, ky, dt, dt2, dt3, dt6.
 {
         float2* lamp;
@@ -34,10 +36,17 @@
                 const bool keep = lok && 3 * (mx < 0 ? -mx : mx) < N && (TH || (mx | lj) != 0);
                 const float kx = a.kx1 * (float)mx;
                 const float k2 = kx * kx + ky * ky;
-                float x;                                                             // L dt / 2
-                if constexpr (TH) x = ad.hkdt * k2;
-                else x = a.hnudt * k2 - ad.hdrag;
-                const float em1 = expm1f(x), em2 = expm1f(2.f * x);
+                std::conditional_t<LINEAR && !TH, cf, float> em1, em2;               // E - 1, E^2 - 1; LINEAR: of conj(E), the transpose of E
+                if constexpr (LINEAR && !TH) {
+                    const float2 l = keep ? ad.lin[(size_t)lj * N + e] : make_float2(0.f, 0.f);   // lambda dt / 2: the forward's load
+                    ps_linear_factors(l, em1, em2);
+                    em1.y = -em1.y; em2.y = -em2.y;
+                } else {
+                    float x;                                                         // L dt / 2
+                    if constexpr (TH) x = ad.hkdt * k2;
+                    else x = a.hnudt * k2 - ad.hdrag;
+                    em1 = expm1f(x); em2 = expm1f(2.f * x);
+                }
                 cf rr = {0.f, 0.f};
                 if constexpr (TH) {
                     if (keep) rr = r[m];

@@ -77,6 +77,16 @@
 // 256^2 x 64, 2.60x and 2.56x at 1024^2 x 8; adjoint / flow adjoint 1.71x ... 1.73x and 1.79x ... 1.80x, where the byte model (219 against 132
 // compacted fields moved per step) says 1.66x.
 //
+// Reverse mode of the linear step, with or without scalar, buoyancy and noise (nns_spec_ns_step_linear_adjoint_f32; restatement:
+// tests/pspec_linear_adjoint_oracle.py): the complex Lawson factor has E(-k) = conj(E(k)), so under the grid sum's pairing its transpose is
+// multiplication by conj(E_k), and the recurrences above hold with conj(E) - 1, conj(E^2) - 1 where they have the real em1, em2.  The same driver
+// with a table: the recomputation's column kernels of stages 1-3 take the PsLinear before the PsKeep / PsKeepScalar (LINEAR and STAGES
+// together), and ps_col_adj_kernel of stages 3-1 takes a PsAdjLinear / PsAdjScalarLinear, whose pass does the forward's 8-byte load and
+// ps_linear_factors and negates the imaginary parts; stages 4 and 0, both row kernels and the scalar's real E_theta are untouched, still 7 + 9
+// launches per step.  The kick of a stochastic step is additive and independent of the state: its Jacobian is the identity, the saved start
+// spectra carry it, and the adjoint of a stochastic step is that of the deterministic step it contains -- no kernel, the generator never runs.
+// The new kernels' registers: profiles/pspec_linear_adjoint_isa.txt (no scratch); times: profiles/pspec_linear_adjoint_run.json.
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 //
 // What the row and column kernels share has one copy each: the LDS layout, PsArgs and the row pass's Hermitian fill and kept-mode store in
@@ -119,7 +129,7 @@ struct PsStoch {          // the last argument of the STOCH column kernels (stag
 struct PsLinear {         // the argument of the LINEAR column kernels (stages 1-3 of a linear step), after PsScalar and before PsStoch
     const float2* lin;    // (Re, Im)(lambda dt / 2) [my1][nx], the layout of one grid of W, shared by the batch
 };
-struct PsKeep {           // the last argument of the STAGES column kernels (stages 1-3 of the adjoint's recomputation; no scalar, noise or table)
+struct PsKeep {           // the last argument of the STAGES column kernels (stages 1-3 of the adjoint's recomputation; no scalar or noise)
     float2* stage;        // [B][my1][nx], the layout of W: receives the next stage's input spectrum (s1, s2 or s3)
 };
 struct PsKeepScalar {     // PsKeep of the SCALAR kernels (after PsScalar): the adjoint of the scalar and the buoyant step recomputes both spectra
@@ -139,6 +149,12 @@ struct PsAdjScalar : PsAdj {      // with a scalar: PsAdj and its twin for theta
     float2* tbar;         // [B][my1][nx]: the cotangent of the step's input theta^ while it is summed (stages 3..0)
     const float2* tstate; // [B][my1][nx]: theta^ of the stage state that state belongs to
     float hkdt;           // -kappa dt / 2
+};
+struct PsAdjLinear : PsAdj {      // the LINEAR adjoint column kernels (stages 3-1 of a linear step's adjoint): PsAdj and the forward's table
+    const float2* lin;    // (Re, Im)(lambda dt / 2) [my1][nx], as PsLinear's: the factors are conj(E), conj(E^2); a.hnudt and hdrag are then unused
+};
+struct PsAdjScalarLinear : PsAdjScalar {      // the same with a scalar, whose own factor stays the real E_theta
+    const float2* lin;
 };
 struct PsAdjGrad {        // the argument of the scalar adjoint row kernel: the uniform mean gradient and the buoyancy
     float gx, gy, bx, by;
@@ -253,7 +269,7 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
 // STOCH (a PsStoch ends the pack; FORCED, S = 1 or 4): S = 1 advances the step count, S = 4 adds the kick to the vorticity's w^ (not the scalar's).
 // LINEAR (a PsLinear in the pack, after PsScalar, before PsStoch; FORCED, S = 1..3): the vorticity's L dt / 2 is the complex table entry
 // lin[j][i], not hnudt |k|^2 - alpha dt / 2 (a.hnudt and fc.hdrag are then unused); the scalar's stays hkdt |k|^2.
-// STAGES (a PsKeep alone in the pack; S = 1..3): the next stage's input spectrum is also stored, lane-owned and coalesced like W / A, for the
+// STAGES (a PsKeep ends the pack, after the PsLinear of a linear step; S = 1..3): the next stage's input spectrum is also stored, lane-owned and coalesced like W / A, for the
 // adjoint (ps_col_adj_kernel) to linearise about; the arithmetic is untouched, so the recomputed stages are the forward's bits.  With a scalar
 // the pack ends in a PsKeepScalar after the PsScalar, and theta^'s next stage input is stored as well (ps_col_adj_kernel with a PsAdjScalar).
 template <int N, int S, bool FORCED = false, bool SCALAR = false, typename... Sc>
@@ -266,9 +282,9 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     constexpr bool KEEP_W = (std::is_same_v<Sc, PsKeep> || ... || false), KEEP_WT = (std::is_same_v<Sc, PsKeepScalar> || ... || false);
     constexpr bool STAGES = KEEP_W || KEEP_WT;
     static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0) + (STAGES ? 1 : 0),
-                  "PsScalar is the SCALAR kernel's argument, PsLinear after it the LINEAR kernel's, PsStoch last the STOCH kernel's");
-    static_assert(!STAGES || (S >= 1 && S <= 3 && KEEP_WT == SCALAR && !STOCH && !LINEAR),
-                  "the stage store is that of stages 1-3 of the steady forms: a PsKeep without a scalar, a PsKeepScalar with one");
+                  "PsScalar is the SCALAR kernel's argument, PsLinear after it the LINEAR kernel's, PsStoch or the PsKeep last");
+    static_assert(!STAGES || (S >= 1 && S <= 3 && KEEP_WT == SCALAR && !STOCH),
+                  "the stage store is that of stages 1-3 of the steady and the linear forms: a PsKeep without a scalar, a PsKeepScalar with one");
     static_assert(!LINEAR || (FORCED && S >= 1 && S <= 3), "the complex factors are those of stages 1-3 of the forced form");
     static_assert(!STOCH || (FORCED && (S == 1 || S == 4)), "the kick is stage 4's and the step count stage 1's, both of the forced form");
     using L = PsLds<N>;
@@ -438,12 +454,21 @@ __global__ __launch_bounds__(kT) void ps_row_adj_kernel(const float2* __restrict
 // r_w takes Ph fields 0 and 1 as without the scalar (field 1 now also holds the scalar's share), r_theta = keep_theta ? Ph field 2 : 0.
 // Preparing: i kx kappa^, i ky kappa^ to G fields 4 and 5 and i kx m^, i ky m^ to 8 and 9 (each while its registers are still there), then the
 // state's four spectra to G fields 0-3 and i kx theta^, i ky theta^ of the state's scalar to 6 and 7.  One spectrum's registers at a time.
+// LINEAR (a PsAdjLinear / PsAdjScalarLinear; S = 3, 2, 1; restatement: tests/pspec_linear_adjoint_oracle.py): the forward's factor is the complex
+// E_k = exp(lambda_k dt / 2) with E(-k) = conj(E(k)), so it maps spectra of real fields to such, and under the grid sum's pairing
+// sum_k Re(conj(a_k) E_k b_k) = sum_k Re(conj(conj(E_k) a_k) b_k): the transpose multiplies by conj(E_k).  The recurrences above hold as they stand
+// with conj(E) - 1 and conj(E^2) - 1 for the vorticity: the forward's 8-byte load and ps_linear_factors, the imaginary parts negated.  The
+// scalar's E_theta stays real, and the row adjoint is untouched (beta sits in lambda, not in N).  The white-in-time kick is added to w^ after the
+// step and does not depend on the state: its Jacobian is the identity, the saved start spectra already carry it, and there is nothing to transpose.
 template <int N, int S, typename Ad>
 __global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, const float* __restrict__ mean,
                                                         PsArgs a, Ad ad) {
     static_assert(S >= 0 && S <= 4, "adjoint stages 4 .. 0");
-    constexpr bool SCALAR = std::is_same_v<Ad, PsAdjScalar>;
-    static_assert(SCALAR || std::is_same_v<Ad, PsAdj>, "a PsAdj, or a PsAdjScalar for the step with a scalar");
+    constexpr bool SCALAR = std::is_same_v<Ad, PsAdjScalar> || std::is_same_v<Ad, PsAdjScalarLinear>;
+    constexpr bool LINEAR = std::is_same_v<Ad, PsAdjLinear> || std::is_same_v<Ad, PsAdjScalarLinear>;
+    static_assert(SCALAR || std::is_same_v<Ad, PsAdj> || std::is_same_v<Ad, PsAdjLinear>,
+                  "a PsAdj, or a PsAdjScalar for the step with a scalar; their LINEAR forms for a linear step");
+    static_assert(!LINEAR || (S >= 1 && S <= 3), "the conjugate factors are those of adjoint stages 3-1: stages 4 and 0 apply none");
     using L = PsLds<N>;
     constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -981,14 +1006,15 @@ int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, c
     return with_stage<0, 4>(S, stage);
 }
 
-// Stage S = 1..3 of the adjoint's recomputation: the plain or the forced kernel with the stage store (launch_col_stage never names this form).
-// ke: a PsKeep, or with a scalar the PsScalar and a PsKeepScalar
-template <int N, typename... Ke>
-int launch_col_keep(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, const PsForce* fc, hipStream_t s,
-                    Ke... ke) {
+// Stage S = 1..3 of the adjoint's recomputation: the plain, the forced or (li, with fc) the linear kernel with the stage store (launch_col_stage
+// never names this form).  keep: a PsKeep, or with a scalar a PsKeepScalar and sc the PsScalar; the pack grows in the kernel's order.
+template <int N, typename Keep, typename... Sc>
+int launch_col_keep(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, const PsForce* fc,
+                    const PsLinear* li, hipStream_t s, Keep keep, Sc... sc) {
     auto go = [&](auto stage_c) {
         constexpr int K = decltype(stage_c)::value;
-        return fc ? launch_col<N, K, true>(Ph, G, W, A, mean, a, 1, fc, s, ke...) : launch_col<N, K, false>(Ph, G, W, A, mean, a, 1, fc, s, ke...);
+        if (fc && li) return launch_col<N, K, true>(Ph, G, W, A, mean, a, 1, fc, s, sc..., *li, keep);
+        return fc ? launch_col<N, K, true>(Ph, G, W, A, mean, a, 1, fc, s, sc..., keep) : launch_col<N, K, false>(Ph, G, W, A, mean, a, 1, fc, s, sc..., keep);
     };
     return with_stage<1, 3>(S, go);
 }
@@ -1003,16 +1029,19 @@ int launch_row_adj(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s, 
     return check_launch(SC ? "spec_ns scalar adjoint row pass" : "spec_ns adjoint row pass");
 }
 
-// ad: a PsAdj, or with a scalar a PsAdjScalar
+// ad: a PsAdj, or with a scalar a PsAdjScalar; a PsAdjLinear / PsAdjScalarLinear for stages 3-1 of a linear step's adjoint (no other stage has that form)
 template <int N, typename Ad>
 int launch_col_adj(int S, const float2* Ph, float2* G, const float* mean, const PsArgs& a, const Ad& ad, hipStream_t s) {
+    constexpr bool SC = std::is_base_of_v<PsAdjScalar, Ad>, LI = std::is_same_v<Ad, PsAdjLinear> || std::is_same_v<Ad, PsAdjScalarLinear>;
     auto go = [&](auto stage_c) {
         constexpr auto kern = ps_col_adj_kernel<N, decltype(stage_c)::value, Ad>;
         if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
         hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, mean, a, ad);
-        return check_launch(std::is_same_v<Ad, PsAdjScalar> ? "spec_ns scalar adjoint column pass" : "spec_ns adjoint column pass");
+        return check_launch(LI   ? (SC ? "spec_ns linear scalar adjoint column pass" : "spec_ns linear adjoint column pass")
+                            : SC ? "spec_ns scalar adjoint column pass"
+                                 : "spec_ns adjoint column pass");
     };
-    return with_stage<0, 4>(S, go);
+    return with_stage<LI ? 1 : 0, LI ? 3 : 4>(S, go);
 }
 
 size_t step_bytes(int batch, int nx, int ny) { return (size_t)6 * batch * nx * kept_y(ny) * sizeof(float2); }
@@ -1399,10 +1428,13 @@ NNS_API int nns_spec_ns_adjoint_workspace(int batch, int nx, int ny, size_t* byt
 // (b != 0), the scalar riding in the flow adjoint's launches.  Per step: the stage states s1, s2, s3 (of w^, and of theta^) recomputed from the
 // step's saved start spectra by the forward's own launches (stage 0, then three row / column pairs whose column kernels also store the next
 // stage's input: 7), then the adjoint's stage 4 column launch and four row / column pairs (9).  No allocation, no host synchronisation.
+// lin != NULL: the linear step's (nu and drag are then unused: the table holds them); the recomputation's stages 1-3 are the LINEAR kernels with
+// the stage store and the adjoint's stages 3-1 the LINEAR adjoint kernels, the other launches are those of the forced step.  A stochastic step
+// needs no form of its own: its start spectra carry the kicks, whose Jacobian is the identity.
 static int spec_ns_step_adjoint(const char* who, const float* what0, const float* that0, const float* mean, const float* ghat, int gbatch,
                                 float* lam, float* mu, float* gbar, void* work, size_t work_bytes_, int batch, int nx, int ny, double Lx,
                                 double Ly, double dt, double nu, double drag, double kappa, double gx, double gy, double bx, double by,
-                                int nsteps, void* stream) {
+                                int nsteps, void* stream, const float* lin = nullptr) {
     const bool scalar = that0 != nullptr;
     if (!what0 || !mean || !lam || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
     if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
@@ -1422,7 +1454,9 @@ static int spec_ns_step_adjoint(const char* who, const float* what0, const float
     float2* wstages = L.keep;                                                                  // s1, s2, s3 of w^
     float2* tstages = scalar ? wstages + 3 * fstride : nullptr;                                // and of theta^
     const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
-    const PsForce* fc = ghat || drag > 0 ? &force : nullptr;                                   // the forward's choice of kernels: its bits
+    const PsForce* fc = ghat || drag > 0 || lin ? &force : nullptr;                            // the forward's choice of kernels: its bits
+    const PsLinear linear{reinterpret_cast<const float2*>(lin)};
+    const PsLinear* li = lin ? &linear : nullptr;
     const float hkdt = (float)(-0.5 * kappa * dt);
     const PsGrad grad{(float)gx, (float)gy};
     const PsBuoyGrad buoy{(float)gx, (float)gy, (float)(-(double)ny * by), (float)((double)ny * bx)};
@@ -1456,8 +1490,8 @@ static int spec_ns_step_adjoint(const char* who, const float* what0, const float
             const size_t off = (size_t)(S - 1) * fstride;
             if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
                     constexpr int N = decltype(n)::value;
-                    return scalar ? launch_col_keep<N>(S, L.Ph, L.G, W, L.A, mean, L.col, fc, s, sc, PsKeepScalar{wstages + off, tstages + off})
-                                  : launch_col_keep<N>(S, L.Ph, L.G, W, L.A, mean, L.col, fc, s, PsKeep{wstages + off});
+                    return scalar ? launch_col_keep<N>(S, L.Ph, L.G, W, L.A, mean, L.col, fc, li, s, PsKeepScalar{wstages + off, tstages + off}, sc)
+                                  : launch_col_keep<N>(S, L.Ph, L.G, W, L.A, mean, L.col, fc, li, s, PsKeep{wstages + off});
                 }))
                 return rc;
         }
@@ -1469,6 +1503,9 @@ static int spec_ns_step_adjoint(const char* who, const float* what0, const float
             ad.ginit = k == nsteps - 1;
             if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
                     constexpr int N = decltype(n)::value;
+                    if (li && S >= 1 && S <= 3)
+                        return scalar ? launch_col_adj<N>(S, L.Ph, L.G, mean, L.col, PsAdjScalarLinear{ad, li->lin}, s)
+                                      : launch_col_adj<N>(S, L.Ph, L.G, mean, L.col, PsAdjLinear{ad, li->lin}, s);
                     return scalar ? launch_col_adj<N>(S, L.Ph, L.G, mean, L.col, ad, s) : launch_col_adj<N, PsAdj>(S, L.Ph, L.G, mean, L.col, ad, s);
                 }))
                 return rc;
@@ -1499,6 +1536,17 @@ NNS_API int nns_spec_ns_step_scalar_adjoint_f32(const float* what0, const float*
     if (!that0 || !mu) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_scalar_adjoint: NULL pointer or batch < 1");
     return spec_ns_step_adjoint("spec_ns_step_scalar_adjoint", what0, that0, mean, ghat, gbatch, lam, mu, gbar, work, work_bytes_, batch, nx, ny,
                                 Lx, Ly, dt, nu, drag, kappa, gx, gy, bx, by, nsteps, stream);
+}
+
+NNS_API int nns_spec_ns_step_linear_adjoint_f32(const float* what0, const float* that0, const float* mean, const float* ghat, int gbatch,
+                                                float* lam, float* mu, float* gbar, void* work, size_t work_bytes_, int batch, int nx, int ny,
+                                                double Lx, double Ly, double dt, double kappa, double gx, double gy, double bx, double by,
+                                                const float* lin, int nsteps, void* stream) {
+    if (!lin) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_linear_adjoint: lin must be non-NULL");
+    if (!that0 != !mu) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_linear_adjoint: that0 and mu must be both NULL (no scalar) or both non-NULL");
+    return spec_ns_step_adjoint("spec_ns_step_linear_adjoint", what0, that0, mean, ghat, gbatch, lam, mu, gbar, work, work_bytes_, batch, nx, ny,
+                                Lx, Ly, dt, 0.0, 0.0, that0 ? kappa : 0.0, that0 ? gx : 0.0, that0 ? gy : 0.0, that0 ? bx : 0.0, that0 ? by : 0.0,
+                                nsteps, stream, lin);
 }
 
 NNS_API int nns_spec_ns_scalar_workspace(int batch, int nx, int ny, size_t* bytes) {

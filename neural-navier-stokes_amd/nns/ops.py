@@ -1360,3 +1360,33 @@ def spec_ns_step_scalar_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, 
                                                          float(bx), float(by), int(what0.shape[0]), _stream()),
           'nns_spec_ns_step_scalar_adjoint_f32')
     return lam, mu, gbar
+
+
+# reverse mode of the periodic solver's linear step, with or without its scalar, buoyancy and noise (nns_spec_ns_step_linear_adjoint_f32)
+def spec_ns_step_linear_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, ny, Lx, Ly, dt, kappa, grad, buoyancy, lin):
+    """spec_ns_step_adjoint_ (that0 and mu None; kappa, grad and buoyancy are then ignored; work: spec_ns_adjoint_workspace bytes) or
+    spec_ns_step_scalar_adjoint_ (both given; work: spec_ns_scalar_adjoint_workspace bytes) for the steps of spec_ns_step_linear_: the
+    vorticity's factors are the conjugates of the forward's, from the same table lin, float32 [my1, nx, 2] = (Re, Im)(lambda dt / 2) on the
+    state's device, which holds viscosity and drag: neither is an argument.  A stochastic step's adjoint is this call on the start spectra the
+    noisy forward saved: the kick's Jacobian is the identity.  16 launches per step, no allocation, no host synchronisation."""
+    who = 'spec_ns_step_linear_adjoint_'
+    B, my1, nx = _spec_ns_state(who, lam, mean, work, ny)
+    if (that0 is None) != (mu is None):
+        raise ValueError("%s: that0 and mu must be both None (no scalar) or both given" % who)
+    starts = {'what0': what0}
+    if that0 is not None:
+        _spec_ns_same(who, mu, lam)
+        starts['that0'] = that0
+    gbatch = _spec_ns_adjoint_tensors(who, lam, ghat, gbar, **starts)
+    _f32(lin)
+    if tuple(lin.shape) != (my1, nx, 2):
+        raise ValueError("%s: lin must be float32 [%d, %d, 2], got %s" % (who, my1, nx, tuple(lin.shape)))
+    if lin.device != lam.device:
+        raise ValueError("%s: lin must be on the state's device %s" % (who, lam.device))
+    (gx, gy), (bx, by) = grad, buoyancy
+    opt = lambda t: None if t is None else _p(t)
+    check(_lib.lib().nns_spec_ns_step_linear_adjoint_f32(_p(what0), opt(that0), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(lam), opt(mu),
+                                                         opt(gbar), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt),
+                                                         float(kappa), float(gx), float(gy), float(bx), float(by), _p(lin),
+                                                         int(what0.shape[0]), _stream()), 'nns_spec_ns_step_linear_adjoint_f32')
+    return lam, mu, gbar

@@ -27,6 +27,8 @@ measured on the MI355X 1.016x the steady-forced step at 256^2 x 64 and 1.003x at
 HIP kernels (tests/pspec_adjoint_oracle.py; measured 2.57x a forward step at 256^2 x 64 and 2.72x at 1024^2 x 8, profiles/pspec_adjoint_run.json).
 ``advance_scalar`` / ``advance_velocity_scalar`` do the same for the flow with its scalar and buoyancy (tests/pspec_scalar_adjoint_oracle.py; measured
 2.5-2.6x a forward scalar step and 1.7-1.8x the flow's adjoint, profiles/pspec_scalar_adjoint_run.json).
+``evolve`` / ``evolve_velocity`` are the complete entry points: the same node on EVERY solver, stochastic forcing, hyperviscosity, hypofriction
+and beta included (tests/pspec_linear_adjoint_oracle.py; profiles/pspec_linear_adjoint_run.json).
 """
 import collections
 import math
@@ -178,15 +180,18 @@ class PeriodicState(object):
 
 
 class _AdvanceFn(torch.autograd.Function):
-    """``PeriodicSolver.advance`` / ``advance_velocity`` and, with ``scalar``, ``advance_scalar`` / ``advance_velocity_scalar`` as one autograd
-    node: forward the solver's own step on a fresh state (with a scalar the scalar step, the buoyant one with b != 0), with the spectra at the
-    start of every step kept (one device copy each between one-step calls: the step itself is untouched); backward the adjoint call
-    (ops.spec_ns_step_adjoint_ / ops.spec_ns_step_scalar_adjoint_) between the compact and expand kernels.  ``velocity``: the flow's ends are
-    init / fields instead of the vorticity's; theta's are spec_ns_scalar_init / spec_ns_scalar_field.  ``fields``: (w,) or (u0, v0), then
-    with ``scalar`` theta."""
+    """``PeriodicSolver.evolve`` / ``evolve_velocity`` and the entry points they complete (``advance`` / ``advance_velocity`` and, with
+    ``scalar``, ``advance_scalar`` / ``advance_velocity_scalar``) as one autograd node: forward the step the solver's own ``_launch_steps``
+    picks on a fresh state (linear, stochastic, buoyant, scalar, forced or plain), with the spectra at the start of every step kept (one device
+    copy each between one-step calls: the step itself is untouched); backward the adjoint call (ops.spec_ns_step_linear_adjoint_ on a solver
+    with the general linear operator, else ops.spec_ns_step_adjoint_ / ops.spec_ns_step_scalar_adjoint_) between the compact and expand
+    kernels.  A stochastic step has no adjoint of its own: the kick is additive and independent of the state, the saved start spectra carry
+    it, and the generator is never run in the backward.  ``noise``: None, or (clock, noise_ids) of ``evolve`` for the state the forward
+    steps (ignored without a stochastic force).  ``velocity``: the flow's ends are init / fields instead of the vorticity's; theta's are
+    spec_ns_scalar_init / spec_ns_scalar_field.  ``fields``: (w,) or (u0, v0), then with ``scalar`` theta."""
 
     @staticmethod
-    def forward(ctx, solver, nsteps, mean, velocity, scalar, forcing, *fields):
+    def forward(ctx, solver, nsteps, mean, velocity, scalar, forcing, noise, *fields):
         s = solver
         theta = fields[-1].detach() if scalar else None
         if velocity:
@@ -198,20 +203,15 @@ class _AdvanceFn(torch.autograd.Function):
         ghat = s._force_of(state) if forcing is None else s._source_spectrum(forcing.detach(), state)
         what0 = torch.empty((nsteps,) + tuple(state.what.shape), dtype=torch.float32, device=state.what.device)
         that0 = torch.empty_like(what0) if scalar else None
-        box = (state.mean, ghat, state.work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag)
+        if noise is not None and s.stoch_amp is not None:
+            state.clock, state.noise_ids = s._noise_args(noise[0], noise[1], state)
         for k in range(nsteps):
             what0[k].copy_(state.what)
             if scalar:
                 that0[k].copy_(state.that)
-                if s._buoyant(state):
-                    ops.spec_ns_step_buoyant_(state.what, state.that, *box, s.kappa, s.scalar_gradient, s.buoyancy, 1)
-                else:
-                    ops.spec_ns_step_scalar_(state.what, state.that, *box, s.kappa, s.scalar_gradient, 1)
-            elif ghat is not None or s.drag > 0:
-                ops.spec_ns_step_forced_(state.what, *box, 1)
-            else:
-                ops.spec_ns_step_(state.what, state.mean, state.work, s.ny, s.Lx, s.Ly, s.dt, s.nu, 1)
+            s._launch_steps(state, 1, ghat)
         ctx.solver, ctx.velocity, ctx.scalar, ctx.squeeze = s, velocity, scalar, fields[0].dim() == 2
+        ctx.lin = s._linear_of(state) if s._linear() else None
         ctx.shared = forcing is not None and forcing.shape[0] == 1 and state.batch > 1
         ctx.force_shape = None if forcing is None else tuple(forcing.shape)
         ctx.save_for_backward(what0, state.mean, *(t for t in (that0, ghat) if t is not None))
@@ -239,8 +239,11 @@ class _AdvanceFn(torch.autograd.Function):
             lam = s.init_vorticity(gout[0]).what
         need_g = ctx.force_shape is not None and ctx.needs_input_grad[5]
         gbar = torch.empty_like(lam) if need_g else None
-        if ctx.scalar:
-            mu = ops.spec_ns_scalar_init(gout[-1], torch.empty_like(lam), work)
+        mu = ops.spec_ns_scalar_init(gout[-1], torch.empty_like(lam), work) if ctx.scalar else None
+        if ctx.lin is not None:
+            ops.spec_ns_step_linear_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, s.ny, s.Lx, s.Ly, s.dt,
+                                             s.kappa if ctx.scalar else 0.0, s.scalar_gradient, s.buoyancy, ctx.lin)
+        elif ctx.scalar:
             ops.spec_ns_step_scalar_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag, s.kappa,
                                              s.scalar_gradient, s.buoyancy)
         else:
@@ -259,7 +262,7 @@ class _AdvanceFn(torch.autograd.Function):
             if ctx.shared:
                 gf = torch.sum(gf, dim=0, keepdim=True)
             gf = gf.reshape(ctx.force_shape)
-        return (None, None, None, None, None, gf) + grads
+        return (None, None, None, None, None, gf, None) + grads
 
 
 class PeriodicSolver(object):
@@ -319,6 +322,16 @@ class PeriodicSolver(object):
     a float32 table made at construction from the arguments as they are then, shared by the batch.  ``linear_spectrum(state)`` gives the
     linear term's energy and enstrophy rates per shell (beta contributes to neither) and ``energy_budget`` uses it.  With nu_h = 0, mu = 0 and
     beta = 0 every call is the one it is without these arguments.
+
+    Reverse mode: ``evolve(w, nsteps, theta=, mean=, forcing=, clock=, noise_ids=)`` and ``evolve_velocity`` advance fields through ``nsteps``
+    steps of ANY solver as one autograd node, differentiable in the initial fields and in a vorticity source ``forcing``: the forward is bitwise
+    ``step``, the backward the adjoint of the Lawson RK4 step as HIP kernels, 16 launches per step.  The linear operator above is transposed
+    exactly: under the grid sum that pairs cotangents the transpose of the factor E_k = exp(lambda_k dt / 2) is conj(E_k), read from the same
+    table.  A stochastic step is differentiated as the deterministic step it contains -- the kick is additive and independent of the state, so
+    its Jacobian is the identity and the saved start spectra carry it; ``clock`` names the first step's noise, so a rollout cut into chunks
+    repeats the uncut noise.  nu, nu_h, mu, beta, the drag, kappa, G, b, the amplitudes, the seed and the mean flow are constants.  ``advance``,
+    ``advance_velocity``, ``advance_scalar`` and ``advance_velocity_scalar`` are the same node on the solvers they were written for (the
+    steady-forced flow; with ``kappa``, its scalar and buoyancy) and refuse the others.
 
     By wavenumber: the stored modes are binned into shells of width dk = min(2 pi / Lx, 2 pi / Ly) centred on k_s = s dk (``shells()``; an
     elongated box has many).  ``spectrum(state)`` gives energy E(s), enstrophy Z(s), the force's injection F(s) and the scalar's variance V(s),
@@ -614,9 +627,12 @@ class PeriodicSolver(object):
         """The scalar of this state acts on its flow: it has one and b != 0."""
         return state.that is not None and self.buoyancy != (0.0, 0.0)
 
-    def _launch_steps(self, state, nsteps):
+    def _launch_steps(self, state, nsteps, force=False):
+        """The step this solver takes on this state.  force: False, the solver's own (``set_forcing``); else the spectrum g^ that takes its place
+        (None: no force), as ``evolve`` passes its ``forcing``."""
         what, that = state.what, state.that
-        box = (self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt)      # what every forced form takes after the mean
+        ghat = self._force_of(state) if force is False else force
+        box = (ghat, state.work, self.ny, self.Lx, self.Ly, self.dt)                        # what every forced form takes after the mean
         kappa = 0.0 if self.kappa is None else self.kappa
         amp, clock, ids = (None, None, None) if self.stoch_amp is None else self._noise_of(state)
         if self._linear():
@@ -629,7 +645,7 @@ class PeriodicSolver(object):
             ops.spec_ns_step_buoyant_(what, that, state.mean, *box, self.nu, self.drag, self.kappa, self.scalar_gradient, self.buoyancy, nsteps)
         elif that is not None:
             ops.spec_ns_step_scalar_(what, that, state.mean, *box, self.nu, self.drag, self.kappa, self.scalar_gradient, nsteps)
-        elif self._forced():
+        elif ghat is not None or self.drag > 0:
             ops.spec_ns_step_forced_(what, state.mean, *box, self.nu, self.drag, nsteps)
         else:
             ops.spec_ns_step_(what, state.mean, *box[1:], self.nu, nsteps)
@@ -644,13 +660,14 @@ class PeriodicSolver(object):
 
     # ---- reverse mode
     def _refuse_unsupported(self, who, scalar=False):
-        """The adjoint covers the forced, damped flow and, through the ``scalar`` entry points, its scalar and buoyancy; name the argument that
-        puts a solver outside it."""
+        """``advance*`` cover the forced, damped flow and, through the ``scalar`` entry points, its scalar and buoyancy; name the argument that
+        puts a solver outside them and point at ``evolve`` / ``evolve_velocity``, which cover every solver."""
         for name, on in (('buoyancy', self.buoyancy != (0.0, 0.0) and not scalar), ('kappa', self.kappa is not None and not scalar),
                          ('set_stochastic_forcing', self.stoch_amp is not None), ('hyperviscosity', self.hyperviscosity[0] > 0),
                          ('hypofriction', self.hypofriction[0] > 0), ('beta', self.beta != 0.0)):
             if on:
-                raise NotImplementedError("%s: no reverse mode yet for a solver with %s" % (who, name))
+                raise NotImplementedError("%s: no reverse mode here for a solver with %s; use %s, which covers every solver"
+                                          % (who, name, 'evolve_velocity' if 'velocity' in who else 'evolve'))
 
     def _grad_field(self, name, a):
         """A float32 device tensor [B, nx, ny] (or [nx, ny]) that autograd can follow: no copy from the host or another dtype."""
@@ -699,13 +716,19 @@ class PeriodicSolver(object):
         work = state.work if state.work.numel() >= need else torch.empty(need, dtype=torch.uint8, device=state.what.device)
         return ops.spec_ns_scalar_field(state.what, work, self.ny, out)
 
-    def _advance_args(self, who, scalar, nsteps, forcing, *fields):
+    def _advance_args(self, who, scalar, nsteps, forcing, *fields, complete=False):
         """The checked arguments of ``advance`` / ``advance_velocity`` and, with ``scalar``, of ``advance_scalar`` / ``advance_velocity_scalar``:
-        the refusals, then the tensor checks.  ``fields``: (name, tensor) pairs."""
-        if scalar and self.kappa is None:
-            raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use %s"
-                             % (who, who.replace('_scalar', '')))
-        self._refuse_unsupported(who, scalar)
+        the refusals, then the tensor checks; ``complete``: of ``evolve`` / ``evolve_velocity``, which refuse no solver and take the scalar iff
+        the solver has one.  ``fields``: (name, tensor) pairs."""
+        if complete:
+            if scalar != (self.kappa is not None):
+                raise ValueError("%s: %s" % (who, "the solver has kappa: its scalar (theta) is part of the state and must be given" if not scalar
+                                         else "a scalar (theta) needs a solver built with kappa (the scalar's diffusivity)"))
+        else:
+            if scalar and self.kappa is None:
+                raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use %s"
+                                 % (who, who.replace('_scalar', '')))
+            self._refuse_unsupported(who, scalar)
         nsteps = _count('nsteps', nsteps, 1)
         fields = [self._grad_field(name, f) for name, f in fields]
         if any(f.shape != fields[0].shape for f in fields[1:]):
@@ -725,18 +748,19 @@ class PeriodicSolver(object):
         ``mean``: the mean velocity ([B, 2] or a pair; None: at rest), a constant of the motion that is not differentiated.  The forward is
         bitwise ``vorticity(step(init_vorticity(w, mean), nsteps))``.  Memory kept for the backward: the spectrum at the start of every step,
         nsteps x B x my1 x nx x 8 bytes (my1 = (ny - 1) // 3 + 1: a third of a field per step and grid); the stages inside a step are recomputed.
-        Not for a solver with kappa or buoyancy (``advance_scalar`` / ``advance_velocity_scalar`` take and return the scalar) and not yet for a
-        stochastic force, hyperviscosity, hypofriction or beta: NotImplementedError."""
+        Not for a solver with kappa or buoyancy (``advance_scalar`` / ``advance_velocity_scalar`` take and return the scalar) and not for a
+        stochastic force, hyperviscosity, hypofriction or beta: NotImplementedError; ``evolve`` covers every solver."""
         nsteps, forcing, (w,) = self._advance_args('advance', False, nsteps, forcing, ('w', w))
-        return _AdvanceFn.apply(self, nsteps, mean, False, False, forcing, w)[0]
+        return _AdvanceFn.apply(self, nsteps, mean, False, False, forcing, None, w)[0]
 
     def advance_velocity(self, u0, v0, nsteps=1, forcing=None):
         """(u, v) after ``nsteps`` steps from the velocity (u0, v0), differentiable like ``advance`` (and in ``forcing``, a vorticity source as
         there): ``fields(step(init(u0, v0), nsteps))[:2]`` forward; backward through the velocity by K^T (ubar, vbar)^ = curl(ubar, vbar)^ / |k|^2,
         the step's adjoint, and init^T (lam) = (lam_y, -lam_x), built from the init / fields kernels and one |k|^-2, |k|^2 table multiply each.
-        The grid means (U0, V0) of (u0, v0) are constants of the motion and are not differentiated.  No pressure output."""
+        The grid means (U0, V0) of (u0, v0) are constants of the motion and are not differentiated.  No pressure output.  The refusals of
+        ``advance``; ``evolve_velocity`` covers every solver."""
         nsteps, forcing, (u0, v0) = self._advance_args('advance_velocity', False, nsteps, forcing, ('u0', u0), ('v0', v0))
-        return _AdvanceFn.apply(self, nsteps, None, True, False, forcing, u0, v0)
+        return _AdvanceFn.apply(self, nsteps, None, True, False, forcing, None, u0, v0)
 
     def advance_scalar(self, w, theta, nsteps=1, mean=None, forcing=None):
         """(w, theta) after ``nsteps`` steps from the vorticity field w and the scalar theta (float32 device tensors [B, nx, ny] or [nx, ny]) on a
@@ -747,18 +771,62 @@ class PeriodicSolver(object):
         fitted to scalar observations.  ``forcing`` and ``mean`` as in ``advance``; the scalar has no source.  The forward is bitwise ``step``
         on ``init_vorticity(w, mean)`` with ``that`` from ``ops.spec_ns_scalar_init(theta)``, read by ``vorticity`` and ``scalar``.  Memory kept
         for the backward: both spectra at the start of every step, nsteps x B x my1 x nx x 16 bytes.  kappa, the gradient G, b, nu, the drag and
-        the mean flow are constants and are not differentiated.  ValueError on a solver without kappa; not yet for a stochastic force,
-        hyperviscosity, hypofriction or beta: NotImplementedError."""
+        the mean flow are constants and are not differentiated.  ValueError on a solver without kappa; not for a stochastic force,
+        hyperviscosity, hypofriction or beta: NotImplementedError (``evolve`` covers every solver)."""
         nsteps, forcing, (w, theta) = self._advance_args('advance_scalar', True, nsteps, forcing, ('w', w), ('theta', theta))
-        return _AdvanceFn.apply(self, nsteps, mean, False, True, forcing, w, theta)
+        return _AdvanceFn.apply(self, nsteps, mean, False, True, forcing, None, w, theta)
 
     def advance_velocity_scalar(self, u0, v0, theta0, nsteps=1, forcing=None):
         """(u, v, theta) after ``nsteps`` steps from the velocity (u0, v0) and the scalar theta0, differentiable like ``advance_scalar``:
         ``fields(step(init(u0, v0, theta0), nsteps))[:2]`` and ``scalar`` of it forward; backward through the velocity's ends as in
-        ``advance_velocity``.  No pressure output."""
+        ``advance_velocity``.  No pressure output.  The refusals of ``advance_scalar``; ``evolve_velocity`` covers every solver."""
         nsteps, forcing, (u0, v0, theta0) = self._advance_args('advance_velocity_scalar', True, nsteps, forcing, ('u0', u0), ('v0', v0),
                                                                ('theta0', theta0))
-        return _AdvanceFn.apply(self, nsteps, None, True, True, forcing, u0, v0, theta0)
+        return _AdvanceFn.apply(self, nsteps, None, True, True, forcing, None, u0, v0, theta0)
+
+    def _noise_args(self, clock, noise_ids, state):
+        """(clock, noise_ids) of ``evolve`` as a state's: clock an int >= 0 or an int64 device tensor [1], copied (the step advances the copy);
+        noise_ids None (arange(B)) or B ints."""
+        dev, B = state.what.device, state.batch
+        if isinstance(clock, torch.Tensor):
+            if clock.dtype != torch.int64 or tuple(clock.shape) != (1,) or clock.device != dev:
+                raise ValueError("clock: an int or an int64 tensor [1] on the state's device expected, got %s %s on %s"
+                                 % (clock.dtype, tuple(clock.shape), clock.device))
+            clock = clock.clone()
+        else:
+            clock = torch.full((1,), _count('clock', clock, 0), dtype=torch.int64, device=dev)
+        if noise_ids is None:
+            ids = torch.arange(B, dtype=torch.int32, device=dev)
+        else:
+            ids = torch.as_tensor(noise_ids).to(device=dev, dtype=torch.int32).reshape(-1).contiguous().clone()
+            if ids.numel() != B:
+                raise ValueError("noise_ids: one id per grid, [%d], expected, got %d" % (B, ids.numel()))
+        return clock, ids
+
+    def evolve(self, w, nsteps=1, theta=None, mean=None, forcing=None, clock=0, noise_ids=None):
+        """``advance`` / ``advance_scalar`` on EVERY solver: the vorticity field after ``nsteps`` steps (with ``theta``, required iff the solver has
+        ``kappa``: the pair (w, theta)), differentiable in w, theta and ``forcing`` through the same autograd node.  The forward takes the step
+        ``step`` takes -- linear (hyperviscosity, hypofriction, beta), stochastic, buoyant, scalar, forced or plain -- and is bitwise ``step`` on
+        the same state; the backward is the adjoint as HIP kernels, with the conjugate Lawson factors conj(E), conj(E^2) read from the forward's
+        table on a solver with the general linear operator.  A stochastic step is differentiated as the deterministic
+        step it contains: the kick is additive and independent of the state, and the saved start spectra carry it.  ``clock``: the index of the
+        first step's noise, an int or an int64 device tensor [1] that is copied, never advanced: a rollout cut into chunks passes n0,
+        n0 + nsteps, ... and reproduces the uncut noise; ``noise_ids`` as on ``PeriodicState`` (None: arange(B)).  Both are ignored without a
+        stochastic force.  ``mean`` and ``forcing`` as in ``advance``; nu, drag, the table, the amplitudes and the seed are constants and are not
+        differentiated.  On a solver ``advance`` / ``advance_scalar`` accept, outputs and gradients are theirs, bitwise."""
+        scalar = theta is not None
+        fields = (('w', w), ('theta', theta)) if scalar else (('w', w),)
+        nsteps, forcing, fields = self._advance_args('evolve', scalar, nsteps, forcing, *fields, complete=True)
+        out = _AdvanceFn.apply(self, nsteps, mean, False, scalar, forcing, (clock, noise_ids), *fields)
+        return out if scalar else out[0]
+
+    def evolve_velocity(self, u0, v0, nsteps=1, theta0=None, forcing=None, clock=0, noise_ids=None):
+        """``evolve`` from and to the velocity: (u, v), or with ``theta0`` (required iff the solver has ``kappa``) (u, v, theta), after ``nsteps``
+        steps, with the ends of ``advance_velocity`` / ``advance_velocity_scalar``.  No pressure output."""
+        scalar = theta0 is not None
+        fields = (('u0', u0), ('v0', v0)) + ((('theta0', theta0),) if scalar else ())
+        nsteps, forcing, fields = self._advance_args('evolve_velocity', scalar, nsteps, forcing, *fields, complete=True)
+        return _AdvanceFn.apply(self, nsteps, None, True, scalar, forcing, (clock, noise_ids), *fields)
 
     def diagnostics(self, state):
         """Diagnostics(energy, enstrophy, power_in), each float64 [B], computed on the device from the state's spectrum:
