@@ -612,6 +612,30 @@ int nns_spec_ns_step_linear_adjoint_f32(const float* what0, const float* that0, 
                                         float* mu, float* gbar, void* work, size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly,
                                         double dt, double kappa, double gx, double gy, double bx, double by, const float* lin, int nsteps,
                                         void* stream);
+/* nns_spec_ns_step_linear_adjoint_f32 that also differentiates the step in its linear operator, the table lin = l = lambda dt / 2 (restatement:
+ * tests/pspec_operator_grad_oracle.py).  With E = exp(l) the Lawson RK4 step s1 = E (w0 + dt/2 N0), s2 = E w0 + dt/2 N1, s3 = E^2 w0 + dt E N2,
+ * w1 = E^2 w0 + dt/6 (E^2 N0 + 2 E N1 + 2 E N2 + N3) has, per mode, without any N and without a division by E (a stiff mode is safe),
+ *     d s1 / dl = s1     d s2 / dl = E w0     d s3 / dl = s3 + E^2 w0     d w1 / dl = (s3 + E^2 w0) / 3 + 2/3 E (s1 + s2)
+ * and a cotangent c of z = D dl gives c conj(D).  With lam the cotangent of w1 and r_S = N'(s_S)^T k_(S+1) that of s_S, both already held by
+ * adjoint stages 3, 2, 1, one step adds
+ *     (r3 + lam / 3) conj(s3 + E^2 w0)  +  r2 conj(E w0) + 2/3 lam conj(E s2)  +  (r1 + 2/3 conj(E) lam) conj(s1)
+ * in the launches of those stages: the same 16 launches per step, five more reads and three read-modify-writes of a compact field.  The steady
+ * force, the scalar, the buoyancy and the noise change nothing here (they live in N or after the step); the scalar's E_theta is a constant.
+ * lbar: float32 [batch][my1][nx][2], out this sum over the steps of the call, ALWAYS one per grid, overwritten; zero outside the band and at
+ * (0, 0).  A grid's lbar does not depend on its batch neighbours, every entry has one owner (no atomics: two runs give the same bits), and
+ * nsteps steps in one call are bitwise nsteps calls of one step, last first, summed in that order.  lbar is the sum BEFORE the weight of the
+ * cotangent convention (the plain grid sum of real fields, unnormalised rfft2 spectra, a stored mode with ky > 0 standing for itself and its
+ * mirror image).  The gradient of a loss L in a table shared by the batch is the unique G [my1][nx][2] with
+ *     dL = sum over stored entries (G.re dRe l + G.im dIm l)   for every dl that keeps l(-k) = conj(l(k))   (ky = 0 stores both kx and -kx)
+ * that obeys this symmetry itself, so that a gradient step on a valid table gives a valid one.  From T = sum over the grids of lbar it is
+ *     G(kx, ky) = 2 T(kx, ky) / (nx ny)   for ky > 0,        G(kx, 0) = (T(kx, 0) + conj(T(-kx, 0))) / (2 nx ny)
+ * (nns.periodic.PeriodicSolver.evolve does this with one table multiply per backward).  lbar == NULL: exactly the launches and the results of
+ * nns_spec_ns_step_linear_adjoint_f32.  nsteps == 0 zeroes lbar, as gbar.  lam, mu, gbar and every other argument, the workspaces and the
+ * errors as there (no allocation, no host synchronisation, capturable). */
+int nns_spec_ns_step_operator_adjoint_f32(const float* what0, const float* that0, const float* mean, const float* ghat, int gbatch, float* lam,
+                                          float* mu, float* gbar, void* work, size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly,
+                                          double dt, double kappa, double gx, double gy, double bx, double by, const float* lin, int nsteps,
+                                          void* stream, float* lbar);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

@@ -5,6 +5,8 @@
 // r_theta is Ph's third field as it stands (no inverse Laplacian, no source to sum a cotangent for).
 // LINEAR (ps_col_adj_kernel's note) is false in every kernel without a table, whose text below is then what it was; with one the vorticity's
 // factors are conj(E) - 1, conj(E^2) - 1 from the table and scal's complex form applies.  The scalar's stay real.
+// OPERATOR (a PsAdjOperator / PsAdjScalarOperator, LINEAR with it) is false in every other kernel, whose text is then what it was; with one
+// the vorticity's pass of stages 3-1 also sums the table's cotangent of the step in ad.lstep and adds it to ad.lbar, lane-owned like gbar.
 // In scope: the names of pspec_col_tile.inc, consume, field, ad (PsAdj, or PsAdjScalar where TH is true), tv, ky, dt, dt2, dt3, dt6.
 {
         float2* lamp;
@@ -74,6 +76,36 @@
                         } else {
                             const cf el = scal(em2, lam);
                             kap[m] = axpy(dt2, er, cf{dt6 * el.x, dt6 * el.y});
+                        }
+                    }
+                }
+                if constexpr (OPERATOR && !TH) {
+                    // the table's cotangent (ps_col_adj_kernel's note): c conj(D) for every z = D dl this stage holds the cotangent c of; only
+                    // conj(E), conj(E^2) appear (conj(E w0) = conj(E) conj(w0)); lam and rr are zero off the kept modes, and so is lbar
+                    if (lok) {
+                        const float2 so = ad.own[si];
+                        cf add;
+                        if constexpr (S == 3) {
+                            const float2 w0 = ad.w0[si];
+                            const cf ew = scal(em2, cf{w0.x, -w0.y});
+                            add = cmul(axpy(1.f / 3.f, lam, rr), cf{so.x + ew.x, ew.y - so.y});
+                        } else if constexpr (S == 2) {
+                            const float2 w0 = ad.w0[si];
+                            const cf ls = cmul(lam, cf{so.x, -so.y});
+                            add = scal(em1, axpy(2.f / 3.f, ls, cmul(rr, cf{w0.x, -w0.y})));
+                        } else {
+                            add = cmul(axpy(2.f / 3.f, scal(em1, lam), rr), cf{so.x, -so.y});
+                        }
+                        if constexpr (S == 3) {
+                            ad.lstep[si] = make_float2(add.x, add.y);
+                        } else {
+                            const float2 p2 = ad.lstep[si];
+                            if constexpr (S == 2) {
+                                ad.lstep[si] = make_float2(p2.x + add.x, p2.y + add.y);
+                            } else {                       // the step's sum is complete: to the call's
+                                const float2 b2 = ad.ginit ? make_float2(0.f, 0.f) : ad.lbar[si];
+                                ad.lbar[si] = make_float2(b2.x + (p2.x + add.x), b2.y + (p2.y + add.y));
+                            }
                         }
                     }
                 }

@@ -87,6 +87,14 @@
 // spectra carry it, and the adjoint of a stochastic step is that of the deterministic step it contains -- no kernel, the generator never runs.
 // The new kernels' registers: profiles/pspec_linear_adjoint_isa.txt (no scratch); times: profiles/pspec_linear_adjoint_run.json.
 //
+// Reverse mode in the linear operator itself (nns_spec_ns_step_operator_adjoint_f32; restatement: tests/pspec_operator_grad_oracle.py): the
+// step reads its operator from the table l = lambda dt / 2, so the table is the object to differentiate -- nu, drag, nu_h, mu, beta and any
+// learned diagonal operator follow by the chain rule on the host.  The stages' derivatives in l need no N and no division by E, and the
+// cotangents they pair with are the ones adjoint stages 3-1 already hold (ps_col_adj_kernel's note): a PsAdjOperator / PsAdjScalarOperator in
+// place of the PsAdjLinear / PsAdjScalarLinear makes those three launches also sum c conj(D) per mode and grid, lane-owned like gbar.  The same
+// driver, workspaces and 16 launches per step; without lbar the call is the linear adjoint's, launch for launch.  Every other kernel keeps
+// its instructions.  Registers and times: profiles/pspec_operator_grad_isa.txt (no scratch), profiles/pspec_operator_grad_run.json.
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 //
 // What the row and column kernels share has one copy each: the LDS layout, PsArgs and the row pass's Hermitian fill and kept-mode store in
@@ -155,6 +163,19 @@ struct PsAdjLinear : PsAdj {      // the LINEAR adjoint column kernels (stages 3
 };
 struct PsAdjScalarLinear : PsAdjScalar {      // the same with a scalar, whose own factor stays the real E_theta
     const float2* lin;
+};
+struct PsAdjOperator : PsAdjLinear {          // the LINEAR kernels that also sum the table's cotangent (nns_spec_ns_step_operator_adjoint_f32)
+    float2* lbar;         // [B][my1][nx]: the cotangent of lin per grid before weight and symmetrisation, summed over the steps: stage 1 adds the
+                          // step's sum to it, or starts it where ginit is set
+    float2* lstep;        // [B][my1][nx]: the step's own sum while it is made (stage 3 writes it, stage 2 adds, stage 1 reads)
+    const float2* own;    // [B][my1][nx]: the state THIS stage's r belongs to (S = 3: s3, 2: s2, 1: s1)
+    const float2* w0;     // [B][my1][nx]: the step's start spectrum (read by S = 3 and 2)
+};
+struct PsAdjScalarOperator : PsAdjScalarLinear {      // the same with a scalar, whose E_theta is a constant
+    float2* lbar;
+    float2* lstep;
+    const float2* own;
+    const float2* w0;
 };
 struct PsAdjGrad {        // the argument of the scalar adjoint row kernel: the uniform mean gradient and the buoyancy
     float gx, gy, bx, by;
@@ -460,14 +481,27 @@ __global__ __launch_bounds__(kT) void ps_row_adj_kernel(const float2* __restrict
 // with conj(E) - 1 and conj(E^2) - 1 for the vorticity: the forward's 8-byte load and ps_linear_factors, the imaginary parts negated.  The
 // scalar's E_theta stays real, and the row adjoint is untouched (beta sits in lambda, not in N).  The white-in-time kick is added to w^ after the
 // step and does not depend on the state: its Jacobian is the identity, the saved start spectra already carry it, and there is nothing to transpose.
+// OPERATOR (a PsAdjOperator / PsAdjScalarOperator; S = 3, 2, 1; restatement: tests/pspec_operator_grad_oracle.py): the LINEAR kernel that also
+// sums the cotangent of the table l = lambda dt / 2.  With E = exp(l), d s1 / dl = s1, d s2 / dl = E w0, d s3 / dl = s3 + E^2 w0 and
+// d w1 / dl = (s3 + E^2 w0) / 3 + 2/3 E (s1 + s2) -- no N and no division by E, so a stiff mode is safe -- and a cotangent c of z = D dl gives
+// c conj(D).  r of stage S is the cotangent of s_S and lam that of w1, so per mode
+//     S = 3   lstep  = (r + lam / 3) (conj(s3) + conj(E^2) conj(w0))
+//     S = 2   lstep += conj(E) (r conj(w0) + 2/3 lam conj(s2))
+//     S = 1   lbar  += lstep + (r + 2/3 conj(E) lam) conj(s1)               (= on the call's first step: ginit)
+// before stage 0 overwrites lam: ad.own is s_S and ad.w0 the step's start, five more reads of a compact field per step and three reads and
+// three writes of the two sums.  A step's sum is made on its own (lstep, a field of the workspace that is idle in these stages) and then
+// added, so nsteps steps in one call are bitwise the sum of nsteps calls of one step.  Both are lane-owned like gbar: no atomics, and a grid's
+// sum does not depend on its batch neighbours.  The weight of a stored mode, 1 / n
+// and the symmetry of the ky = 0 line are the caller's (nns.h: nns_spec_ns_step_operator_adjoint_f32).
 template <int N, int S, typename Ad>
 __global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, const float* __restrict__ mean,
                                                         PsArgs a, Ad ad) {
     static_assert(S >= 0 && S <= 4, "adjoint stages 4 .. 0");
-    constexpr bool SCALAR = std::is_same_v<Ad, PsAdjScalar> || std::is_same_v<Ad, PsAdjScalarLinear>;
-    constexpr bool LINEAR = std::is_same_v<Ad, PsAdjLinear> || std::is_same_v<Ad, PsAdjScalarLinear>;
-    static_assert(SCALAR || std::is_same_v<Ad, PsAdj> || std::is_same_v<Ad, PsAdjLinear>,
-                  "a PsAdj, or a PsAdjScalar for the step with a scalar; their LINEAR forms for a linear step");
+    constexpr bool OPERATOR = std::is_same_v<Ad, PsAdjOperator> || std::is_same_v<Ad, PsAdjScalarOperator>;
+    constexpr bool SCALAR = std::is_same_v<Ad, PsAdjScalar> || std::is_same_v<Ad, PsAdjScalarLinear> || std::is_same_v<Ad, PsAdjScalarOperator>;
+    constexpr bool LINEAR = std::is_same_v<Ad, PsAdjLinear> || std::is_same_v<Ad, PsAdjScalarLinear> || OPERATOR;
+    static_assert(SCALAR || std::is_same_v<Ad, PsAdj> || std::is_same_v<Ad, PsAdjLinear> || std::is_same_v<Ad, PsAdjOperator>,
+                  "a PsAdj, or a PsAdjScalar for the step with a scalar; their LINEAR forms for a linear step, their OPERATOR forms for the table's cotangent");
     static_assert(!LINEAR || (S >= 1 && S <= 3), "the conjugate factors are those of adjoint stages 3-1: stages 4 and 0 apply none");
     using L = PsLds<N>;
     constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
@@ -1029,10 +1063,11 @@ int launch_row_adj(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s, 
     return check_launch(SC ? "spec_ns scalar adjoint row pass" : "spec_ns adjoint row pass");
 }
 
-// ad: a PsAdj, or with a scalar a PsAdjScalar; a PsAdjLinear / PsAdjScalarLinear for stages 3-1 of a linear step's adjoint (no other stage has that form)
+// ad: a PsAdj, or with a scalar a PsAdjScalar; a PsAdjLinear / PsAdjScalarLinear for stages 3-1 of a linear step's adjoint (no other stage has that form),
+// or there a PsAdjOperator / PsAdjScalarOperator when the table's cotangent is wanted
 template <int N, typename Ad>
 int launch_col_adj(int S, const float2* Ph, float2* G, const float* mean, const PsArgs& a, const Ad& ad, hipStream_t s) {
-    constexpr bool SC = std::is_base_of_v<PsAdjScalar, Ad>, LI = std::is_same_v<Ad, PsAdjLinear> || std::is_same_v<Ad, PsAdjScalarLinear>;
+    constexpr bool SC = std::is_base_of_v<PsAdjScalar, Ad>, LI = std::is_base_of_v<PsAdjLinear, Ad> || std::is_base_of_v<PsAdjScalarLinear, Ad>;
     auto go = [&](auto stage_c) {
         constexpr auto kern = ps_col_adj_kernel<N, decltype(stage_c)::value, Ad>;
         if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
@@ -1430,11 +1465,12 @@ NNS_API int nns_spec_ns_adjoint_workspace(int batch, int nx, int ny, size_t* byt
 // stage's input: 7), then the adjoint's stage 4 column launch and four row / column pairs (9).  No allocation, no host synchronisation.
 // lin != NULL: the linear step's (nu and drag are then unused: the table holds them); the recomputation's stages 1-3 are the LINEAR kernels with
 // the stage store and the adjoint's stages 3-1 the LINEAR adjoint kernels, the other launches are those of the forced step.  A stochastic step
-// needs no form of its own: its start spectra carry the kicks, whose Jacobian is the identity.
+// needs no form of its own: its start spectra carry the kicks, whose Jacobian is the identity.  lbar != NULL (with lin): the adjoint's stages 3-1
+// are the OPERATOR kernels, which also sum the table's cotangent; the launches, the workspace and everything else are the same.
 static int spec_ns_step_adjoint(const char* who, const float* what0, const float* that0, const float* mean, const float* ghat, int gbatch,
                                 float* lam, float* mu, float* gbar, void* work, size_t work_bytes_, int batch, int nx, int ny, double Lx,
                                 double Ly, double dt, double nu, double drag, double kappa, double gx, double gy, double bx, double by,
-                                int nsteps, void* stream, const float* lin = nullptr) {
+                                int nsteps, void* stream, const float* lin = nullptr, float* lbar = nullptr) {
     const bool scalar = that0 != nullptr;
     if (!what0 || !mean || !lam || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
     if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
@@ -1444,10 +1480,11 @@ static int spec_ns_step_adjoint(const char* who, const float* what0, const float
     if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, scalar ? kWorkScalarAdjoint : kWorkAdjoint)) return rc;
     hipStream_t s = as_stream(stream);
     if (nsteps == 0) {
-        if (!gbar) return NNS_OK;
-        void* zb[1] = {gbar};
-        const long zn[1] = {(long)((size_t)batch * kept_y(ny) * nx * sizeof(float2))};
-        return zero_buffers(zb, zn, 1, s);
+        const long zbytes = (long)((size_t)batch * kept_y(ny) * nx * sizeof(float2));
+        void* zb[2] = {gbar ? gbar : lbar, lbar};
+        const long zn[2] = {zbytes, zbytes};
+        const int nz = (gbar ? 1 : 0) + (lbar ? 1 : 0);
+        return nz ? zero_buffers(zb, zn, nz, s) : NNS_OK;
     }
     const PsWork L(work, batch, nx, ny, scalar ? kLayScalarAdjoint : kLayAdjoint, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);
     const long fstride = L.col.fstride;
@@ -1503,6 +1540,15 @@ static int spec_ns_step_adjoint(const char* who, const float* what0, const float
             ad.ginit = k == nsteps - 1;
             if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
                     constexpr int N = decltype(n)::value;
+                    if (li && lbar && S >= 1 && S <= 3) {                    // the state this stage's r belongs to, and the step's start
+                        float2* lb = reinterpret_cast<float2*>(lbar);
+                        // the step's own sum lives in a field these stages leave idle: the flow's accumulator A (its wbar is in A_theta's
+                        // place), with a scalar theta^'s s3 (read by stage 4 alone, stored again by the next step's recomputation)
+                        float2* lstep = scalar ? tstages + 2 * fstride : L.A;
+                        const float2* own = wstages + (size_t)(S - 1) * fstride;
+                        return scalar ? launch_col_adj<N>(S, L.Ph, L.G, mean, L.col, PsAdjScalarOperator{PsAdjScalarLinear{ad, li->lin}, lb, lstep, own, W}, s)
+                                      : launch_col_adj<N>(S, L.Ph, L.G, mean, L.col, PsAdjOperator{PsAdjLinear{ad, li->lin}, lb, lstep, own, W}, s);
+                    }
                     if (li && S >= 1 && S <= 3)
                         return scalar ? launch_col_adj<N>(S, L.Ph, L.G, mean, L.col, PsAdjScalarLinear{ad, li->lin}, s)
                                       : launch_col_adj<N>(S, L.Ph, L.G, mean, L.col, PsAdjLinear{ad, li->lin}, s);
@@ -1547,6 +1593,17 @@ NNS_API int nns_spec_ns_step_linear_adjoint_f32(const float* what0, const float*
     return spec_ns_step_adjoint("spec_ns_step_linear_adjoint", what0, that0, mean, ghat, gbatch, lam, mu, gbar, work, work_bytes_, batch, nx, ny,
                                 Lx, Ly, dt, 0.0, 0.0, that0 ? kappa : 0.0, that0 ? gx : 0.0, that0 ? gy : 0.0, that0 ? bx : 0.0, that0 ? by : 0.0,
                                 nsteps, stream, lin);
+}
+
+NNS_API int nns_spec_ns_step_operator_adjoint_f32(const float* what0, const float* that0, const float* mean, const float* ghat, int gbatch,
+                                                  float* lam, float* mu, float* gbar, void* work, size_t work_bytes_, int batch, int nx, int ny,
+                                                  double Lx, double Ly, double dt, double kappa, double gx, double gy, double bx, double by,
+                                                  const float* lin, int nsteps, void* stream, float* lbar) {
+    if (!lin) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_operator_adjoint: lin must be non-NULL");
+    if (!that0 != !mu) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_operator_adjoint: that0 and mu must be both NULL (no scalar) or both non-NULL");
+    return spec_ns_step_adjoint("spec_ns_step_operator_adjoint", what0, that0, mean, ghat, gbatch, lam, mu, gbar, work, work_bytes_, batch, nx, ny,
+                                Lx, Ly, dt, 0.0, 0.0, that0 ? kappa : 0.0, that0 ? gx : 0.0, that0 ? gy : 0.0, that0 ? bx : 0.0, that0 ? by : 0.0,
+                                nsteps, stream, lin, lbar);
 }
 
 NNS_API int nns_spec_ns_scalar_workspace(int batch, int nx, int ny, size_t* bytes) {

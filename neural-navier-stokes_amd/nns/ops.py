@@ -1390,3 +1390,39 @@ def spec_ns_step_linear_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, 
                                                          float(kappa), float(gx), float(gy), float(bx), float(by), _p(lin),
                                                          int(what0.shape[0]), _stream()), 'nns_spec_ns_step_linear_adjoint_f32')
     return lam, mu, gbar
+
+
+# the same reverse mode, also differentiated in the linear operator's table (nns_spec_ns_step_operator_adjoint_f32)
+def spec_ns_step_operator_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, ny, Lx, Ly, dt, kappa, grad, buoyancy, lin, lbar):
+    """spec_ns_step_linear_adjoint_ whose launches also sum the cotangent of the table lin into lbar (float32 [B, my1, nx, 2] on the state's
+    device, overwritten): one per grid, summed over the steps of the call, zero off the band and at (0, 0), BEFORE the weight of the cotangent
+    convention -- include/nns.h gives the table gradient it stands for (PeriodicSolver.evolve applies it).  lbar None: exactly
+    spec_ns_step_linear_adjoint_.  The same 16 launches per step, no allocation, no host synchronisation."""
+    who = 'spec_ns_step_operator_adjoint_'
+    B, my1, nx = _spec_ns_state(who, lam, mean, work, ny)
+    if (that0 is None) != (mu is None):
+        raise ValueError("%s: that0 and mu must be both None (no scalar) or both given" % who)
+    starts = {'what0': what0}
+    if that0 is not None:
+        _spec_ns_same(who, mu, lam)
+        starts['that0'] = that0
+    gbatch = _spec_ns_adjoint_tensors(who, lam, ghat, gbar, **starts)
+    _f32(lin)
+    if tuple(lin.shape) != (my1, nx, 2):
+        raise ValueError("%s: lin must be float32 [%d, %d, 2], got %s" % (who, my1, nx, tuple(lin.shape)))
+    if lin.device != lam.device:
+        raise ValueError("%s: lin must be on the state's device %s" % (who, lam.device))
+    if lbar is not None:
+        _f32(lbar)
+        if tuple(lbar.shape) != tuple(lam.shape):
+            raise ValueError("%s: lbar must be float32 [%d, %d, %d, 2], got %s" % ((who,) + tuple(lam.shape[:3]) + (tuple(lbar.shape),)))
+        if lbar.device != lam.device:
+            raise ValueError("%s: lbar must be on the state's device %s" % (who, lam.device))
+    (gx, gy), (bx, by) = grad, buoyancy
+    opt = lambda t: None if t is None else _p(t)
+    check(_lib.lib().nns_spec_ns_step_operator_adjoint_f32(_p(what0), opt(that0), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(lam),
+                                                           opt(mu), opt(gbar), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly),
+                                                           float(dt), float(kappa), float(gx), float(gy), float(bx), float(by), _p(lin),
+                                                           int(what0.shape[0]), _stream(), opt(lbar)),
+          'nns_spec_ns_step_operator_adjoint_f32')
+    return lam, mu, gbar, lbar

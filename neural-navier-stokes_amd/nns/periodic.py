@@ -29,6 +29,9 @@ HIP kernels (tests/pspec_adjoint_oracle.py; measured 2.57x a forward step at 256
 2.5-2.6x a forward scalar step and 1.7-1.8x the flow's adjoint, profiles/pspec_scalar_adjoint_run.json).
 ``evolve`` / ``evolve_velocity`` are the complete entry points: the same node on EVERY solver, stochastic forcing, hyperviscosity, hypofriction
 and beta included (tests/pspec_linear_adjoint_oracle.py; profiles/pspec_linear_adjoint_run.json).
+Both take ``operator``, a table of the linear operator that the call is differentiable in as well, so nu, drag, nu_h, mu and beta
+(``operator_table``) or a learned lambda(k) (``mode_table``) are trained through the solver (tests/pspec_operator_grad_oracle.py; measured
+1.035x the adjoint without it at 256^2 x 64 and 1.109x at 1024^2 x 8, profiles/pspec_operator_grad_run.json).
 """
 import collections
 import math
@@ -187,11 +190,13 @@ class _AdvanceFn(torch.autograd.Function):
     with the general linear operator, else ops.spec_ns_step_adjoint_ / ops.spec_ns_step_scalar_adjoint_) between the compact and expand
     kernels.  A stochastic step has no adjoint of its own: the kick is additive and independent of the state, the saved start spectra carry
     it, and the generator is never run in the backward.  ``noise``: None, or (clock, noise_ids) of ``evolve`` for the state the forward
-    steps (ignored without a stochastic force).  ``velocity``: the flow's ends are init / fields instead of the vorticity's; theta's are
+    steps (ignored without a stochastic force).  ``operator``: None, or the table of ``evolve`` that takes the solver's place: the step is
+    then the linear one, and where the table requires grad the backward is ops.spec_ns_step_operator_adjoint_, the same launches with the
+    table's cotangent summed per grid, which ``_operator_gradient`` turns into the table's gradient.  ``velocity``: the flow's ends are init / fields instead of the vorticity's; theta's are
     spec_ns_scalar_init / spec_ns_scalar_field.  ``fields``: (w,) or (u0, v0), then with ``scalar`` theta."""
 
     @staticmethod
-    def forward(ctx, solver, nsteps, mean, velocity, scalar, forcing, noise, *fields):
+    def forward(ctx, solver, nsteps, mean, velocity, scalar, forcing, noise, operator, *fields):
         s = solver
         theta = fields[-1].detach() if scalar else None
         if velocity:
@@ -205,13 +210,17 @@ class _AdvanceFn(torch.autograd.Function):
         that0 = torch.empty_like(what0) if scalar else None
         if noise is not None and s.stoch_amp is not None:
             state.clock, state.noise_ids = s._noise_args(noise[0], noise[1], state)
+        if operator is None:
+            lin = s._linear_of(state) if s._linear() else None
+        else:
+            lin = s._operator_of(operator, state)
         for k in range(nsteps):
             what0[k].copy_(state.what)
             if scalar:
                 that0[k].copy_(state.that)
-            s._launch_steps(state, 1, ghat)
+            s._launch_steps(state, 1, ghat, lin)
         ctx.solver, ctx.velocity, ctx.scalar, ctx.squeeze = s, velocity, scalar, fields[0].dim() == 2
-        ctx.lin = s._linear_of(state) if s._linear() else None
+        ctx.lin = lin
         ctx.shared = forcing is not None and forcing.shape[0] == 1 and state.batch > 1
         ctx.force_shape = None if forcing is None else tuple(forcing.shape)
         ctx.save_for_backward(what0, state.mean, *(t for t in (that0, ghat) if t is not None))
@@ -240,7 +249,11 @@ class _AdvanceFn(torch.autograd.Function):
         need_g = ctx.force_shape is not None and ctx.needs_input_grad[5]
         gbar = torch.empty_like(lam) if need_g else None
         mu = ops.spec_ns_scalar_init(gout[-1], torch.empty_like(lam), work) if ctx.scalar else None
-        if ctx.lin is not None:
+        lbar = torch.empty_like(lam) if ctx.needs_input_grad[7] else None
+        if lbar is not None:                              # the same launches, the OPERATOR kernels in stages 3-1
+            ops.spec_ns_step_operator_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, s.ny, s.Lx, s.Ly, s.dt,
+                                               s.kappa if ctx.scalar else 0.0, s.scalar_gradient, s.buoyancy, ctx.lin, lbar)
+        elif ctx.lin is not None:
             ops.spec_ns_step_linear_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, s.ny, s.Lx, s.Ly, s.dt,
                                              s.kappa if ctx.scalar else 0.0, s.scalar_gradient, s.buoyancy, ctx.lin)
         elif ctx.scalar:
@@ -262,7 +275,8 @@ class _AdvanceFn(torch.autograd.Function):
             if ctx.shared:
                 gf = torch.sum(gf, dim=0, keepdim=True)
             gf = gf.reshape(ctx.force_shape)
-        return (None, None, None, None, None, gf, None) + grads
+        gop = None if lbar is None else s._operator_gradient(lbar)
+        return (None, None, None, None, None, gf, None, gop) + grads
 
 
 class PeriodicSolver(object):
@@ -329,7 +343,14 @@ class PeriodicSolver(object):
     exactly: under the grid sum that pairs cotangents the transpose of the factor E_k = exp(lambda_k dt / 2) is conj(E_k), read from the same
     table.  A stochastic step is differentiated as the deterministic step it contains -- the kick is additive and independent of the state, so
     its Jacobian is the identity and the saved start spectra carry it; ``clock`` names the first step's noise, so a rollout cut into chunks
-    repeats the uncut noise.  nu, nu_h, mu, beta, the drag, kappa, G, b, the amplitudes, the seed and the mean flow are constants.  ``advance``,
+    repeats the uncut noise.  Both also take ``operator``, a table (Re, Im)(lambda_k dt / 2) in the step's own layout that replaces the solver's
+    linear operator for the call and in which the call is differentiable too: for E = exp(l) the stages' derivatives in l need no N and no
+    division by E (d s1 = s1, d s2 = E w0, d s3 = s3 + E^2 w0, d w1 = (s3 + E^2 w0) / 3 + 2/3 E (s1 + s2)), and the adjoint's stages 3-1 sum
+    their products with the cotangents they already hold, in the same 16 launches (tests/pspec_operator_grad_oracle.py).  That covers nu, drag,
+    nu_h, mu and beta through ``operator_table`` and any learned diagonal operator, a per-mode eddy viscosity nu(k) for one, through
+    ``mode_table``.  With ``operator`` the call takes the LINEAR form of the step also on a solver without hyperviscosity, hypofriction or
+    beta: with a table of nu and drag alone that is the forced step's mathematics but not bitwise the forced step.  kappa, G, b, the noise
+    amplitudes, the seed, the mean flow and per-grid operators stay constants; ``advance*`` do not take the argument.  ``advance``,
     ``advance_velocity``, ``advance_scalar`` and ``advance_velocity_scalar`` are the same node on the solvers they were written for (the
     steady-forced flow; with ``kappa``, its scalar and buoyancy) and refuse the others.
 
@@ -627,17 +648,18 @@ class PeriodicSolver(object):
         """The scalar of this state acts on its flow: it has one and b != 0."""
         return state.that is not None and self.buoyancy != (0.0, 0.0)
 
-    def _launch_steps(self, state, nsteps, force=False):
+    def _launch_steps(self, state, nsteps, force=False, lin=None):
         """The step this solver takes on this state.  force: False, the solver's own (``set_forcing``); else the spectrum g^ that takes its place
-        (None: no force), as ``evolve`` passes its ``forcing``."""
+        (None: no force), as ``evolve`` passes its ``forcing``.  lin: None, the solver's own table where it has one; else the table that takes
+        its place, as ``evolve`` passes its ``operator``: the step is then the linear one on any solver."""
         what, that = state.what, state.that
         ghat = self._force_of(state) if force is False else force
         box = (ghat, state.work, self.ny, self.Lx, self.Ly, self.dt)                        # what every forced form takes after the mean
         kappa = 0.0 if self.kappa is None else self.kappa
         amp, clock, ids = (None, None, None) if self.stoch_amp is None else self._noise_of(state)
-        if self._linear():
-            ops.spec_ns_step_linear_(what, that, state.mean, *box, kappa, self.scalar_gradient, self.buoyancy, self._linear_of(state), amp,
-                                     self.stoch_seed, clock, ids, nsteps)
+        if lin is not None or self._linear():
+            ops.spec_ns_step_linear_(what, that, state.mean, *box, kappa, self.scalar_gradient, self.buoyancy,
+                                     self._linear_of(state) if lin is None else lin, amp, self.stoch_seed, clock, ids, nsteps)
         elif self.stoch_amp is not None:
             ops.spec_ns_step_stochastic_(what, that, state.mean, *box, self.nu, self.drag, kappa, self.scalar_gradient, self.buoyancy, amp,
                                          self.stoch_seed, clock, ids, nsteps)
@@ -751,7 +773,7 @@ class PeriodicSolver(object):
         Not for a solver with kappa or buoyancy (``advance_scalar`` / ``advance_velocity_scalar`` take and return the scalar) and not for a
         stochastic force, hyperviscosity, hypofriction or beta: NotImplementedError; ``evolve`` covers every solver."""
         nsteps, forcing, (w,) = self._advance_args('advance', False, nsteps, forcing, ('w', w))
-        return _AdvanceFn.apply(self, nsteps, mean, False, False, forcing, None, w)[0]
+        return _AdvanceFn.apply(self, nsteps, mean, False, False, forcing, None, None, w)[0]
 
     def advance_velocity(self, u0, v0, nsteps=1, forcing=None):
         """(u, v) after ``nsteps`` steps from the velocity (u0, v0), differentiable like ``advance`` (and in ``forcing``, a vorticity source as
@@ -760,7 +782,7 @@ class PeriodicSolver(object):
         The grid means (U0, V0) of (u0, v0) are constants of the motion and are not differentiated.  No pressure output.  The refusals of
         ``advance``; ``evolve_velocity`` covers every solver."""
         nsteps, forcing, (u0, v0) = self._advance_args('advance_velocity', False, nsteps, forcing, ('u0', u0), ('v0', v0))
-        return _AdvanceFn.apply(self, nsteps, None, True, False, forcing, None, u0, v0)
+        return _AdvanceFn.apply(self, nsteps, None, True, False, forcing, None, None, u0, v0)
 
     def advance_scalar(self, w, theta, nsteps=1, mean=None, forcing=None):
         """(w, theta) after ``nsteps`` steps from the vorticity field w and the scalar theta (float32 device tensors [B, nx, ny] or [nx, ny]) on a
@@ -774,7 +796,7 @@ class PeriodicSolver(object):
         the mean flow are constants and are not differentiated.  ValueError on a solver without kappa; not for a stochastic force,
         hyperviscosity, hypofriction or beta: NotImplementedError (``evolve`` covers every solver)."""
         nsteps, forcing, (w, theta) = self._advance_args('advance_scalar', True, nsteps, forcing, ('w', w), ('theta', theta))
-        return _AdvanceFn.apply(self, nsteps, mean, False, True, forcing, None, w, theta)
+        return _AdvanceFn.apply(self, nsteps, mean, False, True, forcing, None, None, w, theta)
 
     def advance_velocity_scalar(self, u0, v0, theta0, nsteps=1, forcing=None):
         """(u, v, theta) after ``nsteps`` steps from the velocity (u0, v0) and the scalar theta0, differentiable like ``advance_scalar``:
@@ -782,7 +804,109 @@ class PeriodicSolver(object):
         ``advance_velocity``.  No pressure output.  The refusals of ``advance_scalar``; ``evolve_velocity`` covers every solver."""
         nsteps, forcing, (u0, v0, theta0) = self._advance_args('advance_velocity_scalar', True, nsteps, forcing, ('u0', u0), ('v0', v0),
                                                                ('theta0', theta0))
-        return _AdvanceFn.apply(self, nsteps, None, True, True, forcing, None, u0, v0, theta0)
+        return _AdvanceFn.apply(self, nsteps, None, True, True, forcing, None, None, u0, v0, theta0)
+
+    # ---- the linear operator as an argument of evolve
+    def _operator_arg(self, who, operator, field):
+        """The checked ``operator`` of ``evolve`` / ``evolve_velocity`` (None passes): a float32 tensor [my1, nx, 2] on the fields' device."""
+        if operator is None:
+            return None
+        if not isinstance(operator, torch.Tensor):
+            raise TypeError("%s: operator must be a torch tensor, got %s" % (who, type(operator).__name__))
+        if operator.dtype != torch.float32:
+            raise TypeError("%s: operator must be float32, got %s" % (who, operator.dtype))
+        if tuple(operator.shape) != (self.my1, self.nx, 2):
+            raise ValueError("%s: operator must be [%d, %d, 2] = (Re, Im)(lambda dt / 2) of the stored modes, got %s"
+                             % (who, self.my1, self.nx, tuple(operator.shape)))
+        if operator.device != field.device:
+            raise ValueError("%s: operator is on %s, the fields on %s" % (who, operator.device, field.device))
+        return operator
+
+    def _operator_of(self, operator, state):
+        """What the step reads of an ``operator``: its values, contiguous, on the state's device."""
+        if operator.device != state.what.device:
+            raise ValueError("operator is on %s, the state on %s" % (operator.device, state.what.device))
+        return operator.detach().contiguous()
+
+    def _operator_gradient(self, lbar):
+        """The gradient in the table, float32 [my1, nx, 2], from the per-grid sums lbar [B, my1, nx, 2] of ops.spec_ns_step_operator_adjoint_
+        (include/nns.h has the definition): the grids summed in a fixed order (one deterministic torch.sum), a stored mode with ky > 0 weighted
+        2 / (nx ny) for itself and its mirror image, and the ky = 0 line, which stores both kx and -kx, made (T(kx) + conj(T(-kx))) / (2 nx ny):
+        the part of the cotangent that a table with l(-k) = conj(l(k)) can feel, exactly symmetric in float32 (the sum commutes, the weights are
+        powers of two)."""
+        T = torch.sum(lbar, dim=0)
+        n = float(self.nx * self.ny)
+        G = T * (2.0 / n)
+        mirror = T[0, (-torch.arange(self.nx, device=T.device)) % self.nx]
+        G[0, :, 0] = (T[0, :, 0] + mirror[:, 0]) * (0.5 / n)
+        G[0, :, 1] = (T[0, :, 1] - mirror[:, 1]) * (0.5 / n)
+        return G
+
+    def mode_table(self, device=None):
+        """(kx, ky, k2, kept) of the stored modes in the layout of one grid of ``what`` and of ``operator``, [my1, nx] on ``device`` (None: the
+        default device): the wavenumbers and |k|^2 as float64, and the bool mask of the modes the step keeps (the 2/3 band without (0, 0)).
+        Row j holds ky = 2 pi j / Ly >= 0, column e the kx of numpy.fft.fftfreq; row 0 holds both kx and -kx.  With it an ``operator`` can be
+        written as a function of k, e.g. a network of |k| for a learned eddy viscosity: Re = -nu(|k|) k2 dt / 2 on ``kept``, 0 elsewhere."""
+        from ._util import default_device
+        dev = torch.device(default_device() if device is None else device)
+        S, shell, k2, kept, wt, kx = self._shell_table()
+        ky = 2 * np.pi / self.Ly * np.arange(self.my1, dtype=np.float64)[:, None]
+        t = lambda a: torch.from_numpy(np.array(np.broadcast_to(a, k2.shape))).to(dev)            # a writable copy
+        return t(kx), t(ky), t(k2), t(kept)
+
+    def operator_table(self, nu=None, drag=None, hyperviscosity=None, hypofriction=None, beta=None, device=None):
+        """The table ``evolve(..., operator=)`` takes, float32 [my1, nx, 2] = (Re, Im)(lambda_k dt / 2) on ``device`` (None: the default device),
+        built from the class note's formula as a differentiable torch function of its parameters:
+            lambda_k = -(nu |k|^2 + drag + nu_h |k|^2p + mu |k|^-2q) + i beta kx / |k|^2 on the kept modes, 0 elsewhere and at (0, 0).
+        nu, drag, beta: Python numbers or 0-dim tensors that may require grad; ``hyperviscosity`` = (nu_h, p) and ``hypofriction`` = (mu, q) with
+        nu_h, mu such and p, q Python ints (the powers |k|^2p, |k|^-2q are made on the host in float64 and are constants).  None: the solver's
+        own value.  So ``evolve(w, n, operator=solver.operator_table(nu=nu_t))`` followed by backward() puts d loss / d nu in nu_t.grad, and
+        likewise for drag, nu_h, mu and beta, with no kernel beyond the table's.  Computed in float64 on the device in the order of
+        ``linear_operator`` / ``_linear_table`` (the angle taken into [-pi, pi] the same way) and cast to float32: with the solver's own
+        numbers it is the solver's table.  Signs and finiteness are not checked (that would synchronise with the host)."""
+        from ._util import default_device
+        dev = torch.device(default_device() if device is None else device)
+        S, shell, k2, kept, wt, kx = self._shell_table()
+        k2 = np.where(kept, k2, 1.0)
+        f64 = lambda a: torch.from_numpy(np.array(np.broadcast_to(a, k2.shape), dtype=np.float64)).to(dev)      # a writable copy
+
+        def number(name, x, own):
+            if x is None:
+                return own
+            if isinstance(x, torch.Tensor):
+                if x.dim() != 0:
+                    raise ValueError("%s must be a number or a 0-dim tensor, got shape %s" % (name, tuple(x.shape)))
+                return x.to(device=dev, dtype=torch.float64)
+            return _real(name, x, kind='hold real numbers')
+
+        def power(name, term, own, coef, lo, hi):
+            if term is None:
+                return own
+            try:
+                c, n = term
+            except (TypeError, ValueError):
+                raise TypeError("%s must be None or (%s, power), got %r" % (name, coef, term))
+            n = _int('the power of %s' % name, n)
+            if not lo <= n <= hi:
+                raise ValueError("the power of %s = %d must be in [%d, %d]" % (name, n, lo, hi))
+            return number('%s of %s' % (coef, name), c, None), n
+
+        nu, drag, beta = number('nu', nu, self.nu), number('drag', drag, self.drag), number('beta', beta, self.beta)
+        (nu_h, p), (mu, q) = power('hyperviscosity', hyperviscosity, self.hyperviscosity, 'nu_h', 2, 8), \
+            power('hypofriction', hypofriction, self.hypofriction, 'mu', 1, 4)
+        on = lambda c: isinstance(c, torch.Tensor) or c > 0          # linear_operator's own test for a Python number
+        k2d, keptd = f64(k2), torch.from_numpy(np.ascontiguousarray(kept)).to(dev)
+        with np.errstate(over='ignore', invalid='ignore'):
+            damp = nu * k2d + drag
+            if on(nu_h):
+                damp = damp + nu_h * f64(k2 ** p)
+            if on(mu):
+                damp = damp + mu * f64(k2 ** (-q))
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        re = torch.where(keptd, -damp + 0.0, zero) * (0.5 * self.dt)        # + 0.0: an undamped mode is +0, as the complex sum makes it there
+        im = torch.where(keptd, (beta * f64(kx)) / k2d, zero) * (0.5 * self.dt)
+        im = torch.remainder(im + np.pi, 2 * np.pi) - np.pi
+        return torch.stack([re, im], dim=-1).to(torch.float32)
 
     def _noise_args(self, clock, noise_ids, state):
         """(clock, noise_ids) of ``evolve`` as a state's: clock an int >= 0 or an int64 device tensor [1], copied (the step advances the copy);
@@ -803,7 +927,7 @@ class PeriodicSolver(object):
                 raise ValueError("noise_ids: one id per grid, [%d], expected, got %d" % (B, ids.numel()))
         return clock, ids
 
-    def evolve(self, w, nsteps=1, theta=None, mean=None, forcing=None, clock=0, noise_ids=None):
+    def evolve(self, w, nsteps=1, theta=None, mean=None, forcing=None, clock=0, noise_ids=None, operator=None):
         """``advance`` / ``advance_scalar`` on EVERY solver: the vorticity field after ``nsteps`` steps (with ``theta``, required iff the solver has
         ``kappa``: the pair (w, theta)), differentiable in w, theta and ``forcing`` through the same autograd node.  The forward takes the step
         ``step`` takes -- linear (hyperviscosity, hypofriction, beta), stochastic, buoyant, scalar, forced or plain -- and is bitwise ``step`` on
@@ -812,21 +936,31 @@ class PeriodicSolver(object):
         step it contains: the kick is additive and independent of the state, and the saved start spectra carry it.  ``clock``: the index of the
         first step's noise, an int or an int64 device tensor [1] that is copied, never advanced: a rollout cut into chunks passes n0,
         n0 + nsteps, ... and reproduces the uncut noise; ``noise_ids`` as on ``PeriodicState`` (None: arange(B)).  Both are ignored without a
-        stochastic force.  ``mean`` and ``forcing`` as in ``advance``; nu, drag, the table, the amplitudes and the seed are constants and are not
-        differentiated.  On a solver ``advance`` / ``advance_scalar`` accept, outputs and gradients are theirs, bitwise."""
+        stochastic force.  ``mean`` and ``forcing`` as in ``advance``; the amplitudes and the seed are constants and are not differentiated, and
+        without ``operator`` nu, drag and the table are too.  On a solver ``advance`` / ``advance_scalar`` accept, outputs and gradients are
+        theirs, bitwise.
+        ``operator``: None, or a float32 device tensor [my1, nx, 2] = (Re, Im)(lambda_k dt / 2) in the solver's table layout (``mode_table``
+        names the modes) that takes the place of the solver's own linear operator in this call -- ``operator_table(nu=..., drag=...)`` builds
+        one from physical parameters, a network of |k| a learned one.  The call then takes the LINEAR step with that table, on any solver, and
+        is differentiable in it: the backward sums the table's cotangent in the adjoint's own launches (the class note).  The table must obey
+        l(-k) = conj(l(k)) on the ky = 0 line, where both kx and -kx are stored, and should have Re <= 0; neither is checked.  The gradient
+        returned obeys the symmetry, is zero off the kept modes and at (0, 0), and the gradients of the fields and of ``forcing`` are bitwise
+        those of the call without the table's gradient."""
         scalar = theta is not None
         fields = (('w', w), ('theta', theta)) if scalar else (('w', w),)
         nsteps, forcing, fields = self._advance_args('evolve', scalar, nsteps, forcing, *fields, complete=True)
-        out = _AdvanceFn.apply(self, nsteps, mean, False, scalar, forcing, (clock, noise_ids), *fields)
+        operator = self._operator_arg('evolve', operator, fields[0])
+        out = _AdvanceFn.apply(self, nsteps, mean, False, scalar, forcing, (clock, noise_ids), operator, *fields)
         return out if scalar else out[0]
 
-    def evolve_velocity(self, u0, v0, nsteps=1, theta0=None, forcing=None, clock=0, noise_ids=None):
+    def evolve_velocity(self, u0, v0, nsteps=1, theta0=None, forcing=None, clock=0, noise_ids=None, operator=None):
         """``evolve`` from and to the velocity: (u, v), or with ``theta0`` (required iff the solver has ``kappa``) (u, v, theta), after ``nsteps``
-        steps, with the ends of ``advance_velocity`` / ``advance_velocity_scalar``.  No pressure output."""
+        steps, with the ends of ``advance_velocity`` / ``advance_velocity_scalar``.  No pressure output.  ``operator`` as in ``evolve``."""
         scalar = theta0 is not None
         fields = (('u0', u0), ('v0', v0)) + ((('theta0', theta0),) if scalar else ())
         nsteps, forcing, fields = self._advance_args('evolve_velocity', scalar, nsteps, forcing, *fields, complete=True)
-        return _AdvanceFn.apply(self, nsteps, None, True, scalar, forcing, (clock, noise_ids), *fields)
+        operator = self._operator_arg('evolve_velocity', operator, fields[0])
+        return _AdvanceFn.apply(self, nsteps, None, True, scalar, forcing, (clock, noise_ids), operator, *fields)
 
     def diagnostics(self, state):
         """Diagnostics(energy, enstrophy, power_in), each float64 [B], computed on the device from the state's spectrum:
