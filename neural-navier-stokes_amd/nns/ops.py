@@ -937,12 +937,59 @@ def spec_ns_init(u, v, what, mean, work, Lx, Ly):
     return what, mean
 
 
+def _pn(t):
+    """t's device pointer; None (NULL) for None."""
+    return None if t is None else t.data_ptr()
+
+
+def _spec_ns_f32(who, name, t, shape, device):
+    """t is a contiguous float32 tensor of `shape` on the state's device."""
+    _f32(t)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: %s must be float32 %s, got %s" % (who, name, list(shape), tuple(t.shape)))
+    if t.device != device:
+        raise ValueError("%s: %s must be on the state's device %s" % (who, name, device))
+
+
+_ABSENT = object()                 # in place of an argument that a C entry does not have (None is a NULL it does have)
+
+
+def _spec_ns_step(entry, what, mean, work, ny, Lx, Ly, dt, numbers, nsteps, that=_ABSENT, ghat=_ABSENT, lin=_ABSENT, noise=_ABSENT,
+                  optional=()):
+    """Every forward step: the checks of the tensors, then the call of `entry`, whose arguments are what, [that,] mean, [ghat, gbatch,] work,
+    its size, the box and dt, `numbers` (the entry's doubles after dt), [lin,] [amp, seed, clock, ids,] nsteps and the stream.  that, ghat,
+    lin, noise = (amp, seed, clock, ids): the bracketed ones the entry has; `optional` names those of 'that' and 'noise' it takes as NULL
+    (that None; amp, clock and ids all None).  The caller's name in the messages is the entry's without nns_ and f32."""
+    who = entry[4:-3]
+    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
+    args = [_p(what)]
+    if that is not _ABSENT:
+        if that is not None or 'that' not in optional:
+            _spec_ns_same(who, that, what)
+        args.append(_pn(that))
+    args.append(_p(mean))
+    if ghat is not _ABSENT:
+        args += (_pn(ghat), _spec_ns_force(who, ghat, what))
+    args += (_p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt))
+    args.extend(map(float, numbers))
+    if lin is not _ABSENT:
+        _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), what.device)
+        args.append(_p(lin))
+    if noise is not _ABSENT:
+        amp, seed, clock, ids = noise
+        if 'noise' in optional and (amp is None or clock is None or ids is None):
+            if not (amp is None and clock is None and ids is None):
+                raise ValueError("%s: amp, clock and ids must be all None (no noise) or all given" % who)
+        else:
+            _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
+        args += (_pn(amp), int(seed), _pn(clock), _pn(ids))
+    check(getattr(_lib.lib(), entry)(*args, int(nsteps), _stream()), entry)
+    return what
+
+
 def spec_ns_step_(what, mean, work, ny, Lx, Ly, dt, nu, nsteps=1):
     """nsteps Lawson-RK4 steps on what in place (no allocation, no host synchronisation: capturable)."""
-    B, my1, nx = _spec_ns_state('spec_ns_step_', what, mean, work, ny)
-    check(_lib.lib().nns_spec_ns_step_f32(_p(what), _p(mean), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt),
-                                          float(nu), int(nsteps), _stream()), 'nns_spec_ns_step_f32')
-    return what
+    return _spec_ns_step('nns_spec_ns_step_f32', what, mean, work, ny, Lx, Ly, dt, (nu,), nsteps)
 
 
 def spec_ns_fields(what, mean, work, ny, Lx, Ly, rho, out=None):
@@ -970,12 +1017,7 @@ def _spec_ns_force(who, ghat, what):
 def spec_ns_step_forced_(what, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, nsteps=1):
     """nsteps Lawson-RK4 steps with the force spectrum ghat ([1, my1, nx, 2]: shared by the batch, [B, my1, nx, 2]: one per grid, None: no
     force) and the linear drag `drag` on what in place (no allocation, no host synchronisation: capturable)."""
-    B, my1, nx = _spec_ns_state('spec_ns_step_forced_', what, mean, work, ny)
-    gbatch = _spec_ns_force('spec_ns_step_forced_', ghat, what)
-    check(_lib.lib().nns_spec_ns_step_forced_f32(_p(what), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(work), work.numel(), B, nx,
-                                                 int(ny), float(Lx), float(Ly), float(dt), float(nu), float(drag), int(nsteps), _stream()),
-          'nns_spec_ns_step_forced_f32')
-    return what
+    return _spec_ns_step('nns_spec_ns_step_forced_f32', what, mean, work, ny, Lx, Ly, dt, (nu, drag), nsteps, ghat=ghat)
 
 
 def spec_ns_diag(what, ghat, ny, Lx, Ly, out=None):
@@ -983,12 +1025,12 @@ def spec_ns_diag(what, ghat, ny, Lx, Ly, out=None):
     B, my1, nx = _spec_ns_state('spec_ns_diag', what, None, None, ny)
     gbatch = _spec_ns_force('spec_ns_diag', ghat, what)
     out = _spec_ns_out('spec_ns_diag', out, (B, 3), what.device)
-    check(_lib.lib().nns_spec_ns_diag_f32(_p(what), _p(ghat) if gbatch else None, gbatch, _p(out), B, nx, int(ny), float(Lx), float(Ly),
+    check(_lib.lib().nns_spec_ns_diag_f32(_p(what), _pn(ghat), gbatch, _p(out), B, nx, int(ny), float(Lx), float(Ly),
                                           _stream()), 'nns_spec_ns_diag_f32')
     return out
 
 
-# passive scalar of the periodic solver (nns_spec_ns_scalar_*, nns_spec_ns_step_scalar_f32)
+# passive scalar of the periodic solver (nns_spec_ns_scalar_*, and its step)
 def spec_ns_scalar_workspace(B, nx, ny):
     """Bytes of the workspace the scalar calls need for B grids of nx x ny (>= spec_ns_workspace: it serves every spec_ns call)."""
     return _query_bytes('nns_spec_ns_scalar_workspace', int(B), int(nx), int(ny))
@@ -1029,25 +1071,17 @@ def spec_ns_scalar_field(that, work, ny, out=None):
     return out
 
 
-def _spec_ns_same(who, that, what):
-    _f32(that)
-    if tuple(that.shape) != tuple(what.shape) or that.device != what.device:
-        raise ValueError("%s: that must be float32 %s on the state's device, got %s on %s"
-                         % (who, tuple(what.shape), tuple(that.shape), that.device))
+def _spec_ns_same(who, that, what, name='that'):
+    """that (under `name` in the messages) is a spectrum like what."""
+    _spec_ns_f32(who, name, that, what.shape, what.device)
 
 
 def spec_ns_step_scalar_(what, that, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, kappa, grad=(0.0, 0.0), nsteps=1):
     """nsteps Lawson-RK4 steps of the flow and its passive scalar, (what, that) in place: diffusivity kappa, uniform mean gradient grad =
     (Gx, Gy); ghat and drag as in spec_ns_step_forced_ (None and 0: the unforced flow).  what comes out bitwise as without the scalar.
     work: spec_ns_scalar_workspace bytes.  No allocation, no host synchronisation: capturable."""
-    B, my1, nx = _spec_ns_state('spec_ns_step_scalar_', what, mean, work, ny)
-    _spec_ns_same('spec_ns_step_scalar_', that, what)
-    gbatch = _spec_ns_force('spec_ns_step_scalar_', ghat, what)
-    gx, gy = grad
-    check(_lib.lib().nns_spec_ns_step_scalar_f32(_p(what), _p(that), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(work), work.numel(), B,
-                                                 nx, int(ny), float(Lx), float(Ly), float(dt), float(nu), float(drag), float(kappa), float(gx),
-                                                 float(gy), int(nsteps), _stream()), 'nns_spec_ns_step_scalar_f32')
-    return what, that
+    return _spec_ns_step('nns_spec_ns_step_scalar_f32', what, mean, work, ny, Lx, Ly, dt, (nu, drag, kappa, *grad), nsteps, that=that,
+                         ghat=ghat), that
 
 
 def spec_ns_scalar_diag(what, that, ny, Lx, Ly, kappa, out=None):
@@ -1077,7 +1111,7 @@ def spec_ns_spectrum(what, that, ghat, ny, Lx, Ly, out=None):
     gbatch = _spec_ns_force('spec_ns_spectrum', ghat, what)
     S = spec_ns_shells(nx, ny, Lx, Ly)[0]
     out = _spec_ns_out('spec_ns_spectrum', out, (B, 4, S), what.device)
-    check(_lib.lib().nns_spec_ns_spectrum_f32(_p(what), None if that is None else _p(that), _p(ghat) if gbatch else None, gbatch, _p(out), S, B,
+    check(_lib.lib().nns_spec_ns_spectrum_f32(_p(what), _pn(that), _pn(ghat), gbatch, _p(out), S, B,
                                               nx, int(ny), float(Lx), float(Ly), _stream()), 'nns_spec_ns_spectrum_f32')
     return out
 
@@ -1094,38 +1128,30 @@ def spec_ns_transfer(what, that, work, ny, Lx, Ly, out=None):
         _spec_ns_same('spec_ns_transfer', that, what)
     S = spec_ns_shells(nx, ny, Lx, Ly)[0]
     out = _spec_ns_out('spec_ns_transfer', out, (B, 3, S), what.device)
-    check(_lib.lib().nns_spec_ns_transfer_f32(_p(what), None if that is None else _p(that), _p(out), S, _p(work), work.numel(), B, nx, int(ny),
+    check(_lib.lib().nns_spec_ns_transfer_f32(_p(what), _pn(that), _p(out), S, _p(work), work.numel(), B, nx, int(ny),
                                               float(Lx), float(Ly), _stream()), 'nns_spec_ns_transfer_f32')
     return out
 
 
-# Boussinesq buoyancy of the periodic solver (nns_spec_ns_step_buoyant_f32, nns_spec_ns_fields_buoyant_f32, nns_spec_ns_buoyancy_spectrum_f32)
+# Boussinesq buoyancy of the periodic solver (its step, nns_spec_ns_fields_buoyant_f32, nns_spec_ns_buoyancy_spectrum_f32)
 def spec_ns_step_buoyant_(what, that, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, kappa, grad, buoyancy, nsteps=1):
     """spec_ns_step_scalar_ with the scalar acting on the flow through buoyancy = (bx, by): w_t gains by theta_x - bx theta_y, every stage with
     its own theta^.  (0, 0) makes exactly the calls of spec_ns_step_scalar_.  No allocation, no host synchronisation: capturable."""
-    B, my1, nx = _spec_ns_state('spec_ns_step_buoyant_', what, mean, work, ny)
-    _spec_ns_same('spec_ns_step_buoyant_', that, what)
-    gbatch = _spec_ns_force('spec_ns_step_buoyant_', ghat, what)
-    (gx, gy), (bx, by) = grad, buoyancy
-    check(_lib.lib().nns_spec_ns_step_buoyant_f32(_p(what), _p(that), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(work), work.numel(), B,
-                                                  nx, int(ny), float(Lx), float(Ly), float(dt), float(nu), float(drag), float(kappa), float(gx),
-                                                  float(gy), float(bx), float(by), int(nsteps), _stream()), 'nns_spec_ns_step_buoyant_f32')
-    return what, that
+    return _spec_ns_step('nns_spec_ns_step_buoyant_f32', what, mean, work, ny, Lx, Ly, dt, (nu, drag, kappa, *grad, *buoyancy), nsteps,
+                         that=that, ghat=ghat), that
 
 
-# white-in-time stochastic forcing of the periodic solver (nns_spec_ns_step_stochastic_f32)
+# white-in-time stochastic forcing of the periodic solver
 def _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, device):
     """The checked noise arguments of a step: amp float32 [my1, nx], clock int64 [1] and ids int32 [B] on the state's device, seed a 64-bit int."""
-    _f32(amp)
-    if tuple(amp.shape) != (my1, nx):
-        raise ValueError("%s: amp must be float32 [%d, %d], got %s" % (who, my1, nx, tuple(amp.shape)))
+    _spec_ns_f32(who, 'amp', amp, (my1, nx), device)
     for name, t, dtype, shape in (('clock', clock, torch.int64, (1,)), ('ids', ids, torch.int32, (B,))):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
             raise TypeError("%s: %s must be a contiguous %s device tensor" % (who, name, dtype))
         if tuple(t.shape) != shape:
             raise ValueError("%s: %s must be %s %s, got %s" % (who, name, dtype, list(shape), tuple(t.shape)))
-    if any(t.device != device for t in (amp, clock, ids)):
-        raise ValueError("%s: amp, clock and ids must be on the state's device %s" % (who, device))
+    if clock.device != device or ids.device != device:
+        raise ValueError("%s: clock and ids must be on the state's device %s" % (who, device))
     if isinstance(seed, bool) or not isinstance(seed, numbers.Integral):
         raise TypeError("%s: seed must be an int, got %r" % (who, seed))
     if not 0 <= seed < 2 ** 64:
@@ -1137,18 +1163,8 @@ def spec_ns_step_stochastic_(what, that, mean, ghat, work, ny, Lx, Ly, dt, nu, d
     the kick w^ += sqrt(dt) amp xi(n, ids[b]): amp float32 [my1, nx] (shared by the batch), seed a 64-bit int, clock int64 [1] (the state's
     stochastic step count, advanced on the device) and ids int32 [B], all on the state's device.  No allocation, no host synchronisation:
     capturable, and a replay continues the noise sequence."""
-    who = 'spec_ns_step_stochastic_'
-    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
-    if that is not None:
-        _spec_ns_same(who, that, what)
-    gbatch = _spec_ns_force(who, ghat, what)
-    _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
-    (gx, gy), (bx, by) = grad, buoyancy
-    check(_lib.lib().nns_spec_ns_step_stochastic_f32(_p(what), None if that is None else _p(that), _p(mean), _p(ghat) if gbatch else None, gbatch,
-                                                     _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt), float(nu),
-                                                     float(drag), float(kappa), float(gx), float(gy), float(bx), float(by), _p(amp), int(seed),
-                                                     _p(clock), _p(ids), int(nsteps), _stream()), 'nns_spec_ns_step_stochastic_f32')
-    return what
+    return _spec_ns_step('nns_spec_ns_step_stochastic_f32', what, mean, work, ny, Lx, Ly, dt, (nu, drag, kappa, *grad, *buoyancy), nsteps,
+                         that=that, ghat=ghat, noise=(amp, seed, clock, ids), optional=('that',))
 
 
 def spec_ns_fields_buoyant(what, that, mean, work, ny, Lx, Ly, rho, buoyancy, out=None):
@@ -1177,35 +1193,33 @@ def spec_ns_buoyancy_spectrum(what, that, ny, Lx, Ly, buoyancy, out=None):
     return out
 
 
-# general linear operator of the periodic solver (nns_spec_ns_step_linear_f32, nns_spec_ns_linear_spectrum_f32)
+# general linear operator of the periodic solver (its step, nns_spec_ns_linear_spectrum_f32)
 def spec_ns_step_linear_(what, that, mean, ghat, work, ny, Lx, Ly, dt, kappa, grad, buoyancy, lin, amp=None, seed=0, clock=None, ids=None,
                          nsteps=1):
     """nsteps steps of spec_ns_step_stochastic_ (that None: no scalar; amp, clock and ids all None: no noise) with the vorticity's linear
     operator taken from lin, float32 [my1, nx, 2] = (Re, Im)(lambda dt / 2) on the state's device (shared by the batch), which holds viscosity
     and drag: neither is an argument.  No allocation, no host synchronisation: capturable."""
-    who = 'spec_ns_step_linear_'
-    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
+    return _spec_ns_step('nns_spec_ns_step_linear_f32', what, mean, work, ny, Lx, Ly, dt, (kappa, *grad, *buoyancy), nsteps, that=that,
+                         ghat=ghat, lin=lin, noise=(amp, seed, clock, ids), optional=('that', 'noise'))
+
+
+def spec_ns_advance_(what, that, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, kappa, grad, buoyancy, lin=None, noise=None, nsteps=1):
+    """nsteps steps by the least general of the six entries above that covers the arguments -- the one rule by which the package picks a
+    step: a table lin: the linear step (nu and drag are then the table's); else noise = (amp, seed, clock, ids): the stochastic one; else a
+    scalar that with buoyancy != (0, 0): the buoyant one; else a scalar: the scalar one; else a force ghat or drag > 0: the forced one; else
+    the plain one."""
+    box = (work, ny, Lx, Ly, dt)
+    if lin is not None:
+        return spec_ns_step_linear_(what, that, mean, ghat, *box, kappa, grad, buoyancy, lin, *(noise or (None, 0, None, None)), nsteps)
+    if noise is not None:
+        return spec_ns_step_stochastic_(what, that, mean, ghat, *box, nu, drag, kappa, grad, buoyancy, *noise, nsteps)
+    if that is not None and tuple(buoyancy) != (0.0, 0.0):
+        return spec_ns_step_buoyant_(what, that, mean, ghat, *box, nu, drag, kappa, grad, buoyancy, nsteps)[0]
     if that is not None:
-        _spec_ns_same(who, that, what)
-    gbatch = _spec_ns_force(who, ghat, what)
-    _f32(lin)
-    if tuple(lin.shape) != (my1, nx, 2):
-        raise ValueError("%s: lin must be float32 [%d, %d, 2], got %s" % (who, my1, nx, tuple(lin.shape)))
-    if lin.device != what.device:
-        raise ValueError("%s: lin must be on the state's device %s" % (who, what.device))
-    noise = (amp, clock, ids)
-    if any(t is None for t in noise):
-        if any(t is not None for t in noise):
-            raise ValueError("%s: amp, clock and ids must be all None (no noise) or all given" % who)
-    else:
-        _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
-    (gx, gy), (bx, by) = grad, buoyancy
-    opt = lambda t: None if t is None else _p(t)
-    check(_lib.lib().nns_spec_ns_step_linear_f32(_p(what), opt(that), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(work), work.numel(), B,
-                                                 nx, int(ny), float(Lx), float(Ly), float(dt), float(kappa), float(gx), float(gy), float(bx),
-                                                 float(by), _p(lin), opt(amp), int(seed), opt(clock), opt(ids), int(nsteps), _stream()),
-          'nns_spec_ns_step_linear_f32')
-    return what
+        return spec_ns_step_scalar_(what, that, mean, ghat, *box, nu, drag, kappa, grad, nsteps)[0]
+    if ghat is not None or drag > 0:
+        return spec_ns_step_forced_(what, mean, ghat, *box, nu, drag, nsteps)
+    return spec_ns_step_(what, mean, *box, nu, nsteps)
 
 
 def spec_ns_linear_spectrum(what, rate, ny, Lx, Ly, out=None):
@@ -1300,7 +1314,7 @@ class PinnHeadFn(torch.autograd.Function):
         return grad, None, None, None, None, None, None
 
 
-# reverse mode of the periodic solver's forced step (nns_spec_ns_adjoint_workspace, nns_spec_ns_step_adjoint_f32)
+# reverse mode of the periodic solver's forced step
 def spec_ns_adjoint_workspace(B, nx, ny):
     """Bytes of the workspace spec_ns_step_adjoint_ needs for B grids of nx x ny (>= spec_ns_workspace)."""
     return _query_bytes('nns_spec_ns_adjoint_workspace', int(B), int(nx), int(ny))
@@ -1317,8 +1331,43 @@ def _spec_ns_adjoint_tensors(who, lam, ghat, gbar, **starts):
                              % ((who, name) + tuple(lam.shape[:3]) + (tuple(t.shape),)))
     gbatch = _spec_ns_force(who, ghat, lam)
     if gbar is not None:
-        _spec_ns_same(who, gbar, lam)
+        _spec_ns_same(who, gbar, lam, 'gbar')
     return gbatch
+
+
+def _spec_ns_adjoint(entry, what0, mean, ghat, lam, gbar, work, ny, Lx, Ly, dt, numbers, scalar=_ABSENT, optional=False, lin=_ABSENT,
+                     lbar=_ABSENT):
+    """Every adjoint call: the checks of the tensors, then the call of `entry`, whose arguments are what0, [that0,] mean, ghat, gbatch, lam,
+    [mu,] gbar, work, its size, the box and dt, `numbers` (the entry's doubles after dt), [lin,] nsteps (what0's) and the stream [, lbar].
+    scalar = (that0, mu), lin, lbar: the bracketed ones the entry has; `optional`: it takes that0 and mu as NULL (both None: no scalar).  The
+    caller's name in the messages is the entry's without nns_ and f32."""
+    who = entry[4:-3]
+    B, my1, nx = _spec_ns_state(who, lam, mean, work, ny)
+    that0, mu = (None, None) if scalar is _ABSENT else scalar
+    if optional and (that0 is None) != (mu is None):
+        raise ValueError("%s: that0 and mu must be both None (no scalar) or both given" % who)
+    starts = {'what0': what0}
+    if scalar is not _ABSENT and not (optional and that0 is None):
+        _spec_ns_same(who, mu, lam, 'mu')
+        starts['that0'] = that0
+    gbatch = _spec_ns_adjoint_tensors(who, lam, ghat, gbar, **starts)
+    args = [_p(what0)]
+    if scalar is not _ABSENT:
+        args.append(_pn(that0))
+    args += (_p(mean), _pn(ghat), gbatch, _p(lam))
+    if scalar is not _ABSENT:
+        args.append(_pn(mu))
+    args += (_pn(gbar), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt))
+    args.extend(map(float, numbers))
+    if lin is not _ABSENT:
+        _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), lam.device)
+        args.append(_p(lin))
+    args += (int(what0.shape[0]), _stream())
+    if lbar is not _ABSENT:
+        if lbar is not None:
+            _spec_ns_same(who, lbar, lam, 'lbar')
+        args.append(_pn(lbar))
+    check(getattr(_lib.lib(), entry)(*args), entry)
 
 
 def spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, work, ny, Lx, Ly, dt, nu, drag):
@@ -1327,16 +1376,11 @@ def spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, work, ny, Lx, Ly, dt, nu
     shape, or None) receives the cotangent of g^, one per grid, summed over the steps.  mean, ghat, dt, nu, drag: the forward's.  Cotangents
     are spectra of real fields paired by the grid sum.  work: spec_ns_adjoint_workspace bytes.  16 launches per step, no allocation, no host
     synchronisation."""
-    who = 'spec_ns_step_adjoint_'
-    B, my1, nx = _spec_ns_state(who, lam, mean, work, ny)
-    gbatch = _spec_ns_adjoint_tensors(who, lam, ghat, gbar, what0=what0)
-    check(_lib.lib().nns_spec_ns_step_adjoint_f32(_p(what0), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(lam),
-                                                  None if gbar is None else _p(gbar), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly),
-                                                  float(dt), float(nu), float(drag), int(what0.shape[0]), _stream()), 'nns_spec_ns_step_adjoint_f32')
+    _spec_ns_adjoint('nns_spec_ns_step_adjoint_f32', what0, mean, ghat, lam, gbar, work, ny, Lx, Ly, dt, (nu, drag))
     return lam, gbar
 
 
-# reverse mode of the periodic solver's scalar and buoyant step (nns_spec_ns_scalar_adjoint_workspace, nns_spec_ns_step_scalar_adjoint_f32)
+# reverse mode of the periodic solver's scalar and buoyant step
 def spec_ns_scalar_adjoint_workspace(B, nx, ny):
     """Bytes of the workspace spec_ns_step_scalar_adjoint_ needs for B grids of nx x ny (>= every other spec_ns workspace)."""
     return _query_bytes('nns_spec_ns_scalar_adjoint_workspace', int(B), int(nx), int(ny))
@@ -1349,80 +1393,45 @@ def spec_ns_step_scalar_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, 
     (w^, theta^) after the last step and, out, those of the pair before the first; gbar (the same shape, or None) receives the cotangent of the
     vorticity source g^, one per grid, summed over the steps.  mean, ghat, dt, nu, drag, kappa, grad, buoyancy: the forward's (buoyancy
     (0, 0): the passive scalar).  work: spec_ns_scalar_adjoint_workspace bytes.  16 launches per step, no allocation, no host synchronisation."""
-    who = 'spec_ns_step_scalar_adjoint_'
-    B, my1, nx = _spec_ns_state(who, lam, mean, work, ny)
-    _spec_ns_same(who, mu, lam)
-    gbatch = _spec_ns_adjoint_tensors(who, lam, ghat, gbar, what0=what0, that0=that0)
-    (gx, gy), (bx, by) = grad, buoyancy
-    check(_lib.lib().nns_spec_ns_step_scalar_adjoint_f32(_p(what0), _p(that0), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(lam), _p(mu),
-                                                         None if gbar is None else _p(gbar), _p(work), work.numel(), B, nx, int(ny), float(Lx),
-                                                         float(Ly), float(dt), float(nu), float(drag), float(kappa), float(gx), float(gy),
-                                                         float(bx), float(by), int(what0.shape[0]), _stream()),
-          'nns_spec_ns_step_scalar_adjoint_f32')
+    _spec_ns_adjoint('nns_spec_ns_step_scalar_adjoint_f32', what0, mean, ghat, lam, gbar, work, ny, Lx, Ly, dt,
+                     (nu, drag, kappa, *grad, *buoyancy), scalar=(that0, mu))
     return lam, mu, gbar
 
 
-# reverse mode of the periodic solver's linear step, with or without its scalar, buoyancy and noise (nns_spec_ns_step_linear_adjoint_f32)
+# reverse mode of the periodic solver's linear step, with or without its scalar, buoyancy and noise
 def spec_ns_step_linear_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, ny, Lx, Ly, dt, kappa, grad, buoyancy, lin):
     """spec_ns_step_adjoint_ (that0 and mu None; kappa, grad and buoyancy are then ignored; work: spec_ns_adjoint_workspace bytes) or
     spec_ns_step_scalar_adjoint_ (both given; work: spec_ns_scalar_adjoint_workspace bytes) for the steps of spec_ns_step_linear_: the
     vorticity's factors are the conjugates of the forward's, from the same table lin, float32 [my1, nx, 2] = (Re, Im)(lambda dt / 2) on the
     state's device, which holds viscosity and drag: neither is an argument.  A stochastic step's adjoint is this call on the start spectra the
     noisy forward saved: the kick's Jacobian is the identity.  16 launches per step, no allocation, no host synchronisation."""
-    who = 'spec_ns_step_linear_adjoint_'
-    B, my1, nx = _spec_ns_state(who, lam, mean, work, ny)
-    if (that0 is None) != (mu is None):
-        raise ValueError("%s: that0 and mu must be both None (no scalar) or both given" % who)
-    starts = {'what0': what0}
-    if that0 is not None:
-        _spec_ns_same(who, mu, lam)
-        starts['that0'] = that0
-    gbatch = _spec_ns_adjoint_tensors(who, lam, ghat, gbar, **starts)
-    _f32(lin)
-    if tuple(lin.shape) != (my1, nx, 2):
-        raise ValueError("%s: lin must be float32 [%d, %d, 2], got %s" % (who, my1, nx, tuple(lin.shape)))
-    if lin.device != lam.device:
-        raise ValueError("%s: lin must be on the state's device %s" % (who, lam.device))
-    (gx, gy), (bx, by) = grad, buoyancy
-    opt = lambda t: None if t is None else _p(t)
-    check(_lib.lib().nns_spec_ns_step_linear_adjoint_f32(_p(what0), opt(that0), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(lam), opt(mu),
-                                                         opt(gbar), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt),
-                                                         float(kappa), float(gx), float(gy), float(bx), float(by), _p(lin),
-                                                         int(what0.shape[0]), _stream()), 'nns_spec_ns_step_linear_adjoint_f32')
+    _spec_ns_adjoint('nns_spec_ns_step_linear_adjoint_f32', what0, mean, ghat, lam, gbar, work, ny, Lx, Ly, dt, (kappa, *grad, *buoyancy),
+                     scalar=(that0, mu), optional=True, lin=lin)
     return lam, mu, gbar
 
 
-# the same reverse mode, also differentiated in the linear operator's table (nns_spec_ns_step_operator_adjoint_f32)
+# the same reverse mode, also differentiated in the linear operator's table
 def spec_ns_step_operator_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, ny, Lx, Ly, dt, kappa, grad, buoyancy, lin, lbar):
     """spec_ns_step_linear_adjoint_ whose launches also sum the cotangent of the table lin into lbar (float32 [B, my1, nx, 2] on the state's
     device, overwritten): one per grid, summed over the steps of the call, zero off the band and at (0, 0), BEFORE the weight of the cotangent
     convention -- include/nns.h gives the table gradient it stands for (PeriodicSolver.evolve applies it).  lbar None: exactly
     spec_ns_step_linear_adjoint_.  The same 16 launches per step, no allocation, no host synchronisation."""
-    who = 'spec_ns_step_operator_adjoint_'
-    B, my1, nx = _spec_ns_state(who, lam, mean, work, ny)
-    if (that0 is None) != (mu is None):
-        raise ValueError("%s: that0 and mu must be both None (no scalar) or both given" % who)
-    starts = {'what0': what0}
-    if that0 is not None:
-        _spec_ns_same(who, mu, lam)
-        starts['that0'] = that0
-    gbatch = _spec_ns_adjoint_tensors(who, lam, ghat, gbar, **starts)
-    _f32(lin)
-    if tuple(lin.shape) != (my1, nx, 2):
-        raise ValueError("%s: lin must be float32 [%d, %d, 2], got %s" % (who, my1, nx, tuple(lin.shape)))
-    if lin.device != lam.device:
-        raise ValueError("%s: lin must be on the state's device %s" % (who, lam.device))
+    _spec_ns_adjoint('nns_spec_ns_step_operator_adjoint_f32', what0, mean, ghat, lam, gbar, work, ny, Lx, Ly, dt, (kappa, *grad, *buoyancy),
+                     scalar=(that0, mu), optional=True, lin=lin, lbar=lbar)
+    return lam, mu, gbar, lbar
+
+
+def spec_ns_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, ny, Lx, Ly, dt, nu, drag, kappa, grad, buoyancy, lin=None, lbar=None):
+    """The adjoint of the steps spec_ns_advance_ takes, by the least general of the four entries above that covers the arguments -- the one
+    rule by which the package picks an adjoint: lbar: the operator's (needs lin); else a table lin: the linear one; else a scalar (that0 and
+    mu): the scalar one; else the flow's.  Noise changes nothing: the kick's Jacobian is the identity.  Returns (lam, mu, gbar, lbar)."""
+    box = (work, ny, Lx, Ly, dt)
     if lbar is not None:
-        _f32(lbar)
-        if tuple(lbar.shape) != tuple(lam.shape):
-            raise ValueError("%s: lbar must be float32 [%d, %d, %d, 2], got %s" % ((who,) + tuple(lam.shape[:3]) + (tuple(lbar.shape),)))
-        if lbar.device != lam.device:
-            raise ValueError("%s: lbar must be on the state's device %s" % (who, lam.device))
-    (gx, gy), (bx, by) = grad, buoyancy
-    opt = lambda t: None if t is None else _p(t)
-    check(_lib.lib().nns_spec_ns_step_operator_adjoint_f32(_p(what0), opt(that0), _p(mean), _p(ghat) if gbatch else None, gbatch, _p(lam),
-                                                           opt(mu), opt(gbar), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly),
-                                                           float(dt), float(kappa), float(gx), float(gy), float(bx), float(by), _p(lin),
-                                                           int(what0.shape[0]), _stream(), opt(lbar)),
-          'nns_spec_ns_step_operator_adjoint_f32')
+        spec_ns_step_operator_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, *box, kappa, grad, buoyancy, lin, lbar)
+    elif lin is not None:
+        spec_ns_step_linear_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, *box, kappa, grad, buoyancy, lin)
+    elif that0 is not None:
+        spec_ns_step_scalar_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, *box, nu, drag, kappa, grad, buoyancy)
+    else:
+        spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, *box, nu, drag)
     return lam, mu, gbar, lbar

@@ -16,22 +16,18 @@ library picks that mode while its viscous amplification nu pi N / (sqrt(3) L) st
 otherwise, 2 = float64 forward transforms always.
 
 ``PeriodicSolver`` produces the trajectories such a residual measures: a pseudo-spectral solver of the same equations on the same box
-(csrc/pspec_kernels.hip; scheme in DESIGN.md and tests/pspec_oracle.py), optionally with a steady body force and a linear drag
-(tests/pspec_forced_oracle.py) and with a passive scalar -- temperature, dye -- that the same fused step transports
-(tests/pspec_scalar_oracle.py) and that, with ``buoyancy``, acts back on the flow (tests/pspec_buoyant_oracle.py).  Its ``spectrum`` and ``transfer`` give energy, enstrophy, injection, scalar variance and the nonlinear
-transfers by wavenumber shell (tests/pspec_spectrum_oracle.py).  ``set_stochastic_forcing`` / ``ring_forcing`` add a Gaussian, white-in-time force
-on chosen shells, generated on the device inside the step (tests/pspec_stochastic_oracle.py).  ``hyperviscosity``, ``hypofriction`` and ``beta``
-generalise the linear operator that the Lawson factor integrates exactly, at no launch, transform or stability limit (tests/pspec_linear_oracle.py;
-measured on the MI355X 1.016x the steady-forced step at 256^2 x 64 and 1.003x at 1024^2 x 8, profiles/pspec_linear_run.json).
-``advance`` / ``advance_velocity`` make the forced, damped flow differentiable: an autograd node whose backward is the adjoint of the step as
-HIP kernels (tests/pspec_adjoint_oracle.py; measured 2.57x a forward step at 256^2 x 64 and 2.72x at 1024^2 x 8, profiles/pspec_adjoint_run.json).
-``advance_scalar`` / ``advance_velocity_scalar`` do the same for the flow with its scalar and buoyancy (tests/pspec_scalar_adjoint_oracle.py; measured
-2.5-2.6x a forward scalar step and 1.7-1.8x the flow's adjoint, profiles/pspec_scalar_adjoint_run.json).
-``evolve`` / ``evolve_velocity`` are the complete entry points: the same node on EVERY solver, stochastic forcing, hyperviscosity, hypofriction
-and beta included (tests/pspec_linear_adjoint_oracle.py; profiles/pspec_linear_adjoint_run.json).
-Both take ``operator``, a table of the linear operator that the call is differentiable in as well, so nu, drag, nu_h, mu and beta
-(``operator_table``) or a learned lambda(k) (``mode_table``) are trained through the solver (tests/pspec_operator_grad_oracle.py; measured
-1.035x the adjoint without it at 256^2 x 64 and 1.109x at 1024^2 x 8, profiles/pspec_operator_grad_run.json).
+(csrc/pspec_kernels.hip; scheme and measurements in DESIGN.md).  Its class note is the user documentation; every feature is restated in
+float64 by an oracle under tests/:
+  * the unforced step                                            pspec_oracle.py
+  * steady body force and linear drag                            pspec_forced_oracle.py
+  * passive scalar; with ``buoyancy`` it acts on the flow        pspec_scalar_oracle.py, pspec_buoyant_oracle.py
+  * ``spectrum`` / ``transfer`` by wavenumber shell              pspec_spectrum_oracle.py
+  * white-in-time stochastic forcing made inside the step        pspec_stochastic_oracle.py
+  * hyperviscosity, hypofriction, beta in the Lawson factor      pspec_linear_oracle.py
+  * reverse mode, ``advance*`` (flow; scalar and buoyancy)       pspec_adjoint_oracle.py, pspec_scalar_adjoint_oracle.py
+  * reverse mode on every solver, ``evolve`` / ``evolve_velocity``   pspec_linear_adjoint_oracle.py
+  * their ``operator``: gradients in nu, drag, nu_h, mu, beta, lambda(k)   pspec_operator_grad_oracle.py
+Which C entry a step or an adjoint takes is decided in one place each, ops.spec_ns_advance_ and ops.spec_ns_adjoint_.
 """
 import collections
 import math
@@ -41,6 +37,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._util import default_device
 
 
 class ResidualEngine(object):
@@ -143,6 +140,11 @@ def _seed(seed):
     return seed
 
 
+def _device(device=None):
+    """``device`` as a torch.device; None: the default device."""
+    return torch.device(default_device() if device is None else device)
+
+
 Diagnostics = collections.namedtuple('Diagnostics', ['energy', 'enstrophy', 'power_in'])
 ScalarDiagnostics = collections.namedtuple('ScalarDiagnostics', ['variance', 'dissipation', 'flux_x', 'flux_y'])
 Spectrum = collections.namedtuple('Spectrum', ['k', 'energy', 'enstrophy', 'injection', 'variance'])
@@ -182,22 +184,24 @@ class PeriodicState(object):
         return c
 
 
+_Run = collections.namedtuple('_Run', ['solver', 'nsteps', 'mean', 'velocity', 'scalar', 'noise'])        # the constants of one _AdvanceFn call
+
+
 class _AdvanceFn(torch.autograd.Function):
-    """``PeriodicSolver.evolve`` / ``evolve_velocity`` and the entry points they complete (``advance`` / ``advance_velocity`` and, with
-    ``scalar``, ``advance_scalar`` / ``advance_velocity_scalar``) as one autograd node: forward the step the solver's own ``_launch_steps``
-    picks on a fresh state (linear, stochastic, buoyant, scalar, forced or plain), with the spectra at the start of every step kept (one device
-    copy each between one-step calls: the step itself is untouched); backward the adjoint call (ops.spec_ns_step_linear_adjoint_ on a solver
-    with the general linear operator, else ops.spec_ns_step_adjoint_ / ops.spec_ns_step_scalar_adjoint_) between the compact and expand
-    kernels.  A stochastic step has no adjoint of its own: the kick is additive and independent of the state, the saved start spectra carry
-    it, and the generator is never run in the backward.  ``noise``: None, or (clock, noise_ids) of ``evolve`` for the state the forward
-    steps (ignored without a stochastic force).  ``operator``: None, or the table of ``evolve`` that takes the solver's place: the step is
-    then the linear one, and where the table requires grad the backward is ops.spec_ns_step_operator_adjoint_, the same launches with the
-    table's cotangent summed per grid, which ``_operator_gradient`` turns into the table's gradient.  ``velocity``: the flow's ends are init / fields instead of the vorticity's; theta's are
-    spec_ns_scalar_init / spec_ns_scalar_field.  ``fields``: (w,) or (u0, v0), then with ``scalar`` theta."""
+    """``PeriodicSolver.evolve`` / ``evolve_velocity`` and ``advance*`` as one autograd node.  Inputs: ``run``, the call's constants (a
+    ``_Run``), then what the call is differentiable in: ``forcing`` (or None), ``operator`` (or None) and the ``fields``, (w,) or (u0, v0),
+    then with ``run.scalar`` theta.  Forward: the step the solver's own ``_launch_steps`` takes on a fresh state, with the spectra at the start
+    of every step kept (one device copy each between one-step calls: the step itself is untouched).  Backward: ops.spec_ns_adjoint_ between
+    the compact and expand kernels.  A stochastic step has no adjoint of its own: the kick is additive and independent of the state, the
+    saved start spectra carry it, and the generator is never run in the backward.  ``run.noise``: (clock, noise_ids) of ``evolve`` for the
+    state the forward steps (ignored without a stochastic force).  ``operator``: the table of ``evolve`` that takes the solver's place: the
+    step is then the linear one, and where the table requires grad the adjoint also sums the table's cotangent per grid, which
+    ``_operator_gradient`` turns into the table's gradient.  ``run.velocity``: the flow's ends are init / fields instead of the vorticity's;
+    theta's are spec_ns_scalar_init / spec_ns_scalar_field."""
 
     @staticmethod
-    def forward(ctx, solver, nsteps, mean, velocity, scalar, forcing, noise, operator, *fields):
-        s = solver
+    def forward(ctx, run, forcing, operator, *fields):
+        s, nsteps, mean, velocity, scalar, noise = run
         theta = fields[-1].detach() if scalar else None
         if velocity:
             state = s.init(fields[0].detach(), fields[1].detach(), theta)
@@ -208,7 +212,7 @@ class _AdvanceFn(torch.autograd.Function):
         ghat = s._force_of(state) if forcing is None else s._source_spectrum(forcing.detach(), state)
         what0 = torch.empty((nsteps,) + tuple(state.what.shape), dtype=torch.float32, device=state.what.device)
         that0 = torch.empty_like(what0) if scalar else None
-        if noise is not None and s.stoch_amp is not None:
+        if s.stoch_amp is not None:
             state.clock, state.noise_ids = s._noise_args(noise[0], noise[1], state)
         if operator is None:
             lin = s._linear_of(state) if s._linear() else None
@@ -219,8 +223,7 @@ class _AdvanceFn(torch.autograd.Function):
             if scalar:
                 that0[k].copy_(state.that)
             s._launch_steps(state, 1, ghat, lin)
-        ctx.solver, ctx.velocity, ctx.scalar, ctx.squeeze = s, velocity, scalar, fields[0].dim() == 2
-        ctx.lin = lin
+        ctx.run, ctx.lin, ctx.squeeze = run, lin, fields[0].dim() == 2
         ctx.shared = forcing is not None and forcing.shape[0] == 1 and state.batch > 1
         ctx.force_shape = None if forcing is None else tuple(forcing.shape)
         ctx.save_for_backward(what0, state.mean, *(t for t in (that0, ghat) if t is not None))
@@ -231,52 +234,41 @@ class _AdvanceFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gout):
-        s = ctx.solver
+        s, velocity, scalar = ctx.run.solver, ctx.run.velocity, ctx.run.scalar
+        _, need_g, need_l = ctx.needs_input_grad[:3]                         # of forward's run, forcing, operator
         what0, mean = ctx.saved_tensors[:2]
         rest = list(ctx.saved_tensors[2:])
-        that0 = rest.pop(0) if ctx.scalar else None
+        that0 = rest.pop(0) if scalar else None
         ghat = rest[0] if rest else None
         B, dev = what0.shape[1], what0.device
         shape = (B, s.nx, s.ny)
         gout = [torch.zeros(shape, dtype=torch.float32, device=dev) if g is None else g.reshape(shape).contiguous() for g in gout]
-        zero = torch.zeros((B, 2), dtype=torch.float32, device=dev)
-        workspace = ops.spec_ns_scalar_adjoint_workspace if ctx.scalar else ops.spec_ns_adjoint_workspace
-        work = torch.empty(workspace(B, s.nx, s.ny), dtype=torch.uint8, device=dev)
-        if ctx.velocity:                                  # K^T (ubar, vbar)^ = curl(ubar, vbar)^ / |k|^2
+        work = s._work(ops.spec_ns_scalar_adjoint_workspace if scalar else ops.spec_ns_adjoint_workspace, B, dev)
+        if velocity:                                      # K^T (ubar, vbar)^ = curl(ubar, vbar)^ / |k|^2
             lam = s.init(gout[0], gout[1]).what * s._k2_table(dev, -1)
         else:
             lam = s.init_vorticity(gout[0]).what
-        need_g = ctx.force_shape is not None and ctx.needs_input_grad[5]
         gbar = torch.empty_like(lam) if need_g else None
-        mu = ops.spec_ns_scalar_init(gout[-1], torch.empty_like(lam), work) if ctx.scalar else None
-        lbar = torch.empty_like(lam) if ctx.needs_input_grad[7] else None
-        if lbar is not None:                              # the same launches, the OPERATOR kernels in stages 3-1
-            ops.spec_ns_step_operator_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, s.ny, s.Lx, s.Ly, s.dt,
-                                               s.kappa if ctx.scalar else 0.0, s.scalar_gradient, s.buoyancy, ctx.lin, lbar)
-        elif ctx.lin is not None:
-            ops.spec_ns_step_linear_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, s.ny, s.Lx, s.Ly, s.dt,
-                                             s.kappa if ctx.scalar else 0.0, s.scalar_gradient, s.buoyancy, ctx.lin)
-        elif ctx.scalar:
-            ops.spec_ns_step_scalar_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag, s.kappa,
-                                             s.scalar_gradient, s.buoyancy)
+        mu = ops.spec_ns_scalar_init(gout[-1], torch.empty_like(lam), work) if scalar else None
+        lbar = torch.empty_like(lam) if need_l else None
+        ops.spec_ns_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag, s.kappa if scalar else 0.0,
+                             s.scalar_gradient, s.buoyancy, ctx.lin, lbar)
+        if velocity:                                      # init^T (lam) = (lam_y, -lam_x): the velocity of the streamfunction lam
+            grads = tuple(s.fields(s._at_rest(lam * s._k2_table(dev, 1), work))[:2])
         else:
-            ops.spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, work, s.ny, s.Lx, s.Ly, s.dt, s.nu, s.drag)
-        if ctx.velocity:                                  # init^T (lam) = (lam_y, -lam_x): the velocity of the streamfunction lam
-            grads = tuple(s.fields(PeriodicState(lam * s._k2_table(dev, 1), zero, work))[:2])
-        else:
-            grads = (s.vorticity(PeriodicState(lam, zero, work)),)
-        if ctx.scalar:
+            grads = (s.vorticity(s._at_rest(lam, work)),)
+        if scalar:
             grads = grads + (ops.spec_ns_scalar_field(mu, work, s.ny),)
         if ctx.squeeze:
             grads = tuple(g[0] for g in grads)
         gf = None
         if need_g:
-            gf = s.vorticity(PeriodicState(gbar, zero, work))
+            gf = s.vorticity(s._at_rest(gbar, work))
             if ctx.shared:
                 gf = torch.sum(gf, dim=0, keepdim=True)
             gf = gf.reshape(ctx.force_shape)
         gop = None if lbar is None else s._operator_gradient(lbar)
-        return (None, None, None, None, None, gf, None, gop) + grads
+        return (None, gf, gop) + grads
 
 
 class PeriodicSolver(object):
@@ -373,8 +365,8 @@ class PeriodicSolver(object):
         self.buoyancy = _pair('buoyancy', buoyancy, '(bx, by)')
         if self.buoyancy != (0.0, 0.0) and self.kappa is None:
             raise ValueError("buoyancy = %r needs a solver built with kappa (the diffusivity of the scalar that is buoyant)" % (self.buoyancy,))
-        self.hyperviscosity = self._power_term('hyperviscosity', hyperviscosity, 'nu_h', 'p', 2, 8)
-        self.hypofriction = self._power_term('hypofriction', hypofriction, 'mu', 'q', 1, 4)
+        self.hyperviscosity = self._power_term('hyperviscosity', hyperviscosity, (0.0, 2))
+        self.hypofriction = self._power_term('hypofriction', hypofriction, (0.0, 1))
         self.beta = _real('beta', beta, kind='hold real numbers')
         self.my1 = ops.spec_ns_kept_y(self.ny)
         self._lin = self._linear_table() if self._linear() else None      # (Re, Im)(lambda dt / 2), float32 numpy [my1, nx, 2]
@@ -394,16 +386,30 @@ class PeriodicSolver(object):
     def _lin_dev(self):                        # the linear table's device copies, by device (empty on a solver without the linear form)
         return self._dev['lin']
 
+    def _work(self, query, B, dev, have=None):
+        """A workspace of the size ``query`` (one of ops.spec_ns_*workspace) gives for B of this solver's grids, on dev: ``have`` where that
+        is large enough, else a fresh one."""
+        need = query(B, self.nx, self.ny)
+        return have if have is not None and have.numel() >= need else torch.empty(need, dtype=torch.uint8, device=dev)
+
+    def _at_rest(self, spectrum, work=None):
+        """The state at rest around a spectrum [B, my1, nx, 2]: what ``fields`` and ``vorticity`` need to read it as a field."""
+        B, dev = spectrum.shape[0], spectrum.device
+        return PeriodicState(spectrum, torch.zeros((B, 2), dtype=torch.float32, device=dev),
+                             self._work(ops.spec_ns_workspace, B, dev) if work is None else work)
+
     @staticmethod
-    def _power_term(name, term, coef, power, lo, hi):
-        """(coefficient, exponent) of ``hyperviscosity`` / ``hypofriction``; None: (0.0, lo)."""
+    def _power_term(name, term, own, number=lambda name, c: _real(name, c, '>= 0')):
+        """(coefficient, exponent) of ``hyperviscosity`` / ``hypofriction``; None: ``own``.  number(name, c) checks the coefficient: a real
+        >= 0 at construction, also a 0-dim tensor in ``operator_table``."""
+        coef, power, lo, hi = ('nu_h', 'p', 2, 8) if name == 'hyperviscosity' else ('mu', 'q', 1, 4)
         if term is None:
-            return 0.0, lo
+            return own
         try:
             c, n = term
         except (TypeError, ValueError):
             raise TypeError("%s must be None or (%s, %s), got %r" % (name, coef, power, term))
-        c, n = _real('%s of %s' % (coef, name), c, '>= 0'), _int('%s of %s' % (power, name), n)
+        c, n = number('%s of %s' % (coef, name), c), _int('%s of %s' % (power, name), n)
         if not lo <= n <= hi:
             raise ValueError("%s of %s = %d must be in [%d, %d]" % (power, name, n, lo, hi))
         return c, n
@@ -447,14 +453,12 @@ class PeriodicSolver(object):
             theta = self._field('theta', theta)
             if theta.shape != u.shape:
                 raise ValueError("theta must have the shape of u and v")
-        from ._util import default_device
-        dev = u.device if u.is_cuda else (v.device if v.is_cuda else default_device())
+        dev = u.device if u.is_cuda else (v.device if v.is_cuda else _device())
         u, v = u.to(dev).contiguous(), v.to(dev).contiguous()
         B = u.shape[0]
         what = torch.empty((B, self.my1, self.nx, 2), dtype=torch.float32, device=u.device)
         mean = torch.empty((B, 2), dtype=torch.float32, device=u.device)
-        size = ops.spec_ns_workspace if theta is None else ops.spec_ns_scalar_workspace
-        work = torch.empty(size(B, self.nx, self.ny), dtype=torch.uint8, device=u.device)
+        work = self._work(ops.spec_ns_workspace if theta is None else ops.spec_ns_scalar_workspace, B, u.device)
         ops.spec_ns_init(u, v, what, mean, work, self.Lx, self.Ly)
         that = None if theta is None else ops.spec_ns_scalar_init(theta.to(dev).contiguous(), torch.empty_like(what), work)
         state = PeriodicState(what, mean, work, that)
@@ -494,10 +498,8 @@ class PeriodicSolver(object):
         """(f_sx, f_sy) float32 [Bg, nx, ny]: the part of the force that acts (None without a force)."""
         if self.ghat is None:
             return None
-        Bg = self.ghat.shape[0]
-        zero = torch.zeros((Bg, 2), dtype=torch.float32, device=self.ghat.device)
-        work = torch.empty(ops.spec_ns_workspace(Bg, self.nx, self.ny), dtype=torch.uint8, device=self.ghat.device)
-        return ops.spec_ns_fields(self.ghat, zero, work, self.ny, self.Lx, self.Ly, self.rho)[:2]
+        rest = self._at_rest(self.ghat)
+        return ops.spec_ns_fields(rest.what, rest.mean, rest.work, self.ny, self.Lx, self.Ly, self.rho)[:2]
 
     def _forced(self):
         return self.ghat is not None or self.drag > 0
@@ -649,28 +651,19 @@ class PeriodicSolver(object):
         return state.that is not None and self.buoyancy != (0.0, 0.0)
 
     def _launch_steps(self, state, nsteps, force=False, lin=None):
-        """The step this solver takes on this state.  force: False, the solver's own (``set_forcing``); else the spectrum g^ that takes its place
-        (None: no force), as ``evolve`` passes its ``forcing``.  lin: None, the solver's own table where it has one; else the table that takes
-        its place, as ``evolve`` passes its ``operator``: the step is then the linear one on any solver."""
-        what, that = state.what, state.that
+        """The step this solver takes on this state; ops.spec_ns_advance_ picks the entry.  force: False, the solver's own (``set_forcing``);
+        else the spectrum g^ that takes its place (None: no force), as ``evolve`` passes its ``forcing``.  lin: None, the solver's own table
+        where it has one; else the table that takes its place, as ``evolve`` passes its ``operator``: the step is then the linear one on any
+        solver."""
         ghat = self._force_of(state) if force is False else force
-        box = (ghat, state.work, self.ny, self.Lx, self.Ly, self.dt)                        # what every forced form takes after the mean
-        kappa = 0.0 if self.kappa is None else self.kappa
-        amp, clock, ids = (None, None, None) if self.stoch_amp is None else self._noise_of(state)
-        if lin is not None or self._linear():
-            ops.spec_ns_step_linear_(what, that, state.mean, *box, kappa, self.scalar_gradient, self.buoyancy,
-                                     self._linear_of(state) if lin is None else lin, amp, self.stoch_seed, clock, ids, nsteps)
-        elif self.stoch_amp is not None:
-            ops.spec_ns_step_stochastic_(what, that, state.mean, *box, self.nu, self.drag, kappa, self.scalar_gradient, self.buoyancy, amp,
-                                         self.stoch_seed, clock, ids, nsteps)
-        elif self._buoyant(state):
-            ops.spec_ns_step_buoyant_(what, that, state.mean, *box, self.nu, self.drag, self.kappa, self.scalar_gradient, self.buoyancy, nsteps)
-        elif that is not None:
-            ops.spec_ns_step_scalar_(what, that, state.mean, *box, self.nu, self.drag, self.kappa, self.scalar_gradient, nsteps)
-        elif ghat is not None or self.drag > 0:
-            ops.spec_ns_step_forced_(what, state.mean, *box, self.nu, self.drag, nsteps)
-        else:
-            ops.spec_ns_step_(what, state.mean, *box[1:], self.nu, nsteps)
+        if lin is None and self._linear():
+            lin = self._linear_of(state)
+        noise = None
+        if self.stoch_amp is not None:
+            amp, clock, ids = self._noise_of(state)
+            noise = (amp, self.stoch_seed, clock, ids)
+        ops.spec_ns_advance_(state.what, state.that, state.mean, ghat, state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu, self.drag,
+                             0.0 if self.kappa is None else self.kappa, self.scalar_gradient, self.buoyancy, lin, noise, nsteps)
 
     def step(self, state, nsteps=1):
         """nsteps time steps in place (no allocation, no host synchronisation)."""
@@ -684,6 +677,9 @@ class PeriodicSolver(object):
     def _refuse_unsupported(self, who, scalar=False):
         """``advance*`` cover the forced, damped flow and, through the ``scalar`` entry points, its scalar and buoyancy; name the argument that
         puts a solver outside them and point at ``evolve`` / ``evolve_velocity``, which cover every solver."""
+        if scalar and self.kappa is None:
+            raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use %s"
+                             % (who, who.replace('_scalar', '')))
         for name, on in (('buoyancy', self.buoyancy != (0.0, 0.0) and not scalar), ('kappa', self.kappa is not None and not scalar),
                          ('set_stochastic_forcing', self.stoch_amp is not None), ('hyperviscosity', self.hyperviscosity[0] > 0),
                          ('hypofriction', self.hypofriction[0] > 0), ('beta', self.beta != 0.0)):
@@ -718,11 +714,10 @@ class PeriodicSolver(object):
         """State of the vorticity field w ([B, nx, ny] or [nx, ny], float32) and the mean velocity ``mean`` ([B, 2] or a pair; None: at rest):
         keeps the band-limited part of w and zeroes its (0, 0) mode (a periodic velocity has a zero-mean vorticity)."""
         w = self._field('w', w)
-        from ._util import default_device
-        w = w.to(w.device if w.is_cuda else default_device()).contiguous()
+        w = w.to(w.device if w.is_cuda else _device()).contiguous()
         B, dev = w.shape[0], w.device
         what = torch.empty((B, self.my1, self.nx, 2), dtype=torch.float32, device=dev)
-        work = torch.empty(ops.spec_ns_scalar_workspace(B, self.nx, self.ny), dtype=torch.uint8, device=dev)
+        work = self._work(ops.spec_ns_scalar_workspace, B, dev)
         ops.spec_ns_scalar_init(w, what, work)
         what[:, 0, 0, :] = 0.0
         if mean is None:
@@ -734,23 +729,17 @@ class PeriodicSolver(object):
     def vorticity(self, state, out=None):
         """w float32 [B, nx, ny] of the state (into ``out`` if given)."""
         self._state(state)
-        need = ops.spec_ns_scalar_workspace(state.batch, self.nx, self.ny)
-        work = state.work if state.work.numel() >= need else torch.empty(need, dtype=torch.uint8, device=state.what.device)
+        work = self._work(ops.spec_ns_scalar_workspace, state.batch, state.what.device, have=state.work)
         return ops.spec_ns_scalar_field(state.what, work, self.ny, out)
 
-    def _advance_args(self, who, scalar, nsteps, forcing, *fields, complete=False):
-        """The checked arguments of ``advance`` / ``advance_velocity`` and, with ``scalar``, of ``advance_scalar`` / ``advance_velocity_scalar``:
-        the refusals, then the tensor checks; ``complete``: of ``evolve`` / ``evolve_velocity``, which refuse no solver and take the scalar iff
-        the solver has one.  ``fields``: (name, tensor) pairs."""
-        if complete:
-            if scalar != (self.kappa is not None):
-                raise ValueError("%s: %s" % (who, "the solver has kappa: its scalar (theta) is part of the state and must be given" if not scalar
-                                         else "a scalar (theta) needs a solver built with kappa (the scalar's diffusivity)"))
-        else:
-            if scalar and self.kappa is None:
-                raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use %s"
-                                 % (who, who.replace('_scalar', '')))
-            self._refuse_unsupported(who, scalar)
+    def _evolve(self, who, velocity, fields, nsteps, mean, forcing, clock, noise_ids, operator):
+        """The six differentiable entry points: the checks, then one ``_AdvanceFn``.  ``fields``: (name, tensor) pairs, (w,) or (u0, v0), then
+        theta iff the solver has ``kappa`` (its scalar is part of the state).  Returns the fields after ``nsteps`` steps in that order, a
+        single one bare."""
+        scalar = len(fields) > (2 if velocity else 1)
+        if scalar != (self.kappa is not None):
+            raise ValueError("%s: %s" % (who, "the solver has kappa: its scalar (theta) is part of the state and must be given" if not scalar
+                                     else "a scalar (theta) needs a solver built with kappa (the scalar's diffusivity)"))
         nsteps = _count('nsteps', nsteps, 1)
         fields = [self._grad_field(name, f) for name, f in fields]
         if any(f.shape != fields[0].shape for f in fields[1:]):
@@ -759,52 +748,36 @@ class PeriodicSolver(object):
             forcing = self._grad_field('forcing', forcing)
             if forcing.dim() == 2:
                 forcing = forcing.unsqueeze(0)
-        return nsteps, forcing, fields
+        operator = self._operator_arg(who, operator, fields[0])
+        out = _AdvanceFn.apply(_Run(self, nsteps, mean, velocity, scalar, (clock, noise_ids)), forcing, operator, *fields)
+        return out[0] if len(out) == 1 else out
 
     def advance(self, w, nsteps=1, mean=None, forcing=None):
-        """The vorticity field after ``nsteps`` steps from the vorticity field w (float32 device tensor [B, nx, ny] or [nx, ny]), differentiable:
-        an autograd node whose backward is the adjoint of the Lawson RK4 step as HIP kernels (csrc/pspec_kernels.hip: ps_row_adj_kernel,
-        ps_col_adj_kernel; derivation in DESIGN.md section 4.2), so a closure, a learned forcing or an initial condition can be trained THROUGH
-        the solver.  ``forcing``: a vorticity source g(x), float32 device tensor [B or 1, nx, ny], constant over the call, differentiable too
-        (for a shared one the per-grid gradients are summed, one deterministic torch.sum); None: the force of ``set_forcing``, a constant.
-        ``mean``: the mean velocity ([B, 2] or a pair; None: at rest), a constant of the motion that is not differentiated.  The forward is
-        bitwise ``vorticity(step(init_vorticity(w, mean), nsteps))``.  Memory kept for the backward: the spectrum at the start of every step,
-        nsteps x B x my1 x nx x 8 bytes (my1 = (ny - 1) // 3 + 1: a third of a field per step and grid); the stages inside a step are recomputed.
-        Not for a solver with kappa or buoyancy (``advance_scalar`` / ``advance_velocity_scalar`` take and return the scalar) and not for a
-        stochastic force, hyperviscosity, hypofriction or beta: NotImplementedError; ``evolve`` covers every solver."""
-        nsteps, forcing, (w,) = self._advance_args('advance', False, nsteps, forcing, ('w', w))
-        return _AdvanceFn.apply(self, nsteps, mean, False, False, forcing, None, None, w)[0]
+        """``evolve`` on the solvers it was written for, the steady-forced, damped flow: the vorticity field after ``nsteps`` steps from w,
+        differentiable in w and ``forcing``, bitwise ``evolve``'s outputs and gradients.  Not for a solver with kappa or buoyancy
+        (``advance_scalar`` / ``advance_velocity_scalar`` take and return the scalar) and not for a stochastic force, hyperviscosity,
+        hypofriction or beta: NotImplementedError; ``evolve`` covers every solver.  No ``operator``, ``clock`` or ``noise_ids``."""
+        self._refuse_unsupported('advance')
+        return self._evolve('advance', False, (('w', w),), nsteps, mean, forcing, 0, None, None)
 
     def advance_velocity(self, u0, v0, nsteps=1, forcing=None):
-        """(u, v) after ``nsteps`` steps from the velocity (u0, v0), differentiable like ``advance`` (and in ``forcing``, a vorticity source as
-        there): ``fields(step(init(u0, v0), nsteps))[:2]`` forward; backward through the velocity by K^T (ubar, vbar)^ = curl(ubar, vbar)^ / |k|^2,
-        the step's adjoint, and init^T (lam) = (lam_y, -lam_x), built from the init / fields kernels and one |k|^-2, |k|^2 table multiply each.
-        The grid means (U0, V0) of (u0, v0) are constants of the motion and are not differentiated.  No pressure output.  The refusals of
+        """``advance`` from and to the velocity: (u, v) after ``nsteps`` steps from (u0, v0), as ``evolve_velocity``.  The refusals of
         ``advance``; ``evolve_velocity`` covers every solver."""
-        nsteps, forcing, (u0, v0) = self._advance_args('advance_velocity', False, nsteps, forcing, ('u0', u0), ('v0', v0))
-        return _AdvanceFn.apply(self, nsteps, None, True, False, forcing, None, None, u0, v0)
+        self._refuse_unsupported('advance_velocity')
+        return self._evolve('advance_velocity', True, (('u0', u0), ('v0', v0)), nsteps, None, forcing, 0, None, None)
 
     def advance_scalar(self, w, theta, nsteps=1, mean=None, forcing=None):
-        """(w, theta) after ``nsteps`` steps from the vorticity field w and the scalar theta (float32 device tensors [B, nx, ny] or [nx, ny]) on a
-        solver with ``kappa``, differentiable in w, theta and ``forcing`` like ``advance``: one autograd node whose backward is the adjoint of
-        the scalar step -- of the buoyant one with ``buoyancy`` != 0 -- as HIP kernels (csrc/pspec_kernels.hip: ps_row_adj_kernel and
-        ps_col_adj_kernel in their scalar forms; derivation in DESIGN.md section 4.2), the scalar riding in the launches of the flow's adjoint as it does in
-        the step.  So an initial temperature can be recovered from a late one, a closure trained through a buoyant flow, a vorticity source
-        fitted to scalar observations.  ``forcing`` and ``mean`` as in ``advance``; the scalar has no source.  The forward is bitwise ``step``
-        on ``init_vorticity(w, mean)`` with ``that`` from ``ops.spec_ns_scalar_init(theta)``, read by ``vorticity`` and ``scalar``.  Memory kept
-        for the backward: both spectra at the start of every step, nsteps x B x my1 x nx x 16 bytes.  kappa, the gradient G, b, nu, the drag and
-        the mean flow are constants and are not differentiated.  ValueError on a solver without kappa; not for a stochastic force,
-        hyperviscosity, hypofriction or beta: NotImplementedError (``evolve`` covers every solver)."""
-        nsteps, forcing, (w, theta) = self._advance_args('advance_scalar', True, nsteps, forcing, ('w', w), ('theta', theta))
-        return _AdvanceFn.apply(self, nsteps, mean, False, True, forcing, None, None, w, theta)
+        """``evolve`` with ``theta`` on a solver with ``kappa`` (and ``buoyancy``): (w, theta) after ``nsteps`` steps, differentiable in w,
+        theta and ``forcing``.  ValueError on a solver without kappa; not for a stochastic force, hyperviscosity, hypofriction or beta:
+        NotImplementedError (``evolve`` covers every solver)."""
+        self._refuse_unsupported('advance_scalar', scalar=True)
+        return self._evolve('advance_scalar', False, (('w', w), ('theta', theta)), nsteps, mean, forcing, 0, None, None)
 
     def advance_velocity_scalar(self, u0, v0, theta0, nsteps=1, forcing=None):
-        """(u, v, theta) after ``nsteps`` steps from the velocity (u0, v0) and the scalar theta0, differentiable like ``advance_scalar``:
-        ``fields(step(init(u0, v0, theta0), nsteps))[:2]`` and ``scalar`` of it forward; backward through the velocity's ends as in
-        ``advance_velocity``.  No pressure output.  The refusals of ``advance_scalar``; ``evolve_velocity`` covers every solver."""
-        nsteps, forcing, (u0, v0, theta0) = self._advance_args('advance_velocity_scalar', True, nsteps, forcing, ('u0', u0), ('v0', v0),
-                                                               ('theta0', theta0))
-        return _AdvanceFn.apply(self, nsteps, None, True, True, forcing, None, None, u0, v0, theta0)
+        """``advance_scalar`` from and to the velocity: (u, v, theta) after ``nsteps`` steps, as ``evolve_velocity``.  The refusals of
+        ``advance_scalar``; ``evolve_velocity`` covers every solver."""
+        self._refuse_unsupported('advance_velocity_scalar', scalar=True)
+        return self._evolve('advance_velocity_scalar', True, (('u0', u0), ('v0', v0), ('theta0', theta0)), nsteps, None, forcing, 0, None, None)
 
     # ---- the linear operator as an argument of evolve
     def _operator_arg(self, who, operator, field):
@@ -847,8 +820,7 @@ class PeriodicSolver(object):
         default device): the wavenumbers and |k|^2 as float64, and the bool mask of the modes the step keeps (the 2/3 band without (0, 0)).
         Row j holds ky = 2 pi j / Ly >= 0, column e the kx of numpy.fft.fftfreq; row 0 holds both kx and -kx.  With it an ``operator`` can be
         written as a function of k, e.g. a network of |k| for a learned eddy viscosity: Re = -nu(|k|) k2 dt / 2 on ``kept``, 0 elsewhere."""
-        from ._util import default_device
-        dev = torch.device(default_device() if device is None else device)
+        dev = _device(device)
         S, shell, k2, kept, wt, kx = self._shell_table()
         ky = 2 * np.pi / self.Ly * np.arange(self.my1, dtype=np.float64)[:, None]
         t = lambda a: torch.from_numpy(np.array(np.broadcast_to(a, k2.shape))).to(dev)            # a writable copy
@@ -864,13 +836,12 @@ class PeriodicSolver(object):
         likewise for drag, nu_h, mu and beta, with no kernel beyond the table's.  Computed in float64 on the device in the order of
         ``linear_operator`` / ``_linear_table`` (the angle taken into [-pi, pi] the same way) and cast to float32: with the solver's own
         numbers it is the solver's table.  Signs and finiteness are not checked (that would synchronise with the host)."""
-        from ._util import default_device
-        dev = torch.device(default_device() if device is None else device)
+        dev = _device(device)
         S, shell, k2, kept, wt, kx = self._shell_table()
         k2 = np.where(kept, k2, 1.0)
         f64 = lambda a: torch.from_numpy(np.array(np.broadcast_to(a, k2.shape), dtype=np.float64)).to(dev)      # a writable copy
 
-        def number(name, x, own):
+        def number(name, x, own=None):
             if x is None:
                 return own
             if isinstance(x, torch.Tensor):
@@ -879,21 +850,9 @@ class PeriodicSolver(object):
                 return x.to(device=dev, dtype=torch.float64)
             return _real(name, x, kind='hold real numbers')
 
-        def power(name, term, own, coef, lo, hi):
-            if term is None:
-                return own
-            try:
-                c, n = term
-            except (TypeError, ValueError):
-                raise TypeError("%s must be None or (%s, power), got %r" % (name, coef, term))
-            n = _int('the power of %s' % name, n)
-            if not lo <= n <= hi:
-                raise ValueError("the power of %s = %d must be in [%d, %d]" % (name, n, lo, hi))
-            return number('%s of %s' % (coef, name), c, None), n
-
         nu, drag, beta = number('nu', nu, self.nu), number('drag', drag, self.drag), number('beta', beta, self.beta)
-        (nu_h, p), (mu, q) = power('hyperviscosity', hyperviscosity, self.hyperviscosity, 'nu_h', 2, 8), \
-            power('hypofriction', hypofriction, self.hypofriction, 'mu', 1, 4)
+        nu_h, p = self._power_term('hyperviscosity', hyperviscosity, self.hyperviscosity, number)
+        mu, q = self._power_term('hypofriction', hypofriction, self.hypofriction, number)
         on = lambda c: isinstance(c, torch.Tensor) or c > 0          # linear_operator's own test for a Python number
         k2d, keptd = f64(k2), torch.from_numpy(np.ascontiguousarray(kept)).to(dev)
         with np.errstate(over='ignore', invalid='ignore'):
@@ -928,17 +887,24 @@ class PeriodicSolver(object):
         return clock, ids
 
     def evolve(self, w, nsteps=1, theta=None, mean=None, forcing=None, clock=0, noise_ids=None, operator=None):
-        """``advance`` / ``advance_scalar`` on EVERY solver: the vorticity field after ``nsteps`` steps (with ``theta``, required iff the solver has
-        ``kappa``: the pair (w, theta)), differentiable in w, theta and ``forcing`` through the same autograd node.  The forward takes the step
-        ``step`` takes -- linear (hyperviscosity, hypofriction, beta), stochastic, buoyant, scalar, forced or plain -- and is bitwise ``step`` on
-        the same state; the backward is the adjoint as HIP kernels, with the conjugate Lawson factors conj(E), conj(E^2) read from the forward's
-        table on a solver with the general linear operator.  A stochastic step is differentiated as the deterministic
-        step it contains: the kick is additive and independent of the state, and the saved start spectra carry it.  ``clock``: the index of the
-        first step's noise, an int or an int64 device tensor [1] that is copied, never advanced: a rollout cut into chunks passes n0,
-        n0 + nsteps, ... and reproduces the uncut noise; ``noise_ids`` as on ``PeriodicState`` (None: arange(B)).  Both are ignored without a
-        stochastic force.  ``mean`` and ``forcing`` as in ``advance``; the amplitudes and the seed are constants and are not differentiated, and
-        without ``operator`` nu, drag and the table are too.  On a solver ``advance`` / ``advance_scalar`` accept, outputs and gradients are
-        theirs, bitwise.
+        """The vorticity field after ``nsteps`` steps of ANY solver from the vorticity field w (float32 device tensor [B, nx, ny] or [nx, ny];
+        with ``theta``, required iff the solver has ``kappa``: the pair (w, theta)), differentiable in w, theta and ``forcing``: one autograd
+        node, so a closure, a learned forcing or an initial condition can be trained THROUGH the solver.  The forward takes the step ``step``
+        takes -- linear (hyperviscosity, hypofriction, beta), stochastic, buoyant, scalar, forced or plain -- and is bitwise ``step`` on
+        ``init_vorticity(w, mean)`` (``that`` from ``ops.spec_ns_scalar_init(theta)``), read by ``vorticity`` and ``scalar``; the backward is
+        the adjoint of the Lawson RK4 step as HIP kernels (csrc/pspec_kernels.hip: ps_row_adj_kernel, ps_col_adj_kernel; derivation in
+        DESIGN.md section 4.2), the scalar riding in the flow's launches, with the conjugate Lawson factors conj(E), conj(E^2) read from the
+        forward's table on a solver with the general linear operator.  A stochastic step is differentiated as the deterministic step it
+        contains: the kick is additive and independent of the state, and the saved start spectra carry it.
+        ``forcing``: a vorticity source g(x), float32 device tensor [B or 1, nx, ny], constant over the call, differentiable too (for a shared
+        one the per-grid gradients are summed, one deterministic torch.sum); None: the force of ``set_forcing``, a constant.  The scalar has
+        no source.  ``mean``: the mean velocity ([B, 2] or a pair; None: at rest), a constant of the motion that is not differentiated.
+        ``clock``: the index of the first step's noise, an int or an int64 device tensor [1] that is copied, never advanced: a rollout cut
+        into chunks passes n0, n0 + nsteps, ... and reproduces the uncut noise; ``noise_ids`` as on ``PeriodicState`` (None: arange(B)).  Both
+        are ignored without a stochastic force.  kappa, G, b, the mean flow, the amplitudes and the seed are constants and are not
+        differentiated, and without ``operator`` nu, drag and the table are too.  Memory kept for the backward: the spectrum (with a scalar:
+        both) at the start of every step, nsteps x B x my1 x nx x 8 (16) bytes, my1 = (ny - 1) // 3 + 1: a third of a field per step and
+        grid; the stages inside a step are recomputed.
         ``operator``: None, or a float32 device tensor [my1, nx, 2] = (Re, Im)(lambda_k dt / 2) in the solver's table layout (``mode_table``
         names the modes) that takes the place of the solver's own linear operator in this call -- ``operator_table(nu=..., drag=...)`` builds
         one from physical parameters, a network of |k| a learned one.  The call then takes the LINEAR step with that table, on any solver, and
@@ -946,21 +912,17 @@ class PeriodicSolver(object):
         l(-k) = conj(l(k)) on the ky = 0 line, where both kx and -kx are stored, and should have Re <= 0; neither is checked.  The gradient
         returned obeys the symmetry, is zero off the kept modes and at (0, 0), and the gradients of the fields and of ``forcing`` are bitwise
         those of the call without the table's gradient."""
-        scalar = theta is not None
-        fields = (('w', w), ('theta', theta)) if scalar else (('w', w),)
-        nsteps, forcing, fields = self._advance_args('evolve', scalar, nsteps, forcing, *fields, complete=True)
-        operator = self._operator_arg('evolve', operator, fields[0])
-        out = _AdvanceFn.apply(self, nsteps, mean, False, scalar, forcing, (clock, noise_ids), operator, *fields)
-        return out if scalar else out[0]
+        fields = (('w', w),) if theta is None else (('w', w), ('theta', theta))
+        return self._evolve('evolve', False, fields, nsteps, mean, forcing, clock, noise_ids, operator)
 
     def evolve_velocity(self, u0, v0, nsteps=1, theta0=None, forcing=None, clock=0, noise_ids=None, operator=None):
         """``evolve`` from and to the velocity: (u, v), or with ``theta0`` (required iff the solver has ``kappa``) (u, v, theta), after ``nsteps``
-        steps, with the ends of ``advance_velocity`` / ``advance_velocity_scalar``.  No pressure output.  ``operator`` as in ``evolve``."""
-        scalar = theta0 is not None
-        fields = (('u0', u0), ('v0', v0)) + ((('theta0', theta0),) if scalar else ())
-        nsteps, forcing, fields = self._advance_args('evolve_velocity', scalar, nsteps, forcing, *fields, complete=True)
-        operator = self._operator_arg('evolve_velocity', operator, fields[0])
-        return _AdvanceFn.apply(self, nsteps, None, True, scalar, forcing, (clock, noise_ids), operator, *fields)
+        steps: ``fields(step(init(u0, v0, theta0), nsteps))[:2]`` (and ``scalar`` of it) forward; backward through the velocity by
+        K^T (ubar, vbar)^ = curl(ubar, vbar)^ / |k|^2, the step's adjoint, and init^T (lam) = (lam_y, -lam_x), built from the init / fields
+        kernels and one |k|^-2, |k|^2 table multiply each.  The grid means (U0, V0) of (u0, v0) are constants of the motion and are not
+        differentiated.  No pressure output.  ``forcing``, ``clock``, ``noise_ids`` and ``operator`` as in ``evolve``."""
+        fields = (('u0', u0), ('v0', v0)) if theta0 is None else (('u0', u0), ('v0', v0), ('theta0', theta0))
+        return self._evolve('evolve_velocity', True, fields, nsteps, None, forcing, clock, noise_ids, operator)
 
     def diagnostics(self, state):
         """Diagnostics(energy, enstrophy, power_in), each float64 [B], computed on the device from the state's spectrum:
