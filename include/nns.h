@@ -636,6 +636,29 @@ int nns_spec_ns_step_operator_adjoint_f32(const float* what0, const float* that0
                                           float* mu, float* gbar, void* work, size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly,
                                           double dt, double kappa, double gx, double gy, double bx, double by, const float* lin, int nsteps,
                                           void* stream, float* lbar);
+/* Forward mode of the flow's step (restatement: tests/pspec_tangent_oracle.py): the Jacobian of nsteps steps applied to a perturbation dw^ that
+ * is carried along with the flow, J dw where the adjoint calls give J^T r.  The Lawson RK4 recurrences are linear in (w^, N^), so the tangent
+ * of a step is the same four stages on dw^ with the same factors E and
+ *     dN_i = -M [u dw_x + v dw_y + du w_x + dv w_y]^ + dg^          (u, v, w_x, w_y of the stage state s_i, the means (U0, V0) in u and v;
+ *                                                                    du^ = i ky dw^ / |k|^2, dv^ = -i kx dw^ / |k|^2: no mean flow, no (0, 0) mode)
+ * dw^ rides in the step's launches as the scalar does (G fields 4-7, a second Ph field): still 8 launches per step plus one per call.
+ * what, dwhat: float32 [batch][my1][nx][2], both advanced in place.  what comes out BITWISE as from the forward call the other arguments name --
+ * nns_spec_ns_step_f32 / nns_spec_ns_step_forced_f32 (lin == NULL, amp == NULL; ghat == NULL and drag == 0 take the unforced kernels),
+ * nns_spec_ns_step_linear_f32 (lin: its table; nu and drag are then ignored), their stochastic forms (amp, clock, ids all non-NULL; all NULL:
+ * no noise, seed ignored) -- the advance of clock included; the kick is additive and independent of the state, so the base takes it and dw^
+ * does not.  dghat: the perturbation of the source, float32 [dgbatch][my1][nx][2] with dgbatch = 1 (shared by the batch) or batch, or NULL with
+ * dgbatch = 0; it is added where g^ is, in every stage, also under an unforced base.  The linear operator acts on dw^ through the factors:
+ * drag, hyperviscosity, hypofriction and beta need nothing further.  Linear in (dwhat, dghat) exactly for powers of two; a grid's result does
+ * not depend on its batch neighbours; nsteps steps in one call are bitwise nsteps calls of one step.  Nothing is stored per step.  work:
+ * nns_spec_ns_tangent_workspace bytes (12 compacted fields, >= nns_spec_ns_workspace: it also serves every unscalared nns_spec_ns_* call).  No
+ * allocation, no host synchronisation (capturable).  Not built: the tangent of the scalar and the buoyant step.  Errors, all before any
+ * launch: those of nns_spec_ns_step_linear_f32 (a NULL lin is no error here), plus NNS_ERR_INVALID_ARG for a NULL dwhat and for dgbatch not 0
+ * without dghat, 1 or batch with it, and NNS_ERR_WORKSPACE below nns_spec_ns_tangent_workspace. */
+int nns_spec_ns_tangent_workspace(int batch, int nx, int ny, size_t* bytes);
+int nns_spec_ns_step_tangent_f32(float* what, float* dwhat, const float* mean, const float* ghat, int gbatch, const float* dghat, int dgbatch,
+                                 void* work, size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
+                                 const float* lin, const float* amp, unsigned long long seed, long long* clock, const int* ids, int nsteps,
+                                 void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

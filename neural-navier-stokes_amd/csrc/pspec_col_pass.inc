@@ -1,5 +1,7 @@
 // One field's pass through a column tile of ps_col_kernel (pspec_kernels.hip), which includes this text once per field with TH in scope:
-// TH = false the vorticity (Ph field 0, W / A, G fields 0..3), TH = true the scalar (Ph field 1, theta^ / A_theta, G fields 4 and 5).  Plain
+// TH = false the vorticity (Ph field 0, W / A, G fields 0..3), TH = true the scalar (Ph field 1, theta^ / A_theta, G fields 4 and 5), TG = true
+// (TH = false) the tangent (Ph field 1, dw^ / dA with the vorticity's factors and mask, dg^ where the vorticity adds g^, no kick, no mean
+// flow, its four spectra to G fields 4..7).  Plain
 // text rather than a function or a lambda: the unscalared kernels then compile to the instructions they had before there was a scalar
 // (a lambda's body is optimised on its own before it is inlined, and came out a few instructions and registers different).
 // STOCH (ps_col_kernel's note) is false in every kernel without a PsStoch argument, whose text below is then what it was.
@@ -8,9 +10,9 @@
 // The staged forward transform and the field emit are text of their own (pspec_stage.inc, pspec_field.inc), shared with ps_col_adj_kernel and
 // ps_transfer_kernel; the tile's names (lok, lj, wbase, sok, ...) are those of pspec_col_tile.inc.
 {
-        const float2* ph = TH ? Ph + a.fstride : Ph;
-        float2* Ws = TH ? Th : W;
-        float2* As = TH ? At : A;
+        const float2* ph = TH || TG ? Ph + a.fstride : Ph;
+        float2* Ws = TG ? tg.dW : TH ? Th : W;
+        float2* As = TG ? tg.dA : TH ? At : A;
         cf y[16];
         if constexpr (S == 0) {
 #pragma unroll
@@ -40,8 +42,12 @@
                     em1 = expm1f(x); em2 = expm1f(2.f * x);
                 }
                 cf n = keep ? cf{-z[m].x, -z[m].y} : cf{0.f, 0.f};
-                if constexpr (FORCED && !TH) {
+                if constexpr (FORCED && !TH && !TG) {
                     const float2 g = gok ? fc.g[gbase + e] : make_float2(0.f, 0.f);
+                    if (keep) n = {n.x + g.x, n.y + g.y};
+                }
+                if constexpr (TG) {                     // the source's perturbation, where the vorticity adds g^; the unforced base has none of its own
+                    const float2 g = dgok ? tg.dg[dgbase + e] : make_float2(0.f, 0.f);
                     if (keep) n = {n.x + g.x, n.y + g.y};
                 }
                 const size_t si = wbase + e;
@@ -68,7 +74,7 @@
                     const float2 a2 = lok ? As[si] : make_float2(0.f, 0.f);
                     const cf acc = keep ? cf{a2.x, a2.y} : cf{0.f, 0.f};
                     cf w = axpy(dt6, n, acc);
-                    if constexpr (STOCH && !TH) {       // the kick of the finished step: w += sqrt(dt) a xi, Philox only on the forced ring
+                    if constexpr (STOCH && !TH && !TG) { // the kick of the finished step: w += sqrt(dt) a xi, Philox only on the forced ring
                         const float amp = keep ? samp[(size_t)lj * N + e] : 0.f;
                         if (amp != 0.f) {
                             const bool mirror = lj == 0 && mx < 0;                 // the j = 0 line stores -m_x too: |m_x|'s sample, conjugated
@@ -86,14 +92,15 @@
             }
         }
         if (S < 4 || emit) {
-            const float U0 = !TH && lok ? mean[2 * lb] : 0.f, V0 = !TH && lok ? mean[2 * lb + 1] : 0.f;
+            const float U0 = !TH && !TG && lok ? mean[2 * lb] : 0.f, V0 = !TH && !TG && lok ? mean[2 * lb + 1] : 0.f;
             auto field = [&](auto fc) {
-                constexpr int F = decltype(fc)::value;
+                constexpr int F = decltype(fc)::value, FK = TG ? F - 4 : F;      // the tangent's four spectra go to G fields 4-7
                 int te = tv;
                 asm volatile("" : "+v"(te), "+v"(y[0].x));
 #include "pspec_field.inc"
             };
-            if constexpr (TH) static_for<4, 6>(field);
+            if constexpr (TG) static_for<4, 8>(field);
+            else if constexpr (TH) static_for<4, 6>(field);
             else static_for<0, 4>(field);
         } else {
             __syncthreads();                        // the next staging overwrites line images other waves may still read

@@ -95,6 +95,17 @@
 // driver, workspaces and 16 launches per step; without lbar the call is the linear adjoint's, launch for launch.  Every other kernel keeps
 // its instructions.  Registers and times: profiles/pspec_operator_grad_isa.txt (no scratch), profiles/pspec_operator_grad_run.json.
 //
+// Forward mode (nns_spec_ns_step_tangent_f32; restatement: tests/pspec_tangent_oracle.py): the Jacobian of the step applied to a perturbation dw^
+// that is carried along with the flow.  The Lawson recurrences are linear in (w^, N^), so the tangent step is the same four stages on dw^ with
+// the same factors and dN_i = -M [u dw_x + v dw_y + du w_x + dv w_y]^ + dg^ about stage i's own state: a second field that rides in the step's
+// launches exactly as the scalar does, with the vorticity's factors and mask where the scalar has E_theta and M_theta.  ps_row_tan_kernel<ny>
+// runs four inverse transforms (G fields 0-3 of the base, 4-7 of the perturbation), the base's product with ps_row_kernel's arithmetic and the
+// linearised one, and two forward transforms to Ph fields 0 and 1; a PsTangent first in ps_col_kernel's pack (TANGENT) includes
+// pspec_col_pass.inc once more per tile (TG) for dw^ / dA -- stage 0, the plain and the forced stages 1-4, the LINEAR stages 1-3, the STOCH
+// stages 1 and 4, where the base alone counts the clock and takes the kick.  Still 8 launches per step plus one per call, one driver
+// (spec_ns_step) and one more row of PsLayout (12 compacted fields); the base is bitwise the step without the perturbation, and kernels without
+// the PsTangent keep their names and their code.  Registers and times: profiles/pspec_tangent_isa.txt (no scratch), profiles/pspec_tangent_run.json.
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 //
 // What the row and column kernels share has one copy each: the LDS layout, PsArgs and the row pass's Hermitian fill and kept-mode store in
@@ -136,6 +147,12 @@ struct PsStoch {          // the last argument of the STOCH column kernels (stag
 };
 struct PsLinear {         // the argument of the LINEAR column kernels (stages 1-3 of a linear step), after PsScalar and before PsStoch
     const float2* lin;    // (Re, Im)(lambda dt / 2) [my1][nx], the layout of one grid of W, shared by the batch
+};
+struct PsTangent {        // the first extra argument of the TANGENT column kernels (nns_spec_ns_step_tangent_f32); never with a PsScalar or a PsKeep
+    float2* dW;           // dw^ [B][my1][nx], the layout of W: the tangent spectrum, advanced with the vorticity's own factors and mask
+    float2* dA;           // its Lawson accumulator
+    const float2* dg;     // dg^ [dgbatch][my1][nx], the perturbation of the source, or NULL
+    int dshared;          // 1: one dg^ for every grid; 0: one per grid
 };
 struct PsKeep {           // the last argument of the STAGES column kernels (stages 1-3 of the adjoint's recomputation; no scalar or noise)
     float2* stage;        // [B][my1][nx], the layout of W: receives the next stage's input spectrum (s1, s2 or s3)
@@ -282,6 +299,50 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
     }
 }
 
+// The row pass of the tangent-linear step (nns_spec_ns_step_tangent_f32; restatement: tests/pspec_tangent_oracle.py).  The perturbation dw^
+// rides in the step's launches as the scalar does: G fields 4-7 hold its velocity and gradient (du, dv, dw_x, dw_y: no mean flow), and beside
+// the base's product u w_x + v w_y (Ph field 0: the arithmetic of ps_row_kernel, so the base stays bitwise the step) the row forms the
+// linearised one, u dw_x + v dw_y + du w_x + dv w_y (Ph field 1).  Four inverse and two forward transforms along y.  u + i v and
+// w_x + i w_y stay while one perturbation line at a time passes: du w_x + dv w_y is formed first, as 16 real values that take the place of
+// w_x + i w_y, and the same line then carries grad dw.  Three complex lines are live, as in ps_row_adj_kernel<N, true>.
+template <int N>
+__global__ __launch_bounds__(kT) void ps_row_tan_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a) {
+    using L = PsLds<N>;
+    constexpr int TPF = L::TPF;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const cf* tab = ps_tables<N>(smem);
+    unsigned char* lines = smem + L::TAB_BYTES;
+    const int my1 = a.my1;
+    const long niter = (a.nlines + L::LINES - 1) / L::LINES;
+    for (long it = blockIdx.x; it < niter; it += gridDim.x) {
+#include "pspec_row_line.inc"
+        cf zu[16], zw[16], zd[16];
+        ps_row_load2<N>(g0, g0 + a.fstride, tid, my1, zu);                           // u + i v: stays
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 2 * a.fstride, g0 + 3 * a.fstride, tid, my1, zw);       // w_x + i w_y: stays
+        fft_line<float, N, true>(zw, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zd[m] = {zu[m].x * zw[m].x + zu[m].y * zw[m].y, 0.f};        // u w_x + v w_y
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tid);
+        ps_row_store<N>(zd, Ph + (size_t)row * my1, tid, my1, valid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 4 * a.fstride, g0 + 5 * a.fstride, tid, my1, zd);       // du + i dv
+        fft_line<float, N, true>(zd, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zw[m].x = zd[m].x * zw[m].x + zd[m].y * zw[m].y;             // du w_x + dv w_y: w_x, w_y leave
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 6 * a.fstride, g0 + 7 * a.fstride, tid, my1, zd);       // dw_x + i dw_y
+        fft_line<float, N, true>(zd, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zd[m] = {fmaf(zu[m].x, zd[m].x, fmaf(zu[m].y, zd[m].y, zw[m].x)), 0.f};   // + u dw_x + v dw_y
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tid);
+        ps_row_store<N>(zd, Ph + a.fstride + (size_t)row * my1, tid, my1, valid);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- column pass (axis x)
 // S = 0: prepare stage 1 from W; S = 1..4: consume the RK stage's N (from Ph) and update W / A, then (S < 4 or emit) prepare the next stage.
 // FORCED (S >= 1): N^ += g^ on the kept modes (lane-owned, coalesced, like W / A) and L dt / 2 = hnudt |k|^2 - alpha dt / 2.
@@ -293,6 +354,10 @@ __global__ __launch_bounds__(kT) void ps_row_kernel(const float2* __restrict__ G
 // STAGES (a PsKeep ends the pack, after the PsLinear of a linear step; S = 1..3): the next stage's input spectrum is also stored, lane-owned and coalesced like W / A, for the
 // adjoint (ps_col_adj_kernel) to linearise about; the arithmetic is untouched, so the recomputed stages are the forward's bits.  With a scalar
 // the pack ends in a PsKeepScalar after the PsScalar, and theta^'s next stage input is stored as well (ps_col_adj_kernel with a PsAdjScalar).
+// TANGENT (a PsTangent first in the pack, where a PsScalar would be; never with one or with a PsKeep): after the vorticity's work on a tile the
+// same text runs once more on the perturbation dw^: Ph's second field, dw^ / dA with the VORTICITY's factors (hdrag and the LINEAR complex ones
+// included) and mask, dg^ where the vorticity adds g^ (also under an unforced base, whose own arithmetic stays the unforced kernel's), no kick
+// and no step count of its own, then its velocity and gradient as G fields 4-7 with zero means.  The vorticity's arithmetic is untouched.
 template <int N, int S, bool FORCED = false, bool SCALAR = false, typename... Sc>
 __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, float2* __restrict__ W,
                                                     float2* __restrict__ A, const float* __restrict__ mean, PsArgs a, int emit,
@@ -300,10 +365,12 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     static_assert(!FORCED || S >= 1, "stage 0 only prepares: it has no forced form");
     constexpr bool STOCH = (std::is_same_v<Sc, PsStoch> || ... || false);
     constexpr bool LINEAR = (std::is_same_v<Sc, PsLinear> || ... || false);
+    constexpr bool TANGENT = (std::is_same_v<Sc, PsTangent> || ... || false);
     constexpr bool KEEP_W = (std::is_same_v<Sc, PsKeep> || ... || false), KEEP_WT = (std::is_same_v<Sc, PsKeepScalar> || ... || false);
     constexpr bool STAGES = KEEP_W || KEEP_WT;
-    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0) + (STAGES ? 1 : 0),
-                  "PsScalar is the SCALAR kernel's argument, PsLinear after it the LINEAR kernel's, PsStoch or the PsKeep last");
+    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (TANGENT ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0) + (STAGES ? 1 : 0),
+                  "PsScalar is the SCALAR kernel's argument (PsTangent the TANGENT kernel's), PsLinear after it the LINEAR kernel's, PsStoch or the PsKeep last");
+    static_assert(!TANGENT || (!SCALAR && !STAGES), "the tangent of the scalar system is not built, and the adjoint's recomputation carries no tangent");
     static_assert(!STAGES || (S >= 1 && S <= 3 && KEEP_WT == SCALAR && !STOCH),
                   "the stage store is that of stages 1-3 of the steady and the linear forms: a PsKeep without a scalar, a PsKeepScalar with one");
     static_assert(!LINEAR || (FORCED && S >= 1 && S <= 3), "the complex factors are those of stages 1-3 of the forced form");
@@ -339,6 +406,8 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     }
     [[maybe_unused]] const float2* lin = nullptr;
     if constexpr (LINEAR) lin = pick<PsLinear>(sc...).lin;
+    [[maybe_unused]] PsTangent tg{};
+    if constexpr (TANGENT) tg = pick<PsTangent>(sc...);
     [[maybe_unused]] float2* stage_out = nullptr;
     [[maybe_unused]] float2* tstage_out = nullptr;
     if constexpr (KEEP_W) stage_out = pick<PsKeep>(sc...).stage;
@@ -361,13 +430,23 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
         int tv = tid;
         asm volatile("" : "+v"(tv));
         const float ky = a.ky1 * (float)lj;
-        // one field through the tile, as plain text per field (the note in pspec_col_pass.inc): first the vorticity, then the scalar
+        [[maybe_unused]] size_t dgbase = 0;
+        [[maybe_unused]] bool dgok = false;
+        if constexpr (TANGENT) {
+            dgbase = tg.dshared ? (size_t)lj * N : wbase;
+            dgok = lok && tg.dg != nullptr;
+        }
+        // one field through the tile, as plain text per field (the note in pspec_col_pass.inc): first the vorticity, then the scalar or the tangent
         {
-            constexpr bool TH = false;
+            constexpr bool TH = false, TG = false;
 #include "pspec_col_pass.inc"
         }
         if constexpr (SCALAR) {
-            constexpr bool TH = true;
+            constexpr bool TH = true, TG = false;
+#include "pspec_col_pass.inc"
+        }
+        if constexpr (TANGENT) {
+            constexpr bool TH = false, TG = true;
 #include "pspec_col_pass.inc"
         }
     }
@@ -525,7 +604,7 @@ __global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict
         [[maybe_unused]] const float U0 = S >= 1 && lok ? mean[2 * lb] : 0.f, V0 = S >= 1 && lok ? mean[2 * lb + 1] : 0.f;
         // field F of the spectrum y, transformed along x and written to G through the LDS transpose: ps_col_kernel's, without its pin of y
         [[maybe_unused]] auto field = [&](auto fc, const cf (&y)[16]) {
-            constexpr int F = decltype(fc)::value;
+            constexpr int F = decltype(fc)::value, FK = F;
             int te = tv;
             asm volatile("" : "+v"(te));
 #include "pspec_field.inc"
@@ -987,18 +1066,28 @@ int launch_row(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s, Gr..
     return check_launch(BU ? "spec_ns buoyant row pass" : SC ? "spec_ns scalar row pass" : "spec_ns row pass");
 }
 
-// The column kernel of stage S whose argument pack ends in x...: a PsScalar (the SCALAR kernels), a PsLinear, a PsStoch, in that order, each or
+template <int N>
+int launch_row_tan(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s) {
+    constexpr auto kern = ps_row_tan_kernel<N>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a);
+    return check_launch("spec_ns tangent row pass");
+}
+
+// The column kernel of stage S whose argument pack ends in x...: a PsScalar (the SCALAR kernels) or a PsTangent, a PsLinear, a PsStoch, in that order, each or
 // none.  fc is read only by the FORCED kernels.
 template <int N, int S, bool FORCED, typename... X>
 int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
                hipStream_t s, X... x) {
     constexpr bool SC = has<PsScalar, X...>, LI = has<PsLinear, X...>, ST = has<PsStoch, X...>, KE = has<PsKeep, X...> || has<PsKeepScalar, X...>;
+    constexpr bool TA = has<PsTangent, X...>;
     constexpr auto kern = ps_col_kernel<N, S, FORCED, SC, X...>;
     std::conditional_t<FORCED, PsForce, PsNoForce> f{};
     if constexpr (FORCED) f = *fc;
     if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
     hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, f, x...);
-    return check_launch(KE       ? "spec_ns stage-keeping column pass"
+    return check_launch(TA       ? "spec_ns tangent column pass"
+                        : KE     ? "spec_ns stage-keeping column pass"
                         : LI     ? (SC ? "spec_ns linear scalar column pass" : "spec_ns linear column pass")
                         : ST     ? (SC ? "spec_ns stochastic scalar column pass" : "spec_ns stochastic column pass")
                         : SC     ? "spec_ns scalar column pass"
@@ -1015,10 +1104,11 @@ int with_stage(int S, F&& f) {
 
 // The one place where a stage's run-time facts become a kernel.  fc == nullptr: the unforced kernels (stage 0 has no other form); sc: the
 // SCALAR ones; li (with fc): a linear step, whose stages 1-3 are the LINEAR kernels (stage 4 applies no factor); st (with fc): a stochastic
-// step, whose stages 1 and 4 are the STOCH kernels.  The pack grows in the kernel's order, and a form no step has is never named.
+// step, whose stages 1 and 4 are the STOCH kernels; tg (never with sc): the TANGENT ones, of every stage and form.  The pack grows in the
+// kernel's order, and a form no step has is never named.
 template <int N>
 int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
-                     const PsScalar* sc, hipStream_t s, const PsStoch* st = nullptr, const PsLinear* li = nullptr) {
+                     const PsScalar* sc, hipStream_t s, const PsStoch* st = nullptr, const PsLinear* li = nullptr, const PsTangent* tg = nullptr) {
     auto stage = [&](auto stage_c) {
         constexpr int K = decltype(stage_c)::value;
         auto stoch = [&](auto forced, auto... x) {
@@ -1032,7 +1122,7 @@ int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, c
                 if (li) return stoch(forced, x..., *li);
             return stoch(forced, x...);
         };
-        auto scalar = [&](auto forced) { return sc ? linear(forced, *sc) : linear(forced); };
+        auto scalar = [&](auto forced) { return tg ? linear(forced, *tg) : sc ? linear(forced, *sc) : linear(forced); };
         if constexpr (K >= 1)
             if (fc) return scalar(std::true_type{});
         return scalar(std::false_type{});
@@ -1102,11 +1192,12 @@ size_t scalar_work_bytes(int batch, int nx, int ny) {
 //   the flow's adjoint:  A, wbar in A_theta's place, G[6], Ph[2] (the recomputation's launches use the first 4 and 1 of them), s1, s2, s3: 13
 //   the scalar adjoint:  A, A_theta (wbar and thetabar once the stages are recomputed), G[10], Ph[3] (the recomputation's: 6 and 2), s1, s2, s3
 //                        of w^, then of theta^: 21
+//   the tangent step:    A, dA in A_theta's place, G[8], Ph[2]: 12
 struct PsLayout {
     int acc, g, ph, keep;
     constexpr int fields() const { return acc + g + ph + keep; }
 };
-constexpr PsLayout kLayFlow{1, 4, 1, 0}, kLayScalar{2, 6, 2, 0}, kLayAdjoint{2, 6, 2, 3}, kLayScalarAdjoint{2, 10, 3, 6};
+constexpr PsLayout kLayFlow{1, 4, 1, 0}, kLayScalar{2, 6, 2, 0}, kLayAdjoint{2, 6, 2, 3}, kLayScalarAdjoint{2, 10, 3, 6}, kLayTangent{2, 8, 2, 0};
 
 size_t layout_work_bytes(const PsLayout& lay, int batch, int nx, int ny) {
     const size_t b = work_bytes(batch, nx, ny), st = (size_t)lay.fields() * batch * nx * kept_y(ny) * sizeof(float2);
@@ -1114,6 +1205,7 @@ size_t layout_work_bytes(const PsLayout& lay, int batch, int nx, int ny) {
 }
 size_t adjoint_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayAdjoint, batch, nx, ny); }
 size_t scalar_adjoint_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayScalarAdjoint, batch, nx, ny); }
+size_t tangent_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayTangent, batch, nx, ny); }
 
 // The fields of a layout in work, and the arguments of the column pass (col) and of the row pass (row).
 struct PsWork {
@@ -1153,16 +1245,18 @@ int check_box(const char* what, int nx, int ny, double Lx, double Ly) {
     return check_axes(what, nx, ny);
 }
 
-enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2, kWorkScalarAdjoint = 3 };      // a bool converts: false the flow's workspace, true the scalar's
+enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2, kWorkScalarAdjoint = 3, kWorkTangent = 4 };      // a bool converts: false the flow's workspace, true the scalar's
 
 int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int kind) {
-    const size_t need = kind == kWorkScalarAdjoint ? scalar_adjoint_work_bytes(batch, nx, ny)
+    const size_t need = kind == kWorkTangent       ? tangent_work_bytes(batch, nx, ny)
+                        : kind == kWorkScalarAdjoint ? scalar_adjoint_work_bytes(batch, nx, ny)
                         : kind == kWorkAdjoint     ? adjoint_work_bytes(batch, nx, ny)
                         : kind == kWorkScalar      ? scalar_work_bytes(batch, nx, ny)
                                                    : work_bytes(batch, nx, ny);
     if (wbytes < need)
         return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", what, wbytes, need,
-                    kind == kWorkScalarAdjoint ? "nns_spec_ns_scalar_adjoint_workspace"
+                    kind == kWorkTangent       ? "nns_spec_ns_tangent_workspace"
+                    : kind == kWorkScalarAdjoint ? "nns_spec_ns_scalar_adjoint_workspace"
                     : kind == kWorkAdjoint     ? "nns_spec_ns_adjoint_workspace"
                     : kind == kWorkScalar      ? "nns_spec_ns_scalar_workspace"
                                                : "nns_spec_ns_workspace");
@@ -1351,20 +1445,27 @@ NNS_API int nns_spec_ns_init_f32(const float* u, const float* v, float* what, fl
 // The step of every entry point: ghat == NULL and drag == 0 launch the unforced kernels, that == NULL the unscalared ones, b == 0 the passive ones;
 // st != NULL (amp, key, clock, ids; its sqdt is set here) takes the forced path, with or without ghat and drag, and kicks after every step;
 // lin != NULL takes the forced path too, with the table's factors in stages 1-3 (nu and drag are then unused: the table holds them).
+// dwhat != NULL (never with that): the tangent-linear step, the same launches in their TANGENT forms on the tangent layout of work; the choice
+// of the base's kernels is the one made without dwhat, so what comes out bitwise as from that call.
 static int spec_ns_step(const char* who, float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work,
                         size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa,
                         double gx, double gy, double bx, double by, int nsteps, void* stream, const PsStoch* st = nullptr,
-                        const float* lin = nullptr) {
+                        const float* lin = nullptr, float* dwhat = nullptr, const float* dghat = nullptr, int dgbatch = 0) {
     if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
+    if (dwhat && that) return fail(NNS_ERR_UNSUPPORTED, "%s: the tangent of the scalar system is not built", who);
     if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
     if (int rc = check_scalar_numbers(who, kappa, gx, gy)) return rc;
     if (int rc = check_buoyancy(who, bx, by)) return rc;
     if (int rc = check_gbatch(who, ghat, gbatch, batch)) return rc;
-    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, that != nullptr)) return rc;
+    if (dghat ? (dgbatch != 1 && dgbatch != batch) : dgbatch != 0)
+        return fail(NNS_ERR_INVALID_ARG, "%s: dgbatch = %d must be 0 without dghat, 1 or batch = %d with it", who, dgbatch, batch);
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, dwhat ? kWorkTangent : that ? kWorkScalar : kWorkFlow)) return rc;
     if (nsteps == 0) return NNS_OK;
     hipStream_t s = as_stream(stream);
     float2* W = reinterpret_cast<float2*>(what);
-    const PsWork L(work, batch, nx, ny, that != nullptr, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);
+    const PsWork L(work, batch, nx, ny, dwhat ? kLayTangent : that ? kLayScalar : kLayFlow, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);
+    const PsTangent tangent{reinterpret_cast<float2*>(dwhat), L.At, reinterpret_cast<const float2*>(dghat), dgbatch == 1 && batch > 1 ? 1 : 0};
+    const PsTangent* tg = dwhat ? &tangent : nullptr;
     const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
     const PsForce* fc = ghat || drag > 0 || st || lin ? &force : nullptr;
     const PsLinear linear{reinterpret_cast<const float2*>(lin)};
@@ -1381,11 +1482,12 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
     const PsBuoyGrad buoy{(float)gx, (float)gy, (float)(-(double)ny * by), (float)((double)ny * bx)};
     const PsBuoyGrad* bu = that && (bx != 0.0 || by != 0.0) ? &buoy : nullptr;
     auto col = [&](int S, int emit) {
-        return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, emit, fc, sc, s, stc, li); });
+        return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, emit, fc, sc, s, stc, li, tg); });
     };
     auto row = [&]() {
         return dispatch_pow2(ny, "spec_ns", [&](auto n) {
             constexpr int N = decltype(n)::value;
+            if (tg) return launch_row_tan<N>(L.G, L.Ph, L.row, s);
             return bu ? launch_row<N>(L.G, L.Ph, L.row, s, *bu) : that ? launch_row<N>(L.G, L.Ph, L.row, s, grad) : launch_row<N>(L.G, L.Ph, L.row, s);
         });
     };
@@ -1450,6 +1552,26 @@ NNS_API int nns_spec_ns_step_linear_f32(float* what, float* that, const float* m
     return spec_ns_step("spec_ns_step_linear", what, that, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, 0.0, 0.0,
                         that ? kappa : 0.0, that ? gx : 0.0, that ? gy : 0.0, that ? bx : 0.0, that ? by : 0.0, nsteps, stream,
                         noise ? &st : nullptr, lin);
+}
+
+NNS_API int nns_spec_ns_tangent_workspace(int batch, int nx, int ny, size_t* bytes) {
+    if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_tangent_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
+    if (int rc = check_axes("spec_ns_tangent_workspace", nx, ny)) return rc;
+    *bytes = tangent_work_bytes(batch, nx, ny);
+    return NNS_OK;
+}
+
+NNS_API int nns_spec_ns_step_tangent_f32(float* what, float* dwhat, const float* mean, const float* ghat, int gbatch, const float* dghat,
+                                         int dgbatch, void* work, size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt,
+                                         double nu, double drag, const float* lin, const float* amp, unsigned long long seed, long long* clock,
+                                         const int* ids, int nsteps, void* stream) {
+    if (!dwhat) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_tangent: dwhat must be non-NULL");
+    const bool noise = amp && clock && ids;
+    if (!noise && (amp || clock || ids))
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_tangent: amp, clock and ids must be all NULL (no noise) or all non-NULL");
+    const PsStoch st{amp, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), clock, ids, 0.f};
+    return spec_ns_step("spec_ns_step_tangent", what, nullptr, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, lin ? 0.0 : nu,
+                        lin ? 0.0 : drag, 0.0, 0.0, 0.0, 0.0, 0.0, nsteps, stream, noise ? &st : nullptr, lin, dwhat, dghat, dgbatch);
 }
 
 NNS_API int nns_spec_ns_adjoint_workspace(int batch, int nx, int ny, size_t* bytes) {

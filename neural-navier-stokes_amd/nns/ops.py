@@ -1222,6 +1222,32 @@ def spec_ns_advance_(what, that, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, kap
     return spec_ns_step_(what, mean, *box, nu, nsteps)
 
 
+# forward mode of the periodic solver's step (nns_spec_ns_step_tangent_f32)
+def spec_ns_tangent_workspace(B, nx, ny):
+    """Bytes of the workspace spec_ns_step_tangent_ needs for B grids of nx x ny (>= spec_ns_workspace)."""
+    return _query_bytes('nns_spec_ns_tangent_workspace', int(B), int(nx), int(ny))
+
+
+def spec_ns_step_tangent_(what, dwhat, mean, ghat, dghat, work, ny, Lx, Ly, dt, nu, drag, lin=None, noise=None, nsteps=1):
+    """nsteps steps of the flow and of a perturbation dwhat carried along with it, both in place: what bitwise as by spec_ns_advance_ with the
+    same ghat, nu, drag, lin and noise = (amp, seed, clock, ids) (no scalar), dwhat <- J dwhat + (the response to) dghat, the Jacobian of
+    those steps.  dwhat: float32 like what; dghat: the source's perturbation, float32 [1 or B, my1, nx, 2] or None; lin None: no table.
+    work: spec_ns_tangent_workspace bytes.  8 launches per step and one per call, no allocation, no host synchronisation: capturable."""
+    who = 'spec_ns_step_tangent'
+    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
+    _spec_ns_same(who, dwhat, what, 'dwhat')
+    gbatch, dgbatch = _spec_ns_force(who, ghat, what), _spec_ns_force(who, dghat, what)
+    if lin is not None:
+        _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), what.device)
+    amp, seed, clock, ids = noise or (None, 0, None, None)
+    if noise is not None:
+        _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
+    check(_lib.lib().nns_spec_ns_step_tangent_f32(_p(what), _p(dwhat), _p(mean), _pn(ghat), gbatch, _pn(dghat), dgbatch, _p(work), work.numel(),
+                                                  B, nx, int(ny), float(Lx), float(Ly), float(dt), float(nu), float(drag), _pn(lin), _pn(amp),
+                                                  int(seed), _pn(clock), _pn(ids), int(nsteps), _stream()), 'nns_spec_ns_step_tangent_f32')
+    return what, dwhat
+
+
 def spec_ns_linear_spectrum(what, rate, ny, Lx, Ly, out=None):
     """float64 [B, 2, nshell]: (D_E, D_Z) per shell, the rates at which the linear term changes energy and enstrophy; rate = Re(lambda)
     float64 [my1, nx] on the state's device."""

@@ -27,6 +27,7 @@ float64 by an oracle under tests/:
   * reverse mode, ``advance*`` (flow; scalar and buoyancy)       pspec_adjoint_oracle.py, pspec_scalar_adjoint_oracle.py
   * reverse mode on every solver, ``evolve`` / ``evolve_velocity``   pspec_linear_adjoint_oracle.py
   * their ``operator``: gradients in nu, drag, nu_h, mu, beta, lambda(k)   pspec_operator_grad_oracle.py
+  * forward mode, ``step_tangent`` / ``evolve_tangent`` / ``lyapunov_exponent``   pspec_tangent_oracle.py
 Which C entry a step or an adjoint takes is decided in one place each, ops.spec_ns_advance_ and ops.spec_ns_adjoint_.
 """
 import collections
@@ -345,6 +346,18 @@ class PeriodicSolver(object):
     amplitudes, the seed, the mean flow and per-grid operators stay constants; ``advance*`` do not take the argument.  ``advance``,
     ``advance_velocity``, ``advance_scalar`` and ``advance_velocity_scalar`` are the same node on the solvers they were written for (the
     steady-forced flow; with ``kappa``, its scalar and buoyancy) and refuse the others.
+
+    Forward mode: ``step_tangent(state, dwhat, nsteps, dforcing=)`` advances the state exactly as ``step`` does -- bitwise, on the plain,
+    forced, linear and stochastic solvers -- and with it a perturbation spectrum dwhat, which comes out as J dwhat, J the Jacobian of those
+    steps: where the reverse mode gives J^T r, this gives J d, and sum(J d . r) = sum(d . J^T r) ties the two sets of kernels together at
+    float32 round-off.  The Lawson RK4 recurrences are linear in (w^, N^), so the tangent step is the same four stages on d with the same
+    factors E (drag, hyperviscosity, hypofriction and beta act through them) and dN_i = -M [u d_x + v d_y + du w_x + dv w_y]^ + dg^, u, v,
+    w_x, w_y those of stage i's own state.  The perturbation rides in the step's launches as the scalar does (still 8 per step,
+    capturable), has no mean flow and no (0, 0) mode, and gets no kick: the noise is a constant of the call.  Nothing is stored per step
+    (the adjoint keeps a spectrum per step).  ``evolve_tangent`` / ``evolve_velocity_tangent`` are the field-level forms, ``evolve``'s
+    forward bitwise; ``lyapunov_exponent`` the leading finite-time exponent in the energy norm.  Not built: the tangent of the scalar and
+    the Boussinesq system (a state that carries a scalar is refused), the tangent in ``operator``, several tangents sharing one base, a
+    ``jvp`` hook on the autograd node for ``torch.autograd.forward_ad``, and reverse mode through the tangent (Hessian-vector products).
 
     By wavenumber: the stored modes are binned into shells of width dk = min(2 pi / Lx, 2 pi / Ly) centred on k_s = s dk (``shells()``; an
     elongated box has many).  ``spectrum(state)`` gives energy E(s), enstrophy Z(s), the force's injection F(s) and the scalar's variance V(s),
@@ -672,6 +685,122 @@ class PeriodicSolver(object):
         self._launch_steps(state, nsteps)
         state.steps += nsteps
         return state
+
+    # ---- forward mode
+    def _tangent_spectrum(self, who, dwhat, state):
+        """The checked tangent spectrum of ``who`` for this state; refuses a state that carries a scalar."""
+        self._state(state)
+        if state.that is not None:
+            raise NotImplementedError("%s: the tangent of the scalar system is not built yet: the state carries a scalar (passive or buoyant); "
+                                      "a state without one is stepped as by step" % who)
+        if not isinstance(dwhat, torch.Tensor):
+            raise TypeError("%s: dwhat must be a torch tensor, got %s" % (who, type(dwhat).__name__))
+        if dwhat.dtype != torch.float32 or tuple(dwhat.shape) != tuple(state.what.shape) or dwhat.device != state.what.device \
+                or not dwhat.is_contiguous():
+            raise ValueError("%s: dwhat must be a contiguous float32 %s tensor on the state's device (init_vorticity(dw).what), got %s %s on %s"
+                             % (who, list(state.what.shape), dwhat.dtype, tuple(dwhat.shape), dwhat.device))
+        return dwhat
+
+    def _launch_tangent(self, state, dwhat, nsteps, dghat, force=False):
+        """``_launch_steps`` with the perturbation dwhat riding along: the same choice of force, table and noise, so the base is that step."""
+        ghat = self._force_of(state) if force is False else force
+        lin = self._linear_of(state) if self._linear() else None
+        noise = None
+        if self.stoch_amp is not None:
+            amp, clock, ids = self._noise_of(state)
+            noise = (amp, self.stoch_seed, clock, ids)
+        state.work = self._work(ops.spec_ns_tangent_workspace, state.batch, state.what.device, have=state.work)
+        ops.spec_ns_step_tangent_(state.what, dwhat, state.mean, ghat, dghat, state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu, self.drag,
+                                  lin, noise, nsteps)
+
+    def _dforcing(self, who, dforcing, state):
+        """dg^ of the source perturbation ``dforcing`` ([B or 1, nx, ny] or [nx, ny]; None passes) for this state."""
+        if dforcing is None:
+            return None
+        g = self._field('dforcing', dforcing.detach() if isinstance(dforcing, torch.Tensor) else dforcing)
+        return self._source_spectrum(g.to(state.what.device), state)
+
+    def step_tangent(self, state, dwhat, nsteps=1, dforcing=None):
+        """``step(state, nsteps)`` -- bitwise, ``state.steps`` and ``state.clock`` included -- with the tangent spectrum ``dwhat`` (float32
+        [B, my1, nx, 2], the layout of ``state.what``) advanced in place by the Jacobian of those steps and returned: the perturbation is
+        carried along with the flow, each RK stage linearised about that stage's own state (the class note, "Forward mode").  Build ``dwhat``
+        with ``init_vorticity(dw).what`` (or ``init(du, dv).what`` for a velocity perturbation) and read it with ``vorticity`` / ``fields`` of
+        ``_at_rest(dwhat)``.  ``dforcing``: a perturbation of the vorticity source, float32 [B, nx, ny] or [1, nx, ny] (shared), constant over
+        the call; its band-limited, zero-mean part acts.  Grows ``state.work`` to the tangent workspace on first use (take one step outside
+        before capturing one in a graph); otherwise no allocation without ``dforcing`` and no host synchronisation.  A state that carries a
+        scalar is refused: NotImplementedError."""
+        self._tangent_spectrum('step_tangent', dwhat, state)
+        nsteps = _count('nsteps', nsteps, 0)
+        self._launch_tangent(state, dwhat, nsteps, self._dforcing('step_tangent', dforcing, state))
+        state.steps += nsteps
+        return dwhat
+
+    def _evolve_tangent(self, who, state, dstate, nsteps, forcing, dforcing, clock, noise_ids):
+        nsteps = _count('nsteps', nsteps, 1)
+        if state.what.shape != dstate.what.shape:
+            raise ValueError("%s: the fields and their perturbations must share their shape" % who)
+        if forcing is None:
+            ghat = self._force_of(state)
+        else:
+            ghat = self._source_spectrum(self._field('forcing', forcing.detach() if isinstance(forcing, torch.Tensor) else forcing)
+                                         .to(state.what.device), state)
+        if self.stoch_amp is not None:
+            state.clock, state.noise_ids = self._noise_args(clock, noise_ids, state)
+        self._launch_tangent(state, dstate.what, nsteps, self._dforcing(who, dforcing, state), ghat)
+        state.steps += nsteps
+        return state, self._at_rest(dstate.what, state.work)
+
+    def evolve_tangent(self, w, dw, nsteps=1, mean=None, forcing=None, dforcing=None, clock=0, noise_ids=None):
+        """(w_out, dw_out): the vorticity field after ``nsteps`` steps from w, bitwise ``evolve``'s forward, and the perturbation dw carried
+        along with it, dw_out = J dw (+ the response to ``dforcing``), J the Jacobian of those steps -- the forward-mode twin of ``evolve``,
+        whose backward gives J^T r: sum(dw_out * r) = sum(w.grad * dw) + sum(forcing.grad * dforcing) to float32 rounding.  w, dw: float32
+        [B, nx, ny] or [nx, ny]; ``mean``, ``forcing`` (None: the force of ``set_forcing``, a constant), ``clock`` and ``noise_ids`` as in
+        ``evolve``; ``dforcing``: the perturbation of the source, [B or 1, nx, ny].  The noise of a stochastic solver is a constant of the
+        call: the base takes the kicks, the perturbation none.  NOT an autograd node: the inputs are detached and nothing is recorded.
+        Nothing is stored per step.  No ``theta`` and no ``operator``."""
+        squeeze = isinstance(w, (torch.Tensor, np.ndarray)) and w.ndim == 2
+        state = self.init_vorticity(w.detach() if isinstance(w, torch.Tensor) else w, mean)
+        dstate = self.init_vorticity(dw.detach() if isinstance(dw, torch.Tensor) else dw)
+        state, rest = self._evolve_tangent('evolve_tangent', state, dstate, nsteps, forcing, dforcing, clock, noise_ids)
+        out = self.vorticity(state), self.vorticity(rest)
+        return tuple(o[0] for o in out) if squeeze else out
+
+    def evolve_velocity_tangent(self, u0, v0, du0, dv0, nsteps=1, forcing=None, dforcing=None, clock=0, noise_ids=None):
+        """``evolve_tangent`` from and to the velocity: (u, v, du, dv) after ``nsteps`` steps from (u0, v0) and the perturbation (du0, dv0):
+        ``init`` of both (the perturbation's grid mean is dropped: the mean flow is a constant of the call), the tangent steps, ``fields`` of
+        both.  (u, v) are bitwise ``evolve_velocity``'s forward.  NOT an autograd node: the inputs are detached."""
+        det = lambda a: a.detach() if isinstance(a, torch.Tensor) else a
+        squeeze = isinstance(u0, (torch.Tensor, np.ndarray)) and u0.ndim == 2
+        state, dstate = self.init(det(u0), det(v0)), self.init(det(du0), det(dv0))
+        state, rest = self._evolve_tangent('evolve_velocity_tangent', state, dstate, nsteps, forcing, dforcing, clock, noise_ids)
+        out = tuple(self.fields(state)[:2]) + tuple(self.fields(rest)[:2])
+        return tuple(o[0] for o in out) if squeeze else out
+
+    def lyapunov_exponent(self, state, dwhat, nsteps, renormalize_every):
+        """The leading finite-time Lyapunov exponent of every grid in the energy norm, float64 [B] on the device: sum log(growth) / (nsteps dt)
+        over ``nsteps`` steps of ``step_tangent`` (state and dwhat are advanced in place), growth = sqrt(E_after / E_before) of the
+        perturbation's energy per segment of ``renormalize_every`` steps, after each of which (and at the start) dwhat is rescaled to unit
+        energy: one torch multiply.  E is ``diagnostics(_at_rest(dwhat)).energy``, summed on the device in float64.  No host synchronisation:
+        the caller's read of the result is the only one.  A grid whose perturbation has no energy gives nan."""
+        self._tangent_spectrum('lyapunov_exponent', dwhat, state)
+        nsteps, every = _count('nsteps', nsteps, 1), _count('renormalize_every', renormalize_every, 1)
+        energy = lambda: ops.spec_ns_diag(dwhat, None, self.ny, self.Lx, self.Ly)[:, 0]
+
+        def rescale(e):                                  # dwhat to unit energy; the energy it then has, with the float32 factor as rounded
+            f = torch.rsqrt(e).to(torch.float32)
+            dwhat.mul_(f.reshape(-1, 1, 1, 1))
+            return e * f.to(torch.float64) ** 2
+        before = rescale(energy())
+        total = torch.zeros_like(before)
+        done = 0
+        while done < nsteps:
+            n = min(every, nsteps - done)
+            self.step_tangent(state, dwhat, n)
+            after = energy()
+            total += 0.5 * torch.log(after / before)
+            before = rescale(after)
+            done += n
+        return total / (nsteps * self.dt)
 
     # ---- reverse mode
     def _refuse_unsupported(self, who, scalar=False):
