@@ -651,7 +651,8 @@ int nns_spec_ns_step_operator_adjoint_f32(const float* what0, const float* that0
  * drag, hyperviscosity, hypofriction and beta need nothing further.  Linear in (dwhat, dghat) exactly for powers of two; a grid's result does
  * not depend on its batch neighbours; nsteps steps in one call are bitwise nsteps calls of one step.  Nothing is stored per step.  work:
  * nns_spec_ns_tangent_workspace bytes (12 compacted fields, >= nns_spec_ns_workspace: it also serves every unscalared nns_spec_ns_* call).  No
- * allocation, no host synchronisation (capturable).  Not built: the tangent of the scalar and the buoyant step.  Errors, all before any
+ * allocation, no host synchronisation (capturable).  Several tangents on one base: nns_spec_ns_step_tangents_f32 below.  Not built: the
+ * tangent of the scalar and the buoyant step.  Errors, all before any
  * launch: those of nns_spec_ns_step_linear_f32 (a NULL lin is no error here), plus NNS_ERR_INVALID_ARG for a NULL dwhat and for dgbatch not 0
  * without dghat, 1 or batch with it, and NNS_ERR_WORKSPACE below nns_spec_ns_tangent_workspace. */
 int nns_spec_ns_tangent_workspace(int batch, int nx, int ny, size_t* bytes);
@@ -659,6 +660,27 @@ int nns_spec_ns_step_tangent_f32(float* what, float* dwhat, const float* mean, c
                                  void* work, size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
                                  const float* lin, const float* amp, unsigned long long seed, long long* clock, const int* ids, int nsteps,
                                  void* stream);
+/* ntan tangents on one base, and what a Lyapunov spectrum needs beside them (restatement: tests/pspec_lyapunov_oracle.py).
+ * dwhat: float32 [ntan][batch][my1][nx][2], ntan in [1, 32]; member k is exactly a dwhat of nns_spec_ns_step_tangent_f32 and comes out BITWISE
+ * as from that call on a copy of the state, what as from the forward call the other arguments name.  The base's u, v, w_x, w_y of every stage are
+ * transformed once for all members: per step 2 + 2 ntan inverse and 1 + ntan forward transforms along y where ntan calls run 4 ntan and
+ * 2 ntan, and 1 + ntan passes through a column tile against 2 ntan; still 8 launches per step plus one per call.  No source perturbation per
+ * member.  work: nns_spec_ns_tangents_workspace bytes (6 + 6 ntan compacted fields, >= nns_spec_ns_workspace).  No allocation, no host
+ * synchronisation (capturable).  Errors, all before any launch: NNS_ERR_INVALID_ARG for a NULL dwhat, then for ntan outside [1, 32], then
+ * those of nns_spec_ns_step_tangent_f32 in its order, NNS_ERR_WORKSPACE below nns_spec_ns_tangents_workspace.
+ * nns_spec_ns_tangent_gram_f64: out float64 [batch][ntan][ntan], out[b][k][l] = 1/2 sum wt Re(conj(d_k) d_l) / |k|^2 / (nx ny)^2 over the kept
+ * stored modes (wt 1 on j = 0, 2 on j > 0): the energy inner product, whose diagonal is E of nns_spec_ns_diag_f32 of each member.  Float64
+ * sums in a fixed order, no atomics (two runs give the same bits); both triangles written, bitwise symmetric.
+ * nns_spec_ns_tangent_combine_f32: d_k <- sum_{l <= k} coef[b][l][k] d_l in place, coef float64 [batch][ntan][ntan] upper triangular (the
+ * lower triangle is not read), every stored entry summed in float64 and rounded once.  With coef = R^-1 of the Cholesky factor of the Gram
+ * matrix the two calls are one pass of a Cholesky QR; the ntan x ntan algebra between them is the caller's. */
+int nns_spec_ns_tangents_workspace(int batch, int ntan, int nx, int ny, size_t* bytes);
+int nns_spec_ns_step_tangents_f32(float* what, float* dwhat, int ntan, const float* mean, const float* ghat, int gbatch, void* work,
+                                  size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
+                                  const float* lin, const float* amp, unsigned long long seed, long long* clock, const int* ids,
+                                  int nsteps, void* stream);
+int nns_spec_ns_tangent_gram_f64(const float* dwhat, int ntan, double* out, int batch, int nx, int ny, double Lx, double Ly, void* stream);
+int nns_spec_ns_tangent_combine_f32(float* dwhat, int ntan, const double* coef, int batch, int nx, int ny, void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

@@ -106,6 +106,17 @@
 // (spec_ns_step) and one more row of PsLayout (12 compacted fields); the base is bitwise the step without the perturbation, and kernels without
 // the PsTangent keep their names and their code.  Registers and times: profiles/pspec_tangent_isa.txt (no scratch), profiles/pspec_tangent_run.json.
 //
+// K tangents on one base (nns_spec_ns_step_tangents_f32; restatement: tests/pspec_lyapunov_oracle.py): dwhat [K][B][my1][nx], member k exactly a
+// dwhat of the call above.  u, v, w_x, w_y of a stage are the same for every member, so ps_row_tans_kernel<ny> transforms them once per row
+// and keeps both lines while a run-time loop passes the K perturbations through (2 + 2K inverse and 1 + K forward transforms where K calls
+// run 4K and 2K; G fields 4+4k .. 7+4k, Ph field 1+k), and a PsTangents first in ps_col_kernel's pack (TANGENTS) runs the TG text K times per
+// tile after the vorticity's, on dW + k kstride / dA + k kstride (1 + K passes through a tile against 2K).  Member k's arithmetic is the
+// single tangent's, expression for expression.  No dg^ per member.  One more row of PsLayout that depends on K (6 + 6K compacted fields), the
+// same driver and launch count; the PsTangent kernels and every kernel without either struct keep their names and their code
+// (profiles/pspec_tangents_isa.txt, no scratch; times: profiles/pspec_tangents_run.json).  ps_tangent_gram_kernel is the energy Gram matrix
+// of the K members per grid (float64, ps_diag_kernel's fixed order of summation) and ps_tangent_combine_kernel the in-place triangular
+// recombination d_k <- sum_{l <= k} C[l][k] d_l: the two halves of a Cholesky QR, whose K x K algebra is the caller's.
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 //
 // What the row and column kernels share has one copy each: the LDS layout, PsArgs and the row pass's Hermitian fill and kept-mode store in
@@ -153,6 +164,12 @@ struct PsTangent {        // the first extra argument of the TANGENT column kern
     float2* dA;           // its Lawson accumulator
     const float2* dg;     // dg^ [dgbatch][my1][nx], the perturbation of the source, or NULL
     int dshared;          // 1: one dg^ for every grid; 0: one per grid
+};
+struct PsTangents {       // the first extra argument of the TANGENTS column kernels (nns_spec_ns_step_tangents_f32): K tangents on one base; never with a PsScalar or a PsKeep
+    float2* dW;           // dw^ [K][B][my1][nx]: member k at dW + k kstride, each in the layout of W
+    float2* dA;           // their Lawson accumulators, member k at dA + k kstride
+    long kstride;         // complex elements between two members (= B my1 nx)
+    int K;                // members, 1 .. 32
 };
 struct PsKeep {           // the last argument of the STAGES column kernels (stages 1-3 of the adjoint's recomputation; no scalar or noise)
     float2* stage;        // [B][my1][nx], the layout of W: receives the next stage's input spectrum (s1, s2 or s3)
@@ -343,6 +360,60 @@ __global__ __launch_bounds__(kT) void ps_row_tan_kernel(const float2* __restrict
     }
 }
 
+// The row pass of K tangents on one base (nns_spec_ns_step_tangents_f32).  u + i v and w_x + i w_y are transformed once and stay for the whole
+// row; the base's product leaves first (Ph field 0, ps_row_kernel's arithmetic).  Then a run-time loop over the members: du + i dv (G fields
+// 4+4k, 5+4k), the 16 reals du w_x + dv w_y (zp: w_x, w_y must survive for the next member, so they are not overwritten as in
+// ps_row_tan_kernel), dw_x + i dw_y (6+4k, 7+4k) into the same line, the linearised product spelt as there -- member k's bits are the single
+// tangent's -- and its forward transform to Ph field 1+k.  Three and a half complex lines are live; nothing is indexed by k but pointers.
+// 162 ... 176 VGPRs, 2 waves per SIMD (3 at N = 512), no scratch.
+template <int N>
+__global__ __launch_bounds__(kT) void ps_row_tans_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a, int K) {
+    using L = PsLds<N>;
+    constexpr int TPF = L::TPF;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const cf* tab = ps_tables<N>(smem);
+    unsigned char* lines = smem + L::TAB_BYTES;
+    const int my1 = a.my1;
+    const long niter = (a.nlines + L::LINES - 1) / L::LINES;
+    for (long it = blockIdx.x; it < niter; it += gridDim.x) {
+#include "pspec_row_line.inc"
+        cf zu[16], zw[16], zd[16];
+        float zp[16];
+        ps_row_load2<N>(g0, g0 + a.fstride, tid, my1, zu);                           // u + i v: stays
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 2 * a.fstride, g0 + 3 * a.fstride, tid, my1, zw);       // w_x + i w_y: stays
+        fft_line<float, N, true>(zw, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zd[m] = {zu[m].x * zw[m].x + zu[m].y * zw[m].y, 0.f};        // u w_x + v w_y
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tid);
+        ps_row_store<N>(zd, Ph + (size_t)row * my1, tid, my1, valid);
+        const float2* gk = g0 + 4 * a.fstride;                                       // member k's four fields
+        float2* pk = Ph + a.fstride + (size_t)row * my1;                             // and its Ph field
+        for (int k = 0; k < K; ++k, gk += 4 * a.fstride, pk += a.fstride) {
+            // the lane's index pinned per turn: what the loads, the transforms and the store derive from it (element offsets, predicates,
+            // twiddle addresses) is otherwise hoisted out of the loop and held across it -- 301 ... 313 registers and one wave per SIMD
+            // where this takes 162 ... 176
+            int tk = tid;
+            asm volatile("" : "+v"(tk));
+            __builtin_amdgcn_sched_barrier(0);
+            ps_row_load2<N>(gk, gk + a.fstride, tk, my1, zd);                        // du + i dv
+            fft_line<float, N, true>(zd, tab, tab + N / 2, xb, tk);
+#pragma unroll
+            for (int m = 0; m < 16; ++m) zp[m] = zd[m].x * zw[m].x + zd[m].y * zw[m].y;           // du w_x + dv w_y: w_x, w_y stay
+            __builtin_amdgcn_sched_barrier(0);
+            ps_row_load2<N>(gk + 2 * a.fstride, gk + 3 * a.fstride, tk, my1, zd);    // dw_x + i dw_y
+            fft_line<float, N, true>(zd, tab, tab + N / 2, xb, tk);
+#pragma unroll
+            for (int m = 0; m < 16; ++m) zd[m] = {fmaf(zu[m].x, zd[m].x, fmaf(zu[m].y, zd[m].y, zp[m])), 0.f};   // + u dw_x + v dw_y
+            __builtin_amdgcn_sched_barrier(0);
+            fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tk);
+            ps_row_store<N>(zd, pk, tk, my1, valid);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- column pass (axis x)
 // S = 0: prepare stage 1 from W; S = 1..4: consume the RK stage's N (from Ph) and update W / A, then (S < 4 or emit) prepare the next stage.
 // FORCED (S >= 1): N^ += g^ on the kept modes (lane-owned, coalesced, like W / A) and L dt / 2 = hnudt |k|^2 - alpha dt / 2.
@@ -358,6 +429,9 @@ __global__ __launch_bounds__(kT) void ps_row_tan_kernel(const float2* __restrict
 // same text runs once more on the perturbation dw^: Ph's second field, dw^ / dA with the VORTICITY's factors (hdrag and the LINEAR complex ones
 // included) and mask, dg^ where the vorticity adds g^ (also under an unforced base, whose own arithmetic stays the unforced kernel's), no kick
 // and no step count of its own, then its velocity and gradient as G fields 4-7 with zero means.  The vorticity's arithmetic is untouched.
+// TANGENTS (a PsTangents in the PsTangent's place; never with a PsScalar or a PsKeep): the TG text runs K times in a run-time loop, turn k on
+// dW + k kstride / dA + k kstride, Ph field 1+k and G fields 4+4k .. 7+4k, with no dg^.  The text sees member k under the names it has for
+// the one tangent (Ph, G and tg are shadowed by member k's in the loop's scope), so it is the same text and member k's bits are the TANGENT kernel's.
 template <int N, int S, bool FORCED = false, bool SCALAR = false, typename... Sc>
 __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, float2* __restrict__ W,
                                                     float2* __restrict__ A, const float* __restrict__ mean, PsArgs a, int emit,
@@ -366,11 +440,13 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     constexpr bool STOCH = (std::is_same_v<Sc, PsStoch> || ... || false);
     constexpr bool LINEAR = (std::is_same_v<Sc, PsLinear> || ... || false);
     constexpr bool TANGENT = (std::is_same_v<Sc, PsTangent> || ... || false);
+    constexpr bool TANGENTS = (std::is_same_v<Sc, PsTangents> || ... || false);
     constexpr bool KEEP_W = (std::is_same_v<Sc, PsKeep> || ... || false), KEEP_WT = (std::is_same_v<Sc, PsKeepScalar> || ... || false);
     constexpr bool STAGES = KEEP_W || KEEP_WT;
-    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (TANGENT ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0) + (STAGES ? 1 : 0),
+    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (TANGENT ? 1 : 0) + (TANGENTS ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0) + (STAGES ? 1 : 0),
                   "PsScalar is the SCALAR kernel's argument (PsTangent the TANGENT kernel's), PsLinear after it the LINEAR kernel's, PsStoch or the PsKeep last");
     static_assert(!TANGENT || (!SCALAR && !STAGES), "the tangent of the scalar system is not built, and the adjoint's recomputation carries no tangent");
+    static_assert(!TANGENTS || (!SCALAR && !STAGES && !TANGENT), "K tangents: as the one tangent, and never beside it");
     static_assert(!STAGES || (S >= 1 && S <= 3 && KEEP_WT == SCALAR && !STOCH),
                   "the stage store is that of stages 1-3 of the steady and the linear forms: a PsKeep without a scalar, a PsKeepScalar with one");
     static_assert(!LINEAR || (FORCED && S >= 1 && S <= 3), "the complex factors are those of stages 1-3 of the forced form");
@@ -448,6 +524,18 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
         if constexpr (TANGENT) {
             constexpr bool TH = false, TG = true;
 #include "pspec_col_pass.inc"
+        }
+        if constexpr (TANGENTS) {
+            const PsTangents ts = pick<PsTangents>(sc...);
+            const float2* const Ph0 = Ph;
+            float2* const G0 = G;
+            for (int k = 0; k < ts.K; ++k) {            // member k under the one tangent's names
+                const float2* Ph = Ph0 + (size_t)k * a.fstride;
+                float2* G = G0 + (size_t)(4 * k) * a.fstride;
+                const PsTangent tg{ts.dW + (size_t)k * ts.kstride, ts.dA + (size_t)k * ts.kstride, nullptr, 0};
+                constexpr bool TH = false, TG = true;
+#include "pspec_col_pass.inc"
+            }
         }
     }
 }
@@ -832,6 +920,62 @@ __global__ __launch_bounds__(kDiagT) void ps_scalar_diag_kernel(const float2* __
     }
 }
 
+// out[b][k][l] (float64) = 1/2 sum wt Re(conj(d_k) d_l) / |k|^2 / (nx ny)^2 over the kept stored modes of grid b: the energy inner product of
+// members k and l of D [K][B][my1][nx], whose diagonal is ps_diag_kernel's E of each member.  One workgroup per (grid, pair k <= l), which
+// writes both triangles: symmetric by construction.  ps_diag_kernel's walk, float64 sums, shuffle tree and index-ordered partials: no
+// atomics, so two runs give the same bits and a grid's numbers do not depend on its batch neighbours or on K.
+__global__ __launch_bounds__(kDiagT) void ps_tangent_gram_kernel(const float2* __restrict__ D, double* __restrict__ out, int K, long kstride,
+                                                                  int nx, int my1, double kx1, double ky1, double inv_n2) {
+    __shared__ double part[kDiagT / kWave];
+    int k = 0, rem = (int)blockIdx.x;                       // pair index -> (k, l), k <= l: row k holds K - k pairs
+    while (rem >= K - k) { rem -= K - k; ++k; }
+    const int l = k + rem;
+    const long per = (long)my1 * nx;
+    const float2* dk = D + (size_t)k * kstride + (size_t)blockIdx.y * per;
+    const float2* dl = D + (size_t)l * kstride + (size_t)blockIdx.y * per;
+    double e = 0.;
+    for (long q = threadIdx.x; q < per; q += kDiagT) {
+        const int i = (int)(q % nx), j = (int)(q / nx);
+        const int mx = i < nx / 2 ? i : i - nx;
+        const double kx = kx1 * mx, ky = ky1 * j, k2 = kx * kx + ky * ky;
+        const double ik2 = k2 > 0. && 3 * (mx < 0 ? -mx : mx) < nx ? 1. / k2 : 0.;
+        const double wt = j == 0 ? 1. : 2.;
+        const float2 c = dk[q], d = dl[q];
+        e += wt * ((double)c.x * d.x + (double)c.y * d.y) * ik2;
+    }
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) e += __shfl_xor(e, d, kWave);
+    const int wave = threadIdx.x / kWave;
+    if (threadIdx.x % kWave == 0) part[wave] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double se = 0.;
+        for (int w = 0; w < kDiagT / kWave; ++w) se += part[w];
+        double* o = out + (size_t)blockIdx.y * K * K;
+        o[(size_t)k * K + l] = o[(size_t)l * K + k] = 0.5 * se * inv_n2;
+    }
+}
+
+// d_k <- sum_{l <= k} C[b][l][k] d_l in place, C float64 [B][K][K] upper triangular.  Every stored entry (b, q) has one owning lane, which
+// walks k from K - 1 down to 0: d_k needs only members l <= k, none of which that walk has overwritten yet.  The sum is float64, l ascending,
+// rounded once; the members are read from memory each time (no array over K in registers), the coefficients are uniform loads.
+__global__ __launch_bounds__(256) void ps_tangent_combine_kernel(float2* __restrict__ D, const double* __restrict__ C, int K, long kstride, long per) {
+    const double* c = C + (size_t)blockIdx.y * K * K;
+    float2* d = D + (size_t)blockIdx.y * per;
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < per; q += (long)gridDim.x * blockDim.x) {
+        for (int k = K - 1; k >= 0; --k) {
+            double sx = 0., sy = 0.;
+            for (int l = 0; l <= k; ++l) {
+                const float2 z = d[(size_t)l * kstride + q];
+                const double f = c[(size_t)l * K + k];
+                sx = fma(f, (double)z.x, sx);
+                sy = fma(f, (double)z.y, sy);
+            }
+            d[(size_t)k * kstride + q] = make_float2((float)sx, (float)sy);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- shell spectra and transfers
 // Shells of width dk = min(kx1, ky1) centred on s dk: the mode (m_x, j) belongs to shell s = floor(|k| / dk + 1/2), in float64 (restatement:
 // tests/pspec_spectrum_oracle.py).  nshell = shell of the band's corner + 1; shell 0 holds the (0, 0) mode alone, which contributes nothing.
@@ -1074,19 +1218,28 @@ int launch_row_tan(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s) 
     return check_launch("spec_ns tangent row pass");
 }
 
-// The column kernel of stage S whose argument pack ends in x...: a PsScalar (the SCALAR kernels) or a PsTangent, a PsLinear, a PsStoch, in that order, each or
+template <int N>
+int launch_row_tans(const float2* G, float2* Ph, const PsArgs& a, int K, hipStream_t s) {
+    constexpr auto kern = ps_row_tans_kernel<N>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a, K);
+    return check_launch("spec_ns tangents row pass");
+}
+
+// The column kernel of stage S whose argument pack ends in x...: a PsScalar (the SCALAR kernels), a PsTangent or a PsTangents, a PsLinear, a PsStoch, in that order, each or
 // none.  fc is read only by the FORCED kernels.
 template <int N, int S, bool FORCED, typename... X>
 int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
                hipStream_t s, X... x) {
     constexpr bool SC = has<PsScalar, X...>, LI = has<PsLinear, X...>, ST = has<PsStoch, X...>, KE = has<PsKeep, X...> || has<PsKeepScalar, X...>;
-    constexpr bool TA = has<PsTangent, X...>;
+    constexpr bool TA = has<PsTangent, X...>, TS = has<PsTangents, X...>;
     constexpr auto kern = ps_col_kernel<N, S, FORCED, SC, X...>;
     std::conditional_t<FORCED, PsForce, PsNoForce> f{};
     if constexpr (FORCED) f = *fc;
     if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
     hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, f, x...);
-    return check_launch(TA       ? "spec_ns tangent column pass"
+    return check_launch(TS       ? "spec_ns tangents column pass"
+                        : TA     ? "spec_ns tangent column pass"
                         : KE     ? "spec_ns stage-keeping column pass"
                         : LI     ? (SC ? "spec_ns linear scalar column pass" : "spec_ns linear column pass")
                         : ST     ? (SC ? "spec_ns stochastic scalar column pass" : "spec_ns stochastic column pass")
@@ -1104,11 +1257,12 @@ int with_stage(int S, F&& f) {
 
 // The one place where a stage's run-time facts become a kernel.  fc == nullptr: the unforced kernels (stage 0 has no other form); sc: the
 // SCALAR ones; li (with fc): a linear step, whose stages 1-3 are the LINEAR kernels (stage 4 applies no factor); st (with fc): a stochastic
-// step, whose stages 1 and 4 are the STOCH kernels; tg (never with sc): the TANGENT ones, of every stage and form.  The pack grows in the
-// kernel's order, and a form no step has is never named.
+// step, whose stages 1 and 4 are the STOCH kernels; tg (never with sc): the TANGENT ones, of every stage and form; ts (never with sc or tg):
+// the TANGENTS ones, likewise.  The pack grows in the kernel's order, and a form no step has is never named.
 template <int N>
 int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
-                     const PsScalar* sc, hipStream_t s, const PsStoch* st = nullptr, const PsLinear* li = nullptr, const PsTangent* tg = nullptr) {
+                     const PsScalar* sc, hipStream_t s, const PsStoch* st = nullptr, const PsLinear* li = nullptr, const PsTangent* tg = nullptr,
+                     const PsTangents* ts = nullptr) {
     auto stage = [&](auto stage_c) {
         constexpr int K = decltype(stage_c)::value;
         auto stoch = [&](auto forced, auto... x) {
@@ -1122,7 +1276,7 @@ int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, c
                 if (li) return stoch(forced, x..., *li);
             return stoch(forced, x...);
         };
-        auto scalar = [&](auto forced) { return tg ? linear(forced, *tg) : sc ? linear(forced, *sc) : linear(forced); };
+        auto scalar = [&](auto forced) { return ts ? linear(forced, *ts) : tg ? linear(forced, *tg) : sc ? linear(forced, *sc) : linear(forced); };
         if constexpr (K >= 1)
             if (fc) return scalar(std::true_type{});
         return scalar(std::false_type{});
@@ -1193,6 +1347,7 @@ size_t scalar_work_bytes(int batch, int nx, int ny) {
 //   the scalar adjoint:  A, A_theta (wbar and thetabar once the stages are recomputed), G[10], Ph[3] (the recomputation's: 6 and 2), s1, s2, s3
 //                        of w^, then of theta^: 21
 //   the tangent step:    A, dA in A_theta's place, G[8], Ph[2]: 12
+//   K tangents:          A, dA[K], G[4 + 4K], Ph[1 + K]: 6 + 6K (tangents_layout; K = 1 is the tangent step's)
 struct PsLayout {
     int acc, g, ph, keep;
     constexpr int fields() const { return acc + g + ph + keep; }
@@ -1206,6 +1361,9 @@ size_t layout_work_bytes(const PsLayout& lay, int batch, int nx, int ny) {
 size_t adjoint_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayAdjoint, batch, nx, ny); }
 size_t scalar_adjoint_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayScalarAdjoint, batch, nx, ny); }
 size_t tangent_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayTangent, batch, nx, ny); }
+constexpr int kMaxTangents = 32;
+constexpr PsLayout tangents_layout(int K) { return PsLayout{1 + K, 4 + 4 * K, 1 + K, 0}; }
+size_t tangents_work_bytes(int batch, int ntan, int nx, int ny) { return layout_work_bytes(tangents_layout(ntan), batch, nx, ny); }
 
 // The fields of a layout in work, and the arguments of the column pass (col) and of the row pass (row).
 struct PsWork {
@@ -1245,17 +1403,19 @@ int check_box(const char* what, int nx, int ny, double Lx, double Ly) {
     return check_axes(what, nx, ny);
 }
 
-enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2, kWorkScalarAdjoint = 3, kWorkTangent = 4 };      // a bool converts: false the flow's workspace, true the scalar's
+enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2, kWorkScalarAdjoint = 3, kWorkTangent = 4, kWorkTangents = 5 };      // a bool converts: false the flow's workspace, true the scalar's
 
-int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int kind) {
-    const size_t need = kind == kWorkTangent       ? tangent_work_bytes(batch, nx, ny)
+int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int kind, int ntan = 0) {      // ntan: kWorkTangents' K
+    const size_t need = kind == kWorkTangents      ? tangents_work_bytes(batch, ntan, nx, ny)
+                        : kind == kWorkTangent     ? tangent_work_bytes(batch, nx, ny)
                         : kind == kWorkScalarAdjoint ? scalar_adjoint_work_bytes(batch, nx, ny)
                         : kind == kWorkAdjoint     ? adjoint_work_bytes(batch, nx, ny)
                         : kind == kWorkScalar      ? scalar_work_bytes(batch, nx, ny)
                                                    : work_bytes(batch, nx, ny);
     if (wbytes < need)
         return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", what, wbytes, need,
-                    kind == kWorkTangent       ? "nns_spec_ns_tangent_workspace"
+                    kind == kWorkTangents      ? "nns_spec_ns_tangents_workspace"
+                    : kind == kWorkTangent     ? "nns_spec_ns_tangent_workspace"
                     : kind == kWorkScalarAdjoint ? "nns_spec_ns_scalar_adjoint_workspace"
                     : kind == kWorkAdjoint     ? "nns_spec_ns_adjoint_workspace"
                     : kind == kWorkScalar      ? "nns_spec_ns_scalar_workspace"
@@ -1263,9 +1423,9 @@ int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int k
     return NNS_OK;
 }
 
-int check_common(const char* what, int batch, int nx, int ny, double Lx, double Ly, size_t wbytes, int kind = kWorkFlow) {
+int check_common(const char* what, int batch, int nx, int ny, double Lx, double Ly, size_t wbytes, int kind = kWorkFlow, int ntan = 0) {
     if (int rc = check_box(what, nx, ny, Lx, Ly)) return rc;
-    return check_work(what, batch, nx, ny, wbytes, kind);
+    return check_work(what, batch, nx, ny, wbytes, kind, ntan);
 }
 
 // dt, nu, drag and nsteps of a step, forward or adjoint
@@ -1446,11 +1606,13 @@ NNS_API int nns_spec_ns_init_f32(const float* u, const float* v, float* what, fl
 // st != NULL (amp, key, clock, ids; its sqdt is set here) takes the forced path, with or without ghat and drag, and kicks after every step;
 // lin != NULL takes the forced path too, with the table's factors in stages 1-3 (nu and drag are then unused: the table holds them).
 // dwhat != NULL (never with that): the tangent-linear step, the same launches in their TANGENT forms on the tangent layout of work; the choice
-// of the base's kernels is the one made without dwhat, so what comes out bitwise as from that call.
+// of the base's kernels is the one made without dwhat, so what comes out bitwise as from that call.  ntan >= 1 (with dwhat, no dghat): dwhat holds
+// ntan tangents [ntan][B][my1][nx] on that one base, the TANGENTS forms on the layout of ntan tangents; ntan == 0: the one tangent's call.
 static int spec_ns_step(const char* who, float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work,
                         size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa,
                         double gx, double gy, double bx, double by, int nsteps, void* stream, const PsStoch* st = nullptr,
-                        const float* lin = nullptr, float* dwhat = nullptr, const float* dghat = nullptr, int dgbatch = 0) {
+                        const float* lin = nullptr, float* dwhat = nullptr, const float* dghat = nullptr, int dgbatch = 0,
+                        int ntan = 0) {
     if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
     if (dwhat && that) return fail(NNS_ERR_UNSUPPORTED, "%s: the tangent of the scalar system is not built", who);
     if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
@@ -1459,13 +1621,15 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
     if (int rc = check_gbatch(who, ghat, gbatch, batch)) return rc;
     if (dghat ? (dgbatch != 1 && dgbatch != batch) : dgbatch != 0)
         return fail(NNS_ERR_INVALID_ARG, "%s: dgbatch = %d must be 0 without dghat, 1 or batch = %d with it", who, dgbatch, batch);
-    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, dwhat ? kWorkTangent : that ? kWorkScalar : kWorkFlow)) return rc;
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, ntan ? kWorkTangents : dwhat ? kWorkTangent : that ? kWorkScalar : kWorkFlow, ntan)) return rc;
     if (nsteps == 0) return NNS_OK;
     hipStream_t s = as_stream(stream);
     float2* W = reinterpret_cast<float2*>(what);
-    const PsWork L(work, batch, nx, ny, dwhat ? kLayTangent : that ? kLayScalar : kLayFlow, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);
+    const PsWork L(work, batch, nx, ny, ntan ? tangents_layout(ntan) : dwhat ? kLayTangent : that ? kLayScalar : kLayFlow, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);
     const PsTangent tangent{reinterpret_cast<float2*>(dwhat), L.At, reinterpret_cast<const float2*>(dghat), dgbatch == 1 && batch > 1 ? 1 : 0};
-    const PsTangent* tg = dwhat ? &tangent : nullptr;
+    const PsTangent* tg = dwhat && !ntan ? &tangent : nullptr;
+    const PsTangents tangents{reinterpret_cast<float2*>(dwhat), L.At, L.col.fstride, ntan};      // dA[k] follows A, a field apart like the members
+    const PsTangents* ts = ntan ? &tangents : nullptr;
     const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
     const PsForce* fc = ghat || drag > 0 || st || lin ? &force : nullptr;
     const PsLinear linear{reinterpret_cast<const float2*>(lin)};
@@ -1482,11 +1646,12 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
     const PsBuoyGrad buoy{(float)gx, (float)gy, (float)(-(double)ny * by), (float)((double)ny * bx)};
     const PsBuoyGrad* bu = that && (bx != 0.0 || by != 0.0) ? &buoy : nullptr;
     auto col = [&](int S, int emit) {
-        return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, emit, fc, sc, s, stc, li, tg); });
+        return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, emit, fc, sc, s, stc, li, tg, ts); });
     };
     auto row = [&]() {
         return dispatch_pow2(ny, "spec_ns", [&](auto n) {
             constexpr int N = decltype(n)::value;
+            if (ts) return launch_row_tans<N>(L.G, L.Ph, L.row, ntan, s);
             if (tg) return launch_row_tan<N>(L.G, L.Ph, L.row, s);
             return bu ? launch_row<N>(L.G, L.Ph, L.row, s, *bu) : that ? launch_row<N>(L.G, L.Ph, L.row, s, grad) : launch_row<N>(L.G, L.Ph, L.row, s);
         });
@@ -1572,6 +1737,53 @@ NNS_API int nns_spec_ns_step_tangent_f32(float* what, float* dwhat, const float*
     const PsStoch st{amp, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), clock, ids, 0.f};
     return spec_ns_step("spec_ns_step_tangent", what, nullptr, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, lin ? 0.0 : nu,
                         lin ? 0.0 : drag, 0.0, 0.0, 0.0, 0.0, 0.0, nsteps, stream, noise ? &st : nullptr, lin, dwhat, dghat, dgbatch);
+}
+
+NNS_API int nns_spec_ns_tangents_workspace(int batch, int ntan, int nx, int ny, size_t* bytes) {
+    if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_tangents_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
+    if (ntan < 1 || ntan > kMaxTangents) return fail(NNS_ERR_INVALID_ARG, "spec_ns_tangents_workspace: ntan = %d must be in [1, %d]", ntan, kMaxTangents);
+    if (int rc = check_axes("spec_ns_tangents_workspace", nx, ny)) return rc;
+    *bytes = tangents_work_bytes(batch, ntan, nx, ny);
+    return NNS_OK;
+}
+
+NNS_API int nns_spec_ns_step_tangents_f32(float* what, float* dwhat, int ntan, const float* mean, const float* ghat, int gbatch, void* work,
+                                          size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
+                                          const float* lin, const float* amp, unsigned long long seed, long long* clock, const int* ids,
+                                          int nsteps, void* stream) {
+    if (!dwhat) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_tangents: dwhat must be non-NULL");
+    if (ntan < 1 || ntan > kMaxTangents) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_tangents: ntan = %d must be in [1, %d]", ntan, kMaxTangents);
+    const bool noise = amp && clock && ids;
+    if (!noise && (amp || clock || ids))
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_tangents: amp, clock and ids must be all NULL (no noise) or all non-NULL");
+    const PsStoch st{amp, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), clock, ids, 0.f};
+    return spec_ns_step("spec_ns_step_tangents", what, nullptr, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, lin ? 0.0 : nu,
+                        lin ? 0.0 : drag, 0.0, 0.0, 0.0, 0.0, 0.0, nsteps, stream, noise ? &st : nullptr, lin, dwhat, nullptr, 0, ntan);
+}
+
+// dwhat, ntan, batch and the box of the Gram and the combine call
+static int check_tangents(const char* who, const void* dwhat, const void* other, int ntan, int batch, int nx, int ny) {
+    if (!dwhat || !other || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
+    if (ntan < 1 || ntan > kMaxTangents) return fail(NNS_ERR_INVALID_ARG, "%s: ntan = %d must be in [1, %d]", who, ntan, kMaxTangents);
+    return check_axes(who, nx, ny);
+}
+
+NNS_API int nns_spec_ns_tangent_gram_f64(const float* dwhat, int ntan, double* out, int batch, int nx, int ny, double Lx, double Ly, void* stream) {
+    if (int rc = check_tangents("spec_ns_tangent_gram", dwhat, out, ntan, batch, nx, ny)) return rc;
+    if (int rc = check_lengths("spec_ns_tangent_gram", Lx, Ly)) return rc;
+    const int my1 = kept_y(ny);
+    const double n = (double)nx * ny;
+    hipLaunchKernelGGL(ps_tangent_gram_kernel, dim3(ntan * (ntan + 1) / 2, batch), dim3(kDiagT), 0, as_stream(stream),
+                       reinterpret_cast<const float2*>(dwhat), out, ntan, (long)batch * my1 * nx, nx, my1, 2.0 * M_PI / Lx, 2.0 * M_PI / Ly, 1.0 / (n * n));
+    return check_launch("spec_ns_tangent_gram");
+}
+
+NNS_API int nns_spec_ns_tangent_combine_f32(float* dwhat, int ntan, const double* coef, int batch, int nx, int ny, void* stream) {
+    if (int rc = check_tangents("spec_ns_tangent_combine", dwhat, coef, ntan, batch, nx, ny)) return rc;
+    const long per = (long)kept_y(ny) * nx;
+    hipLaunchKernelGGL(ps_tangent_combine_kernel, dim3(capped_grid((per + 255) / 256, 4096), batch), dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<float2*>(dwhat), coef, ntan, (long)batch * per, per);
+    return check_launch("spec_ns_tangent_combine");
 }
 
 NNS_API int nns_spec_ns_adjoint_workspace(int batch, int nx, int ny, size_t* bytes) {

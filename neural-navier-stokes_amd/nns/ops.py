@@ -1248,6 +1248,76 @@ def spec_ns_step_tangent_(what, dwhat, mean, ghat, dghat, work, ny, Lx, Ly, dt, 
     return what, dwhat
 
 
+# K tangents on one base and their orthonormalisation (nns_spec_ns_step_tangents_f32, nns_spec_ns_tangent_gram_f64, nns_spec_ns_tangent_combine_f32)
+SPEC_NS_MAX_TANGENTS = 32
+
+
+def spec_ns_tangents_workspace(B, K, nx, ny):
+    """Bytes of the workspace spec_ns_step_tangents_ needs for K tangents on B grids of nx x ny (>= spec_ns_workspace)."""
+    return _query_bytes('nns_spec_ns_tangents_workspace', int(B), int(K), int(nx), int(ny))
+
+
+def _spec_ns_tangents(who, dwhat, ny, B=None, my1=None, nx=None, device=None):
+    """(K, B, my1, nx) of the checked tangents dwhat, float32 [K, B, my1, nx, 2] with K in [1, 32]; B, my1, nx, device: those of the state
+    they belong to (all None: the tangents alone, ny decides my1)."""
+    _f32(dwhat)
+    if dwhat.dim() != 5 or dwhat.shape[4] != 2:
+        raise ValueError("%s: dwhat must be float32 [K, B, my1, nx, 2], got %s" % (who, tuple(dwhat.shape)))
+    K = int(dwhat.shape[0])
+    if not 1 <= K <= SPEC_NS_MAX_TANGENTS:
+        raise ValueError("%s: K = %d tangents, must be in [1, %d]" % (who, K, SPEC_NS_MAX_TANGENTS))
+    if B is None:
+        B, my1, nx, device = int(dwhat.shape[1]), spec_ns_kept_y(ny), int(dwhat.shape[3]), dwhat.device
+    if tuple(dwhat.shape[1:4]) != (B, my1, nx):
+        raise ValueError("%s: dwhat must be float32 [K, %d, %d, %d, 2], got %s" % (who, B, my1, nx, tuple(dwhat.shape)))
+    if dwhat.device != device:
+        raise ValueError("%s: dwhat must be on the state's device %s" % (who, device))
+    return K, B, my1, nx
+
+
+def spec_ns_step_tangents_(what, dwhat, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, lin=None, noise=None, nsteps=1):
+    """spec_ns_step_tangent_ with K tangents dwhat (float32 [K, B, my1, nx, 2], K <= 32) on the one base what: what and every dwhat[k] bitwise
+    as from that call with dwhat[k] alone (no dghat), the base's transforms done once for all K.  work: spec_ns_tangents_workspace bytes.
+    8 launches per step and one per call, no allocation, no host synchronisation: capturable."""
+    who = 'spec_ns_step_tangents'
+    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
+    K = _spec_ns_tangents(who, dwhat, ny, B, my1, nx, what.device)[0]
+    gbatch = _spec_ns_force(who, ghat, what)
+    if lin is not None:
+        _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), what.device)
+    amp, seed, clock, ids = noise or (None, 0, None, None)
+    if noise is not None:
+        _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
+    check(_lib.lib().nns_spec_ns_step_tangents_f32(_p(what), _p(dwhat), K, _p(mean), _pn(ghat), gbatch, _p(work), work.numel(), B, nx, int(ny),
+                                                   float(Lx), float(Ly), float(dt), float(nu), float(drag), _pn(lin), _pn(amp), int(seed),
+                                                   _pn(clock), _pn(ids), int(nsteps), _stream()), 'nns_spec_ns_step_tangents_f32')
+    return what, dwhat
+
+
+def spec_ns_tangent_gram(dwhat, ny, Lx, Ly, out=None):
+    """float64 [B, K, K]: the energy inner products of the K tangents dwhat ([K, B, my1, nx, 2]) per grid, 1/2 <du_k . du_l>; the diagonal is
+    spec_ns_diag's energy of each member.  Bitwise symmetric and repeatable.  No host synchronisation."""
+    who = 'spec_ns_tangent_gram'
+    K, B, my1, nx = _spec_ns_tangents(who, dwhat, ny)
+    out = _spec_ns_out(who, out, (B, K, K), dwhat.device)
+    check(_lib.lib().nns_spec_ns_tangent_gram_f64(_p(dwhat), K, _p(out), B, nx, int(ny), float(Lx), float(Ly), _stream()),
+          'nns_spec_ns_tangent_gram_f64')
+    return out
+
+
+def spec_ns_tangent_combine_(dwhat, coef, ny):
+    """dwhat[k] <- sum over l <= k of coef[b, l, k] dwhat[l] in place, coef float64 [B, K, K] upper triangular on dwhat's device: float64
+    sums, rounded once.  No host synchronisation."""
+    who = 'spec_ns_tangent_combine'
+    K, B, my1, nx = _spec_ns_tangents(who, dwhat, ny)
+    if not (isinstance(coef, torch.Tensor) and coef.is_cuda and coef.dtype == torch.float64 and coef.is_contiguous()):
+        raise TypeError("%s: coef must be a contiguous float64 device tensor" % who)
+    if tuple(coef.shape) != (B, K, K) or coef.device != dwhat.device:
+        raise ValueError("%s: coef must be float64 [%d, %d, %d] on dwhat's device, got %s on %s" % (who, B, K, K, tuple(coef.shape), coef.device))
+    check(_lib.lib().nns_spec_ns_tangent_combine_f32(_p(dwhat), K, _p(coef), B, nx, int(ny), _stream()), 'nns_spec_ns_tangent_combine_f32')
+    return dwhat
+
+
 def spec_ns_linear_spectrum(what, rate, ny, Lx, Ly, out=None):
     """float64 [B, 2, nshell]: (D_E, D_Z) per shell, the rates at which the linear term changes energy and enstrophy; rate = Re(lambda)
     float64 [my1, nx] on the state's device."""

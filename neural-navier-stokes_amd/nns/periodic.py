@@ -28,6 +28,7 @@ float64 by an oracle under tests/:
   * reverse mode on every solver, ``evolve`` / ``evolve_velocity``   pspec_linear_adjoint_oracle.py
   * their ``operator``: gradients in nu, drag, nu_h, mu, beta, lambda(k)   pspec_operator_grad_oracle.py
   * forward mode, ``step_tangent`` / ``evolve_tangent`` / ``lyapunov_exponent``   pspec_tangent_oracle.py
+  * K tangents on one base, ``step_tangents`` / ``lyapunov_spectrum``              pspec_lyapunov_oracle.py
 Which C entry a step or an adjoint takes is decided in one place each, ops.spec_ns_advance_ and ops.spec_ns_adjoint_.
 """
 import collections
@@ -157,6 +158,23 @@ def flux(t):
     """The spectral flux Pi(s) = -sum_{s' <= s} T(s') of a transfer T [..., S] (a field of ``Transfer``): the rate at which the nonlinear term
     carries the quantity out of the shells <= s, positive for a cascade towards small scales; Pi(S - 1) = 0 to rounding."""
     return -torch.cumsum(t, dim=-1)
+
+
+def kaplan_yorke_dimension(exponents):
+    """The Kaplan-Yorke (Lyapunov) dimension of a spectrum of exponents [..., K] (a torch tensor; it stays on its device), over the last
+    axis: with the exponents sorted descending and S_j the sum of the first j, j the largest count with S_j >= 0, it is j + S_j / |lambda_(j+1)|.
+    0 where the leading exponent is negative.  K where every partial sum is >= 0: the K exponents given do not reach the point where the
+    volume contracts, so K is then only a LOWER BOUND of the dimension -- compute more exponents.  nan where an exponent is nan."""
+    lam = torch.sort(exponents, dim=-1, descending=True).values
+    K = lam.shape[-1]
+    S = torch.cumsum(lam, dim=-1)
+    count = torch.arange(1, K + 1, device=lam.device)
+    j = torch.amax(torch.where(S >= 0, count, torch.zeros_like(count)), dim=-1, keepdim=True)            # S_j >= 0 holds on a prefix
+    zero = torch.zeros_like(lam[..., :1])
+    Sj = torch.gather(torch.cat([zero, S], dim=-1), -1, j)                                               # S_0 = 0
+    nxt = torch.gather(torch.cat([lam, torch.ones_like(zero)], dim=-1), -1, j)                           # lambda_(j+1); unused at j = K
+    dim = torch.where(j == K, j.to(lam.dtype), j.to(lam.dtype) + Sj / nxt.abs())
+    return torch.where(torch.isnan(lam).any(dim=-1, keepdim=True), torch.full_like(dim, float('nan')), dim)[..., 0]
 
 
 class PeriodicState(object):
@@ -355,8 +373,15 @@ class PeriodicSolver(object):
     w_x, w_y those of stage i's own state.  The perturbation rides in the step's launches as the scalar does (still 8 per step,
     capturable), has no mean flow and no (0, 0) mode, and gets no kick: the noise is a constant of the call.  Nothing is stored per step
     (the adjoint keeps a spectrum per step).  ``evolve_tangent`` / ``evolve_velocity_tangent`` are the field-level forms, ``evolve``'s
-    forward bitwise; ``lyapunov_exponent`` the leading finite-time exponent in the energy norm.  Not built: the tangent of the scalar and
-    the Boussinesq system (a state that carries a scalar is refused), the tangent in ``operator``, several tangents sharing one base, a
+    forward bitwise; ``lyapunov_exponent`` the leading finite-time exponent in the energy norm.  Several tangents sharing one base:
+    ``step_tangents(state, dwhat, nsteps)`` carries K <= 32 perturbations dwhat [K, B, my1, nx, 2] (``init_tangents``) in one call, the state
+    bitwise as by ``step`` and every dwhat[k] bitwise as by ``step_tangent`` alone; u, v, w_x, w_y of a stage are transformed once for all
+    K, so the y-transforms and the passes through a column tile tend to one half of K separate calls' (still 8 launches per step).
+    ``tangent_gram`` is their Gram matrix in the energy inner product, ``orthonormalize_tangents`` a Cholesky QR done twice (Gram and
+    recombination in HIP, the K x K algebra in torch float64 on the device), ``lyapunov_spectrum`` the first K finite-time exponents with
+    the backward Lyapunov vectors left in dwhat, and the module's ``kaplan_yorke_dimension`` the attractor's dimension from them.  Not
+    built: the tangent of the scalar and
+    the Boussinesq system (a state that carries a scalar is refused), the tangent in ``operator``, a source perturbation per tangent, covariant vectors, a
     ``jvp`` hook on the autograd node for ``torch.autograd.forward_ad``, and reverse mode through the tangent (Hessian-vector products).
 
     By wavenumber: the stored modes are binned into shells of width dk = min(2 pi / Lx, 2 pi / Ly) centred on k_s = s dk (``shells()``; an
@@ -799,6 +824,101 @@ class PeriodicSolver(object):
             after = energy()
             total += 0.5 * torch.log(after / before)
             before = rescale(after)
+            done += n
+        return total / (nsteps * self.dt)
+
+    # ---- K tangents on one base
+    def _tangent_spectra(self, who, dwhat, state=None):
+        """The checked tangents [K, B, my1, nx, 2] of ``who`` (for this state, which must carry no scalar); K."""
+        if state is not None:
+            self._state(state)
+            if state.that is not None:
+                raise NotImplementedError("%s: the tangent of the scalar system is not built yet: the state carries a scalar (passive or buoyant); "
+                                          "a state without one is stepped as by step" % who)
+        if not isinstance(dwhat, torch.Tensor):
+            raise TypeError("%s: dwhat must be a torch tensor, got %s" % (who, type(dwhat).__name__))
+        want = (self.my1, self.nx, 2) if state is None else tuple(state.what.shape[1:])
+        if dwhat.dtype != torch.float32 or dwhat.dim() != 5 or tuple(dwhat.shape[2:]) != want or not dwhat.is_cuda or not dwhat.is_contiguous() \
+                or (state is not None and (dwhat.shape[1] != state.batch or dwhat.device != state.what.device)):
+            raise ValueError("%s: dwhat must be a contiguous float32 [K, %s, %d, %d, 2] tensor on the %s (init_tangents(dw)), got %s %s on %s"
+                             % (who, 'B' if state is None else state.batch, self.my1, self.nx, "device" if state is None else "state's device",
+                                dwhat.dtype, tuple(dwhat.shape), dwhat.device))
+        K = int(dwhat.shape[0])
+        if not 1 <= K <= ops.SPEC_NS_MAX_TANGENTS:
+            raise ValueError("%s: K = %d tangents, must be in [1, %d]" % (who, K, ops.SPEC_NS_MAX_TANGENTS))
+        return K
+
+    def init_tangents(self, dw):
+        """The spectra [K, B, my1, nx, 2] of K perturbation vorticity fields dw (float32 [K, B, nx, ny]): ``init_vorticity(dw[k]).what`` of
+        every member, in one call on the K B fields (the band-limited part, the (0, 0) mode zeroed)."""
+        dw = torch.as_tensor(dw)
+        if dw.dim() != 4 or tuple(dw.shape[2:]) != (self.nx, self.ny):
+            raise ValueError("dw: [K, B, %d, %d] expected, got %s" % (self.nx, self.ny, tuple(dw.shape)))
+        K, B = int(dw.shape[0]), int(dw.shape[1])
+        if not 1 <= K <= ops.SPEC_NS_MAX_TANGENTS:
+            raise ValueError("init_tangents: K = %d tangents, must be in [1, %d]" % (K, ops.SPEC_NS_MAX_TANGENTS))
+        return self.init_vorticity(dw.reshape(K * B, self.nx, self.ny)).what.reshape(K, B, self.my1, self.nx, 2)
+
+    def step_tangents(self, state, dwhat, nsteps=1):
+        """``step(state, nsteps)`` -- bitwise, ``state.steps`` and ``state.clock`` included -- with the K tangent spectra ``dwhat`` (float32
+        [K, B, my1, nx, 2], ``init_tangents``) advanced in place and returned, every ``dwhat[k]`` bitwise as by ``step_tangent`` on a clone of
+        the state (the class note, "Forward mode").  Grows ``state.work`` to the workspace of K tangents on first use (take one step outside
+        before capturing one in a graph); otherwise no allocation and no host synchronisation.  A state that carries a scalar is refused:
+        NotImplementedError."""
+        K = self._tangent_spectra('step_tangents', dwhat, state)
+        nsteps = _count('nsteps', nsteps, 0)
+        lin = self._linear_of(state) if self._linear() else None
+        noise = None
+        if self.stoch_amp is not None:
+            amp, clock, ids = self._noise_of(state)
+            noise = (amp, self.stoch_seed, clock, ids)
+        state.work = self._work(lambda B, nx, ny: ops.spec_ns_tangents_workspace(B, K, nx, ny), state.batch, state.what.device, have=state.work)
+        ops.spec_ns_step_tangents_(state.what, dwhat, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu,
+                                   self.drag, lin, noise, nsteps)
+        state.steps += nsteps
+        return dwhat
+
+    def tangent_gram(self, dwhat):
+        """float64 [B, K, K] on the device: the Gram matrix of the K tangents of every grid in the energy inner product, 1/2 <du_k . du_l>;
+        its diagonal is ``diagnostics(_at_rest(dwhat[k])).energy``.  Bitwise symmetric; two calls give the same bits."""
+        self._tangent_spectra('tangent_gram', dwhat)
+        return ops.spec_ns_tangent_gram(dwhat, self.ny, self.Lx, self.Ly)
+
+    def orthonormalize_tangents(self, dwhat):
+        """Orthonormalise the K tangents of every grid in place under the energy inner product, D = Q R with dwhat <- Q, and return
+        log(diag R), float64 [B, K] on the device.  Cholesky QR done twice (the second pass restores the orthogonality that the first loses
+        on nearly dependent vectors): the Gram matrix and the recombination d_k <- sum_{l <= k} (R^-1)[l, k] d_l touch the spectra and are
+        HIP; the Cholesky factor and its triangular inverse are [B, K, K] float64 torch on the device, without error checks, so nothing
+        synchronises.  The logs of the two passes add.  A grid whose vectors are dependent gives nan, as ``lyapunov_exponent`` does for a
+        perturbation without energy."""
+        K = self._tangent_spectra('orthonormalize_tangents', dwhat)
+        eye = torch.eye(K, dtype=torch.float64, device=dwhat.device)
+        logs = None
+        for _ in range(2):
+            gram = ops.spec_ns_tangent_gram(dwhat, self.ny, self.Lx, self.Ly)
+            low, info = torch.linalg.cholesky_ex(gram, check_errors=False)                  # gram = low low^T: R = low^T
+            rinv = torch.linalg.solve_triangular(low.transpose(-1, -2), eye.expand_as(gram), upper=True).contiguous()
+            ops.spec_ns_tangent_combine_(dwhat, rinv, self.ny)
+            diag = torch.diagonal(low, dim1=-2, dim2=-1)
+            failed = (info != 0) | ~(diag > 0).all(dim=-1)                                  # a pivot that is not positive: dependent vectors
+            lg = torch.where(failed.unsqueeze(-1), torch.full_like(diag, float('nan')), torch.log(diag))
+            logs = lg if logs is None else logs + lg
+        return logs
+
+    def lyapunov_spectrum(self, state, dwhat, nsteps, renormalize_every):
+        """The first K finite-time Lyapunov exponents of every grid in the energy norm, float64 [B, K] on the device: the tangents are
+        orthonormalised at the start and after every ``renormalize_every`` steps of ``step_tangents``, and the exponents are the sums of
+        log(diag R) of those factorisations (the first one's excepted) / (nsteps dt).  State and dwhat are advanced in place; dwhat is left
+        orthonormal: the backward Lyapunov vectors at the end of the run.  The exponents come in the order of the vectors, unsorted; they
+        approach descending order as the run grows.  No host synchronisation.  A grid whose vectors become dependent gives nan."""
+        self._tangent_spectra('lyapunov_spectrum', dwhat, state)
+        nsteps, every = _count('nsteps', nsteps, 1), _count('renormalize_every', renormalize_every, 1)
+        total = torch.zeros_like(self.orthonormalize_tangents(dwhat))
+        done = 0
+        while done < nsteps:
+            n = min(every, nsteps - done)
+            self.step_tangents(state, dwhat, n)
+            total += self.orthonormalize_tangents(dwhat)
             done += n
         return total / (nsteps * self.dt)
 
