@@ -651,8 +651,8 @@ int nns_spec_ns_step_operator_adjoint_f32(const float* what0, const float* that0
  * drag, hyperviscosity, hypofriction and beta need nothing further.  Linear in (dwhat, dghat) exactly for powers of two; a grid's result does
  * not depend on its batch neighbours; nsteps steps in one call are bitwise nsteps calls of one step.  Nothing is stored per step.  work:
  * nns_spec_ns_tangent_workspace bytes (12 compacted fields, >= nns_spec_ns_workspace: it also serves every unscalared nns_spec_ns_* call).  No
- * allocation, no host synchronisation (capturable).  Several tangents on one base: nns_spec_ns_step_tangents_f32 below.  Not built: the
- * tangent of the scalar and the buoyant step.  Errors, all before any
+ * allocation, no host synchronisation (capturable).  Several tangents on one base: nns_spec_ns_step_tangents_f32 below; the tangent of the
+ * scalar and the buoyant step: nns_spec_ns_step_scalar_tangent_f32 below (this call has no scalar).  Errors, all before any
  * launch: those of nns_spec_ns_step_linear_f32 (a NULL lin is no error here), plus NNS_ERR_INVALID_ARG for a NULL dwhat and for dgbatch not 0
  * without dghat, 1 or batch with it, and NNS_ERR_WORKSPACE below nns_spec_ns_tangent_workspace. */
 int nns_spec_ns_tangent_workspace(int batch, int nx, int ny, size_t* bytes);
@@ -681,6 +681,31 @@ int nns_spec_ns_step_tangents_f32(float* what, float* dwhat, int ntan, const flo
                                   int nsteps, void* stream);
 int nns_spec_ns_tangent_gram_f64(const float* dwhat, int ntan, double* out, int batch, int nx, int ny, double Lx, double Ly, void* stream);
 int nns_spec_ns_tangent_combine_f32(float* dwhat, int ntan, const double* coef, int batch, int nx, int ny, void* stream);
+/* Forward mode of the scalar and the buoyant step (restatement: tests/pspec_scalar_tangent_oracle.py): the Jacobian of nsteps steps of the
+ * system (w^, theta^) applied to a perturbation (dw^, dtheta^) that is carried along with it, J d where
+ * nns_spec_ns_step_scalar_adjoint_f32 and nns_spec_ns_step_linear_adjoint_f32 give J^T r.  The same four stages on (dw^, dtheta^), dw^ with the
+ * vorticity's factors (real, or complex from lin) and mask, dtheta^ with the scalar's real E_theta and the mask that keeps (0, 0), and about
+ * every stage's own state s_i = (w, theta)_i
+ *     dN_w     = -M       [u dw_x + v dw_y + du w_x + dv w_y]^ + dg^ + M (i kx by - i ky bx) dtheta^
+ *     dN_theta = -M_theta [u dtheta_x + v dtheta_y + du (theta_x + Gx) + dv (theta_y + Gy)]^
+ * (u, v of s_i with the means; du^ = i ky dw^ / |k|^2, dv^ = -i kx dw^ / |k|^2: no mean flow, no (0, 0) mode in dw^; the mean of dtheta is
+ * carried unchanged and acts on nothing; the scalar has no source and takes no kick, and neither does the perturbation).  The pair rides in
+ * the scalar step's launches (G fields 6-11, Ph fields 2 and 3): still 8 launches per step plus one per call, nothing stored per step.
+ * what, that, dwhat, dthat: float32 [batch][my1][nx][2], all advanced in place.  (what, that) come out BITWISE as from the forward call the
+ * other arguments name -- nns_spec_ns_step_linear_f32 (lin: its table; nu and drag are then ignored), nns_spec_ns_step_stochastic_f32 (amp,
+ * clock, ids all non-NULL; all NULL: no noise, seed ignored), nns_spec_ns_step_buoyant_f32 (b != 0), else nns_spec_ns_step_scalar_f32 -- the
+ * advance of clock included.  With b = (0, 0), dwhat comes out bitwise as from nns_spec_ns_step_tangent_f32 on the flow alone.  dghat as there.
+ * Linear in (dwhat, dthat, dghat) exactly for powers of two; a grid's result does not depend on its batch neighbours; nsteps steps in one
+ * call are bitwise nsteps calls of one step.  work: nns_spec_ns_scalar_tangent_workspace bytes (20 compacted fields, >= every other step's
+ * workspace but the adjoints' and nns_spec_ns_tangents_workspace).  No allocation, no host synchronisation (capturable).  Not built: several
+ * tangents on one base with a scalar.  Errors, all before any launch: those of the forward call, plus NNS_ERR_INVALID_ARG for a NULL that,
+ * dwhat or dthat and for dgbatch not 0 without dghat, 1 or batch with it, and NNS_ERR_WORKSPACE below nns_spec_ns_scalar_tangent_workspace. */
+int nns_spec_ns_scalar_tangent_workspace(int batch, int nx, int ny, size_t* bytes);
+int nns_spec_ns_step_scalar_tangent_f32(float* what, float* that, float* dwhat, float* dthat, const float* mean, const float* ghat, int gbatch,
+                                        const float* dghat, int dgbatch, void* work, size_t work_bytes, int batch, int nx, int ny, double Lx,
+                                        double Ly, double dt, double nu, double drag, double kappa, double gx, double gy, double bx, double by,
+                                        const float* lin, const float* amp, unsigned long long seed, long long* clock, const int* ids,
+                                        int nsteps, void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

@@ -1,7 +1,9 @@
 // One field's pass through a column tile of ps_col_kernel (pspec_kernels.hip), which includes this text once per field with TH in scope:
 // TH = false the vorticity (Ph field 0, W / A, G fields 0..3), TH = true the scalar (Ph field 1, theta^ / A_theta, G fields 4 and 5), TG = true
 // (TH = false) the tangent (Ph field 1, dw^ / dA with the vorticity's factors and mask, dg^ where the vorticity adds g^, no kick, no mean
-// flow, its four spectra to G fields 4..7).  Plain
+// flow, its four spectra to G fields 4..7).  TANSC (a PsScalar and a PsTangentScalar in the pack: the tangent of the scalar system) has four
+// fields: the vorticity, the scalar, then TG alone on Ph field 2 and G fields 6..9 and TH with TG, the scalar's perturbation: Ph field 3,
+// dtheta^ / dA_theta with E_theta and the mask that keeps (0, 0), no g^, no dg^, no kick, zero means, its gradient to G fields 10 and 11.  Plain
 // text rather than a function or a lambda: the unscalared kernels then compile to the instructions they had before there was a scalar
 // (a lambda's body is optimised on its own before it is inlined, and came out a few instructions and registers different).
 // STOCH (ps_col_kernel's note) is false in every kernel without a PsStoch argument, whose text below is then what it was.
@@ -10,9 +12,10 @@
 // The staged forward transform and the field emit are text of their own (pspec_stage.inc, pspec_field.inc), shared with ps_col_adj_kernel and
 // ps_transfer_kernel; the tile's names (lok, lj, wbase, sok, ...) are those of pspec_col_tile.inc.
 {
-        const float2* ph = TH || TG ? Ph + a.fstride : Ph;
-        float2* Ws = TG ? tg.dW : TH ? Th : W;
-        float2* As = TG ? tg.dA : TH ? At : A;
+        constexpr int PF = TANSC ? (TG ? 2 : 0) + (TH ? 1 : 0) : TH || TG ? 1 : 0;     // the field of Ph this pass consumes
+        const float2* ph = PF == 0 ? Ph : PF == 1 ? Ph + a.fstride : Ph + PF * a.fstride;
+        float2* Ws = TG ? (TH ? dTh : tg.dW) : TH ? Th : W;
+        float2* As = TG ? (TH ? dAt : tg.dA) : TH ? At : A;
         cf y[16];
         if constexpr (S == 0) {
 #pragma unroll
@@ -42,11 +45,14 @@
                     em1 = expm1f(x); em2 = expm1f(2.f * x);
                 }
                 cf n = keep ? cf{-z[m].x, -z[m].y} : cf{0.f, 0.f};
+                if constexpr (TH && TG) {               // dN_theta has no (0, 0) mode (div u = 0, du has no mean to meet G): exactly, not to rounding,
+                    if ((mx | lj) == 0) n = {0.f, 0.f}; // so the mean of dtheta is carried bit for bit
+                }
                 if constexpr (FORCED && !TH && !TG) {
                     const float2 g = gok ? fc.g[gbase + e] : make_float2(0.f, 0.f);
                     if (keep) n = {n.x + g.x, n.y + g.y};
                 }
-                if constexpr (TG) {                     // the source's perturbation, where the vorticity adds g^; the unforced base has none of its own
+                if constexpr (TG && !TH) {              // the source's perturbation, where the vorticity adds g^; the unforced base has none of its own
                     const float2 g = dgok ? tg.dg[dgbase + e] : make_float2(0.f, 0.f);
                     if (keep) n = {n.x + g.x, n.y + g.y};
                 }
@@ -94,12 +100,14 @@
         if (S < 4 || emit) {
             const float U0 = !TH && !TG && lok ? mean[2 * lb] : 0.f, V0 = !TH && !TG && lok ? mean[2 * lb + 1] : 0.f;
             auto field = [&](auto fc) {
-                constexpr int F = decltype(fc)::value, FK = TG ? F - 4 : F;      // the tangent's four spectra go to G fields 4-7
+                constexpr int F = decltype(fc)::value, FK = TG && !TH ? F - (TANSC ? 6 : 4) : F;      // the tangent's four spectra go to G fields 4-7 (TANSC: 6-9)
                 int te = tv;
                 asm volatile("" : "+v"(te), "+v"(y[0].x));
 #include "pspec_field.inc"
             };
-            if constexpr (TG) static_for<4, 8>(field);
+            if constexpr (TG && TH) static_for<10, 12>(field);
+            else if constexpr (TG && TANSC) static_for<6, 10>(field);
+            else if constexpr (TG) static_for<4, 8>(field);
             else if constexpr (TH) static_for<4, 6>(field);
             else static_for<0, 4>(field);
         } else {

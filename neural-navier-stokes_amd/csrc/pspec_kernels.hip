@@ -117,6 +117,22 @@
 // of the K members per grid (float64, ps_diag_kernel's fixed order of summation) and ps_tangent_combine_kernel the in-place triangular
 // recombination d_k <- sum_{l <= k} C[l][k] d_l: the two halves of a Cholesky QR, whose K x K algebra is the caller's.
 //
+// Forward mode of the scalar and the buoyant step (nns_spec_ns_step_scalar_tangent_f32; restatement: tests/pspec_scalar_tangent_oracle.py): one
+// system (w^, theta^), one tangent (dw^, dtheta^), the same four stages on the pair with dw^ under the vorticity's factors and mask and
+// dtheta^ under the scalar's real E_theta and the mask that keeps (0, 0), and about every stage's own state
+//     dN_w = -M [u dw_x + v dw_y + du w_x + dv w_y]^ + dg^ + M (i kx by - i ky bx) dtheta^
+//     dN_theta = -M_theta [u dtheta_x + v dtheta_y + du (theta_x + Gx) + dv (theta_y + Gy)]^
+// The pair rides in the scalar step's launches: ps_row_tan_scalar_kernel<ny, BUOYANT> (its note: seven inverse and four forward transforms,
+// three lines live; G fields 0-5 the base's, 6-11 the perturbation's; Ph fields 0, 1 the base's products in ps_row_kernel's arithmetic, 2, 3 the
+// linearised ones), and a PsScalar, a PsTangent and a PsTangentScalar together in ps_col_kernel's pack (TANSC) run pspec_col_pass.inc four
+// times per tile: w^, theta^, dw^ (TG: Ph field 2, G fields 6-9) and dtheta^ (TH with TG: Ph field 3, G fields 10 and 11, no g^, no dg^, no kick,
+// zero means; dN_theta's (0, 0) mode, which vanishes identically, is set to zero, so the mean of dtheta is carried bit for bit) -- stage 0,
+// the forced stages 1-4, the LINEAR stages 1-3, the STOCH stages 1 and 4.  These kernels are instantiated in pspec_scalar_tangent.hip (this
+// text under PSPEC_SCALAR_TANGENT_TU; ps_scalar_tangent_col / ps_scalar_tangent_row are the way in).  Still 8 launches per step plus one per call, one driver
+// (spec_ns_step), one more row of PsLayout (4 accumulators, 12 G, 4 Ph: 20 compacted fields); the base is bitwise the step without the
+// perturbation, with b = 0 dw^ is bitwise the flow tangent's, and every other kernel keeps its name and its code.  Registers and times:
+// profiles/pspec_scalar_tangent_isa.txt (no scratch), profiles/pspec_scalar_tangent_run.json.  Not built: K tangents with a scalar.
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 //
 // What the row and column kernels share has one copy each: the LDS layout, PsArgs and the row pass's Hermitian fill and kept-mode store in
@@ -127,6 +143,14 @@
 #include "pspec_device.h"
 #include <type_traits>
 #include <cmath>
+
+// The kernels of the scalar system's tangent are instantiated in a translation unit of their own (pspec_scalar_tangent.hip: this text with
+// PSPEC_SCALAR_TANGENT_TU defined, which keeps the host entry points out and these two functions in), so that the two halves compile side by
+// side.  The structs of the anonymous namespace have one text, so they cross as untyped pointers: a (PsArgs), fc (PsForce or NULL), sc
+// (PsScalar), st (PsStoch or NULL), li (PsLinear or NULL), tg (PsTangent), tt (PsTangentScalar); gr: a PsBuoyGrad (buoyant) or a PsGrad.
+int ps_scalar_tangent_col(int nx, int S, const void* Ph, void* G, void* W, void* A, const float* mean, const void* a, int emit, const void* fc,
+                          const void* sc, void* stream, const void* st, const void* li, const void* tg, const void* tt);
+int ps_scalar_tangent_row(int ny, const void* G, void* Ph, const void* a, void* stream, const void* gr, int buoyant);
 
 namespace {
 
@@ -159,11 +183,15 @@ struct PsStoch {          // the last argument of the STOCH column kernels (stag
 struct PsLinear {         // the argument of the LINEAR column kernels (stages 1-3 of a linear step), after PsScalar and before PsStoch
     const float2* lin;    // (Re, Im)(lambda dt / 2) [my1][nx], the layout of one grid of W, shared by the batch
 };
-struct PsTangent {        // the first extra argument of the TANGENT column kernels (nns_spec_ns_step_tangent_f32); never with a PsScalar or a PsKeep
+struct PsTangent {        // the first extra argument of the TANGENT column kernels (nns_spec_ns_step_tangent_f32); after a PsScalar only with a PsTangentScalar, never with a PsKeep
     float2* dW;           // dw^ [B][my1][nx], the layout of W: the tangent spectrum, advanced with the vorticity's own factors and mask
     float2* dA;           // its Lawson accumulator
     const float2* dg;     // dg^ [dgbatch][my1][nx], the perturbation of the source, or NULL
     int dshared;          // 1: one dg^ for every grid; 0: one per grid
+};
+struct PsTangentScalar {  // follows a PsScalar and a PsTangent in the pack (nns_spec_ns_step_scalar_tangent_f32): the scalar's perturbation; never with a PsKeep or a PsTangents
+    float2* dT;           // dtheta^ [B][my1][nx], the layout of W: advanced with the scalar's E_theta and the mask that keeps (0, 0)
+    float2* dAt;          // its Lawson accumulator
 };
 struct PsTangents {       // the first extra argument of the TANGENTS column kernels (nns_spec_ns_step_tangents_f32): K tangents on one base; never with a PsScalar or a PsKeep
     float2* dW;           // dw^ [K][B][my1][nx]: member k at dW + k kstride, each in the layout of W
@@ -360,6 +388,101 @@ __global__ __launch_bounds__(kT) void ps_row_tan_kernel(const float2* __restrict
     }
 }
 
+// The row pass of the tangent of the scalar system (nns_spec_ns_step_scalar_tangent_f32; restatement: tests/pspec_scalar_tangent_oracle.py):
+// ps_row_tan_kernel's twin, as ps_row_kernel<N, true, BUOYANT> is ps_row_kernel<N>'s.  G fields 0-5 are the base's (u, v, w_x, w_y, theta_x,
+// theta_y), 6-11 the perturbation's (du, dv, dw_x, dw_y, dtheta_x, dtheta_y: no mean flow); Ph fields 0 and 1 take the base's two products,
+// spelt with ps_row_kernel<N, true, BUOYANT>'s arithmetic so that the base stays bitwise the step, 2 and 3 the linearised ones,
+//     u dw_x + v dw_y + du w_x + dv w_y     and     u dtheta_x + v dtheta_y + du (theta_x + Gx) + dv (theta_y + Gy).
+// BUOYANT adds c4 G10 + c5 G11 on the kept modes to the first on its way to Ph, the way it adds G4, G5 to the base's.
+// The order taken: SEVEN inverse transforms (du + i dv twice) and four forward ones, with three complex lines live at any moment, as in
+// ps_row_tan_kernel: u + i v stays, the second line holds a gradient of the base (grad w, then grad theta) until du, dv have turned it into 16
+// reals, the third is the line in flight.  Six inverse transforms are the minimum, but they want a fourth line while grad theta comes in
+// (u + i v, du + i dv, the packed partial products, the incoming line): 32 more registers across a transform in a kernel that runs two waves
+// per SIMD either way, for one transform in eleven whose input (G fields 6 and 7 of the row) was read a few hundred instructions before.
+template <int N, bool BUOYANT>
+__global__ __launch_bounds__(kT) void ps_row_tan_scalar_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a,
+                                                               std::conditional_t<BUOYANT, PsBuoyGrad, PsGrad> gr) {
+    using L = PsLds<N>;
+    constexpr int TPF = L::TPF;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const cf* tab = ps_tables<N>(smem);
+    unsigned char* lines = smem + L::TAB_BYTES;
+    const int my1 = a.my1;
+    const long niter = (a.nlines + L::LINES - 1) / L::LINES;
+    for (long it = blockIdx.x; it < niter; it += gridDim.x) {
+#include "pspec_row_line.inc"
+        cf zu[16], zw[16], zd[16];
+        ps_row_load2<N>(g0, g0 + a.fstride, tid, my1, zu);                           // u + i v: stays
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 2 * a.fstride, g0 + 3 * a.fstride, tid, my1, zw);       // w_x + i w_y: stays until du, dv have met it
+        fft_line<float, N, true>(zw, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zd[m] = {zu[m].x * zw[m].x + zu[m].y * zw[m].y, 0.f};        // u w_x + v w_y
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tid);
+        if constexpr (BUOYANT) {                                 // -ny (by theta_x - bx theta_y)^ on the kept modes, as in ps_row_kernel
+            const float2* t4 = g0 + 4 * a.fstride;
+            const float2* t5 = g0 + 5 * a.fstride;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int e = tid + TPF * m;
+                if (e < my1) {
+                    const float2 p = t4[e], q = t5[e];
+                    zd[m] = {fmaf(gr.c4, p.x, fmaf(gr.c5, q.x, zd[m].x)), fmaf(gr.c4, p.y, fmaf(gr.c5, q.y, zd[m].y))};
+                }
+            }
+        }
+        ps_row_store<N>(zd, Ph + (size_t)row * my1, tid, my1, valid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 6 * a.fstride, g0 + 7 * a.fstride, tid, my1, zd);       // du + i dv
+        fft_line<float, N, true>(zd, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zw[m].x = zd[m].x * zw[m].x + zd[m].y * zw[m].y;             // du w_x + dv w_y: w_x, w_y leave
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 8 * a.fstride, g0 + 9 * a.fstride, tid, my1, zd);       // dw_x + i dw_y
+        fft_line<float, N, true>(zd, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zd[m] = {fmaf(zu[m].x, zd[m].x, fmaf(zu[m].y, zd[m].y, zw[m].x)), 0.f};   // + u dw_x + v dw_y
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tid);
+        if constexpr (BUOYANT) {                                 // the buoyancy of the scalar's perturbation: G fields 10 and 11 of the row
+            const float2* t4 = g0 + 10 * a.fstride;
+            const float2* t5 = g0 + 11 * a.fstride;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int e = tid + TPF * m;
+                if (e < my1) {
+                    const float2 p = t4[e], q = t5[e];
+                    zd[m] = {fmaf(gr.c4, p.x, fmaf(gr.c5, q.x, zd[m].x)), fmaf(gr.c4, p.y, fmaf(gr.c5, q.y, zd[m].y))};
+                }
+            }
+        }
+        ps_row_store<N>(zd, Ph + 2 * a.fstride + (size_t)row * my1, tid, my1, valid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 4 * a.fstride, g0 + 5 * a.fstride, tid, my1, zw);       // theta_x + i theta_y: stays until du, dv have met it
+        fft_line<float, N, true>(zw, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zd[m] = {zu[m].x * (zw[m].x + gr.gx) + zu[m].y * (zw[m].y + gr.gy), 0.f};   // u (theta_x + Gx) + v (theta_y + Gy)
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tid);
+        ps_row_store<N>(zd, Ph + a.fstride + (size_t)row * my1, tid, my1, valid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 6 * a.fstride, g0 + 7 * a.fstride, tid, my1, zd);       // du + i dv once more
+        fft_line<float, N, true>(zd, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zw[m].x = zd[m].x * (zw[m].x + gr.gx) + zd[m].y * (zw[m].y + gr.gy);   // du (theta_x + Gx) + dv (theta_y + Gy)
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 10 * a.fstride, g0 + 11 * a.fstride, tid, my1, zd);     // dtheta_x + i dtheta_y
+        fft_line<float, N, true>(zd, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zd[m] = {fmaf(zu[m].x, zd[m].x, fmaf(zu[m].y, zd[m].y, zw[m].x)), 0.f};   // + u dtheta_x + v dtheta_y
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tid);
+        ps_row_store<N>(zd, Ph + 3 * a.fstride + (size_t)row * my1, tid, my1, valid);
+    }
+}
+
 // The row pass of K tangents on one base (nns_spec_ns_step_tangents_f32).  u + i v and w_x + i w_y are transformed once and stay for the whole
 // row; the base's product leaves first (Ph field 0, ps_row_kernel's arithmetic).  Then a run-time loop over the members: du + i dv (G fields
 // 4+4k, 5+4k), the 16 reals du w_x + dv w_y (zp: w_x, w_y must survive for the next member, so they are not overwritten as in
@@ -425,10 +548,13 @@ __global__ __launch_bounds__(kT) void ps_row_tans_kernel(const float2* __restric
 // STAGES (a PsKeep ends the pack, after the PsLinear of a linear step; S = 1..3): the next stage's input spectrum is also stored, lane-owned and coalesced like W / A, for the
 // adjoint (ps_col_adj_kernel) to linearise about; the arithmetic is untouched, so the recomputed stages are the forward's bits.  With a scalar
 // the pack ends in a PsKeepScalar after the PsScalar, and theta^'s next stage input is stored as well (ps_col_adj_kernel with a PsAdjScalar).
-// TANGENT (a PsTangent first in the pack, where a PsScalar would be; never with one or with a PsKeep): after the vorticity's work on a tile the
+// TANGENT (a PsTangent first in the pack, where a PsScalar would be; with one only in the TANSC form below, never with a PsKeep): after the vorticity's work on a tile the
 // same text runs once more on the perturbation dw^: Ph's second field, dw^ / dA with the VORTICITY's factors (hdrag and the LINEAR complex ones
 // included) and mask, dg^ where the vorticity adds g^ (also under an unforced base, whose own arithmetic stays the unforced kernel's), no kick
 // and no step count of its own, then its velocity and gradient as G fields 4-7 with zero means.  The vorticity's arithmetic is untouched.
+// TANSC (a PsScalar, a PsTangent and a PsTangentScalar, in that order; never with a PsKeep or a PsTangents): the tangent of the system with a
+// scalar.  Four passes per tile: the vorticity, the scalar, the TG text on dw^ (Ph field 2, G fields 6-9) and the TH text with TG on dtheta^ /
+// dA_theta: Ph field 3, E_theta and the mask that keeps (0, 0), no g^, no dg^, no kick, zero means, i kx dtheta^, i ky dtheta^ to G fields 10, 11.
 // TANGENTS (a PsTangents in the PsTangent's place; never with a PsScalar or a PsKeep): the TG text runs K times in a run-time loop, turn k on
 // dW + k kstride / dA + k kstride, Ph field 1+k and G fields 4+4k .. 7+4k, with no dg^.  The text sees member k under the names it has for
 // the one tangent (Ph, G and tg are shadowed by member k's in the loop's scope), so it is the same text and member k's bits are the TANGENT kernel's.
@@ -441,11 +567,13 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     constexpr bool LINEAR = (std::is_same_v<Sc, PsLinear> || ... || false);
     constexpr bool TANGENT = (std::is_same_v<Sc, PsTangent> || ... || false);
     constexpr bool TANGENTS = (std::is_same_v<Sc, PsTangents> || ... || false);
+    constexpr bool TANSC = (std::is_same_v<Sc, PsTangentScalar> || ... || false);
     constexpr bool KEEP_W = (std::is_same_v<Sc, PsKeep> || ... || false), KEEP_WT = (std::is_same_v<Sc, PsKeepScalar> || ... || false);
     constexpr bool STAGES = KEEP_W || KEEP_WT;
-    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (TANGENT ? 1 : 0) + (TANGENTS ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0) + (STAGES ? 1 : 0),
+    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (TANGENT ? 1 : 0) + (TANGENTS ? 1 : 0) + (TANSC ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0) + (STAGES ? 1 : 0),
                   "PsScalar is the SCALAR kernel's argument (PsTangent the TANGENT kernel's), PsLinear after it the LINEAR kernel's, PsStoch or the PsKeep last");
-    static_assert(!TANGENT || (!SCALAR && !STAGES), "the tangent of the scalar system is not built, and the adjoint's recomputation carries no tangent");
+    static_assert(!TANGENT || (SCALAR == TANSC && !STAGES), "the tangent of the scalar system takes a PsScalar, a PsTangent and a PsTangentScalar, and the adjoint's recomputation carries no tangent");
+    static_assert(!TANSC || (SCALAR && TANGENT), "the PsTangentScalar follows a PsScalar and a PsTangent");
     static_assert(!TANGENTS || (!SCALAR && !STAGES && !TANGENT), "K tangents: as the one tangent, and never beside it");
     static_assert(!STAGES || (S >= 1 && S <= 3 && KEEP_WT == SCALAR && !STOCH),
                   "the stage store is that of stages 1-3 of the steady and the linear forms: a PsKeep without a scalar, a PsKeepScalar with one");
@@ -484,6 +612,12 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     if constexpr (LINEAR) lin = pick<PsLinear>(sc...).lin;
     [[maybe_unused]] PsTangent tg{};
     if constexpr (TANGENT) tg = pick<PsTangent>(sc...);
+    [[maybe_unused]] float2* dTh = nullptr;
+    [[maybe_unused]] float2* dAt = nullptr;
+    if constexpr (TANSC) {
+        const PsTangentScalar tt = pick<PsTangentScalar>(sc...);
+        dTh = tt.dT; dAt = tt.dAt;
+    }
     [[maybe_unused]] float2* stage_out = nullptr;
     [[maybe_unused]] float2* tstage_out = nullptr;
     if constexpr (KEEP_W) stage_out = pick<PsKeep>(sc...).stage;
@@ -523,6 +657,10 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
         }
         if constexpr (TANGENT) {
             constexpr bool TH = false, TG = true;
+#include "pspec_col_pass.inc"
+        }
+        if constexpr (TANSC) {
+            constexpr bool TH = true, TG = true;
 #include "pspec_col_pass.inc"
         }
         if constexpr (TANGENTS) {
@@ -1218,6 +1356,16 @@ int launch_row_tan(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s) 
     return check_launch("spec_ns tangent row pass");
 }
 
+// gr: a PsGrad (the passive scalar's tangent) or a PsBuoyGrad (the buoyant one's)
+template <int N, typename Gr>
+int launch_row_tan_scalar(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s, Gr gr) {
+    constexpr bool BU = std::is_same_v<Gr, PsBuoyGrad>;
+    constexpr auto kern = ps_row_tan_scalar_kernel<N, BU>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a, gr);
+    return check_launch(BU ? "spec_ns buoyant tangent row pass" : "spec_ns scalar tangent row pass");
+}
+
 template <int N>
 int launch_row_tans(const float2* G, float2* Ph, const PsArgs& a, int K, hipStream_t s) {
     constexpr auto kern = ps_row_tans_kernel<N>;
@@ -1227,18 +1375,19 @@ int launch_row_tans(const float2* G, float2* Ph, const PsArgs& a, int K, hipStre
 }
 
 // The column kernel of stage S whose argument pack ends in x...: a PsScalar (the SCALAR kernels), a PsTangent or a PsTangents, a PsLinear, a PsStoch, in that order, each or
-// none.  fc is read only by the FORCED kernels.
+// none; a PsTangentScalar follows a PsScalar and a PsTangent.  fc is read only by the FORCED kernels.
 template <int N, int S, bool FORCED, typename... X>
 int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
                hipStream_t s, X... x) {
     constexpr bool SC = has<PsScalar, X...>, LI = has<PsLinear, X...>, ST = has<PsStoch, X...>, KE = has<PsKeep, X...> || has<PsKeepScalar, X...>;
-    constexpr bool TA = has<PsTangent, X...>, TS = has<PsTangents, X...>;
+    constexpr bool TA = has<PsTangent, X...>, TS = has<PsTangents, X...>, TT = has<PsTangentScalar, X...>;
     constexpr auto kern = ps_col_kernel<N, S, FORCED, SC, X...>;
     std::conditional_t<FORCED, PsForce, PsNoForce> f{};
     if constexpr (FORCED) f = *fc;
     if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
     hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, f, x...);
     return check_launch(TS       ? "spec_ns tangents column pass"
+                        : TT     ? "spec_ns scalar tangent column pass"
                         : TA     ? "spec_ns tangent column pass"
                         : KE     ? "spec_ns stage-keeping column pass"
                         : LI     ? (SC ? "spec_ns linear scalar column pass" : "spec_ns linear column pass")
@@ -1257,12 +1406,15 @@ int with_stage(int S, F&& f) {
 
 // The one place where a stage's run-time facts become a kernel.  fc == nullptr: the unforced kernels (stage 0 has no other form); sc: the
 // SCALAR ones; li (with fc): a linear step, whose stages 1-3 are the LINEAR kernels (stage 4 applies no factor); st (with fc): a stochastic
-// step, whose stages 1 and 4 are the STOCH kernels; tg (never with sc): the TANGENT ones, of every stage and form; ts (never with sc or tg):
-// the TANGENTS ones, likewise.  The pack grows in the kernel's order, and a form no step has is never named.
+// step, whose stages 1 and 4 are the STOCH kernels; tg (with sc only beside tt): the TANGENT ones, of every stage and form; tt (with sc
+// and tg): those of the scalar system's tangent, which live in pspec_scalar_tangent.hip and are reached through ps_scalar_tangent_col; ts (never with sc or tg): the TANGENTS ones, likewise.  The pack grows in the kernel's order, and a form no step has is never named.
 template <int N>
 int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
                      const PsScalar* sc, hipStream_t s, const PsStoch* st = nullptr, const PsLinear* li = nullptr, const PsTangent* tg = nullptr,
-                     const PsTangents* ts = nullptr) {
+                     const PsTangents* ts = nullptr, const PsTangentScalar* tt = nullptr) {
+#ifndef PSPEC_SCALAR_TANGENT_TU
+    if (tt) return ps_scalar_tangent_col(N, S, Ph, G, W, A, mean, &a, emit, fc, sc, s, st, li, tg, tt);
+#endif
     auto stage = [&](auto stage_c) {
         constexpr int K = decltype(stage_c)::value;
         auto stoch = [&](auto forced, auto... x) {
@@ -1276,7 +1428,11 @@ int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, c
                 if (li) return stoch(forced, x..., *li);
             return stoch(forced, x...);
         };
+#ifdef PSPEC_SCALAR_TANGENT_TU      // this translation unit names the forms with a PsTangentScalar and no other
+        auto scalar = [&](auto forced) { return linear(forced, *sc, *tg, *tt); };
+#else
         auto scalar = [&](auto forced) { return ts ? linear(forced, *ts) : tg ? linear(forced, *tg) : sc ? linear(forced, *sc) : linear(forced); };
+#endif
         if constexpr (K >= 1)
             if (fc) return scalar(std::true_type{});
         return scalar(std::false_type{});
@@ -1347,12 +1503,14 @@ size_t scalar_work_bytes(int batch, int nx, int ny) {
 //   the scalar adjoint:  A, A_theta (wbar and thetabar once the stages are recomputed), G[10], Ph[3] (the recomputation's: 6 and 2), s1, s2, s3
 //                        of w^, then of theta^: 21
 //   the tangent step:    A, dA in A_theta's place, G[8], Ph[2]: 12
+//   the scalar tangent:  A, A_theta, dA, dA_theta, G[12], Ph[4]: 20
 //   K tangents:          A, dA[K], G[4 + 4K], Ph[1 + K]: 6 + 6K (tangents_layout; K = 1 is the tangent step's)
 struct PsLayout {
     int acc, g, ph, keep;
     constexpr int fields() const { return acc + g + ph + keep; }
 };
-constexpr PsLayout kLayFlow{1, 4, 1, 0}, kLayScalar{2, 6, 2, 0}, kLayAdjoint{2, 6, 2, 3}, kLayScalarAdjoint{2, 10, 3, 6}, kLayTangent{2, 8, 2, 0};
+constexpr PsLayout kLayFlow{1, 4, 1, 0}, kLayScalar{2, 6, 2, 0}, kLayAdjoint{2, 6, 2, 3}, kLayScalarAdjoint{2, 10, 3, 6}, kLayTangent{2, 8, 2, 0},
+                   kLayScalarTangent{4, 12, 4, 0};
 
 size_t layout_work_bytes(const PsLayout& lay, int batch, int nx, int ny) {
     const size_t b = work_bytes(batch, nx, ny), st = (size_t)lay.fields() * batch * nx * kept_y(ny) * sizeof(float2);
@@ -1361,6 +1519,7 @@ size_t layout_work_bytes(const PsLayout& lay, int batch, int nx, int ny) {
 size_t adjoint_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayAdjoint, batch, nx, ny); }
 size_t scalar_adjoint_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayScalarAdjoint, batch, nx, ny); }
 size_t tangent_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayTangent, batch, nx, ny); }
+size_t scalar_tangent_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayScalarTangent, batch, nx, ny); }
 constexpr int kMaxTangents = 32;
 constexpr PsLayout tangents_layout(int K) { return PsLayout{1 + K, 4 + 4 * K, 1 + K, 0}; }
 size_t tangents_work_bytes(int batch, int ntan, int nx, int ny) { return layout_work_bytes(tangents_layout(ntan), batch, nx, ny); }
@@ -1403,10 +1562,11 @@ int check_box(const char* what, int nx, int ny, double Lx, double Ly) {
     return check_axes(what, nx, ny);
 }
 
-enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2, kWorkScalarAdjoint = 3, kWorkTangent = 4, kWorkTangents = 5 };      // a bool converts: false the flow's workspace, true the scalar's
+enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2, kWorkScalarAdjoint = 3, kWorkTangent = 4, kWorkTangents = 5, kWorkScalarTangent = 6 };      // a bool converts: false the flow's workspace, true the scalar's
 
 int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int kind, int ntan = 0) {      // ntan: kWorkTangents' K
-    const size_t need = kind == kWorkTangents      ? tangents_work_bytes(batch, ntan, nx, ny)
+    const size_t need = kind == kWorkScalarTangent ? scalar_tangent_work_bytes(batch, nx, ny)
+                        : kind == kWorkTangents    ? tangents_work_bytes(batch, ntan, nx, ny)
                         : kind == kWorkTangent     ? tangent_work_bytes(batch, nx, ny)
                         : kind == kWorkScalarAdjoint ? scalar_adjoint_work_bytes(batch, nx, ny)
                         : kind == kWorkAdjoint     ? adjoint_work_bytes(batch, nx, ny)
@@ -1414,7 +1574,8 @@ int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int k
                                                    : work_bytes(batch, nx, ny);
     if (wbytes < need)
         return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", what, wbytes, need,
-                    kind == kWorkTangents      ? "nns_spec_ns_tangents_workspace"
+                    kind == kWorkScalarTangent ? "nns_spec_ns_scalar_tangent_workspace"
+                    : kind == kWorkTangents    ? "nns_spec_ns_tangents_workspace"
                     : kind == kWorkTangent     ? "nns_spec_ns_tangent_workspace"
                     : kind == kWorkScalarAdjoint ? "nns_spec_ns_scalar_adjoint_workspace"
                     : kind == kWorkAdjoint     ? "nns_spec_ns_adjoint_workspace"
@@ -1508,6 +1669,7 @@ int launch_transfer(const float2* Ph, const float2* W, const float2* Th, float* 
 
 }  // namespace
 
+#ifndef PSPEC_SCALAR_TANGENT_TU
 NNS_API int nns_spec_ns_shells(int nx, int ny, double Lx, double Ly, int* nshell, double* dk) {
     if (!nshell || !dk) return fail(NNS_ERR_INVALID_ARG, "spec_ns_shells: nshell and dk must be non-NULL");
     if (int rc = check_box("spec_ns_shells", nx, ny, Lx, Ly)) return rc;
@@ -1608,26 +1770,30 @@ NNS_API int nns_spec_ns_init_f32(const float* u, const float* v, float* what, fl
 // dwhat != NULL (never with that): the tangent-linear step, the same launches in their TANGENT forms on the tangent layout of work; the choice
 // of the base's kernels is the one made without dwhat, so what comes out bitwise as from that call.  ntan >= 1 (with dwhat, no dghat): dwhat holds
 // ntan tangents [ntan][B][my1][nx] on that one base, the TANGENTS forms on the layout of ntan tangents; ntan == 0: the one tangent's call.
+// dthat != NULL (with that and dwhat, ntan == 0): the tangent of the scalar system, (dw^, dtheta^) in the launches of the scalar step on the
+// 20-field layout; (what, that) come out bitwise as from the call without the perturbation.
 static int spec_ns_step(const char* who, float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work,
                         size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa,
                         double gx, double gy, double bx, double by, int nsteps, void* stream, const PsStoch* st = nullptr,
                         const float* lin = nullptr, float* dwhat = nullptr, const float* dghat = nullptr, int dgbatch = 0,
-                        int ntan = 0) {
+                        int ntan = 0, float* dthat = nullptr) {
     if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
-    if (dwhat && that) return fail(NNS_ERR_UNSUPPORTED, "%s: the tangent of the scalar system is not built", who);
+    if (dwhat && that && (!dthat || ntan)) return fail(NNS_ERR_UNSUPPORTED, "%s: the tangent of the scalar system is not built", who);
     if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
     if (int rc = check_scalar_numbers(who, kappa, gx, gy)) return rc;
     if (int rc = check_buoyancy(who, bx, by)) return rc;
     if (int rc = check_gbatch(who, ghat, gbatch, batch)) return rc;
     if (dghat ? (dgbatch != 1 && dgbatch != batch) : dgbatch != 0)
         return fail(NNS_ERR_INVALID_ARG, "%s: dgbatch = %d must be 0 without dghat, 1 or batch = %d with it", who, dgbatch, batch);
-    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, ntan ? kWorkTangents : dwhat ? kWorkTangent : that ? kWorkScalar : kWorkFlow, ntan)) return rc;
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, ntan ? kWorkTangents : dthat ? kWorkScalarTangent : dwhat ? kWorkTangent : that ? kWorkScalar : kWorkFlow, ntan)) return rc;
     if (nsteps == 0) return NNS_OK;
     hipStream_t s = as_stream(stream);
     float2* W = reinterpret_cast<float2*>(what);
-    const PsWork L(work, batch, nx, ny, ntan ? tangents_layout(ntan) : dwhat ? kLayTangent : that ? kLayScalar : kLayFlow, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);
-    const PsTangent tangent{reinterpret_cast<float2*>(dwhat), L.At, reinterpret_cast<const float2*>(dghat), dgbatch == 1 && batch > 1 ? 1 : 0};
+    const PsWork L(work, batch, nx, ny, ntan ? tangents_layout(ntan) : dthat ? kLayScalarTangent : dwhat ? kLayTangent : that ? kLayScalar : kLayFlow, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);
+    const PsTangent tangent{reinterpret_cast<float2*>(dwhat), dthat ? L.A + 2 * L.col.fstride : L.At, reinterpret_cast<const float2*>(dghat), dgbatch == 1 && batch > 1 ? 1 : 0};
     const PsTangent* tg = dwhat && !ntan ? &tangent : nullptr;
+    const PsTangentScalar tanscalar{reinterpret_cast<float2*>(dthat), L.A + 3 * L.col.fstride};      // the scalar system's: A, A_theta, dA, dA_theta
+    const PsTangentScalar* tt = dthat ? &tanscalar : nullptr;
     const PsTangents tangents{reinterpret_cast<float2*>(dwhat), L.At, L.col.fstride, ntan};      // dA[k] follows A, a field apart like the members
     const PsTangents* ts = ntan ? &tangents : nullptr;
     const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
@@ -1646,12 +1812,13 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
     const PsBuoyGrad buoy{(float)gx, (float)gy, (float)(-(double)ny * by), (float)((double)ny * bx)};
     const PsBuoyGrad* bu = that && (bx != 0.0 || by != 0.0) ? &buoy : nullptr;
     auto col = [&](int S, int emit) {
-        return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, emit, fc, sc, s, stc, li, tg, ts); });
+        return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, emit, fc, sc, s, stc, li, tg, ts, tt); });
     };
     auto row = [&]() {
         return dispatch_pow2(ny, "spec_ns", [&](auto n) {
             constexpr int N = decltype(n)::value;
             if (ts) return launch_row_tans<N>(L.G, L.Ph, L.row, ntan, s);
+            if (tt) return ps_scalar_tangent_row(N, L.G, L.Ph, &L.row, s, bu ? (const void*)bu : (const void*)&grad, bu != nullptr);
             if (tg) return launch_row_tan<N>(L.G, L.Ph, L.row, s);
             return bu ? launch_row<N>(L.G, L.Ph, L.row, s, *bu) : that ? launch_row<N>(L.G, L.Ph, L.row, s, grad) : launch_row<N>(L.G, L.Ph, L.row, s);
         });
@@ -1737,6 +1904,30 @@ NNS_API int nns_spec_ns_step_tangent_f32(float* what, float* dwhat, const float*
     const PsStoch st{amp, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), clock, ids, 0.f};
     return spec_ns_step("spec_ns_step_tangent", what, nullptr, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, lin ? 0.0 : nu,
                         lin ? 0.0 : drag, 0.0, 0.0, 0.0, 0.0, 0.0, nsteps, stream, noise ? &st : nullptr, lin, dwhat, dghat, dgbatch);
+}
+
+NNS_API int nns_spec_ns_scalar_tangent_workspace(int batch, int nx, int ny, size_t* bytes) {
+    if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_tangent_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
+    if (int rc = check_axes("spec_ns_scalar_tangent_workspace", nx, ny)) return rc;
+    *bytes = scalar_tangent_work_bytes(batch, nx, ny);
+    return NNS_OK;
+}
+
+// The base's kernels are chosen as ops.spec_ns_advance_ chooses its entry: lin the linear step's (nu and drag sit in the table), amp / clock / ids
+// the stochastic one's, b != 0 the buoyant one's, else the scalar one's.
+NNS_API int nns_spec_ns_step_scalar_tangent_f32(float* what, float* that, float* dwhat, float* dthat, const float* mean, const float* ghat,
+                                                int gbatch, const float* dghat, int dgbatch, void* work, size_t work_bytes_, int batch, int nx,
+                                                int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa, double gx,
+                                                double gy, double bx, double by, const float* lin, const float* amp, unsigned long long seed,
+                                                long long* clock, const int* ids, int nsteps, void* stream) {
+    if (!that || !dwhat || !dthat) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_scalar_tangent: that, dwhat and dthat must be non-NULL");
+    const bool noise = amp && clock && ids;
+    if (!noise && (amp || clock || ids))
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_scalar_tangent: amp, clock and ids must be all NULL (no noise) or all non-NULL");
+    const PsStoch st{amp, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), clock, ids, 0.f};
+    return spec_ns_step("spec_ns_step_scalar_tangent", what, that, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt,
+                        lin ? 0.0 : nu, lin ? 0.0 : drag, kappa, gx, gy, bx, by, nsteps, stream, noise ? &st : nullptr, lin, dwhat, dghat, dgbatch,
+                        0, dthat);
 }
 
 NNS_API int nns_spec_ns_tangents_workspace(int batch, int ntan, int nx, int ny, size_t* bytes) {
@@ -2036,3 +2227,29 @@ NNS_API int nns_spec_ns_fields_buoyant_f32(const float* what, const float* that,
     if (!that) return fail(NNS_ERR_INVALID_ARG, "spec_ns_fields_buoyant: NULL pointer or batch < 1");
     return spec_ns_fields("spec_ns_fields_buoyant", what, that, mean, u, v, p, work, work_bytes_, batch, nx, ny, Lx, Ly, rho, bx, by, stream);
 }
+
+#else      // PSPEC_SCALAR_TANGENT_TU: the launches of the scalar system's tangent (declared at the head of this file)
+int ps_scalar_tangent_col(int nx, int S, const void* Ph, void* G, void* W, void* A, const float* mean, const void* a, int emit, const void* fc,
+                          const void* sc, void* stream, const void* st, const void* li, const void* tg, const void* tt) {
+    return dispatch_pow2(nx, "spec_ns", [&](auto n) {
+        return launch_col_stage<decltype(n)::value>(S, static_cast<const float2*>(Ph), static_cast<float2*>(G), static_cast<float2*>(W),
+                                                    static_cast<float2*>(A), mean, *static_cast<const PsArgs*>(a), emit,
+                                                    static_cast<const PsForce*>(fc), static_cast<const PsScalar*>(sc),
+                                                    static_cast<hipStream_t>(stream), static_cast<const PsStoch*>(st),
+                                                    static_cast<const PsLinear*>(li), static_cast<const PsTangent*>(tg), nullptr,
+                                                    static_cast<const PsTangentScalar*>(tt));
+    });
+}
+
+int ps_scalar_tangent_row(int ny, const void* G, void* Ph, const void* a, void* stream, const void* gr, int buoyant) {
+    return dispatch_pow2(ny, "spec_ns", [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        const float2* g = static_cast<const float2*>(G);
+        float2* ph = static_cast<float2*>(Ph);
+        const PsArgs& args = *static_cast<const PsArgs*>(a);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        return buoyant ? launch_row_tan_scalar<N>(g, ph, args, s, *static_cast<const PsBuoyGrad*>(gr))
+                       : launch_row_tan_scalar<N>(g, ph, args, s, *static_cast<const PsGrad*>(gr));
+    });
+}
+#endif

@@ -103,6 +103,8 @@ _SINGLE = {
     'nns_spec_ns_step_operator_adjoint_f32': [_P] * 4 + [_I, _P, _P, _P, _P, _SZ] + [_I] * 3 + [_D] * 8 + [_P, _I, _P, _P],
     'nns_spec_ns_tangent_workspace': [_I, _I, _I, C.POINTER(C.c_size_t)],
     'nns_spec_ns_step_tangent_f32': [_P] * 4 + [_I, _P, _I, _P, _SZ] + [_I] * 3 + [_D] * 5 + [_P, _P, C.c_uint64, _P, _P, _I, _P],
+    'nns_spec_ns_scalar_tangent_workspace': [_I, _I, _I, C.POINTER(C.c_size_t)],
+    'nns_spec_ns_step_scalar_tangent_f32': [_P] * 6 + [_I, _P, _I, _P, _SZ] + [_I] * 3 + [_D] * 10 + [_P, _P, C.c_uint64, _P, _P, _I, _P],
     'nns_spec_ns_tangents_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
     'nns_spec_ns_step_tangents_f32': [_P, _P, _I, _P, _P, _I, _P, _SZ] + [_I] * 3 + [_D] * 5 + [_P, _P, C.c_uint64, _P, _P, _I, _P],
     'nns_spec_ns_tangent_gram_f64': [_P, _I, _P] + [_I] * 3 + [_D, _D, _P],

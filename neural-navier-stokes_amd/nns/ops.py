@@ -1248,6 +1248,38 @@ def spec_ns_step_tangent_(what, dwhat, mean, ghat, dghat, work, ny, Lx, Ly, dt, 
     return what, dwhat
 
 
+# forward mode of the scalar and the buoyant step (nns_spec_ns_step_scalar_tangent_f32)
+def spec_ns_scalar_tangent_workspace(B, nx, ny):
+    """Bytes of the workspace spec_ns_step_scalar_tangent_ needs for B grids of nx x ny (>= spec_ns_scalar_workspace and spec_ns_tangent_workspace)."""
+    return _query_bytes('nns_spec_ns_scalar_tangent_workspace', int(B), int(nx), int(ny))
+
+
+def spec_ns_step_scalar_tangent_(what, that, dwhat, dthat, mean, ghat, dghat, work, ny, Lx, Ly, dt, nu, drag, kappa, grad=(0.0, 0.0),
+                                 buoyancy=(0.0, 0.0), lin=None, noise=None, nsteps=1):
+    """nsteps steps of the system (what, that) and of a perturbation (dwhat, dthat) carried along with it, all four in place: (what, that)
+    bitwise as by spec_ns_advance_ with the same arguments, (dwhat, dthat) <- J (dwhat, dthat) + (the response to) dghat, the Jacobian of
+    those steps.  dwhat, dthat: float32 like what; dghat: the vorticity source's perturbation, float32 [1 or B, my1, nx, 2] or None.
+    work: spec_ns_scalar_tangent_workspace bytes.  8 launches per step and one per call, no allocation, no host synchronisation: capturable."""
+    who = 'spec_ns_step_scalar_tangent'
+    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
+    _spec_ns_same(who, that, what)
+    _spec_ns_same(who, dwhat, what, 'dwhat')
+    _spec_ns_same(who, dthat, what, 'dthat')
+    gbatch, dgbatch = _spec_ns_force(who, ghat, what), _spec_ns_force(who, dghat, what)
+    if lin is not None:
+        _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), what.device)
+    amp, seed, clock, ids = noise or (None, 0, None, None)
+    if noise is not None:
+        _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
+    (gx, gy), (bx, by) = grad, buoyancy
+    check(_lib.lib().nns_spec_ns_step_scalar_tangent_f32(_p(what), _p(that), _p(dwhat), _p(dthat), _p(mean), _pn(ghat), gbatch, _pn(dghat),
+                                                         dgbatch, _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt),
+                                                         float(nu), float(drag), float(kappa), float(gx), float(gy), float(bx), float(by),
+                                                         _pn(lin), _pn(amp), int(seed), _pn(clock), _pn(ids), int(nsteps), _stream()),
+          'nns_spec_ns_step_scalar_tangent_f32')
+    return what, that, dwhat, dthat
+
+
 # K tangents on one base and their orthonormalisation (nns_spec_ns_step_tangents_f32, nns_spec_ns_tangent_gram_f64, nns_spec_ns_tangent_combine_f32)
 SPEC_NS_MAX_TANGENTS = 32
 

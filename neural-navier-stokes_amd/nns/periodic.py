@@ -29,6 +29,7 @@ float64 by an oracle under tests/:
   * their ``operator``: gradients in nu, drag, nu_h, mu, beta, lambda(k)   pspec_operator_grad_oracle.py
   * forward mode, ``step_tangent`` / ``evolve_tangent`` / ``lyapunov_exponent``   pspec_tangent_oracle.py
   * K tangents on one base, ``step_tangents`` / ``lyapunov_spectrum``              pspec_lyapunov_oracle.py
+  * forward mode with a scalar, ``step_tangent_scalar`` / ``evolve_tangent_scalar``  pspec_scalar_tangent_oracle.py
 Which C entry a step or an adjoint takes is decided in one place each, ops.spec_ns_advance_ and ops.spec_ns_adjoint_.
 """
 import collections
@@ -379,10 +380,19 @@ class PeriodicSolver(object):
     K, so the y-transforms and the passes through a column tile tend to one half of K separate calls' (still 8 launches per step).
     ``tangent_gram`` is their Gram matrix in the energy inner product, ``orthonormalize_tangents`` a Cholesky QR done twice (Gram and
     recombination in HIP, the K x K algebra in torch float64 on the device), ``lyapunov_spectrum`` the first K finite-time exponents with
-    the backward Lyapunov vectors left in dwhat, and the module's ``kaplan_yorke_dimension`` the attractor's dimension from them.  Not
-    built: the tangent of the scalar and
-    the Boussinesq system (a state that carries a scalar is refused), the tangent in ``operator``, a source perturbation per tangent, covariant vectors, a
-    ``jvp`` hook on the autograd node for ``torch.autograd.forward_ad``, and reverse mode through the tangent (Hessian-vector products).
+    the backward Lyapunov vectors left in dwhat, and the module's ``kaplan_yorke_dimension`` the attractor's dimension from them.
+    With a scalar (passive or Boussinesq) the perturbation is the pair (dw^, dtheta^) of the one system, under names of its own as
+    ``advance_scalar`` stands beside ``advance``: ``step_tangent_scalar(state, dwhat, dthat, nsteps, dforcing=)`` advances (what, that)
+    bitwise as ``step`` does -- passive, buoyant, linear or stochastic -- and the pair by the Jacobian of those steps, with
+    dN_w = -M [u dw_x + v dw_y + du w_x + dv w_y]^ + dg^ + M (i kx by - i ky bx) dtheta^ and
+    dN_theta = -M_theta [u dtheta_x + v dtheta_y + du (theta_x + Gx) + dv (theta_y + Gy)]^ about every stage's own state; dw^ takes the
+    vorticity's factors, dtheta^ the scalar's real E_theta and keeps its (0, 0) mode, which is carried unchanged and acts on nothing
+    (tests/pspec_scalar_tangent_oracle.py).  The pair rides in the scalar step's launches (still 8 per step).  ``evolve_tangent_scalar`` /
+    ``evolve_velocity_tangent_scalar`` are the field-level forms, ``lyapunov_exponent_scalar`` the leading exponent in the norm
+    E(dw) + scalar_weight 1/2 <dtheta'^2>.  ``step_tangent``, ``lyapunov_exponent``, ``step_tangents`` and ``lyapunov_spectrum`` keep refusing
+    a state that carries a scalar.  Not built: K tangents with a scalar (``step_tangents`` / ``lyapunov_spectrum`` on such a state), the
+    tangent in ``operator``, a source perturbation per tangent, covariant vectors, a ``jvp`` hook on the autograd node for
+    ``torch.autograd.forward_ad``, and reverse mode through the tangent (Hessian-vector products).
 
     By wavenumber: the stored modes are binned into shells of width dk = min(2 pi / Lx, 2 pi / Ly) centred on k_s = s dk (``shells()``; an
     elongated box has many).  ``spectrum(state)`` gives energy E(s), enstrophy Z(s), the force's injection F(s) and the scalar's variance V(s),
@@ -717,7 +727,7 @@ class PeriodicSolver(object):
         self._state(state)
         if state.that is not None:
             raise NotImplementedError("%s: the tangent of the scalar system is not built yet: the state carries a scalar (passive or buoyant); "
-                                      "a state without one is stepped as by step" % who)
+                                      "a state without one is stepped as by step (use step_tangent_scalar)" % who)
         if not isinstance(dwhat, torch.Tensor):
             raise TypeError("%s: dwhat must be a torch tensor, got %s" % (who, type(dwhat).__name__))
         if dwhat.dtype != torch.float32 or tuple(dwhat.shape) != tuple(state.what.shape) or dwhat.device != state.what.device \
@@ -822,6 +832,129 @@ class PeriodicSolver(object):
             n = min(every, nsteps - done)
             self.step_tangent(state, dwhat, n)
             after = energy()
+            total += 0.5 * torch.log(after / before)
+            before = rescale(after)
+            done += n
+        return total / (nsteps * self.dt)
+
+    # ---- forward mode of the system with a scalar
+    def _tangent_pair(self, who, dwhat, dthat, state):
+        """The checked tangent spectra (dwhat, dthat) of ``who`` for this state, which must carry a scalar."""
+        self._state(state)
+        if state.that is None:
+            raise ValueError("%s: the state carries no scalar (build it with init(u, v, theta) on a solver with kappa); "
+                             "without one use %s" % (who, who.replace('_scalar', '')))
+        for name, d in (('dwhat', dwhat), ('dthat', dthat)):
+            if not isinstance(d, torch.Tensor):
+                raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(d).__name__))
+            if d.dtype != torch.float32 or tuple(d.shape) != tuple(state.what.shape) or d.device != state.what.device or not d.is_contiguous():
+                raise ValueError("%s: %s must be a contiguous float32 %s tensor on the state's device, got %s %s on %s"
+                                 % (who, name, list(state.what.shape), d.dtype, tuple(d.shape), d.device))
+        return dwhat, dthat
+
+    def _launch_tangent_scalar(self, state, dwhat, dthat, nsteps, dghat, force=False):
+        """``_launch_steps`` on a state with a scalar, the pair (dwhat, dthat) riding along: the same force, table and noise, so the base is that step."""
+        ghat = self._force_of(state) if force is False else force
+        lin = self._linear_of(state) if self._linear() else None
+        noise = None
+        if self.stoch_amp is not None:
+            amp, clock, ids = self._noise_of(state)
+            noise = (amp, self.stoch_seed, clock, ids)
+        state.work = self._work(ops.spec_ns_scalar_tangent_workspace, state.batch, state.what.device, have=state.work)
+        ops.spec_ns_step_scalar_tangent_(state.what, state.that, dwhat, dthat, state.mean, ghat, dghat, state.work, self.ny, self.Lx, self.Ly,
+                                         self.dt, self.nu, self.drag, self.kappa, self.scalar_gradient, self.buoyancy, lin, noise, nsteps)
+
+    def step_tangent_scalar(self, state, dwhat, dthat, nsteps=1, dforcing=None):
+        """``step(state, nsteps)`` on a state that carries a scalar -- bitwise, ``state.steps`` and ``state.clock`` included -- with the tangent
+        spectra ``dwhat`` and ``dthat`` (float32 [B, my1, nx, 2], the layout of ``state.what``) advanced in place by the Jacobian of those
+        steps of the system (w^, theta^) and returned as (dwhat, dthat) (the class note, "Forward mode").  Build them with
+        ``init_vorticity(dw).what`` and ``ops.spec_ns_scalar_init``; the mean of dtheta, the (0, 0) entry of dthat, is carried unchanged.
+        ``dforcing`` as in ``step_tangent`` (the scalar has no source).  Grows ``state.work`` to the scalar tangent's workspace on first use
+        (take one step outside before capturing one in a graph); otherwise no allocation without ``dforcing`` and no host synchronisation.
+        ValueError on a state without a scalar."""
+        self._tangent_pair('step_tangent_scalar', dwhat, dthat, state)
+        nsteps = _count('nsteps', nsteps, 0)
+        self._launch_tangent_scalar(state, dwhat, dthat, nsteps, self._dforcing('step_tangent_scalar', dforcing, state))
+        state.steps += nsteps
+        return dwhat, dthat
+
+    def _evolve_tangent_scalar(self, who, state, dstate, nsteps, forcing, dforcing, clock, noise_ids):
+        nsteps = _count('nsteps', nsteps, 1)
+        if state.what.shape != dstate.what.shape:
+            raise ValueError("%s: the fields and their perturbations must share their shape" % who)
+        if forcing is None:
+            ghat = self._force_of(state)
+        else:
+            ghat = self._source_spectrum(self._field('forcing', forcing.detach() if isinstance(forcing, torch.Tensor) else forcing)
+                                         .to(state.what.device), state)
+        if self.stoch_amp is not None:
+            state.clock, state.noise_ids = self._noise_args(clock, noise_ids, state)
+        self._launch_tangent_scalar(state, dstate.what, dstate.that, nsteps, self._dforcing(who, dforcing, state), ghat)
+        state.steps += nsteps
+        return state, PeriodicState(dstate.what, torch.zeros_like(state.mean), state.work, dstate.that)
+
+    def _with_scalar(self, who, state, theta):
+        """``state`` (of init_vorticity) with the scalar theta, as ``evolve`` builds it."""
+        if self.kappa is None:
+            raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use %s"
+                             % (who, who.replace('_scalar', '')))
+        theta = self._field('theta', theta.detach() if isinstance(theta, torch.Tensor) else theta).to(state.what.device).contiguous()
+        if theta.shape[0] != state.batch:
+            raise ValueError("%s: the fields must share their shape" % who)
+        state.that = ops.spec_ns_scalar_init(theta, torch.empty_like(state.what), state.work)
+        return state
+
+    def evolve_tangent_scalar(self, w, theta, dw, dtheta, nsteps=1, mean=None, forcing=None, dforcing=None, clock=0, noise_ids=None):
+        """(w_out, theta_out, dw_out, dtheta_out): the fields after ``nsteps`` steps from (w, theta), bitwise the forward of
+        ``evolve(w, nsteps, theta=theta, ...)``, and the perturbation (dw, dtheta) carried along with them by the Jacobian of those steps
+        (+ the response to ``dforcing``) -- the forward-mode twin of ``evolve`` with a scalar, whose backward gives J^T r.  The arguments of
+        ``evolve_tangent``; the solver needs ``kappa``.  NOT an autograd node: the inputs are detached and nothing is recorded."""
+        who = 'evolve_tangent_scalar'
+        det = lambda a: a.detach() if isinstance(a, torch.Tensor) else a
+        squeeze = isinstance(w, (torch.Tensor, np.ndarray)) and w.ndim == 2
+        state = self._with_scalar(who, self.init_vorticity(det(w), mean), theta)
+        dstate = self._with_scalar(who, self.init_vorticity(det(dw)), dtheta)
+        state, rest = self._evolve_tangent_scalar(who, state, dstate, nsteps, forcing, dforcing, clock, noise_ids)
+        out = self.vorticity(state), self.scalar(state), self.vorticity(rest), self.scalar(rest)
+        return tuple(o[0] for o in out) if squeeze else out
+
+    def evolve_velocity_tangent_scalar(self, u0, v0, theta0, du0, dv0, dtheta0, nsteps=1, forcing=None, dforcing=None, clock=0, noise_ids=None):
+        """``evolve_tangent_scalar`` from and to the velocity: (u, v, theta, du, dv, dtheta) after ``nsteps`` steps; (u, v, theta) are bitwise
+        the forward of ``evolve_velocity(u0, v0, nsteps, theta0=theta0, ...)``.  The perturbation's grid-mean velocity is dropped.  NOT an
+        autograd node: the inputs are detached."""
+        who = 'evolve_velocity_tangent_scalar'
+        if self.kappa is None:
+            raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use evolve_velocity_tangent" % who)
+        det = lambda a: a.detach() if isinstance(a, torch.Tensor) else a
+        squeeze = isinstance(u0, (torch.Tensor, np.ndarray)) and u0.ndim == 2
+        state, dstate = self.init(det(u0), det(v0), det(theta0)), self.init(det(du0), det(dv0), det(dtheta0))
+        state, rest = self._evolve_tangent_scalar(who, state, dstate, nsteps, forcing, dforcing, clock, noise_ids)
+        out = tuple(self.fields(state)[:2]) + (self.scalar(state),) + tuple(self.fields(rest)[:2]) + (self.scalar(rest),)
+        return tuple(o[0] for o in out) if squeeze else out
+
+    def lyapunov_exponent_scalar(self, state, dwhat, dthat, nsteps, renormalize_every, scalar_weight=1.0):
+        """``lyapunov_exponent`` of the system with a scalar, float64 [B] on the device, in the norm E(dw) + scalar_weight 1/2 <dtheta'^2>
+        (``scalar_weight`` > 0; the mean of dtheta does not enter): E is column 0 of ``ops.spec_ns_diag`` of dwhat, the variance column 0 of
+        ``ops.spec_ns_scalar_diag`` of (dwhat, dthat), both summed on the device in float64, and both spectra are rescaled by the one factor
+        after every ``renormalize_every`` steps of ``step_tangent_scalar`` (and at the start).  No host synchronisation."""
+        self._tangent_pair('lyapunov_exponent_scalar', dwhat, dthat, state)
+        nsteps, every = _count('nsteps', nsteps, 1), _count('renormalize_every', renormalize_every, 1)
+        weight = _real('scalar_weight', scalar_weight, '> 0')
+        norm = lambda: (ops.spec_ns_diag(dwhat, None, self.ny, self.Lx, self.Ly)[:, 0]
+                        + weight * ops.spec_ns_scalar_diag(dwhat, dthat, self.ny, self.Lx, self.Ly, self.kappa)[:, 0])
+
+        def rescale(e):                                  # the pair to unit norm; the norm it then has, with the float32 factor as rounded
+            f = torch.rsqrt(e).to(torch.float32)
+            dwhat.mul_(f.reshape(-1, 1, 1, 1))
+            dthat.mul_(f.reshape(-1, 1, 1, 1))
+            return e * f.to(torch.float64) ** 2
+        before = rescale(norm())
+        total = torch.zeros_like(before)
+        done = 0
+        while done < nsteps:
+            n = min(every, nsteps - done)
+            self.step_tangent_scalar(state, dwhat, dthat, n)
+            after = norm()
             total += 0.5 * torch.log(after / before)
             before = rescale(after)
             done += n
