@@ -697,8 +697,8 @@ int nns_spec_ns_tangent_combine_f32(float* dwhat, int ntan, const double* coef, 
  * advance of clock included.  With b = (0, 0), dwhat comes out bitwise as from nns_spec_ns_step_tangent_f32 on the flow alone.  dghat as there.
  * Linear in (dwhat, dthat, dghat) exactly for powers of two; a grid's result does not depend on its batch neighbours; nsteps steps in one
  * call are bitwise nsteps calls of one step.  work: nns_spec_ns_scalar_tangent_workspace bytes (20 compacted fields, >= every other step's
- * workspace but the adjoints' and nns_spec_ns_tangents_workspace).  No allocation, no host synchronisation (capturable).  Not built: several
- * tangents on one base with a scalar.  Errors, all before any launch: those of the forward call, plus NNS_ERR_INVALID_ARG for a NULL that,
+ * workspace but the adjoints' and nns_spec_ns_tangents_workspace).  No allocation, no host synchronisation (capturable).  Several
+ * tangents on one base with a scalar: nns_spec_ns_step_scalar_tangents_f32 below.  Errors, all before any launch: those of the forward call, plus NNS_ERR_INVALID_ARG for a NULL that,
  * dwhat or dthat and for dgbatch not 0 without dghat, 1 or batch with it, and NNS_ERR_WORKSPACE below nns_spec_ns_scalar_tangent_workspace. */
 int nns_spec_ns_scalar_tangent_workspace(int batch, int nx, int ny, size_t* bytes);
 int nns_spec_ns_step_scalar_tangent_f32(float* what, float* that, float* dwhat, float* dthat, const float* mean, const float* ghat, int gbatch,
@@ -706,6 +706,30 @@ int nns_spec_ns_step_scalar_tangent_f32(float* what, float* that, float* dwhat, 
                                         double Ly, double dt, double nu, double drag, double kappa, double gx, double gy, double bx, double by,
                                         const float* lin, const float* amp, unsigned long long seed, long long* clock, const int* ids,
                                         int nsteps, void* stream);
+/* ntan tangent pairs on one base with a scalar, and the scalar half of their inner product (restatement: tests/pspec_scalar_lyapunov_oracle.py).
+ * dwhat, dthat: float32 [ntan][batch][my1][nx][2], ntan in [1, 32]; the other arguments are those of nns_spec_ns_step_scalar_tangent_f32
+ * without dghat / dgbatch (no source perturbation per member).  (what, that) come out BITWISE as from the forward call the other arguments name,
+ * the advance of clock included, and every member (dwhat[k], dthat[k]) BITWISE as from nns_spec_ns_step_scalar_tangent_f32 on a copy of the
+ * state with dghat = NULL: the (0, 0) entry of dthat[k] is carried bit for bit, and with b = (0, 0) dwhat[k] is bitwise
+ * nns_spec_ns_step_tangents_f32's member.  The base's three inverse and two forward y-transforms and its two column passes are done once for
+ * all members (3 + 3 ntan and 2 + 2 ntan transforms per row where ntan single calls run 7 ntan and 4 ntan); still 8 launches per step plus one
+ * per call.  A grid's numbers do not depend on its batch neighbours or on ntan; nsteps steps in one call are bitwise nsteps calls of one step.
+ * work: nns_spec_ns_scalar_tangents_workspace bytes: 10 + 10 ntan compacted fields of batch my1 nx complex each (accumulators A, A_theta, dA[ntan],
+ * dA_theta[ntan]; G 6 + 6 ntan; Ph 2 + 2 ntan), never below nns_spec_ns_workspace; ntan = 1 is nns_spec_ns_scalar_tangent_workspace.  No
+ * allocation, no host synchronisation (capturable).  Errors, all before any launch and in this order: NNS_ERR_INVALID_ARG for a NULL that, dwhat
+ * or dthat, then for ntan outside [1, 32], then those of the forward call, then NNS_ERR_WORKSPACE below nns_spec_ns_scalar_tangents_workspace.
+ * nns_spec_ns_tangent_variance_gram_f64: out float64 [batch][ntan][ntan], out[b][k][l] = 1/2 sum wt Re(conj(dtheta_k) dtheta_l) / (nx ny)^2 over
+ * the stored modes but (0, 0) (wt 1 on j = 0, 2 on j > 0): the variance inner product, whose diagonal is bitwise column 0 of
+ * nns_spec_ns_scalar_diag_f32 of each member; bitwise symmetric, fixed order of summation, no atomics.  With nns_spec_ns_tangent_gram_f64 of
+ * dwhat it gives the inner product E(dw) + weight 1/2 <dtheta'^2> of the pairs; nns_spec_ns_tangent_combine_f32 serves dwhat and dthat with the
+ * one coefficient matrix (two calls; the (0, 0) entries of dthat combine linearly with the rest).  Not built: a source perturbation per
+ * member, covariant vectors. */
+int nns_spec_ns_scalar_tangents_workspace(int batch, int ntan, int nx, int ny, size_t* bytes);
+int nns_spec_ns_step_scalar_tangents_f32(float* what, float* that, float* dwhat, float* dthat, int ntan, const float* mean, const float* ghat,
+                                         int gbatch, void* work, size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly, double dt,
+                                         double nu, double drag, double kappa, double gx, double gy, double bx, double by, const float* lin,
+                                         const float* amp, unsigned long long seed, long long* clock, const int* ids, int nsteps, void* stream);
+int nns_spec_ns_tangent_variance_gram_f64(const float* dthat, int ntan, double* out, int batch, int nx, int ny, void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

@@ -3,7 +3,8 @@
 // (TH = false) the tangent (Ph field 1, dw^ / dA with the vorticity's factors and mask, dg^ where the vorticity adds g^, no kick, no mean
 // flow, its four spectra to G fields 4..7).  TANSC (a PsScalar and a PsTangentScalar in the pack: the tangent of the scalar system) has four
 // fields: the vorticity, the scalar, then TG alone on Ph field 2 and G fields 6..9 and TH with TG, the scalar's perturbation: Ph field 3,
-// dtheta^ / dA_theta with E_theta and the mask that keeps (0, 0), no g^, no dg^, no kick, zero means, its gradient to G fields 10 and 11.  Plain
+// dtheta^ / dA_theta with E_theta and the mask that keeps (0, 0), no g^, no dg^, no kick, zero means, its gradient to G fields 10 and 11.  TANSCS
+// (K pairs on one base) includes those two passes in a loop's scope where TANSC is true and Ph, G, tg, dTh, dAt are member k's.  Plain
 // text rather than a function or a lambda: the unscalared kernels then compile to the instructions they had before there was a scalar
 // (a lambda's body is optimised on its own before it is inlined, and came out a few instructions and registers different).
 // STOCH (ps_col_kernel's note) is false in every kernel without a PsStoch argument, whose text below is then what it was.

@@ -131,7 +131,17 @@
 // text under PSPEC_SCALAR_TANGENT_TU; ps_scalar_tangent_col / ps_scalar_tangent_row are the way in).  Still 8 launches per step plus one per call, one driver
 // (spec_ns_step), one more row of PsLayout (4 accumulators, 12 G, 4 Ph: 20 compacted fields); the base is bitwise the step without the
 // perturbation, with b = 0 dw^ is bitwise the flow tangent's, and every other kernel keeps its name and its code.  Registers and times:
-// profiles/pspec_scalar_tangent_isa.txt (no scratch), profiles/pspec_scalar_tangent_run.json.  Not built: K tangents with a scalar.
+// profiles/pspec_scalar_tangent_isa.txt (no scratch), profiles/pspec_scalar_tangent_run.json.
+//
+// K tangent pairs on one base with a scalar (nns_spec_ns_step_scalar_tangents_f32; restatement: tests/pspec_scalar_lyapunov_oracle.py): dwhat,
+// dthat [K][B][my1][nx], member k exactly a pair of the call above with dg^ = NULL.  ps_row_tans_scalar_kernel<ny, BUOYANT> transforms the base's
+// three lines once per row and keeps them while a run-time loop passes the K pairs through (3 + 3K inverse and 2 + 2K forward transforms
+// where K calls run 7K and 4K; G fields 6+6k .. 11+6k, Ph fields 2+2k, 3+2k), and a PsScalar, a PsTangents and a PsTangentsScalar in
+// ps_col_kernel's pack (TANSCS) run the vorticity's pass, the scalar's, then the TANSC form's two tangent passes K times (2 + 2K passes
+// through a tile against 4K).  One more row of PsLayout that depends on K (10 + 10K compacted fields), the same driver and launch count.
+// These kernels are instantiated in pspec_scalar_tangents.hip (this text under PSPEC_SCALAR_TANGENTS_TU), which also holds
+// ps_tangent_variance_gram_kernel, the scalar half of the pairs' inner product; every other kernel keeps its name and its code
+// (profiles/pspec_scalar_tangents_isa.txt, no scratch; times: profiles/pspec_scalar_tangents_run.json).
 //
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 //
@@ -151,6 +161,13 @@
 int ps_scalar_tangent_col(int nx, int S, const void* Ph, void* G, void* W, void* A, const float* mean, const void* a, int emit, const void* fc,
                           const void* sc, void* stream, const void* st, const void* li, const void* tg, const void* tt);
 int ps_scalar_tangent_row(int ny, const void* G, void* Ph, const void* a, void* stream, const void* gr, int buoyant);
+// The kernels of K tangents on the scalar system likewise (pspec_scalar_tangents.hip, PSPEC_SCALAR_TANGENTS_TU); ts: PsTangents, tu: PsTangentsScalar.
+int ps_scalar_tangents_col(int nx, int S, const void* Ph, void* G, void* W, void* A, const float* mean, const void* a, int emit, const void* fc,
+                           const void* sc, void* stream, const void* st, const void* li, const void* ts, const void* tu);
+int ps_scalar_tangents_row(int ny, const void* G, void* Ph, const void* a, void* stream, const void* gr, int buoyant, int K);
+#if defined(PSPEC_SCALAR_TANGENT_TU) || defined(PSPEC_SCALAR_TANGENTS_TU)
+#define PSPEC_KERNEL_TU      // a translation unit of kernels and their launches alone: no host entry point
+#endif
 
 namespace {
 
@@ -193,11 +210,15 @@ struct PsTangentScalar {  // follows a PsScalar and a PsTangent in the pack (nns
     float2* dT;           // dtheta^ [B][my1][nx], the layout of W: advanced with the scalar's E_theta and the mask that keeps (0, 0)
     float2* dAt;          // its Lawson accumulator
 };
-struct PsTangents {       // the first extra argument of the TANGENTS column kernels (nns_spec_ns_step_tangents_f32): K tangents on one base; never with a PsScalar or a PsKeep
+struct PsTangents {       // the first extra argument of the TANGENTS column kernels (nns_spec_ns_step_tangents_f32): K tangents on one base; after a PsScalar only with a PsTangentsScalar, never with a PsKeep
     float2* dW;           // dw^ [K][B][my1][nx]: member k at dW + k kstride, each in the layout of W
     float2* dA;           // their Lawson accumulators, member k at dA + k kstride
     long kstride;         // complex elements between two members (= B my1 nx)
     int K;                // members, 1 .. 32
+};
+struct PsTangentsScalar { // follows a PsScalar and a PsTangents in the pack (nns_spec_ns_step_scalar_tangents_f32): the K scalar perturbations; never with a PsKeep or a PsTangent
+    float2* dT;           // dtheta^ [K][B][my1][nx]: member k at dT + k kstride (the PsTangents' stride), each advanced as a PsTangentScalar's dT
+    float2* dAt;          // their Lawson accumulators, member k at dAt + k kstride
 };
 struct PsKeep {           // the last argument of the STAGES column kernels (stages 1-3 of the adjoint's recomputation; no scalar or noise)
     float2* stage;        // [B][my1][nx], the layout of W: receives the next stage's input spectrum (s1, s2 or s3)
@@ -537,6 +558,104 @@ __global__ __launch_bounds__(kT) void ps_row_tans_kernel(const float2* __restric
     }
 }
 
+// The row pass of K tangent pairs on one base with a scalar (nns_spec_ns_step_scalar_tangents_f32): ps_row_tans_kernel's loop around
+// ps_row_tan_scalar_kernel's arithmetic.  G fields 0-5 are the base's, member k's (du, dv, dw_x, dw_y, dtheta_x, dtheta_y) are 6+6k .. 11+6k; Ph
+// fields 0 and 1 take the base's two products, 2+2k and 3+2k member k's linearised ones.  u + i v, w_x + i w_y and theta_x + i theta_y are
+// transformed once per row and stay; the base's products leave first, spelt as in ps_row_tan_scalar_kernel (so as in ps_row_kernel<N, true,
+// BUOYANT>: the base stays bitwise the step).  Then the run-time loop: du + i dv transformed ONCE per member and turned into the 16 reals
+// du w_x + dv w_y (zp) and the 16 reals du (theta_x + Gx) + dv (theta_y + Gy) (zq); dw_x + i dw_y, its product, forward, BUOYANT's c4 G[10+6k] +
+// c5 G[11+6k], Ph 2+2k; dtheta_x + i dtheta_y, its product, forward, Ph 3+2k.  Every product is spelt as in ps_row_tan_scalar_kernel and a
+// transform of the same input gives the same bits, so member k's bits are that kernel's.  3 + 3K inverse and 2 + 2K forward transforms per
+// row where K single calls run 7K and 4K.  Four complex lines and 32 reals are live; nothing is indexed by k but pointers, and the lane's
+// index is pinned per turn as in ps_row_tans_kernel.
+template <int N, bool BUOYANT>
+__global__ __launch_bounds__(kT) void ps_row_tans_scalar_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a,
+                                                                std::conditional_t<BUOYANT, PsBuoyGrad, PsGrad> gr, int K) {
+    using L = PsLds<N>;
+    constexpr int TPF = L::TPF;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const cf* tab = ps_tables<N>(smem);
+    unsigned char* lines = smem + L::TAB_BYTES;
+    const int my1 = a.my1;
+    const long niter = (a.nlines + L::LINES - 1) / L::LINES;
+    for (long it = blockIdx.x; it < niter; it += gridDim.x) {
+#include "pspec_row_line.inc"
+        cf zu[16], zw[16], zt[16], zd[16];
+        float zp[16], zq[16];
+        ps_row_load2<N>(g0, g0 + a.fstride, tid, my1, zu);                           // u + i v: stays
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 2 * a.fstride, g0 + 3 * a.fstride, tid, my1, zw);       // w_x + i w_y: stays
+        fft_line<float, N, true>(zw, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zd[m] = {zu[m].x * zw[m].x + zu[m].y * zw[m].y, 0.f};        // u w_x + v w_y
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tid);
+        if constexpr (BUOYANT) {                                 // -ny (by theta_x - bx theta_y)^ on the kept modes, as in ps_row_kernel
+            const float2* t4 = g0 + 4 * a.fstride;
+            const float2* t5 = g0 + 5 * a.fstride;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int e = tid + TPF * m;
+                if (e < my1) {
+                    const float2 p = t4[e], q = t5[e];
+                    zd[m] = {fmaf(gr.c4, p.x, fmaf(gr.c5, q.x, zd[m].x)), fmaf(gr.c4, p.y, fmaf(gr.c5, q.y, zd[m].y))};
+                }
+            }
+        }
+        ps_row_store<N>(zd, Ph + (size_t)row * my1, tid, my1, valid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 4 * a.fstride, g0 + 5 * a.fstride, tid, my1, zt);       // theta_x + i theta_y: stays
+        fft_line<float, N, true>(zt, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zd[m] = {zu[m].x * (zt[m].x + gr.gx) + zu[m].y * (zt[m].y + gr.gy), 0.f};   // u (theta_x + Gx) + v (theta_y + Gy)
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tid);
+        ps_row_store<N>(zd, Ph + a.fstride + (size_t)row * my1, tid, my1, valid);
+        const float2* gk = g0 + 6 * a.fstride;                                       // member k's six fields
+        float2* pk = Ph + 2 * a.fstride + (size_t)row * my1;                         // and its two Ph fields
+        for (int k = 0; k < K; ++k, gk += 6 * a.fstride, pk += 2 * a.fstride) {
+            int tk = tid;                                                            // ps_row_tans_kernel's pin
+            asm volatile("" : "+v"(tk));
+            __builtin_amdgcn_sched_barrier(0);
+            ps_row_load2<N>(gk, gk + a.fstride, tk, my1, zd);                        // du + i dv, once
+            fft_line<float, N, true>(zd, tab, tab + N / 2, xb, tk);
+#pragma unroll
+            for (int m = 0; m < 16; ++m) zp[m] = zd[m].x * zw[m].x + zd[m].y * zw[m].y;           // du w_x + dv w_y: w_x, w_y stay
+#pragma unroll
+            for (int m = 0; m < 16; ++m) zq[m] = zd[m].x * (zt[m].x + gr.gx) + zd[m].y * (zt[m].y + gr.gy);   // du (theta_x + Gx) + dv (theta_y + Gy)
+            __builtin_amdgcn_sched_barrier(0);
+            ps_row_load2<N>(gk + 2 * a.fstride, gk + 3 * a.fstride, tk, my1, zd);    // dw_x + i dw_y
+            fft_line<float, N, true>(zd, tab, tab + N / 2, xb, tk);
+#pragma unroll
+            for (int m = 0; m < 16; ++m) zd[m] = {fmaf(zu[m].x, zd[m].x, fmaf(zu[m].y, zd[m].y, zp[m])), 0.f};   // + u dw_x + v dw_y
+            __builtin_amdgcn_sched_barrier(0);
+            fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tk);
+            if constexpr (BUOYANT) {                             // the buoyancy of member k's scalar perturbation: its G fields 10+6k and 11+6k
+                const float2* t4 = gk + 4 * a.fstride;
+                const float2* t5 = gk + 5 * a.fstride;
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    const int e = tk + TPF * m;
+                    if (e < my1) {
+                        const float2 p = t4[e], q = t5[e];
+                        zd[m] = {fmaf(gr.c4, p.x, fmaf(gr.c5, q.x, zd[m].x)), fmaf(gr.c4, p.y, fmaf(gr.c5, q.y, zd[m].y))};
+                    }
+                }
+            }
+            ps_row_store<N>(zd, pk, tk, my1, valid);
+            __builtin_amdgcn_sched_barrier(0);
+            ps_row_load2<N>(gk + 4 * a.fstride, gk + 5 * a.fstride, tk, my1, zd);    // dtheta_x + i dtheta_y
+            fft_line<float, N, true>(zd, tab, tab + N / 2, xb, tk);
+#pragma unroll
+            for (int m = 0; m < 16; ++m) zd[m] = {fmaf(zu[m].x, zd[m].x, fmaf(zu[m].y, zd[m].y, zq[m])), 0.f};   // + u dtheta_x + v dtheta_y
+            __builtin_amdgcn_sched_barrier(0);
+            fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tk);
+            ps_row_store<N>(zd, pk + a.fstride, tk, my1, valid);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- column pass (axis x)
 // S = 0: prepare stage 1 from W; S = 1..4: consume the RK stage's N (from Ph) and update W / A, then (S < 4 or emit) prepare the next stage.
 // FORCED (S >= 1): N^ += g^ on the kept modes (lane-owned, coalesced, like W / A) and L dt / 2 = hnudt |k|^2 - alpha dt / 2.
@@ -558,6 +677,10 @@ __global__ __launch_bounds__(kT) void ps_row_tans_kernel(const float2* __restric
 // TANGENTS (a PsTangents in the PsTangent's place; never with a PsScalar or a PsKeep): the TG text runs K times in a run-time loop, turn k on
 // dW + k kstride / dA + k kstride, Ph field 1+k and G fields 4+4k .. 7+4k, with no dg^.  The text sees member k under the names it has for
 // the one tangent (Ph, G and tg are shadowed by member k's in the loop's scope), so it is the same text and member k's bits are the TANGENT kernel's.
+// TANSCS (a PsScalar, a PsTangents and a PsTangentsScalar, in that order; never with a PsKeep or a PsTangent): K tangent pairs on the system with a
+// scalar.  The vorticity's pass, the scalar's, then a run-time loop whose turn k runs the two tangent passes of the TANSC form on member k: Ph,
+// G, tg, dTh, dAt and TANSC itself are shadowed in the loop's scope (Ph fields 2+2k, 3+2k; G fields 6+6k .. 11+6k; dW, dA, dT, dAt + k kstride),
+// so the text is that form's and member k's bits are the TANSC kernel's with dg^ = NULL.
 template <int N, int S, bool FORCED = false, bool SCALAR = false, typename... Sc>
 __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, float2* __restrict__ W,
                                                     float2* __restrict__ A, const float* __restrict__ mean, PsArgs a, int emit,
@@ -568,13 +691,15 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     constexpr bool TANGENT = (std::is_same_v<Sc, PsTangent> || ... || false);
     constexpr bool TANGENTS = (std::is_same_v<Sc, PsTangents> || ... || false);
     constexpr bool TANSC = (std::is_same_v<Sc, PsTangentScalar> || ... || false);
+    constexpr bool TANSCS = (std::is_same_v<Sc, PsTangentsScalar> || ... || false);
     constexpr bool KEEP_W = (std::is_same_v<Sc, PsKeep> || ... || false), KEEP_WT = (std::is_same_v<Sc, PsKeepScalar> || ... || false);
     constexpr bool STAGES = KEEP_W || KEEP_WT;
-    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (TANGENT ? 1 : 0) + (TANGENTS ? 1 : 0) + (TANSC ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0) + (STAGES ? 1 : 0),
+    static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (TANGENT ? 1 : 0) + (TANGENTS ? 1 : 0) + (TANSC ? 1 : 0) + (TANSCS ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0) + (STAGES ? 1 : 0),
                   "PsScalar is the SCALAR kernel's argument (PsTangent the TANGENT kernel's), PsLinear after it the LINEAR kernel's, PsStoch or the PsKeep last");
     static_assert(!TANGENT || (SCALAR == TANSC && !STAGES), "the tangent of the scalar system takes a PsScalar, a PsTangent and a PsTangentScalar, and the adjoint's recomputation carries no tangent");
     static_assert(!TANSC || (SCALAR && TANGENT), "the PsTangentScalar follows a PsScalar and a PsTangent");
-    static_assert(!TANGENTS || (!SCALAR && !STAGES && !TANGENT), "K tangents: as the one tangent, and never beside it");
+    static_assert(!TANGENTS || (SCALAR == TANSCS && !STAGES && !TANGENT), "K tangents: as the one tangent, and never beside it; with a scalar a PsTangentsScalar follows");
+    static_assert(!TANSCS || (SCALAR && TANGENTS), "the PsTangentsScalar follows a PsScalar and a PsTangents");
     static_assert(!STAGES || (S >= 1 && S <= 3 && KEEP_WT == SCALAR && !STOCH),
                   "the stage store is that of stages 1-3 of the steady and the linear forms: a PsKeep without a scalar, a PsKeepScalar with one");
     static_assert(!LINEAR || (FORCED && S >= 1 && S <= 3), "the complex factors are those of stages 1-3 of the forced form");
@@ -663,7 +788,29 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
             constexpr bool TH = true, TG = true;
 #include "pspec_col_pass.inc"
         }
-        if constexpr (TANGENTS) {
+        if constexpr (TANSCS) {
+            const PsTangents ts = pick<PsTangents>(sc...);
+            const PsTangentsScalar tu = pick<PsTangentsScalar>(sc...);
+            const float2* const Ph0 = Ph;
+            float2* const G0 = G;
+            for (int k = 0; k < ts.K; ++k) {            // member k's pair under the names of the TANSC form: its two passes, in its text
+                constexpr bool TANSC = true;
+                const float2* Ph = Ph0 + (size_t)(2 * k) * a.fstride;
+                float2* G = G0 + (size_t)(6 * k) * a.fstride;
+                const PsTangent tg{ts.dW + (size_t)k * ts.kstride, ts.dA + (size_t)k * ts.kstride, nullptr, 0};
+                float2* const dTh = tu.dT + (size_t)k * ts.kstride;
+                float2* const dAt = tu.dAt + (size_t)k * ts.kstride;
+                {
+                    constexpr bool TH = false, TG = true;
+#include "pspec_col_pass.inc"
+                }
+                {
+                    constexpr bool TH = true, TG = true;
+#include "pspec_col_pass.inc"
+                }
+            }
+        }
+        if constexpr (TANGENTS && !TANSCS) {
             const PsTangents ts = pick<PsTangents>(sc...);
             const float2* const Ph0 = Ph;
             float2* const G0 = G;
@@ -1374,19 +1521,29 @@ int launch_row_tans(const float2* G, float2* Ph, const PsArgs& a, int K, hipStre
     return check_launch("spec_ns tangents row pass");
 }
 
+template <int N, typename Gr>
+int launch_row_tans_scalar(const float2* G, float2* Ph, const PsArgs& a, int K, hipStream_t s, Gr gr) {
+    constexpr bool BU = std::is_same_v<Gr, PsBuoyGrad>;
+    constexpr auto kern = ps_row_tans_scalar_kernel<N, BU>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a, gr, K);
+    return check_launch(BU ? "spec_ns buoyant tangents row pass" : "spec_ns scalar tangents row pass");
+}
+
 // The column kernel of stage S whose argument pack ends in x...: a PsScalar (the SCALAR kernels), a PsTangent or a PsTangents, a PsLinear, a PsStoch, in that order, each or
-// none; a PsTangentScalar follows a PsScalar and a PsTangent.  fc is read only by the FORCED kernels.
+// none; a PsTangentScalar follows a PsScalar and a PsTangent, a PsTangentsScalar a PsScalar and a PsTangents.  fc is read only by the FORCED kernels.
 template <int N, int S, bool FORCED, typename... X>
 int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
                hipStream_t s, X... x) {
     constexpr bool SC = has<PsScalar, X...>, LI = has<PsLinear, X...>, ST = has<PsStoch, X...>, KE = has<PsKeep, X...> || has<PsKeepScalar, X...>;
-    constexpr bool TA = has<PsTangent, X...>, TS = has<PsTangents, X...>, TT = has<PsTangentScalar, X...>;
+    constexpr bool TA = has<PsTangent, X...>, TS = has<PsTangents, X...>, TT = has<PsTangentScalar, X...>, TU = has<PsTangentsScalar, X...>;
     constexpr auto kern = ps_col_kernel<N, S, FORCED, SC, X...>;
     std::conditional_t<FORCED, PsForce, PsNoForce> f{};
     if constexpr (FORCED) f = *fc;
     if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
     hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, W, A, mean, a, emit, f, x...);
-    return check_launch(TS       ? "spec_ns tangents column pass"
+    return check_launch(TU       ? "spec_ns scalar tangents column pass"
+                        : TS     ? "spec_ns tangents column pass"
                         : TT     ? "spec_ns scalar tangent column pass"
                         : TA     ? "spec_ns tangent column pass"
                         : KE     ? "spec_ns stage-keeping column pass"
@@ -1407,13 +1564,15 @@ int with_stage(int S, F&& f) {
 // The one place where a stage's run-time facts become a kernel.  fc == nullptr: the unforced kernels (stage 0 has no other form); sc: the
 // SCALAR ones; li (with fc): a linear step, whose stages 1-3 are the LINEAR kernels (stage 4 applies no factor); st (with fc): a stochastic
 // step, whose stages 1 and 4 are the STOCH kernels; tg (with sc only beside tt): the TANGENT ones, of every stage and form; tt (with sc
-// and tg): those of the scalar system's tangent, which live in pspec_scalar_tangent.hip and are reached through ps_scalar_tangent_col; ts (never with sc or tg): the TANGENTS ones, likewise.  The pack grows in the kernel's order, and a form no step has is never named.
+// and tg): those of the scalar system's tangent, which live in pspec_scalar_tangent.hip and are reached through ps_scalar_tangent_col; ts (never with tg; with sc only beside tu): the TANGENTS ones, likewise;
+// tu (with sc and ts): those of K tangents on the scalar system, which live in pspec_scalar_tangents.hip and are reached through ps_scalar_tangents_col.  The pack grows in the kernel's order, and a form no step has is never named.
 template <int N>
 int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
                      const PsScalar* sc, hipStream_t s, const PsStoch* st = nullptr, const PsLinear* li = nullptr, const PsTangent* tg = nullptr,
-                     const PsTangents* ts = nullptr, const PsTangentScalar* tt = nullptr) {
-#ifndef PSPEC_SCALAR_TANGENT_TU
+                     const PsTangents* ts = nullptr, const PsTangentScalar* tt = nullptr, const PsTangentsScalar* tu = nullptr) {
+#ifndef PSPEC_KERNEL_TU
     if (tt) return ps_scalar_tangent_col(N, S, Ph, G, W, A, mean, &a, emit, fc, sc, s, st, li, tg, tt);
+    if (tu) return ps_scalar_tangents_col(N, S, Ph, G, W, A, mean, &a, emit, fc, sc, s, st, li, ts, tu);
 #endif
     auto stage = [&](auto stage_c) {
         constexpr int K = decltype(stage_c)::value;
@@ -1428,8 +1587,10 @@ int launch_col_stage(int S, const float2* Ph, float2* G, float2* W, float2* A, c
                 if (li) return stoch(forced, x..., *li);
             return stoch(forced, x...);
         };
-#ifdef PSPEC_SCALAR_TANGENT_TU      // this translation unit names the forms with a PsTangentScalar and no other
+#if defined(PSPEC_SCALAR_TANGENT_TU)      // this translation unit names the forms with a PsTangentScalar and no other
         auto scalar = [&](auto forced) { return linear(forced, *sc, *tg, *tt); };
+#elif defined(PSPEC_SCALAR_TANGENTS_TU)   // and this one those with a PsTangentsScalar
+        auto scalar = [&](auto forced) { return linear(forced, *sc, *ts, *tu); };
 #else
         auto scalar = [&](auto forced) { return ts ? linear(forced, *ts) : tg ? linear(forced, *tg) : sc ? linear(forced, *sc) : linear(forced); };
 #endif
@@ -1505,6 +1666,7 @@ size_t scalar_work_bytes(int batch, int nx, int ny) {
 //   the tangent step:    A, dA in A_theta's place, G[8], Ph[2]: 12
 //   the scalar tangent:  A, A_theta, dA, dA_theta, G[12], Ph[4]: 20
 //   K tangents:          A, dA[K], G[4 + 4K], Ph[1 + K]: 6 + 6K (tangents_layout; K = 1 is the tangent step's)
+//   K tangents, scalar:  A, A_theta, dA[K], dA_theta[K], G[6 + 6K], Ph[2 + 2K]: 10 + 10K (scalar_tangents_layout; K = 1 is the scalar tangent's)
 struct PsLayout {
     int acc, g, ph, keep;
     constexpr int fields() const { return acc + g + ph + keep; }
@@ -1523,6 +1685,8 @@ size_t scalar_tangent_work_bytes(int batch, int nx, int ny) { return layout_work
 constexpr int kMaxTangents = 32;
 constexpr PsLayout tangents_layout(int K) { return PsLayout{1 + K, 4 + 4 * K, 1 + K, 0}; }
 size_t tangents_work_bytes(int batch, int ntan, int nx, int ny) { return layout_work_bytes(tangents_layout(ntan), batch, nx, ny); }
+constexpr PsLayout scalar_tangents_layout(int K) { return PsLayout{2 + 2 * K, 6 + 6 * K, 2 + 2 * K, 0}; }
+size_t scalar_tangents_work_bytes(int batch, int ntan, int nx, int ny) { return layout_work_bytes(scalar_tangents_layout(ntan), batch, nx, ny); }
 
 // The fields of a layout in work, and the arguments of the column pass (col) and of the row pass (row).
 struct PsWork {
@@ -1562,10 +1726,11 @@ int check_box(const char* what, int nx, int ny, double Lx, double Ly) {
     return check_axes(what, nx, ny);
 }
 
-enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2, kWorkScalarAdjoint = 3, kWorkTangent = 4, kWorkTangents = 5, kWorkScalarTangent = 6 };      // a bool converts: false the flow's workspace, true the scalar's
+enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2, kWorkScalarAdjoint = 3, kWorkTangent = 4, kWorkTangents = 5, kWorkScalarTangent = 6, kWorkScalarTangents = 7 };      // a bool converts: false the flow's workspace, true the scalar's
 
-int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int kind, int ntan = 0) {      // ntan: kWorkTangents' K
-    const size_t need = kind == kWorkScalarTangent ? scalar_tangent_work_bytes(batch, nx, ny)
+int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int kind, int ntan = 0) {      // ntan: kWorkTangents' and kWorkScalarTangents' K
+    const size_t need = kind == kWorkScalarTangents ? scalar_tangents_work_bytes(batch, ntan, nx, ny)
+                        : kind == kWorkScalarTangent ? scalar_tangent_work_bytes(batch, nx, ny)
                         : kind == kWorkTangents    ? tangents_work_bytes(batch, ntan, nx, ny)
                         : kind == kWorkTangent     ? tangent_work_bytes(batch, nx, ny)
                         : kind == kWorkScalarAdjoint ? scalar_adjoint_work_bytes(batch, nx, ny)
@@ -1574,7 +1739,8 @@ int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int k
                                                    : work_bytes(batch, nx, ny);
     if (wbytes < need)
         return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", what, wbytes, need,
-                    kind == kWorkScalarTangent ? "nns_spec_ns_scalar_tangent_workspace"
+                    kind == kWorkScalarTangents ? "nns_spec_ns_scalar_tangents_workspace"
+                    : kind == kWorkScalarTangent ? "nns_spec_ns_scalar_tangent_workspace"
                     : kind == kWorkTangents    ? "nns_spec_ns_tangents_workspace"
                     : kind == kWorkTangent     ? "nns_spec_ns_tangent_workspace"
                     : kind == kWorkScalarAdjoint ? "nns_spec_ns_scalar_adjoint_workspace"
@@ -1669,7 +1835,7 @@ int launch_transfer(const float2* Ph, const float2* W, const float2* Th, float* 
 
 }  // namespace
 
-#ifndef PSPEC_SCALAR_TANGENT_TU
+#ifndef PSPEC_KERNEL_TU
 NNS_API int nns_spec_ns_shells(int nx, int ny, double Lx, double Ly, int* nshell, double* dk) {
     if (!nshell || !dk) return fail(NNS_ERR_INVALID_ARG, "spec_ns_shells: nshell and dk must be non-NULL");
     if (int rc = check_box("spec_ns_shells", nx, ny, Lx, Ly)) return rc;
@@ -1771,31 +1937,34 @@ NNS_API int nns_spec_ns_init_f32(const float* u, const float* v, float* what, fl
 // of the base's kernels is the one made without dwhat, so what comes out bitwise as from that call.  ntan >= 1 (with dwhat, no dghat): dwhat holds
 // ntan tangents [ntan][B][my1][nx] on that one base, the TANGENTS forms on the layout of ntan tangents; ntan == 0: the one tangent's call.
 // dthat != NULL (with that and dwhat, ntan == 0): the tangent of the scalar system, (dw^, dtheta^) in the launches of the scalar step on the
-// 20-field layout; (what, that) come out bitwise as from the call without the perturbation.
+// 20-field layout; (what, that) come out bitwise as from the call without the perturbation.  dthat != NULL with ntan >= 1 (no dghat): ntan pairs
+// (dwhat, dthat) [ntan][B][my1][nx] on the one base (w^, theta^), the TANSCS forms on the layout of 10 + 10 ntan fields.
 static int spec_ns_step(const char* who, float* what, float* that, const float* mean, const float* ghat, int gbatch, void* work,
                         size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag, double kappa,
                         double gx, double gy, double bx, double by, int nsteps, void* stream, const PsStoch* st = nullptr,
                         const float* lin = nullptr, float* dwhat = nullptr, const float* dghat = nullptr, int dgbatch = 0,
                         int ntan = 0, float* dthat = nullptr) {
     if (!what || !mean || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
-    if (dwhat && that && (!dthat || ntan)) return fail(NNS_ERR_UNSUPPORTED, "%s: the tangent of the scalar system is not built", who);
+    if (dwhat && that && !dthat) return fail(NNS_ERR_UNSUPPORTED, "%s: the tangent of the scalar system is not built", who);
     if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
     if (int rc = check_scalar_numbers(who, kappa, gx, gy)) return rc;
     if (int rc = check_buoyancy(who, bx, by)) return rc;
     if (int rc = check_gbatch(who, ghat, gbatch, batch)) return rc;
     if (dghat ? (dgbatch != 1 && dgbatch != batch) : dgbatch != 0)
         return fail(NNS_ERR_INVALID_ARG, "%s: dgbatch = %d must be 0 without dghat, 1 or batch = %d with it", who, dgbatch, batch);
-    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, ntan ? kWorkTangents : dthat ? kWorkScalarTangent : dwhat ? kWorkTangent : that ? kWorkScalar : kWorkFlow, ntan)) return rc;
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, ntan && dthat ? kWorkScalarTangents : ntan ? kWorkTangents : dthat ? kWorkScalarTangent : dwhat ? kWorkTangent : that ? kWorkScalar : kWorkFlow, ntan)) return rc;
     if (nsteps == 0) return NNS_OK;
     hipStream_t s = as_stream(stream);
     float2* W = reinterpret_cast<float2*>(what);
-    const PsWork L(work, batch, nx, ny, ntan ? tangents_layout(ntan) : dthat ? kLayScalarTangent : dwhat ? kLayTangent : that ? kLayScalar : kLayFlow, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);
+    const PsWork L(work, batch, nx, ny, ntan && dthat ? scalar_tangents_layout(ntan) : ntan ? tangents_layout(ntan) : dthat ? kLayScalarTangent : dwhat ? kLayTangent : that ? kLayScalar : kLayFlow, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);
     const PsTangent tangent{reinterpret_cast<float2*>(dwhat), dthat ? L.A + 2 * L.col.fstride : L.At, reinterpret_cast<const float2*>(dghat), dgbatch == 1 && batch > 1 ? 1 : 0};
     const PsTangent* tg = dwhat && !ntan ? &tangent : nullptr;
     const PsTangentScalar tanscalar{reinterpret_cast<float2*>(dthat), L.A + 3 * L.col.fstride};      // the scalar system's: A, A_theta, dA, dA_theta
-    const PsTangentScalar* tt = dthat ? &tanscalar : nullptr;
-    const PsTangents tangents{reinterpret_cast<float2*>(dwhat), L.At, L.col.fstride, ntan};      // dA[k] follows A, a field apart like the members
+    const PsTangentScalar* tt = dthat && !ntan ? &tanscalar : nullptr;
+    const PsTangents tangents{reinterpret_cast<float2*>(dwhat), dthat ? L.A + 2 * L.col.fstride : L.At, L.col.fstride, ntan};      // dA[k] follows A (with a scalar: A_theta), a field apart like the members
     const PsTangents* ts = ntan ? &tangents : nullptr;
+    const PsTangentsScalar tanscalars{reinterpret_cast<float2*>(dthat), L.A + (size_t)(2 + ntan) * L.col.fstride};      // dA_theta[k] follows dA[K]
+    const PsTangentsScalar* tu = dthat && ntan ? &tanscalars : nullptr;
     const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
     const PsForce* fc = ghat || drag > 0 || st || lin ? &force : nullptr;
     const PsLinear linear{reinterpret_cast<const float2*>(lin)};
@@ -1812,11 +1981,12 @@ static int spec_ns_step(const char* who, float* what, float* that, const float* 
     const PsBuoyGrad buoy{(float)gx, (float)gy, (float)(-(double)ny * by), (float)((double)ny * bx)};
     const PsBuoyGrad* bu = that && (bx != 0.0 || by != 0.0) ? &buoy : nullptr;
     auto col = [&](int S, int emit) {
-        return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, emit, fc, sc, s, stc, li, tg, ts, tt); });
+        return dispatch_pow2(nx, "spec_ns", [&](auto n) { return launch_col_stage<decltype(n)::value>(S, L.Ph, L.G, W, L.A, mean, L.col, emit, fc, sc, s, stc, li, tg, ts, tt, tu); });
     };
     auto row = [&]() {
         return dispatch_pow2(ny, "spec_ns", [&](auto n) {
             constexpr int N = decltype(n)::value;
+            if (tu) return ps_scalar_tangents_row(N, L.G, L.Ph, &L.row, s, bu ? (const void*)bu : (const void*)&grad, bu != nullptr, ntan);
             if (ts) return launch_row_tans<N>(L.G, L.Ph, L.row, ntan, s);
             if (tt) return ps_scalar_tangent_row(N, L.G, L.Ph, &L.row, s, bu ? (const void*)bu : (const void*)&grad, bu != nullptr);
             if (tg) return launch_row_tan<N>(L.G, L.Ph, L.row, s);
@@ -1950,6 +2120,31 @@ NNS_API int nns_spec_ns_step_tangents_f32(float* what, float* dwhat, int ntan, c
     const PsStoch st{amp, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), clock, ids, 0.f};
     return spec_ns_step("spec_ns_step_tangents", what, nullptr, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt, lin ? 0.0 : nu,
                         lin ? 0.0 : drag, 0.0, 0.0, 0.0, 0.0, 0.0, nsteps, stream, noise ? &st : nullptr, lin, dwhat, nullptr, 0, ntan);
+}
+
+NNS_API int nns_spec_ns_scalar_tangents_workspace(int batch, int ntan, int nx, int ny, size_t* bytes) {
+    if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_tangents_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
+    if (ntan < 1 || ntan > kMaxTangents) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_tangents_workspace: ntan = %d must be in [1, %d]", ntan, kMaxTangents);
+    if (int rc = check_axes("spec_ns_scalar_tangents_workspace", nx, ny)) return rc;
+    *bytes = scalar_tangents_work_bytes(batch, ntan, nx, ny);
+    return NNS_OK;
+}
+
+// The base's kernels are chosen as in nns_spec_ns_step_scalar_tangent_f32; every member pair is that call's with dghat = NULL.
+NNS_API int nns_spec_ns_step_scalar_tangents_f32(float* what, float* that, float* dwhat, float* dthat, int ntan, const float* mean,
+                                                 const float* ghat, int gbatch, void* work, size_t work_bytes_, int batch, int nx, int ny,
+                                                 double Lx, double Ly, double dt, double nu, double drag, double kappa, double gx, double gy,
+                                                 double bx, double by, const float* lin, const float* amp, unsigned long long seed,
+                                                 long long* clock, const int* ids, int nsteps, void* stream) {
+    if (!that || !dwhat || !dthat) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_scalar_tangents: that, dwhat and dthat must be non-NULL");
+    if (ntan < 1 || ntan > kMaxTangents) return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_scalar_tangents: ntan = %d must be in [1, %d]", ntan, kMaxTangents);
+    const bool noise = amp && clock && ids;
+    if (!noise && (amp || clock || ids))
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_step_scalar_tangents: amp, clock and ids must be all NULL (no noise) or all non-NULL");
+    const PsStoch st{amp, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), clock, ids, 0.f};
+    return spec_ns_step("spec_ns_step_scalar_tangents", what, that, mean, ghat, gbatch, work, work_bytes_, batch, nx, ny, Lx, Ly, dt,
+                        lin ? 0.0 : nu, lin ? 0.0 : drag, kappa, gx, gy, bx, by, nsteps, stream, noise ? &st : nullptr, lin, dwhat, nullptr, 0, ntan,
+                        dthat);
 }
 
 // dwhat, ntan, batch and the box of the Gram and the combine call
@@ -2228,7 +2423,7 @@ NNS_API int nns_spec_ns_fields_buoyant_f32(const float* what, const float* that,
     return spec_ns_fields("spec_ns_fields_buoyant", what, that, mean, u, v, p, work, work_bytes_, batch, nx, ny, Lx, Ly, rho, bx, by, stream);
 }
 
-#else      // PSPEC_SCALAR_TANGENT_TU: the launches of the scalar system's tangent (declared at the head of this file)
+#elif defined(PSPEC_SCALAR_TANGENT_TU)      // the launches of the scalar system's tangent (declared at the head of this file)
 int ps_scalar_tangent_col(int nx, int S, const void* Ph, void* G, void* W, void* A, const float* mean, const void* a, int emit, const void* fc,
                           const void* sc, void* stream, const void* st, const void* li, const void* tg, const void* tt) {
     return dispatch_pow2(nx, "spec_ns", [&](auto n) {
@@ -2250,6 +2445,30 @@ int ps_scalar_tangent_row(int ny, const void* G, void* Ph, const void* a, void* 
         hipStream_t s = static_cast<hipStream_t>(stream);
         return buoyant ? launch_row_tan_scalar<N>(g, ph, args, s, *static_cast<const PsBuoyGrad*>(gr))
                        : launch_row_tan_scalar<N>(g, ph, args, s, *static_cast<const PsGrad*>(gr));
+    });
+}
+#else      // PSPEC_SCALAR_TANGENTS_TU: the launches of K tangents on the scalar system (declared at the head of this file)
+int ps_scalar_tangents_col(int nx, int S, const void* Ph, void* G, void* W, void* A, const float* mean, const void* a, int emit, const void* fc,
+                           const void* sc, void* stream, const void* st, const void* li, const void* ts, const void* tu) {
+    return dispatch_pow2(nx, "spec_ns", [&](auto n) {
+        return launch_col_stage<decltype(n)::value>(S, static_cast<const float2*>(Ph), static_cast<float2*>(G), static_cast<float2*>(W),
+                                                    static_cast<float2*>(A), mean, *static_cast<const PsArgs*>(a), emit,
+                                                    static_cast<const PsForce*>(fc), static_cast<const PsScalar*>(sc),
+                                                    static_cast<hipStream_t>(stream), static_cast<const PsStoch*>(st),
+                                                    static_cast<const PsLinear*>(li), nullptr, static_cast<const PsTangents*>(ts), nullptr,
+                                                    static_cast<const PsTangentsScalar*>(tu));
+    });
+}
+
+int ps_scalar_tangents_row(int ny, const void* G, void* Ph, const void* a, void* stream, const void* gr, int buoyant, int K) {
+    return dispatch_pow2(ny, "spec_ns", [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        const float2* g = static_cast<const float2*>(G);
+        float2* ph = static_cast<float2*>(Ph);
+        const PsArgs& args = *static_cast<const PsArgs*>(a);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        return buoyant ? launch_row_tans_scalar<N>(g, ph, args, K, s, *static_cast<const PsBuoyGrad*>(gr))
+                       : launch_row_tans_scalar<N>(g, ph, args, K, s, *static_cast<const PsGrad*>(gr));
     });
 }
 #endif

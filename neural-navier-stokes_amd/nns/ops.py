@@ -1350,6 +1350,51 @@ def spec_ns_tangent_combine_(dwhat, coef, ny):
     return dwhat
 
 
+# K tangent pairs on one base with a scalar (nns_spec_ns_step_scalar_tangents_f32, nns_spec_ns_tangent_variance_gram_f64)
+def spec_ns_scalar_tangents_workspace(B, K, nx, ny):
+    """Bytes of the workspace spec_ns_step_scalar_tangents_ needs for K tangent pairs on B grids of nx x ny (10 + 10 K compacted fields;
+    K = 1 is spec_ns_scalar_tangent_workspace)."""
+    return _query_bytes('nns_spec_ns_scalar_tangents_workspace', int(B), int(K), int(nx), int(ny))
+
+
+def spec_ns_step_scalar_tangents_(what, that, dwhat, dthat, mean, ghat, work, ny, Lx, Ly, dt, nu, drag, kappa, grad=(0.0, 0.0),
+                                  buoyancy=(0.0, 0.0), lin=None, noise=None, nsteps=1):
+    """spec_ns_step_scalar_tangent_ with K pairs (dwhat, dthat) (float32 [K, B, my1, nx, 2] each, K <= 32) on the one base (what, that): the
+    base and every pair (dwhat[k], dthat[k]) bitwise as from that call with the pair alone (no dghat), the base's transforms and column passes
+    done once for all K.  work: spec_ns_scalar_tangents_workspace bytes.  8 launches per step and one per call, no allocation, no host
+    synchronisation: capturable."""
+    who = 'spec_ns_step_scalar_tangents'
+    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
+    _spec_ns_same(who, that, what)
+    K = _spec_ns_tangents(who, dwhat, ny, B, my1, nx, what.device)[0]
+    _spec_ns_same(who, dthat, dwhat, 'dthat')
+    gbatch = _spec_ns_force(who, ghat, what)
+    if lin is not None:
+        _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), what.device)
+    amp, seed, clock, ids = noise or (None, 0, None, None)
+    if noise is not None:
+        _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
+    (gx, gy), (bx, by) = grad, buoyancy
+    check(_lib.lib().nns_spec_ns_step_scalar_tangents_f32(_p(what), _p(that), _p(dwhat), _p(dthat), K, _p(mean), _pn(ghat), gbatch, _p(work),
+                                                          work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt), float(nu), float(drag),
+                                                          float(kappa), float(gx), float(gy), float(bx), float(by), _pn(lin), _pn(amp),
+                                                          int(seed), _pn(clock), _pn(ids), int(nsteps), _stream()),
+          'nns_spec_ns_step_scalar_tangents_f32')
+    return what, that, dwhat, dthat
+
+
+def spec_ns_tangent_variance_gram(dthat, ny, out=None):
+    """float64 [B, K, K]: the variance inner products of the K scalar tangents dthat ([K, B, my1, nx, 2]) per grid, 1/2 <dtheta_k' dtheta_l'>
+    (the means, the (0, 0) entries, do not enter); the diagonal is bitwise column 0 of spec_ns_scalar_diag of each member.  Bitwise
+    symmetric and repeatable.  No host synchronisation."""
+    who = 'spec_ns_tangent_variance_gram'
+    K, B, my1, nx = _spec_ns_tangents(who, dthat, ny)
+    out = _spec_ns_out(who, out, (B, K, K), dthat.device)
+    check(_lib.lib().nns_spec_ns_tangent_variance_gram_f64(_p(dthat), K, _p(out), B, nx, int(ny), _stream()),
+          'nns_spec_ns_tangent_variance_gram_f64')
+    return out
+
+
 def spec_ns_linear_spectrum(what, rate, ny, Lx, Ly, out=None):
     """float64 [B, 2, nshell]: (D_E, D_Z) per shell, the rates at which the linear term changes energy and enstrophy; rate = Re(lambda)
     float64 [my1, nx] on the state's device."""

@@ -389,8 +389,14 @@ class PeriodicSolver(object):
     vorticity's factors, dtheta^ the scalar's real E_theta and keeps its (0, 0) mode, which is carried unchanged and acts on nothing
     (tests/pspec_scalar_tangent_oracle.py).  The pair rides in the scalar step's launches (still 8 per step).  ``evolve_tangent_scalar`` /
     ``evolve_velocity_tangent_scalar`` are the field-level forms, ``lyapunov_exponent_scalar`` the leading exponent in the norm
-    E(dw) + scalar_weight 1/2 <dtheta'^2>.  ``step_tangent``, ``lyapunov_exponent``, ``step_tangents`` and ``lyapunov_spectrum`` keep refusing
-    a state that carries a scalar.  Not built: K tangents with a scalar (``step_tangents`` / ``lyapunov_spectrum`` on such a state), the
+    E(dw) + scalar_weight 1/2 <dtheta'^2>.  K pairs on one base with a scalar: ``step_tangents_scalar(state, dwhat, dthat, nsteps)`` carries
+    K <= 32 pairs [K, B, my1, nx, 2] (``init_tangents_scalar``), the state bitwise as by ``step`` and every pair bitwise as by
+    ``step_tangent_scalar`` alone, the base's three inverse and two forward y-transforms and its two passes through a column tile done once
+    for all K; ``tangent_gram_scalar`` is the Gram matrix in that norm (the energy Gram of dwhat + scalar_weight times the variance Gram of
+    dthat, both float64 HIP), ``orthonormalize_tangents_scalar`` the same Cholesky QR done twice on the pair and
+    ``lyapunov_spectrum_scalar`` the first K exponents (tests/pspec_scalar_lyapunov_oracle.py); ``kaplan_yorke_dimension`` applies.
+    ``step_tangent``, ``lyapunov_exponent``, ``step_tangents`` and ``lyapunov_spectrum`` keep refusing
+    a state that carries a scalar.  Not built: the
     tangent in ``operator``, a source perturbation per tangent, covariant vectors, a ``jvp`` hook on the autograd node for
     ``torch.autograd.forward_ad``, and reverse mode through the tangent (Hessian-vector products).
 
@@ -966,8 +972,8 @@ class PeriodicSolver(object):
         if state is not None:
             self._state(state)
             if state.that is not None:
-                raise NotImplementedError("%s: the tangent of the scalar system is not built yet: the state carries a scalar (passive or buoyant); "
-                                          "a state without one is stepped as by step" % who)
+                raise NotImplementedError("%s: the tangent of the scalar system is not built here: the state carries a scalar (passive or buoyant); "
+                                          "use %s_scalar, or a state without one" % (who, who))
         if not isinstance(dwhat, torch.Tensor):
             raise TypeError("%s: dwhat must be a torch tensor, got %s" % (who, type(dwhat).__name__))
         want = (self.my1, self.nx, 2) if state is None else tuple(state.what.shape[1:])
@@ -1025,15 +1031,25 @@ class PeriodicSolver(object):
         synchronises.  The logs of the two passes add.  A grid whose vectors are dependent gives nan, as ``lyapunov_exponent`` does for a
         perturbation without energy."""
         K = self._tangent_spectra('orthonormalize_tangents', dwhat)
-        eye = torch.eye(K, dtype=torch.float64, device=dwhat.device)
+        return self._cholesky_qr_twice(K, dwhat.device, lambda: ops.spec_ns_tangent_gram(dwhat, self.ny, self.Lx, self.Ly),
+                                       lambda rinv: ops.spec_ns_tangent_combine_(dwhat, rinv, self.ny))
+
+    @staticmethod
+    def _cholesky_qr_twice(K, device, gram_of, combine, pivot_floor=0.0):
+        """The K x K algebra of ``orthonormalize_tangents`` and ``orthonormalize_tangents_scalar``: twice, the Gram matrix ``gram_of()``
+        (float64 [B, K, K]) factored, ``combine(R^-1)`` applied to the vectors, the logs of diag R added.  nan where a pivot fails: it is not
+        positive or (``pivot_floor`` > 0) R_kk^2 <= pivot_floor G_kk, a vector within rounding of the span of those before it."""
+        eye = torch.eye(K, dtype=torch.float64, device=device)
         logs = None
         for _ in range(2):
-            gram = ops.spec_ns_tangent_gram(dwhat, self.ny, self.Lx, self.Ly)
+            gram = gram_of()
             low, info = torch.linalg.cholesky_ex(gram, check_errors=False)                  # gram = low low^T: R = low^T
             rinv = torch.linalg.solve_triangular(low.transpose(-1, -2), eye.expand_as(gram), upper=True).contiguous()
-            ops.spec_ns_tangent_combine_(dwhat, rinv, self.ny)
+            combine(rinv)
             diag = torch.diagonal(low, dim1=-2, dim2=-1)
             failed = (info != 0) | ~(diag > 0).all(dim=-1)                                  # a pivot that is not positive: dependent vectors
+            if pivot_floor > 0:
+                failed = failed | ~(diag * diag > pivot_floor * torch.diagonal(gram, dim1=-2, dim2=-1)).all(dim=-1)
             lg = torch.where(failed.unsqueeze(-1), torch.full_like(diag, float('nan')), torch.log(diag))
             logs = lg if logs is None else logs + lg
         return logs
@@ -1052,6 +1068,112 @@ class PeriodicSolver(object):
             n = min(every, nsteps - done)
             self.step_tangents(state, dwhat, n)
             total += self.orthonormalize_tangents(dwhat)
+            done += n
+        return total / (nsteps * self.dt)
+
+    # ---- K tangent pairs on one base with a scalar
+    def _tangent_pairs(self, who, dwhat, dthat, state=None):
+        """The checked tangent pairs (dwhat, dthat), [K, B, my1, nx, 2] each, of ``who`` (for this state, which must carry a scalar); K."""
+        if self.kappa is None:
+            raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use %s"
+                             % (who, who.replace('_scalar', '')))
+        if state is not None:
+            self._state(state)
+            if state.that is None:
+                raise ValueError("%s: the state carries no scalar (build it with init(u, v, theta) on a solver with kappa); "
+                                 "without one use %s" % (who, who.replace('_scalar', '')))
+        want = (self.my1, self.nx, 2) if state is None else tuple(state.what.shape[1:])
+        for name, d in (('dwhat', dwhat), ('dthat', dthat)):
+            if not isinstance(d, torch.Tensor):
+                raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(d).__name__))
+            if d.dtype != torch.float32 or d.dim() != 5 or tuple(d.shape[2:]) != want or not d.is_cuda or not d.is_contiguous() \
+                    or (state is not None and (d.shape[1] != state.batch or d.device != state.what.device)):
+                raise ValueError("%s: %s must be a contiguous float32 [K, %s, %d, %d, 2] tensor on the %s (init_tangents_scalar(dw, dtheta)), "
+                                 "got %s %s on %s" % (who, name, 'B' if state is None else state.batch, self.my1, self.nx,
+                                                      "device" if state is None else "state's device", d.dtype, tuple(d.shape), d.device))
+        if tuple(dthat.shape) != tuple(dwhat.shape) or dthat.device != dwhat.device:
+            raise ValueError("%s: dwhat and dthat must share their shape and device, got %s on %s and %s on %s"
+                             % (who, tuple(dwhat.shape), dwhat.device, tuple(dthat.shape), dthat.device))
+        K = int(dwhat.shape[0])
+        if not 1 <= K <= ops.SPEC_NS_MAX_TANGENTS:
+            raise ValueError("%s: K = %d tangents, must be in [1, %d]" % (who, K, ops.SPEC_NS_MAX_TANGENTS))
+        return K
+
+    def init_tangents_scalar(self, dw, dtheta):
+        """(dwhat, dthat), [K, B, my1, nx, 2] each: the spectra of K perturbation pairs (dw, dtheta) (float32 [K, B, nx, ny] each).  dwhat is
+        ``init_tangents(dw)``; dthat is ``ops.spec_ns_scalar_init`` on the K B fields: the band-limited part with the mean, the (0, 0) mode, kept."""
+        if self.kappa is None:
+            raise ValueError("init_tangents_scalar needs a solver built with kappa (the scalar's diffusivity); without a scalar use init_tangents")
+        dwhat = self.init_tangents(dw)
+        dtheta = torch.as_tensor(dtheta)
+        if tuple(dtheta.shape) != tuple(torch.as_tensor(dw).shape):
+            raise ValueError("dtheta: %s expected (the shape of dw), got %s" % (tuple(torch.as_tensor(dw).shape), tuple(dtheta.shape)))
+        K, B = int(dwhat.shape[0]), int(dwhat.shape[1])
+        theta = self._field('dtheta', dtheta.reshape(K * B, self.nx, self.ny)).to(dwhat.device).contiguous()
+        flat = dwhat.reshape(K * B, self.my1, self.nx, 2)
+        work = self._work(ops.spec_ns_workspace, K * B, dwhat.device)
+        dthat = ops.spec_ns_scalar_init(theta, torch.empty_like(flat), work)
+        return dwhat, dthat.reshape(K, B, self.my1, self.nx, 2)
+
+    def step_tangents_scalar(self, state, dwhat, dthat, nsteps=1):
+        """``step(state, nsteps)`` on a state that carries a scalar -- bitwise, ``state.steps`` and ``state.clock`` included -- with the K
+        tangent pairs (``dwhat``, ``dthat``) (float32 [K, B, my1, nx, 2] each, ``init_tangents_scalar``) advanced in place and returned,
+        every pair bitwise as by ``step_tangent_scalar`` on a clone of the state (the class note, "Forward mode").  Grows ``state.work`` to
+        the workspace of K pairs on first use (take one step outside before capturing one in a graph); otherwise no allocation and no host
+        synchronisation.  ValueError on a state without a scalar (use ``step_tangents``)."""
+        K = self._tangent_pairs('step_tangents_scalar', dwhat, dthat, state)
+        nsteps = _count('nsteps', nsteps, 0)
+        lin = self._linear_of(state) if self._linear() else None
+        noise = None
+        if self.stoch_amp is not None:
+            amp, clock, ids = self._noise_of(state)
+            noise = (amp, self.stoch_seed, clock, ids)
+        state.work = self._work(lambda B, nx, ny: ops.spec_ns_scalar_tangents_workspace(B, K, nx, ny), state.batch, state.what.device,
+                                have=state.work)
+        ops.spec_ns_step_scalar_tangents_(state.what, state.that, dwhat, dthat, state.mean, self._force_of(state), state.work, self.ny, self.Lx,
+                                          self.Ly, self.dt, self.nu, self.drag, self.kappa, self.scalar_gradient, self.buoyancy, lin, noise,
+                                          nsteps)
+        state.steps += nsteps
+        return dwhat, dthat
+
+    def tangent_gram_scalar(self, dwhat, dthat, scalar_weight=1.0):
+        """float64 [B, K, K] on the device: the Gram matrix of the K tangent pairs of every grid in the inner product of
+        ``lyapunov_exponent_scalar``, 1/2 <du_k . du_l> + scalar_weight 1/2 <dtheta_k' dtheta_l'> (``scalar_weight`` > 0; the means of dtheta
+        do not enter): ``tangent_gram(dwhat)`` + scalar_weight times the variance Gram matrix of dthat.  Bitwise symmetric and repeatable."""
+        self._tangent_pairs('tangent_gram_scalar', dwhat, dthat)
+        weight = _real('scalar_weight', scalar_weight, '> 0')
+        return ops.spec_ns_tangent_gram(dwhat, self.ny, self.Lx, self.Ly) + weight * ops.spec_ns_tangent_variance_gram(dthat, self.ny)
+
+    def orthonormalize_tangents_scalar(self, dwhat, dthat, scalar_weight=1.0):
+        """``orthonormalize_tangents`` of the K pairs under the inner product of ``tangent_gram_scalar``: (dwhat, dthat) <- Q in place, both
+        spectra recombined with the one coefficient matrix (the means of dtheta combine with the rest: a tangent is linear), and
+        log(diag R), float64 [B, K] on the device, returned.  The same Cholesky QR done twice, nan convention and absence of
+        synchronisation.  The Gram matrix is a sum of two float64 matrices, so the pivot of an exactly dependent vector is rounding noise of
+        either sign where the energy Gram alone cancels to zero: a pivot with R_kk^2 <= 1e-13 G_kk (450 float64 ulps; the nearly dependent
+        sets a second pass can still repair sit near 1e-10) also counts as failed."""
+        K = self._tangent_pairs('orthonormalize_tangents_scalar', dwhat, dthat)
+        weight = _real('scalar_weight', scalar_weight, '> 0')
+
+        def combine(rinv):
+            ops.spec_ns_tangent_combine_(dwhat, rinv, self.ny)
+            ops.spec_ns_tangent_combine_(dthat, rinv, self.ny)
+        return self._cholesky_qr_twice(K, dwhat.device, lambda: ops.spec_ns_tangent_gram(dwhat, self.ny, self.Lx, self.Ly)
+                                       + weight * ops.spec_ns_tangent_variance_gram(dthat, self.ny), combine, pivot_floor=1e-13)
+
+    def lyapunov_spectrum_scalar(self, state, dwhat, dthat, nsteps, renormalize_every, scalar_weight=1.0):
+        """``lyapunov_spectrum`` of the system with a scalar, float64 [B, K] on the device, in the norm of ``lyapunov_exponent_scalar``: the
+        pairs are orthonormalised (``orthonormalize_tangents_scalar``) at the start and after every ``renormalize_every`` steps of
+        ``step_tangents_scalar``.  State and pairs are advanced in place; the pairs are left orthonormal.  ``kaplan_yorke_dimension`` applies
+        to the result.  No host synchronisation."""
+        self._tangent_pairs('lyapunov_spectrum_scalar', dwhat, dthat, state)
+        nsteps, every = _count('nsteps', nsteps, 1), _count('renormalize_every', renormalize_every, 1)
+        _real('scalar_weight', scalar_weight, '> 0')
+        total = torch.zeros_like(self.orthonormalize_tangents_scalar(dwhat, dthat, scalar_weight))
+        done = 0
+        while done < nsteps:
+            n = min(every, nsteps - done)
+            self.step_tangents_scalar(state, dwhat, dthat, n)
+            total += self.orthonormalize_tangents_scalar(dwhat, dthat, scalar_weight)
             done += n
         return total / (nsteps * self.dt)
 
