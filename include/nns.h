@@ -730,6 +730,45 @@ int nns_spec_ns_step_scalar_tangents_f32(float* what, float* that, float* dwhat,
                                          double nu, double drag, double kappa, double gx, double gy, double bx, double by, const float* lin,
                                          const float* amp, unsigned long long seed, long long* clock, const int* ids, int nsteps, void* stream);
 int nns_spec_ns_tangent_variance_gram_f64(const float* dthat, int ntan, double* out, int batch, int nx, int ny, void* stream);
+/* Second-order adjoint of the flow's step (restatement: tests/pspec_second_adjoint_oracle.py): the derivative of the reverse mode in a
+ * direction, which is the Hessian-vector product of a loss of the rollout.  With (wbar, gbar) = J^T lam of nns_spec_ns_step_adjoint_f32 /
+ * nns_spec_ns_step_linear_adjoint_f32 as a function of the start spectrum w0, the source g^ and the cotangent lam, this call also gives
+ *     (dwbar, dgbar) = d/de (wbar, gbar)(w0 + e dw0, g^ + e dg^, lam + e dlam) at e = 0.
+ * N is bilinear, so N'(s)^T kappa is linear in s, and the derivative of an adjoint stage is the same operator about the TANGENT stage state,
+ * without the mean flow.  With s0..s3 the stage states, d0..d3 the tangent stages of nns_spec_ns_step_tangent_f32, F = conj(E), F2 = conj(E^2)
+ * (a real E: E, E^2), N'(s)^T kappa as in nns_spec_ns_step_adjoint_f32 and N'_0(d)^T kappa the same expression with u, v, w_x, w_y of d and zero
+ * mean flow, one step is
+ *     k4 = dt/6 lam                  dk4 = dt/6 dlam
+ *     r  = N'(s3)^T k4               dr  = N'(s3)^T dk4 + N'_0(d3)^T k4      wbar  = F2 (lam + r)    dwbar  = F2 (dlam + dr)
+ *     k3 = dt/3 F lam + dt F r       dk3 = dt/3 F dlam + dt F dr
+ *     r  = N'(s2)^T k3               dr  = N'(s2)^T dk3 + N'_0(d2)^T k3      wbar += F r             dwbar += F dr
+ *     k2 = dt/3 F lam + dt/2 r       dk2 = dt/3 F dlam + dt/2 dr
+ *     r  = N'(s1)^T k2               dr  = N'(s1)^T dk2 + N'_0(d1)^T k2      wbar += F r             dwbar += F dr
+ *     k1 = dt/6 F2 lam + dt/2 F r    dk1 = dt/6 F2 dlam + dt/2 F dr
+ *     r  = N'(s0)^T k1               dr  = N'(s0)^T dk1 + N'_0(d0)^T k1      wbar += r               dwbar += dr
+ *     gbar += k1 + k2 + k3 + k4      dgbar += dk1 + dk2 + dk3 + dk4
+ * The left column is the adjoint, unchanged: lam and gbar come out BITWISE as from nns_spec_ns_step_adjoint_f32 (lin == NULL) or
+ * nns_spec_ns_step_linear_adjoint_f32 without a scalar (lin: the forward's table; nu and drag are then ignored).  A stochastic step is
+ * differentiated as the deterministic step it contains: the saved starts carry the kicks, the tangent takes none, the generator never runs.
+ * what0, dwhat0: float32 [nsteps][batch][my1][nx][2], the spectrum and its tangent at the start of every step as a forward of
+ * nns_spec_ns_step_tangent_f32 in one-step calls saved them; only read.  mean, ghat / gbatch, dghat / dgbatch: that forward's.  lam, dlam:
+ * float32 [batch][my1][nx][2], in the cotangent of the state after the last step and its derivative in the direction, out (wbar, dwbar) before
+ * the first step; both updated in place.  gbar, dgbar: the same shape, overwritten with the sums over the steps, one per grid; either or both
+ * may be NULL.  Per step the stages (s_i, d_i) are recomputed by the tangent step's 7 launches, whose column kernels of stages 1-3 also store
+ * them, then 9 adjoint launches carry both quadruples: 16 launches per step, no allocation, no host synchronisation (capturable), no atomics;
+ * a grid's result does not depend on its batch neighbours; lam and dlam of nsteps steps in one call are bitwise those of nsteps calls of one
+ * step, last first (gbar and dgbar are then the sums of those calls', rounded in another order); linear in (dwhat0, dghat, dlam) exactly for
+ * powers of two.  nsteps == 0 zeroes gbar and dgbar.  work: nns_spec_ns_second_adjoint_workspace bytes: 24
+ * compacted fields of batch my1 nx complex each (two accumulators that become wbar and dwbar, G 12, Ph 4, the kept stages s1-s3 and d1-d3),
+ * never below nns_spec_ns_workspace: >= nns_spec_ns_adjoint_workspace (13) and nns_spec_ns_tangent_workspace (12).  No scalar and no
+ * derivative in the table.  Errors, all before any launch and in this order: NNS_ERR_INVALID_ARG for a NULL what0, mean, lam or work or
+ * batch < 1, then for a NULL dwhat0 or dlam, then for dt, nu, drag (without lin) or nsteps out of range, then for gbatch, then for dgbatch not 0
+ * without dghat, 1 or batch with it; then the box and the axes; then NNS_ERR_WORKSPACE below nns_spec_ns_second_adjoint_workspace. */
+int nns_spec_ns_second_adjoint_workspace(int batch, int nx, int ny, size_t* bytes);
+int nns_spec_ns_step_second_adjoint_f32(const float* what0, const float* dwhat0, const float* mean, const float* ghat, int gbatch,
+                                        const float* dghat, int dgbatch, float* lam, float* dlam, float* gbar, float* dgbar, void* work,
+                                        size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
+                                        const float* lin, int nsteps, void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

@@ -7,11 +7,18 @@
 // factors are conj(E) - 1, conj(E^2) - 1 from the table and scal's complex form applies.  The scalar's stay real.
 // OPERATOR (a PsAdjOperator / PsAdjScalarOperator, LINEAR with it) is false in every other kernel, whose text is then what it was; with one
 // the vorticity's pass of stages 3-1 also sums the table's cotangent of the step in ad.lstep and adds it to ad.lbar, lane-owned like gbar.
-// In scope: the names of pspec_col_tile.inc, consume, field, ad (PsAdj, or PsAdjScalar where TH is true), tv, ky, dt, dt2, dt3, dt6.
+// TD (ps_col_adj_kernel's SECOND form, TH false with it) is false in every other kernel, whose code is then what it was; with it the pass is the
+// vorticity's on the second quadruple: Ph fields 2 and 3, dlam / dwbar / dgbar (ginit starts dgbar as it starts gbar), grad dkappa to G fields
+// 10 and 11.  The sum of kappa has its statements twice, for ad.gbar and for ad.dgbar: one pointer chosen at the head of the pass compiled the
+// flow's stage 4 to other instructions.
+// In scope: the names of pspec_col_tile.inc, consume, field, ad (PsAdj; PsAdjScalar where TH is true, PsAdjSecond where TD is), tv, ky, dt, dt2, dt3, dt6.
 {
         float2* lamp;
         float2* barp;
-        if constexpr (TH) {
+        if constexpr (TD) {
+            lamp = ad.dlam;
+            barp = ad.dwbar;
+        } else if constexpr (TH) {
             lamp = ad.mu;
             barp = ad.tbar;
         } else {
@@ -24,6 +31,10 @@
             [[maybe_unused]] cf z[16];
             if constexpr (TH) {
                 consume(Ph + 2 * a.fstride, r);
+            } else if constexpr (TD) {
+                consume(Ph + 2 * a.fstride, r);
+                __syncthreads();                    // the next staging overwrites line images other waves may still read
+                consume(Ph + 3 * a.fstride, z);
             } else {
                 consume(Ph, r);
                 __syncthreads();                    // the next staging overwrites line images other waves may still read
@@ -114,7 +125,12 @@
                         lamp[si] = make_float2(wb.x, wb.y);
                     } else {
                         barp[si] = make_float2(wb.x, wb.y);
-                        if constexpr (!TH) {
+                        if constexpr (TD) {
+                            if (ad.dgbar) {
+                                const float2 g2 = ad.dgbar[si];
+                                ad.dgbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
+                            }
+                        } else if constexpr (!TH) {
                             if (ad.gbar) {
                                 const float2 g2 = ad.gbar[si];
                                 ad.gbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
@@ -132,7 +148,12 @@
                 const size_t si = wbase + e;
                 const float2 l2 = lok ? lamp[si] : make_float2(0.f, 0.f);
                 kap[m] = keep ? cf{dt6 * l2.x, dt6 * l2.y} : cf{0.f, 0.f};
-                if constexpr (!TH) {
+                if constexpr (TD) {
+                    if (lok && ad.dgbar) {
+                        const float2 g2 = ad.ginit ? make_float2(0.f, 0.f) : ad.dgbar[si];
+                        ad.dgbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
+                    }
+                } else if constexpr (!TH) {
                     if (lok && ad.gbar) {
                         const float2 g2 = ad.ginit ? make_float2(0.f, 0.f) : ad.gbar[si];
                         ad.gbar[si] = make_float2(g2.x + kap[m].x, g2.y + kap[m].y);
@@ -141,7 +162,7 @@
             }
         }
         if constexpr (S >= 1) {
-            static_for<TH ? 8 : 4, TH ? 10 : 6>([&](auto fc) { field(fc, kap); });
+            static_for<TD ? 10 : TH ? 8 : 4, TD ? 12 : TH ? 10 : 6>([&](auto fc) { field(fc, kap); });
         } else {
             __syncthreads();                        // the next staging overwrites line images other waves may still read
         }

@@ -9,7 +9,8 @@
 // (a lambda's body is optimised on its own before it is inlined, and came out a few instructions and registers different).
 // STOCH (ps_col_kernel's note) is false in every kernel without a PsStoch argument, whose text below is then what it was.
 // LINEAR likewise (a PsLinear argument): the vorticity's factors E - 1, E^2 - 1 are then complex, from the table lin, and scal's complex form applies.
-// STAGES likewise (a PsKeep or a PsKeepScalar argument): stages 1-3 also store the next stage's input to stage_out (the scalar's to tstage_out).
+// STAGES likewise (a PsKeep, a PsKeepScalar or a PsKeepTangent argument): stages 1-3 also store the next stage's input to stage_out (the scalar's
+// to tstage_out, the tangent's to dstage_out).
 // The staged forward transform and the field emit are text of their own (pspec_stage.inc, pspec_field.inc), shared with ps_col_adj_kernel and
 // ps_transfer_kernel; the tile's names (lok, lj, wbase, sok, ...) are those of pspec_col_tile.inc.
 {
@@ -93,7 +94,9 @@
                     if (lok) Ws[si] = make_float2(w.x, w.y);
                     y[m] = w;
                 }
-                if constexpr (STAGES) {
+                if constexpr (STAGES && TG) {
+                    if (lok) dstage_out[si] = make_float2(y[m].x, y[m].y);
+                } else if constexpr (STAGES) {
                     if (lok) (TH ? tstage_out : stage_out)[si] = make_float2(y[m].x, y[m].y);
                 }
             }

@@ -143,6 +143,21 @@
 // ps_tangent_variance_gram_kernel, the scalar half of the pairs' inner product; every other kernel keeps its name and its code
 // (profiles/pspec_scalar_tangents_isa.txt, no scratch; times: profiles/pspec_scalar_tangents_run.json).
 //
+// Second-order adjoint (nns_spec_ns_step_second_adjoint_f32; restatement: tests/pspec_second_adjoint_oracle.py): the derivative of the
+// reverse mode above in a direction (dw^, dg^, dlam) -- the Hessian-vector product of a loss of the rollout.  N is bilinear, so N'(s)^T kappa is
+// linear in s and in kappa, and the derivative of an adjoint stage is
+//     dr = N'(s_i)^T dkappa + N'_0(d_i)^T kappa,
+// d_i the tangent stage state (that of nns_spec_ns_step_tangent_f32) and N'_0 the same operator with u, v, w_x, w_y of d_i and no mean flow;
+// the Lawson recurrences of ps_col_adj_kernel's note are linear, so (dlam, dkappa, dwbar, dgbar) obey them with dr where they have r.  A second
+// quadruple that rides in the adjoint's launches: the recomputation is the TANGENT step's (its column kernels of stages 1-3 take a trailing
+// PsKeepTangent and store the next stage's w^ and dw^), ps_row_adj2_kernel<ny> runs six inverse and four forward transforms (its note), and a
+// PsAdjSecond (PsAdjSecondLinear: the LINEAR twin) makes ps_col_adj_kernel include pspec_col_adj_pass.inc once more per tile (TD) on dlam / dwbar /
+// dgbar, Ph fields 2 and 3 and G fields 10 and 11, then prepare the tangent stage's four spectra as G fields 6-9 with zero means.  The first
+// quadruple's arithmetic is the adjoint's, so lam and gbar come out bitwise as from nns_spec_ns_step_adjoint_f32 / _linear_adjoint_f32.  Still
+// 7 + 9 launches per step, one more row of PsLayout (2 accumulators, 12 G, 4 Ph, 6 kept stages: 24 compacted fields).  The new kernels are
+// instantiated in pspec_second_adjoint.hip (this text under PSPEC_SECOND_ADJOINT_TU); every other kernel keeps its name and its code
+// (profiles/pspec_second_adjoint_isa.txt, no scratch).
+//
 // Init / output (not the hot path) use the standalone rfft2 / irfft2 (spectral_ops.hip) plus the pointwise kernels below.
 //
 // What the row and column kernels share has one copy each: the LDS layout, PsArgs and the row pass's Hermitian fill and kept-mode store in
@@ -165,7 +180,13 @@ int ps_scalar_tangent_row(int ny, const void* G, void* Ph, const void* a, void* 
 int ps_scalar_tangents_col(int nx, int S, const void* Ph, void* G, void* W, void* A, const float* mean, const void* a, int emit, const void* fc,
                            const void* sc, void* stream, const void* st, const void* li, const void* ts, const void* tu);
 int ps_scalar_tangents_row(int ny, const void* G, void* Ph, const void* a, void* stream, const void* gr, int buoyant, int K);
-#if defined(PSPEC_SCALAR_TANGENT_TU) || defined(PSPEC_SCALAR_TANGENTS_TU)
+// The kernels of the second-order adjoint likewise (pspec_second_adjoint.hip, PSPEC_SECOND_ADJOINT_TU); tg: PsTangent, ke: PsKeepTangent, ad: a
+// PsAdjSecond, lin: the table of a linear step or NULL (stages 3-1 then take the PsAdjSecondLinear built from ad and lin).
+int ps_second_adjoint_col_keep(int nx, int S, const void* Ph, void* G, void* W, void* A, const float* mean, const void* a, const void* fc,
+                               const void* li, void* stream, const void* tg, const void* ke);
+int ps_second_adjoint_row(int ny, const void* G, void* Ph, const void* a, void* stream);
+int ps_second_adjoint_col(int nx, int S, const void* Ph, void* G, const float* mean, const void* a, const void* ad, const void* lin, void* stream);
+#if defined(PSPEC_SCALAR_TANGENT_TU) || defined(PSPEC_SCALAR_TANGENTS_TU) || defined(PSPEC_SECOND_ADJOINT_TU)
 #define PSPEC_KERNEL_TU      // a translation unit of kernels and their launches alone: no host entry point
 #endif
 
@@ -227,6 +248,10 @@ struct PsKeepScalar {     // PsKeep of the SCALAR kernels (after PsScalar): the 
     float2* stage;        // [B][my1][nx]: the next stage's w^
     float2* tstage;       // [B][my1][nx]: the next stage's theta^
 };
+struct PsKeepTangent {    // PsKeep of the TANGENT kernels (last in the pack, after the PsLinear of a linear step): the second-order adjoint recomputes both spectra
+    float2* stage;        // [B][my1][nx]: the next stage's w^
+    float2* dstage;       // [B][my1][nx]: the next stage's dw^
+};
 struct PsAdj {            // the argument of the adjoint column kernels
     float2* lam;          // [B][my1][nx]: the cotangent of the step's result; stage 0 writes the cotangent of its input over it
     float2* wbar;         // [B][my1][nx]: the cotangent of the step's input while it is summed (stages 3..0)
@@ -259,6 +284,15 @@ struct PsAdjScalarOperator : PsAdjScalarLinear {      // the same with a scalar,
     float2* lstep;
     const float2* own;
     const float2* w0;
+};
+struct PsAdjSecond : PsAdj {      // the second-order adjoint (nns_spec_ns_step_second_adjoint_f32): PsAdj and its twin for the derivative in the direction
+    float2* dlam;         // [B][my1][nx]: the derivative of lam; stage 0 writes that of the cotangent of the step's input over it
+    float2* dwbar;        // [B][my1][nx]: the derivative of wbar while it is summed (stages 3..0)
+    float2* dgbar;        // [B][my1][nx] or NULL: the derivative of gbar, summed over stages and steps (ginit starts it, as it starts gbar)
+    const float2* dstate; // [B][my1][nx]: the tangent stage state that belongs to state (S = 4: d3, 3: d2, 2: d1, 1: d0), unused by S = 0
+};
+struct PsAdjSecondLinear : PsAdjSecond {      // its LINEAR form (stages 3-1 of a linear step): both quadruples take conj(E), conj(E^2) from the table
+    const float2* lin;
 };
 struct PsAdjGrad {        // the argument of the scalar adjoint row kernel: the uniform mean gradient and the buoyancy
     float gx, gy, bx, by;
@@ -667,6 +701,7 @@ __global__ __launch_bounds__(kT) void ps_row_tans_scalar_kernel(const float2* __
 // STAGES (a PsKeep ends the pack, after the PsLinear of a linear step; S = 1..3): the next stage's input spectrum is also stored, lane-owned and coalesced like W / A, for the
 // adjoint (ps_col_adj_kernel) to linearise about; the arithmetic is untouched, so the recomputed stages are the forward's bits.  With a scalar
 // the pack ends in a PsKeepScalar after the PsScalar, and theta^'s next stage input is stored as well (ps_col_adj_kernel with a PsAdjScalar).
+// With a tangent (the flow's alone) the pack ends in a PsKeepTangent, and dw^'s next stage input is stored as well (ps_col_adj_kernel with a PsAdjSecond).
 // TANGENT (a PsTangent first in the pack, where a PsScalar would be; with one only in the TANSC form below, never with a PsKeep): after the vorticity's work on a tile the
 // same text runs once more on the perturbation dw^: Ph's second field, dw^ / dA with the VORTICITY's factors (hdrag and the LINEAR complex ones
 // included) and mask, dg^ where the vorticity adds g^ (also under an unforced base, whose own arithmetic stays the unforced kernel's), no kick
@@ -693,15 +728,17 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     constexpr bool TANSC = (std::is_same_v<Sc, PsTangentScalar> || ... || false);
     constexpr bool TANSCS = (std::is_same_v<Sc, PsTangentsScalar> || ... || false);
     constexpr bool KEEP_W = (std::is_same_v<Sc, PsKeep> || ... || false), KEEP_WT = (std::is_same_v<Sc, PsKeepScalar> || ... || false);
-    constexpr bool STAGES = KEEP_W || KEEP_WT;
+    constexpr bool KEEP_WD = (std::is_same_v<Sc, PsKeepTangent> || ... || false);
+    constexpr bool STAGES = KEEP_W || KEEP_WT || KEEP_WD;
     static_assert(sizeof...(Sc) == (SCALAR ? 1 : 0) + (TANGENT ? 1 : 0) + (TANGENTS ? 1 : 0) + (TANSC ? 1 : 0) + (TANSCS ? 1 : 0) + (STOCH ? 1 : 0) + (LINEAR ? 1 : 0) + (STAGES ? 1 : 0),
                   "PsScalar is the SCALAR kernel's argument (PsTangent the TANGENT kernel's), PsLinear after it the LINEAR kernel's, PsStoch or the PsKeep last");
-    static_assert(!TANGENT || (SCALAR == TANSC && !STAGES), "the tangent of the scalar system takes a PsScalar, a PsTangent and a PsTangentScalar, and the adjoint's recomputation carries no tangent");
+    static_assert(!TANGENT || (SCALAR == TANSC && (!STAGES || (KEEP_WD && !SCALAR))), "the tangent of the scalar system takes a PsScalar, a PsTangent and a PsTangentScalar; only the flow's tangent is recomputed with a stage store, a PsKeepTangent's");
+    static_assert(!KEEP_WD || TANGENT, "the PsKeepTangent is the TANGENT kernels' stage store");
     static_assert(!TANSC || (SCALAR && TANGENT), "the PsTangentScalar follows a PsScalar and a PsTangent");
     static_assert(!TANGENTS || (SCALAR == TANSCS && !STAGES && !TANGENT), "K tangents: as the one tangent, and never beside it; with a scalar a PsTangentsScalar follows");
     static_assert(!TANSCS || (SCALAR && TANGENTS), "the PsTangentsScalar follows a PsScalar and a PsTangents");
     static_assert(!STAGES || (S >= 1 && S <= 3 && KEEP_WT == SCALAR && !STOCH),
-                  "the stage store is that of stages 1-3 of the steady and the linear forms: a PsKeep without a scalar, a PsKeepScalar with one");
+                  "the stage store is that of stages 1-3 of the steady and the linear forms: a PsKeep (with a tangent: a PsKeepTangent) without a scalar, a PsKeepScalar with one");
     static_assert(!LINEAR || (FORCED && S >= 1 && S <= 3), "the complex factors are those of stages 1-3 of the forced form");
     static_assert(!STOCH || (FORCED && (S == 1 || S == 4)), "the kick is stage 4's and the step count stage 1's, both of the forced form");
     using L = PsLds<N>;
@@ -749,6 +786,11 @@ __global__ __launch_bounds__(kT) void ps_col_kernel(const float2* __restrict__ P
     if constexpr (KEEP_WT) {
         const PsKeepScalar ke = pick<PsKeepScalar>(sc...);
         stage_out = ke.stage; tstage_out = ke.tstage;
+    }
+    [[maybe_unused]] float2* dstage_out = nullptr;
+    if constexpr (KEEP_WD) {
+        const PsKeepTangent ke = pick<PsKeepTangent>(sc...);
+        stage_out = ke.stage; dstage_out = ke.dstage;
     }
     for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
         int tx = threadIdx.x;
@@ -905,6 +947,86 @@ __global__ __launch_bounds__(kT) void ps_row_adj_kernel(const float2* __restrict
     }
 }
 
+// The row pass of the second-order adjoint (nns_spec_ns_step_second_adjoint_f32; restatement: tests/pspec_second_adjoint_oracle.py):
+// ps_row_adj_kernel's twin, as ps_row_tan_kernel is ps_row_kernel's.  G fields 0-3 are the state's (u, v, w_x, w_y, the means in u, v), 4 and 5
+// grad kappa, 6-9 the tangent stage's (du, dv, dw_x, dw_y: no mean flow), 10 and 11 grad dkappa.  Ph fields 0 and 1 take
+//     q1 = u kappa_x + v kappa_y     and     q2 = kappa_x w_y - kappa_y w_x,
+// spelt with ps_row_adj_kernel's expressions from the same transforms of the same G fields, so the first-order cotangents stay bitwise the
+// adjoint's; 2 and 3 their derivatives in the direction,
+//     dq1 = u dkappa_x + v dkappa_y + du kappa_x + dv kappa_y     and     dq2 = dkappa_x w_y - dkappa_y w_x + kappa_x dw_y - kappa_y dw_x.
+// Six inverse transforms, each line read and transformed once, and FOUR forward ones, one per product: packing q + i dq into one forward
+// transform would need the mirrored mode of another lane to take the pair apart again, an exchange the row pass does not have.
+// The order taken: u + i v and grad kappa, q1 out; grad dkappa, whose product with u (16 reals, zp) frees the line of u; grad w into that line,
+// which gives q2 and, with grad dkappa, 16 more reals (zq), q2 out; du + i dv closes dq1, grad dw closes dq2.  grad kappa stays throughout.
+// Each product of dq1 and dq2 has no line in common with the other, so one of them waits as 16 reals while the other's lines come in: three
+// complex lines are live but for the transform of grad w, which runs beside grad kappa, grad dkappa and zp (three and a half, as in
+// ps_row_tans_kernel); holding to three there would take a seventh inverse transform (grad dkappa twice).  The lane's index is pinned anew before
+// each of the three later pairs of transforms (tb, tc, td), as ps_row_tans_kernel pins it per turn: what six loads, ten transforms and four stores
+// derive from it (element offsets, predicates, twiddle addresses) is otherwise computed once and held across the whole row.
+template <int N>
+__global__ __launch_bounds__(kT) void ps_row_adj2_kernel(const float2* __restrict__ G, float2* __restrict__ Ph, PsArgs a) {
+    using L = PsLds<N>;
+    constexpr int TPF = L::TPF;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const cf* tab = ps_tables<N>(smem);
+    unsigned char* lines = smem + L::TAB_BYTES;
+    const int my1 = a.my1;
+    const long niter = (a.nlines + L::LINES - 1) / L::LINES;
+    for (long it = blockIdx.x; it < niter; it += gridDim.x) {
+#include "pspec_row_line.inc"
+        cf zu[16], zk[16], zd[16];
+        float zp[16], zq[16];
+        ps_row_load2<N>(g0, g0 + a.fstride, tid, my1, zu);                           // u + i v
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tid);
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 4 * a.fstride, g0 + 5 * a.fstride, tid, my1, zk);       // kappa_x + i kappa_y: stays
+        fft_line<float, N, true>(zk, tab, tab + N / 2, xb, tid);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zd[m] = {zu[m].x * zk[m].x + zu[m].y * zk[m].y, 0.f};        // u kappa_x + v kappa_y: u, v stay
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zd, tab, tab + N / 2, xb, tid);
+        ps_row_store<N>(zd, Ph + (size_t)row * my1, tid, my1, valid);
+        int tb = tid;
+        asm volatile("" : "+v"(tb));
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 10 * a.fstride, g0 + 11 * a.fstride, tb, my1, zd);     // dkappa_x + i dkappa_y: stays until grad w has met it
+        fft_line<float, N, true>(zd, tab, tab + N / 2, xb, tb);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zp[m] = zu[m].x * zd[m].x + zu[m].y * zd[m].y;               // u dkappa_x + v dkappa_y: u, v leave
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 2 * a.fstride, g0 + 3 * a.fstride, tb, my1, zu);       // w_x + i w_y
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tb);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+            zq[m] = zd[m].x * zu[m].y - zd[m].y * zu[m].x;                                        // dkappa_x w_y - dkappa_y w_x: dkappa leaves
+            zu[m] = {zk[m].x * zu[m].y - zk[m].y * zu[m].x, 0.f};                                 // kappa_x w_y - kappa_y w_x
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tb);
+        ps_row_store<N>(zu, Ph + a.fstride + (size_t)row * my1, tb, my1, valid);
+        int tc = tid;
+        asm volatile("" : "+v"(tc));
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 6 * a.fstride, g0 + 7 * a.fstride, tc, my1, zu);       // du + i dv
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, tc);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zu[m] = {fmaf(zu[m].x, zk[m].x, fmaf(zu[m].y, zk[m].y, zp[m])), 0.f};     // + du kappa_x + dv kappa_y
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zu, tab, tab + N / 2, xb, tc);
+        ps_row_store<N>(zu, Ph + 2 * a.fstride + (size_t)row * my1, tc, my1, valid);
+        int td = tid;
+        asm volatile("" : "+v"(td));
+        __builtin_amdgcn_sched_barrier(0);
+        ps_row_load2<N>(g0 + 8 * a.fstride, g0 + 9 * a.fstride, td, my1, zu);       // dw_x + i dw_y
+        fft_line<float, N, true>(zu, tab, tab + N / 2, xb, td);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) zu[m] = {fmaf(zk[m].x, zu[m].y, fmaf(-zk[m].y, zu[m].x, zq[m])), 0.f};    // + kappa_x dw_y - kappa_y dw_x
+        __builtin_amdgcn_sched_barrier(0);
+        fft_line<float, N, false>(zu, tab, tab + N / 2, xb, td);
+        ps_row_store<N>(zu, Ph + 3 * a.fstride + (size_t)row * my1, td, my1, valid);
+    }
+}
+
 // The adjoint column pass, S = 4 .. 0 in the order it runs (ps_col_kernel's tile: pspec_col_tile.inc, pspec_stage.inc).  With lam the cotangent of the step's
 // result, r = N'(s)^T kappa of the stage just evaluated by the row pass (S < 4: Ph fields 0 and 1 staged and forward-transformed along x,
 // r = keep ? Q1 - Q2 / |k|^2 : 0) and E - 1, E^2 - 1 in the forward's expm1 form:
@@ -945,15 +1067,21 @@ __global__ __launch_bounds__(kT) void ps_row_adj_kernel(const float2* __restrict
 // added, so nsteps steps in one call are bitwise the sum of nsteps calls of one step.  Both are lane-owned like gbar: no atomics, and a grid's
 // sum does not depend on its batch neighbours.  The weight of a stored mode, 1 / n
 // and the symmetry of the ky = 0 line are the caller's (nns.h: nns_spec_ns_step_operator_adjoint_f32).
+// SECOND (a PsAdjSecond, or for stages 3-1 of a linear step a PsAdjSecondLinear; restatement: tests/pspec_second_adjoint_oracle.py): after the
+// vorticity's work on a tile the same text runs once more (TD) on the derivative in the direction: dlam, dkappa, dwbar, dgbar where the first pass
+// has lam, kappa, wbar, gbar, dr = keep ? DQ1 - DQ2 / |k|^2 : 0 from Ph fields 2 and 3, the vorticity's factors (conj(E) from the table in the
+// LINEAR form) and mask, i kx dkappa^, i ky dkappa^ to G fields 10 and 11.  Then the state's four spectra to G fields 0-3 as ever and the tangent
+// stage's (ad.dstate) to G fields 6-9 with zero in the (0, 0) mode.  The first pass is the adjoint's own, so lam, wbar and gbar are its bits.
 template <int N, int S, typename Ad>
 __global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict__ Ph, float2* __restrict__ G, const float* __restrict__ mean,
                                                         PsArgs a, Ad ad) {
     static_assert(S >= 0 && S <= 4, "adjoint stages 4 .. 0");
     constexpr bool OPERATOR = std::is_same_v<Ad, PsAdjOperator> || std::is_same_v<Ad, PsAdjScalarOperator>;
     constexpr bool SCALAR = std::is_same_v<Ad, PsAdjScalar> || std::is_same_v<Ad, PsAdjScalarLinear> || std::is_same_v<Ad, PsAdjScalarOperator>;
-    constexpr bool LINEAR = std::is_same_v<Ad, PsAdjLinear> || std::is_same_v<Ad, PsAdjScalarLinear> || OPERATOR;
-    static_assert(SCALAR || std::is_same_v<Ad, PsAdj> || std::is_same_v<Ad, PsAdjLinear> || std::is_same_v<Ad, PsAdjOperator>,
-                  "a PsAdj, or a PsAdjScalar for the step with a scalar; their LINEAR forms for a linear step, their OPERATOR forms for the table's cotangent");
+    constexpr bool SECOND = std::is_same_v<Ad, PsAdjSecond> || std::is_same_v<Ad, PsAdjSecondLinear>;
+    constexpr bool LINEAR = std::is_same_v<Ad, PsAdjLinear> || std::is_same_v<Ad, PsAdjScalarLinear> || OPERATOR || std::is_same_v<Ad, PsAdjSecondLinear>;
+    static_assert(SCALAR || SECOND || std::is_same_v<Ad, PsAdj> || std::is_same_v<Ad, PsAdjLinear> || std::is_same_v<Ad, PsAdjOperator>,
+                  "a PsAdj, or a PsAdjScalar for the step with a scalar; their LINEAR forms for a linear step, their OPERATOR forms for the table's cotangent; a PsAdjSecond or its LINEAR form for the second-order adjoint");
     static_assert(!LINEAR || (S >= 1 && S <= 3), "the conjugate factors are those of adjoint stages 3-1: stages 4 and 0 apply none");
     using L = PsLds<N>;
     constexpr int TPF = L::TPF, CW = L::LINES, RPI = kT / CW;
@@ -983,11 +1111,15 @@ __global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict
 #include "pspec_field.inc"
         };
         {
-            constexpr bool TH = false;
+            constexpr bool TH = false, TD = false;
 #include "pspec_col_adj_pass.inc"
         }
         if constexpr (SCALAR) {
-            constexpr bool TH = true;
+            constexpr bool TH = true, TD = false;
+#include "pspec_col_adj_pass.inc"
+        }
+        if constexpr (SECOND) {
+            constexpr bool TH = false, TD = true;
 #include "pspec_col_adj_pass.inc"
         }
         if constexpr (S >= 1) {
@@ -998,6 +1130,20 @@ __global__ __launch_bounds__(kT) void ps_col_adj_kernel(const float2* __restrict
                 y[m] = {w.x, w.y};
             }
             static_for<0, 4>([&](auto fc) { field(fc, y); });
+            if constexpr (SECOND) {                     // the tangent stage's four spectra, as ps_col_kernel's tangent pass emits them: no mean flow
+#pragma unroll
+                for (int m = 0; m < 16; ++m) {
+                    const float2 w = lok ? ad.dstate[wbase + tv + TPF * m] : make_float2(0.f, 0.f);
+                    y[m] = {w.x, w.y};
+                }
+                static_for<6, 10>([&](auto fc) {
+                    constexpr int F = decltype(fc)::value, FK = F - 6;
+                    constexpr float U0 = 0.f, V0 = 0.f;
+                    int te = tv;
+                    asm volatile("" : "+v"(te));
+#include "pspec_field.inc"
+                });
+            }
             if constexpr (SCALAR) {
 #pragma unroll
                 for (int m = 0; m < 16; ++m) {
@@ -1535,7 +1681,7 @@ int launch_row_tans_scalar(const float2* G, float2* Ph, const PsArgs& a, int K, 
 template <int N, int S, bool FORCED, typename... X>
 int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* mean, const PsArgs& a, int emit, const PsForce* fc,
                hipStream_t s, X... x) {
-    constexpr bool SC = has<PsScalar, X...>, LI = has<PsLinear, X...>, ST = has<PsStoch, X...>, KE = has<PsKeep, X...> || has<PsKeepScalar, X...>;
+    constexpr bool SC = has<PsScalar, X...>, LI = has<PsLinear, X...>, ST = has<PsStoch, X...>, KE = has<PsKeep, X...> || has<PsKeepScalar, X...> || has<PsKeepTangent, X...>;
     constexpr bool TA = has<PsTangent, X...>, TS = has<PsTangents, X...>, TT = has<PsTangentScalar, X...>, TU = has<PsTangentsScalar, X...>;
     constexpr auto kern = ps_col_kernel<N, S, FORCED, SC, X...>;
     std::conditional_t<FORCED, PsForce, PsNoForce> f{};
@@ -1545,7 +1691,7 @@ int launch_col(const float2* Ph, float2* G, float2* W, float2* A, const float* m
     return check_launch(TU       ? "spec_ns scalar tangents column pass"
                         : TS     ? "spec_ns tangents column pass"
                         : TT     ? "spec_ns scalar tangent column pass"
-                        : TA     ? "spec_ns tangent column pass"
+                        : TA     ? (KE ? "spec_ns stage-keeping tangent column pass" : "spec_ns tangent column pass")
                         : KE     ? "spec_ns stage-keeping column pass"
                         : LI     ? (SC ? "spec_ns linear scalar column pass" : "spec_ns linear column pass")
                         : ST     ? (SC ? "spec_ns stochastic scalar column pass" : "spec_ns stochastic column pass")
@@ -1614,6 +1760,14 @@ int launch_col_keep(int S, const float2* Ph, float2* G, float2* W, float2* A, co
     return with_stage<1, 3>(S, go);
 }
 
+template <int N>
+int launch_row_adj2(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s) {
+    constexpr auto kern = ps_row_adj2_kernel<N>;
+    if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, G, Ph, a);
+    return check_launch("spec_ns second-order adjoint row pass");
+}
+
 // gr: nothing, or with a scalar a PsAdjGrad
 template <int N, typename... Gr>
 int launch_row_adj(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s, Gr... gr) {
@@ -1625,15 +1779,18 @@ int launch_row_adj(const float2* G, float2* Ph, const PsArgs& a, hipStream_t s, 
 }
 
 // ad: a PsAdj, or with a scalar a PsAdjScalar; a PsAdjLinear / PsAdjScalarLinear for stages 3-1 of a linear step's adjoint (no other stage has that form),
-// or there a PsAdjOperator / PsAdjScalarOperator when the table's cotangent is wanted
+// or there a PsAdjOperator / PsAdjScalarOperator when the table's cotangent is wanted; a PsAdjSecond, or for stages 3-1 of a linear step a
+// PsAdjSecondLinear: the second-order adjoint's (named in pspec_second_adjoint.hip only)
 template <int N, typename Ad>
 int launch_col_adj(int S, const float2* Ph, float2* G, const float* mean, const PsArgs& a, const Ad& ad, hipStream_t s) {
-    constexpr bool SC = std::is_base_of_v<PsAdjScalar, Ad>, LI = std::is_base_of_v<PsAdjLinear, Ad> || std::is_base_of_v<PsAdjScalarLinear, Ad>;
+    constexpr bool SC = std::is_base_of_v<PsAdjScalar, Ad>, SE = std::is_base_of_v<PsAdjSecond, Ad>;
+    constexpr bool LI = std::is_base_of_v<PsAdjLinear, Ad> || std::is_base_of_v<PsAdjScalarLinear, Ad> || std::is_base_of_v<PsAdjSecondLinear, Ad>;
     auto go = [&](auto stage_c) {
         constexpr auto kern = ps_col_adj_kernel<N, decltype(stage_c)::value, Ad>;
         if (int rc = lds_opt_in<kern>(PsLds<N>::TOTAL, "spec_ns")) return rc;
         hipLaunchKernelGGL(kern, dim3(grid_of(a.nlines, PsLds<N>::LINES)), dim3(kT), PsLds<N>::TOTAL, s, Ph, G, mean, a, ad);
-        return check_launch(LI   ? (SC ? "spec_ns linear scalar adjoint column pass" : "spec_ns linear adjoint column pass")
+        return check_launch(SE   ? (LI ? "spec_ns linear second-order adjoint column pass" : "spec_ns second-order adjoint column pass")
+                            : LI ? (SC ? "spec_ns linear scalar adjoint column pass" : "spec_ns linear adjoint column pass")
                             : SC ? "spec_ns scalar adjoint column pass"
                                  : "spec_ns adjoint column pass");
     };
@@ -1665,6 +1822,8 @@ size_t scalar_work_bytes(int batch, int nx, int ny) {
 //                        of w^, then of theta^: 21
 //   the tangent step:    A, dA in A_theta's place, G[8], Ph[2]: 12
 //   the scalar tangent:  A, A_theta, dA, dA_theta, G[12], Ph[4]: 20
+//   the second adjoint:  A, dA (wbar and dwbar once the stages are recomputed), G[12], Ph[4] (the recomputation's, the tangent step's: 8 and 2),
+//                        s1, s2, s3 of w^, then d1, d2, d3 of dw^: 24
 //   K tangents:          A, dA[K], G[4 + 4K], Ph[1 + K]: 6 + 6K (tangents_layout; K = 1 is the tangent step's)
 //   K tangents, scalar:  A, A_theta, dA[K], dA_theta[K], G[6 + 6K], Ph[2 + 2K]: 10 + 10K (scalar_tangents_layout; K = 1 is the scalar tangent's)
 struct PsLayout {
@@ -1672,7 +1831,7 @@ struct PsLayout {
     constexpr int fields() const { return acc + g + ph + keep; }
 };
 constexpr PsLayout kLayFlow{1, 4, 1, 0}, kLayScalar{2, 6, 2, 0}, kLayAdjoint{2, 6, 2, 3}, kLayScalarAdjoint{2, 10, 3, 6}, kLayTangent{2, 8, 2, 0},
-                   kLayScalarTangent{4, 12, 4, 0};
+                   kLayScalarTangent{4, 12, 4, 0}, kLaySecondAdjoint{2, 12, 4, 6};
 
 size_t layout_work_bytes(const PsLayout& lay, int batch, int nx, int ny) {
     const size_t b = work_bytes(batch, nx, ny), st = (size_t)lay.fields() * batch * nx * kept_y(ny) * sizeof(float2);
@@ -1682,6 +1841,7 @@ size_t adjoint_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(
 size_t scalar_adjoint_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayScalarAdjoint, batch, nx, ny); }
 size_t tangent_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayTangent, batch, nx, ny); }
 size_t scalar_tangent_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLayScalarTangent, batch, nx, ny); }
+size_t second_adjoint_work_bytes(int batch, int nx, int ny) { return layout_work_bytes(kLaySecondAdjoint, batch, nx, ny); }
 constexpr int kMaxTangents = 32;
 constexpr PsLayout tangents_layout(int K) { return PsLayout{1 + K, 4 + 4 * K, 1 + K, 0}; }
 size_t tangents_work_bytes(int batch, int ntan, int nx, int ny) { return layout_work_bytes(tangents_layout(ntan), batch, nx, ny); }
@@ -1726,10 +1886,11 @@ int check_box(const char* what, int nx, int ny, double Lx, double Ly) {
     return check_axes(what, nx, ny);
 }
 
-enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2, kWorkScalarAdjoint = 3, kWorkTangent = 4, kWorkTangents = 5, kWorkScalarTangent = 6, kWorkScalarTangents = 7 };      // a bool converts: false the flow's workspace, true the scalar's
+enum PsWorkKind { kWorkFlow = 0, kWorkScalar = 1, kWorkAdjoint = 2, kWorkScalarAdjoint = 3, kWorkTangent = 4, kWorkTangents = 5, kWorkScalarTangent = 6, kWorkScalarTangents = 7, kWorkSecondAdjoint = 8 };      // a bool converts: false the flow's workspace, true the scalar's
 
 int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int kind, int ntan = 0) {      // ntan: kWorkTangents' and kWorkScalarTangents' K
-    const size_t need = kind == kWorkScalarTangents ? scalar_tangents_work_bytes(batch, ntan, nx, ny)
+    const size_t need = kind == kWorkSecondAdjoint ? second_adjoint_work_bytes(batch, nx, ny)
+                        : kind == kWorkScalarTangents ? scalar_tangents_work_bytes(batch, ntan, nx, ny)
                         : kind == kWorkScalarTangent ? scalar_tangent_work_bytes(batch, nx, ny)
                         : kind == kWorkTangents    ? tangents_work_bytes(batch, ntan, nx, ny)
                         : kind == kWorkTangent     ? tangent_work_bytes(batch, nx, ny)
@@ -1739,7 +1900,8 @@ int check_work(const char* what, int batch, int nx, int ny, size_t wbytes, int k
                                                    : work_bytes(batch, nx, ny);
     if (wbytes < need)
         return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", what, wbytes, need,
-                    kind == kWorkScalarTangents ? "nns_spec_ns_scalar_tangents_workspace"
+                    kind == kWorkSecondAdjoint ? "nns_spec_ns_second_adjoint_workspace"
+                    : kind == kWorkScalarTangents ? "nns_spec_ns_scalar_tangents_workspace"
                     : kind == kWorkScalarTangent ? "nns_spec_ns_scalar_tangent_workspace"
                     : kind == kWorkTangents    ? "nns_spec_ns_tangents_workspace"
                     : kind == kWorkTangent     ? "nns_spec_ns_tangent_workspace"
@@ -2326,6 +2488,77 @@ NNS_API int nns_spec_ns_step_operator_adjoint_f32(const float* what0, const floa
                                 nsteps, stream, lin, lbar);
 }
 
+NNS_API int nns_spec_ns_second_adjoint_workspace(int batch, int nx, int ny, size_t* bytes) {
+    if (!bytes || batch < 1)
+        return fail(NNS_ERR_INVALID_ARG, "spec_ns_second_adjoint_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
+    if (int rc = check_axes("spec_ns_second_adjoint_workspace", nx, ny)) return rc;
+    *bytes = second_adjoint_work_bytes(batch, nx, ny);
+    return NNS_OK;
+}
+
+// The second-order adjoint of the flow's steps, last step first: spec_ns_step_adjoint's sequence with a second quadruple riding in every launch.
+// Per step: the stage states s1, s2, s3 and the tangent stages d1, d2, d3 recomputed from the step's saved (w^, dw^) by the tangent step's own
+// launches (stage 0, then three row / column pairs whose column kernels carry the PsKeepTangent: 7), then the adjoint's stage 4 column launch and
+// four ps_row_adj2_kernel / column pairs (9).  The base's kernels are chosen as spec_ns_step_adjoint chooses them (ghat, drag or lin: the forced
+// forms), so lam and gbar are that call's bits.  No allocation, no host synchronisation.
+NNS_API int nns_spec_ns_step_second_adjoint_f32(const float* what0, const float* dwhat0, const float* mean, const float* ghat, int gbatch,
+                                                const float* dghat, int dgbatch, float* lam, float* dlam, float* gbar, float* dgbar, void* work,
+                                                size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu,
+                                                double drag, const float* lin, int nsteps, void* stream) {
+    const char* who = "spec_ns_step_second_adjoint";
+    if (!what0 || !mean || !lam || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
+    if (!dwhat0 || !dlam) return fail(NNS_ERR_INVALID_ARG, "%s: dwhat0 and dlam must be non-NULL", who);
+    if (lin) nu = drag = 0.0;                                                                  // the table holds them
+    if (int rc = check_step_numbers(who, dt, nu, drag, nsteps)) return rc;
+    if (int rc = check_gbatch(who, ghat, gbatch, batch)) return rc;
+    if (dghat ? (dgbatch != 1 && dgbatch != batch) : dgbatch != 0)
+        return fail(NNS_ERR_INVALID_ARG, "%s: dgbatch = %d must be 0 without dghat, 1 or batch = %d with it", who, dgbatch, batch);
+    if (int rc = check_common(who, batch, nx, ny, Lx, Ly, work_bytes_, kWorkSecondAdjoint)) return rc;
+    hipStream_t s = as_stream(stream);
+    if (nsteps == 0) {
+        const long zbytes = (long)((size_t)batch * kept_y(ny) * nx * sizeof(float2));
+        void* zb[2] = {gbar ? gbar : dgbar, dgbar};
+        const long zn[2] = {zbytes, zbytes};
+        const int nz = (gbar ? 1 : 0) + (dgbar ? 1 : 0);
+        return nz ? zero_buffers(zb, zn, nz, s) : NNS_OK;
+    }
+    const PsWork L(work, batch, nx, ny, kLaySecondAdjoint, Lx, Ly, (float)(-0.5 * nu * dt), (float)dt);
+    const long fstride = L.col.fstride;
+    float2* wstages = L.keep;                                                                  // s1, s2, s3 of w^
+    float2* dstages = wstages + 3 * fstride;                                                   // d1, d2, d3 of dw^
+    const PsForce force{reinterpret_cast<const float2*>(ghat), gbatch == 1 && batch > 1 ? 1 : 0, (float)(0.5 * drag * dt)};
+    const PsForce* fc = ghat || drag > 0 || lin ? &force : nullptr;                            // the adjoint's choice of kernels: its bits
+    const PsLinear linear{reinterpret_cast<const float2*>(lin)};
+    const PsLinear* li = lin ? &linear : nullptr;
+    // wbar and dwbar take the accumulators' places (PsLayout's note): the recomputation is over when adjoint stage 3 first writes them
+    PsAdjSecond ad{PsAdj{reinterpret_cast<float2*>(lam), L.A, reinterpret_cast<float2*>(gbar), nullptr, force.hdrag, 0},
+                   reinterpret_cast<float2*>(dlam), L.At, reinterpret_cast<float2*>(dgbar), nullptr};
+    for (int k = nsteps - 1; k >= 0; --k) {
+        float2* W = const_cast<float2*>(reinterpret_cast<const float2*>(what0)) + (size_t)k * fstride;      // stages 0-3 only read W and dW
+        float2* dW = const_cast<float2*>(reinterpret_cast<const float2*>(dwhat0)) + (size_t)k * fstride;
+        const PsTangent tg{dW, L.At, reinterpret_cast<const float2*>(dghat), dgbatch == 1 && batch > 1 ? 1 : 0};
+        if (int rc = dispatch_pow2(nx, "spec_ns", [&](auto n) {
+                return launch_col_stage<decltype(n)::value>(0, L.Ph, L.G, W, L.A, mean, L.col, 1, nullptr, nullptr, s, nullptr, nullptr, &tg);
+            }))
+            return rc;
+        for (int S = 1; S <= 3; ++S) {
+            if (int rc = dispatch_pow2(ny, "spec_ns", [&](auto n) { return launch_row_tan<decltype(n)::value>(L.G, L.Ph, L.row, s); })) return rc;
+            const size_t off = (size_t)(S - 1) * fstride;
+            const PsKeepTangent ke{wstages + off, dstages + off};
+            if (int rc = ps_second_adjoint_col_keep(nx, S, L.Ph, L.G, W, L.A, mean, &L.col, fc, li, s, &tg, &ke)) return rc;
+        }
+        for (int S = 4; S >= 0; --S) {
+            if (S < 4)
+                if (int rc = ps_second_adjoint_row(ny, L.G, L.Ph, &L.row, s)) return rc;
+            ad.state = S >= 2 ? wstages + (size_t)(S - 2) * fstride : W;
+            ad.dstate = S >= 2 ? dstages + (size_t)(S - 2) * fstride : dW;
+            ad.ginit = k == nsteps - 1;
+            if (int rc = ps_second_adjoint_col(nx, S, L.Ph, L.G, mean, &L.col, &ad, lin, s)) return rc;
+        }
+    }
+    return NNS_OK;
+}
+
 NNS_API int nns_spec_ns_scalar_workspace(int batch, int nx, int ny, size_t* bytes) {
     if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "spec_ns_scalar_workspace: bytes must be non-NULL and batch >= 1 (batch = %d)", batch);
     if (int rc = check_axes("spec_ns_scalar_workspace", nx, ny)) return rc;
@@ -2445,6 +2678,36 @@ int ps_scalar_tangent_row(int ny, const void* G, void* Ph, const void* a, void* 
         hipStream_t s = static_cast<hipStream_t>(stream);
         return buoyant ? launch_row_tan_scalar<N>(g, ph, args, s, *static_cast<const PsBuoyGrad*>(gr))
                        : launch_row_tan_scalar<N>(g, ph, args, s, *static_cast<const PsGrad*>(gr));
+    });
+}
+#elif defined(PSPEC_SECOND_ADJOINT_TU)      // the launches of the second-order adjoint (declared at the head of this file)
+int ps_second_adjoint_col_keep(int nx, int S, const void* Ph, void* G, void* W, void* A, const float* mean, const void* a, const void* fc,
+                               const void* li, void* stream, const void* tg, const void* ke) {
+    return dispatch_pow2(nx, "spec_ns", [&](auto n) {
+        return launch_col_keep<decltype(n)::value>(S, static_cast<const float2*>(Ph), static_cast<float2*>(G), static_cast<float2*>(W),
+                                                   static_cast<float2*>(A), mean, *static_cast<const PsArgs*>(a), static_cast<const PsForce*>(fc),
+                                                   static_cast<const PsLinear*>(li), static_cast<hipStream_t>(stream),
+                                                   *static_cast<const PsKeepTangent*>(ke), *static_cast<const PsTangent*>(tg));
+    });
+}
+
+int ps_second_adjoint_row(int ny, const void* G, void* Ph, const void* a, void* stream) {
+    return dispatch_pow2(ny, "spec_ns", [&](auto n) {
+        return launch_row_adj2<decltype(n)::value>(static_cast<const float2*>(G), static_cast<float2*>(Ph), *static_cast<const PsArgs*>(a),
+                                                   static_cast<hipStream_t>(stream));
+    });
+}
+
+int ps_second_adjoint_col(int nx, int S, const void* Ph, void* G, const float* mean, const void* a, const void* ad, const void* lin, void* stream) {
+    return dispatch_pow2(nx, "spec_ns", [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        const float2* ph = static_cast<const float2*>(Ph);
+        float2* g = static_cast<float2*>(G);
+        const PsArgs& args = *static_cast<const PsArgs*>(a);
+        const PsAdjSecond& second = *static_cast<const PsAdjSecond*>(ad);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (lin && S >= 1 && S <= 3) return launch_col_adj<N>(S, ph, g, mean, args, PsAdjSecondLinear{second, static_cast<const float2*>(lin)}, s);
+        return launch_col_adj<N>(S, ph, g, mean, args, second, s);
     });
 }
 #else      // PSPEC_SCALAR_TANGENTS_TU: the launches of K tangents on the scalar system (declared at the head of this file)

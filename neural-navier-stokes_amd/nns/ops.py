@@ -1608,3 +1608,33 @@ def spec_ns_adjoint_(what0, that0, mean, ghat, lam, mu, gbar, work, ny, Lx, Ly, 
     else:
         spec_ns_step_adjoint_(what0, mean, ghat, lam, gbar, *box, nu, drag)
     return lam, mu, gbar, lbar
+
+
+# second-order adjoint of the periodic solver's flow step (nns_spec_ns_step_second_adjoint_f32)
+def spec_ns_second_adjoint_workspace(B, nx, ny):
+    """Bytes of the workspace spec_ns_second_adjoint_ needs for B grids of nx x ny (>= spec_ns_adjoint_workspace and spec_ns_tangent_workspace)."""
+    return _query_bytes('nns_spec_ns_second_adjoint_workspace', int(B), int(nx), int(ny))
+
+
+def spec_ns_second_adjoint_(what0, dwhat0, mean, ghat, dghat, lam, dlam, gbar, dgbar, work, ny, Lx, Ly, dt, nu, drag, lin=None):
+    """spec_ns_step_adjoint_ (lin None) or spec_ns_step_linear_adjoint_ without a scalar (lin: the forward's table; nu and drag are then
+    ignored) together with its derivative in a direction: what0, dwhat0 (float32 [nsteps, B, my1, nx, 2], only read) are the spectrum and its
+    tangent at the start of every step of a spec_ns_step_tangent_ forward, dghat the source's perturbation of that forward ([1 or B, my1, nx, 2]
+    or None); lam and dlam ([B, my1, nx, 2]) hold, in, the cotangent of the state after the last step and its derivative and, out, (wbar, dwbar)
+    before the first; gbar and dgbar (the same shape, each or both None) receive the cotangent of g^ and its derivative, one per grid, summed
+    over the steps.  lam and gbar are bitwise the first-order call's.  work: spec_ns_second_adjoint_workspace bytes.  16 launches per step, no
+    allocation, no host synchronisation."""
+    who = 'spec_ns_step_second_adjoint'
+    B, my1, nx = _spec_ns_state(who, lam, mean, work, ny)
+    _spec_ns_same(who, dlam, lam, 'dlam')
+    gbatch = _spec_ns_adjoint_tensors(who, lam, ghat, gbar, what0=what0, dwhat0=dwhat0)
+    dgbatch = _spec_ns_force(who, dghat, lam)
+    if dgbar is not None:
+        _spec_ns_same(who, dgbar, lam, 'dgbar')
+    if lin is not None:
+        _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), lam.device)
+    check(_lib.lib().nns_spec_ns_step_second_adjoint_f32(_p(what0), _p(dwhat0), _p(mean), _pn(ghat), gbatch, _pn(dghat), dgbatch, _p(lam), _p(dlam),
+                                                         _pn(gbar), _pn(dgbar), _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly),
+                                                         float(dt), float(nu), float(drag), _pn(lin), int(what0.shape[0]), _stream()),
+          'nns_spec_ns_step_second_adjoint_f32')
+    return lam, dlam, gbar, dgbar

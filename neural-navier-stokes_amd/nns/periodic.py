@@ -291,6 +291,54 @@ class _AdvanceFn(torch.autograd.Function):
         return (None, gf, gop) + grads
 
 
+SecondOrderGradients = collections.namedtuple('SecondOrderGradients', ['wbar', 'dwbar', 'gbar', 'dgbar'])
+
+
+class SecondOrderRun(object):
+    """What ``PeriodicSolver.second_order_forward`` returns: ``w`` and ``dw``, the vorticity field and its perturbation after the steps
+    (bitwise ``evolve``'s forward and ``evolve_tangent``'s), and the spectra (w^, dw^) at the start of every step, kept for ``backward``
+    (``what0``, ``dwhat0``: float32 [nsteps, B, my1, nx, 2] each).  ``backward`` may be called any number of times."""
+
+    def __init__(self, solver, fields, what0, dwhat0, mean, ghat, dghat, lin, force_shape, squeeze):
+        self.solver, (self.w, self.dw) = solver, fields
+        self.what0, self.dwhat0, self.mean, self.ghat, self.dghat, self.lin = what0, dwhat0, mean, ghat, dghat, lin
+        self.force_shape, self.squeeze = force_shape, squeeze
+
+    def backward(self, lam, dlam):
+        """``SecondOrderGradients(wbar, dwbar, gbar, dgbar)``, fields like ``w``: for the cotangent ``lam`` of ``w`` and its derivative
+        ``dlam`` in the direction the run carries, wbar = J^T lam and gbar, the gradients in the initial field and in ``forcing``, bitwise the
+        backward of ``evolve``; dwbar and dgbar their derivatives in the direction (dw, dforcing, dlam): the second-order adjoint of the
+        Lawson RK4 step as HIP kernels, 16 launches per step (include/nns.h: nns_spec_ns_step_second_adjoint_f32).  gbar and dgbar are None
+        for a run without ``forcing``, and summed over the batch (one deterministic torch.sum each) for a shared one."""
+        s = self.solver
+        B, dev = self.what0.shape[1], self.what0.device
+        shape = (B, s.nx, s.ny)
+        spectra = []
+        for name, f in (('lam', lam), ('dlam', dlam)):
+            f = s._field(name, f.detach() if isinstance(f, torch.Tensor) else f).to(dev)
+            if tuple(f.shape) != shape:
+                raise ValueError("backward: %s must be %s like the run's fields, got %s" % (name, list(shape), tuple(f.shape)))
+            spectra.append(s.init_vorticity(f.contiguous()).what)
+        lamh, dlamh = spectra
+        work = s._work(ops.spec_ns_second_adjoint_workspace, B, dev)
+        need_g = self.force_shape is not None
+        gbar = torch.empty_like(lamh) if need_g else None
+        dgbar = torch.empty_like(lamh) if need_g else None
+        ops.spec_ns_second_adjoint_(self.what0, self.dwhat0, self.mean, self.ghat, self.dghat, lamh, dlamh, gbar, dgbar, work, s.ny, s.Lx, s.Ly,
+                                    s.dt, s.nu, s.drag, self.lin)
+        out = [s.vorticity(s._at_rest(lamh, work)), s.vorticity(s._at_rest(dlamh, work))]
+        if self.squeeze:
+            out = [o[0] for o in out]
+        for g in (gbar, dgbar):
+            if g is not None:
+                g = s.vorticity(s._at_rest(g, work))
+                if self.force_shape[0] == 1 and B > 1:
+                    g = torch.sum(g, dim=0, keepdim=True)
+                g = g.reshape(self.force_shape)
+            out.append(g)
+        return SecondOrderGradients(*out)
+
+
 class PeriodicSolver(object):
     """Batched 2-D incompressible Navier-Stokes on the periodic box [0, Lx) x [0, Ly): float32 fields [B, nx, ny] on the device
     (axis 0 = x), nx and ny each a power of two in [64, 1024].  Vorticity-streamfunction form, 2/3-rule dealiasing
@@ -397,8 +445,21 @@ class PeriodicSolver(object):
     ``lyapunov_spectrum_scalar`` the first K exponents (tests/pspec_scalar_lyapunov_oracle.py); ``kaplan_yorke_dimension`` applies.
     ``step_tangent``, ``lyapunov_exponent``, ``step_tangents`` and ``lyapunov_spectrum`` keep refusing
     a state that carries a scalar.  Not built: the
-    tangent in ``operator``, a source perturbation per tangent, covariant vectors, a ``jvp`` hook on the autograd node for
-    ``torch.autograd.forward_ad``, and reverse mode through the tangent (Hessian-vector products).
+    tangent in ``operator``, a source perturbation per tangent, covariant vectors, and a ``jvp`` hook on the autograd node for
+    ``torch.autograd.forward_ad``.
+
+    Second order: ``hessian_vector_product(loss, w, dw, nsteps, forcing=, dforcing=)`` gives the value, the gradient and the exact
+    Hessian-vector product of a loss of the rollout, jointly in the initial vorticity and the source -- what Newton-CG, trust-region 4D-Var,
+    Hessian eigenvalues and second-order sensitivities need, and what a Gauss-Newton product J^T J d (``evolve_tangent`` then the backward
+    of ``evolve``) leaves out: sum lam . d^2 Phi[d, .].  It is reverse mode through the tangent.  The nonlinear term is bilinear, so
+    N'(s)^T kappa is linear in s and the derivative of an adjoint stage in the direction d is the same operator about the TANGENT stage
+    state, without the mean flow: dr = N'(s_i)^T dkappa + N'_0(d_i)^T kappa, and (dlam, dkappa, dwbar, dgbar) obey the adjoint's own linear
+    recurrences (tests/pspec_second_adjoint_oracle.py).  ``second_order_forward`` is ``evolve_tangent`` with (w^, dw^) kept per step
+    (16 bytes per stored mode), and its run's ``backward(lam, dlam)`` recomputes the stages of both by the tangent step's launches and carries
+    the second quadruple through the adjoint's: still 16 launches per step, the first-order outputs bitwise those of ``evolve``.  Plain,
+    forced, linear and stochastic solvers (a stochastic step is differentiated as the deterministic step it contains).  Not built: the
+    scalar and Boussinesq system (a solver with ``kappa`` is refused), the second derivative in ``operator``, velocity-level ends, K
+    directions sharing one base.
 
     By wavenumber: the stored modes are binned into shells of width dk = min(2 pi / Lx, 2 pi / Ly) centred on k_s = s dk (``shells()``; an
     elongated box has many).  ``spectrum(state)`` gives energy E(s), enstrophy Z(s), the force's injection F(s) and the scalar's variance V(s),
@@ -1427,6 +1488,66 @@ class PeriodicSolver(object):
         differentiated.  No pressure output.  ``forcing``, ``clock``, ``noise_ids`` and ``operator`` as in ``evolve``."""
         fields = (('u0', u0), ('v0', v0)) if theta0 is None else (('u0', u0), ('v0', v0), ('theta0', theta0))
         return self._evolve('evolve_velocity', True, fields, nsteps, None, forcing, clock, noise_ids, operator)
+
+    # ---- second order: reverse mode through the tangent
+    def second_order_forward(self, w, dw, nsteps=1, mean=None, forcing=None, dforcing=None, clock=0, noise_ids=None):
+        """The forward half of a Hessian-vector product through ``nsteps`` steps: ``evolve_tangent`` taken in one-step calls with the
+        spectra (w^, dw^) at the start of every step kept, nsteps x B x my1 x nx x 16 bytes.  Returns a ``SecondOrderRun`` whose ``.w`` is
+        bitwise ``evolve``'s forward and ``.dw`` bitwise ``evolve_tangent``'s, and whose ``backward(lam, dlam)`` is the second-order adjoint
+        (its note).  The arguments are ``evolve_tangent``'s.  Plain, forced, linear (hyperviscosity, hypofriction, beta, drag) and stochastic
+        solvers; a solver with ``kappa`` is refused, NotImplementedError: the second-order adjoint of the scalar system is not built.  NOT an
+        autograd node: the inputs are detached.  No ``operator`` and no velocity ends."""
+        if self.kappa is not None:
+            raise NotImplementedError("second_order_forward: the second-order adjoint of the scalar system is not built (this solver has kappa)")
+        nsteps = _count('nsteps', nsteps, 1)
+        det = lambda a: a.detach() if isinstance(a, torch.Tensor) else a
+        squeeze = isinstance(w, (torch.Tensor, np.ndarray)) and w.ndim == 2
+        state, dstate = self.init_vorticity(det(w), mean), self.init_vorticity(det(dw))
+        if state.what.shape != dstate.what.shape:
+            raise ValueError("second_order_forward: the field and its perturbation must share their shape")
+        given = forcing is not None
+        if given:
+            forcing = self._field('forcing', det(forcing)).to(state.what.device)
+            ghat = self._source_spectrum(forcing, state)
+        else:
+            ghat = self._force_of(state)
+        dghat = self._dforcing('second_order_forward', dforcing, state)
+        if self.stoch_amp is not None:
+            state.clock, state.noise_ids = self._noise_args(clock, noise_ids, state)
+        what0 = torch.empty((nsteps,) + tuple(state.what.shape), dtype=torch.float32, device=state.what.device)
+        dwhat0 = torch.empty_like(what0)
+        for k in range(nsteps):
+            what0[k].copy_(state.what)
+            dwhat0[k].copy_(dstate.what)
+            self._launch_tangent(state, dstate.what, 1, dghat, ghat)
+        out = self.vorticity(state), self.vorticity(self._at_rest(dstate.what, state.work))
+        return SecondOrderRun(self, tuple(o[0] for o in out) if squeeze else out, what0, dwhat0, state.mean, ghat, dghat,
+                              self._linear_of(state) if self._linear() else None, tuple(forcing.shape) if given else None, squeeze)
+
+    def hessian_vector_product(self, loss, w, dw, nsteps=1, mean=None, forcing=None, dforcing=None, clock=0, noise_ids=None):
+        """(loss, grad_w, grad_forcing, hvp_w, hvp_forcing) of l(w, forcing) = ``loss``(the vorticity field after ``nsteps`` steps from w): the
+        value, the gradient and the exact Hessian-vector product H (dw, dforcing), in one tangent forward and one second-order backward where a
+        finite difference of gradients takes two forward and two backward passes and loses the digits the gradients share.  ``loss`` maps the
+        final field ([B, nx, ny], or [nx, ny] for such a w) to a scalar tensor by torch operations; lam = dl/dw_N is taken by autograd and
+        dlam = (d^2 l / dw_N^2) dw_N by a second ``torch.autograd.grad`` of <lam, dw_N>, zero where lam carries no graph (a linear loss).  The
+        Gauss-Newton product J^T (d^2 l) J d is the part that comes from dlam; the rest, sum lam . d^2 Phi[d, .], is what a first-order code
+        cannot give.  The forcing entries are None without ``forcing``; for a shared one ([1, nx, ny]) they are summed over the batch.  H is
+        symmetric: sum(a . H b) = sum(b . H a) to float32 rounding, jointly in (w, forcing).  The other arguments and the refusals are
+        ``second_order_forward``'s."""
+        run = self.second_order_forward(w, dw, nsteps, mean, forcing, dforcing, clock, noise_ids)
+        with torch.enable_grad():
+            w1 = run.w.detach().requires_grad_(True)
+            value = loss(w1)
+            if not (isinstance(value, torch.Tensor) and value.numel() == 1):
+                raise TypeError("hessian_vector_product: loss must return a scalar tensor")
+            lam, = torch.autograd.grad(value, w1, create_graph=True)
+            dlam = None
+            if lam.requires_grad:
+                dlam, = torch.autograd.grad(torch.sum(lam * run.dw), w1, allow_unused=True)
+        if dlam is None:
+            dlam = torch.zeros_like(run.w)
+        out = run.backward(lam.detach(), dlam.detach())
+        return value.detach(), out.wbar, out.gbar, out.dwbar, out.dgbar
 
     def diagnostics(self, state):
         """Diagnostics(energy, enstrophy, power_in), each float64 [B], computed on the device from the state's spectrum:
