@@ -110,6 +110,8 @@ int nns_fd_pressure_rhs_f64(const double* ui, const double* vi, double* C, int b
  * several sweeps in flight skewed by two fronts.  Stops after the first sweep whose
  * max|p - pPrev| <= tol, or after max_sweeps (= nit-1) sweeps.  p is updated in place.
  * info[2*b] = sweeps done, info[2*b+1] = last err (as the field type), per grid b.
+ * Zero-sweep rule: the reference's `while err > tol and it < nit` starts from err = 1, so with
+ * tol >= 1 (or a tol that is NaN) or max_sweeps = 0 no sweep runs: info = (0, 1), p untouched.
  * work: nns_fd_sor_workspace() bytes. One workgroup per grid ("replicas only" across GPUs). */
 size_t nns_fd_sor_workspace(int batch, int nx, int ny, int elem_size);
 /* (The sweeps run speculatively in batches; a stop inside a batch costs a restore + replay.  nns_fd_sor_hint_* take `hint` [batch][2] -- the info of the
@@ -206,7 +208,8 @@ int nns_coarsen_f64(const double* u, const double* v, const double* p, double* c
  * sequence nns_fd_predictor_explicit(_corrected) / nns_bc_apply x 2 / nns_fd_pressure_rhs / nns_fd_sor / nns_bc_apply / nns_fd_correction (the same
  * per-point functions).  p is updated in place (as the reference mutates it) and also written to p_copy when that is not NULL (a trajectory slot);
  * u_out, v_out receive the new velocities (they hold the intermediate ones on the way: they must not alias an input field); info [batch][2] =
- * (sweeps, last err); hint: as nns_fd_sor_hint_* (the previous step's info or NULL); work: nns_fd_sor_workspace(batch, nx, ny, elem) bytes.  Applies when p and its right-hand side fit one workgroup's LDS
+ * (sweeps, last err; the zero-sweep rule of nns_fd_sor_* holds: with tol >= 1 or max_sweeps = 0 info = (0, 1) and p leaves as the pressure boundary list's
+ * image of the p that came in); hint: as nns_fd_sor_hint_* (the previous step's info or NULL); work: nns_fd_sor_workspace(batch, nx, ny, elem) bytes.  Applies when p and its right-hand side fit one workgroup's LDS
  * (nns_fd_step_explicit_fits: 64 x 64 float64, 96 x 96 float32 and below); NNS_ERR_UNSUPPORTED otherwise: use the separate calls. */
 int nns_fd_step_explicit_fits(int nx, int ny, int elem_size);
 int nns_fd_step_explicit_f32(const float* un, const float* vn, const float* un1, const float* vn1, float* p, const nns_bc_list* u_bc, const nns_bc_list* v_bc,

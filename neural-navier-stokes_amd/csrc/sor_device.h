@@ -148,13 +148,16 @@ __device__ __forceinline__ void sor_run_batch(T* pw, const T* cw, int nx, int ny
 // The whole solve of ONE grid by one workgroup of kSorThreads: pw / cw = the working copies of p and C (LDS when IN_LDS, else the global grid
 // itself), sg = the grid's snapshot buffer (global, nx * ny), errs / s_stop_p = the LDS header.  Runs speculative batches of sweeps until the first
 // sweep whose maximum update is <= tol (kept exact: restore + replay) or max_sweeps; returns the sweeps done and the last error (:183-200).
+// No sweep runs when tol is at or above the initial err = 1: done = 0, err = 1.
 template <typename T, bool IN_LDS>
 __device__ __forceinline__ void sor_solve(T* pw, const T* cw, T* sg, int nx, int ny, int max_sweeps, int expect, const SorK<T>& k, T* errs, int* s_stop_p,
                                           int& done_out, T& err_out) {
     const int n = nx * ny, tid = threadIdx.x;
     int done = 0, nbatch = 0;
     T err = (T)1;                                                     // :183
-    while (done < max_sweeps) {
+    // `while err > tol and it < nit` (:190) tests the INITIAL err too: tol >= 1 (or a NaN) means no sweep at all, info = (0, 1), p untouched.
+    // After a batch without a stop err is its last sweep's error, which is > tol: only the first pass can end here.
+    while (done < max_sweeps && err > k.tol) {
         // Sweeps run speculatively in batches (a stop inside a batch costs a restore + replay), so the batch sizes follow what is known: `expect`
         // (the sweep count of the previous solve of this grid, 0 = unknown) for the first one -- a time loop's counts change slowly, and a batch
         // that ends exactly at the stop needs no replay --, one sweep per wave for the second, whatever is left (up to the cap) after that.
