@@ -772,6 +772,48 @@ int nns_spec_ns_step_second_adjoint_f32(const float* what0, const float* dwhat0,
                                         const float* dghat, int dgbatch, float* lam, float* dlam, float* gbar, float* dgbar, void* work,
                                         size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly, double dt, double nu, double drag,
                                         const float* lin, int nsteps, void* stream);
+/* Lagrangian tracers (csrc/pspec_particles.hip; restatement: tests/pspec_particles_oracle.py): the flow read at points that are no grid
+ * nodes, and one Runge-Kutta stage of particle positions.  Interpolation by periodic tensor-product B-splines of order 4 (cubic, 4 x 4 nodes)
+ * or 6 (quintic, 6 x 6 nodes) with the exact prefilter in Fourier space: the coefficients of a field f are
+ *     c = irfft2[ f^(m_x, m_y) / (beta(2 pi m_x / nx) beta(2 pi m_y / ny)) ],
+ *     beta(t) = (2 + cos t) / 3 (order 4),  (66 + 52 cos t + 2 cos 2t) / 120 (order 6);  beta >= 0.5 / 0.325 inside the 2/3 band.
+ * A particle at x has cell i = floor(x / hx), hx = Lx / nx, and offset t = x / hx - i, both in float64; the nodes are i-1 .. i+2 (order 4) or
+ * i-2 .. i+3 (order 6) modulo nx, likewise in y.  Order-4 weights (1-t)^3/6, (3t^3 - 6t^2 + 4)/6, (-3t^3 + 3t^2 + 3t + 1)/6, t^3/6; order-6
+ * weights B5(t - j), j = -2 .. 3, B5 the centred quintic B-spline.  Weights are made in float64 and rounded once to float32; the value is
+ * sum_a wx[a] (sum_c wy[c] C[i+a][j+c]), the inner sum an fmaf chain over c ascending from 0, the outer one over a ascending from 0.  One lane
+ * per particle, no atomics, no reduction across lanes: a particle's result depends only on its own position and its grid's coefficients, and
+ * repeats bitwise.  Every node index is masked with n - 1, so no position, however large, infinite or nan, reads outside its grid (a non-finite
+ * position gives a non-finite value).  Positions are float64 [batch][npart][2] = (x, y), UNWRAPPED: only the cell index is taken modulo the box.
+ *
+ * nns_spec_ns_particle_coefs_f32: coef, float32 [nfields][batch][nx][ny], <- the spline coefficients of the fields named by the mask
+ * `fields` (bit 0 u, 1 v, 2 w, 3 theta; nfields = the bits set, stored by ascending bit) of the state (what, mean[, that]): u^ and v^ from w^ as
+ * nns_spec_ns_fields_f32 takes them, the mean flow in the (0, 0) coefficient (beta(0) = 1 and the weights sum to 1), theta with its mean.  One
+ * pointwise launch and nns_spec_irfft2_f32 over nfields batch grids: the fields() pattern without its pressure solve.  that may be NULL without
+ * bit 3.  work: nns_spec_ns_particle_workspace(batch, nfields, nx, ny) = nfields batch nx (ny / 2 + 1) 8 bytes; nothing is kept in it.
+ * nns_spec_ns_particle_sample_f32: out, float32 [batch][npart][nfields], <- the splines of coef's nfields (1 .. 4) images at pos.
+ * nns_spec_ns_particle_stage_f32: one stage of an explicit Runge-Kutta scheme on coef = the images (u, v), float32 [2][batch][nx][ny]:
+ *     k = (u, v)(pos_in), float32 promoted to float64;   s = (first ? 0 : acc) + wk k;
+ *     closing == 0:  acc <- s,  pos_out <- pos0 + a k;       closing != 0:  pos_out <- pos0 + c s  (acc is read unless first, never written)
+ * every product-sum one float64 fma.  acc, pos0, pos_in, pos_out: float64 [batch][npart][2].  pos_in may alias pos0 or pos_out (a lane reads
+ * its particle before it writes it); pos_out may alias pos0 only in the closing stage; acc may be NULL only when first and closing.
+ * Classical RK4 over a PAIR of flow steps (H = 2 dt; U_n, U_n+1, U_n+2 the coefficients at the step boundaries, which a Lawson RK4 flow gives
+ * exactly: no interpolation in time): (U_n, pos_in = x, a = dt, wk = 1, first), (U_n+1, a = dt, wk = 2), (U_n+1, a = 2 dt, wk = 2),
+ * (U_n+2, wk = 1, c = dt / 3, closing, pos_out = x).  Heun over one step: (U_n, a = dt, wk = 1, first), (U_n+1, wk = 1, c = dt / 2, closing).
+ * No allocation, no host synchronisation (capturable).
+ * Errors, all before any launch and in this order: NNS_ERR_INVALID_ARG for a NULL pointer (coefs: what, mean, coef, work; sample: coef, pos,
+ * out; stage: coef, pos0, pos_in, pos_out) or batch < 1; (stage) for a NULL acc unless first and closing, then for pos_out == pos0 in a stage that
+ * is not closing; (sample, stage) for npart < 1 or batch npart >= 2^31; for order not 4 or 6; (coefs) for fields not in [1, 15], then for bit 3
+ * with a NULL that; (sample) for nfields not in [1, 4]; (stage) for a non-finite a, wk or c; for Lx, Ly not positive and finite; then
+ * NNS_ERR_UNSUPPORTED for an axis that is not a power of two in [64, 1024]; then (coefs) NNS_ERR_WORKSPACE below the size query.  The query:
+ * NNS_ERR_INVALID_ARG for a NULL bytes or batch < 1, then for nfields not in [1, 4], then NNS_ERR_UNSUPPORTED for the axes. */
+int nns_spec_ns_particle_workspace(int batch, int nfields, int nx, int ny, size_t* bytes);
+int nns_spec_ns_particle_coefs_f32(const float* what, const float* that, const float* mean, float* coef, int fields, int order, void* work,
+                                   size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly, void* stream);
+int nns_spec_ns_particle_sample_f32(const float* coef, const double* pos, float* out, int nfields, int order, int batch, long npart, int nx,
+                                    int ny, double Lx, double Ly, void* stream);
+int nns_spec_ns_particle_stage_f32(const float* coef, const double* pos0, const double* pos_in, double* pos_out, double* acc, double a,
+                                   double wk, double c, int first, int closing, int order, int batch, long npart, int nx, int ny, double Lx,
+                                   double Ly, void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

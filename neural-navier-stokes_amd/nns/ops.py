@@ -1638,3 +1638,77 @@ def spec_ns_second_adjoint_(what0, dwhat0, mean, ghat, dghat, lam, dlam, gbar, d
                                                          float(dt), float(nu), float(drag), _pn(lin), int(what0.shape[0]), _stream()),
           'nns_spec_ns_step_second_adjoint_f32')
     return lam, dlam, gbar, dgbar
+
+
+# Lagrangian tracers of the periodic solver (nns_spec_ns_particle_*)
+PARTICLE_FIELDS = ('u', 'v', 'w', 'theta')           # bit k of a field mask names PARTICLE_FIELDS[k]
+
+
+def spec_ns_particle_workspace(B, nfields, nx, ny):
+    """Bytes of the workspace spec_ns_particle_coefs needs for nfields fields of B grids of nx x ny."""
+    return _query_bytes('nns_spec_ns_particle_workspace', int(B), int(nfields), int(nx), int(ny))
+
+
+def _spec_ns_f64(who, name, t, shape, device):
+    """t is a contiguous float64 tensor of `shape` on the state's device."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+        raise TypeError("%s: %s must be a contiguous float64 device tensor" % (who, name))
+    if tuple(t.shape) != tuple(shape) or t.device != device:
+        raise ValueError("%s: %s must be float64 %s on %s, got %s on %s" % (who, name, list(shape), device, tuple(t.shape), t.device))
+
+
+def spec_ns_particle_coefs(what, that, mean, coef, fields, order, work, ny, Lx, Ly):
+    """coef (float32 [nfields, B, nx, ny]) <- the order-4 or order-6 B-spline coefficients of the fields of the mask `fields` (bit 0 u, 1 v,
+    2 w, 3 theta, stored by ascending bit) of the state (what, mean[, that]).  work: spec_ns_particle_workspace bytes.  One launch and an
+    inverse transform, no allocation, no host synchronisation."""
+    who = 'spec_ns_particle_coefs'
+    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
+    if that is not None:
+        _spec_ns_same(who, that, what)
+    fields = int(fields)
+    _spec_ns_f32(who, 'coef', coef, (bin(fields & 15).count('1'), B, nx, int(ny)), what.device)
+    check(_lib.lib().nns_spec_ns_particle_coefs_f32(_p(what), _pn(that), _p(mean), _p(coef), fields, int(order), _p(work), work.numel(), B, nx,
+                                                    int(ny), float(Lx), float(Ly), _stream()), 'nns_spec_ns_particle_coefs_f32')
+    return coef
+
+
+def _spec_ns_particle_coef(who, coef, nfields=None):
+    """(nfields, B, nx, ny) of the checked coefficient images."""
+    _f32(coef)
+    if coef.dim() != 4 or (nfields is not None and coef.shape[0] != nfields):
+        raise ValueError("%s: coef must be float32 [%s, B, nx, ny], got %s" % (who, 'nfields' if nfields is None else nfields, tuple(coef.shape)))
+    return tuple(coef.shape)
+
+
+def spec_ns_particle_sample(coef, pos, order, Lx, Ly, out=None):
+    """float32 [B, P, nfields]: the splines of the coefficient images coef [nfields, B, nx, ny] at the positions pos (float64 [B, P, 2])."""
+    who = 'spec_ns_particle_sample'
+    nf, B, nx, ny = _spec_ns_particle_coef(who, coef)
+    if not (isinstance(pos, torch.Tensor) and pos.dim() == 3):
+        raise ValueError("%s: pos must be float64 [B, P, 2]" % who)
+    P = pos.shape[1]
+    _spec_ns_f64(who, 'pos', pos, (B, P, 2), coef.device)
+    if out is None:
+        out = torch.empty((B, P, nf), dtype=torch.float32, device=coef.device)
+    else:
+        _spec_ns_f32(who, 'out', out, (B, P, nf), coef.device)
+    check(_lib.lib().nns_spec_ns_particle_sample_f32(_p(coef), _p(pos), _p(out), nf, int(order), B, P, nx, ny, float(Lx), float(Ly), _stream()),
+          'nns_spec_ns_particle_sample_f32')
+    return out
+
+
+def spec_ns_particle_stage_(coef, pos0, pos_in, pos_out, acc, a, wk, c, first, closing, order, Lx, Ly):
+    """One Runge-Kutta stage on the images coef = (u, v) [2, B, nx, ny]: k = (u, v)(pos_in); s = (0 if first else acc) + wk k; closing:
+    pos_out <- pos0 + c s; else acc <- s and pos_out <- pos0 + a k.  All positions and acc float64 [B, P, 2] (include/nns.h names the
+    aliasing allowed).  One launch, no allocation, no host synchronisation."""
+    who = 'spec_ns_particle_stage'
+    nf, B, nx, ny = _spec_ns_particle_coef(who, coef, 2)
+    if not (isinstance(pos0, torch.Tensor) and pos0.dim() == 3):
+        raise ValueError("%s: pos0 must be float64 [B, P, 2]" % who)
+    shape = (B, pos0.shape[1], 2)
+    for name, t in (('pos0', pos0), ('pos_in', pos_in), ('pos_out', pos_out)) + ((('acc', acc),) if acc is not None else ()):
+        _spec_ns_f64(who, name, t, shape, coef.device)
+    check(_lib.lib().nns_spec_ns_particle_stage_f32(_p(coef), _p(pos0), _p(pos_in), _p(pos_out), _pn(acc), float(a), float(wk), float(c),
+                                                    int(bool(first)), int(bool(closing)), int(order), B, shape[1], nx, ny, float(Lx), float(Ly),
+                                                    _stream()), 'nns_spec_ns_particle_stage_f32')
+    return pos_out
