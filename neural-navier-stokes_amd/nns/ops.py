@@ -955,11 +955,13 @@ _ABSENT = object()                 # in place of an argument that a C entry does
 
 
 def _spec_ns_step(entry, what, mean, work, ny, Lx, Ly, dt, numbers, nsteps, that=_ABSENT, ghat=_ABSENT, lin=_ABSENT, noise=_ABSENT,
-                  optional=()):
-    """Every forward step: the checks of the tensors, then the call of `entry`, whose arguments are what, [that,] mean, [ghat, gbatch,] work,
-    its size, the box and dt, `numbers` (the entry's doubles after dt), [lin,] [amp, seed, clock, ids,] nsteps and the stream.  that, ghat,
-    lin, noise = (amp, seed, clock, ids): the bracketed ones the entry has; `optional` names those of 'that' and 'noise' it takes as NULL
-    (that None; amp, clock and ids all None).  The caller's name in the messages is the entry's without nns_ and f32."""
+                  optional=(), dwhat=_ABSENT, dthat=_ABSENT, members=False, dghat=_ABSENT):
+    """Every forward step, the tangent ones included: the checks of the tensors, then the call of `entry`, whose arguments are what, [that,]
+    [dwhat, [dthat,] [K,]] mean, [ghat, gbatch, [dghat, dgbatch,]] work, its size, the box and dt, `numbers` (the entry's doubles after dt),
+    [lin,] [amp, seed, clock, ids,] nsteps and the stream.  that, dwhat, dthat, ghat, dghat, lin, noise = (amp, seed, clock, ids): the
+    bracketed ones the entry has; `members`: dwhat and dthat are K members, [K, B, my1, nx, 2] (_spec_ns_tangents), and K is an argument;
+    `optional` names those of 'that', 'lin' and 'noise' it takes as NULL (that None; lin None; amp, clock and ids all None); noise None,
+    the tangent steps' way to say no noise, is four NULLs.  The caller's name in the messages is the entry's without nns_ and f32."""
     who = entry[4:-3]
     B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
     args = [_p(what)]
@@ -967,20 +969,34 @@ def _spec_ns_step(entry, what, mean, work, ny, Lx, Ly, dt, numbers, nsteps, that
         if that is not None or 'that' not in optional:
             _spec_ns_same(who, that, what)
         args.append(_pn(that))
+    if dwhat is not _ABSENT:
+        if members:
+            K = _spec_ns_tangents(who, dwhat, ny, B, my1, nx, what.device)[0]
+        else:
+            _spec_ns_same(who, dwhat, what, 'dwhat')
+        args.append(_p(dwhat))
+        if dthat is not _ABSENT:
+            _spec_ns_same(who, dthat, dwhat, 'dthat')
+            args.append(_p(dthat))
+        if members:
+            args.append(K)
     args.append(_p(mean))
     if ghat is not _ABSENT:
         args += (_pn(ghat), _spec_ns_force(who, ghat, what))
+    if dghat is not _ABSENT:
+        args += (_pn(dghat), _spec_ns_force(who, dghat, what))
     args += (_p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt))
     args.extend(map(float, numbers))
     if lin is not _ABSENT:
-        _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), what.device)
-        args.append(_p(lin))
+        if lin is not None or 'lin' not in optional:
+            _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), what.device)
+        args.append(_pn(lin))
     if noise is not _ABSENT:
-        amp, seed, clock, ids = noise
+        amp, seed, clock, ids = noise or (None, 0, None, None)
         if 'noise' in optional and (amp is None or clock is None or ids is None):
             if not (amp is None and clock is None and ids is None):
                 raise ValueError("%s: amp, clock and ids must be all None (no noise) or all given" % who)
-        else:
+        elif noise is not None:
             _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
         args += (_pn(amp), int(seed), _pn(clock), _pn(ids))
     check(getattr(_lib.lib(), entry)(*args, int(nsteps), _stream()), entry)
@@ -1233,19 +1249,8 @@ def spec_ns_step_tangent_(what, dwhat, mean, ghat, dghat, work, ny, Lx, Ly, dt, 
     same ghat, nu, drag, lin and noise = (amp, seed, clock, ids) (no scalar), dwhat <- J dwhat + (the response to) dghat, the Jacobian of
     those steps.  dwhat: float32 like what; dghat: the source's perturbation, float32 [1 or B, my1, nx, 2] or None; lin None: no table.
     work: spec_ns_tangent_workspace bytes.  8 launches per step and one per call, no allocation, no host synchronisation: capturable."""
-    who = 'spec_ns_step_tangent'
-    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
-    _spec_ns_same(who, dwhat, what, 'dwhat')
-    gbatch, dgbatch = _spec_ns_force(who, ghat, what), _spec_ns_force(who, dghat, what)
-    if lin is not None:
-        _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), what.device)
-    amp, seed, clock, ids = noise or (None, 0, None, None)
-    if noise is not None:
-        _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
-    check(_lib.lib().nns_spec_ns_step_tangent_f32(_p(what), _p(dwhat), _p(mean), _pn(ghat), gbatch, _pn(dghat), dgbatch, _p(work), work.numel(),
-                                                  B, nx, int(ny), float(Lx), float(Ly), float(dt), float(nu), float(drag), _pn(lin), _pn(amp),
-                                                  int(seed), _pn(clock), _pn(ids), int(nsteps), _stream()), 'nns_spec_ns_step_tangent_f32')
-    return what, dwhat
+    return _spec_ns_step('nns_spec_ns_step_tangent_f32', what, mean, work, ny, Lx, Ly, dt, (nu, drag), nsteps, dwhat=dwhat, ghat=ghat,
+                         dghat=dghat, lin=lin, noise=noise, optional=('lin',)), dwhat
 
 
 # forward mode of the scalar and the buoyant step (nns_spec_ns_step_scalar_tangent_f32)
@@ -1260,23 +1265,9 @@ def spec_ns_step_scalar_tangent_(what, that, dwhat, dthat, mean, ghat, dghat, wo
     bitwise as by spec_ns_advance_ with the same arguments, (dwhat, dthat) <- J (dwhat, dthat) + (the response to) dghat, the Jacobian of
     those steps.  dwhat, dthat: float32 like what; dghat: the vorticity source's perturbation, float32 [1 or B, my1, nx, 2] or None.
     work: spec_ns_scalar_tangent_workspace bytes.  8 launches per step and one per call, no allocation, no host synchronisation: capturable."""
-    who = 'spec_ns_step_scalar_tangent'
-    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
-    _spec_ns_same(who, that, what)
-    _spec_ns_same(who, dwhat, what, 'dwhat')
-    _spec_ns_same(who, dthat, what, 'dthat')
-    gbatch, dgbatch = _spec_ns_force(who, ghat, what), _spec_ns_force(who, dghat, what)
-    if lin is not None:
-        _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), what.device)
-    amp, seed, clock, ids = noise or (None, 0, None, None)
-    if noise is not None:
-        _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
     (gx, gy), (bx, by) = grad, buoyancy
-    check(_lib.lib().nns_spec_ns_step_scalar_tangent_f32(_p(what), _p(that), _p(dwhat), _p(dthat), _p(mean), _pn(ghat), gbatch, _pn(dghat),
-                                                         dgbatch, _p(work), work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt),
-                                                         float(nu), float(drag), float(kappa), float(gx), float(gy), float(bx), float(by),
-                                                         _pn(lin), _pn(amp), int(seed), _pn(clock), _pn(ids), int(nsteps), _stream()),
-          'nns_spec_ns_step_scalar_tangent_f32')
+    _spec_ns_step('nns_spec_ns_step_scalar_tangent_f32', what, mean, work, ny, Lx, Ly, dt, (nu, drag, kappa, gx, gy, bx, by), nsteps, that=that,
+                  dwhat=dwhat, dthat=dthat, ghat=ghat, dghat=dghat, lin=lin, noise=noise, optional=('lin',))
     return what, that, dwhat, dthat
 
 
@@ -1311,19 +1302,8 @@ def spec_ns_step_tangents_(what, dwhat, mean, ghat, work, ny, Lx, Ly, dt, nu, dr
     """spec_ns_step_tangent_ with K tangents dwhat (float32 [K, B, my1, nx, 2], K <= 32) on the one base what: what and every dwhat[k] bitwise
     as from that call with dwhat[k] alone (no dghat), the base's transforms done once for all K.  work: spec_ns_tangents_workspace bytes.
     8 launches per step and one per call, no allocation, no host synchronisation: capturable."""
-    who = 'spec_ns_step_tangents'
-    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
-    K = _spec_ns_tangents(who, dwhat, ny, B, my1, nx, what.device)[0]
-    gbatch = _spec_ns_force(who, ghat, what)
-    if lin is not None:
-        _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), what.device)
-    amp, seed, clock, ids = noise or (None, 0, None, None)
-    if noise is not None:
-        _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
-    check(_lib.lib().nns_spec_ns_step_tangents_f32(_p(what), _p(dwhat), K, _p(mean), _pn(ghat), gbatch, _p(work), work.numel(), B, nx, int(ny),
-                                                   float(Lx), float(Ly), float(dt), float(nu), float(drag), _pn(lin), _pn(amp), int(seed),
-                                                   _pn(clock), _pn(ids), int(nsteps), _stream()), 'nns_spec_ns_step_tangents_f32')
-    return what, dwhat
+    return _spec_ns_step('nns_spec_ns_step_tangents_f32', what, mean, work, ny, Lx, Ly, dt, (nu, drag), nsteps, dwhat=dwhat, members=True,
+                         ghat=ghat, lin=lin, noise=noise, optional=('lin',)), dwhat
 
 
 def spec_ns_tangent_gram(dwhat, ny, Lx, Ly, out=None):
@@ -1363,23 +1343,9 @@ def spec_ns_step_scalar_tangents_(what, that, dwhat, dthat, mean, ghat, work, ny
     base and every pair (dwhat[k], dthat[k]) bitwise as from that call with the pair alone (no dghat), the base's transforms and column passes
     done once for all K.  work: spec_ns_scalar_tangents_workspace bytes.  8 launches per step and one per call, no allocation, no host
     synchronisation: capturable."""
-    who = 'spec_ns_step_scalar_tangents'
-    B, my1, nx = _spec_ns_state(who, what, mean, work, ny)
-    _spec_ns_same(who, that, what)
-    K = _spec_ns_tangents(who, dwhat, ny, B, my1, nx, what.device)[0]
-    _spec_ns_same(who, dthat, dwhat, 'dthat')
-    gbatch = _spec_ns_force(who, ghat, what)
-    if lin is not None:
-        _spec_ns_f32(who, 'lin', lin, (my1, nx, 2), what.device)
-    amp, seed, clock, ids = noise or (None, 0, None, None)
-    if noise is not None:
-        _spec_ns_noise(who, amp, seed, clock, ids, B, my1, nx, what.device)
     (gx, gy), (bx, by) = grad, buoyancy
-    check(_lib.lib().nns_spec_ns_step_scalar_tangents_f32(_p(what), _p(that), _p(dwhat), _p(dthat), K, _p(mean), _pn(ghat), gbatch, _p(work),
-                                                          work.numel(), B, nx, int(ny), float(Lx), float(Ly), float(dt), float(nu), float(drag),
-                                                          float(kappa), float(gx), float(gy), float(bx), float(by), _pn(lin), _pn(amp),
-                                                          int(seed), _pn(clock), _pn(ids), int(nsteps), _stream()),
-          'nns_spec_ns_step_scalar_tangents_f32')
+    _spec_ns_step('nns_spec_ns_step_scalar_tangents_f32', what, mean, work, ny, Lx, Ly, dt, (nu, drag, kappa, gx, gy, bx, by), nsteps, that=that,
+                  dwhat=dwhat, dthat=dthat, members=True, ghat=ghat, lin=lin, noise=noise, optional=('lin',))
     return what, that, dwhat, dthat
 
 

@@ -31,7 +31,8 @@ float64 by an oracle under tests/:
   * K tangents on one base, ``step_tangents`` / ``lyapunov_spectrum``              pspec_lyapunov_oracle.py
   * forward mode with a scalar, ``step_tangent_scalar`` / ``evolve_tangent_scalar``  pspec_scalar_tangent_oracle.py
   * Lagrangian tracers, ``init_particles`` / ``sample`` / ``advect``                 pspec_particles_oracle.py
-Which C entry a step or an adjoint takes is decided in one place each, ops.spec_ns_advance_ and ops.spec_ns_adjoint_.
+Which C entry a step, an adjoint or a tangent step takes is decided in one place each: ops.spec_ns_advance_, ops.spec_ns_adjoint_ and
+PeriodicSolver._launch_tangent.
 """
 import collections
 import math
@@ -148,6 +149,12 @@ def _device(device=None):
     """``device`` as a torch.device; None: the default device."""
     return torch.device(default_device() if device is None else device)
 
+
+# (with a scalar, one tangent) -> (workspace query, step) of a tangent step: PeriodicSolver._launch_tangent
+_TANGENT_STEPS = {(False, True): (ops.spec_ns_tangent_workspace, ops.spec_ns_step_tangent_),
+                  (True, True): (ops.spec_ns_scalar_tangent_workspace, ops.spec_ns_step_scalar_tangent_),
+                  (False, False): (ops.spec_ns_tangents_workspace, ops.spec_ns_step_tangents_),
+                  (True, False): (ops.spec_ns_scalar_tangents_workspace, ops.spec_ns_step_scalar_tangents_)}
 
 Diagnostics = collections.namedtuple('Diagnostics', ['energy', 'enstrophy', 'power_in'])
 ScalarDiagnostics = collections.namedtuple('ScalarDiagnostics', ['variance', 'dissipation', 'flux_x', 'flux_y'])
@@ -818,11 +825,11 @@ class PeriodicSolver(object):
         """The scalar of this state acts on its flow: it has one and b != 0."""
         return state.that is not None and self.buoyancy != (0.0, 0.0)
 
-    def _launch_steps(self, state, nsteps, force=False, lin=None):
-        """The step this solver takes on this state; ops.spec_ns_advance_ picks the entry.  force: False, the solver's own (``set_forcing``);
-        else the spectrum g^ that takes its place (None: no force), as ``evolve`` passes its ``forcing``.  lin: None, the solver's own table
-        where it has one; else the table that takes its place, as ``evolve`` passes its ``operator``: the step is then the linear one on any
-        solver."""
+    def _step_inputs(self, state, force=False, lin=None):
+        """(ghat, lin, noise) of the step this solver takes on this state, and of the tangent step that rides on it.  force: False, the
+        solver's own (``set_forcing``); else the spectrum g^ that takes its place (None: no force), as ``evolve`` passes its ``forcing``.
+        lin: None, the solver's own table where it has one; else the table that takes its place, as ``evolve`` passes its ``operator``: the
+        step is then the linear one on any solver.  noise: (amp, seed, clock, ids) of a stochastic solver, else None."""
         ghat = self._force_of(state) if force is False else force
         if lin is None and self._linear():
             lin = self._linear_of(state)
@@ -830,6 +837,11 @@ class PeriodicSolver(object):
         if self.stoch_amp is not None:
             amp, clock, ids = self._noise_of(state)
             noise = (amp, self.stoch_seed, clock, ids)
+        return ghat, lin, noise
+
+    def _launch_steps(self, state, nsteps, force=False, lin=None):
+        """The step this solver takes on this state, with the inputs of ``_step_inputs``; ops.spec_ns_advance_ picks the entry."""
+        ghat, lin, noise = self._step_inputs(state, force, lin)
         ops.spec_ns_advance_(state.what, state.that, state.mean, ghat, state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu, self.drag,
                              0.0 if self.kappa is None else self.kappa, self.scalar_gradient, self.buoyancy, lin, noise, nsteps)
 
@@ -842,31 +854,53 @@ class PeriodicSolver(object):
         return state
 
     # ---- forward mode
-    def _tangent_spectrum(self, who, dwhat, state):
-        """The checked tangent spectrum of ``who`` for this state; refuses a state that carries a scalar."""
-        self._state(state)
-        if state.that is not None:
-            raise NotImplementedError("%s: the tangent of the scalar system is not built yet: the state carries a scalar (passive or buoyant); "
-                                      "a state without one is stepped as by step (use step_tangent_scalar)" % who)
-        if not isinstance(dwhat, torch.Tensor):
-            raise TypeError("%s: dwhat must be a torch tensor, got %s" % (who, type(dwhat).__name__))
-        if dwhat.dtype != torch.float32 or tuple(dwhat.shape) != tuple(state.what.shape) or dwhat.device != state.what.device \
-                or not dwhat.is_contiguous():
-            raise ValueError("%s: dwhat must be a contiguous float32 %s tensor on the state's device (init_vorticity(dw).what), got %s %s on %s"
-                             % (who, list(state.what.shape), dwhat.dtype, tuple(dwhat.shape), dwhat.device))
-        return dwhat
+    def _tangent(self, who, spectra, state=None, members=False):
+        """The checked tangent spectra of ``who``: (dwhat,) for a method of the flow alone, whose state must carry no scalar, (dwhat, dthat)
+        for a ``_scalar`` method, whose solver needs ``kappa`` and whose state must carry one.  Each a contiguous float32 device tensor
+        like ``state.what``, or with ``members`` K of them, [K, B, my1, nx, 2] (state None, the Gram matrix and the orthonormalisation: of
+        any batch), dthat like dwhat.  Returns K (None without ``members``)."""
+        scalar = len(spectra) == 2
+        if scalar and self.kappa is None:
+            raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use %s"
+                             % (who, who.replace('_scalar', '')))
+        if state is not None:
+            self._state(state)
+            if scalar and state.that is None:
+                raise ValueError("%s: the state carries no scalar (build it with init(u, v, theta) on a solver with kappa); "
+                                 "without one use %s" % (who, who.replace('_scalar', '')))
+            if not scalar and state.that is not None:
+                raise NotImplementedError("%s: the tangent of the scalar system is not built here: the state carries a scalar (passive or "
+                                          "buoyant); use %s_scalar, or a state without one" % (who, who))
+        want = (['K'] if members else []) + ['B' if state is None else state.batch, self.my1, self.nx, 2]
+        for name, d in zip(('dwhat', 'dthat'), spectra):
+            if not isinstance(d, torch.Tensor):
+                raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(d).__name__))
+            if d.dtype != torch.float32 or d.dim() != len(want) or tuple(d.shape[-3:]) != tuple(want[-3:]) or not d.is_cuda \
+                    or not d.is_contiguous() or (state is not None and (d.shape[-4] != state.batch or d.device != state.what.device)):
+                raise ValueError("%s: %s must be a contiguous float32 [%s] tensor on the %s, got %s %s on %s"
+                                 % (who, name, ', '.join(map(str, want)), "device" if state is None else "state's device", d.dtype,
+                                    tuple(d.shape), d.device))
+        if scalar and (tuple(spectra[1].shape) != tuple(spectra[0].shape) or spectra[1].device != spectra[0].device):
+            raise ValueError("%s: dwhat and dthat must share their shape and device, got %s on %s and %s on %s"
+                             % (who, tuple(spectra[0].shape), spectra[0].device, tuple(spectra[1].shape), spectra[1].device))
+        if not members:
+            return None
+        K = int(spectra[0].shape[0])
+        if not 1 <= K <= ops.SPEC_NS_MAX_TANGENTS:
+            raise ValueError("%s: K = %d tangents, must be in [1, %d]" % (who, K, ops.SPEC_NS_MAX_TANGENTS))
+        return K
 
-    def _launch_tangent(self, state, dwhat, nsteps, dghat, force=False):
-        """``_launch_steps`` with the perturbation dwhat riding along: the same choice of force, table and noise, so the base is that step."""
-        ghat = self._force_of(state) if force is False else force
-        lin = self._linear_of(state) if self._linear() else None
-        noise = None
-        if self.stoch_amp is not None:
-            amp, clock, ids = self._noise_of(state)
-            noise = (amp, self.stoch_seed, clock, ids)
-        state.work = self._work(ops.spec_ns_tangent_workspace, state.batch, state.what.device, have=state.work)
-        ops.spec_ns_step_tangent_(state.what, dwhat, state.mean, ghat, dghat, state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu, self.drag,
-                                  lin, noise, nsteps)
+    def _launch_tangent(self, state, dwhat, dthat=None, K=None, nsteps=1, dghat=None, force=False):
+        """``_launch_steps`` with a perturbation riding along, the inputs those of ``_step_inputs``, so the base is that step.  The one place
+        that picks a tangent step's C entry: dthat None, the flow's tangent, else the pair's on a state with a scalar; K None, one tangent
+        (which alone takes a source perturbation dghat), else K members [K, B, my1, nx, 2].  Grows ``state.work`` to that entry's workspace."""
+        ghat, lin, noise = self._step_inputs(state, force)
+        scalar, single = dthat is not None, K is None
+        query, step = _TANGENT_STEPS[scalar, single]
+        state.work = self._work(query if single else lambda B, nx, ny: query(B, K, nx, ny), state.batch, state.what.device, have=state.work)
+        step(*((state.what, state.that, dwhat, dthat) if scalar else (state.what, dwhat)), state.mean, *((ghat, dghat) if single else (ghat,)),
+             state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu, self.drag,
+             *((self.kappa, self.scalar_gradient, self.buoyancy) if scalar else ()), lin, noise, nsteps)
 
     def _dforcing(self, who, dforcing, state):
         """dg^ of the source perturbation ``dforcing`` ([B or 1, nx, ny] or [nx, ny]; None passes) for this state."""
@@ -884,26 +918,42 @@ class PeriodicSolver(object):
         the call; its band-limited, zero-mean part acts.  Grows ``state.work`` to the tangent workspace on first use (take one step outside
         before capturing one in a graph); otherwise no allocation without ``dforcing`` and no host synchronisation.  A state that carries a
         scalar is refused: NotImplementedError."""
-        self._tangent_spectrum('step_tangent', dwhat, state)
+        self._tangent('step_tangent', (dwhat,), state)
         nsteps = _count('nsteps', nsteps, 0)
-        self._launch_tangent(state, dwhat, nsteps, self._dforcing('step_tangent', dforcing, state))
+        self._launch_tangent(state, dwhat, None, None, nsteps, self._dforcing('step_tangent', dforcing, state))
         state.steps += nsteps
         return dwhat
 
-    def _evolve_tangent(self, who, state, dstate, nsteps, forcing, dforcing, clock, noise_ids):
+    def _evolve_tangent(self, who, velocity, fields, dfields, nsteps, mean, forcing, dforcing, clock, noise_ids):
+        """The four ``evolve*_tangent*``: the states of ``fields`` and of their perturbations ``dfields`` -- (w,) or (u0, v0), then theta for
+        a ``_scalar`` method --, the tangent steps, and both read back in that order, the perturbation as a state at rest that carries
+        dthat where there is one."""
+        scalar = len(fields) > (2 if velocity else 1)
+        if scalar and self.kappa is None:
+            raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use %s"
+                             % (who, who.replace('_scalar', '')))
+        det = lambda a: a.detach() if isinstance(a, torch.Tensor) else a
+        squeeze = isinstance(fields[0], (torch.Tensor, np.ndarray)) and fields[0].ndim == 2
+        if velocity:
+            state, dstate = self.init(*map(det, fields)), self.init(*map(det, dfields))
+        else:
+            def make(f, mean=None):
+                st = self.init_vorticity(det(f[0]), mean)
+                return self._with_scalar(who, st, f[1]) if scalar else st
+            state, dstate = make(fields, mean), make(dfields)
         nsteps = _count('nsteps', nsteps, 1)
         if state.what.shape != dstate.what.shape:
             raise ValueError("%s: the fields and their perturbations must share their shape" % who)
-        if forcing is None:
-            ghat = self._force_of(state)
-        else:
-            ghat = self._source_spectrum(self._field('forcing', forcing.detach() if isinstance(forcing, torch.Tensor) else forcing)
-                                         .to(state.what.device), state)
+        ghat = self._force_of(state) if forcing is None else self._source_spectrum(self._field('forcing', det(forcing)).to(state.what.device), state)
         if self.stoch_amp is not None:
             state.clock, state.noise_ids = self._noise_args(clock, noise_ids, state)
-        self._launch_tangent(state, dstate.what, nsteps, self._dforcing(who, dforcing, state), ghat)
+        self._launch_tangent(state, dstate.what, dstate.that, None, nsteps, self._dforcing(who, dforcing, state), ghat)
         state.steps += nsteps
-        return state, self._at_rest(dstate.what, state.work)
+        rest = self._at_rest(dstate.what, state.work)
+        rest.that = dstate.that
+        read = (lambda s: tuple(self.fields(s)[:2])) if velocity else (lambda s: (self.vorticity(s),))
+        out = tuple(o for s in (state, rest) for o in read(s) + ((self.scalar(s),) if scalar else ()))
+        return tuple(o[0] for o in out) if squeeze else out
 
     def evolve_tangent(self, w, dw, nsteps=1, mean=None, forcing=None, dforcing=None, clock=0, noise_ids=None):
         """(w_out, dw_out): the vorticity field after ``nsteps`` steps from w, bitwise ``evolve``'s forward, and the perturbation dw carried
@@ -913,23 +963,34 @@ class PeriodicSolver(object):
         ``evolve``; ``dforcing``: the perturbation of the source, [B or 1, nx, ny].  The noise of a stochastic solver is a constant of the
         call: the base takes the kicks, the perturbation none.  NOT an autograd node: the inputs are detached and nothing is recorded.
         Nothing is stored per step.  No ``theta`` and no ``operator``."""
-        squeeze = isinstance(w, (torch.Tensor, np.ndarray)) and w.ndim == 2
-        state = self.init_vorticity(w.detach() if isinstance(w, torch.Tensor) else w, mean)
-        dstate = self.init_vorticity(dw.detach() if isinstance(dw, torch.Tensor) else dw)
-        state, rest = self._evolve_tangent('evolve_tangent', state, dstate, nsteps, forcing, dforcing, clock, noise_ids)
-        out = self.vorticity(state), self.vorticity(rest)
-        return tuple(o[0] for o in out) if squeeze else out
+        return self._evolve_tangent('evolve_tangent', False, (w,), (dw,), nsteps, mean, forcing, dforcing, clock, noise_ids)
 
     def evolve_velocity_tangent(self, u0, v0, du0, dv0, nsteps=1, forcing=None, dforcing=None, clock=0, noise_ids=None):
         """``evolve_tangent`` from and to the velocity: (u, v, du, dv) after ``nsteps`` steps from (u0, v0) and the perturbation (du0, dv0):
         ``init`` of both (the perturbation's grid mean is dropped: the mean flow is a constant of the call), the tangent steps, ``fields`` of
         both.  (u, v) are bitwise ``evolve_velocity``'s forward.  NOT an autograd node: the inputs are detached."""
-        det = lambda a: a.detach() if isinstance(a, torch.Tensor) else a
-        squeeze = isinstance(u0, (torch.Tensor, np.ndarray)) and u0.ndim == 2
-        state, dstate = self.init(det(u0), det(v0)), self.init(det(du0), det(dv0))
-        state, rest = self._evolve_tangent('evolve_velocity_tangent', state, dstate, nsteps, forcing, dforcing, clock, noise_ids)
-        out = tuple(self.fields(state)[:2]) + tuple(self.fields(rest)[:2])
-        return tuple(o[0] for o in out) if squeeze else out
+        return self._evolve_tangent('evolve_velocity_tangent', True, (u0, v0), (du0, dv0), nsteps, None, forcing, dforcing, clock, noise_ids)
+
+    def _growth_rate(self, spectra, norm, step, nsteps, every):
+        """The loop of ``lyapunov_exponent`` and ``lyapunov_exponent_scalar``: sum log(growth) / (nsteps dt) over segments of ``every``
+        steps ``step(n)``, growth = sqrt(norm() after / before); at the start and after every segment each of ``spectra`` is rescaled, in
+        their order, by the one float32 factor per grid that brings norm() to 1."""
+        def rescale(e):                                  # to unit norm; the norm they then have, with the float32 factor as rounded
+            f = torch.rsqrt(e).to(torch.float32)
+            for d in spectra:
+                d.mul_(f.reshape(-1, 1, 1, 1))
+            return e * f.to(torch.float64) ** 2
+        before = rescale(norm())
+        total = torch.zeros_like(before)
+        done = 0
+        while done < nsteps:
+            n = min(every, nsteps - done)
+            step(n)
+            after = norm()
+            total += 0.5 * torch.log(after / before)
+            before = rescale(after)
+            done += n
+        return total / (nsteps * self.dt)
 
     def lyapunov_exponent(self, state, dwhat, nsteps, renormalize_every):
         """The leading finite-time Lyapunov exponent of every grid in the energy norm, float64 [B] on the device: sum log(growth) / (nsteps dt)
@@ -937,53 +998,12 @@ class PeriodicSolver(object):
         perturbation's energy per segment of ``renormalize_every`` steps, after each of which (and at the start) dwhat is rescaled to unit
         energy: one torch multiply.  E is ``diagnostics(_at_rest(dwhat)).energy``, summed on the device in float64.  No host synchronisation:
         the caller's read of the result is the only one.  A grid whose perturbation has no energy gives nan."""
-        self._tangent_spectrum('lyapunov_exponent', dwhat, state)
+        self._tangent('lyapunov_exponent', (dwhat,), state)
         nsteps, every = _count('nsteps', nsteps, 1), _count('renormalize_every', renormalize_every, 1)
-        energy = lambda: ops.spec_ns_diag(dwhat, None, self.ny, self.Lx, self.Ly)[:, 0]
-
-        def rescale(e):                                  # dwhat to unit energy; the energy it then has, with the float32 factor as rounded
-            f = torch.rsqrt(e).to(torch.float32)
-            dwhat.mul_(f.reshape(-1, 1, 1, 1))
-            return e * f.to(torch.float64) ** 2
-        before = rescale(energy())
-        total = torch.zeros_like(before)
-        done = 0
-        while done < nsteps:
-            n = min(every, nsteps - done)
-            self.step_tangent(state, dwhat, n)
-            after = energy()
-            total += 0.5 * torch.log(after / before)
-            before = rescale(after)
-            done += n
-        return total / (nsteps * self.dt)
+        return self._growth_rate((dwhat,), lambda: ops.spec_ns_diag(dwhat, None, self.ny, self.Lx, self.Ly)[:, 0],
+                                 lambda n: self.step_tangent(state, dwhat, n), nsteps, every)
 
     # ---- forward mode of the system with a scalar
-    def _tangent_pair(self, who, dwhat, dthat, state):
-        """The checked tangent spectra (dwhat, dthat) of ``who`` for this state, which must carry a scalar."""
-        self._state(state)
-        if state.that is None:
-            raise ValueError("%s: the state carries no scalar (build it with init(u, v, theta) on a solver with kappa); "
-                             "without one use %s" % (who, who.replace('_scalar', '')))
-        for name, d in (('dwhat', dwhat), ('dthat', dthat)):
-            if not isinstance(d, torch.Tensor):
-                raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(d).__name__))
-            if d.dtype != torch.float32 or tuple(d.shape) != tuple(state.what.shape) or d.device != state.what.device or not d.is_contiguous():
-                raise ValueError("%s: %s must be a contiguous float32 %s tensor on the state's device, got %s %s on %s"
-                                 % (who, name, list(state.what.shape), d.dtype, tuple(d.shape), d.device))
-        return dwhat, dthat
-
-    def _launch_tangent_scalar(self, state, dwhat, dthat, nsteps, dghat, force=False):
-        """``_launch_steps`` on a state with a scalar, the pair (dwhat, dthat) riding along: the same force, table and noise, so the base is that step."""
-        ghat = self._force_of(state) if force is False else force
-        lin = self._linear_of(state) if self._linear() else None
-        noise = None
-        if self.stoch_amp is not None:
-            amp, clock, ids = self._noise_of(state)
-            noise = (amp, self.stoch_seed, clock, ids)
-        state.work = self._work(ops.spec_ns_scalar_tangent_workspace, state.batch, state.what.device, have=state.work)
-        ops.spec_ns_step_scalar_tangent_(state.what, state.that, dwhat, dthat, state.mean, ghat, dghat, state.work, self.ny, self.Lx, self.Ly,
-                                         self.dt, self.nu, self.drag, self.kappa, self.scalar_gradient, self.buoyancy, lin, noise, nsteps)
-
     def step_tangent_scalar(self, state, dwhat, dthat, nsteps=1, dforcing=None):
         """``step(state, nsteps)`` on a state that carries a scalar -- bitwise, ``state.steps`` and ``state.clock`` included -- with the tangent
         spectra ``dwhat`` and ``dthat`` (float32 [B, my1, nx, 2], the layout of ``state.what``) advanced in place by the Jacobian of those
@@ -992,26 +1012,11 @@ class PeriodicSolver(object):
         ``dforcing`` as in ``step_tangent`` (the scalar has no source).  Grows ``state.work`` to the scalar tangent's workspace on first use
         (take one step outside before capturing one in a graph); otherwise no allocation without ``dforcing`` and no host synchronisation.
         ValueError on a state without a scalar."""
-        self._tangent_pair('step_tangent_scalar', dwhat, dthat, state)
+        self._tangent('step_tangent_scalar', (dwhat, dthat), state)
         nsteps = _count('nsteps', nsteps, 0)
-        self._launch_tangent_scalar(state, dwhat, dthat, nsteps, self._dforcing('step_tangent_scalar', dforcing, state))
+        self._launch_tangent(state, dwhat, dthat, None, nsteps, self._dforcing('step_tangent_scalar', dforcing, state))
         state.steps += nsteps
         return dwhat, dthat
-
-    def _evolve_tangent_scalar(self, who, state, dstate, nsteps, forcing, dforcing, clock, noise_ids):
-        nsteps = _count('nsteps', nsteps, 1)
-        if state.what.shape != dstate.what.shape:
-            raise ValueError("%s: the fields and their perturbations must share their shape" % who)
-        if forcing is None:
-            ghat = self._force_of(state)
-        else:
-            ghat = self._source_spectrum(self._field('forcing', forcing.detach() if isinstance(forcing, torch.Tensor) else forcing)
-                                         .to(state.what.device), state)
-        if self.stoch_amp is not None:
-            state.clock, state.noise_ids = self._noise_args(clock, noise_ids, state)
-        self._launch_tangent_scalar(state, dstate.what, dstate.that, nsteps, self._dforcing(who, dforcing, state), ghat)
-        state.steps += nsteps
-        return state, PeriodicState(dstate.what, torch.zeros_like(state.mean), state.work, dstate.that)
 
     def _with_scalar(self, who, state, theta):
         """``state`` (of init_vorticity) with the scalar theta, as ``evolve`` builds it."""
@@ -1029,78 +1034,28 @@ class PeriodicSolver(object):
         ``evolve(w, nsteps, theta=theta, ...)``, and the perturbation (dw, dtheta) carried along with them by the Jacobian of those steps
         (+ the response to ``dforcing``) -- the forward-mode twin of ``evolve`` with a scalar, whose backward gives J^T r.  The arguments of
         ``evolve_tangent``; the solver needs ``kappa``.  NOT an autograd node: the inputs are detached and nothing is recorded."""
-        who = 'evolve_tangent_scalar'
-        det = lambda a: a.detach() if isinstance(a, torch.Tensor) else a
-        squeeze = isinstance(w, (torch.Tensor, np.ndarray)) and w.ndim == 2
-        state = self._with_scalar(who, self.init_vorticity(det(w), mean), theta)
-        dstate = self._with_scalar(who, self.init_vorticity(det(dw)), dtheta)
-        state, rest = self._evolve_tangent_scalar(who, state, dstate, nsteps, forcing, dforcing, clock, noise_ids)
-        out = self.vorticity(state), self.scalar(state), self.vorticity(rest), self.scalar(rest)
-        return tuple(o[0] for o in out) if squeeze else out
+        return self._evolve_tangent('evolve_tangent_scalar', False, (w, theta), (dw, dtheta), nsteps, mean, forcing, dforcing, clock, noise_ids)
 
     def evolve_velocity_tangent_scalar(self, u0, v0, theta0, du0, dv0, dtheta0, nsteps=1, forcing=None, dforcing=None, clock=0, noise_ids=None):
         """``evolve_tangent_scalar`` from and to the velocity: (u, v, theta, du, dv, dtheta) after ``nsteps`` steps; (u, v, theta) are bitwise
         the forward of ``evolve_velocity(u0, v0, nsteps, theta0=theta0, ...)``.  The perturbation's grid-mean velocity is dropped.  NOT an
         autograd node: the inputs are detached."""
-        who = 'evolve_velocity_tangent_scalar'
-        if self.kappa is None:
-            raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use evolve_velocity_tangent" % who)
-        det = lambda a: a.detach() if isinstance(a, torch.Tensor) else a
-        squeeze = isinstance(u0, (torch.Tensor, np.ndarray)) and u0.ndim == 2
-        state, dstate = self.init(det(u0), det(v0), det(theta0)), self.init(det(du0), det(dv0), det(dtheta0))
-        state, rest = self._evolve_tangent_scalar(who, state, dstate, nsteps, forcing, dforcing, clock, noise_ids)
-        out = tuple(self.fields(state)[:2]) + (self.scalar(state),) + tuple(self.fields(rest)[:2]) + (self.scalar(rest),)
-        return tuple(o[0] for o in out) if squeeze else out
+        return self._evolve_tangent('evolve_velocity_tangent_scalar', True, (u0, v0, theta0), (du0, dv0, dtheta0), nsteps, None, forcing, dforcing,
+                                    clock, noise_ids)
 
     def lyapunov_exponent_scalar(self, state, dwhat, dthat, nsteps, renormalize_every, scalar_weight=1.0):
         """``lyapunov_exponent`` of the system with a scalar, float64 [B] on the device, in the norm E(dw) + scalar_weight 1/2 <dtheta'^2>
         (``scalar_weight`` > 0; the mean of dtheta does not enter): E is column 0 of ``ops.spec_ns_diag`` of dwhat, the variance column 0 of
         ``ops.spec_ns_scalar_diag`` of (dwhat, dthat), both summed on the device in float64, and both spectra are rescaled by the one factor
         after every ``renormalize_every`` steps of ``step_tangent_scalar`` (and at the start).  No host synchronisation."""
-        self._tangent_pair('lyapunov_exponent_scalar', dwhat, dthat, state)
+        self._tangent('lyapunov_exponent_scalar', (dwhat, dthat), state)
         nsteps, every = _count('nsteps', nsteps, 1), _count('renormalize_every', renormalize_every, 1)
         weight = _real('scalar_weight', scalar_weight, '> 0')
         norm = lambda: (ops.spec_ns_diag(dwhat, None, self.ny, self.Lx, self.Ly)[:, 0]
                         + weight * ops.spec_ns_scalar_diag(dwhat, dthat, self.ny, self.Lx, self.Ly, self.kappa)[:, 0])
-
-        def rescale(e):                                  # the pair to unit norm; the norm it then has, with the float32 factor as rounded
-            f = torch.rsqrt(e).to(torch.float32)
-            dwhat.mul_(f.reshape(-1, 1, 1, 1))
-            dthat.mul_(f.reshape(-1, 1, 1, 1))
-            return e * f.to(torch.float64) ** 2
-        before = rescale(norm())
-        total = torch.zeros_like(before)
-        done = 0
-        while done < nsteps:
-            n = min(every, nsteps - done)
-            self.step_tangent_scalar(state, dwhat, dthat, n)
-            after = norm()
-            total += 0.5 * torch.log(after / before)
-            before = rescale(after)
-            done += n
-        return total / (nsteps * self.dt)
+        return self._growth_rate((dwhat, dthat), norm, lambda n: self.step_tangent_scalar(state, dwhat, dthat, n), nsteps, every)
 
     # ---- K tangents on one base
-    def _tangent_spectra(self, who, dwhat, state=None):
-        """The checked tangents [K, B, my1, nx, 2] of ``who`` (for this state, which must carry no scalar); K."""
-        if state is not None:
-            self._state(state)
-            if state.that is not None:
-                raise NotImplementedError("%s: the tangent of the scalar system is not built here: the state carries a scalar (passive or buoyant); "
-                                          "use %s_scalar, or a state without one" % (who, who))
-        if not isinstance(dwhat, torch.Tensor):
-            raise TypeError("%s: dwhat must be a torch tensor, got %s" % (who, type(dwhat).__name__))
-        want = (self.my1, self.nx, 2) if state is None else tuple(state.what.shape[1:])
-        if dwhat.dtype != torch.float32 or dwhat.dim() != 5 or tuple(dwhat.shape[2:]) != want or not dwhat.is_cuda or not dwhat.is_contiguous() \
-                or (state is not None and (dwhat.shape[1] != state.batch or dwhat.device != state.what.device)):
-            raise ValueError("%s: dwhat must be a contiguous float32 [K, %s, %d, %d, 2] tensor on the %s (init_tangents(dw)), got %s %s on %s"
-                             % (who, 'B' if state is None else state.batch, self.my1, self.nx, "device" if state is None else "state's device",
-                                dwhat.dtype, tuple(dwhat.shape), dwhat.device))
-        K = int(dwhat.shape[0])
-        if not 1 <= K <= ops.SPEC_NS_MAX_TANGENTS:
-            raise ValueError("%s: K = %d tangents, must be in [1, %d]" % (who, K, ops.SPEC_NS_MAX_TANGENTS))
-        return K
-
     def init_tangents(self, dw):
         """The spectra [K, B, my1, nx, 2] of K perturbation vorticity fields dw (float32 [K, B, nx, ny]): ``init_vorticity(dw[k]).what`` of
         every member, in one call on the K B fields (the band-limited part, the (0, 0) mode zeroed)."""
@@ -1118,23 +1073,16 @@ class PeriodicSolver(object):
         the state (the class note, "Forward mode").  Grows ``state.work`` to the workspace of K tangents on first use (take one step outside
         before capturing one in a graph); otherwise no allocation and no host synchronisation.  A state that carries a scalar is refused:
         NotImplementedError."""
-        K = self._tangent_spectra('step_tangents', dwhat, state)
+        K = self._tangent('step_tangents', (dwhat,), state, members=True)
         nsteps = _count('nsteps', nsteps, 0)
-        lin = self._linear_of(state) if self._linear() else None
-        noise = None
-        if self.stoch_amp is not None:
-            amp, clock, ids = self._noise_of(state)
-            noise = (amp, self.stoch_seed, clock, ids)
-        state.work = self._work(lambda B, nx, ny: ops.spec_ns_tangents_workspace(B, K, nx, ny), state.batch, state.what.device, have=state.work)
-        ops.spec_ns_step_tangents_(state.what, dwhat, state.mean, self._force_of(state), state.work, self.ny, self.Lx, self.Ly, self.dt, self.nu,
-                                   self.drag, lin, noise, nsteps)
+        self._launch_tangent(state, dwhat, None, K, nsteps)
         state.steps += nsteps
         return dwhat
 
     def tangent_gram(self, dwhat):
         """float64 [B, K, K] on the device: the Gram matrix of the K tangents of every grid in the energy inner product, 1/2 <du_k . du_l>;
         its diagonal is ``diagnostics(_at_rest(dwhat[k])).energy``.  Bitwise symmetric; two calls give the same bits."""
-        self._tangent_spectra('tangent_gram', dwhat)
+        self._tangent('tangent_gram', (dwhat,), members=True)
         return ops.spec_ns_tangent_gram(dwhat, self.ny, self.Lx, self.Ly)
 
     def orthonormalize_tangents(self, dwhat):
@@ -1144,7 +1092,7 @@ class PeriodicSolver(object):
         HIP; the Cholesky factor and its triangular inverse are [B, K, K] float64 torch on the device, without error checks, so nothing
         synchronises.  The logs of the two passes add.  A grid whose vectors are dependent gives nan, as ``lyapunov_exponent`` does for a
         perturbation without energy."""
-        K = self._tangent_spectra('orthonormalize_tangents', dwhat)
+        K = self._tangent('orthonormalize_tangents', (dwhat,), members=True)
         return self._cholesky_qr_twice(K, dwhat.device, lambda: ops.spec_ns_tangent_gram(dwhat, self.ny, self.Lx, self.Ly),
                                        lambda rinv: ops.spec_ns_tangent_combine_(dwhat, rinv, self.ny))
 
@@ -1168,51 +1116,29 @@ class PeriodicSolver(object):
             logs = lg if logs is None else logs + lg
         return logs
 
+    def _exponents(self, step, orthonormalize, nsteps, every):
+        """The loop of ``lyapunov_spectrum`` and ``lyapunov_spectrum_scalar``: the sum of ``orthonormalize()``'s log(diag R) after every
+        segment of ``every`` steps ``step(n)`` (the one at the start only orthonormalises) / (nsteps dt)."""
+        total = torch.zeros_like(orthonormalize())
+        done = 0
+        while done < nsteps:
+            n = min(every, nsteps - done)
+            step(n)
+            total += orthonormalize()
+            done += n
+        return total / (nsteps * self.dt)
+
     def lyapunov_spectrum(self, state, dwhat, nsteps, renormalize_every):
         """The first K finite-time Lyapunov exponents of every grid in the energy norm, float64 [B, K] on the device: the tangents are
         orthonormalised at the start and after every ``renormalize_every`` steps of ``step_tangents``, and the exponents are the sums of
         log(diag R) of those factorisations (the first one's excepted) / (nsteps dt).  State and dwhat are advanced in place; dwhat is left
         orthonormal: the backward Lyapunov vectors at the end of the run.  The exponents come in the order of the vectors, unsorted; they
         approach descending order as the run grows.  No host synchronisation.  A grid whose vectors become dependent gives nan."""
-        self._tangent_spectra('lyapunov_spectrum', dwhat, state)
+        self._tangent('lyapunov_spectrum', (dwhat,), state, members=True)
         nsteps, every = _count('nsteps', nsteps, 1), _count('renormalize_every', renormalize_every, 1)
-        total = torch.zeros_like(self.orthonormalize_tangents(dwhat))
-        done = 0
-        while done < nsteps:
-            n = min(every, nsteps - done)
-            self.step_tangents(state, dwhat, n)
-            total += self.orthonormalize_tangents(dwhat)
-            done += n
-        return total / (nsteps * self.dt)
+        return self._exponents(lambda n: self.step_tangents(state, dwhat, n), lambda: self.orthonormalize_tangents(dwhat), nsteps, every)
 
     # ---- K tangent pairs on one base with a scalar
-    def _tangent_pairs(self, who, dwhat, dthat, state=None):
-        """The checked tangent pairs (dwhat, dthat), [K, B, my1, nx, 2] each, of ``who`` (for this state, which must carry a scalar); K."""
-        if self.kappa is None:
-            raise ValueError("%s needs a solver built with kappa (the scalar's diffusivity); without a scalar use %s"
-                             % (who, who.replace('_scalar', '')))
-        if state is not None:
-            self._state(state)
-            if state.that is None:
-                raise ValueError("%s: the state carries no scalar (build it with init(u, v, theta) on a solver with kappa); "
-                                 "without one use %s" % (who, who.replace('_scalar', '')))
-        want = (self.my1, self.nx, 2) if state is None else tuple(state.what.shape[1:])
-        for name, d in (('dwhat', dwhat), ('dthat', dthat)):
-            if not isinstance(d, torch.Tensor):
-                raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(d).__name__))
-            if d.dtype != torch.float32 or d.dim() != 5 or tuple(d.shape[2:]) != want or not d.is_cuda or not d.is_contiguous() \
-                    or (state is not None and (d.shape[1] != state.batch or d.device != state.what.device)):
-                raise ValueError("%s: %s must be a contiguous float32 [K, %s, %d, %d, 2] tensor on the %s (init_tangents_scalar(dw, dtheta)), "
-                                 "got %s %s on %s" % (who, name, 'B' if state is None else state.batch, self.my1, self.nx,
-                                                      "device" if state is None else "state's device", d.dtype, tuple(d.shape), d.device))
-        if tuple(dthat.shape) != tuple(dwhat.shape) or dthat.device != dwhat.device:
-            raise ValueError("%s: dwhat and dthat must share their shape and device, got %s on %s and %s on %s"
-                             % (who, tuple(dwhat.shape), dwhat.device, tuple(dthat.shape), dthat.device))
-        K = int(dwhat.shape[0])
-        if not 1 <= K <= ops.SPEC_NS_MAX_TANGENTS:
-            raise ValueError("%s: K = %d tangents, must be in [1, %d]" % (who, K, ops.SPEC_NS_MAX_TANGENTS))
-        return K
-
     def init_tangents_scalar(self, dw, dtheta):
         """(dwhat, dthat), [K, B, my1, nx, 2] each: the spectra of K perturbation pairs (dw, dtheta) (float32 [K, B, nx, ny] each).  dwhat is
         ``init_tangents(dw)``; dthat is ``ops.spec_ns_scalar_init`` on the K B fields: the band-limited part with the mean, the (0, 0) mode, kept."""
@@ -1235,18 +1161,9 @@ class PeriodicSolver(object):
         every pair bitwise as by ``step_tangent_scalar`` on a clone of the state (the class note, "Forward mode").  Grows ``state.work`` to
         the workspace of K pairs on first use (take one step outside before capturing one in a graph); otherwise no allocation and no host
         synchronisation.  ValueError on a state without a scalar (use ``step_tangents``)."""
-        K = self._tangent_pairs('step_tangents_scalar', dwhat, dthat, state)
+        K = self._tangent('step_tangents_scalar', (dwhat, dthat), state, members=True)
         nsteps = _count('nsteps', nsteps, 0)
-        lin = self._linear_of(state) if self._linear() else None
-        noise = None
-        if self.stoch_amp is not None:
-            amp, clock, ids = self._noise_of(state)
-            noise = (amp, self.stoch_seed, clock, ids)
-        state.work = self._work(lambda B, nx, ny: ops.spec_ns_scalar_tangents_workspace(B, K, nx, ny), state.batch, state.what.device,
-                                have=state.work)
-        ops.spec_ns_step_scalar_tangents_(state.what, state.that, dwhat, dthat, state.mean, self._force_of(state), state.work, self.ny, self.Lx,
-                                          self.Ly, self.dt, self.nu, self.drag, self.kappa, self.scalar_gradient, self.buoyancy, lin, noise,
-                                          nsteps)
+        self._launch_tangent(state, dwhat, dthat, K, nsteps)
         state.steps += nsteps
         return dwhat, dthat
 
@@ -1254,7 +1171,7 @@ class PeriodicSolver(object):
         """float64 [B, K, K] on the device: the Gram matrix of the K tangent pairs of every grid in the inner product of
         ``lyapunov_exponent_scalar``, 1/2 <du_k . du_l> + scalar_weight 1/2 <dtheta_k' dtheta_l'> (``scalar_weight`` > 0; the means of dtheta
         do not enter): ``tangent_gram(dwhat)`` + scalar_weight times the variance Gram matrix of dthat.  Bitwise symmetric and repeatable."""
-        self._tangent_pairs('tangent_gram_scalar', dwhat, dthat)
+        self._tangent('tangent_gram_scalar', (dwhat, dthat), members=True)
         weight = _real('scalar_weight', scalar_weight, '> 0')
         return ops.spec_ns_tangent_gram(dwhat, self.ny, self.Lx, self.Ly) + weight * ops.spec_ns_tangent_variance_gram(dthat, self.ny)
 
@@ -1265,7 +1182,7 @@ class PeriodicSolver(object):
         synchronisation.  The Gram matrix is a sum of two float64 matrices, so the pivot of an exactly dependent vector is rounding noise of
         either sign where the energy Gram alone cancels to zero: a pivot with R_kk^2 <= 1e-13 G_kk (450 float64 ulps; the nearly dependent
         sets a second pass can still repair sit near 1e-10) also counts as failed."""
-        K = self._tangent_pairs('orthonormalize_tangents_scalar', dwhat, dthat)
+        K = self._tangent('orthonormalize_tangents_scalar', (dwhat, dthat), members=True)
         weight = _real('scalar_weight', scalar_weight, '> 0')
 
         def combine(rinv):
@@ -1279,17 +1196,11 @@ class PeriodicSolver(object):
         pairs are orthonormalised (``orthonormalize_tangents_scalar``) at the start and after every ``renormalize_every`` steps of
         ``step_tangents_scalar``.  State and pairs are advanced in place; the pairs are left orthonormal.  ``kaplan_yorke_dimension`` applies
         to the result.  No host synchronisation."""
-        self._tangent_pairs('lyapunov_spectrum_scalar', dwhat, dthat, state)
+        self._tangent('lyapunov_spectrum_scalar', (dwhat, dthat), state, members=True)
         nsteps, every = _count('nsteps', nsteps, 1), _count('renormalize_every', renormalize_every, 1)
         _real('scalar_weight', scalar_weight, '> 0')
-        total = torch.zeros_like(self.orthonormalize_tangents_scalar(dwhat, dthat, scalar_weight))
-        done = 0
-        while done < nsteps:
-            n = min(every, nsteps - done)
-            self.step_tangents_scalar(state, dwhat, dthat, n)
-            total += self.orthonormalize_tangents_scalar(dwhat, dthat, scalar_weight)
-            done += n
-        return total / (nsteps * self.dt)
+        return self._exponents(lambda n: self.step_tangents_scalar(state, dwhat, dthat, n),
+                               lambda: self.orthonormalize_tangents_scalar(dwhat, dthat, scalar_weight), nsteps, every)
 
     # ---- reverse mode
     def _refuse_unsupported(self, who, scalar=False):
@@ -1572,7 +1483,7 @@ class PeriodicSolver(object):
         for k in range(nsteps):
             what0[k].copy_(state.what)
             dwhat0[k].copy_(dstate.what)
-            self._launch_tangent(state, dstate.what, 1, dghat, ghat)
+            self._launch_tangent(state, dstate.what, None, None, 1, dghat, ghat)
         out = self.vorticity(state), self.vorticity(self._at_rest(dstate.what, state.work))
         return SecondOrderRun(self, tuple(o[0] for o in out) if squeeze else out, what0, dwhat0, state.mean, ghat, dghat,
                               self._linear_of(state) if self._linear() else None, tuple(forcing.shape) if given else None, squeeze)
