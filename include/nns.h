@@ -814,6 +814,52 @@ int nns_spec_ns_particle_sample_f32(const float* coef, const double* pos, float*
 int nns_spec_ns_particle_stage_f32(const float* coef, const double* pos0, const double* pos_in, double* pos_out, double* acc, double a,
                                    double wk, double c, int first, int closing, int order, int batch, long npart, int nx, int ny, double Lx,
                                    double Ly, void* stream);
+/* Reverse mode of the sampling (csrc/pspec_particles.hip; restatement: tests/pspec_particles_adjoint_oracle.py): the transpose of the gather
+ * as a sorted spread without floating-point atomics, the transpose of the coefficient build, and the derivative of a sample in the position.
+ *
+ * nns_spec_ns_particle_cells_i32: key, int32 [batch][npart], <- (b nx + ci) ny + cj, (ci, cj) the wrapped cell of the particle as the gather
+ * finds it (the same float64 floor, the same mask: any position, +-inf and nan included, gives a key inside its own grid).  The caller sorts
+ * the keys STABLY (the particles of a cell stay in ascending index, which fixes the order of summation below) and takes perm, int64
+ * [batch npart] = the particle (an index into [batch][npart]) of every sorted slot, and start, int32 [batch nx ny + 1] = the first slot of
+ * every cell and, last, batch npart (torch.sort and torch.searchsorted on the device; neither synchronises the host).
+ * nns_spec_ns_particle_spread_f32: cbar, float32 [nfields][batch][nx][ny], <- the transpose of nns_spec_ns_particle_sample_f32 applied to
+ * cot, float32 [batch][npart][nfields]: cbar[f][b][i0 + a][j0 + c] = sum_p wx_p[a] wy_p[c] cot[b][p][f].  Gather form: a staging launch (one
+ * lane per sorted slot) writes a record (wx, wy, cot) per slot into work, the forward's weights (float64, rounded once); a node launch (one
+ * lane per node) visits the order x order cells whose stencil covers the node, ci = i - a + order / 2 - 1, cj = j - c + order / 2 - 1 modulo
+ * the axis, a ascending, then c ascending, then the cell's slots ascending; wx[a] wy[c] is one float32 multiply, every term one float64 fma
+ * into one float64 accumulator per field, rounded once on store.  Every node is written (zero where no particle reaches: cbar need not be
+ * cleared); no atomics, so two runs give the same bits and a grid does not depend on its batch neighbours.  perm entries outside
+ * [0, batch npart) contribute nothing and start is clamped to [0, batch npart]: a wrong table reads nothing outside the buffers.
+ * work: nns_spec_ns_particle_spread_workspace(batch, npart, order) = batch npart (2 order + 4) 4 bytes.
+ * nns_spec_ns_particle_sample_grad_f32: grad, float32 [batch][npart][nfields][2], <- (d/dx, d/dy) of the splines of coef at pos: the gather of
+ * nns_spec_ns_particle_sample_f32 with derivative weights on one axis, (1 / hx) sum_a wx'[a] (sum_c wy[c] C) and (1 / hy) sum_a wx[a]
+ * (sum_c wy'[c] C), the same fmaf chains (c ascending inside a ascending), the division in float64.  Order-4 derivative weights -(1-t)^2/2,
+ * (3t^2 - 4t)/2, (-3t^2 + 2t + 1)/2, t^2/2; order 6: B5'(t - j) piece by piece; float64, rounded once.  The splines are C^2 (C^4), so the
+ * derivative is continuous across cells.
+ * nns_spec_ns_particle_coefs_adjoint_f32: the transpose of nns_spec_ns_particle_coefs_f32 as a map between physical fields.  cbar, float32
+ * [nfields][batch][nx][ny]: the cotangents of the coefficient images of the mask `fields`, by ascending bit.  wbar_hat (and thbar_hat with bit
+ * 3), float32 [batch][my1][nx][2] in the layout of what, <- with c^ = nns_spec_rfft2_f32(cbar) inside the 2/3 band
+ *     wbar_hat = [(-i ky c_u^ + i kx c_v^) / |k|^2 + c_w^] / (beta_x beta_y), (0, 0) zero;     thbar_hat = c_theta^ / (beta_x beta_y), (0, 0) kept
+ * the forward's multipliers conjugated (the map is real); the unnormalised transform here stands where the forward's 1 / (nx ny) inverse
+ * stood, so nns_spec_ns_scalar_field_f32 of wbar_hat is the cotangent of the vorticity field that init_vorticity took.  The mean flow gets no
+ * cotangent.  wbar_hat may be NULL without bits 0-2, thbar_hat without bit 3.  work: nns_spec_ns_particle_workspace(batch, nfields, nx, ny).
+ * No allocation, no host synchronisation (capturable).
+ * Errors, all before any launch and in this order: (1) NNS_ERR_INVALID_ARG for a NULL pointer (cells: pos, key; spread: cot, pos, perm, start,
+ * cbar, work; sample_grad: coef, pos, grad; coefs_adjoint: cbar, work) or batch < 1; (2) (cells, spread, sample_grad) for npart < 1 or batch
+ * npart >= 2^31; (3) (spread, sample_grad, coefs_adjoint) for order not 4 or 6; (4) (spread, sample_grad) for nfields not in [1, 4],
+ * (coefs_adjoint) for fields not in [1, 15], then for a NULL wbar_hat with bits 0-2, then a NULL thbar_hat with bit 3; (5) for Lx, Ly not
+ * positive and finite; (6) NNS_ERR_UNSUPPORTED for an axis that is not a power of two in [64, 1024], then (cells, spread) for batch nx ny >=
+ * 2^31; (7) (spread, coefs_adjoint) NNS_ERR_WORKSPACE below the size query.  The spread's query: NNS_ERR_INVALID_ARG for a NULL bytes or
+ * batch < 1, then for npart, then for order. */
+int nns_spec_ns_particle_cells_i32(const double* pos, int* key, int batch, long npart, int nx, int ny, double Lx, double Ly, void* stream);
+int nns_spec_ns_particle_spread_workspace(int batch, long npart, int order, size_t* bytes);
+int nns_spec_ns_particle_spread_f32(const float* cot, const double* pos, const long long* perm, const int* start, float* cbar, int nfields,
+                                    int order, void* work, size_t work_bytes, int batch, long npart, int nx, int ny, double Lx, double Ly,
+                                    void* stream);
+int nns_spec_ns_particle_sample_grad_f32(const float* coef, const double* pos, float* grad, int nfields, int order, int batch, long npart,
+                                         int nx, int ny, double Lx, double Ly, void* stream);
+int nns_spec_ns_particle_coefs_adjoint_f32(const float* cbar, float* wbar_hat, float* thbar_hat, int fields, int order, void* work,
+                                           size_t work_bytes, int batch, int nx, int ny, double Lx, double Ly, void* stream);
 
 /* ---- neural_spectral field predictor: src/neural_spectral/spectral_ode.py, anode/ ------------ */
 enum { NNS_ODE_EULER = 0, NNS_ODE_RK2 = 1, NNS_ODE_RK4 = 2 };   /* anode/scheme.py:21-42 */

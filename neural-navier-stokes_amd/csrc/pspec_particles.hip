@@ -276,3 +276,310 @@ NNS_API int nns_spec_ns_particle_stage_f32(const float* coef, const double* pos0
     else launch_stage<6>(first, closing, grid, as_stream(stream), coef, pos0, pos_in, pos_out, acc, a, wk, c, g);
     return check_launch(who);
 }
+
+// ---------------------------------------------------------------------------------------------------- reverse mode of the sampling
+// (include/nns.h: nns_spec_ns_particle_cells_i32, _spread_f32, _sample_grad_f32, _coefs_adjoint_f32; restatement:
+// tests/pspec_particles_adjoint_oracle.py.)
+//   cells:   key[b][p] = (b nx + ci) ny + cj, (ci, cj) the wrapped cell of ps_locate (the same float64 floor, the same mask).  The caller sorts
+//            the keys (stable: the particles of a cell stay in ascending index) and takes the cells' first slots, start[cells + 1].
+//   spread:  the transpose of the gather as a GATHER over the sorted slots, no atomics.  A staging pass (one lane per slot) writes a record
+//            (wx[ORDER], wy[ORDER], cot[4]) of kRec<ORDER> floats per slot: a particle's float64 weights are made once, and the node pass
+//            reads records that lie in slot order.  The node pass has one lane per node (i, j): the ORDER x ORDER cells whose stencil covers
+//            it are ci = i - a + ORDER / 2 - 1, cj = j - c + ORDER / 2 - 1 (masked); a ascending, then c ascending, then the cell's slots
+//            ascending; wx[a] wy[c] one float32 multiply, every term one float64 fma into one accumulator per field, rounded once on store.
+//            Every node is written.  The trip count of the slot loop differs between the lanes of a wave (a wave runs its fullest cell's);
+//            lanes along j read neighbouring cells, whose slots are neighbours too.
+//   grad:    the gather of sample with the weights' derivatives on one axis, the same chains: both sums share their loads.
+//   coefs adjoint:  nns_spec_rfft2_f32 of the cotangent images, then one pointwise kernel: the forward's multipliers conjugated, the band mask.
+namespace {
+
+template <int ORDER> constexpr int kRec = 2 * ORDER + 4;          // floats per record: 48 or 64 bytes, the cotangents 16-byte aligned
+
+// d w[a] / d t of ps_spline_weights, piece by piece
+template <int ORDER>
+__device__ __forceinline__ void ps_spline_dweights(double t, float (&w)[ORDER]) {
+    if constexpr (ORDER == 4) {
+        const double s = 1.0 - t, t2 = t * t;
+        w[0] = (float)(-s * s / 2.0);
+        w[1] = (float)((3.0 * t2 - 4.0 * t) / 2.0);
+        w[2] = (float)((-3.0 * t2 + 2.0 * t + 1.0) / 2.0);
+        w[3] = (float)(t2 / 2.0);
+    } else {
+        const auto inner = [](double x) { const double x2 = x * x; return (-120.0 * x + 120.0 * x2 * x - 50.0 * x2 * x2) / 120.0; };
+        const auto middle = [](double x) {
+            const double x2 = x * x;
+            return (75.0 - 420.0 * x + 450.0 * x2 - 180.0 * x2 * x + 25.0 * x2 * x2) / 120.0;
+        };
+        const auto outer = [](double r) { const double r2 = r * r; return r2 * r2 / 24.0; };            // r = 3 - |x|
+        w[0] = (float)(-outer(1.0 - t));
+        w[1] = (float)middle(t + 1.0);
+        w[2] = (float)inner(t);
+        w[3] = (float)(-inner(1.0 - t));
+        w[4] = (float)(-middle(2.0 - t));
+        w[5] = (float)outer(t);
+    }
+}
+
+// ps_locate with the derivative weights of the same offset beside the weights
+template <int ORDER>
+__device__ __forceinline__ int ps_locate_grad(double x, double h, int n, float (&w)[ORDER], float (&dw)[ORDER]) {
+    const double s = x / h;
+    ps_spline_dweights<ORDER>(s - floor(s), dw);
+    return ps_locate<ORDER>(x, h, n, w);
+}
+
+// the wrapped cell of ps_locate alone: its first node of order 4 is one node before the cell (the weights are not used)
+__device__ __forceinline__ int ps_cell(double x, double h, int n) {
+    float w[4];
+    return (ps_locate<4>(x, h, n, w) + 1) & (n - 1);
+}
+
+__global__ __launch_bounds__(kPT) void ps_particle_cells_kernel(const double* __restrict__ pos, int* __restrict__ key, PsBox g) {
+    const long total = (long)g.batch * g.npart;
+    const long q = blockIdx.x * (long)kPT + threadIdx.x;
+    if (q >= total) return;
+    const int b = (int)(q / g.npart);
+    key[q] = (b * g.nx + ps_cell(pos[2 * q], g.hx, g.nx)) * g.ny + ps_cell(pos[2 * q + 1], g.hy, g.ny);
+}
+
+// ps_spline_sum with a second sum beside it: gx = sum_a dwx[a] (sum_c wy[c] C), gy = sum_a wx[a] (sum_c dwy[c] C), the chains in its order
+template <int ORDER, bool RUN>
+__device__ __forceinline__ void ps_spline_grad(const float* __restrict__ C, int i0, int j0, int nx, int ny, const float (&wx)[ORDER],
+                                               const float (&wy)[ORDER], const float (&dwx)[ORDER], const float (&dwy)[ORDER], float& gx,
+                                               float& gy) {
+    gx = 0.f;
+    gy = 0.f;
+#pragma unroll
+    for (int a = 0; a < ORDER; ++a) {
+        const float* row = C + (size_t)((i0 + a) & (nx - 1)) * ny;
+        float r = 0.f, rd = 0.f;
+        if constexpr (RUN) {
+            const PsRun<ORDER> run = *reinterpret_cast<const PsRun<ORDER>*>(row + j0);
+#pragma unroll
+            for (int c = 0; c < ORDER; ++c) { r = fmaf(wy[c], run.v[c], r); rd = fmaf(dwy[c], run.v[c], rd); }
+        } else {
+#pragma unroll
+            for (int c = 0; c < ORDER; ++c) {
+                const float v = row[(j0 + c) & (ny - 1)];
+                r = fmaf(wy[c], v, r);
+                rd = fmaf(dwy[c], v, rd);
+            }
+        }
+        gx = fmaf(dwx[a], r, gx);
+        gy = fmaf(wx[a], rd, gy);
+    }
+}
+
+// grad[b][p][f] = (d/dx, d/dy) of the spline of coefficient image f at pos[b][p]: the sums in float32, the division by h in float64
+template <int ORDER>
+__global__ __launch_bounds__(kPT) void ps_particle_sample_grad_kernel(const float* __restrict__ coef, const double* __restrict__ pos,
+                                                                      float* __restrict__ grad, int nfields, PsBox g) {
+    const long total = (long)g.batch * g.npart;
+    const long q = blockIdx.x * (long)kPT + threadIdx.x;
+    if (q >= total) return;
+    const long b = q / g.npart;
+    float wx[ORDER], wy[ORDER], dwx[ORDER], dwy[ORDER];
+    const int i0 = ps_locate_grad<ORDER>(pos[2 * q], g.hx, g.nx, wx, dwx), j0 = ps_locate_grad<ORDER>(pos[2 * q + 1], g.hy, g.ny, wy, dwy);
+    const size_t image = (size_t)g.nx * g.ny;
+    for (int f = 0; f < nfields; ++f) {
+        const float* C = coef + ((size_t)f * g.batch + b) * image;
+        float gx, gy;
+        if (j0 + ORDER <= g.ny) ps_spline_grad<ORDER, true>(C, i0, j0, g.nx, g.ny, wx, wy, dwx, dwy, gx, gy);
+        else ps_spline_grad<ORDER, false>(C, i0, j0, g.nx, g.ny, wx, wy, dwx, dwy, gx, gy);
+        reinterpret_cast<float2*>(grad)[q * nfields + f] = make_float2((float)((double)gx / g.hx), (float)((double)gy / g.hy));
+    }
+}
+
+// Staging pass of the spread: slot s of the sorted order holds particle perm[s] (an index into [batch][npart]); its record is the forward's
+// weights and its cotangents, the unused ones zero.  A perm entry outside [0, batch npart) gives a record of zeros: nothing is read for it.
+template <int ORDER>
+__global__ __launch_bounds__(kPT) void ps_particle_spread_stage_kernel(const float* __restrict__ cot, const double* __restrict__ pos,
+                                                                       const long long* __restrict__ perm, float* __restrict__ rec,
+                                                                       int nfields, PsBox g) {
+    const long total = (long)g.batch * g.npart;
+    const long s = blockIdx.x * (long)kPT + threadIdx.x;
+    if (s >= total) return;
+    const long long p = perm[s];
+    float w[2 * ORDER + 4];
+#pragma unroll
+    for (int k = 0; k < 2 * ORDER + 4; ++k) w[k] = 0.f;
+    if (p >= 0 && p < total) {
+        float wx[ORDER], wy[ORDER];
+        ps_locate<ORDER>(pos[2 * p], g.hx, g.nx, wx);
+        ps_locate<ORDER>(pos[2 * p + 1], g.hy, g.ny, wy);
+#pragma unroll
+        for (int k = 0; k < ORDER; ++k) { w[k] = wx[k]; w[ORDER + k] = wy[k]; }
+#pragma unroll
+        for (int f = 0; f < 4; ++f)
+            if (f < nfields) w[2 * ORDER + f] = cot[p * nfields + f];
+    }
+    float4* o = reinterpret_cast<float4*>(rec + (size_t)s * kRec<ORDER>);
+#pragma unroll
+    for (int k = 0; k < kRec<ORDER> / 4; ++k) o[k] = make_float4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+}
+
+// Node pass of the spread: cbar[f][b][i][j] <- the sum over the particles whose stencil covers the node.  start is clamped to the slots
+// that exist, so a wrong table reads no record outside the workspace.
+template <int ORDER, int NF>
+__global__ __launch_bounds__(kPT) void ps_particle_spread_node_kernel(const float* __restrict__ rec, const int* __restrict__ start,
+                                                                      float* __restrict__ cbar, PsBox g) {
+    const long nodes = (long)g.batch * g.nx * g.ny, total = (long)g.batch * g.npart;
+    const long q = blockIdx.x * (long)kPT + threadIdx.x;
+    if (q >= nodes) return;
+    const int j = (int)(q & (g.ny - 1)), i = (int)((q / g.ny) & (g.nx - 1));
+    const long row0 = (q / g.ny - i);                      // b nx
+    double acc[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) acc[f] = 0.0;
+    for (int a = 0; a < ORDER; ++a) {
+        const long crow = (row0 + ((i - a + ORDER / 2 - 1) & (g.nx - 1))) * g.ny;
+        for (int c = 0; c < ORDER; ++c) {
+            const long cell = crow + ((j - c + ORDER / 2 - 1) & (g.ny - 1));
+            long s0 = start[cell], s1 = start[cell + 1];
+            s0 = s0 < 0 ? 0 : s0;
+            s1 = s1 > total ? total : s1;
+            for (long s = s0; s < s1; ++s) {
+                const float* r = rec + (size_t)s * kRec<ORDER>;
+                const float w = r[a] * r[ORDER + c];
+                const float4 ct = *reinterpret_cast<const float4*>(r + 2 * ORDER);
+                const float cv[4] = {ct.x, ct.y, ct.z, ct.w};
+#pragma unroll
+                for (int f = 0; f < NF; ++f) acc[f] = fma((double)w, (double)cv[f], acc[f]);
+            }
+        }
+    }
+#pragma unroll
+    for (int f = 0; f < NF; ++f) cbar[(size_t)f * nodes + q] = (float)acc[f];
+}
+
+// The transpose of ps_particle_spectra_kernel between physical fields: ch [nfields][batch][nx][nh] = rfft2 of the cotangent images (by
+// ascending bit of the mask) -> the compact spectra Wb (and Tb with bit 3), [batch][my1][nx].  The map is real, so its transpose takes the
+// conjugate multipliers: u^ = i ky w^ / |k|^2 gives -i ky c_u^ / |k|^2, v^ = -i kx w^ / |k|^2 gives i kx c_v^ / |k|^2; the forward's inverse
+// transform carries 1 / (nx ny) and the unnormalised forward transform here takes its place, so no factor is left.  Zero outside
+// 3 |mx| < nx, as the state's own compaction; (0, 0) of Wb zero (init_vorticity zeroes it), of Tb kept.
+__global__ void ps_particle_spectra_adjoint_kernel(const float2* __restrict__ ch, float2* __restrict__ Wb, float2* __restrict__ Tb, int mask,
+                                                   int order, int batch, int nx, int ny, int my1, float kx1, float ky1) {
+    const long total = (long)batch * my1 * nx, nh = ny / 2 + 1, per = (long)batch * nx * nh;
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+        const int i = (int)(q % nx), j = (int)((q / nx) % my1);
+        const long b = q / ((long)nx * my1);
+        const int mx = i < nx / 2 ? i : i - nx;
+        cf w = {0.f, 0.f}, th = w;
+        if (3 * (mx < 0 ? -mx : mx) < nx) {
+            const size_t at = ((size_t)b * nx + i) * nh + j;
+            cf c[4] = {w, w, w, w};
+            int slot = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (mask & (1 << k)) { const float2 v = ch[slot * per + at]; c[k] = {v.x, v.y}; ++slot; }
+            const float r = (float)(1.0 / (ps_beta(order, mx, nx) * ps_beta(order, j, ny)));
+            const float kx = kx1 * (float)mx, ky = ky1 * (float)j, k2 = kx * kx + ky * ky;
+            if (k2 > 0.f) {
+                const cf psi = imul(-ky, c[0]), phi = imul(kx, c[1]);
+                w = {((psi.x + phi.x) / k2 + c[2].x) * r, ((psi.y + phi.y) / k2 + c[2].y) * r};
+            }
+            th = {c[3].x * r, c[3].y * r};
+        }
+        if (mask & 7) Wb[q] = make_float2(w.x, w.y);
+        if (mask & 8) Tb[q] = make_float2(th.x, th.y);
+    }
+}
+
+template <int ORDER>
+void launch_spread_node(int nfields, dim3 grid, hipStream_t s, const float* rec, const int* start, float* cbar, const PsBox& g) {
+    switch (nfields) {
+        case 1: hipLaunchKernelGGL((ps_particle_spread_node_kernel<ORDER, 1>), grid, dim3(kPT), 0, s, rec, start, cbar, g); break;
+        case 2: hipLaunchKernelGGL((ps_particle_spread_node_kernel<ORDER, 2>), grid, dim3(kPT), 0, s, rec, start, cbar, g); break;
+        case 3: hipLaunchKernelGGL((ps_particle_spread_node_kernel<ORDER, 3>), grid, dim3(kPT), 0, s, rec, start, cbar, g); break;
+        default: hipLaunchKernelGGL((ps_particle_spread_node_kernel<ORDER, 4>), grid, dim3(kPT), 0, s, rec, start, cbar, g); break;
+    }
+}
+
+size_t spread_work_bytes(int batch, long npart, int order) { return (size_t)batch * npart * (2 * order + 4) * sizeof(float); }
+
+}  // namespace
+
+NNS_API int nns_spec_ns_particle_cells_i32(const double* pos, int* key, int batch, long npart, int nx, int ny, double Lx, double Ly,
+                                           void* stream) {
+    const char* who = "spec_ns_particle_cells";
+    if (!pos || !key || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
+    if (int rc = check_particles(who, batch, npart)) return rc;
+    if (int rc = check_particle_box(who, nx, ny, Lx, Ly)) return rc;
+    if ((long)batch * nx * ny >= (1L << 31))
+        return fail(NNS_ERR_UNSUPPORTED, "%s: batch nx ny = %ld cells must be < 2^31 (the keys are int32)", who, (long)batch * nx * ny);
+    const PsBox g{batch, (int)npart, nx, ny, Lx / nx, Ly / ny};
+    const dim3 grid((unsigned)(((long)batch * npart + kPT - 1) / kPT));
+    hipLaunchKernelGGL(ps_particle_cells_kernel, grid, dim3(kPT), 0, as_stream(stream), pos, key, g);
+    return check_launch(who);
+}
+
+NNS_API int nns_spec_ns_particle_spread_workspace(int batch, long npart, int order, size_t* bytes) {
+    const char* who = "spec_ns_particle_spread_workspace";
+    if (!bytes || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: bytes must be non-NULL and batch >= 1 (batch = %d)", who, batch);
+    if (int rc = check_particles(who, batch, npart)) return rc;
+    if (int rc = check_order(who, order)) return rc;
+    *bytes = spread_work_bytes(batch, npart, order);
+    return NNS_OK;
+}
+
+NNS_API int nns_spec_ns_particle_spread_f32(const float* cot, const double* pos, const long long* perm, const int* start, float* cbar,
+                                            int nfields, int order, void* work, size_t work_bytes_, int batch, long npart, int nx, int ny,
+                                            double Lx, double Ly, void* stream) {
+    const char* who = "spec_ns_particle_spread";
+    if (!cot || !pos || !perm || !start || !cbar || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
+    if (int rc = check_particles(who, batch, npart)) return rc;
+    if (int rc = check_order(who, order)) return rc;
+    if (nfields < 1 || nfields > 4) return fail(NNS_ERR_INVALID_ARG, "%s: nfields = %d must be in [1, 4]", who, nfields);
+    if (int rc = check_particle_box(who, nx, ny, Lx, Ly)) return rc;
+    if ((long)batch * nx * ny >= (1L << 31))
+        return fail(NNS_ERR_UNSUPPORTED, "%s: batch nx ny = %ld cells must be < 2^31", who, (long)batch * nx * ny);
+    const size_t need = spread_work_bytes(batch, npart, order);
+    if (work_bytes_ < need)
+        return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, nns_spec_ns_particle_spread_workspace asks for %zu", who, work_bytes_, need);
+    const PsBox g{batch, (int)npart, nx, ny, Lx / nx, Ly / ny};
+    hipStream_t s = as_stream(stream);
+    float* rec = static_cast<float*>(work);
+    const dim3 slots((unsigned)(((long)batch * npart + kPT - 1) / kPT)), nodes((unsigned)(((long)batch * nx * ny + kPT - 1) / kPT));
+    if (order == 4) hipLaunchKernelGGL(ps_particle_spread_stage_kernel<4>, slots, dim3(kPT), 0, s, cot, pos, perm, rec, nfields, g);
+    else hipLaunchKernelGGL(ps_particle_spread_stage_kernel<6>, slots, dim3(kPT), 0, s, cot, pos, perm, rec, nfields, g);
+    if (int rc = check_launch(who)) return rc;
+    if (order == 4) launch_spread_node<4>(nfields, nodes, s, rec, start, cbar, g);
+    else launch_spread_node<6>(nfields, nodes, s, rec, start, cbar, g);
+    return check_launch(who);
+}
+
+NNS_API int nns_spec_ns_particle_sample_grad_f32(const float* coef, const double* pos, float* grad, int nfields, int order, int batch,
+                                                 long npart, int nx, int ny, double Lx, double Ly, void* stream) {
+    const char* who = "spec_ns_particle_sample_grad";
+    if (!coef || !pos || !grad || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
+    if (int rc = check_particles(who, batch, npart)) return rc;
+    if (int rc = check_order(who, order)) return rc;
+    if (nfields < 1 || nfields > 4) return fail(NNS_ERR_INVALID_ARG, "%s: nfields = %d must be in [1, 4]", who, nfields);
+    if (int rc = check_particle_box(who, nx, ny, Lx, Ly)) return rc;
+    const PsBox g{batch, (int)npart, nx, ny, Lx / nx, Ly / ny};
+    const dim3 grid((unsigned)(((long)batch * npart + kPT - 1) / kPT));
+    if (order == 4) hipLaunchKernelGGL(ps_particle_sample_grad_kernel<4>, grid, dim3(kPT), 0, as_stream(stream), coef, pos, grad, nfields, g);
+    else hipLaunchKernelGGL(ps_particle_sample_grad_kernel<6>, grid, dim3(kPT), 0, as_stream(stream), coef, pos, grad, nfields, g);
+    return check_launch(who);
+}
+
+NNS_API int nns_spec_ns_particle_coefs_adjoint_f32(const float* cbar, float* wbar_hat, float* thbar_hat, int fields, int order, void* work,
+                                                   size_t work_bytes_, int batch, int nx, int ny, double Lx, double Ly, void* stream) {
+    const char* who = "spec_ns_particle_coefs_adjoint";
+    if (!cbar || !work || batch < 1) return fail(NNS_ERR_INVALID_ARG, "%s: NULL pointer or batch < 1", who);
+    if (int rc = check_order(who, order)) return rc;
+    if (fields < 1 || fields > 15) return fail(NNS_ERR_INVALID_ARG, "%s: fields = %d must be a non-empty mask of bits 0 u, 1 v, 2 w, 3 theta", who, fields);
+    if ((fields & 7) && !wbar_hat) return fail(NNS_ERR_INVALID_ARG, "%s: the field mask names u, v or w and wbar_hat is NULL", who);
+    if ((fields & 8) && !thbar_hat) return fail(NNS_ERR_INVALID_ARG, "%s: the field mask asks for theta (bit 3) and thbar_hat is NULL", who);
+    if (int rc = check_particle_box(who, nx, ny, Lx, Ly)) return rc;
+    const int nfields = popcount4(fields);
+    const size_t need = particle_work_bytes(batch, nfields, nx, ny);
+    if (work_bytes_ < need)
+        return fail(NNS_ERR_WORKSPACE, "%s: workspace of %zu bytes, nns_spec_ns_particle_workspace asks for %zu", who, work_bytes_, need);
+    if (int rc = nns_spec_rfft2_f32(cbar, static_cast<float*>(work), nfields * batch, nx, ny, stream)) return rc;
+    const int my1 = kept_y(ny);
+    hipLaunchKernelGGL(ps_particle_spectra_adjoint_kernel, dim3(pw_grid((long)batch * my1 * nx)), dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const float2*>(work), reinterpret_cast<float2*>(wbar_hat), reinterpret_cast<float2*>(thbar_hat), fields,
+                       order, batch, nx, ny, my1, (float)(2.0 * M_PI / Lx), (float)(2.0 * M_PI / Ly));
+    return check_launch(who);
+}

@@ -118,6 +118,11 @@ _SINGLE = {
     'nns_spec_ns_particle_coefs_f32': [_P] * 4 + [_I, _I, _P, _SZ] + [_I] * 3 + [_D, _D, _P],
     'nns_spec_ns_particle_sample_f32': [_P] * 3 + [_I] * 3 + [_L, _I, _I, _D, _D, _P],
     'nns_spec_ns_particle_stage_f32': [_P] * 5 + [_D] * 3 + [_I] * 4 + [_L, _I, _I, _D, _D, _P],
+    'nns_spec_ns_particle_cells_i32': [_P, _P, _I, _L, _I, _I, _D, _D, _P],
+    'nns_spec_ns_particle_spread_workspace': [_I, _L, _I, C.POINTER(C.c_size_t)],
+    'nns_spec_ns_particle_spread_f32': [_P] * 5 + [_I, _I, _P, _SZ, _I, _L, _I, _I, _D, _D, _P],
+    'nns_spec_ns_particle_sample_grad_f32': [_P] * 3 + [_I] * 3 + [_L, _I, _I, _D, _D, _P],
+    'nns_spec_ns_particle_coefs_adjoint_f32': [_P] * 3 + [_I, _I, _P, _SZ] + [_I] * 3 + [_D, _D, _P],
     'nns_pixel_mlp_fwd_f32': [_P] * 4 + [_I, _I, C.POINTER(C.c_int), _I, _I, _P],
     'nns_pixel_mlp_bwd_workspace': [C.POINTER(C.c_int), _I, C.POINTER(C.c_size_t)],
     'nns_pixel_mlp_bwd_f32': [_P] * 7 + [_I, _I, C.POINTER(C.c_int), _I, _I, _P, C.c_size_t, _P],

@@ -1678,3 +1678,91 @@ def spec_ns_particle_stage_(coef, pos0, pos_in, pos_out, acc, a, wk, c, first, c
                                                     int(bool(first)), int(bool(closing)), int(order), B, shape[1], nx, ny, float(Lx), float(Ly),
                                                     _stream()), 'nns_spec_ns_particle_stage_f32')
     return pos_out
+
+
+# reverse mode of the sampling (nns_spec_ns_particle_cells_i32, _spread_f32, _sample_grad_f32, _coefs_adjoint_f32)
+def _spec_ns_particle_pos(who, pos, B, device):
+    """P of the checked positions, float64 [B, P, 2]."""
+    if not (isinstance(pos, torch.Tensor) and pos.dim() == 3):
+        raise ValueError("%s: pos must be float64 [B, P, 2]" % who)
+    _spec_ns_f64(who, 'pos', pos, (B, pos.shape[1], 2), device)
+    return pos.shape[1]
+
+
+def spec_ns_particle_cells(pos, nx, ny, Lx, Ly):
+    """(perm, start) of the positions pos (float64 [B, P, 2]) on B grids of nx x ny: perm, int64 [B P], the particle (an index into [B, P])
+    of every slot of the order sorted by cell (b nx + ci) ny + cj, the particles of one cell in ascending index; start, int32
+    [B nx ny + 1], the first slot of every cell, then B P.  One launch, then torch.sort(stable=True) and torch.searchsorted on the device:
+    no host synchronisation."""
+    who = 'spec_ns_particle_cells'
+    B = pos.shape[0] if isinstance(pos, torch.Tensor) and pos.dim() == 3 else None
+    P = _spec_ns_particle_pos(who, pos, B, getattr(pos, 'device', None))
+    key = torch.empty(B * P, dtype=torch.int32, device=pos.device)
+    check(_lib.lib().nns_spec_ns_particle_cells_i32(_p(pos), _p(key), B, P, int(nx), int(ny), float(Lx), float(Ly), _stream()),
+          'nns_spec_ns_particle_cells_i32')
+    key, perm = torch.sort(key, stable=True)
+    cells = torch.arange(B * int(nx) * int(ny) + 1, dtype=torch.int32, device=pos.device)
+    return perm, torch.searchsorted(key, cells, out_int32=True)
+
+
+def spec_ns_particle_spread_workspace(B, P, order):
+    """Bytes of the workspace spec_ns_particle_spread needs: one record of 2 order + 4 floats per particle."""
+    return _query_bytes('nns_spec_ns_particle_spread_workspace', int(B), int(P), int(order))
+
+
+def spec_ns_particle_spread(cot, pos, perm, start, nx, ny, order, Lx, Ly, out=None, work=None):
+    """float32 [nfields, B, nx, ny]: the transpose of spec_ns_particle_sample applied to cot (float32 [B, P, nfields]); (perm, start) from
+    spec_ns_particle_cells of pos.  Two launches, no atomics: repeats bitwise; every node is written."""
+    who = 'spec_ns_particle_spread'
+    _f32(cot)
+    if cot.dim() != 3 or not 1 <= cot.shape[2] <= 4:
+        raise ValueError("%s: cot must be float32 [B, P, nfields] with nfields in [1, 4], got %s" % (who, tuple(cot.shape)))
+    B, P, nf = cot.shape
+    nx, ny = int(nx), int(ny)
+    if _spec_ns_particle_pos(who, pos, B, cot.device) != P:
+        raise ValueError("%s: pos is for %d particles, cot for %d" % (who, pos.shape[1], P))
+    for name, t, dtype, n in (('perm', perm, torch.int64, B * P), ('start', start, torch.int32, B * nx * ny + 1)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and t.device == cot.device and tuple(t.shape) == (n,)):
+            raise ValueError("%s: %s must be a contiguous %s tensor [%d] on %s (from spec_ns_particle_cells)" % (who, name, dtype, n, cot.device))
+    if out is None:
+        out = torch.empty((nf, B, nx, ny), dtype=torch.float32, device=cot.device)
+    else:
+        _spec_ns_f32(who, 'out', out, (nf, B, nx, ny), cot.device)
+    if work is None:
+        work = torch.empty(spec_ns_particle_spread_workspace(B, P, order), dtype=torch.uint8, device=cot.device)
+    check(_lib.lib().nns_spec_ns_particle_spread_f32(_p(cot), _p(pos), _p(perm), _p(start), _p(out), nf, int(order), _p(work), work.numel(), B, P,
+                                                     nx, ny, float(Lx), float(Ly), _stream()), 'nns_spec_ns_particle_spread_f32')
+    return out
+
+
+def spec_ns_particle_sample_grad(coef, pos, order, Lx, Ly, out=None):
+    """float32 [B, P, nfields, 2]: (d/dx, d/dy) of the splines of the coefficient images coef [nfields, B, nx, ny] at pos (float64 [B, P, 2])."""
+    who = 'spec_ns_particle_sample_grad'
+    nf, B, nx, ny = _spec_ns_particle_coef(who, coef)
+    P = _spec_ns_particle_pos(who, pos, B, coef.device)
+    if out is None:
+        out = torch.empty((B, P, nf, 2), dtype=torch.float32, device=coef.device)
+    else:
+        _spec_ns_f32(who, 'out', out, (B, P, nf, 2), coef.device)
+    check(_lib.lib().nns_spec_ns_particle_sample_grad_f32(_p(coef), _p(pos), _p(out), nf, int(order), B, P, nx, ny, float(Lx), float(Ly),
+                                                          _stream()), 'nns_spec_ns_particle_sample_grad_f32')
+    return out
+
+
+def spec_ns_particle_coefs_adjoint(cbar, fields, order, Lx, Ly, work=None):
+    """(wbar_hat, thbar_hat), float32 [B, my1, nx, 2] each (None where the mask `fields` has none of bits 0-2 / no bit 3): the transpose of
+    spec_ns_particle_coefs applied to the cotangents cbar (float32 [nfields, B, nx, ny], by ascending bit).  work:
+    spec_ns_particle_workspace bytes.  One forward transform and one pointwise launch."""
+    who = 'spec_ns_particle_coefs_adjoint'
+    nf, B, nx, ny = _spec_ns_particle_coef(who, cbar)
+    fields = int(fields)
+    if nf != bin(fields & 15).count('1'):
+        raise ValueError("%s: cbar holds %d images, the mask %d names %d" % (who, nf, fields, bin(fields & 15).count('1')))
+    shape = (B, spec_ns_kept_y(ny), nx, 2)
+    wbar = torch.empty(shape, dtype=torch.float32, device=cbar.device) if fields & 7 else None
+    thbar = torch.empty(shape, dtype=torch.float32, device=cbar.device) if fields & 8 else None
+    if work is None:
+        work = torch.empty(spec_ns_particle_workspace(B, nf, nx, ny), dtype=torch.uint8, device=cbar.device)
+    check(_lib.lib().nns_spec_ns_particle_coefs_adjoint_f32(_p(cbar), _pn(wbar), _pn(thbar), fields, int(order), _p(work), work.numel(), B, nx, ny,
+                                                            float(Lx), float(Ly), _stream()), 'nns_spec_ns_particle_coefs_adjoint_f32')
+    return wbar, thbar
